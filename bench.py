@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — the reference's headline workload on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu] [--no-extra] [--no-full]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu] [--no-extra] [--no-full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ... [--workload c5]
 
 Workload (BASELINE.json configs[1]): tx90p = percentile_doy(window 5, per 90) + threshold_count(">", per-doy fp64
@@ -143,6 +143,52 @@ def chain_event_times(dev, fns, reps):
     return [t / reps for t in tot]
 
 
+DUMP_BUDGET = 60 * 10**6  # bytes of array data written by --dump-outputs (at most 64 MB in all, .npy headers included)
+DUMP_SEED = 20240925
+DUMP_RUN = 64  # sampled cells come in runs of 64 neighbours: one strided copy per run and output
+
+
+def dump_outputs(dev, outdir, outputs, budget=DUMP_BUDGET):
+    """--dump-outputs DIR: write what the last timed step computed, ``outputs`` = {name: device array whose LAST axis is the
+    cell axis}, as DIR/<name>.npy in the array's own dtype (float32 / float64).  Outputs of up to a quarter of the budget are
+    written whole while they fit in half of it; the others share ONE fixed, seeded sample of cells (runs of DUMP_RUN
+    neighbours; the same cells in each of them and from run to run for the same arguments), sized to the rest of the budget
+    and copied out of the device array column block by column block, shape (..., sampled cells)."""
+    os.makedirs(outdir, exist_ok=True)
+    whole, used = [], 0
+    for name, a in sorted(outputs.items(), key=lambda kv: kv[1].nbytes):
+        if a.nbytes <= budget // 4 and used + a.nbytes <= budget // 2:
+            whole.append(name)
+            used += a.nbytes
+    rest = {n: a for n, a in outputs.items() if n not in whole}
+    starts, run, ncell = [], 0, 0
+    if rest:
+        C = {a.shape[-1] for a in rest.values()}
+        assert len(C) == 1, "the sampled outputs must share their cell axis"
+        C = C.pop()
+        per_cell = sum(a.nbytes // C for a in rest.values())
+        ncell = min(C, (budget - used) // per_cell)
+        if ncell < 1:
+            sys.exit(f"bench: --dump-outputs cannot hold one cell of {sorted(rest)} in {budget - used} bytes")
+        run = min(DUMP_RUN, ncell)
+        ncell = ncell // run * run
+        starts = np.sort(np.random.default_rng(DUMP_SEED).choice(C // run, ncell // run, replace=False)) * run
+    for name, a in outputs.items():
+        if name in whole:
+            host = a.get()
+        else:
+            C, it = a.shape[-1], a.dtype.itemsize
+            rows = a.size // C
+            host = np.empty((rows, ncell), a.dtype)
+            for j, c0 in enumerate(starts):  # rows x run cells at columns c0.. of the (rows, C) array -> columns j*run.. of host
+                dev.copy2d(host.ctypes.data + j * run * it, ncell * it, a.ptr + int(c0) * it, C * it, run * it, rows, "d2h")
+            host = host.reshape(a.shape[:-1] + (ncell,))
+        assert host.dtype in (np.float32, np.float64), (name, host.dtype)
+        np.save(os.path.join(outdir, name + ".npy"), host)
+    sys.stderr.write(f"[bench] --dump-outputs {outdir}: {', '.join(sorted(outputs))}"
+                     + (f" ({', '.join(sorted(rest))}: {ncell} of {C} cells, seed {DUMP_SEED})" if rest else "") + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -157,7 +203,12 @@ def main():
     ap.add_argument("--no-extra", action="store_true")
     ap.add_argument("--no-full", action="store_true", help="skip the 3650-step / 30-year extras (they allocate up to 182 GB)")
     ap.add_argument("--no-long", action="store_true", help="skip the 55 152-step extras (PMC passes: per-kernel means must not mix sizes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last one as DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB in all: a fixed, seeded sample of cells of the larger ones)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -257,6 +308,8 @@ def main():
         if not np.array_equal(mine, res_bufs[lastb].get(), equal_nan=True):
             sys.exit("bench: the all-gathered field does not hold this rank's result")
         dt = float(comm.allreduce([dt], "max")[0])
+    if args.dump_outputs and rank == 0:  # the masked counts (the all-gathered field with N > 1), this rank's percentile table
+        dump_outputs(dev, args.dump_outputs, {"tx90p": gathered[(nstep[0] - 1) % 2] if use_dist else res, "percentile_doy": per})
     units_step = float(T) * C * world
     value = units_step * args.steps / dt
 
@@ -389,6 +442,8 @@ def bench_config5(args, dev, K, comm, world, rank):
         if not np.array_equal(mine, send.get()):
             sys.exit("bench: the all-gathered field does not hold this rank's result")
         dt = float(comm.allreduce([dt], "max")[0])
+    if args.dump_outputs and rank == 0:  # (this rank's slab)
+        dump_outputs(dev, args.dump_outputs, {"tx90p": res, "percentile_doy": per, "eqm_af": af, "eqm_hist_q": hq, "scen": scen})
     E = float(T) * C
     bytes_step = (2 * (4 * E + 8 * D * C) + 8 * P * C) + 16 * E  # tx90p unfused + EQM train + adjust
     if rank == 0:

@@ -19,7 +19,7 @@ The result — tests/golden/call_programs.json — holds, per index, its paramet
 signature, the scenario (the scalar arguments of the recorded run), and the operation list with symbolic references
 (parameters, earlier results, module globals by NAME).  tests/callprog.py replays a program inside a stand-in module's
 namespace, so the by-name resolution rules of ``patch.install`` are exercised with the reference's own call sequences.
-tests/test_host_cpu.py re-records the programs when /root/reference is present and compares them with the committed file.
+``python tests/golden/make_call_programs.py --check`` re-records the programs and compares them with the committed file.
 """
 
 import ast
@@ -339,6 +339,13 @@ def main():
     if not os.path.isdir(REF):
         sys.exit("reference tree not present; call programs can only be recorded in the build container")
     progs = build()
+    if "--check" in sys.argv[1:]:
+        with open(os.path.join(HERE, "call_programs.json")) as f:
+            stored = json.load(f)
+        if json.loads(json.dumps(progs, sort_keys=True)) != stored:
+            sys.exit("tests/golden/call_programs.json differs from a fresh recording: regenerate it")
+        print(f"call_programs.json: {len(stored)} programs, as recorded")
+        return
     with open(os.path.join(HERE, "call_programs.json"), "w") as f:
         json.dump(progs, f, indent=1, sort_keys=True)
     for k, p in progs.items():

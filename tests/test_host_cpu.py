@@ -219,6 +219,60 @@ def test_bench_finds_pmc_traffic_of_the_dominant_kernel():
     assert bench.pmc_traffic("k_pdoy_slide<5, 4>", (365, 10, 10)) == (None, None)
 
 
+def test_bench_dump_outputs_writes_whole_columns_of_a_seeded_cell_sample(tmp_path):
+    """bench.dump_outputs on a host-memory device (tools/mock_device.py): an output within the budget is written whole; the
+    others hold whole columns (all rows of a cell) of the same, distinct, ascending cells; the files stay within the budget
+    and are the same from call to call."""
+    import importlib.util
+
+    from tools.mock_device import MockDevice
+
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    dev = MockDevice(0)
+    C = 5000
+    small = np.arange(2 * C, dtype=np.float64).reshape(2, C)
+    big = (np.arange(3 * 7, dtype=np.float32)[:, None] * C + np.arange(C, dtype=np.float32)).reshape(3, 7, C)  # value = row * C + cell
+    outs = {"small": dev.to_device(small), "big": dev.to_device(big), "big64": dev.to_device(big.astype(np.float64))}
+    budget = 400_000
+    for d in ("a", "b"):
+        bench.dump_outputs(dev, str(tmp_path / d), outs, budget=budget)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "small.npy"), small)
+    got, got64 = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "a" / "big64.npy")
+    assert got.dtype == np.float32 and got64.dtype == np.float64 and got.shape[:2] == (3, 7) and got64.shape == got.shape
+    n = got.shape[-1]
+    cells = got[0, 0].astype(np.int64)
+    assert 0 < n < C and (np.diff(cells) > 0).all() and cells[-1] < C
+    np.testing.assert_array_equal(got, big[..., cells])
+    np.testing.assert_array_equal(got64, big.astype(np.float64)[..., cells])
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= budget + 3 * 256   # (.npy headers)
+    for name in outs:
+        assert (tmp_path / "a" / f"{name}.npy").read_bytes() == (tmp_path / "b" / f"{name}.npy").read_bytes()
+
+
+def test_bench_steps_and_dump_outputs_through_the_command_line(tmp_path):
+    """``bench.py --steps K --dump-outputs DIR`` on the host-memory mock device (no-op kernels: the numbers mean nothing): the
+    result line carries K and ms_per_step, DIR holds the outputs of the flagship path in float32 / float64."""
+    import json
+    import subprocess
+
+    env = dict(os.environ, XH_BENCH_MOCK_DEVICE="1")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--grid", "365x4x8",
+           "--no-cpu", "--no-extra", "--dump-outputs", str(tmp_path / "out")]
+    res = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
+    lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, res.stdout
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 7 and rec["warmup"] == 2 and rec["ms_per_step"] > 0 and rec["data"].startswith("mock")
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == ["percentile_doy.npy", "tx90p.npy"]
+    assert np.load(tmp_path / "out" / "tx90p.npy").shape == (1, 32) and np.load(tmp_path / "out" / "percentile_doy.npy").shape == (1, 365, 32)
+    assert cmd[4:6] == ["--steps", "7"]
+    bad = subprocess.run(cmd[:5] + ["0"] + cmd[6:], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    assert bad.returncode != 0 and "--steps must be at least 1" in bad.stderr
+
+
 def test_dim_other_than_time_is_refused():
     """The host mirrors keep the reference's `dim` argument: "time" = axis 0, or (round 6) an INTEGER axis of the plain array;
     a dimension NAME other than "time" means nothing for an array without names and must fail loudly (before any device
@@ -302,16 +356,15 @@ def test_weekly_frequency_needs_weekdays():
 
 def test_adapter_wrappers_have_the_reference_signatures():
     """Every DataArray-level wrapper of xr_adapter.py takes exactly the parameters of the reference function it replaces
-    (names, order, keyword-only and variadic parts) — read from the reference sources with ast; skipped where the reference
-    tree is not present (the GPU box)."""
-    import ast
+    (names, order, keyword-only and variadic parts) — as read from the reference sources with ast into
+    tests/golden/reference_signatures.json (tests/golden/make_reference_shapes.py)."""
     import inspect
+    import json
     import os
     import sys
 
-    root = "/root/reference/src/xclim"
-    if not os.path.isdir(root):
-        pytest.skip("reference tree not present")
+    with open(os.path.join(os.path.dirname(__file__), "golden", "reference_signatures.json")) as f:
+        sigs = json.load(f)
     sys.path.insert(0, os.path.join(os.path.dirname(__file__)))
     import fakexr
     from xclim_amd.xr_adapter import make_wrappers
@@ -327,12 +380,9 @@ def test_adapter_wrappers_have_the_reference_signatures():
     P = inspect.Parameter
     checked = 0
     for rel, names in where.items():
-        tree = ast.parse(open(os.path.join(root, rel)).read())
-        defs = {n.name: n.args for n in tree.body if isinstance(n, ast.FunctionDef)}
         for name in names:
-            a = defs[name]
-            ref = ([x.arg for x in a.posonlyargs + a.args], [x.arg for x in a.kwonlyargs], a.vararg.arg if a.vararg else None,
-                   a.kwarg.arg if a.kwarg else None)
+            a = sigs[rel][name]
+            ref = (a["args"], a["kwonly"], a["vararg"], a["kwarg"])
             sig = inspect.signature(wrappers[name])  # (follows __wrapped__ to the wrapper's own function)
             ps = list(sig.parameters.values())
             ours = ([p.name for p in ps if p.kind in (P.POSITIONAL_ONLY, P.POSITIONAL_OR_KEYWORD)],
@@ -344,23 +394,6 @@ def test_adapter_wrappers_have_the_reference_signatures():
     assert checked == 22
 
 
-def test_call_programs_are_what_the_reference_bodies_do():
-    """tests/golden/call_programs.json (replayed by the adapter tests on the GPU box) equals a fresh recording from the
-    reference's index bodies (AST-extracted and executed with symbolic arguments, tests/golden/make_call_programs.py)."""
-    import json
-
-    if not os.path.isdir("/root/reference/src/xclim"):
-        pytest.skip("the reference tree only exists in the build container")
-    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
-    import make_call_programs as mcp
-
-    fresh = json.loads(json.dumps(mcp.build(), sort_keys=True))
-    with open(os.path.join(os.path.dirname(__file__), "golden", "call_programs.json")) as f:
-        stored = json.load(f)
-    assert fresh == stored
-    assert len(stored) >= 25 and all(p["source"].startswith("src/xclim/indices/") for p in stored.values())
-
-
 def _shape_key(name, npos, kws):
     return f"{name}({npos}; {', '.join(sorted(k for k in kws if k != '**'))})" + (" + **indexer" if "**" in kws else "")
 
@@ -368,34 +401,24 @@ def _shape_key(name, npos, kws):
 def test_every_call_shape_of_a_replaced_function_is_recorded():
     """which distinct (function, positional count, keyword set) shapes do the reference's index modules use
     when they call a function ``patch.install`` replaces — and is each one exercised by a recorded call program (replayed
-    through the wrappers on the GPU box, tests/test_gpu_adapter.py) or explicitly listed as forwarded?  Walks
-    /root/reference/src/xclim/indices/{_threshold,_multivariate,_simple}.py with ``ast`` (128 call sites, 19 shapes)."""
-    import ast
+    through the wrappers on the GPU box, tests/test_gpu_adapter.py) or explicitly listed as forwarded?  The call sites of
+    indices/{_threshold,_multivariate,_simple}.py were walked with ``ast`` into tests/golden/reference_call_sites.json
+    (tests/golden/make_reference_shapes.py; 128 call sites, 19 shapes)."""
     import json
 
     from xclim_amd.patch import _BY_NAME
 
-    ref = "/root/reference/src/xclim/indices"
-    if not os.path.isdir(ref):
-        pytest.skip("the reference tree only exists in the build container")
     generic, rlnames = set(_BY_NAME["xclim.indices._multivariate"]), set(_BY_NAME["xclim.indices.run_length"])
+    with open(os.path.join(os.path.dirname(__file__), "golden", "reference_call_sites.json")) as fh:
+        calls = json.load(fh)
     sites = {}
-    for f in ("_threshold.py", "_multivariate.py", "_simple.py"):
-        with open(os.path.join(ref, f)) as fh:
-            tree = ast.parse(fh.read())
-        for fn in (n for n in tree.body if isinstance(n, ast.FunctionDef)):
-            for node in (n for n in ast.walk(fn) if isinstance(n, ast.Call)):
-                name = None
-                if isinstance(node.func, ast.Name) and node.func.id in generic:
-                    name = node.func.id
-                elif (isinstance(node.func, ast.Attribute) and isinstance(node.func.value, ast.Name) and node.func.value.id == "rl"
-                      and node.func.attr in rlnames):
-                    name = "rl." + node.func.attr
-                if name:
-                    key = _shape_key(name, len(node.args), [k.arg or "**" for k in node.keywords])
-                    sites.setdefault(key.replace(" + **indexer", ""), []).append(f"{f}:{fn.name}:{node.lineno}")
+    for f, fn, lineno, name, npos, kws in calls:
+        if name in generic or (name.startswith("rl.") and name[3:] in rlnames):
+            key = _shape_key(name, npos, kws)
+            sites.setdefault(key.replace(" + **indexer", ""), []).append(f"{f}:{fn}:{lineno}")
     with open(os.path.join(os.path.dirname(__file__), "golden", "call_programs.json")) as fh:
         progs = json.load(fh)
+    assert len(progs) >= 25 and all(p["source"].startswith("src/xclim/indices/") for p in progs.values())
     recorded = {}
     for idx, prog in progs.items():
         vals = []

@@ -361,6 +361,38 @@ int xh_resample_reduce_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, i
 int xh_nan_quantile_f64(xh_ctx* ctx, const double* x, int64_t N, int64_t C, int64_t sn, int64_t sc, const double* q, int nq,
                         double alpha, double beta, double* out);
 
+/* float64 FIELD twins of the compare / run-length / spell / percentile_doy entry points (f64run.hip), same layouts, segment
+ * tables and outputs as their float32 twins; every compare and window statistic is done in float64:
+ *   xh_compare_map_f64      compare (generic.py:301-326) / get_daily_events (generic.py:395-431).  dtypes 0: a (and b) float64;
+ *                           1: a float32 against a float64 b; 2: a float64 against a float32 b (the float32 side is widened,
+ *                           numpy promotion).  b NULL: the double scalar thr.  out_kind 0, 1, 3 as xh_compare_map; 2 and 4
+ *                           return XH_ERR_NOTIMPL.
+ *   xh_run_stats_f64        xh_run_stats with the fused compare in float64 (generic.py:543-585, maximum_consecutive_*_days,
+ *                           indices/_threshold.py:2815-2937); XH_RUN_FIRST / LAST return XH_ERR_NOTIMPL.
+ *   xh_spell_mask_f64       spell_mask (generic.py:434-540, rolling window statistics :506-535): the window sum added in float64
+ *   xh_spell_run_stats_f64  in row order t-w+1 .. t, the mean = sum / w, min / max, compared in float64.  One variable, no
+ *                           weights (XH_ERR_NOTIMPL); the fused form takes window <= 8 (XH_ERR_NOTIMPL beyond).
+ *   xh_run_stats_doy_f64    xh_run_stats_doy (indices/_multivariate.py:66-152, 1693-1793) with a float64 x.
+ *   xh_percentile_doy_f64   xh_percentile_doy (core/calendar.py:395-494; _nan_quantile, core/utils.py:479-557) with a float64
+ *                           x: bit-identical to xh_nan_quantile_f64 of the gathered window samples.  nyears * window <= 4096
+ *                           (XH_ERR_LIMIT beyond). */
+int xh_compare_map_f64(xh_ctx* ctx, const void* a, int64_t T, int64_t C, int64_t st, int op, double thr, const void* b,
+                       int64_t st_b, int dtypes, int out_kind, void* out, int64_t st_out);
+int xh_run_stats_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int64_t st, int64_t sc, int fused_op, double thr,
+                     int window, int stat, int index_first, const int64_t* seg_off, int P, int cut_at_segments, float* out,
+                     int32_t* valid_out);
+int xh_spell_mask_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int64_t st, int64_t sc, int window, int win_reducer,
+                      int op, double thr, const double* weights /* must be NULL */, float* out, int64_t out_st);
+int xh_spell_run_stats_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int64_t st, int64_t sc, int window, int win_reducer,
+                           int op, double thr, const double* weights /* must be NULL */, int stat, const int64_t* seg_off,
+                           int P, float* out, int32_t* valid_out);
+int xh_run_stats_doy_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int64_t st, int64_t sc, int op, const double* table,
+                         int D, const int32_t* tidx, int window, int stat, const int64_t* seg_off, int P, float* out,
+                         int32_t* valid_out);
+int xh_percentile_doy_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int64_t st, int64_t sc, const int32_t* tbase,
+                          int nyears, int ndoy, int window, const double* per /* host */, int nper, double alpha, double beta,
+                          double* out);
+
 /* Weighted quantiles over the first axis (ensemble_percentiles with `weights`, ensembles/_base.py:346-356, which calls
  * xarray's DataArrayWeighted.quantile: Kish effective sample size + type-7 weighted estimator, NaN samples and zero
  * weights dropped).  x (N, C) member-major (sc == 1), weights[N] / q[nq] on the host, out (nq, C) float64; N <= 128.

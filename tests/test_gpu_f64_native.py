@@ -1,0 +1,284 @@
+"""XCLIM_AMD_FLOAT64=native: float64 fields computed in float64 by compare, the run-length indices, the spell indices and
+percentile_doy (xclim_amd/csrc/f64run.hip), equal to the oracle run on the float64 arrays.
+
+The fields put days at thr +- 1 float64 ulp and at thr +- a quarter float32 ulp (a value that rounds ONTO the threshold
+in float32), with NaN days, an all-NaN cell and several years.  Every case also checks that the same data rounded to
+float32 gives a different answer somewhere, so that rounding the field cannot pass these tests."""
+import numpy as np
+import pytest
+
+import fakexr
+from oracle import calendar as ocal
+from oracle import generic as ogen
+from oracle import indices as oidx
+from oracle import run_length as orl
+from oracle.timeutil import OTime
+from xclim_amd import calendar as hcal
+from xclim_amd import generic as hgen
+from xclim_amd import indices as xi
+from xclim_amd import patch
+from xclim_amd import run_length as hrl
+from xclim_amd import sdba as xsdba
+from xclim_amd._capi import Float64FieldError
+from xclim_amd.timeaxis import TimeAxis
+
+pytestmark = pytest.mark.gpu
+
+T3 = 365 * 3
+
+
+@pytest.fixture
+def native(monkeypatch):
+    monkeypatch.setenv("XCLIM_AMD_FLOAT64", "native")
+
+
+def _near(rng, T, shape, thr, spread, p_close=0.5, nan_frac=0.02):
+    """float64 field: about half the days within a float32 ulp of `thr`, the rest spread around it; NaN days and cell 0
+    all-NaN."""
+    u32 = float(np.spacing(np.float32(thr)))
+    close = np.array([np.nextafter(thr, -np.inf), thr, np.nextafter(thr, np.inf), thr + 0.25 * u32, thr - 0.25 * u32,
+                      thr + 0.45 * u32, thr - 0.45 * u32])
+    x = thr + rng.normal(0, spread, (T,) + shape)
+    pick = rng.random(x.shape) < p_close
+    x[pick] = rng.choice(close, int(pick.sum()))
+    x[rng.random(x.shape) < nan_frac] = np.nan
+    x.reshape(T, -1)[:, 0] = np.nan
+    return x
+
+
+def _differs(a, b):
+    return not np.array_equal(np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64), equal_nan=True)
+
+
+def _axes(T, calendar="noleap", start=2001):
+    if calendar == "noleap":
+        return TimeAxis.daily(f"{start}-01-01", T, "noleap"), OTime.noleap(start, T)
+    return TimeAxis.daily(f"{start}-01-01", T, "standard"), OTime.standard(f"{start}-01-01", T)
+
+
+# ---- 1. compare ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("op", [">", "<=", ">=", "<"])
+def test_compare_scalar_and_array_thresholds_in_float64(dev, rng, native, op):
+    thr = 285.0
+    x = _near(rng, T3, (3, 4), thr, 2.0)
+    ta, ot = _axes(T3)
+    got = hgen.compare(x, op, thr, device=dev)
+    exp = ogen.compare(x, op, thr)
+    np.testing.assert_array_equal(got, exp)
+    assert _differs(exp, ogen.compare(x.astype(np.float32), op, np.float32(thr)))
+    # float32 field against a float64 array threshold (numpy promotion: a float64 compare)
+    th = _near(rng, T3, (3, 4), thr, 2.0, nan_frac=0.0)
+    x32 = x.astype(np.float32)
+    got = hgen.compare(x32, op, th, device=dev)
+    np.testing.assert_array_equal(got, ogen.compare(x32, op, th))
+    assert _differs(ogen.compare(x32, op, th), ogen.compare(x32, op, th.astype(np.float32)))
+    # float64 field against a float64 array
+    got = hgen.compare(x, op, th, device=dev)
+    np.testing.assert_array_equal(got, ogen.compare(x, op, th))
+    # get_daily_events: 1 / 0, NaN where the data is NaN
+    ev = hgen.get_daily_events(x, thr, op, device=dev)
+    np.testing.assert_array_equal(ev, ogen.get_daily_events(x, thr, op))
+    # run lengths of that mask
+    m = ogen.compare(x, op, thr)
+    got_m = hgen.compare(x, op, thr, device=dev, keep=True).reshape(T3, 3, 4)
+    np.testing.assert_array_equal(hrl.longest_run(got_m, freq="YS", time=ta, device=dev),
+                                  orl.longest_run(m, ot, "YS"))
+    np.testing.assert_array_equal(hrl.rle_statistics(got_m, "mean", 2, freq="YS", time=ta, device=dev),
+                                  orl.rle_statistics(m, "mean", 2, ot, "YS"))
+
+
+# ---- 2. the cdd family -------------------------------------------------------------------------------------------
+def test_consecutive_day_indices_in_float64(dev, rng, native):
+    thr = 1.0 / 86400.0
+    ta, ot = _axes(T3)
+    pr = _near(rng, T3, (4, 5), thr, 2.0 * thr)
+    pr = np.where(pr < 0, 0.0, pr)
+    for host, exp_fn in ((xi.maximum_consecutive_dry_days, oidx.maximum_consecutive_dry_days),
+                         (xi.maximum_consecutive_wet_days, lambda p, t, o, f: ogen.spell_length_statistics(p, t, 1, None, ">", "max", o, f))):
+        got = host(pr, thr, ta, freq="YS", device=dev)
+        raw = exp_fn(pr, thr, ot, "YS")
+        np.testing.assert_array_equal(got, oidx.apply_missing(raw, pr, ot, "YS"))
+        assert _differs(raw, exp_fn(pr.astype(np.float32), thr, ot, "YS"))
+    tx = _near(rng, T3, (4, 5), 303.15, 3.0)
+    got = xi.maximum_consecutive_tx_days(tx, 303.15, ta, freq="YS", device=dev)
+    raw = ogen.spell_length_statistics(tx, 303.15, 1, None, ">", "max", ot, "YS")
+    np.testing.assert_array_equal(got, oidx.apply_missing(raw, tx, ot, "YS"))
+    assert _differs(raw, ogen.spell_length_statistics(tx.astype(np.float32), 303.15, 1, None, ">", "max", ot, "YS"))
+
+
+# ---- 3. spells ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("window", [1, 3, 5, 8])
+@pytest.mark.parametrize("win_reducer", ["sum", "mean", "min", "max"])
+def test_spell_length_statistics_in_float64(dev, rng, native, window, win_reducer):
+    base = 285.0
+    thr = base * window if win_reducer == "sum" else base
+    ta, ot = _axes(T3)
+    x = _near(rng, T3, (3, 4), base, 1.0, p_close=0.8, nan_frac=0.01)
+    flipped = False
+    for op in (">", "<="):
+        for red in ("max", "sum"):
+            got = hgen.spell_length_statistics(x, thr, window, win_reducer, op, red, ta, "YS", device=dev)
+            exp = ogen.spell_length_statistics(x, thr, window, win_reducer, op, red, ot, "YS")
+            np.testing.assert_array_equal(got, exp)
+            flipped |= _differs(exp, ogen.spell_length_statistics(x.astype(np.float32), thr, window, win_reducer, op, red, ot, "YS"))
+    assert flipped
+
+
+@pytest.mark.parametrize("window", [2, 5, 12])
+def test_spell_mask_in_float64(dev, rng, native, window):
+    x = _near(rng, T3, (3, 4), 285.0, 1.0, p_close=0.8)
+    for red in ("sum", "mean", "min", "max"):
+        thr = 285.0 * window if red == "sum" else 285.0
+        got = hgen.spell_mask(x, window, red, ">", thr, device=dev)
+        np.testing.assert_array_equal(got, ogen.spell_mask(x, window, red, ">", thr))
+
+
+# ---- 4. percentile_doy -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("calendar", ["noleap", "standard"])
+@pytest.mark.parametrize("window", [5, 31])
+@pytest.mark.parametrize("ab", [(1.0 / 3.0, 1.0 / 3.0), (1.0, 1.0)])
+def test_percentile_doy_in_float64(dev, rng, native, calendar, window, ab):
+    start = 1981
+    T = 30 * 365 + (8 if calendar == "standard" else 0)
+    ta, ot = _axes(T, calendar, start)
+    t = np.arange(T)[:, None, None]
+    x = 288.0 + 12 * np.sin(2 * np.pi * (t - 100) / 365.25) + rng.normal(0, 3, (T, 2, 3))
+    x[rng.random(x.shape) < 0.02] = np.nan
+    x[:, 0, 0] = np.nan
+    x[: 365 * 4, 1, 1] = np.nan
+    per = [10, 50, 90]
+    p = hcal.percentile_doy(x, ta, window=window, per=per, alpha=ab[0], beta=ab[1], device=dev)
+    p_o, doys = ocal.percentile_doy(x, ot, window, per, ab[0], ab[1])
+    assert p.data.dtype == np.float64 and np.array_equal(p.dayofyear, doys)
+    np.testing.assert_array_equal(p.values(), p_o)
+    assert np.isnan(p_o[:, 0, 0]).all()
+    p32, _ = ocal.percentile_doy(x.astype(np.float32), ot, window, per, ab[0], ab[1])
+    assert _differs(p_o, p32)
+
+
+# ---- 5. end to end -----------------------------------------------------------------------------------------------
+def test_tx90p_and_wsdi_on_float64_tasmax(dev, rng, native):
+    T = 365 * 6
+    ta, ot = _axes(T)
+    t = np.arange(T)[:, None, None]
+    x = 288.0 + 12 * np.sin(2 * np.pi * (t - 100) / 365) + rng.normal(0, 3, (T, 3, 4))
+    x[rng.random(x.shape) < 0.003] = np.nan
+    p_o, doys = ocal.percentile_doy(x, ot, 5, 90.0)
+    # days on their own percentile +- a float32 ulp: the float64 compare decides
+    d = ta.doy - 1
+    on = rng.random(x.shape) < 0.2
+    thr_t = p_o[d, ..., 0]
+    u32 = np.spacing(thr_t.astype(np.float32)).astype(np.float64)
+    x = np.where(on, thr_t + rng.choice([-0.25, 0.25, 0.0], x.shape) * u32, x)
+    p_o, doys = ocal.percentile_doy(x, ot, 5, 90.0)
+    per = hcal.percentile_doy(x, ta, window=5, per=90.0, device=dev)
+    np.testing.assert_array_equal(per.values(), p_o)
+    got = xi.tx90p(x, per, ta, freq="YS", device=dev)
+    raw = oidx.tx90p(x, p_o[..., 0], doys, ot, "YS")
+    np.testing.assert_array_equal(got, oidx.apply_missing(raw, x, ot, "YS"))
+    assert _differs(raw, oidx.tx90p(x.astype(np.float32), p_o[..., 0], doys, ot, "YS"))
+    got = xi.warm_spell_duration_index(x, per, ta, window=3, freq="YS", device=dev)
+    raw = oidx.warm_spell_duration_index(x, p_o[..., 0], doys, ot, 3, "YS")
+    np.testing.assert_array_equal(got, oidx.apply_missing(raw, x, ot, "YS"))
+    raw32 = oidx.warm_spell_duration_index(x.astype(np.float32), p_o[..., 0], doys, ot, 3, "YS")
+    assert _differs(raw, raw32)
+
+
+# ---- grids of several workgroups: the two-cell and one-cell launches, odd cell counts, both resample orders -------------
+@pytest.mark.parametrize("shape", [(3, 400), (7, 151)])
+def test_float64_marches_on_grids_of_several_workgroups(dev, rng, native, shape):
+    T = 730
+    ta, ot = _axes(T)
+    x = _near(rng, T, shape, 285.0, 1.0, p_close=0.7, nan_frac=0.01)
+    np.testing.assert_array_equal(hgen.compare(x, ">", 285.0, device=dev), ogen.compare(x, ">", 285.0))
+    for window, red, thr in ((3, "mean", 285.0), (12, "sum", 285.0 * 12), (12, "max", 285.0)):  # ring form, memory form
+        np.testing.assert_array_equal(hgen.spell_mask(x, window, red, ">", thr, device=dev), ogen.spell_mask(x, window, red, ">", thr))
+    flipped = False
+    for window, before in ((1, True), (1, False), (3, True), (12, True)):
+        thr = 285.0 * window
+        got = hgen.spell_length_statistics(x, thr, window, "sum", ">", "max", ta, "YS", resample_before_rl=before, device=dev)
+        exp = ogen.spell_length_statistics(x, thr, window, "sum", ">", "max", ot, "YS", resample_before_rl=before)
+        np.testing.assert_array_equal(got, exp)
+        flipped |= _differs(exp, ogen.spell_length_statistics(x.astype(np.float32), thr, window, "sum", ">", "max", ot, "YS",
+                                                               resample_before_rl=before))
+    assert flipped
+    for before in (True, False):   # the run-length indices: resample before and after the run lengths
+        got = xi.maximum_consecutive_tx_days(x, 285.0, ta, freq="YS", resample_before_rl=before, device=dev)
+        raw = ogen.spell_length_statistics(x, 285.0, 1, None, ">", "max", ot, "YS", resample_before_rl=before)
+        np.testing.assert_array_equal(got, oidx.apply_missing(raw, x, ot, "YS"))
+    # the per-doy table forms: percentile_doy over several cell blocks, WSDI against its table
+    p = hcal.percentile_doy(x, ta, window=5, per=90.0, device=dev)
+    p_o, doys = ocal.percentile_doy(x, ot, 5, 90.0)
+    np.testing.assert_array_equal(p.values(), p_o)
+    got = xi.warm_spell_duration_index(x, p, ta, window=3, freq="YS", device=dev)
+    raw = oidx.warm_spell_duration_index(x, p_o[..., 0], doys, ot, 3, "YS")
+    np.testing.assert_array_equal(got, oidx.apply_missing(raw, x, ot, "YS"))
+
+
+def test_percentile_doy_beyond_the_sample_limit_is_refused(dev, rng, native):
+    """nyears x window > 4096 samples: Float64FieldError (the adapter then forwards to the reference), never a device error."""
+    T = 140 * 365
+    ta, _ = _axes(T, start=1901)
+    with pytest.raises(Float64FieldError, match="float64 fields are only served by"):
+        hcal.percentile_doy(rng.normal(280, 5, (T, 2)), ta, window=31, per=90.0, device=dev)
+
+
+# ---- 6. policy ---------------------------------------------------------------------------------------------------
+def test_default_still_refuses_and_native_refuses_what_it_does_not_serve(dev, rng, monkeypatch):
+    ta, ot = _axes(T3)
+    x = _near(rng, T3, (3, 4), 285.0, 2.0)
+    monkeypatch.delenv("XCLIM_AMD_FLOAT64", raising=False)
+    calls = [lambda: hgen.compare(x, ">", 285.0, device=dev),
+             lambda: hgen.compare(x.astype(np.float32), ">", x, device=dev),
+             lambda: xi.maximum_consecutive_dry_days(x, 285.0, ta, device=dev),
+             lambda: hgen.spell_length_statistics(x, 285.0, 3, "mean", ">", "max", ta, "YS", device=dev),
+             lambda: hcal.percentile_doy(x, ta, device=dev)]
+    for call in calls:
+        with pytest.raises(Float64FieldError, match="float64 fields are only served by"):
+            call()
+    monkeypatch.setenv("XCLIM_AMD_FLOAT64", "native")
+    for call in calls:
+        call()
+    with pytest.raises(Float64FieldError, match="float64 fields are only served by"):
+        hgen.spell_mask(x, 3, "mean", ">", 285.0, weights=[0.2, 0.3, 0.5], device=dev)
+    with pytest.raises(Float64FieldError, match="float64 fields are only served by"):
+        xsdba.EmpiricalQuantileMapping.train(x, x, nquantiles=10, kind="+", device=dev)
+    with pytest.raises(Float64FieldError, match="float64 fields are only served by"):
+        hgen.spell_length_statistics([x, x], [285.0, 285.0], 3, "min", ">", "max", ta, "YS", device=dev)
+
+
+# ---- 7. adapter --------------------------------------------------------------------------------------------------
+@pytest.fixture()
+def ref(dev):
+    env = fakexr.make_env()
+    mods = fakexr.make_reference_like_modules(env)
+    import xclim_amd._capi as capi
+
+    old = capi._default_device
+    capi._default_device = dev
+    patch.install(env, mods)
+    yield env, mods
+    patch.uninstall()
+    capi._default_device = old
+
+
+def test_tx90p_on_float64_through_the_adapter(ref, dev, rng, monkeypatch):
+    env, mods = ref
+    T = 365 * 3
+    ta, ot = _axes(T)
+    t = np.arange(T)[:, None, None]
+    x = 288.0 + 12 * np.sin(2 * np.pi * (t - 100) / 365) + rng.normal(0, 3, (T, 3, 4))
+    tasmax = fakexr.field(x, ta)
+    monkeypatch.setenv("XCLIM_AMD_FLOAT64", "native")
+    trace = dev.start_trace()
+    per = mods["xclim.core.calendar"].percentile_doy(tasmax, window=5, per=90.0)
+    out = mods["xclim.indices._multivariate"].tx90p(tasmax, per.sel(percentiles=90.0), freq="YS")
+    dev.stop_trace()
+    names = [n for n, _ in trace]
+    assert "xh_percentile_doy_f64" in names and "xh_threshold_count_f64" in names
+    assert "xh_percentile_doy" not in names
+    p_o, doys = ocal.percentile_doy(x, ot, 5, 90.0)
+    np.testing.assert_array_equal(out.transpose("time", ...).values, oidx.tx90p(x, p_o[..., 0], doys, ot, "YS"))
+    monkeypatch.delenv("XCLIM_AMD_FLOAT64", raising=False)
+    with pytest.raises(AssertionError, match="was reached"):   # the reference's own percentile_doy (a stub here)
+        mods["xclim.core.calendar"].percentile_doy(tasmax, window=5, per=90.0)

@@ -43,18 +43,49 @@ class Float64FieldError(TypeError):
     dtype; rounding the field first can flip a count next to a threshold, so it is refused unless asked for."""
 
 
+FLOAT64_POLICIES = ("raise", "round", "native")
+
+# what XCLIM_AMD_FLOAT64=native serves with float64 kernels (xh_*_f64), on top of the four entry points that always do
+NATIVE_SERVED = ("compare, get_daily_events, spell_length_statistics, spell_mask, spell_length, the run-length indices "
+                 "(maximum_consecutive_*_days, hot / cold / dry / wet spells), warm / cold_spell_duration_index and percentile_doy")
+
+
+def float64_policy() -> str:
+    """``XCLIM_AMD_FLOAT64``: "raise" (default, also for an unknown value), "round" or "native"."""
+    p = os.environ.get("XCLIM_AMD_FLOAT64", "raise").strip().lower()
+    return p if p in FLOAT64_POLICIES else "raise"
+
+
+def float64_native() -> bool:
+    """True under ``XCLIM_AMD_FLOAT64=native``: entry points with a float64 twin upload a float64 field as it is."""
+    return float64_policy() == "native"
+
+
 def handle_float64(a, what: str) -> None:
     """Policy for float64 fields on float32-only kernels (``XCLIM_AMD_FLOAT64``): "raise" (default) -> Float64FieldError;
-    "round" -> PrecisionWarning and the field is rounded to float32.  threshold_count / count_occurrences /
-    select_resample_op / calc_perc have native float64 kernels (xh_*_f64) and never come here."""
+    "round" -> PrecisionWarning and the field is rounded to float32; "native" -> the entry points with a float64 twin
+    (NATIVE_SERVED) never come here, every other one raises Float64FieldError (never rounds).  threshold_count /
+    count_occurrences / select_resample_op / calc_perc have native float64 kernels (xh_*_f64) and never come here."""
     if getattr(a, "dtype", None) != np.float64 or getattr(a, "ndim", 0) == 0:
         return
-    if os.environ.get("XCLIM_AMD_FLOAT64", "raise").lower() == "round":
+    policy = float64_policy()
+    if policy == "round":
         warn_downcast(a, what)
         return
+    if policy == "native":
+        refuse_float64(what)
     raise Float64FieldError(f"{what}: float64 fields are only served by threshold_count, count_occurrences, select_resample_op and "
                             "calc_perc (xh_*_f64); cast to float32 yourself, or set XCLIM_AMD_FLOAT64=round to have it "
                             "rounded with a PrecisionWarning")
+
+
+def refuse_float64(what: str) -> None:
+    """Float64FieldError for a float64 field on a step without a float64 kernel under ``native`` (an entry point without a
+    twin, or a form its twin does not cover: weighted or multi-variable spells, bootstrap, per-cell thresholds ...)."""
+    raise Float64FieldError(f"{what}: float64 fields are only served by threshold_count, count_occurrences, select_resample_op, "
+                            f"calc_perc and, under XCLIM_AMD_FLOAT64=native, {NATIVE_SERVED}; this call has no float64 "
+                            "kernel: cast to float32 yourself, or set XCLIM_AMD_FLOAT64=round to have it rounded with a "
+                            "PrecisionWarning")
 
 
 class BackendUnavailable(RuntimeError):
@@ -144,6 +175,12 @@ SIGNATURES: dict[str, list] = {
     "xh_threshold_count_f64": [_vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _dbl, _vp, _i64, _vp, _vp, _int, _vp, _vp],
     "xh_resample_reduce_f64": [_vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _vp, _int, _vp, _vp],
     "xh_nan_quantile_f64": [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _int, _dbl, _dbl, _vp],
+    "xh_compare_map_f64": [_vp, _vp, _i64, _i64, _i64, _int, _dbl, _vp, _i64, _int, _int, _vp, _i64],
+    "xh_run_stats_f64": [_vp, _vp, _i64, _i64, _i64, _i64, _int, _dbl, _int, _int, _int, _vp, _int, _int, _vp, _vp],
+    "xh_spell_mask_f64": [_vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _int, _dbl, _vp, _vp, _i64],
+    "xh_spell_run_stats_f64": [_vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _int, _dbl, _vp, _int, _vp, _int, _vp, _vp],
+    "xh_run_stats_doy_f64": [_vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _int, _vp, _int, _int, _vp, _int, _vp, _vp],
+    "xh_percentile_doy_f64": [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _int, _int, _int, _vp, _int, _dbl, _dbl, _vp],
     "xh_weighted_quantile": [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _int, _vp],
     "xh_percentile_doy": [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _int, _int, _int, _vp, _int, _dbl, _dbl, _vp],
     "xh_percentile_doy_mapped": [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _int, _int, _int, _vp, _int, _dbl, _dbl, _vp, _i64, _vp],

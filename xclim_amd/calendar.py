@@ -10,7 +10,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import kernels as K
-from ._capi import DeviceArray, handle_float64, get_device
+from ._capi import DeviceArray, float64_native, handle_float64, get_device
 from .timeaxis import TimeAxis, _is_leap
 
 
@@ -250,7 +250,7 @@ def percentile_doy(arr, time: TimeAxis, window: int = 5, per=10.0, alpha: float 
     ``copy`` is accepted for signature parity; the device kernels never mutate their input, so it is a no-op.
     """
     dev = device or get_device()
-    x, cell_shape = _flatten(arr, dev)
+    x, cell_shape = _flatten(arr, dev, f64=float64_native())  # native: xh_percentile_doy_f64 (`diff` in float64, utl:486)
     if len(time) != x.shape[0]:
         raise ValueError("time axis length does not match the data")
     tb, years, doys = time.doy_table()

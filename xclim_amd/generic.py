@@ -12,7 +12,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import kernels as K
-from ._capi import handle_float64, OPS, DeviceArray, get_device
+from ._capi import float64_native, handle_float64, refuse_float64, OPS, DeviceArray, get_device
 from .calendar import DoyPercentile, _flatten, adjust_doy_calendar, resample_doy_index
 from .timeaxis import TimeAxis
 
@@ -155,33 +155,44 @@ def compare(left, op: str, right, constrain=None, *, device=None, keep=False):
     float (fp32 compare), ``np.float64`` (fp64 compare) or an array of the shape of ``left``."""
     sym = get_op(op, constrain)
     dev = device or get_device()
-    x, cell_shape = _flatten(left, dev)
+    x, cell_shape = _flatten(left, dev, f64=float64_native())  # XCLIM_AMD_FLOAT64=native: float64 compare (xh_compare_map_f64)
     # keep=True: a float32 1 / 0 mask, the form every device consumer (run_length.*, spell kernels) reads; otherwise a
     # uint8 mask (a quarter of the bytes over PCIe) turned into numpy bool
     kind = "maskf" if keep else "mask"
     if np.ndim(right) == 0 and not isinstance(right, DeviceArray):
         m = K.compare_map(dev, x, sym, right, kind)
     else:
-        handle_float64(np.asarray(right), "compare: array threshold")
-        b, _ = _flatten(np.broadcast_to(np.asarray(right, dtype=np.float32), np.shape(left))
-                        if not isinstance(right, DeviceArray) else right, dev)
+        b = _array_threshold(right, left, x, dev)
         m = K.compare_map(dev, x, sym, b, kind)
     if keep:
         return m
     return m.get().reshape((x.shape[0],) + tuple(cell_shape)).astype(bool)
 
 
+def _array_threshold(thr, data, x: DeviceArray, dev):
+    """The array threshold of compare / get_daily_events as a (T, C) device field.  Under XCLIM_AMD_FLOAT64=native a float64
+    side keeps the compare in float64 (numpy promotion): a float64 threshold is uploaded as float64, and so is any
+    non-float32 threshold against a float64 field.  Otherwise the float64 policy applies and the threshold is float32."""
+    if float64_native():
+        if isinstance(thr, DeviceArray):
+            return _flatten(thr, dev, f64=True)[0]
+        t = np.asarray(thr)
+        if t.dtype == np.float64 or (x.dtype == np.float64 and t.dtype != np.float32):
+            return _flatten(np.ascontiguousarray(np.broadcast_to(t.astype(np.float64, copy=False), np.shape(data))), dev, f64=True)[0]
+    handle_float64(np.asarray(thr), "compare: array threshold")
+    return _flatten(np.broadcast_to(np.asarray(thr, dtype=np.float32), np.shape(data))
+                    if not isinstance(thr, DeviceArray) else thr, dev)[0]
+
+
 def get_daily_events(da, threshold, op: str, constrain=None, *, device=None, keep=False):
     """gen:395-431: 1 where ``da op threshold``, 0 where not, NaN where ``da`` is NaN (float32)."""
     sym = get_op(op, constrain)
     dev = device or get_device()
-    x, cell_shape = _flatten(da, dev)
+    x, cell_shape = _flatten(da, dev, f64=float64_native())
     if np.ndim(threshold) == 0 and not isinstance(threshold, DeviceArray):
         ev = K.compare_map(dev, x, sym, threshold, "events")
     else:
-        handle_float64(np.asarray(threshold), "compare: array threshold")
-        b, _ = _flatten(np.broadcast_to(np.asarray(threshold, dtype=np.float32), np.shape(da))
-                        if not isinstance(threshold, DeviceArray) else threshold, dev)
+        b = _array_threshold(threshold, da, x, dev)
         ev = K.compare_map(dev, x, sym, b, "events")
     if keep:
         return ev
@@ -302,7 +313,7 @@ def spell_length_statistics(data, threshold, window: int, win_reducer, op: str, 
         flat = [_flatten(d, dev) for d in data]
         x, cell_shape = flat[0]
     else:
-        x, cell_shape = _flatten(data, dev)
+        x, cell_shape = _flatten(data, dev, f64=float64_native())  # native: xh_run_stats_f64 / xh_spell_*_f64
     if indexer and any(v is not None for k, v in indexer.items() if k != "include_bounds"):
         from .calendar import select_time
 
@@ -358,7 +369,7 @@ def spell_length(data, threshold: float, reducer: str, time: TimeAxis, freq: str
     if reducer not in ("max", "min", "mean", "sum"):
         raise ValueError(f"reducer must be one of max, min, mean, sum; got {reducer!r}")
     dev = device or get_device()
-    x, cell_shape = _flatten(data, dev)
+    x, cell_shape = _flatten(data, dev, f64=float64_native())
     seg, _ = time.segments(freq)
     out, val = K.run_stats(dev, x, reducer, 1, seg, cut=True, fused_op=get_op(op), thresh=float(threshold))
     return _finish(out, val, cell_shape, keep, with_valid)
@@ -406,8 +417,10 @@ def spell_mask(data, window: int, win_reducer: str, op: str, thresh, min_gap: in
         else:
             m = K.spell_mask_multi(dev, xs, window, win_reducer, sym, th, var_reducer, weights)
     else:
-        x, cell_shape = _flatten(data, dev)
+        x, cell_shape = _flatten(data, dev, f64=float64_native())
         cell = _cell_threshold(dev, thresh, data)
+        if x.dtype == np.float64 and (cell is not None or weights is not None):
+            refuse_float64("spell_mask with a per-cell threshold or weights")
         if cell is not None:
             # one threshold per grid cell (a DataArray without the time dim in the reference: tests/test_generic.py:754-766).
             # The compare runs against the one-row float64 table; with a window the three steps of gen:519-535 are kept

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import generic
 from . import kernels as K
-from ._capi import get_device
+from ._capi import float64_native, get_device
 from .bootstrapping import percentile_bootstrap
 from .calendar import DoyPercentile
 from .timeaxis import TimeAxis
@@ -158,7 +158,7 @@ def _percentile_run(da, per: DoyPercentile, stat, window, time, freq, resample_b
     from .calendar import _flatten, adjust_doy_calendar, resample_doy_index
 
     sym = generic.get_op(op, constrain)
-    x, cell_shape = _flatten(da, dev)
+    x, cell_shape = _flatten(da, dev, f64=float64_native())  # native: xh_run_stats_doy_f64
     doy = adjust_doy_calendar(per, time, dev)
     if doy.data.shape[0] != 1:
         raise ValueError("select one percentile first (DoyPercentile.sel)")
@@ -361,7 +361,7 @@ def _run_index(da, thresh, op, constrain, stat, window, time, freq, resample_bef
     sym = generic.get_op(op, constrain)
     from .calendar import _flatten
 
-    x, cell_shape = _flatten(da, dev)
+    x, cell_shape = _flatten(da, dev, f64=float64_native())  # native: xh_run_stats_f64 (fused compare in float64)
     seg, _ = time.segments(freq)
     cell = generic._cell_threshold(dev, thresh, da)
     if cell is not None:  # one threshold per grid cell (a DataArray threshold in the reference)

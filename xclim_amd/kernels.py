@@ -34,6 +34,19 @@ def _tc(x: DeviceArray, dtype=np.float32):
     return int(x.shape[0]), int(x.shape[1])
 
 
+def _field(x: DeviceArray):
+    """(T, C, is_float64) of a float32 or float64 field: a float64 field picks the entry point's ``_f64`` twin."""
+    f64 = np.dtype(x.dtype) == np.float64
+    T, C_ = _tc(x, np.float64 if f64 else np.float32)
+    return T, C_, f64
+
+
+def _f32_only(x, what: str) -> None:
+    """A float64 field on a form without a float64 kernel: Float64FieldError (never rounded)."""
+    if isinstance(x, DeviceArray) and np.dtype(x.dtype) == np.float64:
+        capi.refuse_float64(what)
+
+
 def _seg(seg_off):
     s = np.ascontiguousarray(seg_off, dtype=np.int64)
     return s, len(s) - 1
@@ -181,7 +194,7 @@ def run_stats(dev: Device, x: DeviceArray, stat: str, window: int, seg_off, *, c
     """xh_run_stats.  ``one_dim``: the NaN semantics of the reference's 1-D ufunc path (index "first" only); True = the
     windowed_run_count / windowed_run_events form, "stat" = the statistics_run_1d form (NaN for a series with NaN steps and
     no qualifying run)."""
-    T, C_ = _tc(x)
+    T, C_, f64 = _field(x)
     seg, P = _seg(seg_off)
     if out is not None:
         out, valid = out
@@ -189,7 +202,9 @@ def run_stats(dev: Device, x: DeviceArray, stat: str, window: int, seg_off, *, c
         out = dev.empty((P, C_), np.float32)
         valid = dev.empty((P, C_), np.int32) if want_valid else None
     fop = -1 if fused_op is None else op_code(fused_op)
-    dev.call("xh_run_stats", _vp(x.ptr), T, C_, C_, 1, fop, float(thresh), int(window), RUN_STATS[stat],
+    if f64 and stat in ("first", "last"):
+        capi.refuse_float64(f"run_stats({stat})")
+    dev.call("xh_run_stats_f64" if f64 else "xh_run_stats", _vp(x.ptr), T, C_, C_, 1, fop, float(thresh), int(window), RUN_STATS[stat],
              ((3 if one_dim == "stat" else 2) if one_dim else 1) if index == "first" else 0, np_ptr(seg), P, int(bool(cut)), _vp(out.ptr),
              _vp(valid.ptr if valid else 0))
     return out, valid
@@ -221,8 +236,10 @@ def range_reduce(dev: Device, low: DeviceArray, high: DeviceArray, mode: str, re
 def compare_map(dev: Device, a: DeviceArray, op, thr, kind: str = "mask") -> DeviceArray:
     """kind: "mask" (uint8) | "maskf" (float 1/0) | "events" (float 1/0/NaN) | "where" (a where cond else NaN) | "excess"
     ((a - thr).clip(0), NaN kept; op unused); thr: scalar or DeviceArray."""
-    T, C_ = _tc(a)
     ok = {"mask": 0, "events": 1, "where": 2, "maskf": 3, "excess": 4}[kind]
+    if a.dtype == np.float64 or (isinstance(thr, DeviceArray) and thr.dtype == np.float64):
+        return _compare_map_f64(dev, a, op, thr, ok)
+    T, C_ = _tc(a)
     out = dev.empty(a.shape, np.uint8 if ok == 0 else np.float32)
     if isinstance(thr, DeviceArray):
         assert thr.shape == a.shape and thr.dtype == np.float32
@@ -230,6 +247,23 @@ def compare_map(dev: Device, a: DeviceArray, op, thr, kind: str = "mask") -> Dev
     else:
         dev.call("xh_compare_map", _vp(a.ptr), T, C_, C_, op_code(op), float(thr), int(isinstance(thr, np.float64)), _vp(0), 0, ok,
                  _vp(out.ptr), C_)
+    return out
+
+
+def _compare_map_f64(dev: Device, a: DeviceArray, op, thr, ok: int) -> DeviceArray:
+    """xh_compare_map_f64: the compare in float64 (numpy promotion: a float32 side is widened).  Masks only."""
+    if ok in (2, 4):
+        capi.refuse_float64("compare_map(where / excess)")
+    T, C_ = _tc(a, None)
+    if a.dtype not in (np.float32, np.float64):
+        raise TypeError(f"expected a float32 or float64 device array, got {np.dtype(a.dtype).name}")
+    out = dev.empty(a.shape, np.uint8 if ok == 0 else np.float32)
+    if isinstance(thr, DeviceArray):
+        assert thr.shape == a.shape and thr.dtype in (np.float32, np.float64)
+        dtypes = 1 if a.dtype == np.float32 else (2 if thr.dtype == np.float32 else 0)
+        dev.call("xh_compare_map_f64", _vp(a.ptr), T, C_, C_, op_code(op), 0.0, _vp(thr.ptr), C_, dtypes, ok, _vp(out.ptr), C_)
+    else:
+        dev.call("xh_compare_map_f64", _vp(a.ptr), T, C_, C_, op_code(op), float(thr), _vp(0), 0, 0, ok, _vp(out.ptr), C_)
     return out
 
 
@@ -291,8 +325,14 @@ WIN_REDUCERS = {"sum": 0, "mean": 1, "min": 2, "max": 3, "wmean": 4}
 
 
 def spell_mask(dev: Device, x: DeviceArray, window: int, win_reducer: str, op: str, thresh: float, weights=None) -> DeviceArray:
-    T, C_ = _tc(x)
+    T, C_, f64 = _field(x)
     out = dev.empty((T, C_), np.float32)
+    if f64:  # xh_spell_mask_f64: window statistic and compare in float64; weighted windows are not served
+        if weights is not None:
+            capi.refuse_float64("spell_mask(weights=...)")
+        dev.call("xh_spell_mask_f64", _vp(x.ptr), T, C_, C_, 1, int(window), WIN_REDUCERS[win_reducer or "min"], op_code(op),
+                 float(thresh), _vp(0), _vp(out.ptr), C_)
+        return out
     w = np.ascontiguousarray(weights, dtype=np.float32) if weights is not None else None
     red = WIN_REDUCERS["wmean" if w is not None else (win_reducer or "min")]
     dev.call("xh_spell_mask", _vp(x.ptr), T, C_, C_, 1, int(window), red, op_code(op), float(thresh),
@@ -306,15 +346,17 @@ def spell_run_stats(dev: Device, x: DeviceArray, window: int, win_reducer: str, 
     Returns None when the shape is not covered (window > 8): the caller then takes spell_mask + run_stats."""
     from ._capi import XH_ERR_NOTIMPL, XclimHipError
 
-    T, C_ = _tc(x)
+    T, C_, f64 = _field(x)
     seg, P = _seg(seg_off)
+    if f64 and weights is not None:
+        capi.refuse_float64("spell_run_stats(weights=...)")
     out = dev.empty((P, C_), np.float32)
     valid = dev.empty((P, C_), np.int32) if want_valid else None
     w = np.ascontiguousarray(weights, dtype=np.float32) if weights is not None else None
     red = WIN_REDUCERS["wmean" if w is not None else (win_reducer or "min")]
     try:
-        dev.call("xh_spell_run_stats", _vp(x.ptr), T, C_, C_, 1, int(window), red, op_code(op), float(thresh),
-                 np_ptr(w) if w is not None else _vp(0), RUN_STATS[stat], np_ptr(seg), P, _vp(out.ptr),
+        dev.call("xh_spell_run_stats_f64" if f64 else "xh_spell_run_stats", _vp(x.ptr), T, C_, C_, 1, int(window), red, op_code(op),
+                 float(thresh), np_ptr(w) if w is not None else _vp(0), RUN_STATS[stat], np_ptr(seg), P, _vp(out.ptr),
                  _vp(valid.ptr if valid else 0))
     except XclimHipError as e:
         if e.code == XH_ERR_NOTIMPL:
@@ -425,14 +467,19 @@ def percentile_doy(dev: Device, x: DeviceArray, tbase, window: int, per, alpha=1
                    out=None, vmap=None) -> DeviceArray:
     """Returns (nper, ndoy, C) float64 — percentile_doy before the 366-day adjustment.
 
-    `vmap` (int32[Tv], optional): virtual-day -> physical-row table; `tbase` then indexes virtual days."""
-    T, C_ = _tc(x)
+    `vmap` (int32[Tv], optional): virtual-day -> physical-row table; `tbase` then indexes virtual days.  A float64 field
+    takes xh_percentile_doy_f64 (no virtual axis: bootstrap is not served for float64)."""
+    T, C_, f64 = _field(x)
+    if f64 and vmap is not None:
+        capi.refuse_float64("percentile_doy(bootstrap)")
+    if f64 and np.shape(tbase)[0] * int(window) > 4096:  # xh_percentile_doy_f64 gathers <= 4096 samples per (doy, cell)
+        capi.refuse_float64(f"percentile_doy({np.shape(tbase)[0]} years x window {window} > 4096 samples)")
     tb = np.ascontiguousarray(tbase, dtype=np.int32)
     nyears, ndoy = tb.shape
     per = np.ascontiguousarray(np.atleast_1d(per), dtype=np.float64)
     out = out if out is not None else dev.empty((len(per), ndoy, C_), np.float64)
     if vmap is None:
-        dev.call("xh_percentile_doy", _vp(x.ptr), T, C_, C_, 1, np_ptr(tb), nyears, ndoy, int(window), np_ptr(per), len(per),
+        dev.call("xh_percentile_doy_f64" if f64 else "xh_percentile_doy", _vp(x.ptr), T, C_, C_, 1, np_ptr(tb), nyears, ndoy, int(window), np_ptr(per), len(per),
                  float(alpha), float(beta), _vp(out.ptr))
     else:
         vm = np.ascontiguousarray(vmap, dtype=np.int32)
@@ -504,6 +551,7 @@ def within_bnds_doy(dev: Device, x: DeviceArray, low: DeviceArray, high: DeviceA
 
 def compare_doy(dev: Device, x: DeviceArray, op: str, table: DeviceArray, tidx) -> DeviceArray:
     """float32 1/0 mask of x[t] op table[tidx[t]] (fp64 compare, (D, C) float64 per-doy table)."""
+    _f32_only(x, "compare against a per-cell or per-doy threshold (resample after run length)")
     T, C_ = _tc(x)
     D = table.shape[0]
     tidx = np.ascontiguousarray(tidx, dtype=np.int32)
@@ -515,14 +563,14 @@ def compare_doy(dev: Device, x: DeviceArray, op: str, table: DeviceArray, tidx) 
 
 def run_stats_doy(dev: Device, x: DeviceArray, op: str, table: DeviceArray, tidx, stat: str, window: int, seg_off, want_valid=True):
     """xh_run_stats_doy: run statistics (cut at the period edges) of x[t] op table[tidx[t]]; table (D, C) float64."""
-    T, C_ = _tc(x)
+    T, C_, f64 = _field(x)
     D = table.shape[0]
     tidx = np.ascontiguousarray(tidx, dtype=np.int32)
     assert len(tidx) == T and table.shape == (D, C_) and table.dtype == np.float64
     seg, P = _seg(seg_off)
     out = dev.empty((P, C_), np.float32)
     valid = dev.empty((P, C_), np.int32) if want_valid else None
-    dev.call("xh_run_stats_doy", _vp(x.ptr), T, C_, C_, 1, op_code(op), _vp(table.ptr), D, np_ptr(tidx), int(window), RUN_STATS[stat],
+    dev.call("xh_run_stats_doy_f64" if f64 else "xh_run_stats_doy", _vp(x.ptr), T, C_, C_, 1, op_code(op), _vp(table.ptr), D, np_ptr(tidx), int(window), RUN_STATS[stat],
              np_ptr(seg), P, _vp(out.ptr), _vp(valid.ptr if valid else 0))
     return out, valid
 

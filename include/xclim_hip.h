@@ -246,7 +246,7 @@ int xh_resample_reduce(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_
                        int skipna, const int64_t* seg_off, int P, void* out, int32_t* valid_out);
 
 /* MissingAny (core/missing.py:318-322): out64[p, c] = valid[p, c] != expected[p] ? NaN : value.
- * value_kind 0: int32 input, 1: float32 input. */
+ * value_kind 0: int32 input, 1: float32 input, 2: float64 input (the results of the float64 twins). */
 int xh_apply_missing_mask(xh_ctx* ctx, const void* value, int value_kind, const int32_t* valid,
                           const int32_t* expected, int P, int64_t C, double* out64);
 
@@ -392,6 +392,34 @@ int xh_run_stats_doy_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int
 int xh_percentile_doy_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int64_t st, int64_t sc, const int32_t* tbase,
                           int nyears, int ndoy, int window, const double* per /* host */, int nper, double alpha, double beta,
                           double* out);
+
+/* float64 FIELD twins of the period reductions (f64red.hip), same layouts, segment tables and valid counts as their float32
+ * twins; every difference, sum and compare is done in float64, sums are added in row order (bit-identical to numpy's axis-0
+ * sums of the float64 arrays), float results are FLOAT64, counts int32:
+ *   xh_thresholded_reduce_f64  xh_thresholded_reduce: mode 0 thresholded_statistics (generic.py:1278-1320), 1 temperature_sum
+ *                              (generic.py:1323-1357, with its sign), 2 cumulative_difference (generic.py:1514-1552:
+ *                              growing / heating / cooling degree days); out (P, C) float64.
+ *   xh_range_reduce_f64        xh_range_reduce: mode 0 diurnal_temperature_range (generic.py:1076-1105), 1 interday
+ *                              (generic.py:1360-1385, diff drops day 0 and the value belongs to the later day), 2 extreme
+ *                              (generic.py:1388-1414); out (P, C) float64.  dtypes 0: low and high float64; 1: low float32;
+ *                              2: high float32 (the float32 side is widened exactly, numpy promotion).
+ *   xh_domain_count_f64        xh_domain_count (generic.py:364-392, days_with_snow): (x op1 thr1) and|or (x op2 thr2) in float64.
+ *   xh_bivariate_count_f64     xh_bivariate_count (generic.py:1002-1073, 913-957); dtypes as xh_range_reduce_f64 for x1 / x2.
+ *                              A float32 side compares against its threshold rounded to float32 (numpy's weak python scalar).
+ *   xh_rolling_reduce_f64      xh_rolling_reduce (generic.py:128-174 rolling step): rolling(window, center).{sum, mean, min, max,
+ *                              std, var, count} for any window >= 1, out (T, C) float64; the window is added first row to last,
+ *                              std / var are numpy's two passes (population). */
+int xh_thresholded_reduce_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int64_t st, int64_t sc, int op, double thr,
+                              int mode, int reducer, const int64_t* seg_off, int P, double* out, int32_t* valid_out);
+int xh_range_reduce_f64(xh_ctx* ctx, const void* low, const void* high, int64_t T, int64_t C, int64_t st_low, int64_t st_high,
+                        int dtypes, int mode, int reducer, const int64_t* seg_off, int P, double* out, int32_t* valid_out);
+int xh_domain_count_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int64_t st, int64_t sc, int op1, double thr1, int op2,
+                        double thr2, int combine, const int64_t* seg_off, int P, int32_t* count_out, int32_t* valid_out);
+int xh_bivariate_count_f64(xh_ctx* ctx, const void* x1, const void* x2, int64_t T, int64_t C, int64_t st1, int64_t st2, int dtypes,
+                           int op1, double thr1, int op2, double thr2, int combine, const int64_t* seg_off, int P,
+                           int32_t* count_out, int32_t* valid_out);
+int xh_rolling_reduce_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int64_t st, int64_t sc, int window, int center,
+                          int reducer, double* out, int64_t out_st);
 
 /* Weighted quantiles over the first axis (ensemble_percentiles with `weights`, ensembles/_base.py:346-356, which calls
  * xarray's DataArrayWeighted.quantile: Kish effective sample size + type-7 weighted estimator, NaN samples and zero

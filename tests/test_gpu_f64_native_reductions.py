@@ -1,0 +1,418 @@
+"""XCLIM_AMD_FLOAT64=native: float64 fields computed in float64 by the degree-day / thresholded reductions, the temperature
+ranges, domain and bivariate counts, rolling statistics (xclim_amd/csrc/f64red.hip) and by the seasons, first-day and
+day-of-year functions built on the existing float64 twins, equal to the oracle run on the float64 arrays.
+
+Fields are built like test_gpu_f64_native._near: days at the threshold +- 1 float64 ulp and +- a quarter / half float32 ulp,
+NaN days and an all-NaN cell.  Every case also checks that the same data rounded to float32 gives a different answer
+somewhere.  Sums are compared BIT FOR BIT: the kernels add each period (each window) in row order, which is the order of
+numpy's axis-0 sum of a C-contiguous group that the oracle takes; std / var of a rolling window are compared with
+rtol 1e-13."""
+import numpy as np
+import pytest
+
+import fakexr
+from oracle import generic as ogen
+from oracle import indices as oidx
+from oracle import run_length as orl
+from oracle.timeutil import OTime
+from xclim_amd import generic as hgen
+from xclim_amd import indices as xi
+from xclim_amd import kernels as K
+from xclim_amd import patch
+from xclim_amd._capi import Float64FieldError
+from xclim_amd.timeaxis import TimeAxis
+
+pytestmark = pytest.mark.gpu
+
+T2 = 730
+SHAPES = [(3, 400), (7, 151)]   # 1200 cells: two cells per lane; 1057 cells: one cell per lane; both several workgroups
+AXES = [("noleap", "YS"), ("standard", "MS")]
+
+
+@pytest.fixture
+def native(monkeypatch):
+    monkeypatch.setenv("XCLIM_AMD_FLOAT64", "native")
+
+
+def _near(rng, T, shape, thr, spread, p_close=0.5, nan_frac=0.02):
+    u32 = float(np.spacing(np.float32(thr)))
+    close = np.array([np.nextafter(thr, -np.inf), thr, np.nextafter(thr, np.inf), thr + 0.25 * u32, thr - 0.25 * u32,
+                      thr + 0.45 * u32, thr - 0.45 * u32])
+    x = thr + rng.normal(0, spread, (T,) + shape)
+    pick = rng.random(x.shape) < p_close
+    x[pick] = rng.choice(close, int(pick.sum()))
+    x[rng.random(x.shape) < nan_frac] = np.nan
+    x.reshape(T, -1)[:, 0] = np.nan
+    return x
+
+
+def _differs(a, b):
+    return not np.array_equal(np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64), equal_nan=True)
+
+
+def _axes(T, calendar="noleap", start=2001):
+    if calendar == "noleap":
+        return TimeAxis.daily(f"{start}-01-01", T, "noleap"), OTime.noleap(start, T)
+    return TimeAxis.daily(f"{start}-01-01", T, "standard"), OTime.standard(f"{start}-01-01", T)
+
+
+def _traced(dev, fn):
+    trace = dev.start_trace()
+    try:
+        out = fn()
+    finally:
+        dev.stop_trace()
+    return out, [n for n, _ in trace]
+
+
+def _bits(got, exp):
+    got = np.asarray(got)
+    assert got.dtype == np.float64
+    np.testing.assert_array_equal(got, exp)
+
+
+# ---- 1. degree days and thresholded statistics (xh_thresholded_reduce_f64) ----------------------------------------------
+@pytest.mark.parametrize("shape", SHAPES)
+@pytest.mark.parametrize("calendar, freq", AXES)
+def test_degree_days_and_thresholded_statistics_in_float64(dev, rng, native, shape, calendar, freq):
+    thr = 283.15
+    T = T2 + (1 if calendar == "standard" else 0)
+    ta, ot = _axes(T, calendar)
+    x = _near(rng, T, shape, thr, 3.0)
+    x32 = x.astype(np.float32)
+    for op in (">", "<"):   # growing / heating degree days
+        got, names = _traced(dev, lambda: hgen.cumulative_difference(x, thr, op, ta, freq, device=dev))
+        exp = ogen.cumulative_difference(x, thr, op, ot, freq)
+        _bits(got, exp)   # bit for bit: row-order sums
+        assert "xh_thresholded_reduce_f64" in names and "xh_thresholded_reduce" not in names
+        assert _differs(exp, ogen.cumulative_difference(x32, thr, op, ot, freq))
+    for op in (">", "<="):
+        got, names = _traced(dev, lambda: hgen.temperature_sum(x, op, thr, ta, freq, device=dev))
+        exp = ogen.temperature_sum(x, op, thr, ot, freq)
+        _bits(got, exp)
+        assert "xh_thresholded_reduce_f64" in names and "xh_thresholded_reduce" not in names
+        assert _differs(exp, ogen.temperature_sum(x32, op, thr, ot, freq))
+        for red in ("sum", "mean", "min", "max"):
+            got = hgen.thresholded_statistics(x, op, thr, red, ta, freq, device=dev)
+            exp = ogen.thresholded_statistics(x, op, thr, red, ot, freq)
+            _bits(got, exp)
+            assert _differs(exp, ogen.thresholded_statistics(x32, op, thr, red, ot, freq))
+    # the fused MissingAny count: the valid days of every period
+    _, val = hgen.cumulative_difference(x, thr, ">", ta, freq, device=dev, with_valid=True)
+    np.testing.assert_array_equal(val, ogen.select_resample_op(x, "count", ot, freq))
+
+
+# ---- 2. domain and bivariate counts -------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape", SHAPES)
+@pytest.mark.parametrize("calendar, freq", AXES)
+def test_domain_count_in_float64(dev, rng, native, shape, calendar, freq):
+    low, high = 1.0 / 86400.0, 2.5 / 86400.0
+    ta, ot = _axes(T2, calendar)
+    x = _near(rng, T2, shape, low, low)
+    at_high = _near(rng, T2, shape, high, 0.0, p_close=1.0, nan_frac=0.0)   # the upper edge too
+    sel = rng.random(x.shape) < 0.3
+    x[sel] = at_high[sel]
+    got, names = _traced(dev, lambda: hgen.domain_count(x, low, high, ta, freq, device=dev))
+    exp = ogen.domain_count(x, low, high, ot, freq)
+    np.testing.assert_array_equal(got, exp)
+    assert "xh_domain_count_f64" in names and "xh_domain_count" not in names
+    assert _differs(exp, ogen.domain_count(x.astype(np.float32), low, high, ot, freq))
+
+
+@pytest.mark.parametrize("shape", SHAPES)
+@pytest.mark.parametrize("calendar, freq", AXES)
+def test_bivariate_count_occurrences_in_float64_and_mixed_pairs(dev, rng, native, shape, calendar, freq):
+    t1, t2 = 283.15, 295.15
+    ta, ot = _axes(T2, calendar)
+    v1, v2 = _near(rng, T2, shape, t1, 2.0), _near(rng, T2, shape, t2, 2.0)
+    flipped = False
+    for a, b in ((v1, v2), (v1.astype(np.float32), v2), (v1, v2.astype(np.float32))):
+        for red, op1, op2 in (("all", ">", "<="), ("any", ">=", "<")):
+            got, names = _traced(dev, lambda: hgen.bivariate_count_occurrences(
+                data_var1=a, data_var2=b, threshold_var1=t1, threshold_var2=t2, time=ta, freq=freq, op_var1=op1, op_var2=op2,
+                var_reducer=red, device=dev))
+            exp = ogen.bivariate_count_occurrences(a, b, t1, t2, ot, freq, op1, op2, red)
+            np.testing.assert_array_equal(got, exp)
+            assert "xh_bivariate_count_f64" in names and "xh_bivariate_count" not in names
+            flipped |= _differs(exp, ogen.bivariate_count_occurrences(a.astype(np.float32), b.astype(np.float32), t1, t2, ot, freq,
+                                                                     op1, op2, red))
+    assert flipped
+    # the valid count: days on which both variables are present
+    _, val = hgen.bivariate_count_occurrences(data_var1=v1, data_var2=v2, threshold_var1=t1, threshold_var2=t2, time=ta, freq=freq,
+                                              op_var1=">", op_var2=">", var_reducer="all", device=dev, with_valid=True)
+    both = np.where(np.isnan(v1) | np.isnan(v2), np.nan, 0.0)
+    np.testing.assert_array_equal(val, ogen.select_resample_op(both, "count", ot, freq))
+
+
+# ---- 3. temperature ranges (xh_range_reduce_f64), float64 and mixed pairs ------------------------------------------------
+@pytest.mark.parametrize("shape", SHAPES)
+@pytest.mark.parametrize("calendar, freq", AXES)
+def test_temperature_ranges_in_float64_and_mixed_pairs(dev, rng, native, shape, calendar, freq):
+    ta, ot = _axes(T2, calendar)
+    lo = _near(rng, T2, shape, 280.0, 3.0)
+    hi = lo + 8.0 + rng.normal(0, 2.0, lo.shape)
+    hi[rng.random(hi.shape) < 0.02] = np.nan
+    for a, b in ((lo, hi), (lo.astype(np.float32), hi), (lo, hi.astype(np.float32))):
+        a32, b32 = a.astype(np.float32), b.astype(np.float32)
+        for red in ("max", "min", "mean", "sum"):
+            got, names = _traced(dev, lambda: hgen.diurnal_temperature_range(a, b, red, ta, freq, device=dev))
+            exp = ogen.diurnal_temperature_range(a, b, red, ot, freq)
+            _bits(got, exp)
+            assert "xh_range_reduce_f64" in names and "xh_range_reduce" not in names
+            assert _differs(exp, ogen.diurnal_temperature_range(a32, b32, red, ot, freq))
+        got = hgen.interday_diurnal_temperature_range(a, b, ta, freq, device=dev)
+        exp = ogen.interday_diurnal_temperature_range(a, b, ot, freq)
+        _bits(got, exp)   # diff drops day 0; the first day of a period differences against the day before it
+        assert _differs(exp, ogen.interday_diurnal_temperature_range(a32, b32, ot, freq))
+        got = hgen.extreme_temperature_range(a, b, ta, freq, device=dev)
+        exp = ogen.extreme_temperature_range(a, b, ot, freq)
+        _bits(got, exp)
+        assert _differs(exp, ogen.extreme_temperature_range(a32, b32, ot, freq))
+    _, val = hgen.extreme_temperature_range(lo, hi, ta, freq, device=dev, with_valid=True)
+    both = np.where(np.isnan(lo) | np.isnan(hi), np.nan, 0.0)
+    np.testing.assert_array_equal(val, ogen.select_resample_op(both, "count", ot, freq))
+
+
+# ---- 4. rolling statistics (xh_rolling_reduce_f64) ------------------------------------------------------------------------
+def _rolling_count(x, window, center):
+    T = x.shape[0]
+    left = window // 2 if center else window - 1
+    ok = ~np.isnan(x)
+    out = np.zeros(x.shape)
+    for t in range(T):
+        out[t] = ok[max(0, t - left): min(T, t - left + window)].sum(axis=0)
+    return out
+
+
+@pytest.mark.parametrize("shape", SHAPES)
+@pytest.mark.parametrize("window", [1, 3, 5, 8, 9, 31])
+def test_rolling_statistics_in_float64(dev, rng, native, shape, window):
+    x = _near(rng, T2, shape, 285.0, 1.0, nan_frac=0.004).reshape(T2, -1)
+    d = dev.to_device(x, dtype=np.float64)
+    flipped = False
+    for center in (True, False):
+        for red in ("sum", "mean", "min", "max", "std", "var", "count"):
+            got, names = _traced(dev, lambda: K.rolling_reduce(dev, d, window, red, center).get())
+            assert got.dtype == np.float64
+            assert "xh_rolling_reduce_f64" in names and "xh_rolling_reduce" not in names
+            if red == "count":
+                np.testing.assert_array_equal(got, _rolling_count(x, window, center))
+                continue
+            exp = ogen.rolling(x, window, red, center)
+            if red in ("std", "var"):
+                np.testing.assert_allclose(got, exp, rtol=1e-13, atol=0, equal_nan=True)
+            else:
+                np.testing.assert_array_equal(got, exp)   # bit for bit: the window added first row to last
+            flipped |= _differs(exp, ogen.rolling(x.astype(np.float32), window, red, center))
+    assert flipped
+
+
+@pytest.mark.parametrize("calendar, freq", AXES)
+def test_select_rolling_resample_op_in_float64(dev, rng, native, calendar, freq):
+    ta, ot = _axes(T2, calendar)
+    x = _near(rng, T2, (7, 151), 285.0, 1.0, nan_frac=0.004)
+    for window, center, wop, op in ((5, True, "mean", "max"), (9, False, "sum", "min"), (31, True, "max", "mean")):
+        got, names = _traced(dev, lambda: hgen.select_rolling_resample_op(x, op, window, ta, center, wop, freq, device=dev))
+        exp = ogen.select_rolling_resample_op(x, op, window, ot, center, wop, freq)
+        assert got.dtype == np.float64 and "xh_rolling_reduce_f64" in names and "xh_resample_reduce_f64" in names
+        if op == "mean":
+            np.testing.assert_allclose(got, exp, rtol=1e-13, equal_nan=True)
+        else:
+            np.testing.assert_array_equal(got, exp)
+        assert _differs(exp, ogen.select_rolling_resample_op(x.astype(np.float32), op, window, ot, center, wop, freq))
+    with pytest.raises(Float64FieldError, match="float64 fields are only served by"):   # select_time has no float64 kernel
+        hgen.select_rolling_resample_op(x, "max", 5, ta, freq=freq, device=dev, month=[6, 7, 8])
+
+
+# ---- 5. seasons, first days, occurrences and doymax on the existing float64 twins -----------------------------------------
+def _season_field(rng, T, shape, thr):
+    t = np.arange(T)[:, None, None]
+    x = thr + 8.0 * np.sin(2 * np.pi * (t - 100) / 365.0) + rng.normal(0, 2.0, (T,) + shape)
+    u32 = float(np.spacing(np.float32(thr)))
+    pick = rng.random(x.shape) < 0.3
+    x[pick] = rng.choice(np.array([thr, np.nextafter(thr, -np.inf), thr - 0.25 * u32, thr + 0.25 * u32]), int(pick.sum()))
+    x[rng.random(x.shape) < 0.003] = np.nan
+    return x
+
+
+def _to_doy(idx, seg, ta):
+    out = np.full(idx.shape, np.nan)
+    for p in range(idx.shape[0]):
+        ok = ~np.isnan(idx[p])
+        out[p][ok] = ta.doy[int(seg[p]) + idx[p][ok].astype(int)]
+    return out
+
+
+@pytest.mark.parametrize("shape", SHAPES)
+def test_season_first_day_and_occurrences_in_float64(dev, rng, native, shape):
+    thr = 278.15
+    T = 365 * 3
+    ta, ot = _axes(T)
+    seg, _ = ta.segments("YS")
+    x = _season_field(rng, T, shape, thr)
+    x32 = x.astype(np.float32)
+    res, names = _traced(dev, lambda: hgen.season(x, thr, 6, ">=", ta, "YS", "07-01", device=dev))
+    assert "xh_spell_mask_f64" in names and "xh_spell_mask" not in names
+    beg, end, length = orl.season_per_period(x >= thr, 6, "07-01", ot, "YS")
+    np.testing.assert_array_equal(res["length"], length)
+    np.testing.assert_array_equal(res["start"], _to_doy(beg, seg, ta))
+    np.testing.assert_array_equal(res["end"], _to_doy(end, seg, ta))
+    assert _differs(length, orl.season_per_period(x32 >= np.float32(thr), 6, "07-01", ot, "YS")[2])
+    # first_day_threshold_reached (first_day_temperature_above)
+    got, names = _traced(dev, lambda: hgen.first_day_threshold_reached(x, threshold=thr, op=">", after_date="03-01", time=ta, window=3,
+                                                                        device=dev))
+    assert "xh_spell_mask_f64" in names and "xh_spell_mask" not in names
+    first = lambda c: np.stack([orl.first_run_after_date(c[idx], 3, "03-01", ot.isel(idx)) for _, idx in orl.groups(ot, "YS")])
+    exp = first(x > thr)
+    np.testing.assert_array_equal(got, _to_doy(exp, seg, ta))
+    assert _differs(exp, first(x32 > np.float32(thr)))
+    # first / last occurrence
+    for last, fn in ((False, hgen.first_occurrence), (True, hgen.last_occurrence)):
+        got = fn(x, thr, ">", ta, "YS", device=dev)
+        idx = np.full((len(seg) - 1,) + shape, np.nan)
+        for p in range(len(seg) - 1):
+            c = x[seg[p]:seg[p + 1]] > thr
+            n = c.shape[0]
+            pos = (n - 1 - np.argmax(c[::-1], axis=0)) if last else np.argmax(c, axis=0)
+            idx[p] = np.where(c.any(axis=0), pos, np.nan)
+        np.testing.assert_array_equal(got, _to_doy(idx, seg, ta))
+
+
+def test_doymax_and_doymin_in_float64(dev, rng, native):
+    T = 365 * 3
+    ta, ot = _axes(T)
+    seg, _ = ta.segments("YS")
+    x = rng.normal(290.0, 3.0, (T, 3, 400))
+    for p in range(3):   # per period two days one float64 ulp apart: float32 makes them a tie (the first one wins)
+        a, b = seg[p] + 40, seg[p] + 200
+        x[a] = 320.0
+        x[b] = np.nextafter(320.0, np.inf)
+        x[a + 1] = 250.0
+        x[b + 1] = np.nextafter(250.0, -np.inf)
+    x[rng.random(x.shape) < 0.01] = np.nan
+    x[:, 0, 0] = np.nan
+    for which, fn, nanarg in (("max", hgen.doymax, np.nanargmax), ("min", hgen.doymin, np.nanargmin)):
+        got, names = _traced(dev, lambda: fn(x, ta, "YS", device=dev))
+        assert "xh_resample_reduce_f64" in names and "xh_resample_reduce" not in names
+
+        def expect(v):
+            out = np.full((3,) + v.shape[1:], np.nan)
+            for p in range(3):
+                g = v[seg[p]:seg[p + 1]]
+                alln = np.isnan(g).all(axis=0)
+                i = nanarg(np.where(alln, 0.0, g), axis=0)
+                ok = ~alln & (np.nanstd(np.where(alln[None], 0.0, g), axis=0) != 0)
+                out[p][ok] = ta.doy[int(seg[p]) + i[ok]]
+            return out
+        exp = expect(x)
+        np.testing.assert_array_equal(got, exp)
+        assert _differs(exp, expect(x.astype(np.float32)))
+
+
+# ---- the host indices: float64 results through the fused MissingAny mask (xh_apply_missing_mask, float64 values) -----------
+@pytest.mark.parametrize("shape", SHAPES)
+@pytest.mark.parametrize("calendar, freq", AXES)
+def test_degree_day_and_range_indices_with_their_missing_mask_in_float64(dev, rng, native, shape, calendar, freq):
+    """The indices hand the float64 device result and its valid count to the missing mask: the mask must read float64
+    values (it used to read every value buffer that was not int32 as float32)."""
+    ta, ot = _axes(T2, calendar)
+    tas = _near(rng, T2, shape, 283.15, 3.0, nan_frac=0.0005)   # a few NaN days: some periods masked, most kept
+    for fn, thr, op in ((xi.growing_degree_days, 283.15, ">"), (xi.cooling_degree_days, 291.15, ">"), (xi.heating_degree_days, 290.15, "<")):
+        got, names = _traced(dev, lambda: fn(tas, thr, ta, freq, device=dev))
+        assert "xh_thresholded_reduce_f64" in names and "xh_apply_missing_mask" in names
+        raw = ogen.cumulative_difference(tas, thr, op, ot, freq)
+        exp = oidx.apply_missing(raw, tas, ot, freq)
+        assert got.dtype == np.float64 and np.isfinite(exp).any() and np.isnan(exp).any()
+        np.testing.assert_array_equal(got, exp)
+        assert _differs(exp, oidx.apply_missing(ogen.cumulative_difference(tas.astype(np.float32), thr, op, ot, freq), tas, ot, freq))
+    got = xi.tg_mean(tas, ta, freq, device=dev)   # select_resample_op's float64 mean takes the same mask
+    np.testing.assert_allclose(got, oidx.apply_missing(ogen.select_resample_op(tas, "mean", ot, freq), tas, ot, freq), rtol=1e-13)
+    lo = tas
+    hi = lo + 8.0 + rng.normal(0, 2.0, lo.shape)
+    hi[rng.random(hi.shape) < 0.0005] = np.nan
+
+    def both(raw, a, b):
+        return oidx.apply_missing(oidx.apply_missing(raw, a, ot, freq), b, ot, freq)
+    for a, b in ((lo, hi), (lo.astype(np.float32), hi)):
+        for op in ("mean", "max"):
+            got = xi.daily_temperature_range(a, b, ta, freq, op, device=dev)
+            np.testing.assert_array_equal(got, both(ogen.diurnal_temperature_range(a, b, op, ot, freq), a, b))
+        got = xi.daily_temperature_range_variability(a, b, ta, freq, device=dev)
+        np.testing.assert_array_equal(got, both(ogen.interday_diurnal_temperature_range(a, b, ot, freq), a, b))
+        got, names = _traced(dev, lambda: xi.extreme_temperature_range(a, b, ta, freq, device=dev))
+        assert "xh_range_reduce_f64" in names
+        exp = both(ogen.extreme_temperature_range(a, b, ot, freq), a, b)
+        np.testing.assert_array_equal(got, exp)
+        assert np.isfinite(exp).any()
+
+
+# ---- 6. policy -------------------------------------------------------------------------------------------------------------
+def test_default_still_refuses_the_new_reductions(dev, rng, monkeypatch):
+    ta, _ = _axes(T2)
+    x = _near(rng, T2, (3, 4), 283.15, 2.0)
+    monkeypatch.delenv("XCLIM_AMD_FLOAT64", raising=False)
+    calls = [lambda: hgen.cumulative_difference(x, 283.15, ">", ta, "YS", device=dev),
+             lambda: hgen.domain_count(x, 280.0, 290.0, ta, "YS", device=dev),
+             lambda: hgen.extreme_temperature_range(x, x, ta, "YS", device=dev),
+             lambda: hgen.season(x, 283.15, 6, ">=", ta, "YS", device=dev),
+             lambda: hgen.select_rolling_resample_op(x, "max", 5, ta, device=dev)]
+    for call in calls:
+        with pytest.raises(Float64FieldError, match="float64 fields are only served by"):
+            call()
+    monkeypatch.setenv("XCLIM_AMD_FLOAT64", "native")
+    for call in calls:
+        call()
+
+
+# ---- 7. adapter ------------------------------------------------------------------------------------------------------------
+@pytest.fixture()
+def ref(dev):
+    env = fakexr.make_env()
+    mods = fakexr.make_reference_like_modules(env)
+    import xclim_amd._capi as capi
+
+    old = capi._default_device
+    capi._default_device = dev
+    patch.install(env, mods)
+    yield env, mods
+    patch.uninstall()
+    capi._default_device = old
+
+
+def test_degree_days_seasons_and_counts_on_float64_through_the_adapter(ref, dev, rng, monkeypatch):
+    env, mods = ref
+    th, gen = mods["xclim.indices._threshold"], mods["xclim.indices.generic"]
+    T = 365 * 3
+    ta, ot = _axes(T)
+    seg, _ = ta.segments("YS")
+    x = _season_field(rng, T, (3, 4), 278.15)
+    tas = fakexr.field(x, ta)
+    monkeypatch.setenv("XCLIM_AMD_FLOAT64", "native")
+    trace = dev.start_trace()
+    gdd = th.growing_degree_days(tas, thresh=283.15, freq="YS")
+    hdd = th.heating_degree_days(tas, thresh=290.15, freq="YS")
+    gsl = th.growing_season_length(tas, thresh=278.15, window=6, mid_date="07-01", freq="YS")
+    fda = th.first_day_temperature_above(tas, thresh=278.15, after_date="03-01", window=3, freq="YS")
+    pr = _near(rng, T, (3, 4), 1.0 / 86400.0, 2.0 / 86400.0)
+    pr = np.where(pr < 0, 0.0, pr)
+    prda = fakexr.field(pr, ta, attrs={"units": "kg m-2 s-1"})
+    dws = th.days_with_snow(prda, low=1.0 / 86400.0, high=20.0 / 86400.0, freq="YS")
+    tx = fakexr.field(x + 6.0, ta)
+    biv = gen.bivariate_count_occurrences(data_var1=tas, data_var2=tx, threshold_var1=278.15, threshold_var2=284.15, freq="MS",
+                                          op_var1=">", op_var2=">=", var_reducer="all")
+    dev.stop_trace()
+    names = [n for n, _ in trace]
+    for name in ("xh_thresholded_reduce_f64", "xh_spell_mask_f64", "xh_domain_count_f64", "xh_bivariate_count_f64"):
+        assert name in names and name[:-4] not in names
+    assert gdd.dtype == np.float64 and hdd.dtype == np.float64
+    np.testing.assert_array_equal(gdd.transpose("time", ...).values, ogen.cumulative_difference(x, 283.15, ">", ot, "YS"))
+    np.testing.assert_array_equal(hdd.transpose("time", ...).values, ogen.cumulative_difference(x, 290.15, "<", ot, "YS"))
+    np.testing.assert_array_equal(gsl.transpose("time", ...).values, orl.season_per_period(x >= 278.15, 6, "07-01", ot, "YS")[2])
+    first = np.stack([orl.first_run_after_date(x[idx] > 278.15, 3, "03-01", ot.isel(idx)) for _, idx in orl.groups(ot, "YS")])
+    np.testing.assert_array_equal(fda.transpose("time", ...).values, _to_doy(first, seg, ta))
+    np.testing.assert_array_equal(dws.transpose("time", ...).values, ogen.domain_count(pr, 1.0 / 86400.0, 20.0 / 86400.0, ot, "YS"))
+    np.testing.assert_array_equal(biv.transpose("time", ...).values,
+                                  ogen.bivariate_count_occurrences(x, x + 6.0, 278.15, 284.15, ot, "MS", ">", ">=", "all"))
+    monkeypatch.delenv("XCLIM_AMD_FLOAT64", raising=False)
+    with pytest.raises(AssertionError, match="was reached"):   # the reference's own cumulative_difference (a stub here)
+        th.growing_degree_days(tas, thresh=283.15, freq="YS")

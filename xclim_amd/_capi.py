@@ -47,7 +47,11 @@ FLOAT64_POLICIES = ("raise", "round", "native")
 
 # what XCLIM_AMD_FLOAT64=native serves with float64 kernels (xh_*_f64), on top of the four entry points that always do
 NATIVE_SERVED = ("compare, get_daily_events, spell_length_statistics, spell_mask, spell_length, the run-length indices "
-                 "(maximum_consecutive_*_days, hot / cold / dry / wet spells), warm / cold_spell_duration_index and percentile_doy")
+                 "(maximum_consecutive_*_days, hot / cold / dry / wet spells), warm / cold_spell_duration_index, percentile_doy, "
+                 "cumulative_difference, temperature_sum, thresholded_statistics (growing / heating / cooling degree days), season "
+                 "(growing / frost season start / end / length), first_day_threshold_reached, first / last_occurrence, domain_count, "
+                 "bivariate_count_occurrences, diurnal / interday_diurnal / extreme_temperature_range, "
+                 "select_rolling_resample_op (without an indexer) and doymax / doymin")
 
 
 def float64_policy() -> str:
@@ -181,6 +185,11 @@ SIGNATURES: dict[str, list] = {
     "xh_spell_run_stats_f64": [_vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _int, _dbl, _vp, _int, _vp, _int, _vp, _vp],
     "xh_run_stats_doy_f64": [_vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _int, _vp, _int, _int, _vp, _int, _vp, _vp],
     "xh_percentile_doy_f64": [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _int, _int, _int, _vp, _int, _dbl, _dbl, _vp],
+    "xh_thresholded_reduce_f64": [_vp, _vp, _i64, _i64, _i64, _i64, _int, _dbl, _int, _int, _vp, _int, _vp, _vp],
+    "xh_range_reduce_f64": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _int, _vp, _int, _vp, _vp],
+    "xh_domain_count_f64": [_vp, _vp, _i64, _i64, _i64, _i64, _int, _dbl, _int, _dbl, _int, _vp, _int, _vp, _vp],
+    "xh_bivariate_count_f64": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _dbl, _int, _dbl, _int, _vp, _int, _vp, _vp],
+    "xh_rolling_reduce_f64": [_vp, _vp, _i64, _i64, _i64, _i64, _int, _int, _int, _vp, _i64],
     "xh_weighted_quantile": [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _int, _vp],
     "xh_percentile_doy": [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _int, _int, _int, _vp, _int, _dbl, _dbl, _vp],
     "xh_percentile_doy_mapped": [_vp, _vp, _i64, _i64, _i64, _i64, _vp, _int, _int, _int, _vp, _int, _dbl, _dbl, _vp, _i64, _vp],

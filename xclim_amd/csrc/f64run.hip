@@ -14,55 +14,13 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "f64util.h"
 #include "runacc.h"
 
 namespace {
 
 template <int VEC>
-struct VD {
-  double v[VEC];
-};
-template <int VEC>
-__device__ __forceinline__ VD<VEC> ld2(const double* __restrict__ p) {
-  VD<VEC> r;
-  if (VEC == 2) {
-    const double2 t = *reinterpret_cast<const double2*>(p);
-    r.v[0] = t.x;
-    r.v[1 % VEC] = t.y;
-  } else {
-    r.v[0] = *p;
-  }
-  return r;
-}
-
-// rows [t0, t1) in double-buffered batches of 8, f(t, row)
-template <int VEC, typename F>
-__device__ __forceinline__ void march(const double* __restrict__ p, int64_t st, int64_t t0, int64_t t1, F&& f) {
-  constexpr int U = 8;
-  int64_t t = t0;
-  const int64_t nfull = t1 > t0 ? (t1 - t0) / U : 0;
-  if (nfull > 0) {
-    VD<VEC> buf[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) buf[u] = ld2<VEC>(p + (t + u) * st);
-    for (int64_t b = 0; b < nfull; ++b) {
-      VD<VEC> nxt[U];
-      const bool more = b + 1 < nfull;
-      if (more) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) nxt[u] = ld2<VEC>(p + (t + U + u) * st);
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) f(t + u, buf[u]);
-      if (more) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) buf[u] = nxt[u];
-      }
-      t += U;
-    }
-  }
-  for (; t < t1; ++t) f(t, ld2<VEC>(p + t * st));
-}
+using VD = VR<double, VEC>;
 
 // ---- compare ------------------------------------------------------------------------------------------------------
 // a op (b or thr) in float64; TA / TB are the element types of a and b (a float32 side is widened exactly, as numpy
@@ -437,13 +395,13 @@ k_run_stats_doy_f64(const double* __restrict__ x, int64_t C, int64_t st, int op,
 #pragma unroll
       for (int u = 0; u < 8; ++u) r[u] = tidx[t + u];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) xv[u] = ld2<VEC>(x + (t + u) * st + c);
+      for (int u = 0; u < 8; ++u) xv[u] = ldv<VEC>(x + (t + u) * st + c);
 #pragma unroll
-      for (int u = 0; u < 8; ++u) tv[u] = ld2<VEC>(table + (int64_t)r[u] * C + c);
+      for (int u = 0; u < 8; ++u) tv[u] = ldv<VEC>(table + (int64_t)r[u] * C + c);
 #pragma unroll
       for (int u = 0; u < 8; ++u) step(xv[u], tv[u]);
     }
-    for (; t < t1; ++t) step(ld2<VEC>(x + t * st + c), ld2<VEC>(table + (int64_t)tidx[t] * C + c));
+    for (; t < t1; ++t) step(ldv<VEC>(x + t * st + c), ldv<VEC>(table + (int64_t)tidx[t] * C + c));
     const int64_t o = (int64_t)p * C + c;
 #pragma unroll
     for (int i = 0; i < VEC; ++i) {
@@ -550,30 +508,6 @@ k_percentile_doy_f64(const double* __restrict__ x, int64_t T, int64_t C, int64_t
     }
     out[((int64_t)jq * ndoy + d) * C + c] = r;
   }
-}
-
-int check_field(const char* fn, xh_ctx* ctx, const void* x, int64_t T, int64_t C, int64_t st, int64_t sc) {
-  XH_REQUIRE(ctx && x, XH_ERR_ARG, "%s: NULL argument", fn);
-  XH_REQUIRE(T >= 0 && C >= 0, XH_ERR_ARG, "%s: negative shape", fn);
-  XH_REQUIRE(sc == 1 && st >= C, XH_ERR_LAYOUT, "%s: streaming kernels need a time-major view (sc == 1, st >= C); got st=%lld sc=%lld",
-             fn, (long long)st, (long long)sc);
-  return XH_OK;
-}
-
-int upload_segs(xh_ctx* ctx, size_t* cur, const int64_t* seg_off, int P, int64_t T, const char* fn, const int64_t** d_seg) {
-  XH_REQUIRE(seg_off && P >= 1, XH_ERR_ARG, "%s: seg_off NULL or P < 1", fn);
-  for (int p = 0; p < P; ++p)
-    XH_REQUIRE(seg_off[p] <= seg_off[p + 1] && seg_off[p] >= 0 && seg_off[p + 1] <= T, XH_ERR_ARG,
-               "%s: seg_off must be non-decreasing within [0, T]", fn);
-  void* d = nullptr;
-  const int rc = xh_scratch_upload(ctx, cur, seg_off, sizeof(int64_t) * (size_t)(P + 1), &d);
-  if (rc) return rc;
-  *d_seg = (const int64_t*)d;
-  return XH_OK;
-}
-
-inline int pick_vec(const void* p, int64_t C, int64_t st) {
-  return ((reinterpret_cast<uintptr_t>(p) & 15) == 0 && (C % 2) == 0 && (st % 2) == 0) ? 2 : 1;
 }
 
 inline int stat_group(int stat) {  // runacc.h: 1 max, 2 sum / count / mean / plain sum, 0 all

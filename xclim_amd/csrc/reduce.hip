@@ -256,7 +256,8 @@ k_apply_missing_mask(const void* __restrict__ value, int kind, const int32_t* __
   if (i >= n) return;
   int p = (int)(i / C);
   double v = kind == 0 ? (double)reinterpret_cast<const int32_t*>(value)[i]
-                       : (double)reinterpret_cast<const float*>(value)[i];
+             : kind == 1 ? (double)reinterpret_cast<const float*>(value)[i]
+                         : reinterpret_cast<const double*>(value)[i];  // 2: the float64 results of the _f64 twins
   out[i] = (valid[i] != expected[p]) ? xh_nan64() : v;
 }
 
@@ -446,7 +447,7 @@ int xh_resample_reduce(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_
 int xh_apply_missing_mask(xh_ctx* ctx, const void* value, int value_kind, const int32_t* valid, const int32_t* expected,
                           int P, int64_t C, double* out64) {
   XH_REQUIRE(ctx && value && valid && expected && out64, XH_ERR_ARG, "xh_apply_missing_mask: NULL argument");
-  XH_REQUIRE(value_kind == 0 || value_kind == 1, XH_ERR_ARG, "xh_apply_missing_mask: value_kind must be 0 or 1");
+  XH_REQUIRE(value_kind >= 0 && value_kind <= 2, XH_ERR_ARG, "xh_apply_missing_mask: value_kind must be 0, 1 or 2");
   XH_REQUIRE(P >= 1 && C >= 0, XH_ERR_ARG, "xh_apply_missing_mask: bad shape");
   size_t cur = 0;
   void* d_exp = nullptr;

@@ -117,7 +117,7 @@ def count_occurrences(da, threshold: float, op: str, time: TimeAxis, freq: str, 
 def domain_count(da, low: float, high: float, time: TimeAxis, freq: str, *, device=None, keep=False, with_valid=False):
     """gen:364-392: count of ``low < da <= high`` per period."""
     dev = device or get_device()
-    x, cell_shape = _flatten(da, dev)
+    x, cell_shape = _flatten(da, dev, f64=float64_native())  # native: xh_domain_count_f64
     seg, _ = time.segments(freq)
     cnt, val = K.domain_count(dev, x, ">", low, "<=", high, "and", seg)
     return _finish(cnt, val, cell_shape, keep, with_valid)
@@ -142,8 +142,8 @@ def bivariate_count_occurrences(*, data_var1, data_var2, threshold_var1: float, 
     if var_reducer not in ("all", "any"):
         raise ValueError(f"Unsupported value for var_reducer: {var_reducer}")
     dev = device or get_device()
-    a, cell_shape = _flatten(data_var1, dev)
-    b, _ = _flatten(data_var2, dev)
+    a, cell_shape = _flatten(data_var1, dev, f64=float64_native())  # native: xh_bivariate_count_f64 (also a float32 + float64 pair)
+    b, _ = _flatten(data_var2, dev, f64=float64_native())
     seg, _ = time.segments(freq)
     cnt, val = K.bivariate_count(dev, a, b, get_op(op_var1, constrain_var1), threshold_var1, get_op(op_var2, constrain_var2),
                                  threshold_var2, var_reducer, seg)
@@ -201,8 +201,8 @@ def get_daily_events(da, threshold, op: str, constrain=None, *, device=None, kee
 
 def _range(low_data, high_data, mode, reducer, time, freq, device, keep, with_valid):
     dev = device or get_device()
-    lo, cell_shape = _flatten(low_data, dev)
-    hi, _ = _flatten(high_data, dev)
+    lo, cell_shape = _flatten(low_data, dev, f64=float64_native())  # native: xh_range_reduce_f64 (also a float32 + float64 pair)
+    hi, _ = _flatten(high_data, dev, f64=float64_native())
     seg, _ = time.segments(freq)
     out, val = K.range_reduce(dev, lo, hi, mode, reducer, seg)
     return _finish(out, val, cell_shape, keep, with_valid)
@@ -231,7 +231,7 @@ def extreme_temperature_range(low_data, high_data, time: TimeAxis, freq: str, *,
 def _thresholded(data, op, threshold, mode, reducer, time, freq, constrain, device, keep, with_valid):
     sym = get_op(op, constrain)
     dev = device or get_device()
-    x, cell_shape = _flatten(data, dev)
+    x, cell_shape = _flatten(data, dev, f64=float64_native())  # native: xh_thresholded_reduce_f64
     seg, _ = time.segments(freq)
     out, val = K.thresholded_reduce(dev, x, sym, float(threshold), mode, reducer, seg)
     return _finish(out, val, cell_shape, keep, with_valid)
@@ -281,9 +281,13 @@ def select_resample_op(da, op: str, time: TimeAxis, freq: str = "YS", *, device=
 def select_rolling_resample_op(da, op: str, window: int, time: TimeAxis, window_center: bool = True,
                                window_op: str = "mean", freq: str = "YS", *, device=None, keep=False,
                                with_valid=False, **indexer):
-    """gen:128-174: rolling(window).window_op() then select_resample_op (``**indexer`` applies to the ROLLED series)."""
+    """gen:128-174: rolling(window).window_op() then select_resample_op (``**indexer`` applies to the ROLLED series).
+
+    Under XCLIM_AMD_FLOAT64=native a float64 field is rolled and reduced in float64 (xh_rolling_reduce_f64,
+    xh_resample_reduce_f64); with an ``**indexer`` it still raises Float64FieldError, because the time selection
+    (calendar.select_time) has no float64 kernel."""
     dev = device or get_device()
-    x, cell_shape = _flatten(da, dev)
+    x, cell_shape = _flatten(da, dev, f64=float64_native() and not indexer)
     rolled = K.rolling_reduce(dev, x, window, window_op, window_center)
     if indexer:
         from .calendar import select_time
@@ -479,7 +483,7 @@ def _occurrence(data, threshold, op, time, freq, constrain, device, last):
 
     sym = get_op(op, constrain)
     dev = device or get_device()
-    x, cell_shape = _flatten(data, dev)
+    x, cell_shape = _flatten(data, dev, f64=float64_native())  # native: the compare in float64 (xh_spell_mask_f64, window 1)
     cond = K.spell_mask(dev, x, 1, "min", sym, float(threshold))
     seg, _ = time.segments(freq)
     out, _ = K.run_stats(dev, cond, "last" if last else "first", 1, seg, cut=True, want_valid=False)
@@ -504,7 +508,7 @@ def first_day_threshold_reached(data, *, threshold: float, op: str, after_date: 
 
     sym = get_op(op, constrain)
     dev = device or get_device()
-    x, cell_shape = _flatten(data, dev)
+    x, cell_shape = _flatten(data, dev, f64=float64_native())  # native: the compare in float64 (xh_spell_mask_f64, window 1)
     cond = K.spell_mask(dev, x, 1, "min", sym, float(threshold))
     return hrl.first_run_after_date(cond.reshape((x.shape[0],) + tuple(cell_shape)), window, after_date, coord="dayofyear",
                                     time=time, freq=freq, device=dev)
@@ -522,7 +526,7 @@ def doymin(da, time: TimeAxis, freq: str = "YS", *, device=None):
 
 def _doy_extreme(da, time, freq, which, device):
     dev = device or get_device()
-    x, cell_shape = _flatten(da, dev)
+    x, cell_shape = _flatten(da, dev, f64=float64_native())  # native: argmax / argmin and std in float64 (xh_resample_reduce_f64)
     seg, _ = time.segments(freq)
     idx, _ = K.resample_reduce(dev, x, which, seg)
     std, _ = K.resample_reduce(dev, x, "std", seg, want_valid=False)
@@ -545,7 +549,7 @@ def season(data, thresh: float, window: int, op: str, time: TimeAxis, freq: str,
 
     sym = get_op(op)
     dev = device or get_device()
-    x, cell_shape = _flatten(data, dev)
+    x, cell_shape = _flatten(data, dev, f64=float64_native())  # native: the compare in float64 (xh_spell_mask_f64, window 1)
     cond = K.spell_mask(dev, x, 1, "min", sym, float(thresh))
     return hrl.season(cond.reshape((x.shape[0],) + tuple(cell_shape)), window, mid_date, time=time, freq=freq,
                       coord="dayofyear", device=dev)

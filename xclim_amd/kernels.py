@@ -125,11 +125,11 @@ def threshold_count(dev: Device, x: DeviceArray, op: str, seg_off, *, scalar=Non
 
 
 def domain_count(dev: Device, x: DeviceArray, op1, thr1, op2, thr2, combine, seg_off, want_valid=True):
-    T, C_ = _tc(x)
+    T, C_, f64 = _field(x)  # a float64 field compares in float64 (xh_domain_count_f64)
     seg, P = _seg(seg_off)
     count = dev.empty((P, C_), np.int32)
     valid = dev.empty((P, C_), np.int32) if want_valid else None
-    dev.call("xh_domain_count", _vp(x.ptr), T, C_, C_, 1, op_code(op1), float(thr1), op_code(op2), float(thr2),
+    dev.call("xh_domain_count_f64" if f64 else "xh_domain_count", _vp(x.ptr), T, C_, C_, 1, op_code(op1), float(thr1), op_code(op2), float(thr2),
              {"and": 1, "or": 2}[combine], np_ptr(seg), P, _vp(count.ptr), _vp(valid.ptr if valid else 0))
     return count, valid
 
@@ -153,15 +153,19 @@ def apply_missing_mask(dev: Device, value: DeviceArray, valid: DeviceArray, expe
     exp = np.ascontiguousarray(expected, dtype=np.int32)
     assert exp.shape == (P,)
     out = out if out is not None else dev.empty((P, C_), np.float64)
-    kind = 0 if value.dtype == np.int32 else 1
+    kinds = {np.dtype(np.int32): 0, np.dtype(np.float32): 1, np.dtype(np.float64): 2}  # float64: the results of the _f64 twins
+    if np.dtype(value.dtype) not in kinds:
+        raise TypeError(f"apply_missing_mask: values must be int32, float32 or float64, got {np.dtype(value.dtype).name}")
+    kind = kinds[np.dtype(value.dtype)]
     dev.call("xh_apply_missing_mask", _vp(value.ptr), kind, _vp(valid.ptr), np_ptr(exp), P, C_, _vp(out.ptr))
     return out
 
 
 def rolling_reduce(dev: Device, x: DeviceArray, window: int, reducer: str, center=True) -> DeviceArray:
-    T, C_ = _tc(x)
-    out = dev.empty((T, C_), np.float32)
-    dev.call("xh_rolling_reduce", _vp(x.ptr), T, C_, C_, 1, int(window), int(bool(center)), REDUCERS[reducer],
+    """xh_rolling_reduce; a float64 field gives a float64 result (xh_rolling_reduce_f64, the window added in float64)."""
+    T, C_, f64 = _field(x)
+    out = dev.empty((T, C_), np.float64 if f64 else np.float32)
+    dev.call("xh_rolling_reduce_f64" if f64 else "xh_rolling_reduce", _vp(x.ptr), T, C_, C_, 1, int(window), int(bool(center)), REDUCERS[reducer],
              _vp(out.ptr), C_)
     return out
 
@@ -210,26 +214,51 @@ def run_stats(dev: Device, x: DeviceArray, stat: str, window: int, seg_off, *, c
     return out, valid
 
 
+def _pair(a: DeviceArray, b: DeviceArray):
+    """(T, C, dtypes) of two fields of one shape: dtypes None for two float32 fields (the float32 kernel), else the `dtypes`
+    argument of the ``_f64`` twins (0: both float64, 1: the first float32, 2: the second float32)."""
+    assert b.shape == a.shape
+    T, C_ = _tc(a, None)
+    da, db = np.dtype(a.dtype), np.dtype(b.dtype)
+    for d in (da, db):
+        if d not in (np.float32, np.float64):
+            raise TypeError(f"expected a float32 or float64 device array, got {d.name}")
+    if da == np.float32 and db == np.float32:
+        return T, C_, None
+    return T, C_, 1 if da == np.float32 else (2 if db == np.float32 else 0)
+
+
 def bivariate_count(dev: Device, x1: DeviceArray, x2: DeviceArray, op1, thr1, op2, thr2, combine, seg_off, want_valid=True):
-    T, C_ = _tc(x1)
-    assert x2.shape == x1.shape
+    """A float64 field on either side: xh_bivariate_count_f64 (a float32 side compares against its threshold rounded to
+    float32, as numpy does with a python float)."""
+    T, C_, dtypes = _pair(x1, x2)
     seg, P = _seg(seg_off)
     count = dev.empty((P, C_), np.int32)
     valid = dev.empty((P, C_), np.int32) if want_valid else None
-    dev.call("xh_bivariate_count", _vp(x1.ptr), _vp(x2.ptr), T, C_, C_, C_, op_code(op1), float(thr1), op_code(op2), float(thr2),
-             {"all": 1, "and": 1, "any": 2, "or": 2}[combine], np_ptr(seg), P, _vp(count.ptr), _vp(valid.ptr if valid else 0))
+    comb = {"all": 1, "and": 1, "any": 2, "or": 2}[combine]
+    if dtypes is None:
+        dev.call("xh_bivariate_count", _vp(x1.ptr), _vp(x2.ptr), T, C_, C_, C_, op_code(op1), float(thr1), op_code(op2), float(thr2),
+                 comb, np_ptr(seg), P, _vp(count.ptr), _vp(valid.ptr if valid else 0))
+    else:
+        dev.call("xh_bivariate_count_f64", _vp(x1.ptr), _vp(x2.ptr), T, C_, C_, C_, dtypes, op_code(op1), float(thr1), op_code(op2),
+                 float(thr2), comb, np_ptr(seg), P, _vp(count.ptr), _vp(valid.ptr if valid else 0))
     return count, valid
 
 
 def range_reduce(dev: Device, low: DeviceArray, high: DeviceArray, mode: str, reducer: str, seg_off, want_valid=True):
-    """mode: "range" (reducer of high - low) | "interday" (mean |diff|) | "extreme" (max(high) - min(low))."""
-    T, C_ = _tc(low)
-    assert high.shape == low.shape
+    """mode: "range" (reducer of high - low) | "interday" (mean |diff|) | "extreme" (max(high) - min(low)).  A float64 field
+    on either side: xh_range_reduce_f64 (float64 result, a float32 side widened)."""
+    T, C_, dtypes = _pair(low, high)
     seg, P = _seg(seg_off)
-    out = dev.empty((P, C_), np.float32)
+    out = dev.empty((P, C_), np.float32 if dtypes is None else np.float64)
     valid = dev.empty((P, C_), np.int32) if want_valid else None
-    dev.call("xh_range_reduce", _vp(low.ptr), _vp(high.ptr), T, C_, C_, C_, {"range": 0, "interday": 1, "extreme": 2}[mode],
-             REDUCERS.get(reducer, 0), np_ptr(seg), P, _vp(out.ptr), _vp(valid.ptr if valid else 0))
+    m = {"range": 0, "interday": 1, "extreme": 2}[mode]
+    if dtypes is None:
+        dev.call("xh_range_reduce", _vp(low.ptr), _vp(high.ptr), T, C_, C_, C_, m, REDUCERS.get(reducer, 0), np_ptr(seg), P,
+                 _vp(out.ptr), _vp(valid.ptr if valid else 0))
+    else:
+        dev.call("xh_range_reduce_f64", _vp(low.ptr), _vp(high.ptr), T, C_, C_, C_, dtypes, m, REDUCERS.get(reducer, 0), np_ptr(seg),
+                 P, _vp(out.ptr), _vp(valid.ptr if valid else 0))
     return out, valid
 
 
@@ -293,11 +322,11 @@ def mask_to_f32(dev: Device, mask: DeviceArray) -> DeviceArray:
 
 
 def thresholded_reduce(dev: Device, x: DeviceArray, op, thr, mode: int, reducer: str, seg_off, want_valid=True):
-    T, C_ = _tc(x)
+    T, C_, f64 = _field(x)  # a float64 field: differences, sums and compares in float64, float64 result
     seg, P = _seg(seg_off)
-    out = dev.empty((P, C_), np.float32)
+    out = dev.empty((P, C_), np.float64 if f64 else np.float32)
     valid = dev.empty((P, C_), np.int32) if want_valid else None
-    dev.call("xh_thresholded_reduce", _vp(x.ptr), T, C_, C_, 1, op_code(op), float(thr), int(mode), REDUCERS.get(reducer, 0),
+    dev.call("xh_thresholded_reduce_f64" if f64 else "xh_thresholded_reduce", _vp(x.ptr), T, C_, C_, 1, op_code(op), float(thr), int(mode), REDUCERS.get(reducer, 0),
              np_ptr(seg), P, _vp(out.ptr), _vp(valid.ptr if valid else 0))
     return out, valid
 

@@ -1,0 +1,137 @@
+"""GPU parity of the one-year sliding percentile_doy kernel (k_pdoy_slide) and the fp64-table threshold count at cell counts
+that leave partial waves and workgroups: 4 cells per lane as two cell pairs, whole-line loads and stores, lanes past C kept
+alive; the 1-cell-per-lane fallback for misaligned buffers; both fast modes and the sorting path; NaN and infinite samples."""
+
+import numpy as np
+import pytest
+
+from oracle import calendar as ocal
+from oracle import generic as ogen
+from oracle import quantile as oq
+from oracle.timeutil import OTime
+from xclim_amd import kernels as K
+from xclim_amd.timeaxis import TimeAxis
+
+pytestmark = pytest.mark.gpu
+
+T = 365
+
+
+def _field(rng, C, nan_frac=0.01, specials=True):
+    t = np.arange(T)[:, None]
+    x = (288 + 12 * np.sin(2 * np.pi * (t - 100) / 365) + rng.normal(0, 3, (T, C))).astype(np.float32)
+    x[rng.random((T, C)) < nan_frac] = np.nan
+    if specials and C >= 8:
+        x[:, C // 2] = np.nan                      # all-NaN column
+        x[100:103, C // 3] = np.nan                # a window with 2 .. 5 NaNs
+        x[rng.random(T) < 0.05, C // 4] = np.inf   # +inf samples (an infinite maximum is its own nanmax)
+        x[rng.random(T) < 0.05, C - 1] = -np.inf   # -inf samples (an infinite minimum: the lerp is NaN -> nanmax)
+        x[::7, C - 2] = -np.inf
+    return x
+
+
+def _axes():
+    return TimeAxis.daily("2001-01-01", T, "noleap"), OTime.noleap(2001, T, "noleap")
+
+
+def _oracle(x, window, per):
+    ta, ot = _axes()
+    tb, years, doys = ta.doy_table()
+    C = x.shape[1]
+    rr = ocal.rolling_construct_center(x, window)
+    stack = np.full((len(doys), len(years), C, window), np.nan, dtype=np.float32)
+    stack[np.searchsorted(doys, ot.doy), np.searchsorted(years, ot.year)] = rr
+    stack = np.moveaxis(stack, 1, -2).reshape(len(doys), C, len(years) * window)
+    return np.moveaxis(oq.calc_perc(stack, per, 1 / 3, 1 / 3), -1, 0)  # (nper, ndoy, C)
+
+
+def _pdoy(dev, xd, window, per, out=None):
+    ta, _ = _axes()
+    tb, _, _ = ta.doy_table()
+    return K.percentile_doy(dev, xd, tb, window, per, out=out).get()
+
+
+@pytest.mark.parametrize("C", [1, 2, 3, 255, 256, 257, 511, 1000, 1026, 65537])
+def test_slide_partial_waves_and_blocks(dev, rng, C):
+    x = _field(rng, C)
+    got = _pdoy(dev, dev.to_device(x), 5, [90.0])
+    np.testing.assert_array_equal(got, _oracle(x, 5, [90.0]))
+
+
+@pytest.mark.parametrize("window", [3, 5, 7])
+@pytest.mark.parametrize("per", [[90.0], [50.0], [5.0], [1.0, 5.0, 10.0, 25.0, 50.0, 75.0, 90.0, 99.0]])
+@pytest.mark.parametrize("C", [258, 1030])
+def test_slide_windows_percentiles_and_specials(dev, rng, window, per, C):
+    """per 90 / 5 with a full window clip to the maximum / minimum (fast modes 1 / 2), per 50 and nper 8 sort."""
+    x = _field(rng, C, nan_frac=0.02)
+    got = _pdoy(dev, dev.to_device(x), window, per)
+    np.testing.assert_array_equal(got, _oracle(x, window, per))
+
+
+def test_slide_all_nan_and_nan_free_waves(dev, rng):
+    """Whole waves without a NaN take the wave-uniform paths, a wave with one NaN column the per-lane path."""
+    C = 1024 + 256 + 2
+    x = _field(rng, C, nan_frac=0.0, specials=False)
+    x[:, 256:512] = np.nan
+    x[40:45, 700] = np.nan
+    for per in ([90.0], [5.0], [50.0]):
+        np.testing.assert_array_equal(_pdoy(dev, dev.to_device(x), 5, per), _oracle(x, 5, per))
+
+
+@pytest.mark.parametrize("x_off,out_off", [(4, 0), (8, 0), (0, 8), (4, 8)])
+def test_slide_misaligned_buffers(dev, rng, x_off, out_off):
+    """x 4 bytes off (1 cell per lane), x 8 bytes off (pairs need 8 bytes only), out 8 bytes off (1 cell per lane):
+    bit-identical to the aligned call and to the oracle."""
+    C, per = 1030, [5.0, 50.0, 90.0]
+    x = _field(rng, C)
+    ref = _pdoy(dev, dev.to_device(x), 5, per)
+    np.testing.assert_array_equal(ref, _oracle(x, 5, per))
+    pad = x_off // 4
+    big = np.zeros(T * C + 4, np.float32)
+    big[pad: pad + T * C] = x.reshape(-1)
+    dbig = dev.to_device(big)
+    xv = dev.wrap(dbig.ptr + x_off, (T, C), np.float32)
+    obig = dev.empty((len(per) * T * C + 2,), np.float64)
+    ov = dev.wrap(obig.ptr + out_off, (len(per), T, C), np.float64)
+    got = _pdoy(dev, xv, 5, per, out=ov)
+    np.testing.assert_array_equal(got, ref)
+
+
+@pytest.mark.parametrize("C", [1, 3, 255, 257, 511, 1000, 65537])
+def test_threshold_count_f64_tables_odd_cells(dev, rng, C):
+    ta, ot = _axes()
+    x = _field(rng, C)
+    seg, _ = ta.segments("MS")
+    table = 288 + 12 * np.sin(2 * np.pi * (np.arange(365)[:, None] - 100) / 365) + rng.normal(0, 1, (365, C))
+    table[:, :: 5] = np.round(table[:, :: 5] * 2) / 2        # thresholds equal to samples
+    x[:, :: 5] = np.round(x[:, :: 5] * 2) / 2
+    tidx = (ta.doy - 1).astype(np.int32)
+    d = dev.to_device(x)
+    for op in (">", "<="):
+        exp = ogen.threshold_count(x, op, table[tidx], ot, "MS")
+        c1, v1 = K.threshold_count(dev, d, op, seg, doy_table=dev.to_device(table), tidx=tidx)
+        c2, v2 = K.threshold_count(dev, d, op, seg, full=dev.to_device(table[tidx]))
+        np.testing.assert_array_equal(c1.get(), exp)
+        np.testing.assert_array_equal(c2.get(), exp)
+        np.testing.assert_array_equal(v1.get(), v2.get())
+        np.testing.assert_array_equal(v1.get(), ogen.select_resample_op(x, "count", ot, "MS"))
+
+
+@pytest.mark.parametrize("C", [3, 257, 1000, 1026])
+@pytest.mark.parametrize("per,op", [(90.0, ">"), (5.0, "<"), (50.0, ">=")])
+def test_percentile_doy_count_one_year(dev, rng, C, per, op):
+    """xh_percentile_doy_count (k_pdoy_slide<.., COUNT>) = percentile_doy -> threshold_count on the same year."""
+    ta, _ = _axes()
+    x = _field(rng, C)
+    tb, _, doys = ta.doy_table()
+    seg, _ = ta.segments("MS")
+    P = len(seg) - 1
+    tidx = np.searchsorted(doys, ta.doy).astype(np.int32)
+    xd = dev.to_device(x)
+    p = K.percentile_doy(dev, xd, tb, 5, [per])
+    cnt, val = K.threshold_count(dev, xd, op, seg, doy_table=p.reshape(len(doys), C), tidx=tidx)
+    period = (np.searchsorted(seg, tb, side="right") - 1).astype(np.int32)
+    fused = K.percentile_doy_count(dev, xd, tb, 5, per, op, period, P)
+    assert fused is not None
+    np.testing.assert_array_equal(fused[0].get(), cnt.get())
+    np.testing.assert_array_equal(fused[1].get(), val.get())

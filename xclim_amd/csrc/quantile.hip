@@ -177,8 +177,24 @@ k_pdoy_slide(const float* __restrict__ x, int64_t T, int64_t C, int64_t st, int6
   __shared__ QTab s_tab[8 * (W + 1)];
   for (int i = threadIdx.x; i < nper * (W + 1); i += XH_BLOCK) s_tab[i] = qtab[i];
   __syncthreads();
-  int64_t c = ((int64_t)blockIdx.x * XH_BLOCK + threadIdx.x) * VEC;
-  if (c >= C) return;
+  // Cells of a lane.  VEC = 4: lane l owns the cell PAIRS {2l, 2l+1} and {128+2l, 129+2l} of its wave's 256 cells, so every
+  // wave load reads 512 contiguous bytes and every double2 store writes 1 KiB contiguous — whole 128-byte lines per
+  // instruction (4 consecutive cells per lane wrote every other 16 bytes of a 2 KiB span per store: 0.96 -> 0.85 ms for
+  // this kernel's traffic, tools/mix_ubench.hip).  VEC = 1: one cell per lane.  A wave past C leaves; the other lanes
+  // stay (a pair past C reads the row's last pair and stores nothing), so the wave-wide votes below see whole waves.
+  constexpr int NP = VEC == 4 ? 2 : 1;  // cell groups per lane (pairs, or the one cell)
+  constexpr int GW = VEC == 4 ? 2 : 1;  // cells per group
+  const int lane = threadIdx.x & 63;
+  const int64_t wbase = ((int64_t)blockIdx.x * XH_BLOCK + (threadIdx.x & ~63)) * VEC;
+  if (wbase >= C) return;
+  int64_t cg[NP];
+  bool okg[NP];
+#pragma unroll
+  for (int g = 0; g < NP; ++g) {
+    cg[g] = wbase + (VEC == 4 ? 2 * lane + 128 * g : lane);
+    okg[g] = cg[g] < C;  // (VEC = 4: C is even, a pair is whole or absent)
+  }
+  auto cell = [&](int v) -> int64_t { return cg[v / GW] + v % GW; };
   constexpr int half = W / 2;
   int d0 = blockIdx.y * chunk, d1 = d0 + chunk;
   if (d1 > ndoy) d1 = ndoy;
@@ -194,7 +210,15 @@ k_pdoy_slide(const float* __restrict__ x, int64_t T, int64_t C, int64_t st, int6
   // vmcnt(0)) and one doy AHEAD of their use, so the row of doy d+1 is in flight while doy d is selected and stored
   auto fetch = [&](int64_t t) -> VecF<VEC> {
     const int64_t tc = t < 0 ? 0 : (t >= T ? T - 1 : t);
-    return xh_load<VEC>(x + tc * st + c);
+    const float* row = x + tc * st;
+    VecF<VEC> r;
+#pragma unroll
+    for (int g = 0; g < NP; ++g) {
+      const VecF<GW> h = xh_load<GW>(row + (okg[g] ? cg[g] : C - GW));
+#pragma unroll
+      for (int k = 0; k < GW; ++k) r.v[(g * GW + k) % VEC] = h.v[k];
+    }
+    return r;
   };
   int ccnt[VEC], cval[VEC], cper = -1;
 #pragma unroll
@@ -203,8 +227,8 @@ k_pdoy_slide(const float* __restrict__ x, int64_t T, int64_t C, int64_t st, int6
     if (cper >= 0) {
 #pragma unroll
       for (int v = 0; v < VEC; ++v) {
-        if (ccnt[v]) atomicAdd(&cnt_out[(int64_t)cper * C + c + v], ccnt[v]);
-        if (valid_out && cval[v]) atomicAdd(&valid_out[(int64_t)cper * C + c + v], cval[v]);
+        if (ccnt[v] && okg[v / GW]) atomicAdd(&cnt_out[(int64_t)cper * C + cell(v)], ccnt[v]);
+        if (valid_out && cval[v] && okg[v / GW]) atomicAdd(&valid_out[(int64_t)cper * C + cell(v)], cval[v]);
         ccnt[v] = 0; cval[v] = 0;
       }
     }
@@ -221,13 +245,14 @@ k_pdoy_slide(const float* __restrict__ x, int64_t T, int64_t C, int64_t st, int6
         cval[v] += (xv == xv) ? 1 : 0;
       }
     } else {
-      double* optr = out + ((int64_t)j * ndoy + d) * C + c;
-      if (VEC == 4) {
-        *reinterpret_cast<double2*>(optr) = make_double2(r[0], r[1 % VEC]);
-        *reinterpret_cast<double2*>(optr + 2) = make_double2(r[2 % VEC], r[3 % VEC]);
-      } else {
+      double* orow = out + ((int64_t)j * ndoy + d) * C;
 #pragma unroll
-        for (int v = 0; v < VEC; ++v) optr[v] = r[v];
+      for (int g = 0; g < NP; ++g) {
+        if (!okg[g]) continue;
+        if (VEC == 4)
+          *reinterpret_cast<double2*>(orow + cg[g]) = make_double2(r[(2 * g) % VEC], r[(2 * g + 1) % VEC]);
+        else
+          orow[cg[g]] = r[0];
       }
     }
   };
@@ -371,6 +396,13 @@ k_pdoy_slide(const float* __restrict__ x, int64_t T, int64_t C, int64_t st, int6
     if (W > 6 && d + 6 < d1) step(d + 6, std::integral_constant<int, 6 % W>{});
   }
   if (COUNT) flush_counts();
+}
+
+// Cells per lane of k_pdoy_slide: 4 (two float2 loads per row, two double2 stores per doy) needs 8-byte aligned rows of an
+// even number of cells and a 16-byte aligned output (out == NULL: the COUNT variant stores nothing), else 1.
+static int slide_vec(const float* x, int64_t C, int64_t st, const double* out) {
+  if ((reinterpret_cast<uintptr_t>(x) & 7) != 0 || (C % 2) != 0 || (st % 2) != 0) return 1;
+  return (reinterpret_cast<uintptr_t>(out) & 15) == 0 ? 4 : 1;
 }
 
 // Host side of the table: one entry per (percentile j, valid count n), mirroring xh_hf_quantile.
@@ -779,8 +811,7 @@ static int pdoy_impl(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t 
     if (rc) return rc;
     int chunk = 32;
     if (const char* e = xh_diag_env("XH_PDOY_SLIDE_CHUNK")) chunk = atoi(e) > 0 ? atoi(e) : chunk;  // diagnostics
-    int vec = xh_pick_vec(x, C, st);
-    if ((reinterpret_cast<uintptr_t>(out) & 15) != 0) vec = 1;
+    const int vec = slide_vec(x, C, st, out);
     dim3 grid((unsigned)cdiv64(cdiv64(C, vec), XH_BLOCK), (unsigned)((ndoy + chunk - 1) / chunk));
 #define XH_SLIDE(W, V)                                                                                              \
   hipLaunchKernelGGL((k_pdoy_slide<W, V>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, T, C, st, (int64_t)tbase[0], ndoy, \
@@ -947,7 +978,7 @@ static int pdoy_count_impl(xh_ctx* ctx, const float* x, int64_t T, int64_t C, in
   if (valid_out) XH_CHECK_HIP(hipMemsetAsync(valid_out, 0, sizeof(int32_t) * (size_t)P * (size_t)C, ctx->stream));
   int chunk = 61;  // doys per workgroup (W - 1 halo rows each): 16 / 32 / 46 / 61 / 92 / 183 -> 0.61 / 0.57 / 0.56 / 0.54 / 0.55 / 0.56 ms
   if (const char* e = xh_diag_env("XH_PDOY_SLIDE_COUNT_CHUNK")) chunk = atoi(e) > 0 ? atoi(e) : chunk;  // diagnostics
-  const int vec = xh_pick_vec(x, C, st);
+  const int vec = slide_vec(x, C, st, nullptr);
   dim3 grid((unsigned)cdiv64(cdiv64(C, vec), XH_BLOCK), (unsigned)((ndoy + chunk - 1) / chunk));
 #define XH_SLIDEC(W, V)                                                                                                   \
   hipLaunchKernelGGL((k_pdoy_slide<W, V, true>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, T, C, st, (int64_t)tbase[0], ndoy, \

@@ -672,6 +672,50 @@ int xh_trend_apply_groups(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int
                           const int64_t* offs /* host */, int G, const double* u, const double* p0, const double* p1, int mode,
                           float* out, int64_t out_st);
 
+
+/* ---- Canadian Forest Fire Weather Index System (indices/fire/_cffwis.py) ----------------------------------------- */
+/* xh_fire_weather: the whole of _fire_weather_calc (_cffwis.py:655-880) in one launch, one lane per cell.
+ *   Fields (T, C) float32 with row stride st (DEVICE): tas [degC], pr [mm/day], hurs [%], sfcwind [km/h], snd [m] (LA08 /
+ *   GFWED seasons only); NULL where no requested output or season method reads them.  month (HOST, T): 1..12 per row.
+ *   lat (DEVICE float64, C).  dc0 / dmc0 / ffmc0 / winter_pr (DEVICE float32, C, NaN = not given; NULL = all NaN, winter_pr
+ *   NULL = 0).  season_mask (DEVICE uint8 (T, C), row stride st_mask) for XH_FIRE_SEASON_MASK.
+ *   params (HOST, XH_FIRE_NPARAM doubles, indices XH_FIRE_*): thresholds and start values of default_params (:162-179).
+ *   outputs (HOST, 7 device pointers DC DMC FFMC ISI BUI FWI DSR, (T, C) float32 with row stride st_out; NULL = not
+ *   requested; an index needs the codes it derives from).  season_mask_out (uint8 (T, C), st_out) and winter_pr_out (C)
+ *   may be NULL.  XH_ERR_NOTIMPL (no error text) for XH_FIRE_DRY_GFWED_SNOW and GFWED condition windows over 7 days;
+ *   XH_ERR_ARG "Invalid lat specified." when DC, or DMC with a known previous value, meets a latitude outside [-90, 90]. */
+#define XH_FIRE_SEASON_NONE 0
+#define XH_FIRE_SEASON_MASK 1
+#define XH_FIRE_SEASON_WF93 2
+#define XH_FIRE_SEASON_LA08 3
+#define XH_FIRE_SEASON_GFWED 4
+#define XH_FIRE_DRY_NONE 0
+#define XH_FIRE_DRY_CFS 1
+#define XH_FIRE_DRY_GFWED 2
+#define XH_FIRE_DRY_GFWED_SNOW 3
+#define XH_FIRE_TEMP_START 0
+#define XH_FIRE_TEMP_END 1
+#define XH_FIRE_SNOW 2
+#define XH_FIRE_PREC 3
+#define XH_FIRE_CARRY_OVER 4
+#define XH_FIRE_WETTING_EFF 5
+#define XH_FIRE_DC_START 6
+#define XH_FIRE_DMC_START 7
+#define XH_FIRE_FFMC_START 8
+#define XH_FIRE_DC_DRY 9
+#define XH_FIRE_DMC_DRY 10
+#define XH_FIRE_NPARAM 11
+int xh_fire_weather(xh_ctx* ctx, int64_t T, int64_t C, int64_t st, const float* tas, const float* pr, const float* hurs,
+                    const float* sfcwind, const float* snd, const int32_t* month /* host */, const double* lat, const float* dc0,
+                    const float* dmc0, const float* ffmc0, const float* winter_pr, const uint8_t* season_mask,
+                    int64_t st_mask, int season_method, int temp_condition_days, int snow_condition_days, int overwintering,
+                    int dry_start, int initial_start_up, const double* params /* host */, float* const* outputs /* host */,
+                    int64_t st_out, uint8_t* season_mask_out, float* winter_pr_out);
+/* overwintering_drought_code (_cffwis.py:530-568, public form :1054-1104): out[i] from last_dc[i], winter_pr[i] [mm]
+ * (DEVICE float32, n), float64 arithmetic, NaN in either -> NaN. */
+int xh_overwintering_dc(xh_ctx* ctx, const float* last_dc, const float* winter_pr, int64_t n, double carry_over_fraction,
+                        double wetting_efficiency_fraction, double min_dc, float* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,276 @@
+"""The fire weather system on the device (xh_fire_weather, xclim_amd.fire) against the reference's own outputs
+(tests/golden/fire_vectors.npz) and, for fields larger than the golden cases, against the numpy restatement
+tests/firecpu.py; the adapter (patch.install) through a stand-in ``xclim.indices.fire._cffwis`` module."""
+
+import types
+
+import numpy as np
+import pytest
+
+import fakexr
+import firecpu
+from test_fire_cpu import CASES, check_outputs, golden_case
+from xclim_amd import fire, patch
+from xclim_amd import kernels as K
+from xclim_amd.timeaxis import TimeAxis
+
+pytestmark = pytest.mark.gpu
+
+
+def _kernel_run(dev, inp, P, tas_view=None):
+    """xh_fire_weather on a golden case through kernels.fire_weather (every season / dry-start combination)."""
+    fields = {k: dev.to_device(inp[k]) for k in ("tas", "pr", "hurs", "sfcWind", "snd")}
+    if tas_view is not None:
+        fields["tas"] = tas_view
+    cells = lambda a: dev.to_device(np.ascontiguousarray(a, dtype=np.float32))  # noqa: E731
+    starts = {"dc0": cells(inp["dc0"]), "dmc0": cells(inp["dmc0"]), "ffmc0": cells(inp["ffmc0"])}
+    if P["overwintering"]:
+        starts["winter_pr"] = cells(inp["winter_pr_in"])
+    sm = P["season_method"]
+    mask = dev.to_device(inp["season_mask"].astype(np.uint8)) if sm == "mask" else None
+    outs = K.fire_weather(dev, fields, inp["month"], dev.to_device(inp["lat"].astype(np.float64)), starts, P["indexes"], P,
+                          season_method=sm, season_mask=mask, overwintering=P["overwintering"], dry_start=P["dry_start"],
+                          initial_start_up=P["initial_start_up"], want_mask=sm not in (None, "mask"),
+                          want_winter_pr=P["overwintering"])
+    return {k: v.get() for k, v in outs.items()}
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_device_matches_reference(dev, name):
+    inp, P, exp = golden_case(name)
+    check_outputs(_kernel_run(dev, inp, P), exp)
+
+
+def _time_for(month, T):
+    return TimeAxis.daily(f"2001-{int(month[0]):02d}-01", T, "noleap")
+
+
+def _public(name):
+    """GFWED dry starts with a snow season are GFWED+SNOW in the public API (out of scope): kernel-level cases only."""
+    P = golden_case(name)[1]
+    return not (P["season_method"] in ("LA08", "GFWED") and P["dry_start"] == "GFWED")
+
+
+@pytest.mark.parametrize("name", [c for c in CASES if _public(c)])
+def test_host_api_matches_reference(dev, name):
+    """xclim_amd.fire.fire_weather_ufunc (time first, TimeAxis months) on the cases its public arguments can express."""
+    inp, P, exp = golden_case(name)
+    T = inp["tas"].shape[0]
+    kw = {k: P[k] for k in firecpu.DEFAULTS}
+    out = fire.fire_weather_ufunc(tas=inp["tas"], pr=inp["pr"], hurs=inp["hurs"], sfcWind=inp["sfcWind"],
+                                  snd=inp["snd"] if P["season_method"] in ("LA08", "GFWED") else None, lat=inp["lat"],
+                                  dc0=inp["dc0"], dmc0=inp["dmc0"], ffmc0=inp["ffmc0"],
+                                  winter_pr=inp["winter_pr_in"] if P["overwintering"] else None,
+                                  season_mask=inp.get("season_mask"), indexes=P["indexes"],
+                                  season_method=None if P["season_method"] == "mask" else P["season_method"],
+                                  overwintering=P["overwintering"], dry_start=P["dry_start"],
+                                  initial_start_up=P["initial_start_up"], time=_time_for(inp["month"], T), device=dev, **kw)
+    check_outputs(out, exp)
+
+
+def _weather(rng, T, C, nan_frac=0.0):
+    t = np.arange(T)[:, None]
+    tas = rng.uniform(-4, 12, C) + rng.uniform(8, 18, C) * np.sin(2 * np.pi * (t - 105) / 365.0) + rng.normal(0, 3.5, (T, C))
+    pr = np.where(rng.random((T, C)) < 0.35, rng.gamma(0.7, 6.0, (T, C)), 0.0)
+    hurs = np.clip(rng.normal(65, 18, (T, C)) + 2 * pr, 5, 100)
+    ws = np.abs(rng.normal(12, 7, (T, C)))
+    snd = np.clip(0.4 * np.cos(2 * np.pi * (t - 20) / 365.0) - 0.05 + rng.normal(0, 0.05, (T, C)), 0, None)
+    out = [np.ascontiguousarray(a, dtype=np.float32) for a in (tas, pr, hurs, ws, snd)]
+    if nan_frac:
+        for a in out[:4]:
+            a[rng.random(a.shape) < nan_frac] = np.nan
+    return out
+
+
+def _cpu(inp, month, lat, **kw):
+    return firecpu.fire_weather(*inp, month, lat, **kw)
+
+
+@pytest.mark.parametrize("T,C", [(1, 1), (1, 300), (2, 63), (37, 65), (40, 257), (400, 1001)])
+@pytest.mark.parametrize("mode", ["none", "wf93_ow", "gfwed"])
+def test_partial_waves_odd_cells_short_series(dev, T, C, mode):
+    rng = np.random.default_rng(T * 1000 + C)
+    inp = _weather(rng, T, C, nan_frac=0.002)
+    time = TimeAxis.daily("2001-03-01", T, "noleap")
+    lat = rng.uniform(-90, 90, C)
+    kw = {"none": {}, "wf93_ow": dict(season_method="WF93", overwintering=True, dry_start="CFS"),
+          "gfwed": dict(season_method="GFWED", temp_condition_days=2, snow_condition_days=4)}[mode]
+    exp = _cpu(inp, time.month, lat, **kw)
+    got = fire.fire_weather_ufunc(tas=inp[0], pr=inp[1], hurs=inp[2], sfcWind=inp[3],
+                                  snd=inp[4] if mode == "gfwed" else None, lat=lat, time=time, device=dev, **kw)
+    check_outputs(got, exp)
+
+
+def test_misaligned_views(dev):
+    """Fields at a 4-byte offset inside a larger device buffer."""
+    inp, P, exp = golden_case("wf93_overwinter")
+    T, C = inp["tas"].shape
+    big = dev.to_device(np.concatenate([np.zeros(1, np.float32), inp["tas"].reshape(-1)]))
+    view = dev.wrap(big.ptr + 4, (T, C), np.float32)
+    check_outputs(_kernel_run(dev, inp, P, tas_view=view), exp)
+
+
+def test_fuzz_ten_years(dev):
+    """Seeded 10-year x 2000-cell field with NaNs, WF93 season, overwintering and the CFS dry start."""
+    rng = np.random.default_rng(7)
+    T, C = 3650, 2000
+    inp = _weather(rng, T, C, nan_frac=0.0005)
+    time = TimeAxis.daily("2001-01-01", T, "noleap")
+    lat = rng.uniform(-90, 90, C)
+    kw = dict(season_method="WF93", overwintering=True, dry_start="CFS", indexes=list(firecpu.INDEXES))
+    exp = _cpu(inp, time.month, lat, **kw)
+    got = fire.fire_weather_ufunc(tas=inp[0], pr=inp[1], hurs=inp[2], sfcWind=inp[3], lat=lat, time=time, device=dev, **kw)
+    check_outputs(got, exp)
+
+
+def test_full_size_sampled(dev):
+    """365 x 1440 x 720 (1 036 800 cells) in one launch; 2000 sampled cells checked against firecpu."""
+    T, C = 365, 1440 * 720
+    rng = np.random.default_rng(11)
+    t = np.arange(T)
+    base = (8 + 12 * np.sin(2 * np.pi * (t - 105) / 365.0)).astype(np.float32)
+    flds = [K.fill_synthetic(dev, T, C, 0, 1, base, 6.0), K.fill_synthetic(dev, T, C, 1, 2, np.zeros(T, np.float32), 12.0, 0.35),
+            K.fill_synthetic(dev, T, C, 0, 3, np.full(T, 60.0, np.float32), 30.0),
+            K.fill_synthetic(dev, T, C, 0, 4, np.full(T, 14.0, np.float32), 10.0)]
+    lat = np.linspace(-89.9, 89.9, 720)[:, None] * np.ones((1, 1440))
+    time = TimeAxis.daily("2001-01-01", T, "noleap")
+    outs = fire.fire_weather_ufunc(tas=flds[0], pr=flds[1], hurs=flds[2], sfcWind=flds[3], lat=lat.reshape(-1),
+                                   time=time, device=dev, keep=True)
+    cols = np.sort(rng.choice(C, 2000, replace=False))
+    inp = [f.get()[:, cols] for f in flds]
+    exp = _cpu(inp + [None], time.month, lat.reshape(-1)[cols])
+    got = {k: v.get()[:, cols] for k, v in outs.items()}
+    check_outputs(got, exp)
+
+
+def test_fire_season_and_longest_run(dev):
+    rng = np.random.default_rng(3)
+    T, C = 365 * 3, 333
+    inp = _weather(rng, T, C)
+    time = TimeAxis.daily("2001-01-01", T, "noleap")
+    for method in ("WF93", "LA08", "GFWED"):
+        exp = firecpu.fire_season(inp[0], inp[4], method, 12.0, 5.0, 0.01, 3, 3)
+        got = fire.fire_season(inp[0], snd=inp[4], method=method, time=time, device=dev)
+        np.testing.assert_array_equal(got, exp, err_msg=method)
+    got = fire.fire_season(inp[0], method="WF93", freq="YS", time=time, device=dev)
+    exp = firecpu.fire_season(inp[0], None, "WF93", 12.0, 5.0, 0.01, 3, 3)
+    for y in range(3):  # every year on its own keeps its first longest run (a year without a run: its first day)
+        e = exp[365 * y:365 * (y + 1)]
+        g = got[365 * y:365 * (y + 1)]
+        for c in range(C):
+            col = np.concatenate([[0], e[:, c].astype(int), [0]])
+            d = np.diff(col)
+            starts, ends = np.flatnonzero(d == 1), np.flatnonzero(d == -1)
+            want = np.zeros(365, bool)
+            if starts.size:
+                k = int(np.argmax(ends - starts))
+                want[starts[k]:ends[k]] = True
+            else:
+                want[0] = True
+            np.testing.assert_array_equal(g[:, c], want, err_msg=f"year {y} cell {c}")
+
+
+def test_overwintering_drought_code_device(dev):
+    cases = [([300, 110, 0.75, 0.75, 15], 109.4657), ([300, 110, 1.0, 0.9, 15], 16.35315),
+             ([100, 50, 0.75, 0.75, 15], 105.176), ([1, 550, 0.75, 0.75, 10], 10)]
+    for inputs, e in cases:
+        got = fire.overwintering_drought_code(np.array([inputs[0]], np.float32), np.array([inputs[1]], np.float32),
+                                              *inputs[2:], device=dev)
+        np.testing.assert_allclose(got, e, rtol=1e-6)
+    rng = np.random.default_rng(5)
+    a, b = rng.uniform(0, 600, 1001).astype(np.float32), rng.uniform(0, 500, 1001).astype(np.float32)
+    a[::97] = np.nan
+    np.testing.assert_allclose(fire.overwintering_drought_code(a, b, device=dev),
+                               firecpu.overwintering_dc(a, b, 0.75, 0.75, 15).astype(np.float32), rtol=1e-6, equal_nan=True)
+
+
+def test_invalid_latitude_raises(dev):
+    inp = _weather(np.random.default_rng(1), 10, 5)
+    time = TimeAxis.daily("2001-01-01", 10, "noleap")
+    with pytest.raises(ValueError, match="Invalid lat specified."):
+        fire.drought_code(inp[0], inp[1], np.array([0, 10, 95.0, 0, 0]), time=time, device=dev)
+
+
+# ---- the adapter ---------------------------------------------------------------------------------------------------
+@pytest.fixture()
+def cffwis(dev):
+    """A stand-in xclim.indices.fire._cffwis whose originals assert if they are reached (unless allowed)."""
+    import xclim_amd._capi as capi
+
+    calls = []
+
+    def orig_calc(*a, **k):
+        calls.append("calc")
+        assert k.get("allow_forward") or mod.allow_forward, "the original _fire_weather_calc was reached"
+        return "forwarded"
+
+    def orig_season(*a, **k):
+        calls.append("season")
+        assert mod.allow_forward, "the original _fire_season was reached"
+        return "forwarded"
+
+    mod = types.SimpleNamespace(_fire_weather_calc=orig_calc, _fire_season=orig_season, allow_forward=False, calls=calls)
+    old = capi._default_device
+    capi._default_device = dev
+    done = patch.install(env=fakexr.make_env(), modules={"xclim.indices.fire._cffwis": mod})
+    assert "xclim.indices.fire._cffwis._fire_weather_calc" in done and "xclim.indices.fire._cffwis._fire_season" in done
+    yield mod
+    patch.uninstall()
+    capi._default_device = old
+
+
+def _time_last(a):
+    """The transposed view xr.apply_ufunc hands over: a (T, C) array with time moved last."""
+    return np.moveaxis(a, 0, -1)
+
+
+def test_adapter_serves_calc_once_per_call(dev, cffwis):
+    inp, P, exp = golden_case("wf93_overwinter_cfs")
+    T, C = inp["tas"].shape
+    params = {k: P[k] for k in firecpu.DEFAULTS}
+    params.update(snow_cover_days=60, snow_min_cover_frac=0.75, snow_min_mean_depth=0.1, season_method="WF93",
+                  overwintering=True, dry_start="CFS", initial_start_up=True,
+                  outputs=list(P["indexes"]) + ["season_mask", "winter_pr"])
+    trace = dev.start_trace()
+    try:
+        res = cffwis._fire_weather_calc(_time_last(inp["tas"]), _time_last(inp["pr"]), _time_last(inp["hurs"]),
+                                        _time_last(inp["sfcWind"]), None, inp["month"][None, :], inp["lat"], None,
+                                        inp["dc0"], inp["dmc0"], inp["ffmc0"], inp["winter_pr_in"], **params)
+    finally:
+        dev.stop_trace()
+    assert [n for n, _ in trace if n.startswith("xh_fire")] == ["xh_fire_weather"]
+    got = dict(zip(params["outputs"], res))
+    for k in P["indexes"] + ["season_mask"]:
+        assert got[k].shape == (C, T)
+        got[k] = np.moveaxis(got[k], -1, 0)
+    check_outputs(got, exp)
+    assert cffwis.calls == []
+
+
+def test_adapter_fire_season(dev, cffwis):
+    rng = np.random.default_rng(9)
+    inp = _weather(rng, 500, 77)
+    got = cffwis._fire_season(_time_last(inp[0]), _time_last(inp[4]), method="LA08")
+    np.testing.assert_array_equal(np.moveaxis(got, -1, 0), firecpu.fire_season(inp[0], inp[4], "LA08", 12.0, 5.0, 0.01, 3, 3))
+
+
+def test_adapter_forwards_what_it_does_not_serve(dev, cffwis):
+    cffwis.allow_forward = True
+    x = np.ones((4, 30), np.float32)
+    base = dict(temp_start_thresh=12.0, temp_end_thresh=5.0, snow_thresh=0.01, temp_condition_days=3, snow_condition_days=3,
+                carry_over_fraction=0.75, wetting_efficiency_fraction=0.75, dc_start=15, dmc_start=6, ffmc_start=85,
+                prec_thresh=1.0, dc_dry_factor=5, dmc_dry_factor=2, season_method=None, overwintering=False,
+                dry_start=None, initial_start_up=True, outputs=["DC"])
+    args = (x, x, x, x, None, np.ones((1, 30)), np.full(4, 45.0), None, np.full(4, np.nan, np.float32),
+            np.full(4, np.nan, np.float32), np.full(4, np.nan, np.float32), None)
+    f64 = (x.astype(np.float64),) + args[1:]
+    assert cffwis._fire_weather_calc(*f64, **base) == "forwarded"                                    # float64 field
+    assert cffwis._fire_weather_calc(*args, **dict(base, dry_start="GFWED+SNOW")) == "forwarded"     # GFWED+SNOW
+    assert cffwis._fire_weather_calc(*args, **dict(base, season_method="GFWED", temp_condition_days=9)) == "forwarded"
+    bc = (x, x[:1], x, x) + args[4:]
+    assert cffwis._fire_weather_calc(*bc, **base) == "forwarded"                                     # broadcast field
+    assert cffwis._fire_season(x, x, method="GFWED", temp_condition_days=8) == "forwarded"
+    assert cffwis.calls == ["calc"] * 4 + ["season"]
+    cffwis.calls.clear()
+    out = cffwis._fire_weather_calc(*args, **base)  # a served form does not reach the original
+    assert out.shape == (4, 30) and cffwis.calls == []

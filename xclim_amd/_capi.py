@@ -219,6 +219,9 @@ SIGNATURES: dict[str, list] = {
     "xh_window_nanmean": [_vp, _vp, _i64, _i64, _i64, _i64, _int, _vp, _i64],
     "xh_poly_trend_groups": [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _int, _vp, _int, _vp, _vp],
     "xh_trend_apply_groups": [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _int, _vp, _vp, _vp, _int, _vp, _i64],
+    "xh_fire_weather": [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _int,
+                        _int, _int, _int, _vp, _vp, _i64, _vp, _vp],
+    "xh_overwintering_dc": [_vp, _vp, _vp, _i64, _dbl, _dbl, _dbl, _vp],
 }
 _RESTYPES = {"xh_last_error": C.c_char_p}
 

@@ -950,3 +950,76 @@ def apply_factor(dev: Device, base: DeviceArray, fac: DeviceArray, kind="+", out
     out = out if out is not None else dev.empty((T, C_), np.float32)
     dev.call("xh_apply_factor", _vp(base.ptr), _vp(fac.ptr), T, C_, C_, C_, {"+": 0, "*": 1}[kind], _vp(out.ptr), C_)
     return out
+
+
+FIRE_INDEXES = ("DC", "DMC", "FFMC", "ISI", "BUI", "FWI", "DSR")
+FIRE_SEASONS = {None: 0, "mask": 1, "WF93": 2, "LA08": 3, "GFWED": 4}
+FIRE_DRY = {None: 0, "CFS": 1, "GFWED": 2, "GFWED+SNOW": 3}
+FIRE_PARAMS = ("temp_start_thresh", "temp_end_thresh", "snow_thresh", "prec_thresh", "carry_over_fraction",
+               "wetting_efficiency_fraction", "dc_start", "dmc_start", "ffmc_start", "dc_dry_factor", "dmc_dry_factor")
+
+
+def fire_weather(dev: Device, fields: dict, month, lat: DeviceArray | None, starts: dict, indexes, params: dict, *,
+                 season_method=None, season_mask: DeviceArray | None = None, overwintering=False, dry_start=None,
+                 initial_start_up=True, want_mask=False, want_winter_pr=False):
+    """xh_fire_weather.  ``fields``: name -> (T, C) float32 DeviceArray for tas / pr / hurs / sfcWind / snd (the ones the
+    request reads); ``month`` host int (T); ``lat`` float64 (C); ``starts``: dc0 / dmc0 / ffmc0 / winter_pr float32 (C)
+    DeviceArrays or None; ``indexes``: the (closed) subset of FIRE_INDEXES.  Returns ``{name: DeviceArray}`` with the
+    indexes, "season_mask" (uint8) and "winter_pr" when asked for.  Raises NotImplementedError for the forms the kernel does
+    not serve (GFWED+SNOW dry starts, GFWED windows over 7 days) and ValueError for an invalid latitude."""
+    ref = next(iter(fields.values()))
+    T, C_ = _tc(ref)
+    for v in fields.values():
+        if _tc(v) != (T, C_):
+            raise ValueError("fire_weather: every field must have the same (T, C) shape")
+    m = np.ascontiguousarray(month, dtype=np.int32)
+    if m.shape != (T,):
+        raise ValueError(f"fire_weather: month must have {T} entries, got {m.shape}")
+    outs = {}
+    ptrs = (_vp * 7)()
+    for k, name in enumerate(FIRE_INDEXES):
+        if name in indexes:
+            outs[name] = dev.empty((T, C_), np.float32)
+            ptrs[k] = outs[name].ptr
+    mask_out = dev.empty((T, C_), np.uint8) if want_mask else None
+    wpr_out = dev.empty((C_,), np.float32) if want_winter_pr else None
+    p = np.array([float(params[k]) for k in FIRE_PARAMS], dtype=np.float64)
+
+    def ptr(a, dtype, shape):
+        if a is None:
+            return _vp(0)
+        if a.dtype != np.dtype(dtype) or tuple(a.shape) != shape:
+            raise TypeError(f"fire_weather: expected {np.dtype(dtype).name} {shape}, got {np.dtype(a.dtype).name} {a.shape}")
+        return _vp(a.ptr)
+
+    f = {k: ptr(fields.get(k), np.float32, (T, C_)) for k in ("tas", "pr", "hurs", "sfcWind", "snd")}
+    try:
+        dev.call("xh_fire_weather", T, C_, C_, f["tas"], f["pr"], f["hurs"], f["sfcWind"], f["snd"], np_ptr(m),
+                 ptr(lat, np.float64, (C_,)), ptr(starts.get("dc0"), np.float32, (C_,)), ptr(starts.get("dmc0"), np.float32, (C_,)),
+                 ptr(starts.get("ffmc0"), np.float32, (C_,)), ptr(starts.get("winter_pr"), np.float32, (C_,)),
+                 ptr(season_mask, np.uint8, (T, C_)), C_, FIRE_SEASONS[season_method], int(params["temp_condition_days"]),
+                 int(params["snow_condition_days"]), int(bool(overwintering)), FIRE_DRY[dry_start], int(bool(initial_start_up)),
+                 np_ptr(p), ptrs, C_, _vp(mask_out.ptr if mask_out is not None else 0), _vp(wpr_out.ptr if wpr_out is not None else 0))
+    except capi.XclimHipError as err:
+        if err.code == capi.XH_ERR_NOTIMPL:
+            raise NotImplementedError(f"fire_weather: dry_start={dry_start!r} / {season_method} windows of "
+                                      f"{params['temp_condition_days']}, {params['snow_condition_days']} days are not served") from None
+        if err.msg == "Invalid lat specified.":
+            raise ValueError("Invalid lat specified.") from None
+        raise
+    if mask_out is not None:
+        outs["season_mask"] = mask_out
+    if wpr_out is not None:
+        outs["winter_pr"] = wpr_out
+    return outs
+
+
+def overwintering_dc(dev: Device, last_dc: DeviceArray, winter_pr: DeviceArray, carry_over_fraction, wetting_efficiency_fraction,
+                     min_dc) -> DeviceArray:
+    """xh_overwintering_dc: element-wise over two float32 device arrays of one shape."""
+    if last_dc.shape != winter_pr.shape or last_dc.dtype != np.float32 or winter_pr.dtype != np.float32:
+        raise TypeError("overwintering_dc: last_dc and winter_pr must be float32 arrays of one shape")
+    out = dev.empty(last_dc.shape, np.float32)
+    dev.call("xh_overwintering_dc", _vp(last_dc.ptr), _vp(winter_pr.ptr), last_dc.size, float(carry_over_fraction),
+             float(wetting_efficiency_fraction), float(min_dc), _vp(out.ptr))
+    return out

@@ -98,6 +98,10 @@ _BY_NAME = {
 }
 
 
+_FIRE_MODULE = "xclim.indices.fire._cffwis"
+_FIRE_NAMES = ("_fire_weather_calc", "_fire_season")
+
+
 def real_env():
     """The :class:`xr_adapter.Env` of an installation that has xarray and xclim."""
     import xarray as xr
@@ -205,6 +209,15 @@ def install(env=None, modules=None) -> list[str]:
     patch("xsdba.nbutils", "quantile", wrappers["sdba_quantile"])
     # qm_adjust / qdm_adjust reach the factor interpolation as ``u.interp_on_quantiles`` (module object): group="time" -> xh_eqm_adjust
     patch("xsdba.utils", "interp_on_quantiles", wrappers["sdba_interp_on_quantiles"])
+    # the fire weather system: fire_weather_ufunc / fire_season reach these two by module-global name (through
+    # xr.apply_ufunc / map_blocks), so every public fire function and indicator is served through them
+    fmod = resolve(_FIRE_MODULE)
+    if fmod is not None and all(hasattr(fmod, n) for n in _FIRE_NAMES):
+        from .fire import make_adapters
+
+        fire = make_adapters(*(_saved.get((_FIRE_MODULE, n), getattr(fmod, n)) for n in _FIRE_NAMES))
+        for name in _FIRE_NAMES:
+            patch(_FIRE_MODULE, name, fire[name])
     _saved_modules.update({} if modules is None else modules)
     return done
 

@@ -716,6 +716,38 @@ int xh_fire_weather(xh_ctx* ctx, int64_t T, int64_t C, int64_t st, const float* 
 int xh_overwintering_dc(xh_ctx* ctx, const float* last_dc, const float* winter_pr, int64_t n, double carry_over_fraction,
                         double wetting_efficiency_fraction, double min_dc, float* out);
 
+/* ---- standardized indices: SPI / SPEI (indices/stats.py) --------------------------------------------------------- */
+/* xh_si_fit: the per-group fits of standardized_index_fit_params (stats.py:855-964) through _fitfunc_1d (:40-113) and
+ *   _fit_start (:576-684), one lane per (cell, group), float64.  x (T, C) float32 with row stride st (DEVICE): the
+ *   resampled, rolled calibration rows.  group (HOST, T): group index 0..G-1 of every row, -1 = row not used.
+ *   dist XH_SI_GAMMA / XH_SI_FISK; method XH_SI_APP (needs has_floc: the closed forms of _fit_start with loc = floc) or
+ *   XH_SI_ML (gamma with floc: scipy's root of log a - digamma(a) = s by brentq; otherwise scipy's fmin Nelder-Mead on
+ *   _penalized_nnlf from the _fit_start point, 3 parameters, or 2 with loc fixed to floc).  zero_inflated: zeros are
+ *   left out of the sample.  staging: XH_SI_STAGE_AUTO / _GLOBAL / _LDS (where the sample is kept between objective
+ *   evaluations; LDS holds at most 64 values per group, XH_ERR_LIMIT beyond).
+ *   params (DEVICE float64 (G, 3, C)): shape, loc, scale; NaN for samples of fewer than 2 values, for data at or below
+ *   floc (gamma ML; scipy raises FitDataError) and for fits that end off the parameter domain (scipy raises FitError).
+ *   nzeros / nnotnull (DEVICE float64 (G, C), both or neither): zeros and non-NaN values per group.  nfev (DEVICE int32
+ *   (G, C), may be NULL): objective evaluations of the Nelder-Mead fits (0 for the others). */
+#define XH_SI_GAMMA 0
+#define XH_SI_FISK 1
+#define XH_SI_APP 0
+#define XH_SI_ML 1
+#define XH_SI_STAGE_AUTO 0
+#define XH_SI_STAGE_GLOBAL 1
+#define XH_SI_STAGE_LDS 2
+int xh_si_fit(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, const int32_t* group /* host */, int G, int dist,
+              int method, int has_floc, double floc, int zero_inflated, int staging, double* params, double* nzeros,
+              double* nnotnull, int32_t* nfev);
+/* xh_si_apply: the transform of standardized_index (stats.py:1156-1197): out[t, c] = clip(norm.ppf(prob), -8.21, 8.21)
+ *   with prob = cdf(x[t, c]; params[group[t], :, c]), or with nzeros / nnotnull (DEVICE float64 (G, C); NaN = group absent
+ *   from the fit) the zero-inflated mixture: zeros get (1 - interp) r1 + interp rn, other values rn + (1 - rn) cdf, where
+ *   r1 = (1 - alpha) / (nnotnull + 1 - alpha - beta), rn = (nzeros - alpha) / (same).  x (T, C) float32 row stride st,
+ *   group (HOST, T; -1 = NaN out), params (DEVICE float64 (G, 3, C)), out (DEVICE float64 (T, C), row stride st_out). */
+int xh_si_apply(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, const int32_t* group /* host */, int G,
+                const double* params, const double* nzeros, const double* nnotnull, int dist, double alpha, double beta,
+                double interp, double* out, int64_t st_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,266 @@
+"""Standardized indices (SPI / SPEI) on the device: xh_si_fit / xh_si_apply (xclim_amd/csrc/stdidx.hip) and the host mirror
+xclim_amd.stats against the reference's own fits (tests/golden/spi_vectors.npz) and against scipy on random grids."""
+
+import json
+import math
+import os
+import sys
+
+import numpy as np
+import pytest
+import scipy.stats
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import spicpu  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "spi_vectors.npz")
+Z = np.load(GOLD)
+META = json.loads(str(Z["meta"]))
+FAST = {n for n, m in META.items() if m["method"] == "APP" or (m["dist"] == "gamma" and m["floc"] is not None)}
+SF_ATOL = 4.5e-16  # two ulps of 1.0: a cdf near 1 is only known to that much in float64
+
+
+def case(name):
+    return {k.split("__", 1)[1]: Z[k] for k in Z.files if k.startswith(name + "__")}, META[name]
+
+
+@pytest.fixture(scope="module")
+def dev():
+    from xclim_amd._capi import get_device
+
+    return get_device(0)
+
+
+def zero_opts(m):
+    interp = {"center": 0.5, "upper": 1.0}.get(m["interp"], m["interp"]) if isinstance(m["interp"], str) else m["interp"]
+    ab = {"ecdf": (0, 1), "weibull": (0, 0)}[m["plotting"]] if isinstance(m["plotting"], str) else m["plotting"]
+    return float(interp), float(ab[0]), float(ab[1])
+
+
+def assert_si_close(got, exp, atol=1e-6):
+    """|SI| <= 5: absolute; beyond, the tail probability min(p, 1 - p) relative (norm.ppf amplifies the cdf's last bit)."""
+    np.testing.assert_array_equal(np.isnan(got), np.isnan(exp))
+    ok = ~np.isnan(exp)
+    g, e = got[ok], exp[ok]
+    core = np.abs(e) <= 5
+    np.testing.assert_allclose(g[core], e[core], rtol=0, atol=atol)
+    tail = ~core
+    if tail.any():
+        assert np.all(np.sign(g[tail]) == np.sign(e[tail]))
+        np.testing.assert_allclose(scipy.stats.norm.sf(np.abs(g[tail])), scipy.stats.norm.sf(np.abs(e[tail])), rtol=1e-9,
+                                   atol=SF_ATOL)
+
+
+def assert_params_close(name, got, ref, share_out=None, nfev=None):
+    """Nelder-Mead fits that stop at the 600-evaluation budget have not converged: scipy's result is wherever its walk was
+    at the cutoff (fisk without floc can run off towards loc -> -inf, scale and c -> inf).  On the device a few of them
+    end elsewhere (9 of 36 fisk fits, a few 3-value gamma fits).  Why is NOT established: the restatement
+    (tests/spicpu.py) with lgamma or log moved by one ulp keeps every such fit in place, so it is not a plain last-bit
+    difference of those functions.  Those fits are compared through their index (test_golden_fit_and_index), the
+    converged ones to 1e-3."""
+    np.testing.assert_array_equal(np.isnan(got), np.isnan(ref))
+    if name in FAST:
+        np.testing.assert_allclose(got, ref, rtol=1e-9, atol=0, equal_nan=True)
+    else:
+        conv = np.ones(got.shape[0:1] + got.shape[2:], bool) if nfev is None else nfev < 600
+        conv = np.broadcast_to(conv[:, None, :], got.shape)
+        np.testing.assert_allclose(got[conv], ref[conv], rtol=1e-3, atol=0, equal_nan=True)
+        fin = ~np.isnan(ref[:, 0])
+        same = np.all(np.isclose(got, ref, rtol=1e-8, atol=0, equal_nan=True), axis=1)[fin]
+        if share_out is not None:
+            share_out.append((name, int(same.sum()), int(same.size)))
+
+
+@pytest.mark.parametrize("staging", ["global", "lds"])
+@pytest.mark.parametrize("name", sorted(META))
+def test_golden_fit_and_index(dev, name, staging):
+    from xclim_amd import kernels as K
+
+    c, m = case(name)
+    xfit = c["xp_fit"] if m["cal"] == "reuse" else c["xp"]
+    params, nz, nn, nfev = K.si_fit(dev, dev.to_device(xfit), c["fit_g"], m["G"], m["dist"], m["method"], floc=m["floc"],
+                                    zero_inflated=m["zero_inflated"], staging=staging, want_nfev=True)
+    shares = []
+    nf = nfev.get()
+    assert_params_close(name, params.get(), c["params"], shares, nf)
+    if m["zero_inflated"]:
+        np.testing.assert_array_equal(nz.get(), c["nz"])
+        np.testing.assert_array_equal(nn.get(), c["nn"])
+    assert nf.max() <= 600
+    for n, k, tot in shares:
+        print(f"{n} [{staging}]: {k}/{tot} Nelder-Mead fits match scipy to 1e-8, {(nf >= 600).sum()} stopped at the budget")
+        assert k >= 0.8 * tot
+    if (nf >= 600).any():  # unconverged fits: the index from the device's own parameters within upstream's 2e-2
+        interp, alpha, beta = zero_opts(m)
+        zi = m["zero_inflated"]
+        own = K.si_apply(dev, dev.to_device(c["xp"]), c["gidx"], params, m["dist"], nz, nn, alpha=alpha, beta=beta,
+                         interp=interp).get()
+        bad = (nf >= 600)[c["gidx"]]
+        np.testing.assert_array_equal(np.isnan(own[bad]), np.isnan(c["spi"][bad]))
+        # a 3-parameter fit of 2 or 3 values has no maximum (the likelihood grows without bound): both walks stop at
+        # arbitrary points, so a few of those indexes may differ; nearly all must agree
+        close = np.isclose(own[bad], c["spi"][bad], rtol=0, atol=2e-2, equal_nan=True)
+        print(f"{name} [{staging}]: {close.mean():.4f} of the indexes of unconverged fits within 2e-2")
+        assert close.mean() >= 0.99
+    # the transform from the reference's own parameters
+    interp, alpha, beta = zero_opts(m)
+    zi = m["zero_inflated"]
+    si = K.si_apply(dev, dev.to_device(c["xp"]), c["gidx"], dev.to_device(c["params"]), m["dist"],
+                    dev.to_device(c["nz"]) if zi else None, dev.to_device(c["nn"]) if zi else None, alpha=alpha, beta=beta,
+                    interp=interp).get()
+    assert_si_close(si, c["spi"])
+
+
+@pytest.mark.parametrize("name", sorted(META))
+def test_golden_host_mirror(dev, name):
+    """The whole chain from the daily input: device preprocessing within one float32 ulp of the golden series, the index
+    within the Nelder-Mead tolerance (a one-ulp preprocessing difference moves a fit by ~1e-7)."""
+    from xclim_amd import stats as xs
+    from xclim_amd.timeaxis import TimeAxis
+
+    c, m = case(name)
+    x = c["codes"].astype(np.float32) * np.float32(c["scale"])
+    C = x.shape[1]
+    x[100:160, C - 1] = np.nan
+    if m["freq"] == "D":
+        x[400:403, 0] = np.nan
+    t = TimeAxis(c["year"].astype(np.int64), c["month"].astype(np.int64), c["day"].astype(np.int64), m["calendar"])
+    interp, alpha, beta = zero_opts(m)
+    kw = dict(dist=m["dist"], method=m["method"], zero_inflated=m["zero_inflated"],
+              fitkwargs={} if m["floc"] is None else {"floc": m["floc"]})
+    pz = m["interp"] if isinstance(m["interp"], str) else float(m["interp"])
+    pp = m["plotting"] if isinstance(m["plotting"], str) else tuple(m["plotting"])
+    if m["cal"] == "reuse":
+        Ta = int(c["reuse_T"])
+        params = xs.standardized_index_fit_params(x[:Ta], t.subset(slice(0, Ta)), m["freq"], m["window"], device=dev, **kw)
+        assert params.attrs["freq"] == m["freq"] and params.attrs["window"] == m["window"]
+        with pytest.warns(UserWarning, match="overrides"):
+            si = xs.standardized_index(x, t, None, None, params=params, cal_start="1999-01-01", prob_zero_interpolation=pz,
+                                       plotting_position_zero=pp, device=dev)
+        np.testing.assert_allclose(params.values, c["params"], rtol=1e-3, equal_nan=True)
+    else:
+        cal = m["cal"] or (None, None)
+        si = xs.standardized_index(x, t, m["freq"], m["window"], cal_start=cal[0], cal_end=cal[1], prob_zero_interpolation=pz,
+                                   plotting_position_zero=pp, device=dev, **kw)
+    x2, _ = xs._preprocess(dev, dev.to_device(x), t, m["freq"], m["window"])
+    np.testing.assert_allclose(x2.get(), c["xp"], rtol=1.2e-7, atol=0, equal_nan=True)
+    np.testing.assert_array_equal(np.isnan(si), np.isnan(c["spi"]))
+    if name in FAST:
+        np.testing.assert_allclose(si, c["spi"], rtol=0, atol=1e-4, equal_nan=True)
+    else:  # unconverged 3-parameter fits of 3 values (daily groups of 3 years) may stop elsewhere: upstream's 2e-2 for all
+        np.testing.assert_allclose(si, c["spi"], rtol=0, atol=2e-2, equal_nan=True)
+        assert np.isclose(si, c["spi"], rtol=0, atol=1e-3, equal_nan=True).mean() >= 0.99
+
+
+def test_fit_params_round_trip(dev):
+    """fit_params fed back through params= gives the one-call SPI exactly (same calibration, same kernels)."""
+    from xclim_amd import indices as xi
+    from xclim_amd import stats as xs
+    from xclim_amd.timeaxis import TimeAxis
+
+    rng = np.random.default_rng(3)
+    T, C = 365 * 12 + 40, 37
+    t = TimeAxis.daily("1990-01-01", T, "noleap")
+    pr = np.where(rng.random((T, C)) < 0.4, rng.gamma(0.8, 5.0, (T, C)), 0.0).astype(np.float32)
+    one = xi.standardized_precipitation_index(pr, t, freq="MS", window=3, device=dev)
+    p = xs.standardized_index_fit_params(pr, t, "MS", 3, "gamma", "ML", zero_inflated=True, device=dev)
+    two = xi.standardized_precipitation_index(pr, t, params=p, device=dev)
+    np.testing.assert_array_equal(one, two)
+    assert one.shape == (len(xs.preprocessed_time(t, "MS")), C)
+    assert np.isnan(one[:2]).all() and np.isfinite(one[2:]).mean() > 0.99
+
+
+def _scipy_fit(sample, dist, floc):
+    """scipy's own fit of one sample from the reference's start values (restated _fit_start)."""
+    s = [float(v) for v in sample]
+    if len(s) <= 1:
+        return [math.nan] * 3
+    sd = getattr(scipy.stats, dist)
+    loc0 = floc if floc is not None else spicpu.loc_estimation(s)
+    p0, sc0 = spicpu.fit_start(dist, s, loc0)
+    kw = {} if floc is None else {"floc": floc}
+    try:
+        return list(sd.fit(np.array(s), p0, loc=loc0, scale=sc0, method="mle", **kw))
+    except Exception:
+        return [math.nan] * 3
+
+
+@pytest.mark.parametrize("dist,floc,zi", [("gamma", None, True), ("gamma", 0.0, True), ("fisk", None, False)])
+def test_random_grid_against_scipy(dev, dist, floc, zi):
+    """Odd cell counts, T not a multiple of 12 months, NaN prefixes and a strided view; seeded sample of cells vs scipy."""
+    from xclim_amd import stats as xs
+    from xclim_amd.timeaxis import TimeAxis
+
+    rng = np.random.default_rng(11 + (floc is not None) + 2 * (dist == "fisk"))
+    T, C = 365 * 23 + 151, 333
+    t = TimeAxis.daily("1971-01-01", T, "noleap")
+    if dist == "gamma":
+        full = np.where(rng.random((T, C + 1)) < 0.45, rng.gamma(0.9, 4.0, (T, C + 1)), 0.0).astype(np.float32)
+    else:
+        full = (rng.gamma(2.0, 2.0, (T, C + 1)) - 4.0 + rng.normal(0, 1, (T, 1))).astype(np.float32)
+    full[: rng.integers(0, 400), 5] = np.nan
+    full[:800, 17] = np.nan
+    x = full[:, 1:]  # a misaligned, non-contiguous view
+    p = xs.standardized_index_fit_params(x, t, "MS", 2, dist, "ML", zero_inflated=zi,
+                                         fitkwargs={} if floc is None else {"floc": floc}, device=dev)
+    vals = p.values
+    xp, t2 = xs._preprocess(dev, dev.to_device(np.ascontiguousarray(x)), t, "MS", 2)
+    xp = xp.get()
+    from xclim_amd import kernels as K
+
+    nfev = K.si_fit(dev, dev.to_device(xp), (t2.month - 1).astype(np.int32), 12, dist, "ML", floc=floc, zero_inflated=zi,
+                    want_nfev=True)[3].get()
+    cells = rng.choice(C, 20, replace=False)
+    same = tot = 0
+    for c in cells:
+        for g in range(12):
+            v = xp[t2.month - 1 == g, c].astype(np.float64)
+            v = v[~np.isnan(v)]
+            if zi:
+                v = v[v != 0]
+            ref = np.array(_scipy_fit(v, dist, floc))
+            got = vals[g, :, c]
+            assert np.isnan(got).all() == np.isnan(ref).all(), (c, g, got, ref)
+            if not np.isnan(ref).all() and (nfev[g, c] >= 600 or ref[0] > 1e3):
+                # an unconverged walk, or fisk run off to its c -> inf limit (loc -> -inf, scale -> inf: a flat
+                # likelihood, the parameters are arbitrary there): compare the distributions on the sample instead
+                q = lambda p: scipy.stats.norm.ppf(getattr(scipy.stats, dist).cdf(v, *p))  # noqa: E731
+                np.testing.assert_allclose(q(got), q(ref), rtol=0, atol=2e-2)
+            elif not np.isnan(ref).all():
+                np.testing.assert_allclose(got, ref, rtol=1e-3 if floc is None or dist == "fisk" else 1e-9)
+                same += np.allclose(got, ref, rtol=1e-8, atol=0)
+                tot += 1
+    print(f"{dist} floc={floc}: {same}/{tot} fits match scipy to 1e-8")
+    si = xs.standardized_index(x, t, "MS", 2, dist=dist, method="ML", zero_inflated=zi,
+                               fitkwargs={} if floc is None else {"floc": floc}, device=dev)
+    exp = spicpu.index(xp, (t2.month - 1).astype(int), vals, dist, p.number_of_zeros if zi else None,
+                       p.number_of_notnull if zi else None)
+    assert_si_close(si, exp, atol=1e-9)
+
+
+def test_full_grid_monthly_spi3(dev):
+    """1440 x 720 cells, 20 years of monthly precipitation, SPI-3 gamma ML: sampled cells against the restatement."""
+    from xclim_amd import indices as xi
+    from xclim_amd import stats as xs
+    from xclim_amd.timeaxis import TimeAxis
+
+    rng = np.random.default_rng(5)
+    Y, Xn, years = 720, 1440, 20
+    T = 12 * years
+    t = TimeAxis(np.repeat(np.arange(2000, 2000 + years), 12), np.tile(np.arange(1, 13), years), np.ones(T, np.int64), "noleap")
+    pr = rng.gamma(2.0, 1.5, (T, Y * Xn)).astype(np.float32)
+    pr[:, ::97] = 0.0
+    si = xi.standardized_precipitation_index(pr.reshape(T, Y, Xn), t, freq="MS", window=3, device=dev, keep=True)
+    cells = rng.choice(Y * Xn, 24, replace=False)
+    got = si.get()[:, cells]
+    xp = np.full((T, len(cells)), np.nan, np.float32)
+    w = pr[:, cells].astype(np.float64)
+    for k in range(2, T):
+        xp[k] = ((w[k - 2] + w[k - 1]) + w[k]) / 3.0
+    gidx = (t.month - 1).astype(int)
+    p, nz, nn, _ = spicpu.fit(xp, gidx, 12, "gamma", "ML", True, None)
+    exp = spicpu.index(xp, gidx, p, "gamma", nz, nn)
+    np.testing.assert_allclose(got, exp, rtol=0, atol=1e-3, equal_nan=True)
+    assert np.isnan(got[:2]).all()

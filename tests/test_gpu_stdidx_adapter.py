@@ -1,0 +1,159 @@
+"""The xarray adapter of the standardized indices, EXECUTED: ``patch.install(env, modules)`` on stand-in modules wired like
+the reference — ``xclim.indices.stats`` defines ``standardized_index`` / ``standardized_index_fit_params``, ``_agro`` and
+``_hydrology`` import ``standardized_index`` by name (indices/_agro.py:36, indices/_hydrology.py:16) — with the DataArray
+stand-in of tests/fakexr.py.  The stand-in originals only record that they were reached (the forwarded forms)."""
+
+import os
+import sys
+import types
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import fakexr  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+# the call of standardized_index in the reference's SPI body (_agro.py:1108-1126), held by module-global name
+_SPI_SRC = '''
+def standardized_precipitation_index(pr, freq="MS", window=1, dist="gamma", method="ML", fitkwargs=None, cal_start=None,
+                                     cal_end=None, params=None, prob_zero_interpolation="upper",
+                                     plotting_position_zero="ecdf", **indexer):
+    return standardized_index(pr, freq=freq, window=window, dist=dist, method=method, zero_inflated=True,
+                              fitkwargs=fitkwargs or {}, cal_start=cal_start, cal_end=cal_end, params=params,
+                              prob_zero_interpolation=prob_zero_interpolation,
+                              plotting_position_zero=plotting_position_zero, **indexer)
+'''
+
+
+@pytest.fixture()
+def wired():
+    from xclim_amd import patch
+
+    env = fakexr.make_env()
+    mods = fakexr.make_reference_like_modules(env)
+    reached = []
+
+    def orig_index(*a, **k):
+        reached.append(("standardized_index", a, k))
+        return "original standardized_index"
+
+    def orig_fit(*a, **k):
+        reached.append(("standardized_index_fit_params", a, k))
+        return "original standardized_index_fit_params"
+
+    stats = types.ModuleType("xclim.indices.stats")
+    stats.standardized_index, stats.standardized_index_fit_params = orig_index, orig_fit
+    agro = types.ModuleType("xclim.indices._agro")
+    hydro = types.ModuleType("xclim.indices._hydrology")
+    for m in (agro, hydro):
+        m.standardized_index = orig_index
+    exec(_SPI_SRC, agro.__dict__)
+    mods.update({"xclim.indices.stats": stats, "xclim.indices._agro": agro, "xclim.indices._hydrology": hydro})
+    names = patch.install(env, mods)
+    try:
+        yield env, mods, names, reached, orig_index
+    finally:
+        patch.uninstall()
+
+
+def _pr(seed=0, years=8, ny=3, nx=5):
+    from xclim_amd.timeaxis import TimeAxis
+
+    rng = np.random.default_rng(seed)
+    T = 365 * years + 17
+    t = TimeAxis.daily("2001-01-01", T, "noleap")
+    pr = np.where(rng.random((T, ny, nx)) < 0.4, rng.gamma(0.8, 5.0, (T, ny, nx)), 0.0).astype(np.float32)
+    pr[:40, 1, 2] = np.nan
+    return pr, t
+
+
+def test_install_replaces_every_holder(wired):
+    _, mods, names, _, orig = wired
+    for n in ("xclim.indices.stats.standardized_index", "xclim.indices.stats.standardized_index_fit_params",
+              "xclim.indices._agro.standardized_index", "xclim.indices._hydrology.standardized_index"):
+        assert n in names
+    assert mods["xclim.indices._hydrology"].standardized_index is mods["xclim.indices.stats"].standardized_index
+    assert mods["xclim.indices.stats"].standardized_index.__wrapped__ is orig
+
+
+@pytest.mark.parametrize("dims", [("time", "lat", "lon"), ("lat", "time", "lon")])
+def test_spi_through_the_reference_body(wired, dims):
+    from xclim_amd import indices as xi
+    from xclim_amd import stats as xs
+
+    _, mods, _, reached, _ = wired
+    pr, t = _pr()
+    exp = xi.standardized_precipitation_index(pr, t, freq="MS", window=3)
+    order = [("time", "lat", "lon").index(d) for d in dims]
+    da = fakexr.field(np.transpose(pr, order), t, dims=dims, attrs={"units": "mm/d"})
+    out = mods["xclim.indices._agro"].standardized_precipitation_index(da, freq="MS", window=3)
+    assert not reached
+    assert out.dims == ("time", "lat", "lon")
+    np.testing.assert_array_equal(out.values, exp)
+    t2 = xs.preprocessed_time(t, "MS")
+    np.testing.assert_array_equal(out["time"].dt.month.values, t2.month)
+    np.testing.assert_array_equal(out["time"].dt.year.values, t2.year)
+    assert out.attrs["freq"] == "MS" and out.attrs["window"] == 3 and out.attrs["units"] == ""
+    assert out.attrs["scipy_dist"] == "gamma" and out.attrs["group"] == "time.month"
+    assert out.attrs["calibration_period"] == ("2001-01-01", "2009-01-01")
+
+
+def test_fit_params_round_trip_and_from_arrays(wired):
+    """The params DataArray of the fit wrapper (the reference's layout: present groups only, counts as coordinates) fed
+    back through params= gives the one-call index (SIParams.from_arrays rebuilds the full group tables)."""
+    from xclim_amd import indices as xi
+
+    _, mods, _, reached, _ = wired
+    st = mods["xclim.indices.stats"]
+    pr, t = _pr(1)
+    pr[:, 0, 0] = 0.0
+    da = fakexr.field(pr, t, attrs={"units": "mm/d"})
+    p = st.standardized_index_fit_params(da, "MS", 2, "gamma", "APP", zero_inflated=True, fitkwargs={"floc": 0.0})
+    assert p.dims == ("month", "dparams", "lat", "lon")
+    np.testing.assert_array_equal(p["month"].values, np.arange(1, 13))
+    assert p.attrs["method"] == "APP" and p.attrs["window"] == 2 and p.attrs["freq"] == "MS"
+    nz = p.coords["number_of_zeros"].values
+    assert nz.shape == (12, 3, 5) and nz[:, 0, 0].min() > 0
+    one = xi.standardized_precipitation_index(pr, t, freq="MS", window=2, method="APP", fitkwargs={"floc": 0.0})
+    two = st.standardized_index(da, None, None, None, None, None, None, None, None, params=p)
+    assert not reached
+    np.testing.assert_array_equal(two.values, one)
+    assert two.attrs["window"] == 2 and two.attrs["freq"] == "MS"
+    # a params table holding only some months: the others are absent (NaN), as the reference's reindexing gives
+    sub = fakexr.DataArray(p.values[:6], coords={"month": np.arange(1, 7), "dparams": p.coords["dparams"].values,
+                                                 "number_of_zeros": fakexr.DataArray(nz[:6], dims=("month", "lat", "lon")),
+                                                 "number_of_notnull": fakexr.DataArray(
+                                                     p.coords["number_of_notnull"].values[:6], dims=("month", "lat", "lon"))},
+                           dims=p.dims, attrs=p.attrs)
+    three = st.standardized_index(da, None, None, None, None, None, None, None, None, params=sub).values
+    t2m = np.asarray(two["time"].dt.month.values)
+    np.testing.assert_array_equal(three[t2m <= 6], one[t2m <= 6])
+    assert np.isnan(three[t2m > 6]).all()
+
+
+@pytest.mark.parametrize("kw", [dict(dist="genextreme"), dict(freq="W"), dict(fitkwargs={"fscale": 2.0}), dict(month=[1, 2]),
+                                dict(float64=True)])
+def test_unserved_forms_go_to_the_original(wired, kw):
+    _, mods, _, reached, _ = wired
+    pr, t = _pr(2, years=3)
+    if kw.pop("float64", False):
+        pr = pr.astype(np.float64)
+    da = fakexr.field(pr, t, attrs={"units": "mm/d"})
+    out = mods["xclim.indices._agro"].standardized_precipitation_index(da, **kw)
+    assert out == "original standardized_index"
+    assert [r[0] for r in reached] == ["standardized_index"]
+    out = mods["xclim.indices.stats"].standardized_index_fit_params(da, kw.get("freq", "MS"), 1, kw.get("dist", "gamma"), "ML",
+                                                                     fitkwargs=kw.get("fitkwargs"),
+                                                                     **({"month": kw["month"]} if "month" in kw else {}))
+    assert out == "original standardized_index_fit_params"
+
+
+def test_uninstall_restores(wired):
+    from xclim_amd import patch
+
+    _, mods, _, _, orig = wired
+    patch.uninstall()
+    assert mods["xclim.indices._agro"].standardized_index is orig
+    assert mods["xclim.indices.stats"].standardized_index is orig

@@ -1,0 +1,110 @@
+"""CPU checks of the standardized indices: the numpy restatement of stdidx.hip (tests/spicpu.py) against the reference's own
+fits (tests/golden/spi_vectors.npz), and the argument errors / refusals of the host mirror (xclim_amd.stats)."""
+
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import spicpu  # noqa: E402
+
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "spi_vectors.npz")
+Z = np.load(GOLD)
+META = json.loads(str(Z["meta"]))
+FAST = [n for n in META if META[n]["method"] == "APP" or (META[n]["dist"] == "gamma" and META[n]["floc"] is not None)]
+
+
+def case(name):
+    return {k.split("__", 1)[1]: Z[k] for k in Z.files if k.startswith(name + "__")}, META[name]
+
+
+def test_golden_covers_the_issue():
+    kinds = {(m["dist"], m["method"], m["floc"] is not None) for m in META.values()}
+    assert {("gamma", "APP", True), ("gamma", "ML", True), ("gamma", "ML", False), ("fisk", "APP", True),
+            ("fisk", "ML", False)} <= kinds
+    assert {m["window"] for m in META.values()} >= {1, 3, 12}
+    assert {m["freq"] for m in META.values()} == {"MS", "D"}
+    leap = case("gamma_app_daily_leap")[0]
+    assert 365 in leap["gidx"]  # day 366
+    assert os.path.getsize(GOLD) < 200_000
+
+
+def _fit(name):
+    c, m = case(name)
+    x = c["xp_fit"] if m["cal"] == "reuse" else c["xp"]
+    return c, m, spicpu.fit(x, c["fit_g"], m["G"], m["dist"], m["method"], m["zero_inflated"], m["floc"])
+
+
+@pytest.mark.parametrize("name", sorted(META))
+def test_restatement_matches_reference_fits(name):
+    c, m, (p, nz, nn, nfev) = _fit(name)
+    ref = c["params"]
+    np.testing.assert_array_equal(np.isnan(p), np.isnan(ref))
+    np.testing.assert_array_equal(nz, c["nz"])
+    np.testing.assert_array_equal(nn, c["nn"])
+    rtol = 1e-9 if name in FAST else 1e-3
+    np.testing.assert_allclose(p, ref, rtol=rtol, atol=0, equal_nan=True)
+    if name not in FAST:
+        same = np.all(np.isclose(p, ref, rtol=1e-8, atol=0, equal_nan=True), axis=1).mean()
+        assert same > 0.9, f"only {same:.3f} of the Nelder-Mead fits follow scipy's trajectory"
+        assert nfev.max() <= 600
+
+
+@pytest.mark.parametrize("name", sorted(META))
+def test_restatement_index(name):
+    c, m, _ = _fit(name)
+    interp = {"center": 0.5, "upper": 1.0}.get(m["interp"], m["interp"]) if isinstance(m["interp"], str) else m["interp"]
+    ab = {"ecdf": (0, 1), "weibull": (0, 0)}[m["plotting"]] if isinstance(m["plotting"], str) else m["plotting"]
+    zi = m["zero_inflated"]
+    si = spicpu.index(c["xp"], c["gidx"], c["params"], m["dist"], c["nz"] if zi else None, c["nn"] if zi else None,
+                      float(interp), float(ab[0]), float(ab[1]))
+    np.testing.assert_array_equal(np.isnan(si), np.isnan(c["spi"]))
+    np.testing.assert_allclose(si, c["spi"], rtol=0, atol=1e-9, equal_nan=True)
+
+
+# ---- the host mirror's argument checks and refusals (raised before any device work) -------------------------------------
+def _pr():
+    from xclim_amd.timeaxis import TimeAxis
+
+    return np.zeros((730, 2), np.float32), TimeAxis.daily("2000-01-01", 730, "noleap")
+
+
+def test_spi_argument_errors():
+    from xclim_amd import indices as xi
+
+    pr, t = _pr()
+    with pytest.raises(NotImplementedError, match="PWM method is not implemented for gamma distribution"):
+        xi.standardized_precipitation_index(pr, t, method="PWM")
+    with pytest.raises(NotImplementedError, match="weibull_min distribution is not yet implemented."):
+        xi.standardized_precipitation_evapotranspiration_index(pr, t, dist="weibull_min")
+    with pytest.raises(ValueError, match="Pass a value for `floc`"):
+        xi.standardized_precipitation_index(pr, t, method="APP")
+    with pytest.raises(ValueError, match="Accepted strings for `prob_zero_interpolation`"):
+        xi.standardized_precipitation_index(pr, t, prob_zero_interpolation="lower")
+    with pytest.raises(ValueError, match="Accepted strings for `plotting_position_zero`"):
+        xi.standardized_precipitation_index(pr, t, plotting_position_zero="hazen")
+
+
+def test_refusals_are_loud():
+    from xclim_amd import indices as xi
+    from xclim_amd import stats as xs
+    from xclim_amd._capi import Float64FieldError
+
+    pr, t = _pr()
+    cases = [dict(freq="W"), dict(dist="genextreme"), dict(dist="lognorm"), dict(fitkwargs={"fscale": 1.0}),
+             dict(month=[1, 2])]
+    for kw in cases:
+        with pytest.raises(xs.NotServed):
+            xi.standardized_precipitation_index(pr, t, **kw)
+    with pytest.raises(xs.NotServed):
+        xs.standardized_index(pr, t, "MS", 1, dist=object(), method="ML", zero_inflated=True, fitkwargs={}, cal_start=None,
+                              cal_end=None)
+    with pytest.raises(NotImplementedError):  # the reference's own check rejects PWM / MM for gamma first
+        xs.standardized_index_fit_params(pr, t, "MS", 1, dist="gamma", method="MM")
+    with pytest.raises(ValueError, match="If `params` is `None`"):
+        xs.standardized_index(pr, t, "MS", None, "gamma", "ML", True, None, None, None)
+    with pytest.raises(Float64FieldError):
+        xi.standardized_precipitation_index(pr.astype(np.float64), t)

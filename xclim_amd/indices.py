@@ -558,3 +558,45 @@ for _n, _f in list(globals().items()):
     if callable(_f) and not _n.startswith("_") and getattr(_f, "__module__", None) == __name__ and not isinstance(_f, type):
         globals()[_n] = _indexed(_f, 0 if _n in _MASK_LEVEL else (2 if _n in _TWO_INPUTS else 1))
 del _n, _f
+
+
+# ---- standardized indices (indices/_agro.py:987-1245) ------------------------------------------------------------------
+def _si_dist_methods(dist, method):
+    """The argument checks of standardized_precipitation_index / _evapotranspiration_index (_agro.py:1108-1124, 1211-1226)."""
+    dist_methods = {"fisk": ["ML", "APP"], "gamma": ["ML", "APP"], "genextreme": ["ML"], "lognorm": ["ML", "APP"]}
+    if isinstance(dist, str):
+        if dist in dist_methods:
+            if method not in dist_methods[dist]:
+                raise NotImplementedError(f"{method} method is not implemented for {dist} distribution")
+        else:
+            raise NotImplementedError(f"{dist} distribution is not yet implemented.")
+
+
+def standardized_precipitation_index(pr, time: TimeAxis, freq: str | None = "MS", window: int = 1, dist="gamma",
+                                     method: str = "ML", fitkwargs: dict | None = None, cal_start=None, cal_end=None,
+                                     params=None, prob_zero_interpolation="upper", plotting_position_zero="ecdf", *,
+                                     device=None, keep: bool = False, **indexer):
+    """SPI (_agro.py:987-1126): :func:`xclim_amd.stats.standardized_index` with ``zero_inflated=True``.  ``pr`` (T, *cells)
+    float32; the result (T', *cells) float64 is on ``xclim_amd.stats.preprocessed_time(time, freq)``."""
+    from . import stats
+
+    fitkwargs = fitkwargs or {}
+    _si_dist_methods(dist, method)
+    return stats.standardized_index(pr, time, freq=freq, window=window, dist=dist, method=method, zero_inflated=True,
+                                    fitkwargs=fitkwargs, cal_start=cal_start, cal_end=cal_end, params=params,
+                                    prob_zero_interpolation=prob_zero_interpolation,
+                                    plotting_position_zero=plotting_position_zero, device=device, keep=keep, **indexer)
+
+
+def standardized_precipitation_evapotranspiration_index(wb, time: TimeAxis, freq: str | None = "MS", window: int = 1,
+                                                        dist="gamma", method: str = "ML", fitkwargs: dict | None = None,
+                                                        cal_start=None, cal_end=None, params=None, *, device=None,
+                                                        keep: bool = False, **indexer):
+    """SPEI (_agro.py:1129-1245): :func:`xclim_amd.stats.standardized_index` of the water budget, not zero-inflated."""
+    from . import stats
+
+    fitkwargs = fitkwargs or {}
+    _si_dist_methods(dist, method)
+    return stats.standardized_index(wb, time, freq=freq, window=window, dist=dist, method=method, zero_inflated=False,
+                                    fitkwargs=fitkwargs, cal_start=cal_start, cal_end=cal_end, params=params,
+                                    device=device, keep=keep, **indexer)

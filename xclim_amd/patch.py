@@ -98,6 +98,13 @@ _BY_NAME = {
 }
 
 
+# the standardized indices: stats.py defines both; _agro.py (SPI / SPEI) and _hydrology.py (SSI / SGI) import
+# standardized_index by name (indices/_agro.py:36, indices/_hydrology.py:16)
+_SI_MODULE = "xclim.indices.stats"
+_SI_NAMES = ("standardized_index", "standardized_index_fit_params")
+_SI_BY_NAME = {"xclim.indices.stats": _SI_NAMES, "xclim.indices._agro": ("standardized_index",),
+               "xclim.indices._hydrology": ("standardized_index",)}
+
 _FIRE_MODULE = "xclim.indices.fire._cffwis"
 _FIRE_NAMES = ("_fire_weather_calc", "_fire_season")
 
@@ -218,6 +225,15 @@ def install(env=None, modules=None) -> list[str]:
         fire = make_adapters(*(_saved.get((_FIRE_MODULE, n), getattr(fmod, n)) for n in _FIRE_NAMES))
         for name in _FIRE_NAMES:
             patch(_FIRE_MODULE, name, fire[name])
+    # SPI / SPEI / SSI / SGI: the forms the device does not serve go to the saved originals
+    smod = resolve(_SI_MODULE)
+    if smod is not None and all(hasattr(smod, n) for n in _SI_NAMES):
+        from .stats import make_adapters as si_adapters
+
+        si = si_adapters(env, *(_saved.get((_SI_MODULE, n), getattr(smod, n)) for n in _SI_NAMES))
+        for modname, names in _SI_BY_NAME.items():
+            for name in names:
+                patch(modname, name, si[name])
     _saved_modules.update({} if modules is None else modules)
     return done
 

@@ -716,6 +716,23 @@ int xh_fire_weather(xh_ctx* ctx, int64_t T, int64_t C, int64_t st, const float* 
 int xh_overwintering_dc(xh_ctx* ctx, const float* last_dc, const float* winter_pr, int64_t n, double carry_over_fraction,
                         double wetting_efficiency_fraction, double min_dc, float* out);
 
+/* ---- McArthur Forest Fire Danger system (indices/fire/_ffdi.py) ------------------------------------------------- */
+/* xh_mcarthur: _keetch_byram_drought_index (_ffdi.py:38-89), _griffiths_drought_factor (:92-183) and the FFDI expression
+ *   of mcarthur_forest_fire_danger_index (:359-402) in one launch, one lane per cell, float64 arithmetic.
+ *   Fields (T, C) with row stride st (DEVICE), float32 or float64 as flagged: pr [mm/day] (pr_f64); tasmax [degC], hurs [%],
+ *   sfcwind [km/h] (tas_f64); smd [mm/day] and df, the drought factor FFDI reads when DF is not computed (smd_f64).
+ *   pr_annual [mm/year] (DEVICE float64, C); kbdi0 (DEVICE float64, C; NULL = 0).  lim: 0 = "xlim", 1 = "discrete".
+ *   n13 (HOST, 20 doubles): n13[k] = (k + 1) ** 1.3.
+ *   Outputs (DEVICE float64 (T, C), row stride st_out; NULL = stage not run): kbdi_out reads pr, tasmax, pr_annual, kbdi0;
+ *   df_out reads pr and the KBDI of the same launch (smd when kbdi_out is NULL), rows 0..18 NaN; ffdi_out reads hurs,
+ *   sfcwind, tasmax and the DF of the same launch (df when df_out is NULL).  FFDI rounds like numpy on the given dtypes:
+ *   the exponent is float32 with float32 constants when tas_f64 = 0, df ** 0.987 is float32 for a float32 df, and the
+ *   product is float32 when both are.  At least one output. */
+int xh_mcarthur(xh_ctx* ctx, int64_t T, int64_t C, int64_t st, int pr_f64, int tas_f64, int smd_f64, const void* pr,
+                const void* tasmax, const void* hurs, const void* sfcwind, const void* smd, const void* df,
+                const double* pr_annual, const double* kbdi0, int lim, const double* n13 /* host */, double* kbdi_out,
+                double* df_out, double* ffdi_out, int64_t st_out);
+
 /* ---- standardized indices: SPI / SPEI (indices/stats.py) --------------------------------------------------------- */
 /* xh_si_fit: the per-group fits of standardized_index_fit_params (stats.py:855-964) through _fitfunc_1d (:40-113) and
  *   _fit_start (:576-684), one lane per (cell, group), float64.  x (T, C) float32 with row stride st (DEVICE): the

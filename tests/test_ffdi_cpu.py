@@ -1,0 +1,196 @@
+"""CPU checks of the McArthur fire danger system: the numpy restatement (tests/ffdicpu.py) against the reference's own
+outputs (tests/golden/ffdi_vectors.npz, tests/golden/make_ffdi_golden.py) and known answers, the C ABI of the new entry
+point, and the argument errors of xclim_amd.ffdi (raised before any device is touched)."""
+
+import ctypes
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+sys.path.insert(0, HERE)
+sys.path.insert(0, ROOT)
+
+import ffdicpu  # noqa: E402
+
+from xclim_amd import _capi  # noqa: E402
+from xclim_amd import ffdi  # noqa: E402
+from xclim_amd import kernels as K  # noqa: E402
+
+GOLD = np.load(os.path.join(HERE, "golden", "ffdi_vectors.npz"))
+CASES = [str(c) for c in GOLD["cases"]]
+OUTS = ("kbdi", "df", "ffdi", "ffdi_df32", "df_smd")
+
+
+def decode(q):
+    """float32 fields are stored as int16 multiples of 0.1, NaN = -32768 (tests/golden/make_ffdi_golden.py: decode)."""
+    return np.where(q == -32768, np.nan, q / 10.0).astype(np.float32)
+
+
+def golden_case(name):
+    """Inputs of a golden case with TIME FIRST (fields (T, C), per-cell inputs (C)), lim, and the expected outputs (T, C)."""
+    g = {k.split("/", 1)[1]: GOLD[k] for k in GOLD.files if k.startswith(name + "/")}
+    inp = {k: (np.ascontiguousarray(decode(v).T if v.dtype == np.int16 else v.T) if v.ndim == 2 else v)
+           for k, v in g.items() if k not in OUTS}
+    inp["lim"] = int(g["lim"])
+    inp.setdefault("kbdi0", None)
+    exp = {k: np.ascontiguousarray(g[k].T) for k in OUTS if k in g}
+    return inp, exp
+
+
+# KBDI to the float64 exp of the libraries (1 ulp apart); DF the same plus its divisions; FFDI to 1e-6 relative with
+# float32 fields (numpy's float32 exp and pow are not correctly rounded)
+RTOL = {"kbdi": 1e-12, "df": 1e-12, "df_smd": 1e-12, "ffdi": 1e-6, "ffdi_df32": 1e-6}
+ATOL = {"kbdi": 1e-9, "df": 1e-12, "df_smd": 1e-12, "ffdi": 1e-9, "ffdi_df32": 1e-9}
+
+
+def check(name, got, exp, f64_fields=False):
+    rtol = 1e-12 if (f64_fields and name == "ffdi") else RTOL[name]
+    assert got.shape == exp.shape, (name, got.shape, exp.shape)
+    np.testing.assert_array_equal(np.isnan(got), np.isnan(exp), err_msg=name)
+    np.testing.assert_allclose(got.astype(np.float64), exp.astype(np.float64), rtol=rtol, atol=ATOL[name], equal_nan=True,
+                               err_msg=name)
+
+
+def test_golden_cover_the_traps():
+    lims = {int(GOLD[f"{c}/lim"]) for c in CASES}
+    assert lims == {0, 1}
+    Ts = {GOLD[f"{c}/pr"].shape[1] for c in CASES}
+    assert {20, 365, 1095} <= Ts
+    kb = np.concatenate([GOLD[f"{c}/kbdi"].ravel() for c in CASES])
+    assert (kb == 203.2).sum() > 0 and (kb == 0.0).sum() > 0  # both clamps reached
+    inputs = [golden_case(c)[0] for c in CASES]
+    assert {i["pr"].dtype for i in inputs} == {np.dtype(np.float32), np.dtype(np.float64)}
+    pr = np.concatenate([i["pr"].ravel() for i in inputs])
+    assert (pr == 2.0).any() and np.isnan(pr).any()
+    assert any(np.isnan(i["tasmax"]).any() for i in inputs)
+    assert any(np.isnan(GOLD[f"{c}/smd"]).any() for c in CASES if f"{c}/smd" in GOLD.files)
+    assert any(f"{c}/kbdi0" in GOLD.files for c in CASES) and any(f"{c}/kbdi0" not in GOLD.files for c in CASES)
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_restatement_matches_reference(name):
+    inp, exp = golden_case(name)
+    f64 = inp["pr"].dtype == np.float64
+    k, d, f = ffdicpu.chain(inp["pr"], inp["tasmax"], inp["hurs"], inp["sfcWind"], inp["pr_annual"], inp["kbdi0"],
+                            inp["lim"])
+    np.testing.assert_array_equal(k, exp["kbdi"])  # the same float64 operations: exact
+    check("df", d, exp["df"])
+    check("ffdi", f, exp["ffdi"], f64)
+    check("ffdi_df32", ffdicpu.ffdi(d.astype(np.float32), inp["tasmax"], inp["hurs"], inp["sfcWind"]), exp["ffdi_df32"], f64)
+    if "smd" in inp:
+        check("df_smd", ffdicpu.drought_factor(inp["pr"], inp["smd"], inp["lim"]), exp["df_smd"])
+
+
+# the reference's known answers (tests/test_ffdi.py of xclim): (pr, tasmax, pr_annual, kbdi0) -> last KBDI, atol 1e-5
+P10 = [10, 0, 0.1, 6, 0, 0, 0.5, 0.3, 0, 1]
+T10 = [20, 30, 20, 30, 30, 25, 40, 35, 20, 20]
+KBDI_KNOWN = [(10 * [100], 10 * [0], 1.0, 0.0, 0.0), (10 * [0], 10 * [100], 1.0, 0.0, 203.2),
+              (P10, 10 * [30], 1.0, 0.0, 7.25278), (10 * [0], T10, 1.0, 0.0, 8.46632), (P10, T10, 1.0, 0.0, 7.10174),
+              (P10, T10, 1.0, 10.0, 12.18341), (P10, T10, 100.0, 0.0, 8.45569), (P10, T10, 1.0, 203.2, 197.33375)]
+# (pr, smd, last DF with "xlim", whether "discrete" gives round(that))
+DF_KNOWN = [(17 * [0] + [5, 10, 20], 10, 0.40471, False), ([20, 10, 5] + 17 * [0], 10, 6.13148, True),
+            ([0, 30, 5, 0, 0, 5, 10, 0, 0, 2, 0, 0, 0, 0, 0, 0, 0, 1, 3, 1], 30, 6.82454, True),
+            ([0, 10, 5, 0, 0, 5, 10, 0, 0, 20, 0, 0, 0, 20, 0, 0, 0, 5, 4, 3], 30, 6.59186, False),
+            ([0, 10, 5, 0, 0, 50, 100, 0, 0, 20, 0, 0, 0, 0, 0, 0, 0, 1, 3, 1], 10, 3.91578, False),
+            ([0, 300, 5, 0, 0, 50, 100, 0, 0, 20, 0, 0, 0, 0, 0, 0, 0, 1, 3, 1], 30, 3.76635, False)]
+DF_SLIDING = [1.07024, 3.14744, 4.71645, 5.64112, 6.14665]
+
+
+def col(x, dtype=np.float64):
+    return np.asarray(x, dtype=dtype)[:, None]
+
+
+@pytest.mark.parametrize("p,t,pa,k0,exp", KBDI_KNOWN)
+def test_kbdi_known_answers(p, t, pa, k0, exp):
+    np.testing.assert_allclose(ffdicpu.kbdi(col(p), col(t), [pa], [k0])[-1, 0], exp, atol=1e-5)
+
+
+@pytest.mark.parametrize("p,s,exp,discrete", DF_KNOWN)
+def test_df_known_answers(p, s, exp, discrete):
+    np.testing.assert_allclose(ffdicpu.drought_factor(col(p), col(20 * [s]), 0)[-1, 0], exp, atol=1e-5)
+    if discrete:
+        np.testing.assert_allclose(ffdicpu.drought_factor(col(p), col(20 * [s]), 1)[-1, 0], round(exp), atol=1e-5)
+
+
+def test_df_sliding_known_answer():
+    p = np.zeros(24)
+    p[19] = 20.0
+    np.testing.assert_allclose(ffdicpu.drought_factor(col(p), col(np.full(24, 20.0)), 0)[19:, 0], DF_SLIDING, atol=1e-5)
+
+
+def test_ffdi_identity():
+    """FFDI against its original arrangement 2 exp(-0.45 + 0.987 ln D - 0.0345 H + 0.0338 T + 0.0234 V), rtol 1e-6."""
+    D, T, H, V = (col(np.arange(a, a + 10), np.float64) for a in (1, 30, 10, 10))
+    exp = 2.0 * np.exp(-0.450 + 0.987 * np.log(D) - 0.0345 * H + 0.0338 * T + 0.0234 * V)
+    np.testing.assert_allclose(ffdicpu.ffdi(D, T, H, V), exp, rtol=1e-6)
+
+
+def _header_decl(name):
+    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "xclim_hip.h")).read(), flags=re.S)
+    m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*)\);", txt)
+    assert m, name
+    return [a.strip() for a in m.group(1).split(",")]
+
+
+def test_entry_point_header_ctypes_and_exports():
+    lib = _capi.load_library()
+    assert hasattr(lib, "xh_mcarthur")
+    assert len(_header_decl("xh_mcarthur")) == 21 == len(_capi.SIGNATURES["xh_mcarthur"])
+
+
+def test_entry_point_rejects_bad_arguments():
+    """Argument errors come back as codes with a NULL context (no device is touched)."""
+    lib = _capi.load_library()
+    null = ctypes.c_void_p(0)
+    n13 = K.MCARTHUR_N13.ctypes.data_as(ctypes.c_void_p)
+    some = ctypes.c_void_p(64)  # never dereferenced: the checks fail first
+    assert lib.xh_mcarthur(null, 30, 4, 4, 0, 0, 0, *([null] * 8), 0, n13, null, null, null, 4) == _capi.XH_ERR_ARG
+    # no context
+    assert lib.xh_mcarthur(null, 30, 4, 4, 0, 0, 0, some, some, null, null, null, null, some, null, 0, n13, some, null,
+                           null, 4) == _capi.XH_ERR_ARG
+
+
+def _fields(T=30, C=3, dtype=np.float32):
+    return np.ones((T, C), dtype)
+
+
+def test_host_argument_errors():
+    x, x64 = _fields(), _fields(dtype=np.float64)
+    with pytest.raises(ValueError, match="bogus is not a valid input for `limiting_func`"):
+        ffdi.griffiths_drought_factor(x, x, "bogus")
+    with pytest.raises(ValueError, match="not a valid input for `limiting_func`"):
+        ffdi.mcarthur_indices(x, x, x, x, np.ones(3), limiting_func="XLIM")
+    with pytest.raises(IndexError):  # the reference's isel(time=19) on fewer than 20 days
+        ffdi.griffiths_drought_factor(_fields(T=19), _fields(T=19))
+    with pytest.raises(IndexError):
+        ffdi.mcarthur_indices(*([_fields(T=5)] * 4), np.ones(3))
+    with pytest.raises(TypeError, match="all float32 or all float64"):
+        ffdi.mcarthur_forest_fire_danger_index(x64, x, x64, x)
+    with pytest.raises(TypeError, match="all float32 or all float64"):
+        ffdi.mcarthur_forest_fire_danger_index(x64, x.astype(np.int32), x.astype(np.int32), x.astype(np.int32))
+    with pytest.raises(TypeError, match="all float32 or all float64"):
+        ffdi.mcarthur_indices(x, x, x64, x, np.ones(3))
+    with pytest.raises(ValueError, match="differs"):
+        ffdi.keetch_byram_drought_index(x, _fields(C=4), np.ones(3))
+    with pytest.raises(ValueError, match="does not broadcast"):
+        ffdi.keetch_byram_drought_index(x, x, np.ones(5), device=object())
+
+
+def test_adapter_forward_decisions():
+    """What the adapters hand to the reference's originals, decided before any device work."""
+    x = np.ones((3, 30), np.float32)
+    with pytest.raises(ffdi._Forward):
+        ffdi.df_ufunc(x, x, 2)
+    with pytest.raises(ffdi._Forward):
+        ffdi.df_ufunc(x.astype(np.float16), x, 0)
+    with pytest.raises(ffdi._Forward):
+        ffdi.kbdi_ufunc(x.astype(np.int64), x, np.ones(3), np.zeros(3))
+    with pytest.raises(ffdi._Forward):
+        ffdi.kbdi_ufunc(x, x, np.ones(4), np.zeros(3))  # loop shapes (3,) and (4,) do not broadcast
+    with pytest.raises(ffdi._Forward):
+        ffdi.kbdi_ufunc(x, x[:, :29], np.ones(3), np.zeros(3))  # core dimensions differ

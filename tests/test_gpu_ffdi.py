@@ -1,0 +1,210 @@
+"""The McArthur fire danger system on the device (xh_mcarthur, xclim_amd.ffdi) against the reference's own outputs
+(tests/golden/ffdi_vectors.npz) and, where no golden output exists, against the numpy restatement tests/ffdicpu.py; the
+adapter (patch.install) through a stand-in ``xclim.indices.fire._ffdi`` module."""
+
+import types
+
+import numpy as np
+import pytest
+
+import fakexr
+import ffdicpu
+from test_ffdi_cpu import CASES, DF_KNOWN, DF_SLIDING, KBDI_KNOWN, check, col, golden_case
+from xclim_amd import ffdi, patch
+from xclim_amd import kernels as K
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_device_matches_reference(dev, name):
+    inp, exp = golden_case(name)
+    lf = ["xlim", "discrete"][inp["lim"]]
+    f64 = inp["pr"].dtype == np.float64
+    pr, tas, h, w = inp["pr"], inp["tasmax"], inp["hurs"], inp["sfcWind"]
+    check("kbdi", ffdi.keetch_byram_drought_index(pr, tas, inp["pr_annual"], inp["kbdi0"], device=dev), exp["kbdi"])
+    check("df", ffdi.griffiths_drought_factor(pr, exp["kbdi"], lf, device=dev), exp["df"])
+    if "smd" in inp:
+        check("df_smd", ffdi.griffiths_drought_factor(pr, inp["smd"], lf, device=dev), exp["df_smd"])
+    got = ffdi.mcarthur_forest_fire_danger_index(exp["df"], tas, h, w, device=dev)
+    assert got.dtype == np.float64
+    check("ffdi", got, exp["ffdi"], f64)
+    got32 = ffdi.mcarthur_forest_fire_danger_index(exp["df"].astype(np.float32), tas, h, w, device=dev)
+    assert got32.dtype == exp["ffdi_df32"].dtype
+    check("ffdi_df32", got32, exp["ffdi_df32"], f64)
+    ch = ffdi.mcarthur_indices(pr, tas, h, w, inp["pr_annual"], inp["kbdi0"], lf, device=dev)
+    check("kbdi", ch.KBDI, exp["kbdi"])
+    check("df", ch.DF, exp["df"])
+    check("ffdi", ch.FFDI, exp["ffdi"], f64)
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_device_other_dtype(dev, name):
+    """float32 cases widened to float64: KBDI and DF bit for bit those of the float32 fields (widening is exact), FFDI
+    on float64 fields; float64 cases rounded to float32: against the restatement on the rounded fields."""
+    inp, exp = golden_case(name)
+    lf = ["xlim", "discrete"][inp["lim"]]
+    to = np.float64 if inp["pr"].dtype == np.float32 else np.float32
+    o = {k: inp[k].astype(to) for k in ("pr", "tasmax", "hurs", "sfcWind")}
+    ch = ffdi.mcarthur_indices(o["pr"], o["tasmax"], o["hurs"], o["sfcWind"], inp["pr_annual"], inp["kbdi0"], lf, device=dev)
+    k, d, f = ffdicpu.chain(o["pr"], o["tasmax"], o["hurs"], o["sfcWind"], inp["pr_annual"], inp["kbdi0"], inp["lim"])
+    check("kbdi", ch.KBDI, k)
+    check("df", ch.DF, d)
+    check("ffdi", ch.FFDI, f, to == np.float64)
+    if to == np.float64:
+        native = ffdi.mcarthur_indices(inp["pr"], inp["tasmax"], inp["hurs"], inp["sfcWind"], inp["pr_annual"], inp["kbdi0"],
+                                       lf, device=dev)
+        np.testing.assert_array_equal(ch.KBDI, native.KBDI)
+        np.testing.assert_array_equal(ch.DF, native.DF)
+        kb = ffdi.keetch_byram_drought_index(o["pr"], o["tasmax"], inp["pr_annual"], inp["kbdi0"], device=dev)
+        np.testing.assert_array_equal(kb, ffdi.keetch_byram_drought_index(inp["pr"], inp["tasmax"], inp["pr_annual"],
+                                                                         inp["kbdi0"], device=dev))
+        np.testing.assert_array_equal(ffdi.griffiths_drought_factor(o["pr"], kb, lf, device=dev),
+                                      ffdi.griffiths_drought_factor(inp["pr"], kb, lf, device=dev))
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_chain_is_the_three_calls_bitwise(dev, name):
+    inp, _ = golden_case(name)
+    lf = ["xlim", "discrete"][inp["lim"]]
+    pr, tas, h, w = inp["pr"], inp["tasmax"], inp["hurs"], inp["sfcWind"]
+    ch = ffdi.mcarthur_indices(pr, tas, h, w, inp["pr_annual"], inp["kbdi0"], lf, device=dev)
+    kb = ffdi.keetch_byram_drought_index(pr, tas, inp["pr_annual"], inp["kbdi0"], device=dev)
+    df = ffdi.griffiths_drought_factor(pr, kb, lf, device=dev)
+    ff = ffdi.mcarthur_forest_fire_danger_index(df, tas, h, w, device=dev)
+    np.testing.assert_array_equal(ch.KBDI, kb)
+    np.testing.assert_array_equal(ch.DF, df)
+    np.testing.assert_array_equal(ch.FFDI, ff)
+
+
+def test_known_answers_on_device(dev):
+    for p, t, pa, k0, e in KBDI_KNOWN:
+        np.testing.assert_allclose(ffdi.keetch_byram_drought_index(col(p), col(t), pa, k0, device=dev)[-1, 0], e, atol=1e-5)
+    for p, s, e, discrete in DF_KNOWN:
+        np.testing.assert_allclose(ffdi.griffiths_drought_factor(col(p), col(20 * [s]), device=dev)[-1, 0], e, atol=1e-5)
+        if discrete:
+            np.testing.assert_allclose(ffdi.griffiths_drought_factor(col(p), col(20 * [s]), "discrete", device=dev)[-1, 0],
+                                       round(e), atol=1e-5)
+    p = np.zeros(24)
+    p[19] = 20.0
+    np.testing.assert_allclose(ffdi.griffiths_drought_factor(col(p), col(np.full(24, 20.0)), device=dev)[19:, 0], DF_SLIDING,
+                               atol=1e-5)
+
+
+def _column_f64(dev, out, T, C, cells):
+    """Columns ``cells`` of a (T, C) float64 device array: transposed on the device as (T, 2C) float32 words."""
+    tr = K.transpose(dev, dev.wrap(out.ptr, (T, 2 * C), np.float32))
+    res = np.empty((T, len(cells)))
+    for j, c in enumerate(cells):
+        two = dev.wrap(tr.ptr + 2 * int(c) * T * 4, (2, T), np.float32).get()
+        res[:, j] = np.ascontiguousarray(np.stack([two[0], two[1]], axis=-1)).view(np.float64)[:, 0]
+    del tr
+    return res
+
+
+def test_30_years_1440x90_chain_against_restatement(dev):
+    """30 years x 1440 x 90 in one launch; 48 seeded cells against the restatement over the whole recurrence."""
+    T, C = 365 * 30, 1440 * 90
+    t = np.arange(T)
+    bases = [(np.zeros(T, np.float32), 9.0, 0.3), ((24 + 9 * np.sin(2 * np.pi * (t - 20) / 365.0)).astype(np.float32), 5.0, 0),
+             (np.full(T, 45.0, np.float32), 20.0, 0), (np.full(T, 18.0, np.float32), 8.0, 0)]
+    kinds = [1, 0, 0, 0]
+
+    def field(i, n, cell0=0):
+        b, amp, pw = bases[i]
+        return K.fill_synthetic(dev, T, n, kinds[i], 40 + i, b, amp, pw or 0.3, cell0=cell0)
+
+    flds = [field(i, C) for i in range(4)]
+    rng = np.random.default_rng(30)
+    pa = rng.uniform(200, 1600, C)
+    k0 = rng.uniform(0, 210, C)
+    outs = ffdi.mcarthur_indices(*flds, pa, k0, "xlim", device=dev, keep=True)
+    cells = np.sort(rng.choice(C, 48, replace=False))
+    one = [np.concatenate([field(i, 1, cell0=int(c)).get() for c in cells], axis=1) for i in range(4)]
+    exp = ffdicpu.chain(*one, pa[cells], k0[cells], 0)
+    for name, key, e in zip(("kbdi", "df", "ffdi"), ("KBDI", "DF", "FFDI"), exp):
+        check(name, _column_f64(dev, getattr(outs, key), T, C, cells), e)
+
+
+# ---- the adapter ---------------------------------------------------------------------------------------------------
+@pytest.fixture()
+def ffdimod(dev):
+    """A stand-in xclim.indices.fire._ffdi whose originals assert if they are reached (unless allowed)."""
+    import xclim_amd._capi as capi
+
+    calls = []
+
+    def orig_kbdi(*a):
+        calls.append("kbdi")
+        assert mod.allow_forward, "the original _keetch_byram_drought_index was reached"
+        return "forwarded"
+
+    def orig_df(*a):
+        calls.append("df")
+        assert mod.allow_forward, "the original _griffiths_drought_factor was reached"
+        return "forwarded"
+
+    mod = types.SimpleNamespace(_keetch_byram_drought_index=orig_kbdi, _griffiths_drought_factor=orig_df,
+                                allow_forward=False, calls=calls)
+    old = capi._default_device
+    capi._default_device = dev
+    done = patch.install(env=fakexr.make_env(), modules={"xclim.indices.fire._ffdi": mod})
+    assert {"xclim.indices.fire._ffdi._keetch_byram_drought_index", "xclim.indices.fire._ffdi._griffiths_drought_factor"} <= set(done)
+    yield mod
+    patch.uninstall()
+    capi._default_device = old
+
+
+def _time_last(a):
+    """The transposed view xr.apply_ufunc hands over: a (T, C) array with time moved last."""
+    return np.moveaxis(a, 0, -1)
+
+
+@pytest.mark.parametrize("name", ["seasonal_365_discrete_kbdi0", "nan_150", "f64_seasonal_365"])
+def test_adapter_serves_time_last_views(dev, ffdimod, name):
+    inp, exp = golden_case(name)
+    k0 = inp["kbdi0"] if inp["kbdi0"] is not None else np.zeros(inp["pr"].shape[1], inp["pr"].dtype)
+    trace = dev.start_trace()
+    try:
+        kb = ffdimod._keetch_byram_drought_index(_time_last(inp["pr"]), _time_last(inp["tasmax"]), inp["pr_annual"], k0)
+        df = ffdimod._griffiths_drought_factor(_time_last(inp["pr"]), kb, inp["lim"])
+    finally:
+        dev.stop_trace()
+    assert [n for n, _ in trace if n.startswith("xh_")] == ["xh_mcarthur", "xh_mcarthur"]
+    assert kb.shape == df.shape == inp["pr"].shape[::-1]
+    check("kbdi", np.moveaxis(kb, -1, 0), exp["kbdi"])
+    check("df", np.moveaxis(df, -1, 0), exp["df"])
+    assert ffdimod.calls == []
+
+
+def test_adapter_size1_broadcast(dev, ffdimod):
+    """apply_ufunc inserts size-1 loop axes (the (1,)-shaped pr_annual of the reference's tests): gufunc broadcasting."""
+    p, t, pa, k0, e = KBDI_KNOWN[5]
+    got = ffdimod._keetch_byram_drought_index(np.array(p, np.float64), np.array(t, np.float64), np.array([pa]),
+                                              np.array([k0]))
+    assert got.shape == (1, 10)
+    np.testing.assert_allclose(got[0, -1], e, atol=1e-5)
+    got = ffdimod._keetch_byram_drought_index(np.array([p], np.float32), np.array(t, np.float32)[None, :].repeat(3, 0),
+                                              np.array([1.0, 100.0, 1.0]), np.array([[0.0, 0.0, 203.2]]))
+    assert got.shape == (1, 3, 10)
+    np.testing.assert_allclose(got[0, :, -1], [KBDI_KNOWN[4][4], KBDI_KNOWN[6][4], KBDI_KNOWN[7][4]], atol=1e-5)
+    pw, s, e, _ = DF_KNOWN[1]
+    got = ffdimod._griffiths_drought_factor(np.array([pw] * 2, np.float32), np.full((1, 20), float(s)), 0)
+    assert got.shape == (2, 20)
+    np.testing.assert_allclose(got[:, -1], e, atol=1e-5)
+    assert np.isnan(got[:, :19]).all()
+    assert ffdimod.calls == []
+
+
+def test_adapter_forwards_what_it_does_not_serve(dev, ffdimod):
+    ffdimod.allow_forward = True
+    x = np.ones((4, 30), np.float32)
+    assert ffdimod._keetch_byram_drought_index(x.astype(np.float16), x, np.ones(4), np.zeros(4)) == "forwarded"
+    assert ffdimod._keetch_byram_drought_index(x, x.astype(np.int32), np.ones(4), np.zeros(4)) == "forwarded"
+    assert ffdimod._keetch_byram_drought_index(x, x, np.ones(5), np.zeros(4)) == "forwarded"  # loop shapes (4,), (5,)
+    assert ffdimod._griffiths_drought_factor(x.astype(np.float16), x, 0) == "forwarded"
+    assert ffdimod._griffiths_drought_factor(x, x, 2) == "forwarded"
+    assert ffdimod.calls == ["kbdi"] * 3 + ["df"] * 2
+    ffdimod.calls.clear()
+    out = ffdimod._griffiths_drought_factor(x, x, 1)  # a served form does not reach the original
+    assert out.shape == (4, 30) and out.dtype == np.float64 and ffdimod.calls == []

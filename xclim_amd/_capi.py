@@ -224,6 +224,8 @@ SIGNATURES: dict[str, list] = {
     "xh_overwintering_dc": [_vp, _vp, _vp, _i64, _dbl, _dbl, _dbl, _vp],
     "xh_si_fit": [_vp, _vp, _i64, _i64, _i64, _vp, _int, _int, _int, _int, _dbl, _int, _int, _vp, _vp, _vp, _vp],
     "xh_si_apply": [_vp, _vp, _i64, _i64, _i64, _vp, _int, _vp, _vp, _vp, _int, _dbl, _dbl, _dbl, _vp, _i64],
+    "xh_mcarthur": [_vp, _i64, _i64, _i64, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp,
+                    _i64],
 }
 _RESTYPES = {"xh_last_error": C.c_char_p}
 

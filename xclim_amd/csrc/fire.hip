@@ -17,6 +17,7 @@
 //   * The GFWED season means are numpy float32 means: a float32 sum in order, then a float32 divide (windows <= 7).
 // Python's max / min (`max(a, b)` keeps a unless b > a) are kept as written: they propagate a NaN first argument.
 #include "common.h"
+#include "pyminmax.h"
 
 namespace {
 
@@ -33,8 +34,6 @@ __constant__ double c_day_length_factor[12][3] = {
     {6.4, 1.39, -1.6}, {5.0, 1.39, -1.6}, {2.4, 1.39, -1.6}, {0.4, 1.39, 0.9},  {-1.6, 1.39, 3.8}, {-1.6, 1.39, 5.8},
     {-1.6, 1.39, 6.4}, {-1.6, 1.39, 5.0}, {-1.6, 1.39, 2.4}, {0.9, 1.39, 0.4},  {3.8, 1.39, -1.6}, {5.8, 1.39, -1.6}};
 
-__device__ __forceinline__ double pymax(double a, double b) { return b > a ? b : a; }
-__device__ __forceinline__ double pymin(double a, double b) { return b < a ? b : a; }
 __device__ __forceinline__ float f32exp(float x) { return (float)exp((double)x); }
 __device__ __forceinline__ float f32log(float x) { return (float)log((double)x); }
 __device__ __forceinline__ float f32pow(float a, float b) { return (float)pow((double)a, (double)b); }

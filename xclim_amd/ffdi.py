@@ -1,0 +1,241 @@
+"""Host mirror of the McArthur Forest Fire Danger system (reference: src/xclim/indices/fire/_ffdi.py).
+
+The Keetch-Byram drought index, the Griffiths drought factor and the McArthur forest fire danger index (Mark 5) run as ONE
+launch of ``xh_mcarthur`` (xclim_amd/csrc/ffdi.hip): one lane per cell carries the KBDI state and the 20-day rain window
+down the time-major field, and any chain of the three stages feeds the next one from registers.
+
+Inputs are numpy arrays (or device arrays) with TIME ON AXIS 0, ``(T, *cells)``, already in the units of the equations:
+pr [mm/day], tasmax [degC], hurs [%], sfcWind [km/h], smd [mm/day]; ``pr_annual`` [mm/year] and ``kbdi0`` have the cell
+shape (they are broadcast to it).  Outputs are numpy ``(T, *cells)``, or ``(T, C)`` device arrays with ``keep=True``.
+
+Dtypes.  The reference's KBDI and DF are numba gufuncs with a float64-only loop: float32 inputs are widened and the result
+is float64 (``output_dtypes=[pr.dtype]`` only sets dask's meta).  Widening is exact, so float32 and float64 fields are
+both read natively by the kernel and give float64 results; other dtypes (integers, float16) are widened to float64 here
+before the upload, which is what the gufunc's casting does.  None of this depends on ``XCLIM_AMD_FLOAT64``: no value is
+rounded.  FFDI is a numpy expression, so it keeps numpy's dtypes: tasmax, hurs and sfcWind must be all float32 or all
+float64 (TypeError otherwise); with float32 ones the exponent is float32, a float32 drought factor gives a float32
+power, and the result is float32 when both are.
+"""
+
+from __future__ import annotations
+
+from collections import namedtuple
+
+import numpy as np
+
+from . import kernels as K
+from ._capi import DeviceArray, get_device
+
+__all__ = ["keetch_byram_drought_index", "griffiths_drought_factor", "mcarthur_forest_fire_danger_index",
+           "mcarthur_indices", "McArthurIndices", "DF_WINDOW"]
+
+DF_WINDOW = 20  # _ffdi.py:118: the first drought factor is that of row 19
+
+McArthurIndices = namedtuple("McArthurIndices", ["KBDI", "DF", "FFDI"])
+
+
+def _native(a, name):
+    """A field as float32 / float64 (other dtypes widened to float64); device arrays must already be one of the two."""
+    if isinstance(a, DeviceArray):
+        if np.dtype(a.dtype) not in (np.float32, np.float64):
+            raise TypeError(f"{name}: device arrays must be float32 or float64, got {np.dtype(a.dtype).name}")
+        return a
+    a = np.asarray(a)
+    return a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+
+
+def _limit(limiting_func):
+    """_ffdi.py:329-334."""
+    if limiting_func == "xlim":
+        return 0
+    if limiting_func == "discrete":
+        return 1
+    raise ValueError(f"{limiting_func} is not a valid input for `limiting_func`")
+
+
+def _met_dtype(tasmax, hurs, sfcWind):
+    """FFDI's fields as given: all float32 or all float64 (TypeError otherwise)."""
+    tasmax, hurs, sfcWind = (x if isinstance(x, DeviceArray) else np.asarray(x) for x in (tasmax, hurs, sfcWind))
+    kinds = {np.dtype(x.dtype) for x in (tasmax, hurs, sfcWind)}
+    if len(kinds) != 1 or kinds.pop() not in (np.float32, np.float64):
+        raise TypeError("tasmax, hurs and sfcWind must be all float32 or all float64, got "
+                        f"{', '.join(np.dtype(x.dtype).name for x in (tasmax, hurs, sfcWind))}")
+
+
+def _shape(fields: dict):
+    """(T, cell_shape) of the fields; every field must have it."""
+    shapes = {n: tuple(a.shape) for n, a in fields.items()}
+    first = next(iter(shapes.values()))
+    if len(first) < 1:
+        raise ValueError("fields must have a time axis (axis 0)")
+    for n, s in shapes.items():
+        if s != first:
+            raise ValueError(f"{n}: shape {s} differs from {first}")
+    return first[0], first[1:]
+
+
+def _upload(dev, a, T, C_):
+    if isinstance(a, DeviceArray):
+        return a.reshape(T, C_)
+    return dev.to_device(np.ascontiguousarray(a).reshape(T, C_))
+
+
+def _cells(a, cell_shape, name):
+    """A per-cell input broadcast to the cell shape, as a float64 (C) array (None stays None)."""
+    if a is None:
+        return None
+    try:
+        b = np.broadcast_to(np.asarray(a, dtype=np.float64), cell_shape)
+    except ValueError:
+        raise ValueError(f"{name}: shape {np.shape(a)} does not broadcast to the cell shape {tuple(cell_shape)}") from None
+    return np.ascontiguousarray(b).reshape(-1)
+
+
+def _run(fields: dict, outputs, pr_annual=None, kbdi0=None, lim=0, device=None, keep=False):
+    T, cell_shape = _shape(fields)
+    C_ = int(np.prod(cell_shape, dtype=np.int64))
+    if T == 0 or C_ == 0:
+        empty = {o: np.empty((T,) + tuple(cell_shape), np.float64) for o in outputs}
+        return empty if not keep else {o: (device or get_device()).empty((T, C_), np.float64) for o in outputs}
+    pa, k0 = _cells(pr_annual, cell_shape, "pr_annual"), _cells(kbdi0, cell_shape, "kbdi0")
+    dev = device or get_device()
+    d = {n: _upload(dev, a, T, C_) for n, a in fields.items()}
+    outs = K.mcarthur(dev, d, dev.to_device(pa) if pa is not None else None, dev.to_device(k0) if k0 is not None else None,
+                      outputs=outputs, lim=lim)
+    if keep:
+        return outs
+    return {n: v.get().reshape((T,) + tuple(cell_shape)) for n, v in outs.items()}
+
+
+def keetch_byram_drought_index(pr, tasmax, pr_annual, kbdi0=None, *, device=None, keep=False):
+    """_ffdi.py:188-270: KBDI [mm/day], float64 ``(T, *cells)``.  ``kbdi0`` None = 0 (:252)."""
+    fields = {"pr": _native(pr, "pr"), "tasmax": _native(tasmax, "tasmax")}
+    return _run(fields, ["KBDI"], pr_annual, kbdi0, device=device, keep=keep)["KBDI"]
+
+
+def griffiths_drought_factor(pr, smd, limiting_func="xlim", *, device=None, keep=False):
+    """_ffdi.py:273-350: DF, float64 ``(T, *cells)``; rows 0..18 are NaN (the reference's ``.where``, :350).  Fewer than
+    20 rows raise IndexError, as the reference's ``isel(time=19)`` does."""
+    lim = _limit(limiting_func)
+    fields = {"pr": _native(pr, "pr"), "smd": _native(smd, "smd")}
+    T, _ = _shape(fields)
+    if T < DF_WINDOW:
+        raise IndexError(f"index {DF_WINDOW - 1} is out of bounds for axis 0 with size {T}")
+    return _run(fields, ["DF"], lim=lim, device=device, keep=keep)["DF"]
+
+
+def mcarthur_forest_fire_danger_index(drought_factor, tasmax, hurs, sfcWind, *, device=None, keep=False):
+    """_ffdi.py:359-402 on arrays: ``drought_factor ** 0.987 * exp(0.0338 tasmax - 0.0345 hurs + 0.0234 sfcWind +
+    0.243147)`` with numpy's dtypes (float32 when the drought factor and the three fields are float32, float64 otherwise;
+    ``keep=True`` returns the float64 device array, which holds the float32 values exactly)."""
+    _met_dtype(tasmax, hurs, sfcWind)
+    met = {"tasmax": _native(tasmax, "tasmax"), "hurs": _native(hurs, "hurs"), "sfcWind": _native(sfcWind, "sfcWind")}
+    df = _native(drought_factor, "drought_factor")
+    out = _run({"df": df, **met}, ["FFDI"], device=device, keep=keep)["FFDI"]
+    if keep:
+        return out
+    f32 = np.dtype(df.dtype) == np.float32 and np.dtype(met["tasmax"].dtype) == np.float32
+    return out.astype(np.float32) if f32 else out
+
+
+def mcarthur_indices(pr, tasmax, hurs, sfcWind, pr_annual, kbdi0=None, limiting_func="xlim", *, device=None, keep=False):
+    """KBDI -> DF -> FFDI in one launch: ``McArthurIndices(KBDI, DF, FFDI)``, what
+    ``mcarthur_forest_fire_danger_index(griffiths_drought_factor(pr, keetch_byram_drought_index(pr, tasmax, pr_annual,
+    kbdi0), limiting_func), tasmax, hurs, sfcWind)`` gives, bit for bit; the three are float64."""
+    lim = _limit(limiting_func)
+    _met_dtype(tasmax, hurs, sfcWind)
+    fields = {"pr": _native(pr, "pr"), "tasmax": _native(tasmax, "tasmax"), "hurs": _native(hurs, "hurs"),
+              "sfcWind": _native(sfcWind, "sfcWind")}
+    T, _ = _shape(fields)
+    if T < DF_WINDOW:
+        raise IndexError(f"index {DF_WINDOW - 1} is out of bounds for axis 0 with size {T}")
+    out = _run(fields, ["KBDI", "DF", "FFDI"], pr_annual, kbdi0, lim=lim, device=device, keep=keep)
+    return McArthurIndices(out["KBDI"], out["DF"], out["FFDI"])
+
+
+# ---- the adapter callees (patch.install): the reference's gufuncs, time LAST ----------------------------------------
+class _Forward(Exception):
+    """A form the device path does not take: the adapter hands the call to the reference's own gufunc."""
+
+
+_SERVED = (np.float32, np.float64)
+
+
+def _loop_fields(named: dict, scalars: dict):
+    """The gufunc's loop broadcast: time-last fields (…, n) and loop scalars (…) -> (n, loop shape, fields as (n, C)
+    arrays, scalars as float64 (C) arrays)."""
+    arrs = {k: np.asarray(v) for k, v in named.items()}
+    sc = {k: np.asarray(v) for k, v in scalars.items() if v is not None}
+    for k, a in list(arrs.items()) + list(sc.items()):
+        if a.dtype not in _SERVED:
+            raise _Forward(k)
+    if any(a.ndim < 1 for a in arrs.values()):
+        raise _Forward("core dimension")
+    n = {a.shape[-1] for a in arrs.values()}
+    if len(n) != 1:
+        raise _Forward("core dimension")
+    n = n.pop()
+    try:
+        loop = np.broadcast_shapes(*[a.shape[:-1] for a in arrs.values()], *[a.shape for a in sc.values()])
+    except ValueError:
+        raise _Forward("loop shape") from None
+    C_ = int(np.prod(loop, dtype=np.int64))
+    fields = {}
+    for k, a in arrs.items():
+        b = np.broadcast_to(a, loop + (n,))
+        fields[k] = np.ascontiguousarray(np.moveaxis(b, -1, 0)).reshape(n, C_)
+    cells = {k: np.ascontiguousarray(np.broadcast_to(a, loop), dtype=np.float64).reshape(-1) for k, a in sc.items()}
+    return n, loop, fields, cells
+
+
+def _time_last(out, n, loop):
+    return np.moveaxis(out.get().reshape((n,) + tuple(loop)), 0, -1)
+
+
+def kbdi_ufunc(p, t, pa, kbdi0, *, device=None):
+    """Drop-in for ``_keetch_byram_drought_index(p, t, pa, kbdi0)`` (_ffdi.py:38-89, signature ``(n),(n),(),()->(n)``) on
+    the numpy arrays ``xr.apply_ufunc`` passes: time last, float64 result of the loop shape.  Raises ``_Forward`` for
+    what the device path does not take (other dtypes, loop shapes that do not broadcast)."""
+    n, loop, f, c = _loop_fields({"pr": p, "tasmax": t}, {"pa": pa, "kbdi0": kbdi0})
+    if n == 0 or not c["pa"].size:
+        raise _Forward("empty")
+    dev = device or get_device()
+    d = {k: dev.to_device(v) for k, v in f.items()}
+    outs = K.mcarthur(dev, d, dev.to_device(c["pa"]), dev.to_device(c["kbdi0"]) if "kbdi0" in c else None,
+                      outputs=["KBDI"])
+    return _time_last(outs["KBDI"], n, loop)
+
+
+def df_ufunc(p, smd, lim, *, device=None):
+    """Drop-in for ``_griffiths_drought_factor(p, smd, lim)`` (_ffdi.py:92-183, ``(n),(n),()->(n)``), time last; rows
+    before the 20th are NaN (the reference leaves them unset and masks them afterwards).  Raises ``_Forward`` for other
+    dtypes, loop shapes that do not broadcast and ``lim`` other than 0 or 1."""
+    if np.ndim(lim) != 0 or np.asarray(lim).dtype.kind not in "iub" or int(lim) not in (0, 1):
+        raise _Forward("lim")
+    n, loop, f, _ = _loop_fields({"pr": p, "smd": smd}, {})
+    if n == 0 or not int(np.prod(loop, dtype=np.int64)):
+        raise _Forward("empty")
+    dev = device or get_device()
+    outs = K.mcarthur(dev, {k: dev.to_device(v) for k, v in f.items()}, outputs=["DF"], lim=int(lim))
+    return _time_last(outs["DF"], n, loop)
+
+
+def make_adapters(orig_kbdi, orig_df):
+    """The two module attributes patch.install() puts into xclim.indices.fire._ffdi: each forwards to the saved original
+    for the forms the device path does not take."""
+
+    def _keetch_byram_drought_index(p, t, pa, kbdi0):
+        try:
+            return kbdi_ufunc(p, t, pa, kbdi0)
+        except _Forward:
+            return orig_kbdi(p, t, pa, kbdi0)
+
+    def _griffiths_drought_factor(p, smd, lim):
+        try:
+            return df_ufunc(p, smd, lim)
+        except _Forward:
+            return orig_df(p, smd, lim)
+
+    _keetch_byram_drought_index.__wrapped__ = orig_kbdi
+    _griffiths_drought_factor.__wrapped__ = orig_df
+    return {"_keetch_byram_drought_index": _keetch_byram_drought_index, "_griffiths_drought_factor": _griffiths_drought_factor}

@@ -1025,6 +1025,62 @@ def overwintering_dc(dev: Device, last_dc: DeviceArray, winter_pr: DeviceArray, 
     return out
 
 
+MCARTHUR_LIMITS = {"xlim": 0, "discrete": 1}
+MCARTHUR_N13 = np.array([n ** 1.3 for n in range(1, 21)], dtype=np.float64)  # python's pow, as numba and the reference
+
+
+def mcarthur(dev: Device, fields: dict, pr_annual: DeviceArray | None = None, kbdi0: DeviceArray | None = None, *,
+             outputs=("KBDI", "DF", "FFDI"), lim: int = 0) -> dict:
+    """xh_mcarthur.  ``fields``: name -> (T, C) float32 or float64 DeviceArray for pr / tasmax / hurs / sfcWind / smd / df
+    (the ones the requested ``outputs`` read; hurs and sfcWind of tasmax's dtype, smd and df of one dtype); ``pr_annual``
+    and ``kbdi0`` float64 (C) (kbdi0 None = 0).  DF reads the KBDI of the same launch when both are requested (smd
+    otherwise), FFDI the DF of the same launch (df otherwise).  Returns ``{name: (T, C) float64 DeviceArray}``."""
+    outputs = [o for o in ("KBDI", "DF", "FFDI") if o in set(outputs)]
+    if not outputs or len(outputs) != len(set(outputs)):
+        raise ValueError("mcarthur: outputs must be a non-empty subset of KBDI, DF, FFDI")
+    if lim not in (0, 1):
+        raise ValueError(f"mcarthur: lim must be 0 (xlim) or 1 (discrete), got {lim!r}")
+    k, d, f = "KBDI" in outputs, "DF" in outputs, "FFDI" in outputs
+    need = {"pr": k or d, "tasmax": k or f, "hurs": f, "sfcWind": f, "smd": d and not k, "df": f and not d}
+    for name, used in need.items():
+        if used and fields.get(name) is None:
+            raise TypeError(f"mcarthur: {name} is needed for {outputs}")
+    got = {n: fields[n] for n, used in need.items() if used}
+    T, C_ = None, None
+    for n, v in got.items():
+        if np.dtype(v.dtype) not in (np.float32, np.float64):
+            raise TypeError(f"mcarthur: {n} must be float32 or float64, got {np.dtype(v.dtype).name}")
+        if (T, C_) == (None, None):
+            T, C_ = _tc(v, None)
+        elif _tc(v, None) != (T, C_):
+            raise ValueError("mcarthur: every field must have the same (T, C) shape")
+
+    def f64(*names):
+        kinds = {np.dtype(got[n].dtype) == np.float64 for n in names if n in got}
+        if len(kinds) > 1:
+            raise TypeError(f"mcarthur: {' / '.join(n for n in names if n in got)} must share one dtype")
+        return int(kinds.pop()) if kinds else 0
+
+    pr64, tas64, smd64 = f64("pr"), f64("tasmax", "hurs", "sfcWind"), f64("smd", "df")
+
+    def cell(a, name):
+        if a is None:
+            return _vp(0)
+        if np.dtype(a.dtype) != np.float64 or tuple(a.shape) != (C_,):
+            raise TypeError(f"mcarthur: {name} must be float64 ({C_},), got {np.dtype(a.dtype).name} {a.shape}")
+        return _vp(a.ptr)
+
+    if k and pr_annual is None:
+        raise TypeError("mcarthur: KBDI needs pr_annual")
+    outs = {o: dev.empty((T, C_), np.float64) for o in outputs}
+    ptr = lambda n: _vp(got[n].ptr) if n in got else _vp(0)  # noqa: E731
+    optr = lambda n: _vp(outs[n].ptr) if n in outs else _vp(0)  # noqa: E731
+    dev.call("xh_mcarthur", T, C_, C_, pr64, tas64, smd64, ptr("pr"), ptr("tasmax"), ptr("hurs"), ptr("sfcWind"), ptr("smd"),
+             ptr("df"), cell(pr_annual, "pr_annual") if k else _vp(0), cell(kbdi0, "kbdi0") if k else _vp(0), int(lim),
+             np_ptr(MCARTHUR_N13), optr("KBDI"), optr("DF"), optr("FFDI"), C_)
+    return outs
+
+
 SI_DISTS = {"gamma": 0, "fisk": 1}
 SI_METHODS = {"APP": 0, "ML": 1}
 SI_STAGING = {"auto": 0, "global": 1, "lds": 2}

@@ -107,6 +107,8 @@ _SI_BY_NAME = {"xclim.indices.stats": _SI_NAMES, "xclim.indices._agro": ("standa
 
 _FIRE_MODULE = "xclim.indices.fire._cffwis"
 _FIRE_NAMES = ("_fire_weather_calc", "_fire_season")
+_FFDI_MODULE = "xclim.indices.fire._ffdi"
+_FFDI_NAMES = ("_keetch_byram_drought_index", "_griffiths_drought_factor")
 
 
 def real_env():
@@ -225,6 +227,15 @@ def install(env=None, modules=None) -> list[str]:
         fire = make_adapters(*(_saved.get((_FIRE_MODULE, n), getattr(fmod, n)) for n in _FIRE_NAMES))
         for name in _FIRE_NAMES:
             patch(_FIRE_MODULE, name, fire[name])
+    # the McArthur system: the public KBDI / DF functions (and their indicators) reach the two gufuncs by module-global name
+    # inside xr.apply_ufunc; mcarthur_forest_fire_danger_index is one xarray expression and stays xclim's
+    dmod = resolve(_FFDI_MODULE)
+    if dmod is not None and all(hasattr(dmod, n) for n in _FFDI_NAMES):
+        from .ffdi import make_adapters as ffdi_adapters
+
+        ffdi = ffdi_adapters(*(_saved.get((_FFDI_MODULE, n), getattr(dmod, n)) for n in _FFDI_NAMES))
+        for name in _FFDI_NAMES:
+            patch(_FFDI_MODULE, name, ffdi[name])
     # SPI / SPEI / SSI / SGI: the forms the device does not serve go to the saved originals
     smod = resolve(_SI_MODULE)
     if smod is not None and all(hasattr(smod, n) for n in _SI_NAMES):

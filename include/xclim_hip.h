@@ -716,6 +716,47 @@ int xh_fire_weather(xh_ctx* ctx, int64_t T, int64_t C, int64_t st, const float* 
 int xh_overwintering_dc(xh_ctx* ctx, const float* last_dc, const float* winter_pr, int64_t n, double carry_over_fraction,
                         double wetting_efficiency_fraction, double min_dc, float* out);
 
+/* ---- potential evapotranspiration and the water budget (indices/converters.py, indices/helpers.py) ---------------- */
+/* xh_solar_table: extraterrestrial_solar_radiation (helpers.py:400-447: Spencer day_angle / solar_declination /
+ *   eccentricity_correction_factor :95-238, the daily integral of cosine_of_solar_zenith_angle with stat="integral",
+ *   sunlit=True and _sunlit_integral_of_cosine_of_solar_zenith_angle :241-397) and day_lengths without infill (:450-525)
+ *   over R rows and L latitudes, float64.  day_angle (DEVICE, R) [rad]: (decimal_year % 1) * 2 pi of each row; lat_deg
+ *   (DEVICE, L) [degrees north]; solar_constant [W m-2] (1361; MB05 1367).  Outputs (DEVICE (R, L), NULL = not
+ *   computed): ra_out [J m-2 d-1], dl_out [h] (NaN in the polar day and night).  At least one output. */
+int xh_solar_table(xh_ctx* ctx, int64_t R, int64_t L, const double* day_angle, const double* lat_deg,
+                   double solar_constant, double* ra_out, double* dl_out);
+/* xh_pet_month_table: per (month, latitude) tables of the monthly PET methods from a daily table (D, L) over WHOLE calendar
+ *   months (converters.py:1798-1812 _get_D_from_M); seg (DEVICE int64, M + 1) = first day of each month, seg[M] <= D.
+ *   kind 0: mean over the non-NaN days of day_length / 12 (TW48, :2087-2089); kind 1: sum of Ra in MJ m-2 d-1, times 0.408
+ *   (DA02, :2040-2044).  out: DEVICE float64 (M, L). */
+int xh_pet_month_table(xh_ctx* ctx, int64_t D, int64_t L, const double* daily, int64_t M, const int64_t* seg, int kind,
+                       double* out);
+/* xh_pet_daily: potential_evapotranspiration (converters.py:1890-2152) of the daily methods, element-wise, float64
+ *   arithmetic in the reference's order.  method 0 BR65 (:2000-2009), 1 HG85 (:2011-2026), 2 MB05 (:2060-2080, solar
+ *   constant 1367), 3 FAO_PM98 (:2121-2145 with fao_allen98 :1825-1874, sonntag90 :410-423, the 10 m -> 2 m wind of
+ *   helpers.py:809-850).  Fields (T, C) with row stride st (DEVICE), all float32 (f64 = 0) or all float64: tasmin, tasmax,
+ *   tas (NULL = (tasmin + tasmax) / 2; read by HG85 and MB05) [K], hurs [%], rsds / rsus / rlds / rlus [W m-2],
+ *   sfcwind [m s-1] at 10 m, pr [kg m-2 s-1] (the water budget only).  ra (DEVICE float64 (T, L)) from xh_solar_table and
+ *   lat_idx (DEVICE int32, C): row of each cell's latitude (not read by FAO_PM98).  peta / petb: MB05's a / b.  Outputs
+ *   (DEVICE float64 (T, C), row stride st_out, NULL = not written): pet_out [kg m-2 s-1] (amount2rate of mm/d then the
+ *   hydro context, :2149-2151), wb_out = pr - PET (water_budget, :2652-2740).  At least one output. */
+int xh_pet_daily(xh_ctx* ctx, int64_t T, int64_t C, int64_t st, int method, int f64, const void* tasmin,
+                 const void* tasmax, const void* tas, const void* hurs, const void* rsds, const void* rsus,
+                 const void* rlds, const void* rlus, const void* sfcwind, const void* pr, const double* ra, int64_t L,
+                 const int32_t* lat_idx, double peta, double petb, double* pet_out, double* wb_out, int64_t st_out);
+/* xh_pet_monthly: the monthly methods, one lane per cell marching down the rows of each month: method 4 TW48
+ *   (converters.py:2082-2119: tas clipped at 0 before the NaN-skipping monthly mean, the yearly heat index over the months
+ *   present, a(id)), 5 DA02 (:2028-2058: monthly means of tasmin / tasmax / tas / pr, pr in mm per pint month of
+ *   365.25 / 12 days, 0 where ab ** 0.76 is NaN).  Fields as xh_pet_daily (tasmin, tasmax, tas, pr); M months starting in
+ *   month-of-year first_month (0 = January); seg (DEVICE int64, M + 1): first row of each month, non-decreasing, seg[M] <= T;
+ *   month_table (DEVICE float64 (M, L)) from xh_pet_month_table (kind 0 for TW48, 1 for DA02); month_seconds (DEVICE
+ *   float64, M): seconds of each calendar month (amount2rate).  Means of float32 fields are float64 sums rounded once to
+ *   float32.  Outputs (DEVICE float64 (M, C), row stride st_out): pet_out [kg m-2 s-1], wb_out = monthly mean of pr - PET. */
+int xh_pet_monthly(xh_ctx* ctx, int64_t T, int64_t C, int64_t st, int method, int f64, const void* tasmin,
+                   const void* tasmax, const void* tas, const void* pr, int64_t M, int first_month, const int64_t* seg,
+                   const double* month_table, const double* month_seconds, int64_t L, const int32_t* lat_idx,
+                   double* pet_out, double* wb_out, int64_t st_out);
+
 /* ---- McArthur Forest Fire Danger system (indices/fire/_ffdi.py) ------------------------------------------------- */
 /* xh_mcarthur: _keetch_byram_drought_index (_ffdi.py:38-89), _griffiths_drought_factor (:92-183) and the FFDI expression
  *   of mcarthur_forest_fire_danger_index (:359-402) in one launch, one lane per cell, float64 arithmetic.

@@ -1,0 +1,142 @@
+"""The xarray adapter of potential evapotranspiration and the water budget, EXECUTED: ``patch.install(env, modules)`` on
+stand-in modules wired like the reference — ``xclim.indices.converters`` defines both functions (``water_budget`` calls
+``potential_evapotranspiration`` by module-global name, converters.py:2718) and the Converter indicators hold them as a
+staticmethod ``compute`` on their classes (core/indicator.py:515-517, indicators/convert/_conversion.py:418-470) — with the
+DataArray stand-in of tests/fakexr.py.  The stand-in originals only record that they were reached (the forwarded forms)."""
+
+import os
+import sys
+import types
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import fakexr  # noqa: E402
+
+from xclim_amd import converters as xc  # noqa: E402
+from xclim_amd._capi import get_device  # noqa: E402
+from xclim_amd.timeaxis import TimeAxis  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+_WB_SRC = '''
+def water_budget(pr, evspsblpot=None, tasmin=None, tasmax=None, tas=None, lat=None, hurs=None, rsds=None, rsus=None,
+                 rlds=None, rlus=None, sfcWind=None, method="BR65"):
+    reached.append("water_budget")
+    pet = potential_evapotranspiration(tasmin=tasmin, tasmax=tasmax, tas=tas, lat=lat, hurs=hurs, rsds=rsds, rsus=rsus,
+                                       rlds=rlds, rlus=rlus, sfcWind=sfcWind, method=method)
+    return ("original water_budget", pet)
+'''
+
+
+@pytest.fixture()
+def wired():
+    from xclim_amd import patch
+
+    env = fakexr.make_env()
+    reached = []
+    conv = types.ModuleType("xclim.indices.converters")
+
+    def potential_evapotranspiration(*a, **k):
+        reached.append("potential_evapotranspiration")
+        return "original potential_evapotranspiration"
+
+    conv.potential_evapotranspiration = potential_evapotranspiration
+    conv.reached = reached
+    conv._gather_lat = lambda da: fakexr.DataArray(np.linspace(-60, 60, da.shape[da.dims.index("lat")]), dims=("lat",))
+    exec(_WB_SRC, conv.__dict__)
+    ind = types.ModuleType("xclim.indicators.convert._conversion")
+    originals = {"potential_evapotranspiration": conv.potential_evapotranspiration, "water_budget_from_tas": conv.water_budget,
+                 "water_budget": conv.water_budget}
+    for name, fn in originals.items():  # one class per indicator, as Indicator.__new__ makes them
+        ind.__dict__[name] = type(f"Converter_{name}", (), {"compute": staticmethod(fn)})()
+    mods = {"xclim.indices.converters": conv, "xclim.indicators.convert._conversion": ind}
+    names = patch.install(env, mods)
+    try:
+        yield mods, names, reached, originals
+    finally:
+        patch.uninstall()
+
+
+def _fields(T=70, start="2001-03-01", ny=4, nx=3):
+    rng = np.random.default_rng(3)
+    t = TimeAxis.daily(start, T)
+    tn = (rng.uniform(270, 290, (T, ny, nx))).astype(np.float32)
+    f = {"tasmin": tn, "tasmax": tn + np.float32(6), "tas": tn + np.float32(3),
+         "pr": (rng.gamma(0.7, 8, (T, ny, nx)) / 86400).astype(np.float32)}
+    units = {"tasmin": "K", "tasmax": "K", "tas": "K", "pr": "kg m-2 s-1"}
+    return t, f, {k: fakexr.field(v, t, attrs={"units": units[k]}) for k, v in f.items()}
+
+
+def test_install_replaces_functions_and_indicator_computes(wired):
+    mods, names, _, originals = wired
+    conv, ind = mods["xclim.indices.converters"], mods["xclim.indicators.convert._conversion"]
+    for n in ("potential_evapotranspiration", "water_budget"):
+        assert f"xclim.indices.converters.{n}" in names
+    for n in originals:
+        assert f"xclim.indicators.convert._conversion.{n}.compute" in names
+        assert type(ind.__dict__[n]).__dict__["compute"].__func__.__wrapped__ is originals[n]
+    assert conv.potential_evapotranspiration.__wrapped__ is originals["potential_evapotranspiration"]
+
+
+def test_served_calls_reach_the_kernels(wired):
+    mods, _, reached, _ = wired
+    conv, ind = mods["xclim.indices.converters"], mods["xclim.indicators.convert._conversion"]
+    t, f, da = _fields()
+    lat = np.linspace(-60, 60, 4)[:, None]
+    dev = get_device()
+    dev.trace = []
+    try:
+        pet = conv.potential_evapotranspiration(tasmin=da["tasmin"], tasmax=da["tasmax"], method="HG85")
+        wb = ind.water_budget_from_tas.compute(da["pr"], tasmin=da["tasmin"], tasmax=da["tasmax"], method="BR65")
+        tw = ind.potential_evapotranspiration.compute(tas=da["tas"], method="TW48")
+        launched = [n for n, _ in dev.trace]
+    finally:
+        dev.trace = None
+    assert not reached
+    assert "xh_pet_daily" in launched and "xh_pet_monthly" in launched and "xh_solar_table" in launched
+    assert pet.dims == ("time", "lat", "lon") and pet.attrs["units"] == "kg m-2 s-1"
+    np.testing.assert_array_equal(pet.values, xc.potential_evapotranspiration(f["tasmin"], f["tasmax"], lat=lat, time=t,
+                                                                              method="HG85"))
+    np.testing.assert_array_equal(wb.values, xc.water_budget(f["pr"], f["tasmin"], f["tasmax"], lat=lat, time=t))
+    exp, months = xc.potential_evapotranspiration(tas=f["tas"], lat=lat, time=t, method="TW48")
+    np.testing.assert_array_equal(tw.values, exp)
+    np.testing.assert_array_equal(tw["time"].dt.month.values, months.month)
+
+
+@pytest.mark.parametrize("form", ["chunked", "gappy", "monthly", "evspsblpot", "method"])
+def test_forwarded_forms_reach_the_original(wired, form):
+    mods, _, reached, _ = wired
+    conv = mods["xclim.indices.converters"]
+    t, f, da = _fields()
+    kw = dict(tasmin=da["tasmin"], tasmax=da["tasmax"], method="BR65")
+    if form == "chunked":
+        kw["tasmin"] = fakexr.field(f["tasmin"], t, attrs={"units": "K"}, chunks={"lat": 2})
+    elif form in ("gappy", "monthly"):
+        keep = np.r_[0:10, 11:70] if form == "gappy" else np.flatnonzero(t.day == 1)
+        t2 = t.subset(keep)
+        kw.update(tasmin=fakexr.field(f["tasmin"][keep], t2, attrs={"units": "K"}),
+                  tasmax=fakexr.field(f["tasmax"][keep], t2, attrs={"units": "K"}))
+    elif form == "method":
+        kw["method"] = "bogus"
+    if form == "evspsblpot":
+        out = conv.water_budget(da["pr"], evspsblpot=da["pr"], **kw)
+        # the original reaches PET by module-global name: the served adapter
+        assert out[0] == "original water_budget" and out[1].attrs["units"] == "kg m-2 s-1"
+        assert reached == ["water_budget"]
+        return
+    assert conv.potential_evapotranspiration(**kw) == "original potential_evapotranspiration"
+    assert reached == ["potential_evapotranspiration"]
+
+
+def test_uninstall_restores(wired):
+    from xclim_amd import patch
+
+    mods, _, _, originals = wired
+    patch.uninstall()
+    conv, ind = mods["xclim.indices.converters"], mods["xclim.indicators.convert._conversion"]
+    assert conv.potential_evapotranspiration is originals["potential_evapotranspiration"]
+    assert conv.water_budget is originals["water_budget"]
+    for n, fn in originals.items():
+        assert type(ind.__dict__[n]).__dict__["compute"].__func__ is fn

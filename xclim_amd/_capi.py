@@ -226,6 +226,12 @@ SIGNATURES: dict[str, list] = {
     "xh_si_apply": [_vp, _vp, _i64, _i64, _i64, _vp, _int, _vp, _vp, _vp, _int, _dbl, _dbl, _dbl, _vp, _i64],
     "xh_mcarthur": [_vp, _i64, _i64, _i64, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp,
                     _i64],
+    "xh_solar_table": [_vp, _i64, _i64, _vp, _vp, _dbl, _vp, _vp],
+    "xh_pet_month_table": [_vp, _i64, _i64, _vp, _i64, _vp, _int, _vp],
+    "xh_pet_daily": [_vp, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _dbl,
+                     _dbl, _vp, _vp, _i64],
+    "xh_pet_monthly": [_vp, _i64, _i64, _i64, _int, _int, _vp, _vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                       _i64],
 }
 _RESTYPES = {"xh_last_error": C.c_char_p}
 

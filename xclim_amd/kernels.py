@@ -1025,6 +1025,133 @@ def overwintering_dc(dev: Device, last_dc: DeviceArray, winter_pr: DeviceArray, 
     return out
 
 
+PET_DAILY = {"BR65": 0, "HG85": 1, "MB05": 2, "FAO_PM98": 3}
+PET_MONTHLY = {"TW48": 4, "DA02": 5}
+_PET_FIELDS = ("tasmin", "tasmax", "tas", "hurs", "rsds", "rsus", "rlds", "rlus", "sfcWind", "pr")
+
+
+def pet_solar_table(dev: Device, day_angle, lat_deg, solar_constant: float = 1361.0, *, ra: bool = True, dl: bool = False):
+    """xh_solar_table.  ``day_angle`` (R) [rad] and ``lat_deg`` (L) host float64 arrays.  Returns ``(ra, dl)``: (R, L)
+    float64 DeviceArrays of Ra [J m-2 d-1] and the day length [h], None for the one not requested."""
+    da = np.ascontiguousarray(day_angle, dtype=np.float64)
+    la = np.ascontiguousarray(lat_deg, dtype=np.float64)
+    if da.ndim != 1 or la.ndim != 1:
+        raise ValueError("pet_solar_table: day_angle and lat_deg must be 1-D")
+    if not (ra or dl):
+        raise ValueError("pet_solar_table: no output requested")
+    R, L = len(da), len(la)
+    o_ra = dev.empty((R, L), np.float64) if ra else None
+    o_dl = dev.empty((R, L), np.float64) if dl else None
+    d_da, d_la = dev.to_device(da), dev.to_device(la)
+    dev.call("xh_solar_table", R, L, _vp(d_da.ptr), _vp(d_la.ptr), float(solar_constant),
+             _vp(o_ra.ptr) if ra else _vp(0), _vp(o_dl.ptr) if dl else _vp(0))
+    return o_ra, o_dl
+
+
+def _pet_seg(seg, n, what):
+    s = np.ascontiguousarray(seg, dtype=np.int64)
+    if s.ndim != 1 or len(s) < 1 or s[0] < 0 or s[-1] > n or np.any(np.diff(s) < 0):
+        raise ValueError(f"{what}: month offsets must be non-decreasing within [0, {n}]")
+    return s
+
+
+def pet_month_table(dev: Device, daily: DeviceArray, seg, kind: int) -> DeviceArray:
+    """xh_pet_month_table: (M, L) float64 from the (D, L) daily table; ``seg`` (M + 1) host offsets of the months' days.
+    kind 0: mean of day length / 12 over the non-NaN days (TW48); 1: 0.408 x the sum of Ra in MJ (DA02)."""
+    D, L = _tc(daily, np.float64)
+    s = _pet_seg(seg, D, "pet_month_table")
+    if kind not in (0, 1):
+        raise ValueError(f"pet_month_table: kind must be 0 or 1, got {kind!r}")
+    M = len(s) - 1
+    out = dev.empty((M, L), np.float64)
+    d_s = dev.to_device(s)  # held until the launch is enqueued: a freed buffer goes back to the pool
+    dev.call("xh_pet_month_table", D, L, _vp(daily.ptr), M, _vp(d_s.ptr), int(kind), _vp(out.ptr))
+    return out
+
+
+def _pet_fields(fields: dict, need):
+    got = {n: fields[n] for n in _PET_FIELDS if fields.get(n) is not None}
+    for n in need:
+        if n not in got:
+            raise TypeError(f"pet: {n} is needed")
+    kinds = {np.dtype(v.dtype) for v in got.values()}
+    if not got or len(kinds) != 1 or next(iter(kinds)) not in (np.float32, np.float64):
+        raise TypeError("pet: the fields must be all float32 or all float64")
+    shapes = {_tc(v, None) for v in got.values()}
+    if len(shapes) != 1:
+        raise ValueError("pet: every field must have the same (T, C) shape")
+    T, C_ = shapes.pop()
+    return got, T, C_, int(kinds.pop() == np.float64)
+
+
+def _pet_lat_idx(dev, lat_idx, C_, L):
+    li = np.ascontiguousarray(lat_idx, dtype=np.int32)
+    if li.shape != (C_,) or (C_ and (li.min() < 0 or li.max() >= L)):
+        raise ValueError(f"pet: lat_idx must be ({C_},) indices into {L} table columns")
+    return dev.to_device(li)
+
+
+def _pet_outs(dev, outputs, rows, C_, got):
+    outputs = [o for o in ("pet", "wb") if o in set(outputs)]
+    if not outputs:
+        raise ValueError("pet: outputs must be a non-empty subset of pet, wb")
+    if "wb" in outputs and "pr" not in got:
+        raise TypeError("pet: the water budget needs pr")
+    return {o: dev.empty((rows, C_), np.float64) for o in outputs}
+
+
+def pet_daily(dev: Device, method: str, fields: dict, ra: DeviceArray | None = None, lat_idx=None, *,
+              peta: float = 0.00516409319477, petb: float = 0.0874972822289, outputs=("pet",)) -> dict:
+    """xh_pet_daily.  ``fields``: name -> (T, C) DeviceArray, all float32 or all float64 (tasmin, tasmax, tas, hurs, rsds,
+    rsus, rlds, rlus, sfcWind, pr); ``ra`` (T, L) float64 from :func:`pet_solar_table` and ``lat_idx`` (C) host int
+    indices into its columns (not used by FAO_PM98).  Returns ``{"pet" | "wb": (T, C) float64 DeviceArray}``
+    [kg m-2 s-1]."""
+    code = PET_DAILY[method]
+    need = {0: ("tasmin", "tasmax"), 1: ("tasmin", "tasmax"), 2: () if fields.get("tas") is not None else ("tasmin", "tasmax"),
+            3: ("tasmin", "tasmax", "hurs", "rsds", "rsus", "rlds", "rlus", "sfcWind")}[code]
+    got, T, C_, f64 = _pet_fields(fields, need)
+    if code == 2 and "tas" not in got and not {"tasmin", "tasmax"} <= set(got):
+        raise TypeError("pet: MB05 needs tas or tasmin and tasmax")
+    outs = _pet_outs(dev, outputs, T, C_, got)
+    L, d_li = 0, None
+    if code != 3:
+        T2, L = _tc(ra, np.float64)
+        if T2 != T:
+            raise ValueError(f"pet_daily: the Ra table has {T2} rows for {T} field rows")
+        d_li = _pet_lat_idx(dev, lat_idx, C_, L)
+    ptr = lambda n: _vp(got[n].ptr) if n in got else _vp(0)  # noqa: E731
+    optr = lambda n: _vp(outs[n].ptr) if n in outs else _vp(0)  # noqa: E731
+    dev.call("xh_pet_daily", T, C_, C_, code, f64, *(ptr(n) for n in _PET_FIELDS), _vp(ra.ptr) if code != 3 else _vp(0), L,
+             _vp(d_li.ptr) if d_li is not None else _vp(0), float(peta), float(petb), optr("pet"), optr("wb"), C_)
+    return outs
+
+
+def pet_monthly(dev: Device, method: str, fields: dict, seg, first_month: int, month_table: DeviceArray, month_seconds,
+                lat_idx, *, outputs=("pet",)) -> dict:
+    """xh_pet_monthly.  ``fields`` as :func:`pet_daily` (tasmin, tasmax, tas, pr); ``seg`` (M + 1) host offsets of the
+    months' rows, ``first_month`` 0..11 the month of year of the first one, ``month_table`` (M, L) float64 from
+    :func:`pet_month_table`, ``month_seconds`` (M) host.  Returns ``{"pet" | "wb": (M, C) float64 DeviceArray}``."""
+    code = PET_MONTHLY[method]
+    need = ("tasmin", "tasmax", "pr") if code == 5 else (() if fields.get("tas") is not None else ("tasmin", "tasmax"))
+    got, T, C_, f64 = _pet_fields(fields, need)
+    s = _pet_seg(seg, T, "pet_monthly")
+    M = len(s) - 1
+    M2, L = _tc(month_table, np.float64)
+    sec = np.ascontiguousarray(month_seconds, dtype=np.float64)
+    if M2 != M or sec.shape != (M,):
+        raise ValueError(f"pet_monthly: the month table and seconds must have {M} rows")
+    if not 0 <= int(first_month) < 12:
+        raise ValueError(f"pet_monthly: first_month must be 0..11, got {first_month!r}")
+    outs = _pet_outs(dev, outputs, M, C_, got)
+    d_li = _pet_lat_idx(dev, lat_idx, C_, L)
+    ptr = lambda n: _vp(got[n].ptr) if n in got else _vp(0)  # noqa: E731
+    optr = lambda n: _vp(outs[n].ptr) if n in outs else _vp(0)  # noqa: E731
+    d_s, d_sec = dev.to_device(s), dev.to_device(sec)
+    dev.call("xh_pet_monthly", T, C_, C_, code, f64, ptr("tasmin"), ptr("tasmax"), ptr("tas"), ptr("pr"), M, int(first_month),
+             _vp(d_s.ptr), _vp(month_table.ptr), _vp(d_sec.ptr), L, _vp(d_li.ptr), optr("pet"), optr("wb"), C_)
+    return outs
+
+
 MCARTHUR_LIMITS = {"xlim": 0, "discrete": 1}
 MCARTHUR_N13 = np.array([n ** 1.3 for n in range(1, 21)], dtype=np.float64)  # python's pow, as numba and the reference
 

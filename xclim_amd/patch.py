@@ -109,6 +109,13 @@ _FIRE_MODULE = "xclim.indices.fire._cffwis"
 _FIRE_NAMES = ("_fire_weather_calc", "_fire_season")
 _FFDI_MODULE = "xclim.indices.fire._ffdi"
 _FFDI_NAMES = ("_keetch_byram_drought_index", "_griffiths_drought_factor")
+# PET and the water budget: water_budget calls potential_evapotranspiration by module-global name (converters.py:2718); the
+# three indicators hold the function objects as a staticmethod ``compute`` on their classes (core/indicator.py:515-517,
+# indicators/convert/_conversion.py:418-470)
+_PET_MODULE = "xclim.indices.converters"
+_PET_NAMES = ("potential_evapotranspiration", "water_budget")
+_PET_INDICATORS = {"xclim.indicators.convert._conversion": ("potential_evapotranspiration", "water_budget_from_tas",
+                                                           "water_budget")}
 
 
 def real_env():
@@ -236,6 +243,25 @@ def install(env=None, modules=None) -> list[str]:
         ffdi = ffdi_adapters(*(_saved.get((_FFDI_MODULE, n), getattr(dmod, n)) for n in _FFDI_NAMES))
         for name in _FFDI_NAMES:
             patch(_FFDI_MODULE, name, ffdi[name])
+    cmod = resolve(_PET_MODULE)
+    if cmod is not None and all(hasattr(cmod, n) for n in _PET_NAMES):
+        from .converters import make_adapters as pet_adapters
+
+        origs = {n: _saved.get((_PET_MODULE, n), getattr(cmod, n)) for n in _PET_NAMES}
+        pet = pet_adapters(env, origs["potential_evapotranspiration"], origs["water_budget"],
+                           getattr(cmod, "_gather_lat", None))
+        for name in _PET_NAMES:
+            patch(_PET_MODULE, name, pet[name])
+        by_orig = {id(origs[n]): pet[n] for n in _PET_NAMES}
+        for modname, names in _PET_INDICATORS.items():
+            imod = resolve(modname)
+            for name in names:
+                cls = type(getattr(imod, name, None))
+                own = cls.__dict__.get("compute") if imod is not None else None
+                if isinstance(own, staticmethod) and id(own.__func__) in by_orig and cls not in _saved_compute:
+                    _saved_compute[cls] = own
+                    cls.compute = staticmethod(by_orig[id(own.__func__)])
+                    done.append(f"{modname}.{name}.compute")
     # SPI / SPEI / SSI / SGI: the forms the device does not serve go to the saved originals
     smod = resolve(_SI_MODULE)
     if smod is not None and all(hasattr(smod, n) for n in _SI_NAMES):
@@ -251,6 +277,7 @@ def install(env=None, modules=None) -> list[str]:
 
 _INHERITED = object()  # marker in _saved: the class did not define the attribute itself (uninstall deletes the override)
 _saved_modules: dict = {}
+_saved_compute: dict = {}  # indicator class -> its original staticmethod compute
 _cleanups: list = []  # per install(): drops the valid-count cache of its wrappers
 
 
@@ -267,6 +294,9 @@ def uninstall() -> None:
                 setattr(getattr(mod, cname), meth, fn)
         else:
             setattr(mod, attr, fn)
+    for cls, fn in _saved_compute.items():
+        cls.compute = fn
+    _saved_compute.clear()
     _saved.clear()
     _saved_modules.clear()
     for fn in _cleanups:

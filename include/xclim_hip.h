@@ -805,6 +805,17 @@ int xh_si_fit(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, con
 int xh_si_apply(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, const int32_t* group /* host */, int G,
                 const double* params, const double* nzeros, const double* nnotnull, int dist, double alpha, double beta,
                 double interp, double* out, int64_t st_out);
+/* xh_si_fit_f64 / xh_si_apply_f64: the float64 FIELD twins of xh_si_fit / xh_si_apply (same templates, stdidx.hip), same
+ *   arguments, layouts and outputs except that x is float64: the field is read, compared against zero and staged in
+ *   float64, never rounded to float32.  LDS staging holds at most 32 values per group (the same 32 KB per block as the
+ *   float32 instance's 64); XH_SI_STAGE_AUTO falls back to the global work buffer (float64) beyond, XH_SI_STAGE_LDS
+ *   returns XH_ERR_LIMIT. */
+int xh_si_fit_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int64_t st, const int32_t* group /* host */, int G,
+                  int dist, int method, int has_floc, double floc, int zero_inflated, int staging, double* params,
+                  double* nzeros, double* nnotnull, int32_t* nfev);
+int xh_si_apply_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int64_t st, const int32_t* group /* host */, int G,
+                    const double* params, const double* nzeros, const double* nnotnull, int dist, double alpha, double beta,
+                    double interp, double* out, int64_t st_out);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,313 @@
+"""Standardized indices of FLOAT64 fields on the device: xh_si_fit_f64 / xh_si_apply_f64 (xclim_amd/csrc/stdidx.hip) and the
+host mirror under XCLIM_AMD_FLOAT64=native, against the reference's own fits on float64 samples
+(tests/golden/spei_vectors.npz), scipy on random grids, and the device-resident water budget -> SPEI chain."""
+
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+import scipy.stats
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import spei64cpu  # noqa: E402
+from test_gpu_stdidx import _scipy_fit, assert_params_close, assert_si_close, zero_opts  # noqa: E402
+from test_spei64_cpu import field  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "spei_vectors.npz")
+Z = np.load(GOLD)
+META = json.loads(str(Z["meta"]))
+FAST = {n for n, m in META.items() if m["method"] == "APP" or (m["dist"] == "gamma" and m["floc"] is not None)}
+LDS_MAX_F64 = 32
+
+
+def case(name):
+    return {k.split("__", 1)[1]: Z[k] for k in Z.files if k.startswith(name + "__")}, META[name]
+
+
+@pytest.fixture(scope="module")
+def dev():
+    from xclim_amd._capi import get_device
+
+    return get_device(0)
+
+
+@pytest.fixture()
+def native(monkeypatch):
+    monkeypatch.setenv("XCLIM_AMD_FLOAT64", "native")
+
+
+def _max_group(g):
+    g = np.asarray(g)
+    return int(np.bincount(g[g >= 0]).max())
+
+
+@pytest.mark.parametrize("staging", ["auto", "global", "lds"])
+@pytest.mark.parametrize("name", sorted(META))
+def test_golden_fit_and_index(dev, name, staging):
+    """The C ABI on the golden float64 series: fits within the tolerances of test_gpu_stdidx.py, the index from the
+    reference's own parameters.  LDS staging above its 32-value cap is refused with the cap in the message."""
+    from xclim_amd import kernels as K
+    from xclim_amd._capi import XclimHipError
+
+    c, m = case(name)
+    xfit = c["xp_fit"] if m["cal"] == "reuse" else c["xp"]
+    assert xfit.dtype == np.float64
+    d = dev.to_device(xfit)
+    kw = dict(floc=m["floc"], zero_inflated=m["zero_inflated"], staging=staging, want_nfev=True)
+    if staging == "lds" and _max_group(c["fit_g"]) > LDS_MAX_F64:
+        with pytest.raises(XclimHipError, match=f"xh_si_fit_f64: LDS staging holds at most {LDS_MAX_F64} values per group"):
+            K.si_fit(dev, d, c["fit_g"], m["G"], m["dist"], m["method"], **kw)
+        return
+    params, nz, nn, nfev = K.si_fit(dev, d, c["fit_g"], m["G"], m["dist"], m["method"], **kw)
+    shares = []
+    nf = nfev.get()
+    # fits stopped at the budget, and fisk fits run off to the flat c -> inf limit (loc -> -inf, scale -> inf, where the
+    # parameters are arbitrary: c ~ 1e8 in spei_fisk_ml_ms1), are compared through their index
+    settled = (nf >= 600) | ((c["params"][:, 0, :] > 1e3) & (name not in FAST))
+    assert_params_close(name, params.get(), c["params"], shares, np.where(settled, 600, nf))
+    if m["zero_inflated"]:
+        np.testing.assert_array_equal(nz.get(), c["nz"])
+        np.testing.assert_array_equal(nn.get(), c["nn"])
+    assert nf.max() <= 600
+    for n, k, tot in shares:
+        print(f"{n} [{staging}]: {k}/{tot} Nelder-Mead fits match scipy to 1e-8, {(nf >= 600).sum()} stopped at the budget, "
+              f"{int(settled.sum())} compared through the index")
+        assert k >= 0.8 * tot
+    interp, alpha, beta = zero_opts(m)
+    zi = m["zero_inflated"]
+    if settled.any():  # the index from the device's own parameters within upstream's 2e-2
+        own = K.si_apply(dev, dev.to_device(c["xp"]), c["gidx"], params, m["dist"], nz, nn, alpha=alpha, beta=beta,
+                         interp=interp).get()
+        bad = settled[c["gidx"]]
+        np.testing.assert_array_equal(np.isnan(own[bad]), np.isnan(c["spi"][bad]))
+        assert np.isclose(own[bad], c["spi"][bad], rtol=0, atol=2e-2, equal_nan=True).mean() >= 0.99
+    si = K.si_apply(dev, dev.to_device(c["xp"]), c["gidx"], dev.to_device(c["params"]), m["dist"],
+                    dev.to_device(c["nz"]) if zi else None, dev.to_device(c["nn"]) if zi else None, alpha=alpha, beta=beta,
+                    interp=interp).get()
+    assert_si_close(si, c["spi"])
+
+
+def test_float64_is_never_rounded(dev):
+    """APP parameters of a field float32 cannot hold: the float64 twin agrees with the float64 restatement to 1e-12, where
+    the same field rounded to float32 is off by ~1e-7.  A float32 narrowing anywhere in the float64 path fails this."""
+    from xclim_amd import kernels as K
+
+    c, m = case("spei_gamma_app_negfloc_ms3")
+    x = c["xp"]
+    g = c["gidx"]
+    exp, _, _, _ = spei64cpu.fit(x, g, 12, "gamma", "APP", False, -30.0)
+    got = K.si_fit(dev, dev.to_device(x), g, 12, "gamma", "APP", floc=-30.0)[0].get()
+    r32 = K.si_fit(dev, dev.to_device(x.astype(np.float32)), g, 12, "gamma", "APP", floc=-30.0)[0].get()
+    ok = np.isfinite(exp)
+    np.testing.assert_allclose(got[ok], exp[ok], rtol=1e-12, atol=0)
+    rel32 = np.abs(r32[ok] - exp[ok]) / np.abs(exp[ok])
+    assert rel32[exp[ok] != -30.0].max() > 1e-9  # the rounded field is visibly elsewhere
+    # the transform too: the float64 value against the rounded one
+    si64 = K.si_apply(dev, dev.to_device(x), g, dev.to_device(exp), "gamma").get()
+    si32 = K.si_apply(dev, dev.to_device(x.astype(np.float32)), g, dev.to_device(exp), "gamma").get()
+    ref = spei64cpu.index(x, g, exp, "gamma")
+    assert_si_close(si64, ref, atol=1e-9)
+    assert np.nanmax(np.abs(si32 - ref)) > 1e-8
+
+
+def test_float64_device_array_outside_native_is_a_type_error(dev, monkeypatch):
+    from xclim_amd import indices as xi
+    from xclim_amd.timeaxis import TimeAxis
+
+    monkeypatch.setenv("XCLIM_AMD_FLOAT64", "round")
+    t = TimeAxis.daily("2000-01-01", 730, "noleap")
+    with pytest.raises(TypeError, match="must be float32, got float64"):
+        xi.standardized_precipitation_evapotranspiration_index(dev.to_device(np.zeros((730, 3))), t)
+
+
+@pytest.mark.parametrize("name", sorted(META))
+def test_golden_host_mirror(dev, native, name):
+    """The whole chain from the float64 input under native: the device preprocessing is bitwise the golden series (the
+    same summation order), the index within the tolerances of test_gpu_stdidx.py."""
+    from xclim_amd import stats as xs
+    from xclim_amd.timeaxis import TimeAxis
+
+    c, m = case(name)
+    x = field(c, m)
+    t = TimeAxis(c["year"].astype(np.int64), c["month"].astype(np.int64), c["day"].astype(np.int64), m["calendar"])
+    kw = dict(dist=m["dist"], method=m["method"], zero_inflated=m["zero_inflated"],
+              fitkwargs={} if m["floc"] is None else {"floc": m["floc"]})
+    pz = m["interp"] if isinstance(m["interp"], str) else float(m["interp"])
+    pp = m["plotting"] if isinstance(m["plotting"], str) else tuple(m["plotting"])
+    if m["cal"] == "reuse":
+        Ta = int(c["reuse_T"])
+        params = xs.standardized_index_fit_params(x[:Ta], t.subset(slice(0, Ta)), m["freq"], m["window"], device=dev, **kw)
+        assert params.attrs["freq"] == m["freq"] and params.attrs["window"] == m["window"]
+        with pytest.warns(UserWarning, match="overrides"):
+            si = xs.standardized_index(x, t, None, None, params=params, cal_start="1999-01-01", prob_zero_interpolation=pz,
+                                       plotting_position_zero=pp, device=dev)
+    else:
+        cal = m["cal"] or (None, None)
+        si = xs.standardized_index(x, t, m["freq"], m["window"], cal_start=cal[0], cal_end=cal[1], prob_zero_interpolation=pz,
+                                   plotting_position_zero=pp, device=dev, **kw)
+    x2, _ = xs._preprocess(dev, dev.to_device(x), t, m["freq"], m["window"])
+    assert x2.dtype == np.float64
+    np.testing.assert_array_equal(x2.get(), c["xp"])
+    np.testing.assert_array_equal(np.isnan(si), np.isnan(c["spi"]))
+    if name in FAST:
+        assert_si_close(si, c["spi"], atol=1e-9)
+    else:
+        np.testing.assert_allclose(si, c["spi"], rtol=0, atol=2e-2, equal_nan=True)
+        assert np.isclose(si, c["spi"], rtol=0, atol=1e-3, equal_nan=True).mean() >= 0.97
+
+
+def test_params_from_float32_and_float64_fits(dev, native):
+    """params= with a float64 field: parameters fitted on float64 data give the one-call index exactly; parameters fitted
+    on the same values rounded to float32 apply to the float64 field too (the transform reads it in float64)."""
+    from xclim_amd import indices as xi
+    from xclim_amd import kernels as K
+    from xclim_amd import stats as xs
+    from xclim_amd.timeaxis import TimeAxis
+
+    rng = np.random.default_rng(4)
+    T, C = 365 * 12 + 40, 23
+    t = TimeAxis.daily("1990-01-01", T, "noleap")
+    wb = rng.gamma(2.0, 2.0, (T, C)) - 3.0 - np.sin(np.arange(T) / 58.0)[:, None]
+    one = xi.standardized_precipitation_evapotranspiration_index(wb, t, window=3, device=dev)
+    p64 = xs.standardized_index_fit_params(wb, t, "MS", 3, "gamma", "ML", device=dev)
+    two = xi.standardized_precipitation_evapotranspiration_index(wb, t, params=p64, device=dev)
+    np.testing.assert_array_equal(one, two)
+    assert np.isfinite(one[2:]).mean() > 0.99
+    p32 = xs.standardized_index_fit_params(wb.astype(np.float32), t, "MS", 3, "gamma", "ML", device=dev)
+    three = xi.standardized_precipitation_evapotranspiration_index(wb, t, params=p32, device=dev)
+    xp, t2 = xs._preprocess(dev, dev.to_device(wb), t, "MS", 3)
+    exp = K.si_apply(dev, xp, (t2.month - 1).astype(np.int32), p32.d_params, "gamma").get()
+    np.testing.assert_array_equal(three, exp)
+    assert not np.array_equal(p32.values, p64.values)
+
+
+def _scipy_grid(xp, month, vals, cells, dist, floc, zi, nfev):
+    same = tot = 0
+    for c in cells:
+        for g in range(12):
+            v = xp[month == g, c]
+            v = v[~np.isnan(v)]
+            if zi:
+                v = v[v != 0]
+            ref = np.array(_scipy_fit(v, dist, floc))
+            got = vals[g, :, c]
+            assert np.isnan(got).all() == np.isnan(ref).all(), (c, g, got, ref)
+            if np.isnan(ref).all():
+                continue
+            if nfev[g, c] >= 600 or ref[0] > 1e3:  # an unconverged walk or fisk's flat c -> inf limit: the distributions
+                q = lambda p: scipy.stats.norm.ppf(getattr(scipy.stats, dist).cdf(v, *p))  # noqa: E731
+                np.testing.assert_allclose(q(got), q(ref), rtol=0, atol=2e-2)
+            else:
+                np.testing.assert_allclose(got, ref, rtol=1e-3 if floc is None or dist == "fisk" else 1e-9)
+                same += np.allclose(got, ref, rtol=1e-8, atol=0)
+                tot += 1
+    return same, tot
+
+
+@pytest.mark.parametrize("dist,floc,zi", [("gamma", None, False), ("fisk", None, False), ("gamma", 0.0, True)])
+def test_random_grid_against_scipy(dev, native, dist, floc, zi):
+    """Odd cell counts, NaN prefixes, a non-contiguous float64 view; a seeded sample of cells against scipy's own fit of
+    the float64 sample (no float32 anywhere)."""
+    from xclim_amd import kernels as K
+    from xclim_amd import stats as xs
+    from xclim_amd.timeaxis import TimeAxis
+
+    rng = np.random.default_rng(31 + 2 * (dist == "fisk") + (floc is not None))
+    T, C = 365 * 23 + 151, 257
+    t = TimeAxis.daily("1971-01-01", T, "noleap")
+    if zi:
+        full = np.where(rng.random((T, C + 1)) < 0.45, rng.gamma(0.9, 4.0, (T, C + 1)), 0.0)
+    else:
+        full = rng.gamma(2.0, 2.0, (T, C + 1)) - 4.0 + rng.normal(0, 1, (T, 1))
+    full[: rng.integers(0, 400), 5] = np.nan
+    full[:800, 17] = np.nan
+    x = full[:, 1:]
+    fk = {} if floc is None else {"floc": floc}
+    p = xs.standardized_index_fit_params(x, t, "MS", 2, dist, "ML", zero_inflated=zi, fitkwargs=fk, device=dev)
+    vals = p.values
+    xp, t2 = xs._preprocess(dev, dev.to_device(np.ascontiguousarray(x)), t, "MS", 2)
+    assert xp.dtype == np.float64
+    month = (t2.month - 1).astype(np.int32)
+    nfev = K.si_fit(dev, xp, month, 12, dist, "ML", floc=floc, zero_inflated=zi, want_nfev=True)[3].get()
+    xp = xp.get()
+    same, tot = _scipy_grid(xp, month, vals, rng.choice(C, 16, replace=False), dist, floc, zi, nfev)
+    print(f"float64 {dist} floc={floc}: {same}/{tot} fits match scipy to 1e-8")
+    si = xs.standardized_index(x, t, "MS", 2, dist=dist, method="ML", zero_inflated=zi, fitkwargs=fk, device=dev)
+    exp = spei64cpu.index(xp, month.astype(int), vals, dist, p.number_of_zeros if zi else None,
+                          p.number_of_notnull if zi else None)
+    assert_si_close(si, exp, atol=1e-9)
+
+
+def monthly_wb_field(dev, years, ny, nx, seed, cells):
+    """A (12 years, ny * nx) float64 water-budget-like monthly field built on the device 12 rows at a time (float64
+    uniforms: no value is a float32); returns the device array and the host columns ``cells``."""
+    T, C = 12 * years, ny * nx
+    d = dev.empty((T, C), np.float64)
+    rng = np.random.default_rng(seed)
+    season = 2.0 + 1.5 * np.sin(2 * np.pi * (np.arange(12) - 3) / 12.0)
+    cell_shift = rng.uniform(-1.0, 1.0, C)
+    host = np.empty((T, len(cells)))
+    for y in range(years):
+        chunk = 4.0 * rng.random((12, C)) + 2.0 * rng.random((12, C)) - season[:, None] + cell_shift[None, :]
+        dev.copy2d(d.ptr + y * 12 * C * 8, C * 8, chunk.ctypes.data, C * 8, C * 8, 12, "h2d")
+        host[12 * y : 12 * y + 12] = chunk[:, cells]
+    return d, host
+
+
+def test_full_grid_monthly_spei3(dev, native):
+    """1440 x 720 cells, 70 years of monthly water budget, SPEI-3 gamma ML calibrated on 30 years, straight from a float64
+    device array: sampled cells against the float64 restatement."""
+    from xclim_amd import indices as xi
+    from xclim_amd.timeaxis import TimeAxis
+
+    Y, Xn, years = 720, 1440, 70
+    T = 12 * years
+    cells = np.random.default_rng(6).choice(Y * Xn, 16, replace=False)
+    d, host = monthly_wb_field(dev, years, Y, Xn, 8, cells)
+    t = TimeAxis(np.repeat(np.arange(1951, 1951 + years), 12), np.tile(np.arange(1, 13), years), np.ones(T, np.int64),
+                 "noleap")
+    si = xi.standardized_precipitation_evapotranspiration_index(d, t, freq="MS", window=3, cal_start="1981-01-01",
+                                                                cal_end="2010-12-31", device=dev, keep=True)
+    assert si.shape == (T, Y * Xn) and si.dtype == np.float64
+    rows = np.empty((T, len(cells)))
+    for k, c in enumerate(cells):  # the sampled columns only: T values of stride C each
+        col = np.empty(T)
+        dev.copy2d(col.ctypes.data, 8, si.ptr + int(c) * 8, Y * Xn * 8, 8, T, "d2h")
+        rows[:, k] = col
+    xp = spei64cpu.rolling_mean(host, 3)
+    gidx = (t.month - 1).astype(int)
+    cal = np.where((t.year >= 1981) & (t.year <= 2010), gidx, -1)
+    p, _, _, _ = spei64cpu.fit(xp, cal, 12, "gamma", "ML", False, None)
+    exp = spei64cpu.index(xp, gidx, p, "gamma")
+    np.testing.assert_allclose(rows, exp, rtol=0, atol=1e-3, equal_nan=True)
+    assert np.isnan(rows[:2]).all() and np.isfinite(rows[2:]).mean() > 0.99
+
+
+def test_water_budget_to_spei_stays_on_the_device(dev, native):
+    """water_budget(keep=True) -> SPEI: the float64 device array goes straight in, bitwise the same as the host round trip."""
+    from xclim_amd import converters as xc
+    from xclim_amd import indices as xi
+    from xclim_amd.timeaxis import TimeAxis
+
+    rng = np.random.default_rng(12)
+    T, ny, nx = 365 * 9 + 2, 6, 7
+    t = TimeAxis.daily("2001-01-01", T, "standard")
+    doy = np.arange(T) % 365
+    base = 283.0 + 10.0 * np.sin(2 * np.pi * (doy - 100) / 365.0)[:, None, None] + rng.normal(0, 2, (T, ny, nx))
+    spread = rng.uniform(4, 12, (T, ny, nx))
+    f = {"tasmin": (base - spread / 2).astype(np.float32), "tasmax": (base + spread / 2).astype(np.float32),
+         "tas": base.astype(np.float32)}
+    pr = (np.where(rng.random((T, ny, nx)) < 0.45, rng.gamma(0.8, 7.0, (T, ny, nx)), 0.0) / 86400).astype(np.float32)
+    lat = np.linspace(-50, 60, ny)[:, None]
+    wb = xc.water_budget(pr, **f, lat=lat, time=t, method="BR65", keep=True)
+    assert wb.dtype == np.float64 and wb.shape == (T, ny * nx)
+    on_dev = xi.standardized_precipitation_evapotranspiration_index(wb, t, window=3, device=dev)
+    host = wb.get().reshape(T, ny, nx)
+    assert (host < 0).any() and (host > 0).any()
+    via_host = xi.standardized_precipitation_evapotranspiration_index(host, t, window=3, device=dev)
+    np.testing.assert_array_equal(on_dev.reshape(via_host.shape), via_host)
+    assert np.isfinite(via_host[2:]).mean() > 0.99

@@ -1,0 +1,106 @@
+"""The xarray adapter of the standardized indices on FLOAT64 fields under XCLIM_AMD_FLOAT64=native, EXECUTED on the stand-in
+modules of tests/test_gpu_stdidx_adapter.py: the reference's SPEI body (its call of ``standardized_index``,
+indices/_agro.py:1148-1241) on a float64 water budget reaches xh_si_fit_f64 / xh_si_apply_f64 (the launch log of
+``Device.start_trace``) and never the original; the ``params=`` form too."""
+
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import fakexr  # noqa: E402
+from test_gpu_stdidx_adapter import wired  # noqa: E402,F401  (the fixture)
+
+pytestmark = pytest.mark.gpu
+
+# the call of standardized_index in the reference's SPEI body, held by module-global name
+_SPEI_SRC = '''
+def standardized_precipitation_evapotranspiration_index(wb, freq="MS", window=1, dist="gamma", method="ML",
+                                                        fitkwargs=None, cal_start=None, cal_end=None, params=None,
+                                                        **indexer):
+    return standardized_index(wb, freq=freq, window=window, dist=dist, method=method, zero_inflated=False,
+                              fitkwargs=fitkwargs or {}, cal_start=cal_start, cal_end=cal_end, params=params, **indexer)
+'''
+
+
+@pytest.fixture()
+def spei(wired, monkeypatch):  # noqa: F811
+    env, mods, names, reached, orig = wired
+    agro = mods["xclim.indices._agro"]
+    agro.standardized_index = mods["xclim.indices.stats"].standardized_index  # the patched holder, as install() left it
+    exec(_SPEI_SRC, agro.__dict__)
+    monkeypatch.setenv("XCLIM_AMD_FLOAT64", "native")
+    return agro.standardized_precipitation_evapotranspiration_index, mods, reached
+
+
+def _wb(seed=0, years=8, ny=3, nx=5):
+    from xclim_amd.timeaxis import TimeAxis
+
+    rng = np.random.default_rng(seed)
+    T = 365 * years + 17
+    t = TimeAxis.daily("2001-01-01", T, "noleap")
+    wb = rng.gamma(2.0, 2.0, (T, ny, nx)) - 3.0 - np.sin(2 * np.pi * np.arange(T) / 365.0)[:, None, None]
+    wb[:40, 1, 2] = np.nan
+    return wb, t
+
+
+def _launched(trace):
+    return [name for name, _ in trace if name.startswith("xh_si_")]
+
+
+def test_spei_on_a_float64_field_reaches_the_float64_twins(spei):
+    from xclim_amd import indices as xi
+    from xclim_amd._capi import get_device
+
+    fn, _, reached = spei
+    wb, t = _wb()
+    assert wb.dtype == np.float64
+    exp = xi.standardized_precipitation_evapotranspiration_index(wb, t, freq="MS", window=3)
+    dev = get_device()
+    trace = dev.start_trace()
+    try:
+        out = fn(fakexr.field(wb, t, attrs={"units": "mm/d"}), freq="MS", window=3)
+    finally:
+        dev.stop_trace()
+    assert not reached
+    assert _launched(trace) == ["xh_si_fit_f64", "xh_si_apply_f64"]
+    names = [n for n, _ in trace]
+    assert "xh_resample_reduce_f64" in names and "xh_rolling_reduce_f64" in names
+    assert out.dims == ("time", "lat", "lon") and out.attrs["freq"] == "MS" and out.attrs["window"] == 3
+    np.testing.assert_array_equal(out.values, exp)
+
+
+def test_params_form_on_a_float64_field(spei):
+    """fit_params on the float64 field, then params= through the SPEI body: the float64 twins, never the originals, and
+    the one-call index exactly."""
+    from xclim_amd._capi import get_device
+
+    fn, mods, reached = spei
+    st = mods["xclim.indices.stats"]
+    wb, t = _wb(1)
+    da = fakexr.field(wb, t, attrs={"units": "mm/d"})
+    dev = get_device()
+    trace = dev.start_trace()
+    try:
+        p = st.standardized_index_fit_params(da, "MS", 2, "fisk", "ML")
+        two = fn(da, params=p)
+    finally:
+        dev.stop_trace()
+    assert not reached
+    assert _launched(trace) == ["xh_si_fit_f64", "xh_si_apply_f64"]
+    assert p.dims == ("month", "dparams", "lat", "lon") and p.attrs["scipy_dist"] == "fisk"
+    one = fn(da, freq="MS", window=2, dist="fisk")
+    assert not reached
+    np.testing.assert_array_equal(two.values, one.values)
+    assert np.isfinite(one.values[1:]).mean() > 0.99
+
+
+def test_default_policy_still_forwards(spei, monkeypatch):
+    fn, _, reached = spei
+    monkeypatch.delenv("XCLIM_AMD_FLOAT64")
+    wb, t = _wb(2, years=3)
+    out = fn(fakexr.field(wb, t, attrs={"units": "mm/d"}), freq="MS", window=1)
+    assert out == "original standardized_index"
+    assert [r[0] for r in reached] == ["standardized_index"]

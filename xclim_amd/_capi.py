@@ -51,7 +51,8 @@ NATIVE_SERVED = ("compare, get_daily_events, spell_length_statistics, spell_mask
                  "cumulative_difference, temperature_sum, thresholded_statistics (growing / heating / cooling degree days), season "
                  "(growing / frost season start / end / length), first_day_threshold_reached, first / last_occurrence, domain_count, "
                  "bivariate_count_occurrences, diurnal / interday_diurnal / extreme_temperature_range, "
-                 "select_rolling_resample_op (without an indexer) and doymax / doymin")
+                 "select_rolling_resample_op (without an indexer), doymax / doymin and the standardized indices "
+                 "(standardized_index, standardized_index_fit_params: SPI / SPEI / SSI / SGI)")
 
 
 def float64_policy() -> str:
@@ -224,6 +225,8 @@ SIGNATURES: dict[str, list] = {
     "xh_overwintering_dc": [_vp, _vp, _vp, _i64, _dbl, _dbl, _dbl, _vp],
     "xh_si_fit": [_vp, _vp, _i64, _i64, _i64, _vp, _int, _int, _int, _int, _dbl, _int, _int, _vp, _vp, _vp, _vp],
     "xh_si_apply": [_vp, _vp, _i64, _i64, _i64, _vp, _int, _vp, _vp, _vp, _int, _dbl, _dbl, _dbl, _vp, _i64],
+    "xh_si_fit_f64": [_vp, _vp, _i64, _i64, _i64, _vp, _int, _int, _int, _int, _dbl, _int, _int, _vp, _vp, _vp, _vp],
+    "xh_si_apply_f64": [_vp, _vp, _i64, _i64, _i64, _vp, _int, _vp, _vp, _vp, _int, _dbl, _dbl, _dbl, _vp, _i64],
     "xh_mcarthur": [_vp, _i64, _i64, _i64, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp,
                     _i64],
     "xh_solar_table": [_vp, _i64, _i64, _vp, _vp, _dbl, _vp, _vp],

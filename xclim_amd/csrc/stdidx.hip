@@ -14,6 +14,10 @@
 // coefficients as written, and the file is built with -ffp-contract=off (no FMA contraction).  What can still differ
 // is the last bit of log / pow / lgamma, which can send a Nelder–Mead fit down a slightly different path to the same
 // optimum (tests/test_gpu_stdidx.py reports the share of fits that match scipy to 1e-8).
+//
+// The fit and the transform are templates on the field's element type: float (xh_si_fit / xh_si_apply) and double
+// (xh_si_fit_f64 / xh_si_apply_f64).  A float64 field is read, compared against zero and staged as double, never narrowed;
+// past the read both instances run the same float64 arithmetic.
 #include <math.h>
 
 #include "common.h"
@@ -21,7 +25,10 @@
 namespace {
 
 constexpr int FIT_BLOCK = 128;
-constexpr int LDS_MAX_N = 64;                            // LDS staging: FIT_BLOCK * 64 * 4 B = 32 KB per block
+// LDS staging: 256 B per lane, FIT_BLOCK * 256 B = 32 KB per block (4 blocks of 2 waves per SIMD fit in a CU's LDS):
+// 64 float values or 32 double values per lane
+template <typename E>
+constexpr int LDS_MAX_N = 256 / (int)sizeof(E);
 constexpr double LOGXMAX = 7.09782712893383973096e+02;  // log(DBL_MAX): scipy's _LOGXMAX
 constexpr double XATOL = 1e-4, FATOL = 1e-4;             // fmin(xtol=1e-4, ftol=1e-4)
 constexpr double MACHEP = 1.11022302462515654042e-16;
@@ -162,7 +169,9 @@ __device__ double dist_cdf(int dist, double v, double p0, double loc, double sca
   return 1.0 / (1.0 + pow(x, -p0));  // burr._cdf(x, c, 1) = (1 + x**-c)**-1
 }
 
-__device__ double norm_ppf_clipped(double p) {
+// forced inline here and in gamma_shape_root: called from two kernel instances, they would otherwise be outlined, which
+// would change the float32 instance's code
+__device__ __forceinline__ double norm_ppf_clipped(double p) {
   if (isnan64(p) || p < 0.0 || p > 1.0) return NAN;
   const double s = normcdfinv(p);
   return s < -SI_CLIP ? -SI_CLIP : (s > SI_CLIP ? SI_CLIP : s);
@@ -171,8 +180,9 @@ __device__ double norm_ppf_clipped(double p) {
 // ---- the sample of one lane ---------------------------------------------------------------------------------------
 // The compacted sample (NaN dropped, zeros too when zero-inflated) is staged once, either in LDS (value k of lane t at
 // lds[k * FIT_BLOCK + t]) or in a global work buffer laid out like the field (value k at work[(row0 + k) * C + c]).
+template <typename E>
 struct Sample {
-  const float* base;
+  const E* base;
   int64_t stride;
   int n;
   __device__ double operator[](int k) const { return (double)base[(int64_t)k * stride]; }
@@ -180,7 +190,8 @@ struct Sample {
 
 // _penalized_nnlf(theta, x) (scipy _distn_infrastructure.py): inf off the parameter domain; points outside the support
 // or with a non-finite log-density add 100 * log(DBL_MAX) each instead of their log-density; + n * log(scale).
-__device__ __noinline__ double nnlf(int dist, const Sample& s, double p0, double loc, double scale) {
+template <typename E>
+__device__ __noinline__ double nnlf(int dist, const Sample<E>& s, double p0, double loc, double scale) {
   if (!(p0 > 0.0) || !(scale > 0.0)) return INFINITY;
   double cst, am1;
   if (dist == XH_SI_GAMMA) {
@@ -229,7 +240,8 @@ __device__ __noinline__ double nnlf(int dist, const Sample& s, double p0, double
 }
 
 // _loc_estimation (stats.py:609-620): from the two smallest values and the largest
-__device__ double loc_estimation(const Sample& s) {
+template <typename E>
+__device__ double loc_estimation(const Sample<E>& s) {
   double x1 = INFINITY, x2 = INFINITY, xn = -INFINITY;
   for (int k = 0; k < s.n; ++k) {
     const double v = s[k];
@@ -248,7 +260,8 @@ __device__ double loc_estimation(const Sample& s) {
 
 // The start values of _fit_start (stats.py:622-673) for gamma / fisk with loc0 given: (shape0, scale0) from the values
 // above loc0.  Each mean is numpy's (pairwise sum over the filtered values) / count.
-__device__ void fit_start(int dist, const Sample& s, double loc0, double& p0, double& scale0) {
+template <typename E>
+__device__ void fit_start(int dist, const Sample<E>& s, double loc0, double& p0, double& scale0) {
   int npos = 0;
   for (int k = 0; k < s.n; ++k) npos += (s[k] - loc0 > 0.0);
   PwSum s1, s2;
@@ -276,7 +289,7 @@ __device__ void fit_start(int dist, const Sample& s, double loc0, double& p0, do
 
 // gamma_gen.fit with floc (scipy _continuous_distns.py): the root of log(a) - digamma(a) = s by scipy's brentq
 // (Zeros/brentq.c, xtol 2e-12, rtol 4 eps, 100 iterations) on [0.6, 1.4] * the Choi-Wette estimate.
-__device__ double gamma_shape_root(double s) {
+__device__ __forceinline__ double gamma_shape_root(double s) {
   if (!(s > 0.0)) return NAN;  // identical values: the bracket is [inf, inf] and brentq fails in the reference
   const double aest = (3.0 - s + sqrt((s - 3.0) * (s - 3.0) + 24.0 * s)) / (12.0 * s);
   auto f = [s](double a) { return log(a) - digamma_pos(a) - s; };
@@ -336,8 +349,8 @@ __device__ double gamma_shape_root(double s) {
 // optimize.fmin(func, x0, xtol=1e-4, ftol=1e-4, disp=0): _minimize_neldermead, non-adaptive (rho 1, chi 2, psi 1/2,
 // sigma 1/2), maxiter = maxfun = 200 N.  A call past maxfun ends the iteration where it stands, as scipy's
 // _MaxFuncCallError does.  N = 3: (shape, loc, scale); N = 2: (shape, scale) with loc fixed.  Returns the evaluations.
-template <int N>
-__device__ __noinline__ int nelder_mead(int dist, const Sample& s, double floc, double (&x)[3]) {
+template <int N, typename E>
+__device__ __noinline__ int nelder_mead(int dist, const Sample<E>& s, double floc, double (&x)[3]) {
   double sim[N + 1][N], fs[N + 1];
   const int maxfun = 200 * N, maxiter = 200 * N;
   int fcalls = 0;
@@ -477,42 +490,45 @@ __device__ __noinline__ int nelder_mead(int dist, const Sample& s, double floc, 
   return fcalls;
 }
 
+template <typename E>
 struct FitArgs {
-  const float* x;
+  const E* x;
   int64_t C, st;
   const int32_t* rows;  // the calibration rows of every group, group after group
   const int32_t* off;   // (G + 1) offsets into rows
   int dist, method, has_floc, zero_inflated, lds;
   double floc;
-  float* work;  // global staging (lds == 0): (rows, C)
+  E* work;  // global staging (lds == 0): (rows, C)
   double* params;  // (G, 3, C)
   double* nzeros;  // (G, C) or NULL
   double* nnotnull;
   int32_t* nfev;  // (G, C) or NULL
 };
 
-__global__ void __launch_bounds__(FIT_BLOCK) k_si_fit(FitArgs a) {
-  extern __shared__ float lds[];
+template <typename E>
+__global__ void __launch_bounds__(FIT_BLOCK) k_si_fit(FitArgs<E> a) {
+  extern __shared__ float lds_f[];  // the kernel's only LDS, at offset 0: aligned for double
+  E* lds = reinterpret_cast<E*>(lds_f);
   const int64_t c = (int64_t)blockIdx.x * FIT_BLOCK + threadIdx.x;
   const int g = blockIdx.y;
   if (c >= a.C) return;
   const int r0 = a.off[g], m = a.off[g + 1] - r0;
   // stage the sample: drop NaN (and zeros when zero-inflated), count the zeros and the valid values
-  float* dst = a.lds ? lds + threadIdx.x : a.work + (int64_t)r0 * a.C + c;
+  E* dst = a.lds ? lds + threadIdx.x : a.work + (int64_t)r0 * a.C + c;
   const int64_t dstride = a.lds ? FIT_BLOCK : a.C;
   int n = 0, nz = 0, nn = 0;
   for (int k = 0; k < m; ++k) {
-    const float v = a.x[(int64_t)a.rows[r0 + k] * a.st + c];
+    const E v = a.x[(int64_t)a.rows[r0 + k] * a.st + c];
     if (v != v) continue;
     ++nn;
-    if (v == 0.0f) {
+    if (v == (E)0) {
       ++nz;
       if (a.zero_inflated) continue;
     }
     dst[(int64_t)n * dstride] = v;
     ++n;
   }
-  const Sample s{dst, dstride, n};
+  const Sample<E> s{dst, dstride, n};
   double pr[3] = {NAN, NAN, NAN};
   int nfev = 0;
   if (n > 1) {
@@ -567,8 +583,9 @@ __global__ void __launch_bounds__(FIT_BLOCK) k_si_fit(FitArgs a) {
   if (a.nfev) a.nfev[(int64_t)g * a.C + c] = nfev;
 }
 
+template <typename E>
 struct ApplyArgs {
-  const float* x;
+  const E* x;
   int64_t T, C, st, st_out;
   const int32_t* group;  // (T) device: group of every row, -1 = none (NaN out)
   const double* params;  // (G, 3, C)
@@ -580,7 +597,8 @@ struct ApplyArgs {
 };
 
 // standardized_index (stats.py:1156-1190): cdf, the zero-inflated mixture, norm.ppf, clip to +-8.21; one thread per value
-__global__ void k_si_apply(ApplyArgs a) {
+template <typename E>
+__global__ void k_si_apply(ApplyArgs<E> a) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.T * a.C) return;
   const int64_t t = i / a.C, c = i - t * a.C;
@@ -606,36 +624,37 @@ __global__ void k_si_apply(ApplyArgs a) {
   a.out[t * a.st_out + c] = si;
 }
 
-}  // namespace
-
-int xh_si_fit(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, const int32_t* group, int G, int dist,
-              int method, int has_floc, double floc, int zero_inflated, int staging, double* params, double* nzeros,
-              double* nnotnull, int32_t* nfev) {
-  XH_REQUIRE(ctx && group && params, XH_ERR_ARG, "xh_si_fit: NULL argument");
-  XH_REQUIRE(T >= 0 && C >= 0 && G >= 1 && G <= 65535, XH_ERR_ARG, "xh_si_fit: bad shape (T %lld, C %lld, G %d)",
+// ---- host entry points (one template per pair of twins; fn names the entry point in error messages) -------------
+template <typename E>
+int si_fit(const char* fn, xh_ctx* ctx, const E* x, int64_t T, int64_t C, int64_t st, const int32_t* group, int G, int dist,
+           int method, int has_floc, double floc, int zero_inflated, int staging, double* params, double* nzeros,
+           double* nnotnull, int32_t* nfev) {
+  constexpr int lds_max = LDS_MAX_N<E>;
+  XH_REQUIRE(ctx && group && params, XH_ERR_ARG, "%s: NULL argument", fn);
+  XH_REQUIRE(T >= 0 && C >= 0 && G >= 1 && G <= 65535, XH_ERR_ARG, "%s: bad shape (T %lld, C %lld, G %d)", fn,
              (long long)T, (long long)C, G);
-  XH_REQUIRE(T == 0 || C == 0 || (x && st >= C), XH_ERR_LAYOUT, "xh_si_fit: needs a time-major view (st >= C)");
-  XH_REQUIRE(dist == XH_SI_GAMMA || dist == XH_SI_FISK, XH_ERR_ARG, "xh_si_fit: unknown distribution %d", dist);
-  XH_REQUIRE(method == XH_SI_APP || method == XH_SI_ML, XH_ERR_ARG, "xh_si_fit: unknown method %d", method);
-  XH_REQUIRE(method != XH_SI_APP || has_floc, XH_ERR_ARG, "xh_si_fit: the APP method needs floc");
-  XH_REQUIRE(staging >= XH_SI_STAGE_AUTO && staging <= XH_SI_STAGE_LDS, XH_ERR_ARG, "xh_si_fit: unknown staging %d", staging);
-  XH_REQUIRE((nzeros == nullptr) == (nnotnull == nullptr), XH_ERR_ARG, "xh_si_fit: nzeros and nnotnull go together");
+  XH_REQUIRE(T == 0 || C == 0 || (x && st >= C), XH_ERR_LAYOUT, "%s: needs a time-major view (st >= C)", fn);
+  XH_REQUIRE(dist == XH_SI_GAMMA || dist == XH_SI_FISK, XH_ERR_ARG, "%s: unknown distribution %d", fn, dist);
+  XH_REQUIRE(method == XH_SI_APP || method == XH_SI_ML, XH_ERR_ARG, "%s: unknown method %d", fn, method);
+  XH_REQUIRE(method != XH_SI_APP || has_floc, XH_ERR_ARG, "%s: the APP method needs floc", fn);
+  XH_REQUIRE(staging >= XH_SI_STAGE_AUTO && staging <= XH_SI_STAGE_LDS, XH_ERR_ARG, "%s: unknown staging %d", fn, staging);
+  XH_REQUIRE((nzeros == nullptr) == (nnotnull == nullptr), XH_ERR_ARG, "%s: nzeros and nnotnull go together", fn);
   if (C == 0) return XH_OK;
-  XH_REQUIRE(T * st + C < ((int64_t)1 << 40), XH_ERR_LIMIT, "xh_si_fit: field too large");
+  XH_REQUIRE(T * st + C < ((int64_t)1 << 40), XH_ERR_LIMIT, "%s: field too large", fn);
   // the rows of every group, in time order
   int32_t* off = (int32_t*)calloc((size_t)G + 1, sizeof(int32_t));
   int32_t* rows = (int32_t*)malloc(sizeof(int32_t) * (size_t)(T > 0 ? T : 1));
   if (!off || !rows) {
     free(off);
     free(rows);
-    xh_set_error("xh_si_fit: out of host memory");
+    xh_set_error("%s: out of host memory", fn);
     return XH_ERR_HIP;
   }
   for (int64_t t = 0; t < T; ++t) {
     if (group[t] < -1 || group[t] >= G) {
       free(off);
       free(rows);
-      xh_set_error("xh_si_fit: group[%lld] = %d outside -1..%d", (long long)t, (int)group[t], G - 1);
+      xh_set_error("%s: group[%lld] = %d outside -1..%d", fn, (long long)t, (int)group[t], G - 1);
       return XH_ERR_ARG;
     }
     if (group[t] >= 0) ++off[group[t] + 1];
@@ -651,7 +670,7 @@ int xh_si_fit(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, con
     if (!fill) {
       free(off);
       free(rows);
-      xh_set_error("xh_si_fit: out of host memory");
+      xh_set_error("%s: out of host memory", fn);
       return XH_ERR_HIP;
     }
     memcpy(fill, off, sizeof(int32_t) * (size_t)G);
@@ -659,11 +678,11 @@ int xh_si_fit(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, con
       if (group[t] >= 0) rows[fill[group[t]]++] = (int32_t)t;
     free(fill);
   }
-  bool lds = staging == XH_SI_STAGE_LDS || (staging == XH_SI_STAGE_AUTO && maxm <= LDS_MAX_N);
-  if (staging == XH_SI_STAGE_LDS && maxm > LDS_MAX_N) {
+  bool lds = staging == XH_SI_STAGE_LDS || (staging == XH_SI_STAGE_AUTO && maxm <= lds_max);
+  if (staging == XH_SI_STAGE_LDS && maxm > lds_max) {
     free(off);
     free(rows);
-    xh_set_error("xh_si_fit: LDS staging holds at most %d values per group, got %d", LDS_MAX_N, maxm);
+    xh_set_error("%s: LDS staging holds at most %d values per group, got %d", fn, lds_max, maxm);
     return XH_ERR_LIMIT;
   }
   size_t cur = 0;
@@ -674,7 +693,7 @@ int xh_si_fit(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, con
   free(off);
   free(rows);
   if (rc) return rc;
-  FitArgs a{};
+  FitArgs<E> a{};
   a.x = x;
   a.C = C;
   a.st = st;
@@ -692,34 +711,35 @@ int xh_si_fit(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, con
   a.nfev = nfev;
   if (!lds && nrows > 0) {
     void* w = nullptr;
-    rc = xh_big_scratch(ctx, sizeof(float) * (size_t)nrows * (size_t)C, &w);
+    rc = xh_big_scratch(ctx, sizeof(E) * (size_t)nrows * (size_t)C, &w);
     if (rc) return rc;
-    a.work = (float*)w;
+    a.work = (E*)w;
   }
-  const size_t shmem = lds ? sizeof(float) * FIT_BLOCK * (size_t)(maxm > 0 ? maxm : 1) : 0;
-  hipLaunchKernelGGL(k_si_fit, dim3((unsigned)cdiv64(C, FIT_BLOCK), (unsigned)G), dim3(FIT_BLOCK), shmem, ctx->stream, a);
+  const size_t shmem = lds ? sizeof(E) * FIT_BLOCK * (size_t)(maxm > 0 ? maxm : 1) : 0;
+  hipLaunchKernelGGL(k_si_fit<E>, dim3((unsigned)cdiv64(C, FIT_BLOCK), (unsigned)G), dim3(FIT_BLOCK), shmem, ctx->stream, a);
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
 
-int xh_si_apply(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, const int32_t* group, int G,
-                const double* params, const double* nzeros, const double* nnotnull, int dist, double alpha, double beta,
-                double interp, double* out, int64_t st_out) {
-  XH_REQUIRE(ctx && group && params && out, XH_ERR_ARG, "xh_si_apply: NULL argument");
-  XH_REQUIRE(T >= 0 && C >= 0 && G >= 1, XH_ERR_ARG, "xh_si_apply: bad shape");
-  XH_REQUIRE(T == 0 || C == 0 || (x && st >= C && st_out >= C), XH_ERR_LAYOUT, "xh_si_apply: needs time-major views");
-  XH_REQUIRE(dist == XH_SI_GAMMA || dist == XH_SI_FISK, XH_ERR_ARG, "xh_si_apply: unknown distribution %d", dist);
-  XH_REQUIRE((nzeros == nullptr) == (nnotnull == nullptr), XH_ERR_ARG, "xh_si_apply: nzeros and nnotnull go together");
+template <typename E>
+int si_apply(const char* fn, xh_ctx* ctx, const E* x, int64_t T, int64_t C, int64_t st, const int32_t* group, int G,
+             const double* params, const double* nzeros, const double* nnotnull, int dist, double alpha, double beta,
+             double interp, double* out, int64_t st_out) {
+  XH_REQUIRE(ctx && group && params && out, XH_ERR_ARG, "%s: NULL argument", fn);
+  XH_REQUIRE(T >= 0 && C >= 0 && G >= 1, XH_ERR_ARG, "%s: bad shape", fn);
+  XH_REQUIRE(T == 0 || C == 0 || (x && st >= C && st_out >= C), XH_ERR_LAYOUT, "%s: needs time-major views", fn);
+  XH_REQUIRE(dist == XH_SI_GAMMA || dist == XH_SI_FISK, XH_ERR_ARG, "%s: unknown distribution %d", fn, dist);
+  XH_REQUIRE((nzeros == nullptr) == (nnotnull == nullptr), XH_ERR_ARG, "%s: nzeros and nnotnull go together", fn);
   if (T == 0 || C == 0) return XH_OK;
-  XH_REQUIRE(T * st + C < ((int64_t)1 << 40) && T * st_out + C < ((int64_t)1 << 40), XH_ERR_LIMIT, "xh_si_apply: field too large");
+  XH_REQUIRE(T * st + C < ((int64_t)1 << 40) && T * st_out + C < ((int64_t)1 << 40), XH_ERR_LIMIT, "%s: field too large", fn);
   for (int64_t t = 0; t < T; ++t)
-    XH_REQUIRE(group[t] >= -1 && group[t] < G, XH_ERR_ARG, "xh_si_apply: group[%lld] = %d outside -1..%d", (long long)t,
+    XH_REQUIRE(group[t] >= -1 && group[t] < G, XH_ERR_ARG, "%s: group[%lld] = %d outside -1..%d", fn, (long long)t,
                (int)group[t], G - 1);
   size_t cur = 0;
   void* d_group = nullptr;
   int rc = xh_scratch_upload(ctx, &cur, group, sizeof(int32_t) * (size_t)T, &d_group);
   if (rc) return rc;
-  ApplyArgs a{};
+  ApplyArgs<E> a{};
   a.x = x;
   a.T = T;
   a.C = C;
@@ -734,7 +754,36 @@ int xh_si_apply(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, c
   a.beta = beta;
   a.interp = interp;
   a.out = out;
-  hipLaunchKernelGGL(k_si_apply, dim3((unsigned)cdiv64(T * C, XH_BLOCK)), dim3(XH_BLOCK), 0, ctx->stream, a);
+  hipLaunchKernelGGL(k_si_apply<E>, dim3((unsigned)cdiv64(T * C, XH_BLOCK)), dim3(XH_BLOCK), 0, ctx->stream, a);
   XH_LAUNCH_CHECK();
   return XH_OK;
+}
+
+}  // namespace
+
+int xh_si_fit(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, const int32_t* group, int G, int dist,
+              int method, int has_floc, double floc, int zero_inflated, int staging, double* params, double* nzeros,
+              double* nnotnull, int32_t* nfev) {
+  return si_fit("xh_si_fit", ctx, x, T, C, st, group, G, dist, method, has_floc, floc, zero_inflated, staging, params, nzeros,
+                nnotnull, nfev);
+}
+
+int xh_si_fit_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int64_t st, const int32_t* group, int G, int dist,
+                  int method, int has_floc, double floc, int zero_inflated, int staging, double* params, double* nzeros,
+                  double* nnotnull, int32_t* nfev) {
+  return si_fit("xh_si_fit_f64", ctx, x, T, C, st, group, G, dist, method, has_floc, floc, zero_inflated, staging, params,
+                nzeros, nnotnull, nfev);
+}
+
+int xh_si_apply(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, const int32_t* group, int G,
+                const double* params, const double* nzeros, const double* nnotnull, int dist, double alpha, double beta,
+                double interp, double* out, int64_t st_out) {
+  return si_apply("xh_si_apply", ctx, x, T, C, st, group, G, params, nzeros, nnotnull, dist, alpha, beta, interp, out, st_out);
+}
+
+int xh_si_apply_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int64_t st, const int32_t* group, int G,
+                    const double* params, const double* nzeros, const double* nnotnull, int dist, double alpha, double beta,
+                    double interp, double* out, int64_t st_out) {
+  return si_apply("xh_si_apply_f64", ctx, x, T, C, st, group, G, params, nzeros, nnotnull, dist, alpha, beta, interp, out,
+                  st_out);
 }

@@ -1215,9 +1215,10 @@ SI_STAGING = {"auto": 0, "global": 1, "lds": 2}
 
 def si_fit(dev: Device, x: DeviceArray, group, G: int, dist: str, method: str, floc=None, zero_inflated=False,
            staging="auto", want_nfev=False):
-    """xh_si_fit: per-(group, cell) fits of a (T, C) float32 field; ``group`` host int (T), -1 = row not used.  Returns
-    ``(params (G, 3, C) float64, nzeros, nnotnull (G, C) float64 or None, nfev (G, C) int32 or None)`` as DeviceArrays."""
-    T, C_ = _tc(x)
+    """xh_si_fit: per-(group, cell) fits of a (T, C) float32 field, or float64 (xh_si_fit_f64, read without rounding);
+    ``group`` host int (T), -1 = row not used.  Returns ``(params (G, 3, C) float64, nzeros, nnotnull (G, C) float64 or
+    None, nfev (G, C) int32 or None)`` as DeviceArrays."""
+    T, C_, f64 = _field(x)
     g = np.ascontiguousarray(group, dtype=np.int32)
     if g.shape != (T,):
         raise ValueError(f"si_fit: group must have {T} entries, got {g.shape}")
@@ -1225,17 +1226,18 @@ def si_fit(dev: Device, x: DeviceArray, group, G: int, dist: str, method: str, f
     nz = dev.empty((G, C_), np.float64) if zero_inflated else None
     nn = dev.empty((G, C_), np.float64) if zero_inflated else None
     nfev = dev.empty((G, C_), np.int32) if want_nfev else None
-    dev.call("xh_si_fit", _vp(x.ptr), T, C_, C_, np_ptr(g), int(G), SI_DISTS[dist], SI_METHODS[method], int(floc is not None),
-             float(floc if floc is not None else 0.0), int(bool(zero_inflated)), SI_STAGING[staging], _vp(params.ptr),
-             _vp(nz.ptr if nz is not None else 0), _vp(nn.ptr if nn is not None else 0), _vp(nfev.ptr if nfev is not None else 0))
+    dev.call("xh_si_fit_f64" if f64 else "xh_si_fit", _vp(x.ptr), T, C_, C_, np_ptr(g), int(G), SI_DISTS[dist],
+             SI_METHODS[method], int(floc is not None), float(floc if floc is not None else 0.0), int(bool(zero_inflated)),
+             SI_STAGING[staging], _vp(params.ptr), _vp(nz.ptr if nz is not None else 0), _vp(nn.ptr if nn is not None else 0),
+             _vp(nfev.ptr if nfev is not None else 0))
     return params, nz, nn, nfev
 
 
 def si_apply(dev: Device, x: DeviceArray, group, params: DeviceArray, dist: str, nzeros: DeviceArray | None = None,
              nnotnull: DeviceArray | None = None, alpha=0.0, beta=1.0, interp=1.0) -> DeviceArray:
-    """xh_si_apply: the standardized index (T, C) float64 of a float32 field from (G, 3, C) float64 parameters; with
-    ``nzeros`` / ``nnotnull`` ((G, C) float64) the zero-inflated mixture."""
-    T, C_ = _tc(x)
+    """xh_si_apply: the standardized index (T, C) float64 of a float32 or float64 field (xh_si_apply_f64) from (G, 3, C)
+    float64 parameters; with ``nzeros`` / ``nnotnull`` ((G, C) float64) the zero-inflated mixture."""
+    T, C_, f64 = _field(x)
     G = int(params.shape[0])
     if tuple(params.shape) != (G, 3, C_) or np.dtype(params.dtype) != np.float64:
         raise TypeError(f"si_apply: params must be float64 (G, 3, {C_}), got {np.dtype(params.dtype).name} {params.shape}")
@@ -1246,7 +1248,7 @@ def si_apply(dev: Device, x: DeviceArray, group, params: DeviceArray, dist: str,
     if g.shape != (T,):
         raise ValueError(f"si_apply: group must have {T} entries, got {g.shape}")
     out = dev.empty((T, C_), np.float64)
-    dev.call("xh_si_apply", _vp(x.ptr), T, C_, C_, np_ptr(g), G, _vp(params.ptr), _vp(nzeros.ptr if nzeros is not None else 0),
-             _vp(nnotnull.ptr if nnotnull is not None else 0), SI_DISTS[dist], float(alpha), float(beta), float(interp),
-             _vp(out.ptr), C_)
+    dev.call("xh_si_apply_f64" if f64 else "xh_si_apply", _vp(x.ptr), T, C_, C_, np_ptr(g), G, _vp(params.ptr),
+             _vp(nzeros.ptr if nzeros is not None else 0), _vp(nnotnull.ptr if nnotnull is not None else 0), SI_DISTS[dist],
+             float(alpha), float(beta), float(interp), _vp(out.ptr), C_)
     return out

@@ -1,26 +1,35 @@
 """Host mirror of the standardized indices of ``indices/stats.py`` (reference: src/xclim/indices/stats.py:770-1197).
 
 ``standardized_index_fit_params`` and ``standardized_index`` take a daily (or already resampled) field with TIME ON AXIS 0,
-``(T, *cells)``, as a numpy array or a float32 device array, plus its :class:`~xclim_amd.timeaxis.TimeAxis`.  The chain:
+``(T, *cells)``, as a numpy array or a device array, plus its :class:`~xclim_amd.timeaxis.TimeAxis`.  The chain:
 
-1. preprocess (:770-852): the ``MS`` means (``xh_resample_reduce``, NaN skipped, float32 result) and the trailing
+1. preprocess (:770-852): the ``MS`` means (``xh_resample_reduce``, NaN skipped) and the trailing
    ``rolling(time=window).mean(skipna=False)`` (``xh_rolling_reduce``, a NaN anywhere in the window gives NaN);
 2. the fits, one lane per (cell, group) in float64 (``xh_si_fit``, xclim_amd/csrc/stdidx.hip): month groups for ``MS``,
    day-of-year groups (day 366 included) for ``D``;
 3. the transform (``xh_si_apply``): cdf, the zero-inflated mixture, ``norm.ppf``, clipped to +-8.21; float64 out.
 
+Float64 fields follow ``XCLIM_AMD_FLOAT64``.  Under ``native`` (a float64 host field or device array, e.g. the
+``water_budget(..., keep=True)`` of :mod:`xclim_amd.converters`) every step runs on the float64 twins:
+``xh_resample_reduce_f64`` (the month sums added in row order), ``xh_rolling_reduce_f64`` (the window added first row to
+last), ``xh_si_fit_f64`` and ``xh_si_apply_f64``; nothing is rounded to float32.  Under ``raise`` (the default) a float64
+host field raises :class:`~xclim_amd._capi.Float64FieldError`, under ``round`` it is rounded with a PrecisionWarning; a
+float64 device array outside ``native`` is a TypeError.
+
 Served: ``dist`` "gamma" / "fisk", ``method`` "APP" (with ``fitkwargs={"floc": v}``) and "ML" with or without ``floc``.
 Refused with :class:`NotServed` (a NotImplementedError; the xarray adapter forwards these to the reference): weekly groups,
 other distributions and ``rv_continuous`` objects, the PWM / MM / MSE methods, ``fscale`` and other fit keywords, time
 selections (``**indexer``), day-of-year parameters whose calendar differs from the data's (the reference interpolates them,
-``adjust_doy_calendar``).  Float64 fields follow ``XCLIM_AMD_FLOAT64`` (no float64 twin).
+``adjust_doy_calendar``).
 
 Differences from the reference, all where the reference itself fails:
 * gamma ML with ``floc`` and a value at or below ``floc``: NaN parameters (scipy raises FitDataError);
 * a Nelder–Mead fit that ends off the parameter domain: NaN parameters (scipy raises FitError);
 * the fits see the float32 preprocessed values widened to float64 (the reference hands scipy the float32 slices, so its
   start values are float32 means); the means of step 1 are float64 sums rounded once to float32, as every float32 mean of
-  this package.
+  this package;
+* float64 fields: the rolling mean is the window sum added in order, divided by the window; xarray's own rolling mean
+  (bottleneck's running sum, or numpy's sum of the window view) can differ from it in the last bit.
 """
 
 from __future__ import annotations
@@ -31,7 +40,7 @@ import warnings
 import numpy as np
 
 from . import kernels as K
-from ._capi import DeviceArray, float64_policy, get_device, handle_float64
+from ._capi import DeviceArray, float64_native, float64_policy, get_device, handle_float64
 from .calendar import _flatten
 from .timeaxis import TimeAxis
 
@@ -161,7 +170,8 @@ def preprocessed_time(time: TimeAxis, freq: str | None) -> TimeAxis:
 
 
 def _preprocess(dev, x: DeviceArray, time: TimeAxis, freq, window: int):
-    """Resample (MS means) and roll (trailing mean, NaN-propagating): (T', C) float32 on the device + its axis."""
+    """Resample (MS means) and roll (trailing mean, NaN-propagating): (T', C) on the device in the field's dtype (float32,
+    or float64 under ``native``) + its axis."""
     if window is None or int(window) < 1:
         raise ValueError(f"window must be an integer >= 1, got {window!r}")
     if len(time) != x.shape[0]:
@@ -219,8 +229,9 @@ def _zero_options(prob_zero_interpolation, plotting_position_zero):
 
 
 def _refuse_float64(da):
-    """The XCLIM_AMD_FLOAT64 refusal before any device work (``round`` warns once, in _flatten)."""
-    if not isinstance(da, DeviceArray) and getattr(da, "dtype", None) == np.float64 and float64_policy() != "round":
+    """The XCLIM_AMD_FLOAT64 refusal before any device work (``round`` warns once, in _flatten; ``native`` uploads the
+    field as it is, _flatten(..., f64=True))."""
+    if not isinstance(da, DeviceArray) and getattr(da, "dtype", None) == np.float64 and float64_policy() == "raise":
         handle_float64(np.asarray(da), "standardized_index")
 
 
@@ -244,7 +255,7 @@ def standardized_index_fit_params(da, time: TimeAxis, freq: str | None, window: 
     _refuse_unserved(dist, method, fitkwargs, indexer, freq)
     _refuse_float64(da)
     dev = device or get_device()
-    x, cells = _flatten(da, dev)
+    x, cells = _flatten(da, dev, f64=float64_native())  # native: the _f64 twins (xh_si_fit_f64 / xh_si_apply_f64)
     x, t2 = _preprocess(dev, x, time, freq, window)
     group = _group_of(freq, t2)
     params, nz, nn, present = _fit(dev, x, t2, group, dist, method, zero_inflated, fitkwargs, np.ones(len(t2), bool), None)
@@ -283,7 +294,7 @@ def standardized_index(da, time: TimeAxis, freq: str | None, window: int | None,
     _refuse_unserved(dist, method if params is None else None, fitkwargs if params is None else {}, indexer, freq)
     _refuse_float64(da)
     dev = device or get_device()
-    x, cells = _flatten(da, dev)
+    x, cells = _flatten(da, dev, f64=float64_native())  # native: the _f64 twins (xh_si_fit_f64 / xh_si_apply_f64)
     x, t2 = _preprocess(dev, x, time, freq, window)
     if params is None:
         group = _group_of(None, t2)  # the fit runs on the preprocessed series with freq=None (stats.py:1105-1113)
@@ -343,7 +354,8 @@ def _params_table(params, da_cell_dims, cell_shape, dev):
 def make_adapters(env, orig_index, orig_fit, device=None) -> dict:
     """Same-signature replacements of ``standardized_index`` / ``standardized_index_fit_params`` (stats.py:855-1197) on
     DataArrays (time may be anywhere; results come back time first).  Forms the device does not serve (:class:`NotServed`,
-    float64 fields, chunked fields, parameters in an unserved layout) go to ``orig_index`` / ``orig_fit``."""
+    float64 fields outside ``XCLIM_AMD_FLOAT64=native``, chunked fields, parameters in an unserved layout) go to
+    ``orig_index`` / ``orig_fit``."""
     from ._capi import Float64FieldError
     from .xr_adapter import _cell_coords, _cell_dims, _tfirst, time_axis_of
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — the reference's headline workload on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu] [--no-extra] [--no-full] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-cpu] [--no-extra] [--no-full-configs] [--no-long]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ... [--workload c5]
 
 Workload (BASELINE.json configs[1]): tx90p = percentile_doy(window 5, per 90) + threshold_count(">", per-doy fp64
@@ -11,10 +11,13 @@ resident in HBM.  One "step" = one full pass of that chain through the C ABI.  W
 over RCCL at the end of each step (the only exchange on this path) — through the C ABI (xh_comm_*), no torch.
 --workload c5 runs BASELINE configs[4] instead (tx90p + EQM on the 30-year 360x1440 slab one of 8 GPUs owns).
 
-Prints ONE JSON line (rank 0): metric = grid-cells x timesteps / s (whole job), plus
+Prints ONE JSON line (rank 0): metric = grid-cells x timesteps / s (whole job).  A plain run does only what that figure
+needs: set up, warm up, time the steps, --dump-outputs, print.  With --full the line also carries
   roofline     — dominant kernel (percentile_doy), algorithmic bytes / HIP-event time on the kernel's own stream
   cpu_baseline — the numpy oracle (a port: the reference stack is not installable) on a bounded lat-band sample
-  extra        — the two other north-star workloads at the same grid (cdd run-length, EQM train+adjust)
+  extra        — the two other north-star workloads at the same grid (cdd run-length, EQM train+adjust), the full-size
+                 configurations and the other flows (--no-full-configs / --no-long trim them)
+(null / {} without --full).  --workload c5 has no legs of its own: its roofline is the whole step's, from the timed steps.
 Nothing here imports torch: with N > 1 the launcher (torch.distributed.run, or anything that sets RANK / LOCAL_RANK /
 WORLD_SIZE) only starts the ranks; rendezvous and the collective go through xclim_amd.shard.Comm -> libxclimhip.so -> RCCL.
 """
@@ -199,10 +202,15 @@ def main():
     ap.add_argument("--workload", choices=["c2", "c5"], default="c2",
                     help="c2 (default): BASELINE configs[1], tx90p on 365x1440x720 per GPU; c5: configs[4], tx90p + EQM on a "
                          "30-year 360x1440 slab per GPU")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
-    ap.add_argument("--no-full", action="store_true", help="skip the 3650-step / 30-year extras (they allocate up to 182 GB)")
-    ap.add_argument("--no-long", action="store_true", help="skip the 55 152-step extras (PMC passes: per-kernel means must not mix sizes)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline value does not need: the dominant kernel's roofline "
+                         "(launches of its own), the extra workloads and the CPU baseline; the four options below trim it")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra workloads")
+    ap.add_argument("--no-full-configs", action="store_true",
+                    help="with --full: skip the 3650-step / 30-year extras (they allocate up to 182 GB)")
+    ap.add_argument("--no-long", action="store_true",
+                    help="with --full: skip the 55 152-step extras (PMC passes: per-kernel means must not mix sizes)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the outputs of the last one as DIR/<name>.npy (float32 / float64, at most "
                          "64 MB in all: a fixed, seeded sample of cells of the larger ones)")
@@ -313,42 +321,43 @@ def main():
     units_step = float(T) * C * world
     value = units_step * args.steps / dt
 
-    # ---- roofline of the dominant kernel (per launch, this rank) ----
-    # Each kernel is timed with HIP events on the kernel's own stream INSIDE the chain (pdoy -> count -> mask repeated
-    # like the timed steps): the write-heavy percentile kernel runs ~10 % slower when it is launched back-to-back with
-    # itself (sustained 3 GB writes) than in its place in the chain, and the chain is what `value` measures.
-    reps = max(5, min(args.steps, 20))
-    ms_pdoy, ms_count, ms_mask = chain_event_times(dev, [k_pdoy, k_count, k_mask], reps)
-    E = float(T) * C
-    D = float(len(doys))
-    bytes_pdoy = 4 * E + 8 * D * C  # read x once, write (D, C) fp64
-    bytes_count = 4 * E + 8 * D * C + 8 * P * C  # read x, read per-doy fp64 table, write count+valid int32
-    roofline = {
-        "bound": "hbm",
-        "kernel": "k_pdoy_slide<5, 4> (xh_percentile_doy)",
-        "achieved": bytes_pdoy / (ms_pdoy * 1e-3) / 1e9,
-        "peak": HBM_PEAK_GBS,
-        "unit": "GB/s",
-        "frac": bytes_pdoy / (ms_pdoy * 1e-3) / 1e9 / HBM_PEAK_GBS,
-        "traffic": pmc_traffic("k_pdoy_slide<5, 4>", (T, Y, X))[0],
-        "traffic_source": pmc_traffic("k_pdoy_slide<5, 4>", (T, Y, X))[1],
-        "algorithmic_bytes": bytes_pdoy,
-        "ms": ms_pdoy,
-        "chain": {
-            "percentile_doy": {"ms": ms_pdoy, "GB/s": bytes_pdoy / ms_pdoy / 1e6},
-            "threshold_count_doy": {"ms": ms_count, "GB/s": bytes_count / ms_count / 1e6},
-            "missing_mask": {"ms": ms_mask},
-            "tx90p_unfused_total": {"ms": ms_pdoy + ms_count + ms_mask,
-                                    "GB/s": (bytes_pdoy + bytes_count) / (ms_pdoy + ms_count + ms_mask) / 1e6},
-        },
-    }
+    # ---- with --full: roofline of the dominant kernel (per launch, this rank), the extra workloads, the CPU baseline ----
+    roofline, extra, cpu = None, {}, None
+    if args.full:
+        # Each kernel is timed with HIP events on the kernel's own stream INSIDE the chain (pdoy -> count -> mask repeated
+        # like the timed steps): the write-heavy percentile kernel runs ~10 % slower when it is launched back-to-back with
+        # itself (sustained 3 GB writes) than in its place in the chain, and the chain is what `value` measures.
+        reps = max(5, min(args.steps, 20))
+        ms_pdoy, ms_count, ms_mask = chain_event_times(dev, [k_pdoy, k_count, k_mask], reps)
+        E = float(T) * C
+        D = float(len(doys))
+        bytes_pdoy = 4 * E + 8 * D * C  # read x once, write (D, C) fp64
+        bytes_count = 4 * E + 8 * D * C + 8 * P * C  # read x, read per-doy fp64 table, write count+valid int32
+        roofline = {
+            "bound": "hbm",
+            "kernel": "k_pdoy_slide<5, 4> (xh_percentile_doy)",
+            "achieved": bytes_pdoy / (ms_pdoy * 1e-3) / 1e9,
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": bytes_pdoy / (ms_pdoy * 1e-3) / 1e9 / HBM_PEAK_GBS,
+            "traffic": pmc_traffic("k_pdoy_slide<5, 4>", (T, Y, X))[0],
+            "traffic_source": pmc_traffic("k_pdoy_slide<5, 4>", (T, Y, X))[1],
+            "algorithmic_bytes": bytes_pdoy,
+            "ms": ms_pdoy,
+            "chain": {
+                "percentile_doy": {"ms": ms_pdoy, "GB/s": bytes_pdoy / ms_pdoy / 1e6},
+                "threshold_count_doy": {"ms": ms_count, "GB/s": bytes_count / ms_count / 1e6},
+                "missing_mask": {"ms": ms_mask},
+                "tx90p_unfused_total": {"ms": ms_pdoy + ms_count + ms_mask,
+                                        "GB/s": (bytes_pdoy + bytes_count) / (ms_pdoy + ms_count + ms_mask) / 1e6},
+            },
+        }
 
-    extra = {}
-    if not args.no_extra and rank == 0 and world == 1:
-        extra = bench_extra(dev, K, ta, T, C, seg, P, tasmax, tb, per, len(doys), full_configs=not args.no_full, long_series=not args.no_long)
+    if args.full and not args.no_extra and rank == 0 and world == 1:
+        extra = bench_extra(dev, K, ta, T, C, seg, P, tasmax, tb, per, len(doys), full_configs=not args.no_full_configs,
+                            long_series=not args.no_long)
 
-    cpu = None
-    if not args.no_cpu and rank == 0 and world == 1:
+    if args.full and not args.no_cpu and rank == 0 and world == 1:
         cpu = cpu_baseline(T, Y, X)
 
     if rank == 0:
@@ -920,7 +929,7 @@ def bench_bootstrap(dev, K, Cb):
 
 def bench_c5_slab(dev, K):
     """The per-GPU work of BASELINE configs[4] (`--workload c5 --gpus 1`: tx90p + EQM train + adjust on ONE 360 x 1440 slab of
-    the 2880 x 1440 grid, 30 years) inside the default line — the N = 1 anchor of a future 8-GPU SCALE run lives in the
+    the 2880 x 1440 grid, 30 years) inside the --full line — the N = 1 anchor of a future 8-GPU SCALE run lives in the
     same file (VERDICT r4 #8).  No exchange (one rank)."""
     from xclim_amd.timeaxis import TimeAxis
 

@@ -67,7 +67,7 @@ def test_bench_two_ranks_on_one_device(tmp_path, workload, grid):
     env = dict(os.environ, WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT="29547", LOCAL_RANK="0",
                XH_RENDEZVOUS_DIR=str(tmp_path), XH_RENDEZVOUS_KEY=f"two_{workload}")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--grid", grid,
-           "--workload", workload, "--no-cpu", "--no-extra"]
+           "--workload", workload, "--full", "--no-cpu", "--no-extra"]
     procs = [subprocess.Popen(cmd, env=dict(env, RANK=str(r)), cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
              for r in (1, 0)]
     outs = [p.communicate(timeout=600) for p in procs]

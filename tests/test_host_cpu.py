@@ -273,6 +273,30 @@ def test_bench_steps_and_dump_outputs_through_the_command_line(tmp_path):
     assert bad.returncode != 0 and "--steps must be at least 1" in bad.stderr
 
 
+def test_bench_plain_run_measures_only_the_headline_and_full_adds_the_rest():
+    """A plain ``bench.py`` run (mock device) prints the headline without the legs that take launches or processes of their
+    own: no roofline, no extra workloads, no CPU baseline.  ``--full`` brings the dominant kernel's roofline back."""
+    import json
+    import subprocess
+
+    env = dict(os.environ, XH_BENCH_MOCK_DEVICE="1")
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--grid", "365x4x8"]
+
+    def line(*more):
+        res = subprocess.run(cmd + list(more), capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
+        lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, res.stdout
+        return json.loads(lines[0])
+
+    plain = line()
+    assert plain["steps"] == 3 and plain["ms_per_step"] > 0 and plain["value"] > 0 and plain["unit"] == "cell-timesteps/s"
+    assert plain["roofline"] is None and plain["extra"] == {} and plain["cpu_baseline"] is None
+    full = line("--full", "--no-cpu", "--no-extra")
+    assert full["roofline"]["bound"] == "hbm" and full["roofline"]["kernel"].startswith("k_pdoy_slide")
+    assert full["extra"] == {} and full["cpu_baseline"] is None
+
+
 def test_dim_other_than_time_is_refused():
     """The host mirrors keep the reference's `dim` argument: "time" = axis 0, or (round 6) an INTEGER axis of the plain array;
     a dimension NAME other than "time" means nothing for an array without names and must fail loudly (before any device

@@ -168,7 +168,7 @@ def test_bench_two_ranks_plumbing_without_gpus(tmp_path, workload):
     env = dict(os.environ, OMP_NUM_THREADS="1", XH_BENCH_MOCK_DEVICE="1", XH_BENCH_NO_RCCL="1", XH_RENDEZVOUS_DIR=str(tmp_path))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", "29541" if workload == "c2" else "29543", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--grid", "365x4x8" if workload == "c2" else "1095x4x8", "--no-cpu", "--no-extra", "--workload", workload]
+           "--grid", "365x4x8" if workload == "c2" else "1095x4x8", "--full", "--no-cpu", "--no-extra", "--workload", workload]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]

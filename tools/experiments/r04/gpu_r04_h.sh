@@ -8,7 +8,7 @@ export XH_DIAGNOSTICS=1
 for rep in 1 2 3; do
   for v in 0 1; do
     if [ $v = 1 ]; then export XH_PDOY_NONP1=1; else unset XH_PDOY_NONP1; fi
-    python bench.py --no-cpu --no-full --steps 50 --warmup 10 2>/dev/null | python -c "
+    python bench.py --full --no-cpu --no-full-configs --steps 50 --warmup 10 2>/dev/null | python -c "
 import sys,json
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 print('nonp1=$v', 'ms_per_step', round(d['ms_per_step'],4), 'pdoy_ms', round(d['roofline']['ms'],4), 'frac', round(d['roofline']['frac'],4))"

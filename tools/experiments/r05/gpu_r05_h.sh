@@ -5,7 +5,7 @@ O=$GRAFT_REPO_ROOT/gpurun_out/r05h; rm -rf $O; mkdir -p $O
 cd $GRAFT_REPO_ROOT
 timeout 600 python -m pytest -m gpu -q --tb=short tests/test_gpu_api.py -k "qdm or eqm" > $O/pytest.log 2>&1; echo "rc=$?" | tee $O/summary.txt
 tail -5 $O/pytest.log
-timeout 1200 python bench.py --no-cpu > $O/bench.log 2>&1
+timeout 1200 python bench.py --full --no-cpu > $O/bench.log 2>&1
 tail -1 $O/bench.log | python -c "
 import sys,json
 d=json.loads(sys.stdin.read())

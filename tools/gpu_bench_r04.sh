@@ -3,7 +3,7 @@
 set -u
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/${1:-bench_r04}; rm -rf $O; mkdir -p $O
-timeout 1500 python bench.py ${2:-} > $O/bench.out 2> $O/bench.err; echo "rc=$?" | tee $O/summary.txt
+timeout 1500 python bench.py --full ${2:-} > $O/bench.out 2> $O/bench.err; echo "rc=$?" | tee $O/summary.txt
 tail -c 300 $O/bench.err
 python - <<PY
 import json

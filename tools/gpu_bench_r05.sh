@@ -3,7 +3,7 @@
 set -u
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/bench_r05; rm -rf $O; mkdir -p $O
-timeout 1500 python bench.py > $O/bench.log 2>&1; echo "rc=$?"
+timeout 1500 python bench.py --full > $O/bench.log 2>&1; echo "rc=$?"
 grep -h "^{\"metric\"" $O/bench.log | tail -1 > $O/bench_line.json
 python - <<'PY'
 import json

@@ -6,10 +6,10 @@ set -u
 O=$GRAFT_REPO_ROOT/gpurun_out/prof_r05; rm -rf $O; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 B=$GRAFT_REPO_ROOT/bench.py
-timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o stats -- python $B --no-cpu > $O/stats.log 2>&1
+timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o stats -- python $B --full --no-cpu > $O/stats.log 2>&1
 grep -h "^{\"metric\"" $O/stats.log | tail -1 > $O/bench_line_under_rocprof.json
-SMALL="python $B --steps 5 --warmup 1 --no-cpu --no-full"
-FULL="python $B --steps 2 --warmup 1 --no-cpu --no-long"
+SMALL="python $B --steps 5 --warmup 1 --full --no-cpu --no-full-configs"
+FULL="python $B --steps 2 --warmup 1 --full --no-cpu --no-long"
 timeout 900 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/small/pmc_fetch -o f -- $SMALL > $O/small_fetch.log 2>&1
 timeout 900 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/small/pmc_write -o w -- $SMALL > $O/small_write.log 2>&1
 if [ "${XH_PROF_SKIP_FULL:-0}" != "1" ]; then  # (the 30-year kernels did not change since the committed profiles/r05/pmc_hbm_traffic_30yr.json)

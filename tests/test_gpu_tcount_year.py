@@ -1,0 +1,185 @@
+"""The one-year day-of-year count kernel (k_tcount_year, reduce.hip: operator at compile time, the loads of four rows issued
+together, period bounds in the kernel arguments) against the numpy oracle AND the kernel it replaces on this path
+(k_threshold_count, kept behind the diagnostics switch XH_TCOUNT_ROWWISE): counts and valid counts are integers, the
+comparison is exact.  Also both sides of the caps below which small host tables travel in the kernel arguments instead of
+an upload (period bounds: 32 periods; expected counts of the missing mask: 64 periods)."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from xclim_amd import kernels as K
+from xclim_amd._capi import DeviceArray, np_ptr
+
+pytestmark = pytest.mark.gpu
+
+OPS = [">", "<", ">=", "<=", "==", "!="]
+NPOP = {">": np.greater, "<": np.less, ">=": np.greater_equal, "<=": np.less_equal, "==": np.equal, "!=": np.not_equal}
+_vp = ctypes.c_void_p
+
+
+def _field(rng, T, C):
+    """Whole numbers (so == and != have both outcomes), NaN cells, whole NaN rows, infinities of both signs."""
+    x = np.round(rng.normal(20, 3, (T, C))).astype(np.float32)
+    r = rng.random((T, C))
+    x[r < 0.03] = np.nan
+    x[(r >= 0.03) & (r < 0.04)] = np.inf
+    x[(r >= 0.04) & (r < 0.05)] = -np.inf
+    x[:, 0] = np.nan
+    x[T // 3] = np.nan
+    x[T - 1] = np.nan
+    if C > 2:
+        x[:, 2] = np.inf
+    return x
+
+
+def _table(rng, D, C):
+    t = np.round(rng.normal(20, 2, (D, C))).astype(np.float64)
+    t += np.where(rng.random((D, C)) < 0.3, 0.5, 0.0)   # (values no float32 whole number equals)
+    t[5] = np.nan
+    t[D // 2] = np.inf
+    t[D - 2] = -np.inf
+    t[rng.random((D, C)) < 0.02] = np.nan
+    return t
+
+
+def _oracle(x, table, tidx, seg, op):
+    with np.errstate(invalid="ignore"):
+        hit = NPOP[op](x.astype(np.float64), table[tidx])
+    ok = ~np.isnan(x)
+    cnt = np.stack([hit[a:b].sum(0) for a, b in zip(seg[:-1], seg[1:])]).astype(np.int32)
+    val = np.stack([ok[a:b].sum(0) for a, b in zip(seg[:-1], seg[1:])]).astype(np.int32)
+    return cnt, val
+
+
+def _call(dev, x, table, tidx, seg, op, st=None, ts=None, shift=0):
+    """xh_threshold_count_doy through dev.call: row strides st >= C / ts >= C, the table view starting `shift` doubles into
+    its buffer.  Returns (count, valid) as numpy."""
+    T, C = x.shape
+    D = table.shape[0]
+    st, ts = st or C, ts or C
+    xs = np.full((T, st), -7.0, np.float32)
+    xs[:, :C] = x
+    tb = np.full(D * ts + shift, 1e30, np.float64)
+    tb[shift:].reshape(D, ts)[:, :C] = table
+    d_x, d_tb = dev.to_device(xs), dev.to_device(tb)
+    d_t = DeviceArray(dev, d_tb.ptr + 8 * shift, (D, ts), np.float64, owner=False)
+    d_i = dev.to_device(np.ascontiguousarray(tidx, dtype=np.int32))
+    s = np.ascontiguousarray(seg, dtype=np.int64)
+    P = len(s) - 1
+    cnt = dev.to_device(np.full((P, C), -1, np.int32))
+    val = dev.to_device(np.full((P, C), -1, np.int32))
+    dev.call("xh_threshold_count_doy", _vp(d_x.ptr), T, C, st, 1, K.op_code(op), _vp(d_t.ptr), ts, D, _vp(d_i.ptr), np_ptr(s), P,
+             _vp(cnt.ptr), _vp(val.ptr))
+    dev.sync()
+    return cnt.get(), val.get()
+
+
+def _check(dev, monkeypatch, x, table, tidx, seg, op, **kw):
+    exp_c, exp_v = _oracle(x, table, tidx, np.asarray(seg), op)
+    got_c, got_v = _call(dev, x, table, tidx, seg, op, **kw)
+    with monkeypatch.context() as m:
+        m.setenv("XH_DIAGNOSTICS", "1")
+        m.setenv("XH_TCOUNT_ROWWISE", "1")
+        old_c, old_v = _call(dev, x, table, tidx, seg, op, **kw)
+    assert np.array_equal(got_c, exp_c), (op, np.argwhere(got_c != exp_c)[:5])
+    assert np.array_equal(got_v, exp_v), (op, np.argwhere(got_v != exp_v)[:5])
+    assert np.array_equal(got_c, old_c) and np.array_equal(got_v, old_v), op
+    assert exp_c.max() > 0
+
+
+@pytest.mark.parametrize("op", OPS)
+@pytest.mark.parametrize("T", [365, 366, 367, 368, 730])   # 1, 2, 3, 0 and 2 rows after the last batch of four
+def test_series_lengths_and_tail_rows(dev, rng, monkeypatch, op, T):
+    C, D = 1024, 365
+    x, table = _field(rng, T, C), _table(rng, D, C)
+    _check(dev, monkeypatch, x, table, np.arange(T) % D, [0, T], op)
+
+
+@pytest.mark.parametrize("op", OPS)
+@pytest.mark.parametrize("C", [4, 1028, 1300, 2048])   # one lane; a partial last workgroup (twice); whole workgroups
+def test_cell_counts(dev, rng, monkeypatch, op, C):
+    T, D = 365, 365
+    x, table = _field(rng, T, C), _table(rng, D, C)
+    _check(dev, monkeypatch, x, table, np.arange(T), [0, T], op)
+
+
+@pytest.mark.parametrize("op", OPS)
+@pytest.mark.parametrize("how", ["odd_C", "odd_table_stride", "table_view_8_bytes_in"])
+def test_unaligned_views_take_the_row_kernel_and_agree(dev, rng, monkeypatch, op, how):
+    T, D = 366, 365
+    C = 1023 if how == "odd_C" else 1024
+    x, table = _field(rng, T, C), _table(rng, D, C)
+    kw = {"odd_table_stride": dict(ts=C + 1), "table_view_8_bytes_in": dict(shift=1)}.get(how, {})
+    _check(dev, monkeypatch, x, table, np.minimum(np.arange(T), D - 1), [0, T], op, **kw)
+
+
+@pytest.mark.parametrize("op", OPS)
+def test_row_strides_beyond_the_cell_count(dev, rng, monkeypatch, op):
+    """st > C and thr_stride > C (kernels.threshold_count always passes st = C): both 16-byte multiples, the batched kernel"""
+    T, D, C = 365, 365, 1028
+    x, table = _field(rng, T, C), _table(rng, D, C)
+    _check(dev, monkeypatch, x, table, np.arange(T), [0, T], op, st=C + 12, ts=C + 36)
+    _check(dev, monkeypatch, x, table, np.arange(T), [0, 120, T], op, st=C + 4)
+
+
+@pytest.mark.parametrize("op", OPS)
+@pytest.mark.parametrize("periods", ["months", "gaps", "cap_32", "cap_33", "many"])
+def test_periods(dev, rng, monkeypatch, op, periods):
+    """P = 12 (the months of one year); bounds that leave rows before, between (an empty period) and after the periods; 32 and
+    33 periods (the last table that travels in the kernel arguments, the first that is uploaded); 100 short periods."""
+    T, D, C = 365, 365, 1300
+    x, table = _field(rng, T, C), _table(rng, D, C)
+    seg = {"months": np.r_[0, np.cumsum([31, 28, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31])],
+           "gaps": np.array([10, 100, 100, 103, 300]),
+           "cap_32": np.linspace(0, T, 33).astype(np.int64),
+           "cap_33": np.linspace(3, T - 2, 34).astype(np.int64),
+           "many": np.linspace(0, T, 101).astype(np.int64)}[periods]
+    _check(dev, monkeypatch, x, table, np.arange(T), seg, op)
+    if periods == "gaps":   # an empty period counts nothing and has no valid day
+        c, v = _call(dev, x, table, np.arange(T), seg, op)
+        assert (c[1] == 0).all() and (v[1] == 0).all()
+
+
+@pytest.mark.parametrize("op", OPS)
+@pytest.mark.parametrize("index", ["mid_year_wrap", "leap_year_repeat", "reversed"])
+def test_day_of_year_index_is_not_the_row_number(dev, rng, monkeypatch, op, index):
+    """A series that starts in the middle of the year (the index wraps inside a batch); a leap year against a 365-row table
+    (one table row serves two days); any order at all."""
+    D, C = 365, 1024
+    T = 366 if index == "leap_year_repeat" else 365
+    x, table = _field(rng, T, C), _table(rng, D, C)
+    tidx = {"mid_year_wrap": (np.arange(T) + 199) % D, "leap_year_repeat": np.r_[np.arange(60), 59, np.arange(60, 365)],
+            "reversed": np.arange(T)[::-1]}[index]
+    seg = [0, T] if index != "mid_year_wrap" else [0, 166, T]
+    _check(dev, monkeypatch, x, table, tidx, seg, op)
+
+
+@pytest.mark.parametrize("op", OPS)
+def test_through_the_typed_wrapper(dev, rng, monkeypatch, op):
+    """kernels.threshold_count (the call of the tx90p chain), with and without the valid counts"""
+    T, D, C = 365, 365, 2048
+    x, table = _field(rng, T, C), _table(rng, D, C)
+    tidx, seg = np.arange(T), np.array([0, T])
+    exp_c, exp_v = _oracle(x, table, tidx, seg, op)
+    d_x, d_t = dev.to_device(x), dev.to_device(table)
+    c, v = K.threshold_count(dev, d_x, op, seg, doy_table=d_t, tidx=tidx)
+    assert np.array_equal(c.get(), exp_c) and np.array_equal(v.get(), exp_v)
+    c, v = K.threshold_count(dev, d_x, op, seg, doy_table=d_t, tidx=tidx, want_valid=False)
+    assert v is None and np.array_equal(c.get(), exp_c)
+    monkeypatch.setenv("XH_DIAGNOSTICS", "1")
+    monkeypatch.setenv("XH_TCOUNT_ROWWISE", "1")
+    c, v = K.threshold_count(dev, d_x, op, seg, doy_table=d_t, tidx=tidx)
+    assert np.array_equal(c.get(), exp_c) and np.array_equal(v.get(), exp_v)
+
+
+@pytest.mark.parametrize("P", [1, 12, 64, 65, 200])   # 64: the last table in the kernel arguments; 65: the first uploaded
+@pytest.mark.parametrize("dtype", [np.int32, np.float32, np.float64])
+def test_missing_mask_expected_counts_on_both_sides_of_the_cap(dev, rng, P, dtype):
+    C = 333
+    value = rng.integers(0, 90, (P, C)).astype(dtype)
+    expected = rng.integers(28, 32, P).astype(np.int32)
+    valid = np.where(rng.random((P, C)) < 0.2, expected[:, None] - 1, expected[:, None]).astype(np.int32)
+    got = K.apply_missing_mask(dev, dev.to_device(value), dev.to_device(valid), expected).get()
+    exp = np.where(valid != expected[:, None], np.nan, value.astype(np.float64))
+    np.testing.assert_array_equal(got, exp)

@@ -168,14 +168,20 @@ __device__ __forceinline__ void sort_small(uint32_t (&k)[W]) {
 // day that leaves — and nothing is ever shifted (sorting and min/max do not care about the order).  `fast` (host:
 // every percentile clips to the window maximum (1) / minimum (2) when the window is full, e.g. per = 90 with 5
 // samples, utl:443-452) selects a path without the sorting network when no lane of the wave holds a NaN.
+//
+// The quantile table (at most 8 percentiles x 8 valid counts, 1 KiB) travels BY VALUE in the kernel arguments: it is rebuilt
+// from the call's arguments on every call, and an upload of 96 bytes was a copy kernel of its own in stream order.
+struct QTabArg {
+  QTab e[8 * 8];
+};
 template <int W, int VEC, bool COUNT = false>
 __global__ void __launch_bounds__(XH_BLOCK)
 k_pdoy_slide(const float* __restrict__ x, int64_t T, int64_t C, int64_t st, int64_t t_first, int ndoy, int chunk,
-             const QTab* __restrict__ qtab, int nper, double* __restrict__ out, int fast, int op = 0,
+             const QTabArg qtab, int nper, double* __restrict__ out, int fast, int op = 0,
              const int32_t* __restrict__ doy_period = nullptr, int32_t* __restrict__ cnt_out = nullptr,
              int32_t* __restrict__ valid_out = nullptr) {
   __shared__ QTab s_tab[8 * (W + 1)];
-  for (int i = threadIdx.x; i < nper * (W + 1); i += XH_BLOCK) s_tab[i] = qtab[i];
+  for (int i = threadIdx.x; i < nper * (W + 1); i += XH_BLOCK) s_tab[i] = qtab.e[i];
   __syncthreads();
   // Cells of a lane.  VEC = 4: lane l owns the cell PAIRS {2l, 2l+1} and {128+2l, 129+2l} of its wave's 256 cells, so every
   // wave load reads 512 contiguous bytes and every double2 store writes 1 KiB contiguous — whole 128-byte lines per
@@ -804,18 +810,17 @@ static int pdoy_impl(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t 
   bool contiguous = !vmap && nyears == 1 && nper <= 8 && (window == 3 || window == 5 || window == 7) && tbase[0] >= 0;
   for (int d = 1; contiguous && d < ndoy; ++d) contiguous = tbase[d] == tbase[0] + d;
   if (contiguous) {
-    QTab tab[8 * 8];
+    QTabArg targ;
+    memset(&targ, 0, sizeof(targ));
+    QTab* tab = targ.e;
     build_qtab(window, qh, nper, alpha, beta, tab);
-    void* d_tab = nullptr;
-    int rc = xh_scratch_upload(ctx, &cur, tab, sizeof(QTab) * (size_t)nper * (window + 1), &d_tab);
-    if (rc) return rc;
     int chunk = 32;
     if (const char* e = xh_diag_env("XH_PDOY_SLIDE_CHUNK")) chunk = atoi(e) > 0 ? atoi(e) : chunk;  // diagnostics
     const int vec = slide_vec(x, C, st, out);
     dim3 grid((unsigned)cdiv64(cdiv64(C, vec), XH_BLOCK), (unsigned)((ndoy + chunk - 1) / chunk));
 #define XH_SLIDE(W, V)                                                                                              \
   hipLaunchKernelGGL((k_pdoy_slide<W, V>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, T, C, st, (int64_t)tbase[0], ndoy, \
-                     chunk, (const QTab*)d_tab, nper, out, slide_fast_mode(tab, nper, window))
+                     chunk, targ, nper, out, slide_fast_mode(tab, nper, window))
     if (vec == 4) {
       if (window == 3) XH_SLIDE(3, 4); else if (window == 5) XH_SLIDE(5, 4); else XH_SLIDE(7, 4);
     } else {
@@ -967,12 +972,13 @@ static int pdoy_count_impl(xh_ctx* ctx, const float* x, int64_t T, int64_t C, in
   for (int d = 0; d < ndoy; ++d)
     XH_REQUIRE(doy_period[d] >= 0 && doy_period[d] < P, XH_ERR_ARG, "xh_percentile_doy_count: doy_period[%d] outside [0, P)", d);
   size_t cur = 0;
-  QTab tab[8];
+  QTabArg targ;
+  memset(&targ, 0, sizeof(targ));
+  QTab* tab = targ.e;
   const double q = per / 100.0;
   build_qtab(window, &q, 1, alpha, beta, tab);
-  void *d_tab = nullptr, *d_dp = nullptr;
-  int rc = xh_scratch_upload(ctx, &cur, tab, sizeof(QTab) * (size_t)(window + 1), &d_tab);
-  if (!rc) rc = xh_scratch_upload(ctx, &cur, doy_period, sizeof(int32_t) * (size_t)ndoy, &d_dp);
+  void* d_dp = nullptr;
+  int rc = xh_scratch_upload(ctx, &cur, doy_period, sizeof(int32_t) * (size_t)ndoy, &d_dp);
   if (rc) return rc;
   XH_CHECK_HIP(hipMemsetAsync(count_out, 0, sizeof(int32_t) * (size_t)P * (size_t)C, ctx->stream));
   if (valid_out) XH_CHECK_HIP(hipMemsetAsync(valid_out, 0, sizeof(int32_t) * (size_t)P * (size_t)C, ctx->stream));
@@ -982,7 +988,7 @@ static int pdoy_count_impl(xh_ctx* ctx, const float* x, int64_t T, int64_t C, in
   dim3 grid((unsigned)cdiv64(cdiv64(C, vec), XH_BLOCK), (unsigned)((ndoy + chunk - 1) / chunk));
 #define XH_SLIDEC(W, V)                                                                                                   \
   hipLaunchKernelGGL((k_pdoy_slide<W, V, true>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, T, C, st, (int64_t)tbase[0], ndoy, \
-                     chunk, (const QTab*)d_tab, 1, (double*)nullptr, slide_fast_mode(tab, 1, window), op,          \
+                     chunk, targ, 1, (double*)nullptr, slide_fast_mode(tab, 1, window), op,                        \
                      (const int32_t*)d_dp, count_out, valid_out)
   if (vec == 4) {
     if (window == 3) XH_SLIDEC(3, 4); else if (window == 5) XH_SLIDEC(5, 4); else XH_SLIDEC(7, 4);

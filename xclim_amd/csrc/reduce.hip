@@ -94,6 +94,121 @@ static int launch_threshold_count(xh_ctx* ctx, int kind, dim3 grid, const float*
 
 static inline unsigned period_grid(int P) { return (unsigned)(P < 1 ? 1 : (P > 4096 ? 4096 : P)); }
 
+// ---- threshold_count, per-doy fp64 table, one or two years (the tx90p chain) ---------------------------------------
+// k_threshold_count waits once per ROW on this path: the doy index of a row is a scalar load, the table row a dependent
+// vector load, and the run-time operator keeps the compiler from hoisting either.  Here the operator is a template
+// parameter and a batch of R rows issues ALL its loads (R float4 samples, 2R double2 table pieces) before the first is
+// consumed; the R doy indices of a batch are wave-uniform scalar loads (lgkmcnt, not in the vector-load chain).  R = 4:
+// with 8 the scheduler re-serialises the 24 loads to save registers (tests/test_isa_count_loop_cpu.py holds the loop
+// to its shape).  Same grid, lane map and period handling as k_threshold_count<4, XH_THR_DOY_F64>; the compare is the
+// fp64 compare of xh_cmp_f64, so counts are bit-identical.  The loop shape alone measured the same as k_threshold_count
+// (0.748 against 0.751 ms); the non-temporal loads below and the period bounds in the arguments are what pays.
+#define XH_TCY_R 4
+// period bounds by value in the kernel arguments (no upload for a table of a few bytes); seg_ptr when P is larger
+#define XH_SEG_ARG_MAX 32
+struct XhSegArg {
+  int64_t off[XH_SEG_ARG_MAX + 1];
+};
+// At most 4 waves per SIMD: the grid of the one-year field is 4 waves per SIMD anyway, and the register budget that goes
+// with it (128 VGPRs; the loop takes 96) is what keeps the scheduler from splitting the batch into 7 loads, a drain,
+// 5 loads, a drain to stay under 64.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define XH_TCY_WAVES __attribute__((amdgpu_waves_per_eu(4, 4)))
+#else
+#define XH_TCY_WAVES
+#endif
+
+// Every byte of the field and of the table is read ONCE per launch: the loads are non-temporal (the `nt` bit), so the
+// stream does not displace what the caches hold and is not kept behind the lines the producer of the table left dirty.
+// Measured: 0.745 -> 0.685 ms back-to-back (6.6 TB/s), 54 us off the tx90p step.  (g++, the
+// host build of the tests, has no such builtin: plain loads there.)
+#if defined(__clang__)
+typedef float tcy_f4 __attribute__((ext_vector_type(4)));
+typedef double tcy_d2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float4 tcy_load(const float* p) {
+  const tcy_f4 t = __builtin_nontemporal_load(reinterpret_cast<const tcy_f4*>(p));
+  return make_float4(t.x, t.y, t.z, t.w);
+}
+__device__ __forceinline__ double2 tcy_load(const double* p) {
+  const tcy_d2 t = __builtin_nontemporal_load(reinterpret_cast<const tcy_d2*>(p));
+  return make_double2(t.x, t.y);
+}
+#else
+__device__ __forceinline__ float4 tcy_load(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ double2 tcy_load(const double* p) { return *reinterpret_cast<const double2*>(p); }
+#endif
+
+template <int OP, bool SEGARG>
+__global__ void __launch_bounds__(XH_BLOCK) XH_TCY_WAVES
+k_tcount_year(const float* __restrict__ x, int64_t C, int64_t st, const double* __restrict__ table, int64_t tstride,
+              const int32_t* __restrict__ tidx, const int64_t* __restrict__ seg_ptr, const XhSegArg seg_val, int P,
+              int32_t* __restrict__ count_out, int32_t* __restrict__ valid_out, int period_fast) {
+  constexpr int R = XH_TCY_R;
+  const unsigned tile = period_fast ? blockIdx.y : blockIdx.x;
+  const int pstart = period_fast ? blockIdx.x : blockIdx.y, pstep = period_fast ? gridDim.x : gridDim.y;
+  const int64_t c = ((int64_t)tile * XH_BLOCK + threadIdx.x) * 4;
+  if (c >= C) return;
+  const float* __restrict__ xc = x + c;
+  const double* __restrict__ tc = table + c;
+  for (int p = pstart; p < P; p += pstep) {
+    // (SEGARG at compile time: a run-time choice between the two tables becomes a per-lane load of the bounds, and
+    // with it every doy index of the march a vector load)
+    const int64_t t0 = SEGARG ? seg_val.off[p] : seg_ptr[p], t1 = SEGARG ? seg_val.off[p + 1] : seg_ptr[p + 1];
+    int cnt[4] = {0, 0, 0, 0}, val[4] = {0, 0, 0, 0};
+    auto tally = [&](const float4& v, const double2& a, const double2& b) {
+      cnt[0] += xh_cmp_f64((double)v.x, OP, a.x) ? 1 : 0;
+      cnt[1] += xh_cmp_f64((double)v.y, OP, a.y) ? 1 : 0;
+      cnt[2] += xh_cmp_f64((double)v.z, OP, b.x) ? 1 : 0;
+      cnt[3] += xh_cmp_f64((double)v.w, OP, b.y) ? 1 : 0;
+      val[0] += (v.x == v.x) ? 1 : 0;
+      val[1] += (v.y == v.y) ? 1 : 0;
+      val[2] += (v.z == v.z) ? 1 : 0;
+      val[3] += (v.w == v.w) ? 1 : 0;
+    };
+    // Batches of R rows, then the rows that are left one by one.  The doy indices of a batch are read one batch ahead
+    // (the last batch re-reads its own), so the scalar-load latency is not paid in front of the vector loads either.
+    const int64_t nfull = (t1 - t0) / R;
+    int64_t tb = t0;
+    int32_t nxt[R] = {};
+    if (nfull > 0) {
+#pragma unroll
+      for (int r = 0; r < R; ++r) nxt[r] = tidx[tb + r];
+    }
+    for (int64_t k = 0; k < nfull; ++k) {
+      int64_t row[R];
+#pragma unroll
+      for (int r = 0; r < R; ++r) row[r] = (int64_t)nxt[r];
+      const int64_t tn = k + 1 < nfull ? tb + R : tb;
+#pragma unroll
+      for (int r = 0; r < R; ++r) nxt[r] = tidx[tn + r];
+      float4 v[R];
+      double2 a[R], b[R];
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        v[r] = tcy_load(xc + (tb + r) * st);
+        const double* tp = tc + row[r] * tstride;
+        a[r] = tcy_load(tp);
+        b[r] = tcy_load(tp + 2);
+      }
+#pragma unroll
+      for (int r = 0; r < R; ++r) tally(v[r], a[r], b[r]);
+      tb = tn;
+    }
+    for (int64_t t = t0 + nfull * R; t < t1; ++t) {  // tail rows one by one
+      const float4 v = tcy_load(xc + t * st);
+      const double* tp = tc + (int64_t)tidx[t] * tstride;
+      tally(v, tcy_load(tp), tcy_load(tp + 2));
+    }
+    const int64_t o = (int64_t)p * C + c;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) count_out[o + i] = cnt[i];
+    if (valid_out) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) valid_out[o + i] = val[i];
+    }
+  }
+}
+
 // ---- domain_count ----------------------------------------------------------------------------------
 // FAST: both conditions in the one-compare form of xh_one_cmp (sgn * x > thr): 2 multiplies + 2 compares per element
 // instead of two run-time operators (PMC: 28 VALU per element, 0.39 ms at 365 x 1440 x 720 before).
@@ -248,9 +363,16 @@ static int launch_resample_reduce(xh_ctx* ctx, int reducer, dim3 grid, const flo
 }
 
 // ---- missing mask ----------------------------------------------------------------------------------
+// expected == NULL: the expected counts travel in the kernel arguments (P <= XH_EXP_ARG_MAX; no upload for a few bytes)
+#define XH_EXP_ARG_MAX 64
+struct XhExpArg {
+  int32_t n[XH_EXP_ARG_MAX];
+};
+
 __global__ void __launch_bounds__(XH_BLOCK)
 k_apply_missing_mask(const void* __restrict__ value, int kind, const int32_t* __restrict__ valid,
-                     const int32_t* __restrict__ expected, int P, int64_t C, double* __restrict__ out) {
+                     const int32_t* __restrict__ expected, const XhExpArg exp_val, int P, int64_t C,
+                     double* __restrict__ out) {
   int64_t i = (int64_t)blockIdx.x * XH_BLOCK + threadIdx.x;
   int64_t n = (int64_t)P * C;
   if (i >= n) return;
@@ -258,7 +380,7 @@ k_apply_missing_mask(const void* __restrict__ value, int kind, const int32_t* __
   double v = kind == 0 ? (double)reinterpret_cast<const int32_t*>(value)[i]
              : kind == 1 ? (double)reinterpret_cast<const float*>(value)[i]
                          : reinterpret_cast<const double*>(value)[i];  // 2: the float64 results of the _f64 twins
-  out[i] = (valid[i] != expected[p]) ? xh_nan64() : v;
+  out[i] = (valid[i] != (expected ? expected[p] : exp_val.n[p])) ? xh_nan64() : v;
 }
 
 // ---- rolling reductions --------------------------------------------------------------------------------
@@ -326,16 +448,45 @@ static int check_tc(const char* fn, xh_ctx* ctx, const void* x, int64_t T, int64
   return XH_OK;
 }
 
-static int upload_segments(xh_ctx* ctx, size_t* cur, const int64_t* seg_off, int P, int64_t T, const char* fn,
-                           const int64_t** d_seg) {
+static int check_segments(const int64_t* seg_off, int P, int64_t T, const char* fn) {
   XH_REQUIRE(seg_off && P >= 1, XH_ERR_ARG, "%s: seg_off NULL or P < 1", fn);
   for (int p = 0; p < P; ++p)
     XH_REQUIRE(seg_off[p] <= seg_off[p + 1] && seg_off[p] >= 0 && seg_off[p + 1] <= T, XH_ERR_ARG,
                "%s: seg_off must be non-decreasing within [0, T]", fn);
+  return XH_OK;
+}
+
+static int upload_segments(xh_ctx* ctx, size_t* cur, const int64_t* seg_off, int P, int64_t T, const char* fn,
+                           const int64_t** d_seg) {
+  int rc = check_segments(seg_off, P, T, fn);
+  if (rc) return rc;
   void* d = nullptr;
-  int rc = xh_scratch_upload(ctx, cur, seg_off, sizeof(int64_t) * (size_t)(P + 1), &d);
+  rc = xh_scratch_upload(ctx, cur, seg_off, sizeof(int64_t) * (size_t)(P + 1), &d);
   if (rc) return rc;
   *d_seg = (const int64_t*)d;
+  return XH_OK;
+}
+
+// d_seg == NULL: the period bounds travel in the kernel arguments (P <= XH_SEG_ARG_MAX)
+static int launch_tcount_year(xh_ctx* ctx, dim3 grid, const float* x, int64_t C, int64_t st, int op, const double* table,
+                              int64_t tstride, const int32_t* tidx, const int64_t* d_seg, const int64_t* h_seg, int P,
+                              int32_t* count_out, int32_t* valid_out, int period_fast) {
+  XhSegArg sv;
+  memset(&sv, 0, sizeof(sv));
+  if (!d_seg) memcpy(sv.off, h_seg, sizeof(int64_t) * (size_t)(P + 1));
+#define XH_TCY2(OPV, BYVAL)                                                                                              \
+  hipLaunchKernelGGL((k_tcount_year<OPV, BYVAL>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, table, tstride, tidx, d_seg, \
+                     sv, P, count_out, valid_out, period_fast)
+#define XH_TCY(OPV)                                  \
+  case OPV:                                          \
+    if (d_seg) XH_TCY2(OPV, false); else XH_TCY2(OPV, true); \
+    break;
+  switch (op) {
+    XH_TCY(XH_OP_GT) XH_TCY(XH_OP_LT) XH_TCY(XH_OP_GE) XH_TCY(XH_OP_LE) XH_TCY(XH_OP_EQ) XH_TCY(XH_OP_NE)
+  }
+#undef XH_TCY
+#undef XH_TCY2
+  XH_LAUNCH_CHECK();
   return XH_OK;
 }
 
@@ -353,26 +504,45 @@ static int threshold_count_impl(xh_ctx* ctx, const float* x, int64_t T, int64_t 
     if (thr_kind == XH_THR_DOY_F64 || thr_kind == XH_THR_DOY_F32)
       XH_REQUIRE(tidx, XH_ERR_ARG, "xh_threshold_count: tidx required for per-doy thresholds");
   }
+  rc = check_segments(seg_off, P, T, "xh_threshold_count");
+  if (rc) return rc;
   size_t cur = 0;
   const int64_t* d_seg = nullptr;
-  rc = upload_segments(ctx, &cur, seg_off, P, T, "xh_threshold_count", &d_seg);
-  if (rc) return rc;
-  if (C == 0) return XH_OK;
-  if (thr_kind == XH_THR_DOY_F64 && ndoy > 0 && !xh_diag_env("XH_TCOUNT_LEGACY")) {
+  const bool legacy = xh_diag_env("XH_TCOUNT_LEGACY") != nullptr;
+  if (thr_kind == XH_THR_DOY_F64 && ndoy > 0 && !legacy && C > 0) {
     // multi-year series: one workgroup per column tile with the table slice in LDS (tcount.hip)
-    rc = xh_launch_tcount_doy(ctx, x, T, C, st, op, static_cast<const double*>(thr_table), thr_stride, tidx, d_seg, seg_off, P,
-                              ndoy, count_out, valid_out);
-    if (rc != XH_ERR_NOTIMPL) return rc;
+    int64_t longest = 0;
+    for (int p = 0; p < P; ++p) longest = seg_off[p + 1] - seg_off[p] > longest ? seg_off[p + 1] - seg_off[p] : longest;
+    size_t lds = 0;
+    int narrow = 0;
+    if (xh_tcount_plan(T, C, st, op, P, ndoy, longest, &lds, &narrow) == XH_OK) {  // (else: no upload before the choice below)
+      rc = upload_segments(ctx, &cur, seg_off, P, T, "xh_threshold_count", &d_seg);
+      if (rc) return rc;
+      rc = xh_launch_tcount_doy(ctx, x, T, C, st, op, static_cast<const double*>(thr_table), thr_stride, tidx, d_seg, seg_off, P,
+                                ndoy, count_out, valid_out);
+      if (rc != XH_ERR_NOTIMPL) return rc;
+    }
   }
   int vec = xh_pick_vec(x, C, st);
   if (thr_kind >= XH_THR_DOY_F64) {
     size_t esz = (thr_kind == XH_THR_DOY_F64 || thr_kind == XH_THR_FULL_F64) ? 8 : 4;
     if ((reinterpret_cast<uintptr_t>(thr_table) & 15) != 0 || (thr_stride * esz) % 16 != 0) vec = 1;
   }
+  // one or two years against the per-doy fp64 table: loads issued per batch, operator at compile time (k_tcount_year);
+  // XH_TCOUNT_LEGACY / XH_TCOUNT_ROWWISE (diagnostics) keep k_threshold_count, which is also the fallback for VEC = 1
+  const bool year = thr_kind == XH_THR_DOY_F64 && vec == 4 && !legacy && !xh_diag_env("XH_TCOUNT_ROWWISE");
+  if (!d_seg && !(year && P <= XH_SEG_ARG_MAX)) {
+    rc = upload_segments(ctx, &cur, seg_off, P, T, "xh_threshold_count", &d_seg);
+    if (rc) return rc;
+  }
+  if (C == 0) return XH_OK;
   unsigned tiles = (unsigned)cdiv64(cdiv64(C, vec), XH_BLOCK);
   const bool doy = thr_kind == XH_THR_DOY_F64 || thr_kind == XH_THR_DOY_F32;
   const int period_fast = (doy && P > 1 && tiles <= 65535u) ? 1 : 0;
   dim3 grid = period_fast ? dim3(period_grid(P), tiles) : dim3(tiles, period_grid(P));
+  if (year)
+    return launch_tcount_year(ctx, grid, x, C, st, op, static_cast<const double*>(thr_table), thr_stride, tidx, d_seg, seg_off, P,
+                              count_out, valid_out, period_fast);
   if (vec == 4)
     return launch_threshold_count<4>(ctx, thr_kind, grid, x, C, st, op, thr_scalar, thr_table, thr_stride, tidx, d_seg, P,
                                      count_out, valid_out, period_fast);
@@ -451,12 +621,18 @@ int xh_apply_missing_mask(xh_ctx* ctx, const void* value, int value_kind, const 
   XH_REQUIRE(P >= 1 && C >= 0, XH_ERR_ARG, "xh_apply_missing_mask: bad shape");
   size_t cur = 0;
   void* d_exp = nullptr;
-  int rc = xh_scratch_upload(ctx, &cur, expected, sizeof(int32_t) * (size_t)P, &d_exp);
-  if (rc) return rc;
+  XhExpArg ev;
+  memset(&ev, 0, sizeof(ev));
+  if (P <= XH_EXP_ARG_MAX) {
+    memcpy(ev.n, expected, sizeof(int32_t) * (size_t)P);
+  } else {
+    int rc = xh_scratch_upload(ctx, &cur, expected, sizeof(int32_t) * (size_t)P, &d_exp);
+    if (rc) return rc;
+  }
   int64_t n = (int64_t)P * C;
   if (n == 0) return XH_OK;
   hipLaunchKernelGGL(k_apply_missing_mask, dim3((unsigned)cdiv64(n, XH_BLOCK)), dim3(XH_BLOCK), 0, ctx->stream, value,
-                     value_kind, valid, (const int32_t*)d_exp, P, C, out64);
+                     value_kind, valid, (const int32_t*)d_exp, ev, P, C, out64);
   XH_LAUNCH_CHECK();
   return XH_OK;
 }

@@ -1,0 +1,56 @@
+"""The two-call tx90p chain over several steps without a host synchronisation, ONE table buffer rewritten by every step.
+
+k_pdoy_slide writes the (365, C) fp64 table with non-temporal stores and k_tcount_year reads it back with non-temporal
+loads: the count of step k must see the table of step k (not what the caches held from step k - 1), and the table of step
+k + 1 must not land before the count of step k has read.  Every step has its own field and its own count buffers, so a
+stale or early table shows as a wrong count of that step.  Sizes: one partial workgroup, and several workgroups with a
+partial wave at the end."""
+
+import numpy as np
+import pytest
+
+from oracle import calendar as ocal
+from oracle import generic as ogen
+from oracle.timeutil import OTime
+from xclim_amd import kernels as K
+from xclim_amd.timeaxis import TimeAxis
+
+pytestmark = pytest.mark.gpu
+
+T, STEPS = 365, 4
+
+
+def _fields(rng, C):
+    t = np.arange(T)[:, None]
+    xs = []
+    for k in range(STEPS):
+        x = (288 + 2 * k + 12 * np.sin(2 * np.pi * (t - 100 - 20 * k) / 365) + rng.normal(0, 3, (T, C))).astype(np.float32)
+        x[rng.random((T, C)) < 0.01] = np.nan
+        xs.append(x)
+    return xs
+
+
+@pytest.mark.parametrize("C", [1000, 4 * 1024 + 132])
+@pytest.mark.parametrize("op", [">", "<="])
+def test_chain_steps_share_one_table(dev, rng, C, op):
+    ta, ot = TimeAxis.daily("2001-01-01", T, "noleap"), OTime.noleap(2001, T, "noleap")
+    tb, _, doys = ta.doy_table()
+    seg, _ = ta.segments("MS")
+    tidx = dev.to_device((ta.doy - 1).astype(np.int32))
+    xs = _fields(rng, C)
+    ds = [dev.to_device(x) for x in xs]
+    per = dev.empty((1, len(doys), C), np.float64)
+    table = per.reshape(len(doys), C)
+    outs = [(dev.empty((len(seg) - 1, C), np.int32), dev.empty((len(seg) - 1, C), np.int32)) for _ in range(STEPS)]
+    dev.sync()
+    for k in range(STEPS):  # nothing waits on the host between the calls
+        K.percentile_doy(dev, ds[k], tb, 5, [90.0], out=per)
+        K.threshold_count(dev, ds[k], op, seg, doy_table=table, tidx=tidx, out=outs[k])
+    last = per.get()
+    for k in range(STEPS):
+        p_o, _ = ocal.percentile_doy(xs[k], ot, 5, 90.0)
+        thr = p_o[..., 0]
+        np.testing.assert_array_equal(outs[k][0].get(), ogen.threshold_count(xs[k], op, thr[ta.doy - 1], ot, "MS"), err_msg=f"step {k}")
+        np.testing.assert_array_equal(outs[k][1].get(), ogen.select_resample_op(xs[k], "count", ot, "MS"), err_msg=f"step {k}")
+    # the buffer holds the last step's table, bit for bit what a call of its own gives
+    np.testing.assert_array_equal(last, K.percentile_doy(dev, ds[-1], tb, 5, [90.0]).get())

@@ -174,6 +174,20 @@ __device__ __forceinline__ void sort_small(uint32_t (&k)[W]) {
 struct QTabArg {
   QTab e[8 * 8];
 };
+// The table rows are written once and read by no lane of this launch: the VEC = 4 stores are non-temporal (the `nt` bit), so
+// the 3 GB of the one-year table do not stay behind as dirty lines in the Infinity Cache, which the next kernel's first reads
+// would have to evict (round 8 measured that wait on the count kernel: 50 us).  tools/chain_ubench.hip, the stand-ins of the
+// tx90p chain back to back: 1.560 -> 1.502 ms per step with the count's non-temporal loads, 1.630 -> 1.582 ms with plain ones
+// (DESIGN.md §7, round 13).  (g++, the host build of the tests, has no such builtin: plain stores there.)
+#if defined(__clang__)
+typedef double slide_d2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void slide_store(double* p, double a, double b) {
+  const slide_d2 v = {a, b};
+  __builtin_nontemporal_store(v, reinterpret_cast<slide_d2*>(p));
+}
+#else
+__device__ __forceinline__ void slide_store(double* p, double a, double b) { *reinterpret_cast<double2*>(p) = make_double2(a, b); }
+#endif
 template <int W, int VEC, bool COUNT = false>
 __global__ void __launch_bounds__(XH_BLOCK)
 k_pdoy_slide(const float* __restrict__ x, int64_t T, int64_t C, int64_t st, int64_t t_first, int ndoy, int chunk,
@@ -256,7 +270,7 @@ k_pdoy_slide(const float* __restrict__ x, int64_t T, int64_t C, int64_t st, int6
       for (int g = 0; g < NP; ++g) {
         if (!okg[g]) continue;
         if (VEC == 4)
-          *reinterpret_cast<double2*>(orow + cg[g]) = make_double2(r[(2 * g) % VEC], r[(2 * g + 1) % VEC]);
+          slide_store(orow + cg[g], r[(2 * g) % VEC], r[(2 * g + 1) % VEC]);
         else
           orow[cg[g]] = r[0];
       }

@@ -13,9 +13,19 @@
  *     host<->device staging is explicit (xh_memcpy_h2d / xh_memcpy_d2h).
  *   - arrays are 2-D views (T, C): T time steps, C grid cells (lat*lon flattened).
  *     `st`, `sc` are ELEMENT strides of the time and cell axes.  Streaming kernels
- *     need sc == 1 ("time-major", xarray's native (time, lat, lon) C order);
- *     column kernels (full-series quantiles) take st == 1 ("time-minor", what
- *     apply_ufunc hands its callee) or transpose internally.
+ *     need sc == 1 and st >= C ("time-major", xarray's native (time, lat, lon) C
+ *     order; a row may be longer than C: a column slab of a wider field).  The
+ *     column kernels — xh_quantile_series, xh_eqm_train, xh_qdm_adjust,
+ *     xh_quantile_cells, xh_adapt_freq, and xh_nan_quantile / xh_nan_quantile_f64
+ *     with (sn, sc) — also take st == 1 and sc >= T ("time-minor", what apply_ufunc
+ *     hands its callee; a column may be longer than T); given a time-major view
+ *     they transpose batches of columns into scratch memory where the series
+ *     length asks for a column kernel.  xh_weighted_quantile takes the member-major
+ *     view only (sc == 1, sn >= C).  Outputs and second operands with a stride
+ *     parameter of their own (st_out, out_st, scen_st, st_b, st_high, fst,
+ *     thr_stride, ...) are time-major rows of at least C elements; outputs without
+ *     one are dense (row stride C).  Any other combination returns XH_ERR_LAYOUT.
+ *     tests/test_gpu_strided_abi.py runs every entry point on padded rows.
  *   - periods of `resample(time=freq)` are contiguous time segments described by
  *     seg_off[P+1] (host computes them from the calendar, xclim_amd/timeaxis.py).
  *   - work is enqueued on the context's HIP stream; xh_sync / xh_memcpy_d2h wait.

@@ -1,0 +1,1648 @@
+"""Every strided entry point of the C ABI on padded, poisoned row views (tests/stridedabi.py).
+
+Each case runs a wrapper of xclim_amd.kernels or a host mirror twice on the same seeded inputs: plainly, and inside
+``padded(...)``, which moves every strided operand into rows longer than the field is wide (a different pad for every
+stride argument of the call, NaN or 1e30 in the extra columns of the inputs, 0xA5 bytes in those of the outputs).
+  (a) the plain result meets the oracle at the bar its family has elsewhere in this suite;
+  (b) the padded result equals the plain one bit for bit (NaN equal to NaN): each cell's arithmetic runs in the same
+      order whatever the vector width;
+  (c) the replay reached every entry point of the case's ``reaches`` with a stride other than the operand's width.
+One more test hands every entry point of the table a row stride one short of the width and expects XH_ERR_LAYOUT."""
+import os
+import sys
+import warnings
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+if HERE not in sys.path:
+    sys.path.insert(0, HERE)
+
+import stridedabi as S  # noqa: E402
+from oracle import calendar as ocal  # noqa: E402
+from oracle import ensembles as oens  # noqa: E402
+from oracle import generic as ogen  # noqa: E402
+from oracle import quantile as oq  # noqa: E402
+from oracle import run_length as orl  # noqa: E402
+from oracle import sdba as osdba  # noqa: E402
+from oracle import synth as osynth  # noqa: E402
+from oracle.timeutil import OTime  # noqa: E402
+from xclim_amd.timeaxis import TimeAxis  # noqa: E402
+
+EXACT = None
+R6 = dict(rtol=1e-6, atol=0)
+START, STEPS = "2001-03-15", 800   # MS and YS segments with a partial period at each end
+NPOP = {">": np.greater, "<": np.less, ">=": np.greater_equal, "<=": np.less_equal, "==": np.equal, "!=": np.not_equal}
+
+# (cells, pads, shift): every stride odd (scalar paths), even strides (float64 keeps two lanes, float32 loses four), strides
+# that keep the vector paths (C = 260 only), and those on a base that is one element off
+LAYOUTS = [(67, (1, 3, 5), 0), (67, (2, 6, 10), 0), (260, (1, 3, 5), 0), (260, (2, 6, 10), 0), (260, (4, 12, 36), 0),
+           (260, (4, 12, 36), 1)]
+
+
+class Case:
+    def __init__(self, name, build, reaches, cells, f64):
+        self.name, self.build, self.reaches, self.cells, self.f64 = name, build, tuple(reaches), tuple(cells), f64
+
+
+CASES = {}
+
+
+def case(name, reaches, cells=(67, 260), f64=False, **kw):
+    """Register ``fn(rng, C, **kw) -> (run, oracle)``: ``run(dev)`` gives a list of arrays, ``oracle()`` a list of
+    (expected, bar) with bar None for bit-exact, keywords of assert_allclose, or a function (got, expected)."""
+    def deco(fn):
+        assert name not in CASES
+        CASES[name] = Case(name, lambda rng, C: fn(rng, C, **kw), reaches, cells, f64)
+        return fn
+    return deco
+
+
+def _axes(T=STEPS, start=START, calendar="standard"):
+    if calendar == "standard":
+        return TimeAxis.daily(start, T), OTime.standard(start, T)
+    return TimeAxis.daily(start, T, calendar), OTime.noleap(int(start[:4]), T, calendar)
+
+
+def _temp(rng, T, C, dtype=np.float32):
+    """Temperature-like: a 2 % NaN sprinkle, one all-NaN column, one constant column, ties."""
+    t = np.arange(T)[:, None]
+    x = 288 + 12 * np.sin(2 * np.pi * (t - 100) / 365) + rng.normal(0, 3, (T, C))
+    x = x.astype(dtype)
+    x[rng.random((T, C)) < 0.02] = np.nan
+    x[:, 0] = np.nan
+    if C > 2:
+        x[:, 1] = 290.0
+        x[:, 2] = np.round(x[:, 2])
+    if T > 5:
+        x[5, 3:] = 290.0   # exact ties with the threshold of the count cases
+    return x
+
+
+def _precip(rng, T, C):
+    x = np.where(rng.random((T, C)) < 0.35, rng.gamma(0.8, 8.0, (T, C)), 0.0).astype(np.float32)
+    x[rng.random((T, C)) < 0.02] = np.nan
+    x[:, 0] = np.nan
+    x[:, 1] = 0.0
+    return x
+
+
+def _mask(rng, T, C, nan=True):
+    m = (rng.random((T, C)) < 0.6).astype(np.float32)
+    m[10:60, : C // 3] = 1
+    if nan:
+        m[rng.random((T, C)) < 0.02] = np.nan
+    m[:, 0] = np.nan if nan else 0
+    m[:, 1] = 1
+    m[:, 2] = 0
+    return m
+
+
+def _per(a, seg, fn):
+    return np.stack([fn(a[s:e]) for s, e in zip(seg[:-1], seg[1:])])
+
+
+def _gets(*arrays):
+    return [a.get() for a in arrays if a is not None]
+
+
+def K():
+    from xclim_amd import kernels
+
+    return kernels
+
+
+# ---------------------------------------------------------------------------------------------- counts and reductions
+@case("threshold_count_scalar", ["xh_threshold_count"])
+@case("threshold_count_scalar_one_step", ["xh_threshold_count"], T=1)
+def _threshold_count_scalar(rng, C, T=STEPS):
+    x = _temp(rng, T, C)
+    ta, ot = _axes(T)
+    seg, _ = ta.segments("MS")
+
+    def run(dev):
+        return _gets(*K().threshold_count(dev, dev.to_device(x), ">=", seg, scalar=290.0))
+
+    return run, lambda: [(ogen.count_occurrences(x, 290.0, ">=", ot, "MS"), EXACT), (ogen.select_resample_op(x, "count", ot, "MS"), EXACT)]
+
+
+def _doy_table(rng, C, dtype):
+    t = 288 + 12 * np.sin(2 * np.pi * (np.arange(366)[:, None] - 100) / 365) + rng.normal(0, 1, (366, C))
+    t[rng.random(t.shape) < 0.01] = np.nan
+    return t.astype(dtype)
+
+
+@case("threshold_count_doy_table_f32", ["xh_threshold_count"], dtype=np.float32)
+@case("threshold_count_doy_table_f64", ["xh_threshold_count_doy"], dtype=np.float64)
+@case("threshold_count_full_f64", ["xh_threshold_count"], dtype=np.float64, full=True)
+def _threshold_count_table(rng, C, dtype, full=False):
+    x = _temp(rng, STEPS, C)
+    ta, ot = _axes()
+    seg, _ = ta.segments("YS")
+    table = _doy_table(rng, C, dtype)
+    tidx = (ta.doy - 1).astype(np.int32)
+
+    def run(dev):
+        k = K()
+        if full:
+            return _gets(*k.threshold_count(dev, dev.to_device(x), ">", seg, full=dev.to_device(table[tidx])))
+        return _gets(*k.threshold_count(dev, dev.to_device(x), ">", seg, doy_table=dev.to_device(table), tidx=tidx))
+
+    return run, lambda: [(ogen.threshold_count(x, ">", table[tidx], ot, "YS"), EXACT), (ogen.select_resample_op(x, "count", ot, "YS"), EXACT)]
+
+
+@case("domain_count", ["xh_domain_count"])
+def _domain_count(rng, C):
+    x = _temp(rng, STEPS, C)
+    ta, ot = _axes()
+    seg, _ = ta.segments("MS")
+
+    def run(dev):
+        return _gets(*K().domain_count(dev, dev.to_device(x), ">", 285.0, "<=", 295.0, "and", seg))
+
+    return run, lambda: [(ogen.domain_count(x, np.float32(285.0), np.float32(295.0), ot, "MS"), EXACT), (ogen.select_resample_op(x, "count", ot, "MS"), EXACT)]
+
+
+@case("bivariate_count", ["xh_bivariate_count"])
+def _bivariate_count(rng, C):
+    a, b = _temp(rng, STEPS, C), _temp(rng, STEPS, C) + np.float32(6)
+    ta, _ = _axes()
+    seg, _ = ta.segments("MS")
+
+    def run(dev):
+        return _gets(*K().bivariate_count(dev, dev.to_device(a), dev.to_device(b), ">", 288.0, "<", 296.0, "all", seg))
+
+    def oracle():
+        with np.errstate(invalid="ignore"):
+            hit = (a > np.float32(288.0)) & (b < np.float32(296.0))
+        ok = ~np.isnan(a) & ~np.isnan(b)
+        return [(_per(hit, seg, lambda g: g.sum(0)).astype(np.int32), EXACT), (_per(ok, seg, lambda g: g.sum(0)).astype(np.int32), EXACT)]
+
+    return run, oracle
+
+
+@case("range_reduce", ["xh_range_reduce"])
+def _range_reduce(rng, C):
+    lo = _temp(rng, STEPS, C)
+    hi = (lo + np.abs(rng.normal(6, 2, lo.shape))).astype(np.float32)
+    hi[rng.random(hi.shape) < 0.02] = np.nan
+    ta, ot = _axes()
+    seg, _ = ta.segments("MS")
+
+    def run(dev):
+        k, dl, dh = K(), dev.to_device(lo), dev.to_device(hi)
+        return [k.range_reduce(dev, dl, dh, "range", "mean", seg)[0].get(), k.range_reduce(dev, dl, dh, "interday", "mean", seg)[0].get(),
+                k.range_reduce(dev, dl, dh, "extreme", "max", seg)[0].get()]
+
+    def oracle():
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            return [(ogen.diurnal_temperature_range(lo, hi, "mean", ot, "MS"), R6),
+                    (ogen.interday_diurnal_temperature_range(lo, hi, ot, "MS"), dict(rtol=2e-6, atol=0)),
+                    (ogen.extreme_temperature_range(lo, hi, ot, "MS"), R6)]
+
+    return run, oracle
+
+
+@case("select_rows", ["xh_select_rows"])
+def _select_rows(rng, C):
+    x = _temp(rng, STEPS, C)
+    idx = rng.integers(-1, STEPS, 300)
+    idx[:3] = [-1, 0, STEPS - 1]
+
+    def run(dev):
+        k, d = K(), dev.to_device(x)
+        scatter = dev.to_device(np.full((40, C), -3.0, np.float32))
+        k.select_rows(dev, d, idx[:13], out=scatter, out_row=1, out_stride_rows=3)   # a strided destination of the caller
+        return [k.select_rows(dev, d, idx).get(), scatter.get()]
+
+    def oracle():
+        full = np.where(idx[:, None] >= 0, x[np.clip(idx, 0, None)], np.nan).astype(np.float32)
+        sc = np.full((40, C), -3.0, np.float32)
+        sc[1:1 + 13 * 3:3] = full[:13]
+        return [(full, EXACT), (sc, EXACT)]
+
+    return run, oracle
+
+
+@case("compare_map", ["xh_compare_map"])
+@case("compare_map_one_step", ["xh_compare_map"], T=1)
+def _compare_map(rng, C, T=STEPS):
+    a, b = _temp(rng, T, C), _temp(rng, T, C)
+    thr = 290.0
+
+    def run(dev):
+        k, da, db = K(), dev.to_device(a), dev.to_device(b)
+        return [k.compare_map(dev, da, ">=", thr, kind).get() for kind in ("mask", "events", "where", "maskf", "excess")] + \
+               [k.compare_map(dev, da, "<", db, "mask").get(), k.compare_map(dev, da, "<", db, "where").get()]
+
+    def oracle():
+        with np.errstate(invalid="ignore"):
+            c, cb = a >= np.float32(thr), a < b
+        nan = np.isnan(a)
+        return [(c.astype(np.uint8), EXACT), (np.where(nan, np.nan, c).astype(np.float32), EXACT), (np.where(c, a, np.nan), EXACT),
+                (c.astype(np.float32), EXACT), (np.where(nan, np.nan, np.clip(a - np.float32(thr), 0, None)).astype(np.float32), EXACT),
+                (cb.astype(np.uint8), EXACT), (np.where(cb, a, np.nan), EXACT)]
+
+    return run, oracle
+
+
+@case("thresholded_reduce", ["xh_thresholded_reduce"])
+def _thresholded_reduce(rng, C):
+    x = _temp(rng, STEPS, C)
+    ta, ot = _axes()
+    seg, _ = ta.segments("MS")
+
+    def run(dev):
+        k, d = K(), dev.to_device(x)
+        return [k.thresholded_reduce(dev, d, ">", 289.0, 0, "mean", seg)[0].get(), k.thresholded_reduce(dev, d, ">", 289.0, 1, "sum", seg)[0].get(),
+                k.thresholded_reduce(dev, d, ">", 289.0, 2, "sum", seg)[0].get()]
+
+    def oracle():
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            return [(ogen.thresholded_statistics(x, ">", np.float32(289.0), "mean", ot, "MS"), R6),
+                    (ogen.temperature_sum(x, ">", np.float32(289.0), ot, "MS"), dict(rtol=1e-6, atol=1e-4)),
+                    (ogen.cumulative_difference(x, np.float32(289.0), ">", ot, "MS"), dict(rtol=1e-6, atol=1e-4))]
+
+    return run, oracle
+
+
+@case("resample_reduce", ["xh_resample_reduce"])
+@case("resample_reduce_one_step", ["xh_resample_reduce"], T=1)
+def _resample_reduce(rng, C, T=STEPS):
+    x = _temp(rng, T, C)
+    ta, ot = _axes(T)
+    seg, _ = ta.segments("MS")
+    reducers = ("sum", "mean", "min", "std", "count", "argmax")
+
+    def run(dev):
+        d = dev.to_device(x)
+        return [K().resample_reduce(dev, d, r, seg)[0].get() for r in reducers]
+
+    def oracle():
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            return [(ogen.select_resample_op(x, r, ot, "MS"), EXACT if r in ("count", "argmax") else dict(rtol=1e-6, atol=1e-6 if r == "std" else 1e-30))
+                    for r in reducers]
+
+    return run, oracle
+
+
+@case("rolling_reduce", ["xh_rolling_reduce"])
+def _rolling_reduce(rng, C):
+    x = _temp(rng, 120, C)
+
+    def run(dev):
+        d = dev.to_device(x)
+        return [K().rolling_reduce(dev, d, 5, "mean", True).get(), K().rolling_reduce(dev, d, 3, "std", False).get(),
+                K().rolling_reduce(dev, d, 14, "max", True).get()]
+
+    return run, lambda: [(ogen.rolling(x, 5, "mean", True), R6), (ogen.rolling(x, 3, "std", False), dict(rtol=1e-6, atol=2e-6)),
+                         (ogen.rolling(x, 14, "max", True), R6)]
+
+
+@case("rolling_dot", ["xh_rolling_dot"])
+def _rolling_dot(rng, C):
+    x = _temp(rng, 200, C)
+    w = rng.random(7) + 0.1
+
+    def run(dev):
+        return [K().rolling_dot(dev, dev.to_device(x), w).get()]
+
+    def oracle():
+        exp = np.full(x.shape, np.nan)
+        for t in range(6, len(x)):
+            exp[t] = w @ x[t - 6: t + 1].astype(np.float64)
+        return [(exp.astype(np.float32), EXACT)]
+
+    return run, oracle
+
+
+@case("mask_rows", ["xh_mask_rows"])
+def _mask_rows(rng, C):
+    m = _mask(rng, STEPS, C)
+    ta, _ = _axes()
+    seg, _ = ta.segments("MS")
+    P = len(seg) - 1
+    lo, hi = rng.integers(0, 10, P), rng.integers(12, 40, P)
+
+    def run(dev):
+        return [K().mask_rows(dev, dev.to_device(m), seg, lo, hi).get()]
+
+    def oracle():
+        exp = np.zeros_like(m)
+        for p in range(P):
+            a, b = seg[p] + lo[p], min(seg[p] + hi[p], seg[p + 1])
+            exp[a:b] = np.nan_to_num(m[a:b], nan=0.0)
+        return [(exp, EXACT)]
+
+    return run, oracle
+
+
+@case("doy_mean_std_1y", ["xh_doy_mean_std"], cells=(67,), nyears=1)
+@case("doy_mean_std_5y", ["xh_doy_mean_std"], cells=(67,), nyears=5)
+@case("doy_mean_std_40y", ["xh_doy_mean_std"], cells=(67,), nyears=40)
+def _doy_mean_std(rng, C, nyears):
+    from xclim_amd.calendar import climatological_mean_doy
+
+    T = 365 * nyears
+    ta, ot = _axes(T, "1981-01-01", "noleap")
+    x = _temp(rng, T, C)
+
+    def run(dev):
+        m, s, _ = climatological_mean_doy(x, ta, window=5, device=dev)
+        return [m, s]
+
+    def oracle():
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            em, es, _ = ocal.climatological_mean_doy(x, ot, 5)
+        return [(em, R6), (es, dict(rtol=2e-6, atol=1e-6))]
+
+    return run, oracle
+
+
+# ---------------------------------------------------------------------------------------------------- run lengths
+@case("cumsum_reset_rle", ["xh_cumsum_reset", "xh_rle"])
+@case("cumsum_reset_rle_one_step", ["xh_cumsum_reset", "xh_rle"], T=1)
+def _cumsum_rle(rng, C, T=200):
+    m = _mask(rng, T, C) if T > 60 else (rng.random((T, C)) < 0.5).astype(np.float32)
+
+    def run(dev):
+        d = dev.to_device(m)
+        return [K().cumsum_reset(dev, d, "last").get(), K().cumsum_reset(dev, d, "first").get(), K().rle(dev, d, "first").get(),
+                K().rle(dev, d, "last").get()]
+
+    return run, lambda: [(orl.cumsum_reset(m, "last"), EXACT), (orl.cumsum_reset(m, "first"), EXACT), (orl.rle(m, "first"), EXACT),
+                         (orl.rle(m, "last"), EXACT)]
+
+
+@case("run_stats", ["xh_run_stats"])
+def _run_stats(rng, C):
+    m = _mask(rng, STEPS, C)
+    pr = _precip(rng, STEPS, C)
+    ta, ot = _axes()
+    seg, _ = ta.segments("MS")
+    forms = [("max", 1, True, "first"), ("mean", 3, False, "last"), ("count", 2, True, "last"), ("first", 3, True, "first")]
+
+    def run(dev):
+        d = dev.to_device(m)
+        out = [K().run_stats(dev, d, s, w, seg, cut=c, index=i)[0].get() for s, w, c, i in forms]
+        fused, valid = K().run_stats(dev, dev.to_device(pr), "max", 1, seg, cut=True, fused_op="<", thresh=1.0)
+        return out + [fused.get(), valid.get()]
+
+    def oracle():
+        exp = []
+        for s, w, c, i in forms:
+            if s == "first":
+                exp.append((orl.resample_and_rl(m, c, orl.first_run, w, time=ot, freq="MS"), EXACT))
+            else:
+                exp.append((orl.resample_and_rl(m, c, orl.rle_statistics, time=ot, freq="MS", reducer=s, window=w, index=i, ufunc_1dim=False),
+                            R6 if s == "mean" else EXACT))
+        exp.append((ogen.spell_length_statistics(pr, 1.0, 1, None, "<", "max", ot, "MS", resample_before_rl=True), EXACT))
+        exp.append((ogen.select_resample_op(pr, "count", ot, "MS"), EXACT))
+        return exp
+
+    return run, oracle
+
+
+@case("spell_mask", ["xh_spell_mask"])
+def _spell_mask(rng, C):
+    x = _temp(rng, 400, C)
+    w = [0.2, 0.5, 0.3]
+
+    def run(dev):
+        d = dev.to_device(x)
+        return [K().spell_mask(dev, d, 3, "mean", ">", 289.0).get(), K().spell_mask(dev, d, 5, "min", ">=", 286.0).get(),
+                K().spell_mask(dev, d, 3, "mean", ">", 289.0, weights=w).get()]
+
+    return run, lambda: [(ogen.spell_mask(x, 3, "mean", ">", 289.0).astype(np.float32), EXACT),
+                         (ogen.spell_mask(x, 5, "min", ">=", 286.0).astype(np.float32), EXACT),
+                         (ogen.spell_mask(x, 3, "mean", ">", 289.0, weights=w).astype(np.float32), EXACT)]
+
+
+@case("spell_run_stats", ["xh_spell_run_stats"])
+def _spell_run_stats(rng, C):
+    x = _temp(rng, STEPS, C)
+    ta, ot = _axes()
+    seg, _ = ta.segments("MS")
+
+    def run(dev):
+        out, valid = K().spell_run_stats(dev, dev.to_device(x), 3, "mean", ">", 289.0, "max", seg)
+        return [out.get(), valid.get()]
+
+    return run, lambda: [(ogen.spell_length_statistics(x, 289.0, 3, "mean", ">", "max", ot, "MS", resample_before_rl=True), EXACT),
+                         (ogen.select_resample_op(x, "count", ot, "MS"), EXACT)]
+
+
+@case("spell_mask_multi", ["xh_spell_mask_multi"])
+def _spell_mask_multi(rng, C):
+    a, b = _temp(rng, 400, C), _temp(rng, 400, C)
+
+    def run(dev):
+        return [K().spell_mask_multi(dev, [dev.to_device(a), dev.to_device(b)], 3, "min", ">", [287.0, 286.0], "all").get()]
+
+    return run, lambda: [(ogen.spell_mask([a, b], 3, "min", ">", [287.0, 286.0], var_reducer="all").astype(np.float32), EXACT)]
+
+
+@case("runs_with_holes", ["xh_runs_with_holes"])
+def _runs_with_holes(rng, C):
+    start = rng.random((400, C)) < 0.4
+    stop = rng.random((400, C)) < 0.3
+    start[:, 0], start[:, 1] = False, True
+
+    def run(dev):
+        k = K()
+        ds, dp = dev.to_device(start.astype(np.float32)), dev.to_device(stop.astype(np.float32))
+        return [k.runs_with_holes(dev, ds, 3, dp, 2).get(), k.runs_with_holes(dev, ds, 2, None, 2).get()]
+
+    return run, lambda: [(np.asarray(orl.runs_with_holes(start, 3, stop, 2), np.float32), EXACT),
+                         (np.asarray(orl.runs_with_holes(start, 2, ~start, 2), np.float32), EXACT)]
+
+
+@case("keep_longest_run", ["xh_keep_longest_run"])
+def _keep_longest_run(rng, C):
+    a = rng.random((STEPS, C)) < 0.6
+    a[:, 0], a[:, 1] = False, True
+    ta, ot = _axes()
+    seg, _ = ta.segments("MS")
+
+    def run(dev):
+        return [K().keep_longest_run(dev, dev.to_device(a.astype(np.float32)), seg).get()]
+
+    return run, lambda: [(np.asarray(orl.keep_longest_run(a, ot, "MS"), np.float32), EXACT)]
+
+
+@case("season", ["xh_season"])
+def _season(rng, C):
+    from xclim_amd import run_length as xrl
+
+    T = STEPS
+    t = np.arange(T)[:, None]
+    cond = 5 + 12 * np.sin(2 * np.pi * (t - 30) / 365) + rng.normal(0, 4, (T, C)) > 5
+    cond[:, 0], cond[:, 1] = True, False
+    ta, ot = _axes()
+
+    def run(dev):
+        got = xrl.season(cond, 5, "07-01", time=ta, freq="YS", device=dev)
+        return [np.asarray(got[k]) for k in ("start", "end", "length")]
+
+    return run, lambda: [(e, EXACT) for e in orl.season_per_period(cond, 5, "07-01", ot, "YS")]
+
+
+@case("max_run_sum", ["xh_max_run_sum"])
+def _max_run_sum(rng, C):
+    x = np.clip(_temp(rng, STEPS, C) - np.float32(289), 0, None)
+    ta, ot = _axes()
+    seg, _ = ta.segments("MS")
+
+    def run(dev):
+        return [K().max_run_sum(dev, dev.to_device(x), 3, seg, cut=True).get()]
+
+    def oracle():
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            return [(orl.resample_and_rl(x, True, orl.windowed_max_run_sum, 3, time=ot, freq="MS"), R6)]
+
+    return run, oracle
+
+
+@case("run_events", ["xh_run_events"])
+def _run_events(rng, C):
+    T, maxev = 400, 40
+    runs = np.repeat(rng.random((T // 8, C)) < 0.5, 8, axis=0).astype(np.float32)
+    runs[:, 0], runs[:, 1] = 0, 1
+    eff = (rng.random((T, C)) < 0.7).astype(np.float32)
+    data = rng.gamma(1.0, 3.0, (T, C)).astype(np.float32)
+    data[rng.random((T, C)) < 0.01] = np.nan
+    names = ("start", "end", "len", "eff", "sum")
+
+    def run(dev):
+        out = K().run_events(dev, dev.to_device(runs), [0, T], maxev, eff=dev.to_device(eff), data=dev.to_device(data), want=names)
+        return [out[k].get() for k in names]
+
+    def oracle():
+        exp = {k: np.full((1, maxev, C), np.nan, np.float32) for k in names}
+        # the sum up to the first NaN of the data, in the reference's own float32 arithmetic (differences of one running sum)
+        esum = orl.cumsum_reset_xr(np.where(runs == 1, data, np.float32(np.nan)), "first", False)
+        for c in range(C):
+            k, t = 0, 0
+            while t < T:
+                if runs[t, c] == 0:
+                    t += 1
+                    continue
+                e = t
+                while e < T and runs[e, c] != 0:
+                    e += 1
+                exp["start"][0, k, c], exp["len"][0, k, c] = t, e - t
+                exp["end"][0, k, c] = e if e < T else np.nan
+                exp["eff"][0, k, c] = (eff[t:e, c] != 0).sum()
+                exp["sum"][0, k, c] = esum[t, c]
+                k, t = k + 1, e
+        return [(exp[k], EXACT) for k in names]
+
+    return run, oracle
+
+
+@case("suspicious_run", ["xh_suspicious_run"])
+def _suspicious_run(rng, C):
+    x = np.round(_temp(rng, 400, C) / 4)
+
+    def run(dev):
+        return [K().suspicious_run(dev, dev.to_device(x), 3, ">", 71.0).get(), K().suspicious_run(dev, dev.to_device(x), 2).get()]
+
+    return run, lambda: [(np.asarray(orl.suspicious_run(x, 3, ">", 71.0), np.uint8), EXACT), (np.asarray(orl.suspicious_run(x, 2, ">", None), np.uint8), EXACT)]
+
+
+# ------------------------------------------------------------------------------------------- day-of-year tables
+def _doy_inputs(rng, C):
+    x = _temp(rng, STEPS, C)
+    ta, ot = _axes()
+    tidx = (ta.doy - 1).astype(np.int32)
+    return x, ta, ot, tidx
+
+
+@case("within_bnds_doy", ["xh_within_bnds_doy"])
+def _within_bnds(rng, C):
+    x, ta, ot, tidx = _doy_inputs(rng, C)
+    low, high = _doy_table(rng, C, np.float64) - 4, _doy_table(rng, C, np.float64) + 4
+
+    def run(dev):
+        return [K().within_bnds_doy(dev, dev.to_device(x), dev.to_device(low), dev.to_device(high), tidx).get()]
+
+    def oracle():
+        with np.errstate(invalid="ignore"):
+            return [(((low[tidx] < x) & (x < high[tidx])).astype(np.uint8), EXACT)]
+
+    return run, oracle
+
+
+@case("compare_doy_run_stats_doy", ["xh_compare_doy", "xh_run_stats_doy"])
+def _compare_doy(rng, C):
+    x, ta, ot, tidx = _doy_inputs(rng, C)
+    table = _doy_table(rng, C, np.float64)
+    seg, _ = ta.segments("MS")
+
+    def run(dev):
+        d, dt = dev.to_device(x), dev.to_device(table)
+        st, valid = K().run_stats_doy(dev, d, ">", dt, tidx, "max", 3, seg)
+        return [K().compare_doy(dev, d, ">", dt, tidx).get(), st.get(), valid.get()]
+
+    def oracle():
+        with np.errstate(invalid="ignore"):
+            cond = x.astype(np.float64) > table[tidx]
+        return [(cond.astype(np.float32), EXACT), (_per(cond, seg, lambda g: orl.rle_statistics(g, "max", 3)), EXACT),
+                (ogen.select_resample_op(x, "count", ot, "MS"), EXACT)]
+
+    return run, oracle
+
+
+@case("precip_over_doy", ["xh_precip_over_doy"])
+def _precip_over(rng, C):
+    x = _precip(rng, STEPS, C)
+    ta, ot = _axes()
+    tidx = (ta.doy - 1).astype(np.int32)
+    seg, _ = ta.segments("MS")
+    table = np.abs(rng.normal(6, 4, (366, C)))
+    table[rng.random(table.shape) < 0.02] = np.nan
+
+    def run(dev):
+        cnt, frac, valid = K().precip_over_doy(dev, dev.to_device(x), ">", 1.0, dev.to_device(table), tidx, seg, want=("count", "frac"))
+        return [cnt.get(), frac.get(), valid.get()]
+
+    def oracle():
+        with np.errstate(invalid="ignore", divide="ignore"):
+            tp = np.where(table[tidx] > 1.0, table[tidx], 1.0)
+            over = x.astype(np.float64) > tp
+            wet = x > np.float32(1.0)
+            num = _per(np.where(over, x, 0).astype(np.float64), seg, lambda g: g.sum(0))
+            den = _per(np.where(wet, x, 0).astype(np.float64), seg, lambda g: g.sum(0))
+            return [(_per(over, seg, lambda g: g.sum(0)).astype(np.int32), EXACT), ((num / den).astype(np.float32), dict(rtol=1e-6, atol=0)),
+                    (ogen.select_resample_op(x, "count", ot, "MS"), EXACT)]
+
+    return run, oracle
+
+
+@case("mask_doy_cells", ["xh_mask_doy_cells"])
+def _mask_doy_cells(rng, C):
+    x, ta, ot, _ = _doy_inputs(rng, C)
+    start = rng.integers(1, 366, C).astype(np.float32)
+    end = rng.integers(1, 366, C).astype(np.float32)
+    start[3], end[4] = np.nan, np.nan
+
+    def run(dev):
+        return [K().mask_doy_cells(dev, dev.to_device(x), ta.doy, dev.to_device(start), dev.to_device(end)).get()]
+
+    def oracle():
+        s, e, d = np.where(np.isnan(start), 1, start), np.where(np.isnan(end), 366, end), np.asarray(ta.doy)[:, None]
+        inside = np.where(s <= e, (d >= s) & (d <= e), (d >= s) | (d <= e))
+        return [(np.where(inside, x, np.nan), EXACT)]
+
+    return run, oracle
+
+
+@case("mask_days_cells", ["xh_mask_days_cells"])
+def _mask_days_cells(rng, C):
+    x, ta, ot, _ = _doy_inputs(rng, C)
+    seg, _ = ta.segments("MS")
+    P = len(seg) - 1
+    lo = rng.integers(0, 12, (P, C)).astype(np.float32)
+    hi = rng.integers(10, 31, (P, C)).astype(np.float32)
+    lo[2, :5] = np.inf
+
+    def run(dev):
+        return [K().mask_days_cells(dev, dev.to_device(x), seg, dev.to_device(lo), dev.to_device(hi)).get()]
+
+    def oracle():
+        exp = np.full_like(x, np.nan)
+        for p in range(P):
+            rel = np.arange(seg[p + 1] - seg[p])[:, None]
+            blk = x[seg[p]:seg[p + 1]]
+            exp[seg[p]:seg[p + 1]] = np.where((lo[p] <= rel) & (rel <= hi[p]), blk, np.nan)
+        return [(exp, EXACT)]
+
+    return run, oracle
+
+
+# ------------------------------------------------------------------------------------------------------ quantiles
+def _series(rng, T, C):
+    from test_gpu_ladders import TM_SPLITS, _series as ladder_series
+
+    return ladder_series(rng, T, C, TM_SPLITS)
+
+
+@case("nan_quantile", ["xh_nan_quantile"])
+def _nan_quantile(rng, C, dtype=np.float32):
+    x = _temp(rng, 150, C, dtype)
+    q = np.array([0.0, 0.1, 0.5, 0.9, 1.0])
+
+    def run(dev):
+        return [K().nan_quantile(dev, dev.to_device(x), q, 1 / 3, 1 / 3).get()]
+
+    def oracle():
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            return [(oq.nan_quantile(x, q, 0, 1 / 3, 1 / 3), dict(rtol=1e-12, atol=0))]
+
+    return run, oracle
+
+
+case("nan_quantile_f64", ["xh_nan_quantile_f64"], dtype=np.float64)(_nan_quantile)
+
+
+def _nan_quantile_minor(rng, C, T, dtype):
+    x = _series(rng, T, C).astype(dtype)
+    q = np.array([0.0, 0.1, 0.5, 0.9, 1.0])
+
+    def run(dev):
+        return [K().nan_quantile(dev, dev.to_device(np.ascontiguousarray(x.T)), q, 1.0, 1.0, sample_axis=1).get()]
+
+    def oracle():
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            return [(oq.nan_quantile(x, q, 0, 1.0, 1.0), dict(rtol=1e-12, atol=0))]
+
+    return run, oracle
+
+
+for _T in (300, 1500):
+    case(f"nan_quantile_time_minor_{_T}", ["xh_nan_quantile"], cells=(67,), T=_T, dtype=np.float32)(_nan_quantile_minor)
+    case(f"nan_quantile_f64_time_minor_{_T}", ["xh_nan_quantile_f64"], cells=(67,), T=_T, dtype=np.float64)(_nan_quantile_minor)
+
+
+@case("weighted_quantile", ["xh_weighted_quantile"])
+def _weighted_quantile(rng, C):
+    x = _temp(rng, 30, C)
+    w = rng.random(30) + 0.1
+    w[4] = 0.0
+    q = np.array([0.1, 0.5, 0.9])
+
+    def run(dev):
+        return [K().weighted_quantile(dev, dev.to_device(x), w, q).get()]
+
+    def oracle():
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            return [(np.stack([oens.weighted_quantile_1d(x[:, c], w, q) for c in range(C)], axis=1), R6)]
+
+    return run, oracle
+
+
+def _percentile_doy(rng, C, nyears):
+    from xclim_amd.calendar import percentile_doy
+
+    T = 365 * nyears
+    ta, ot = _axes(T, "1981-01-01", "noleap")
+    x = _temp(rng, T, C)
+    per = [10.0, 50.0, 90.0]
+
+    def run(dev):
+        return [percentile_doy(x, ta, window=5, per=per, device=dev).values()]
+
+    def oracle():
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            return [(ocal.percentile_doy(x, ot, 5, per)[0], dict(rtol=1e-12, atol=0))]
+
+    return run, oracle
+
+
+def _percentile_doy_one(rng, C, nyears):
+    """One percentile on a window of 5: the quad kernel on multi-year base periods."""
+    from xclim_amd.calendar import percentile_doy
+
+    T = 365 * nyears
+    ta, ot = _axes(T, "1981-01-01", "noleap")
+    x = _temp(rng, T, C)
+
+    def run(dev):
+        return [percentile_doy(x, ta, window=5, per=[90.0], device=dev).values()]
+
+    def oracle():
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            return [(ocal.percentile_doy(x, ot, 5, [90.0])[0], dict(rtol=1e-12, atol=0))]
+
+    return run, oracle
+
+
+def _percentile_doy_count(rng, C, nyears):
+    T = 365 * nyears
+    ta, ot = _axes(T, "1981-01-01", "noleap")
+    x = _temp(rng, T, C)
+    per = {1: 90.0, 3: 90.0, 40: 95.0, 70: 99.0}[nyears]
+    tb, years, doys = ta.doy_table()
+    seg, _ = ta.segments("YS")
+    P = len(seg) - 1
+    period = (np.searchsorted(seg, tb, side="right") - 1).astype(np.int32)
+    period[tb < 0] = -1
+
+    tidx = np.searchsorted(doys, ta.doy).astype(np.int32)
+
+    def run(dev):
+        d = dev.to_device(x)
+        fused = K().percentile_doy_count(dev, d, tb, 5, per, ">", period, P)
+        # the fused kernels serve one year and 7 .. 64 years (quantile.hip: pdoy_count_multi); else the two-step chain
+        assert (fused is not None) == (nyears in (1, 40)), "the fused kernel served another set of shapes"
+        if fused is None:
+            p = K().percentile_doy(dev, d, tb, 5, [per])
+            fused = K().threshold_count(dev, d, ">", seg, doy_table=p.reshape(len(doys), C), tidx=tidx)
+        return [fused[0].get(), fused[1].get()]
+
+    def oracle():
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            pe, d2 = ocal.percentile_doy(x, ot, 5, per)
+            thresh = ocal.resample_doy(pe[..., 0], d2, ot)
+            return [(ogen.threshold_count(x, ">", thresh, ot, "YS"), EXACT), (ogen.select_resample_op(x, "count", ot, "YS"), EXACT)]
+
+    return run, oracle
+
+
+for _ny in (1, 3, 40, 70):
+    case(f"percentile_doy_{_ny}y", ["xh_percentile_doy"], cells=(67,), nyears=_ny)(_percentile_doy)
+    case(f"percentile_doy_count_{_ny}y", ["xh_percentile_doy_count"] if _ny in (1, 40) else ["xh_percentile_doy", "xh_threshold_count_doy"],
+         cells=(67,), nyears=_ny)(_percentile_doy_count)
+case("percentile_doy_one_percentile_40y", ["xh_percentile_doy"], cells=(67,), nyears=40)(_percentile_doy_one)
+
+
+@case("percentile_doy_mapped", ["xh_percentile_doy_mapped"], cells=(67,))
+def _percentile_doy_mapped(rng, C):
+    nyears, T = 4, 365 * 4
+    ta, ot = _axes(T, "2001-01-01", "noleap")
+    x = _temp(rng, T, C)
+    tb, years, doys = ta.doy_table()
+    vmap = np.arange(T, dtype=np.int32)
+    vmap[365:730] = np.arange(365 * 3, 365 * 4)
+    vmap[365 * 2 + 59] = -1
+
+    def run(dev):
+        return [K().percentile_doy(dev, dev.to_device(x), tb, 5, [10.0, 90.0], vmap=vmap).get()]
+
+    def oracle():
+        xm = np.where(vmap[:, None] >= 0, x[np.clip(vmap, 0, None)], np.nan).astype(np.float32)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            return [(np.moveaxis(ocal.percentile_doy(xm, ot, 5, [10.0, 90.0])[0], -1, 0), dict(rtol=1e-12, atol=0))]
+
+    return run, oracle
+
+
+# ----------------------------------------------------------------------------------------------------------- sdba
+def _quantile_series(rng, C, T, minor=False):
+    x = _series(rng, T, C)
+    q = osdba.equally_spaced_nodes(20)
+
+    def run(dev):
+        if minor:
+            return [K().quantile_series(dev, dev.to_device(np.ascontiguousarray(x.T)), q, time_axis=1).get()]
+        return [K().quantile_series(dev, dev.to_device(x), q).get()]
+
+    def oracle():
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            return [(osdba.quantile(x, q), R6)]
+
+    return run, oracle
+
+
+def _eqm_train(rng, C, T, minor=False):
+    ref, hist = _series(rng, T, C), (_series(rng, T, C) + np.float32(1.5))
+    q = osdba.equally_spaced_nodes(20)
+
+    def run(dev):
+        if minor:
+            return _gets(*K().eqm_train(dev, dev.to_device(np.ascontiguousarray(ref.T)), dev.to_device(np.ascontiguousarray(hist.T)), q, "+", time_axis=1))
+        return _gets(*K().eqm_train(dev, dev.to_device(ref), dev.to_device(hist), q, "+"))
+
+    def oracle():
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            eaf, ehq = osdba.eqm_train(ref, hist, 20, "+")
+        return [(eaf, dict(rtol=1e-5, atol=1e-5)), (ehq, R6)]
+
+    return run, oracle
+
+
+def _qdm_adjust(rng, C, T, minor=False):
+    nq = 20
+    q = osdba.equally_spaced_nodes(nq)
+    sim = np.abs(13 + 4 * rng.standard_normal((T, C))).astype(np.float32) + 1
+    sim[rng.random((T, C)) < 0.03] = np.nan
+    sim[:, 0] = np.nan
+    sim[:, 1] = 7.25
+    sim[:, 2] = np.round(sim[:, 2])
+    if T > 10:
+        sim[T // 3] = sim[T // 2]
+    af = rng.normal(0, 1, (nq, C)).astype(np.float32)
+
+    def run(dev):
+        if minor:
+            return [K().qdm_adjust(dev, dev.to_device(np.ascontiguousarray(sim.T)), dev.to_device(af), q, "+", "linear", "constant", time_axis=1).get().T]
+        return [K().qdm_adjust(dev, dev.to_device(sim), dev.to_device(af), q, "+", "linear", "constant").get()]
+
+    def oracle():
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            return [(osdba.qdm_adjust(sim, af, q, "+", "linear", "constant"), R6)]
+
+    return run, oracle
+
+
+for _T in (400, 700, 1100):   # the short kernels, the transposed pipeline, select4.hip
+    case(f"quantile_series_{_T}", ["xh_quantile_series"], T=_T)(_quantile_series)
+    case(f"eqm_train_{_T}", ["xh_eqm_train"], T=_T)(_eqm_train)
+    case(f"qdm_adjust_{_T}", ["xh_qdm_adjust"], T=_T)(_qdm_adjust)
+for _T in (300, 1500):
+    case(f"quantile_series_time_minor_{_T}", ["xh_quantile_series"], cells=(67,), T=_T, minor=True)(_quantile_series)
+    case(f"eqm_train_time_minor_{_T}", ["xh_eqm_train"], cells=(67,), T=_T, minor=True)(_eqm_train)
+    case(f"qdm_adjust_time_minor_{_T}", ["xh_qdm_adjust"], cells=(67,), T=_T, minor=True)(_qdm_adjust)
+case("quantile_series_one_step", ["xh_quantile_series"], cells=(67,), T=1)(_quantile_series)
+
+
+def _quantile_cells(rng, C, T, minor=False):
+    x = _series(rng, T, C)
+    qc = rng.random(C)
+    qc[4] = np.nan
+
+    def run(dev):
+        if minor:
+            return [K().quantile_cells(dev, dev.to_device(np.ascontiguousarray(x.T)), qc, time_axis=1).get()]
+        return [K().quantile_cells(dev, dev.to_device(x), qc).get()]
+
+    def oracle():
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            exp = np.array([oq.nan_quantile(x[:, c:c + 1], np.array([qc[c]]), 0, 1.0, 1.0)[0, 0] if not np.isnan(qc[c]) else np.nan
+                            for c in range(C)])
+        return [(exp.astype(np.float32), R6)]
+
+    return run, oracle
+
+
+case("quantile_cells", ["xh_quantile_cells"], T=400)(_quantile_cells)
+for _T in (300, 1500):
+    case(f"quantile_cells_time_minor_{_T}", ["xh_quantile_cells"], cells=(67,), T=_T, minor=True)(_quantile_cells)
+
+
+def _adapt_freq(rng, C, T, minor=False):
+    sim, ref = _precip(rng, T, C), _precip(rng, T, C)
+    ref[ref < 2.5] = 0          # a drier reference: dP0 > 0 in most cells
+    ref[:, 5:9] = sim[:, 5:9] * np.float32(1.3)
+    f32 = np.float32
+    with np.errstate(all="ignore"), warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        p0_sim = (sim <= f32(1.0)).sum(axis=0) / (~np.isnan(sim)).sum(axis=0)
+        p0_ref = (ref <= f32(1.0)).sum(axis=0) / (~np.isnan(ref)).sum(axis=0)
+        dp0 = (p0_sim - p0_ref) / p0_sim
+        pth = np.full(C, np.nan, f32)
+        for c in range(C):
+            if dp0[c] > 0:
+                pth[c] = oq.nan_quantile(ref[:, c], np.array([p0_sim[c]]), axis=0, alpha=1.0, beta=1.0)[0].astype(f32)
+
+    def run(dev):
+        if minor:   # (kernels.adapt_freq passes the time-major strides only: the time-minor form through dev.call)
+            import ctypes
+
+            vp = ctypes.c_void_p
+            d = dev.to_device(np.ascontiguousarray(sim.T))
+            tabs = [dev.to_device(np.ascontiguousarray(a, dtype=dt)) for a, dt in ((p0_ref, np.float64), (p0_sim, np.float64), (dp0, np.float64), (pth, np.float32))]
+            scen = dev.empty((C, T), np.float32)
+            dev.call("xh_adapt_freq", vp(d.ptr), T, C, 1, T, *(vp(a.ptr) for a in tabs), 1.0, 7, None, 0, vp(scen.ptr))
+            dev.sync()
+            return [scen.get().T]
+        return [K().adapt_freq(dev, dev.to_device(sim), p0_ref, p0_sim, dp0, pth, 1.0, seed=7).get()]
+
+    def oracle():
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            return [(osdba.adapt_freq(ref, sim, 1.0, seed=7)[0], R6)]
+
+    return run, oracle
+
+
+case("adapt_freq", ["xh_adapt_freq"], T=400)(_adapt_freq)
+for _T in (300, 1500):
+    case(f"adapt_freq_time_minor_{_T}", ["xh_adapt_freq"], cells=(67,), T=_T, minor=True)(_adapt_freq)
+
+
+def _eqm_nodes(rng, nq, C):
+    from test_gpu_ladders import _eqm_nodes as ladder_nodes
+
+    return ladder_nodes(rng, nq, C)
+
+
+def _eqm_adjust(rng, C, nq):
+    sim = _temp(rng, 413, C) + np.float32(2)
+    eaf, ehq = _eqm_nodes(rng, nq, C)
+    interps = ("nearest", "linear") + (("cubic",) if nq <= 32 else ())   # (the cubic kernel holds at most 32 nodes)
+
+    def run(dev):
+        d, a, h = dev.to_device(sim), dev.to_device(eaf), dev.to_device(ehq)
+        return [K().eqm_adjust(dev, d, a, h, "+", i, "constant").get() for i in interps]
+
+    def oracle():
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            return [(osdba.eqm_adjust(sim, eaf, ehq, "+", i, "constant"), dict(rtol=2e-6, atol=0) if i == "cubic" else R6) for i in interps]
+
+    return run, oracle
+
+
+def _grouped_nearest(rng, C, nq):
+    from test_gpu_ladders import _group_nodes
+
+    G, T = 12, 300
+    hq, af = _group_nodes(rng, G, nq, C)
+    x = (288 + rng.normal(0, 8, (T, C))).astype(np.float32)
+    x[rng.random((T, C)) < 0.03] = np.nan
+    x[:, 0] = np.nan
+    g = rng.integers(1, G + 1, T).astype(np.float64)
+    g[:2] = [1.0, float(G)]
+    labels = np.arange(1, G + 1)
+    rows = x[g == 5]
+    base = (x * np.float32(0.5) + rng.normal(0, 1, x.shape)).astype(np.float32)
+
+    def run(dev):
+        import ctypes
+
+        vp = ctypes.c_void_p
+        hd, ad, xd = dev.to_device(hq), dev.to_device(af), dev.to_device(x)
+        bd, gd, scen = dev.to_device(base), dev.to_device(g), dev.empty((T, C), np.float32)
+        # the factor applied to another field than the abscissa (kernels.plane_nearest has no `base`)
+        dev.call("xh_plane_nearest", vp(xd.ptr), vp(bd.ptr), T, C, C, vp(gd.ptr), vp(hd.ptr), None, vp(ad.ptr), G, nq, 0, 0, vp(scen.ptr), C)
+        dev.sync()
+        return [K().plane_nearest(dev, xd, g, ad, hd, "+", "constant").get(),
+                K().eqm_adjust_g2d(dev, dev.to_device(rows), ad, hd, 5, "+", "constant").get(), scen.get()]
+
+    def ties(got, exp):   # (as tests/test_gpu_api.py: two nodes at exactly the same distance of a query; scipy returns either)
+        from test_gpu_api import _accept_plane_nearest_ties
+
+        bad = ~np.isclose(got, exp, rtol=1e-6, atol=0, equal_nan=True)
+        if bad.any():
+            ties.at = bad.copy()
+            bad = _accept_plane_nearest_ties(bad, got, x, g, hq, af, "+")
+        assert not bad.any(), f"{int(bad.sum())} mismatches"
+
+    ties.at = np.zeros(x.shape, bool)
+
+    def with_base(got, exp):   # (the same queries: only those accepted as exact ties above may differ)
+        bad = ~np.isclose(got, exp, rtol=1e-6, atol=0, equal_nan=True) & ~ties.at
+        assert not bad.any(), f"{int(bad.sum())} mismatches"
+
+    def oracle():
+        fac = osdba.interp_on_quantiles_2d(x, g, labels, hq, af, "nearest", "constant")
+        fac5 = osdba.interp_on_quantiles_2d(rows, np.full(len(rows), 5.0), labels, hq, af, "nearest", "constant")
+        return [((x + fac).astype(np.float32), ties), (rows + fac5, R6), ((base + fac).astype(np.float32), with_base)]
+
+    return run, oracle
+
+
+def _plane_linear(rng, C, nq):
+    from test_gpu_plane import _cocircular, _nodes
+
+    G, T = 12, 200
+    xq, yq = _nodes(rng, G, nq, C, 1.5, "t")
+    lo, hi = xq.min(), xq.max()
+    x = rng.uniform(lo - 0.1 * (hi - lo), hi + 0.1 * (hi - lo), (T, C)).astype(np.float32)
+    x[rng.random((T, C)) < 0.03] = np.nan
+    x[:, 0] = np.nan
+    g = rng.uniform(0.5, G + 0.5, T)
+    base = (x * np.float32(0.5)).astype(np.float32)
+
+    def run(dev):
+        xd, yd, qd = dev.to_device(x), dev.to_device(yq), dev.to_device(xq)
+        return [K().plane_linear(dev, xd, g, yd, xq_all=qd, kind="factor").get(),
+                K().plane_linear(dev, xd, g, yd, xq_all=qd, base=dev.to_device(base), kind="+").get()]
+
+    def bar(got, exp):   # the acceptance of tests/test_gpu_plane.py: only verified exact degeneracies may differ, a handful at most
+        assert np.array_equal(np.isnan(got), np.isnan(exp))
+        bad = ~np.isclose(got, exp, rtol=1e-6, atol=1e-6 * max(1.0, float(np.nanmax(np.abs(yq)))), equal_nan=True)
+        assert bad.sum() <= 4, f"{int(bad.sum())} mismatches"
+        for t, c in np.argwhere(bad):
+            assert _cocircular(x, g, xq, yq, t, c), f"query ({t}, {c}): got {got[t, c]}, scipy {exp[t, c]}"
+
+    def oracle():
+        fac = osdba.interp_on_quantiles_2d(x, g, np.arange(1, G + 1), xq, yq, "linear", "constant")
+        return [(fac, bar), ((base + fac).astype(np.float32), bar)]
+
+    return run, oracle
+
+
+for _nq in (10, 20, 32, 33):
+    case(f"eqm_adjust_nq{_nq}", ["xh_eqm_adjust"], cells=(67,), nq=_nq)(_eqm_adjust)
+    case(f"plane_linear_nq{_nq}", ["xh_plane_linear"], cells=(67,), nq=_nq)(_plane_linear)
+for _nq in (10, 20, 32):   # (both refuse more than 32 nodes: tests/test_gpu_ladders.py)
+    case(f"grouped_nearest_nq{_nq}", ["xh_plane_nearest", "xh_eqm_adjust_g2d"], cells=(67,), nq=_nq)(_grouped_nearest)
+case("eqm_adjust_260", ["xh_eqm_adjust"], cells=(260,), nq=20)(_eqm_adjust)
+case("plane_linear_260", ["xh_plane_linear"], cells=(260,), nq=10)(_plane_linear)
+case("grouped_nearest_260", ["xh_plane_nearest", "xh_eqm_adjust_g2d"], cells=(260,), nq=10)(_grouped_nearest)
+
+
+@case("apply_factor", ["xh_apply_factor"])
+@case("apply_factor_one_step", ["xh_apply_factor"], T=1)
+def _apply_factor(rng, C, T=400):
+    base, fac = _temp(rng, T, C), rng.normal(1, 0.1, (T, C)).astype(np.float32)
+
+    def run(dev):
+        k, b, f = K(), dev.to_device(base), dev.to_device(fac)
+        inplace = dev.to_device(base)
+        k.apply_factor(dev, inplace, f, "*", out=inplace)
+        return [k.apply_factor(dev, b, f, "+").get(), k.apply_factor(dev, b, f, "*").get(), inplace.get()]
+
+    return run, lambda: [(base + fac, EXACT), (base * fac, EXACT), (base * fac, EXACT)]
+
+
+@case("detrend", ["xh_poly_trend", "xh_trend_apply", "xh_poly_trend_u", "xh_trend_apply_u", "xh_window_nanmean"])
+def _detrend(rng, C):
+    T = 400
+    x = _temp(rng, T, C)
+    u = np.sort(rng.uniform(-200, 200, T))
+
+    def run(dev):
+        k, d, du = K(), dev.to_device(x), dev.to_device(u)
+        p0, p1 = k.poly_trend(dev, d, 1)
+        q0, q1 = k.poly_trend(dev, d, 1, u=du)
+        return [p0.get(), p1.get(), k.trend_apply(dev, d, p0, p1, "-").get(), q0.get(), q1.get(), k.trend_apply(dev, d, q0, q1, "/", u=du).get(),
+                k.window_nanmean(dev, d, 31).get()]
+
+    def oracle():
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            tc = np.arange(T) - (T - 1) / 2
+            p0, p1 = _fit(x, tc)
+            q0, q1 = _fit(x, u)
+            return [(p0, dict(rtol=1e-9, atol=1e-9)), (p1, dict(rtol=1e-7, atol=1e-9)),
+                    ((x - (p0 + p1 * tc[:, None])).astype(np.float32), dict(rtol=1e-6, atol=1e-5)),
+                    (q0, dict(rtol=1e-9, atol=1e-9)), (q1, dict(rtol=1e-7, atol=1e-9)),
+                    ((x / (q0 + q1 * u[:, None])).astype(np.float32), R6), (osdba.window_nanmean(x, 31), dict(rtol=3e-7, atol=1e-7))]
+
+    return run, oracle
+
+
+def _fit(x, u):
+    """Least-squares line through the valid samples of every column, as p0 + p1 u (float64)."""
+    p0, p1 = np.full(x.shape[1], np.nan), np.full(x.shape[1], np.nan)
+    for c in range(x.shape[1]):
+        ok = ~np.isnan(x[:, c])
+        if ok.sum() >= 2:
+            p1[c], p0[c] = np.polyfit(u[ok], x[ok, c].astype(np.float64), 1)
+    return p0, p1
+
+
+def _sdba_fields(rng, T, C, kind):
+    t = np.arange(T)[:, None]
+    seas = 8 * np.sin(2 * np.pi * (t - 100) / 365)
+    base = 0.0 if kind == "+" else 25.0
+    ref = (base + 10 + seas + rng.normal(0, 3, (T, C))).astype(np.float32)
+    hist = (base + 11.5 + 1.2 * seas + rng.normal(0, 4, (T, C))).astype(np.float32)
+    sim = (base + 12 + 1.2 * seas + 3.0 * t / T + rng.normal(0, 4, (T, C))).astype(np.float32)
+    sim[rng.random((T, C)) < 0.02] = np.nan
+    hist[:50, 0] = np.nan
+    return ref, hist, sim
+
+
+@case("eqm_doy_groups", ["xh_eqm_train_groups"], cells=(67,), window=1)
+@case("eqm_doy_window", ["xh_eqm_train_window"], cells=(67,), window=31)
+def _eqm_grouped(rng, C, window):
+    from xclim_amd import sdba as xsdba
+
+    T = 365 * 3
+    ta, ot = _axes(T, "2001-01-01", "noleap")
+    ref, hist, sim = _sdba_fields(rng, T, C, "+")
+
+    def run(dev):
+        eqm = xsdba.EmpiricalQuantileMapping.train(ref, hist, nquantiles=15, kind="+", group="time.dayofyear", window=window, time=ta, device=dev)
+        return [np.asarray(eqm.af), np.asarray(eqm.hist_q)]
+
+    def oracle():
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            oaf, ohq, _ = osdba.eqm_train_grouped(ref, hist, ot, "dayofyear", window, 15, "+")
+        return [(oaf, dict(rtol=1e-6, atol=1e-5)), (ohq, R6)]
+
+    return run, oracle
+
+
+@case("dqm_month", ["xh_poly_trend_groups", "xh_trend_apply_groups"], cells=(67,), group="time.month", window=1)
+@case("dqm_doy_groups", ["xh_dqm_train_groups"], cells=(67,), group="time.dayofyear", window=1)
+@case("dqm_doy_window", ["xh_dqm_train_window"], cells=(67,), group="time.dayofyear", window=31)
+def _dqm_grouped(rng, C, group, window):
+    from xclim_amd import sdba as xsdba
+
+    T = 365 * 3
+    ta, ot = _axes(T, "2001-01-01", "noleap")
+    ref, hist, sim = _sdba_fields(rng, T, C, "+")
+    prop = group.split(".")[1]
+
+    def run(dev):
+        dqm = xsdba.DetrendedQuantileMapping.train(ref, hist, nquantiles=15, kind="+", group=group, window=window, time=ta, device=dev)
+        out = [np.asarray(dqm.af), np.asarray(dqm.hist_q), np.asarray(dqm.scaling)]
+        if prop == "month":
+            out.append(dqm.adjust(sim, detrend=1, time=ta, grouped_nearest="group"))
+        return out
+
+    def oracle():
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            labels, eaf, ehq, escal = osdba.dqm_train_grouped(ref, hist, ot, prop, 15, "+", window=window)
+            exp = [(eaf, dict(rtol=1e-5, atol=1e-5)), (ehq, dict(rtol=1e-5, atol=2e-6)), (escal, R6)]
+            if prop == "month":
+                exp.append((osdba.dqm_adjust_grouped(sim, ot, prop, labels, eaf, ehq, escal, "+", "constant", 1, mode="group"),
+                            dict(rtol=2e-5, atol=2e-5)))
+        return exp
+
+    return run, oracle
+
+
+@case("qdm_doy_groups", ["xh_qdm_adjust_groups"], cells=(67,))
+def _qdm_grouped(rng, C):
+    from xclim_amd import sdba as xsdba
+
+    T = 365 * 3
+    ta, ot = _axes(T, "2001-01-01", "noleap")
+    ref, hist, sim = _sdba_fields(rng, T, C, "+")
+
+    def run(dev):
+        qdm = xsdba.QuantileDeltaMapping.train(ref, hist, nquantiles=15, kind="+", group="time.dayofyear", time=ta, device=dev)
+        self_af, self_q = np.asarray(qdm.af), np.asarray(qdm.quantiles)
+        run.nodes = (self_af, self_q, qdm.group_labels)
+        return [qdm.adjust(sim, time=ta)]
+
+    def oracle():
+        af, q, labels = run.nodes
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            return [(osdba.qdm_adjust_grouped(sim, ot, "dayofyear", labels, af, q, "+", "nearest", "constant", mode="group"), R6)]
+
+    return run, oracle
+
+
+# ------------------------------------------------------------------------------------ synthetic fields, transposes
+@case("fill_synthetic", ["xh_fill_synthetic"])
+def _fill_synthetic(rng, C):
+    import ctypes
+
+    T = 200
+    base = osynth.seasonal_base(T)
+
+    def run(dev):
+        out = dev.empty((T, C), np.float32)
+        db = dev.to_device(np.asarray(base, np.float32))
+        dev.call("xh_fill_synthetic", ctypes.c_void_p(out.ptr), T, C, C, 0, 42, 5000, ctypes.c_void_p(db.ptr), 3.0, 0.3, 1000)
+        dev.sync()
+        return [out.get()]
+
+    return run, lambda: [(osynth.fill_synthetic(T, np.arange(5000, 5000 + C), 0, 42, base, 3.0, 0.3, 1000), EXACT)]
+
+
+@case("transpose", ["xh_transpose_f32"])
+def _transpose(rng, C):
+    import ctypes
+
+    R = 131
+    x = rng.normal(size=(R, C)).astype(np.float32)
+
+    def run(dev):
+        d, out = dev.to_device(x), dev.empty((C, R), np.float32)
+        dev.call("xh_transpose_f32", ctypes.c_void_p(d.ptr), R, C, C, ctypes.c_void_p(out.ptr), R)
+        dev.sync()
+        return [out.get()]
+
+    return run, lambda: [(np.ascontiguousarray(x.T), EXACT)]
+
+
+# ---------------------------------------------------------------------- fire weather, fire danger, evapotranspiration
+@case("fire_weather", ["xh_fire_weather"])
+@case("fire_weather_one_step", ["xh_fire_weather"], T=1)
+@case("fire_weather_season_mask", ["xh_fire_weather"], masked=True)
+@case("fire_weather_snow_season", ["xh_fire_weather"], snow=True)
+def _fire_weather(rng, C, T=400, masked=False, snow=False):
+    import firecpu
+    from test_fire_cpu import check_outputs
+    from test_gpu_fire import _weather
+    from xclim_amd import fire
+
+    inp = _weather(rng, T, C, nan_frac=0.002)   # (a NaN day poisons the rest of its cell's recurrence: a sparser sprinkle here)
+    for a in inp[:4]:
+        a[:, 0] = np.nan
+    time = TimeAxis.daily("2001-03-01", T, "noleap")
+    lat = rng.uniform(-90, 90, C)
+    kw = dict(season_method="WF93", overwintering=True, dry_start="CFS", indexes=list(firecpu.INDEXES))
+    if snow:     # GFWED reads the snow depth
+        kw = dict(season_method="GFWED", temp_condition_days=2, snow_condition_days=4, indexes=list(firecpu.INDEXES))
+    dkw = kw
+    if masked:   # the caller's own season mask: a strided uint8 field (st_mask)
+        mask = np.repeat(rng.random((T // 20, C)) < 0.7, 20, axis=0)
+        kw = dict(season_method="mask", season_mask=mask, indexes=list(firecpu.INDEXES))
+        dkw = dict(season_mask=mask, indexes=list(firecpu.INDEXES))
+
+    def run(dev):
+        got = fire.fire_weather_ufunc(tas=inp[0], pr=inp[1], hurs=inp[2], sfcWind=inp[3], snd=inp[4] if snow else None, lat=lat, time=time,
+                                      device=dev, **dkw)
+        run.keys = sorted(got)
+        return [np.asarray(got[k]) for k in run.keys]
+
+    def oracle():
+        exp = firecpu.fire_weather(*inp, time.month, lat, **kw)
+        return [(exp[k], lambda g, e, k=k: check_outputs({k: g}, {k: e})) for k in run.keys]
+
+    return run, oracle
+
+
+@case("mcarthur", ["xh_mcarthur"])
+def _mcarthur(rng, C, dtype=np.float32):
+    import ffdicpu
+    from test_ffdi_cpu import check
+    from xclim_amd import ffdi
+
+    T = 120
+    pr = np.where(rng.random((T, C)) < 0.3, rng.gamma(0.7, 9.0, (T, C)), 0.0).astype(dtype)
+    tas = (24 + rng.normal(0, 6, (T, C))).astype(dtype)
+    hurs = np.clip(rng.normal(45, 20, (T, C)), 2, 100).astype(dtype)
+    wind = np.abs(rng.normal(18, 8, (T, C))).astype(dtype)
+    for a in (pr, tas, hurs, wind):   # (KBDI and DF are recurrences: a sparser NaN sprinkle than elsewhere, one all-NaN cell)
+        a[rng.random((T, C)) < 0.002] = np.nan
+        a[:, 0] = np.nan
+    pa, k0 = rng.uniform(200, 1600, C), rng.uniform(0, 210, C)
+    smd = rng.uniform(0, 200, (T, C)).astype(dtype)      # the stages on their own read the soil moisture deficit / the drought
+    dfac = rng.uniform(0, 10, (T, C)).astype(dtype)      # factor as strided fields too
+    smd[rng.random((T, C)) < 0.02] = np.nan
+    dfac[rng.random((T, C)) < 0.02] = np.nan
+
+    def run(dev):
+        ch = ffdi.mcarthur_indices(pr, tas, hurs, wind, pa, k0, "xlim", device=dev)
+        return [ch.KBDI, ch.DF, ch.FFDI, ffdi.griffiths_drought_factor(pr, smd, "xlim", device=dev),
+                np.asarray(ffdi.mcarthur_forest_fire_danger_index(dfac, tas, hurs, wind, device=dev), np.float64)]
+
+    def oracle():
+        k, d, f = ffdicpu.chain(pr, tas, hurs, wind, pa, k0, 0)
+        return [(k, lambda g, e: check("kbdi", g, e)), (d, lambda g, e: check("df", g, e)),
+                (f, lambda g, e: check("ffdi", g, e, dtype == np.float64)),
+                (ffdicpu.drought_factor(pr, smd, 0), lambda g, e: check("df", g, e)),
+                (ffdicpu.ffdi(dfac, tas, hurs, wind), lambda g, e: check("ffdi", g, e, dtype == np.float64))]
+
+    return run, oracle
+
+
+case("mcarthur_f64", ["xh_mcarthur"], dtype=np.float64)(_mcarthur)
+
+
+def _pet(rng, C, method, T, dtype=np.float32, water=False):
+    import petcpu
+    from xclim_amd import converters as xc
+
+    t = TimeAxis.daily("2000-02-17", T)
+    lat = np.linspace(-85, 85, C)
+    base = 295 - 0.4 * np.abs(lat) + 10 * np.cos(2 * np.pi * np.arange(T) / 365.0)[:, None] * np.sign(lat) + rng.normal(0, 3, (T, C))
+    spread = rng.uniform(2, 14, (T, C))
+    f = {"tasmin": base - spread / 2, "tasmax": base + spread / 2, "tas": base + rng.normal(0, 0.5, (T, C)),
+         "hurs": rng.uniform(5, 100, (T, C)), "rsds": rng.uniform(0, 350, (T, C)), "rlds": rng.uniform(230, 380, (T, C)),
+         "sfcWind": rng.uniform(0, 12, (T, C)), "pr": np.where(rng.random((T, C)) < 0.4, rng.gamma(0.7, 8, (T, C)), 0) / 86400}
+    f["rsus"] = 0.2 * f["rsds"]
+    f["rlus"] = f["rlds"] + rng.uniform(10, 80, (T, C))
+    for k in f:
+        f[k][rng.random((T, C)) < 0.02] = np.nan
+    f = {k: v.astype(dtype) for k, v in f.items()}
+    monthly = method in ("TW48", "DA02")
+    use_tas = method in ("HG85", "MB05", "TW48")
+    fld = {k: v for k, v in f.items() if (k != "tas" or use_tas) and (k != "pr" or water or method == "DA02")}
+
+    def run(dev):
+        if water:
+            pr = fld["pr"]
+            got = xc.water_budget(pr, **{k: v for k, v in fld.items() if k != "pr"}, lat=lat, time=t, method=method, time_of_day=12.0, device=dev)
+        else:
+            got = xc.potential_evapotranspiration(**fld, lat=lat, time=t, method=method, time_of_day=12.0, device=dev)
+        return [got[0] if monthly else got]
+
+    def oracle():
+        if monthly:
+            exp = petcpu.pet_monthly(method, t, lat, **{k: fld.get(k) for k in ("tasmin", "tasmax", "tas", "pr")})[1 if water else 0]
+        else:
+            exp = petcpu.pet_daily(method, t, lat, **{k: v for k, v in fld.items() if k != "pr"}, time_of_day=12.0)[0]
+            if water:
+                exp = fld["pr"].astype(np.float64) - exp
+        scale = 1e-12 * np.nanmax(np.abs(exp))
+
+        def bar(g, e):
+            assert np.array_equal(np.isnan(g), np.isnan(e))
+            np.testing.assert_allclose(g, e, rtol=1e-10 if method == "TW48" else 1e-12, atol=scale)
+
+        return [(exp, bar)]
+
+    return run, oracle
+
+
+for _m in ("BR65", "HG85", "MB05", "FAO_PM98"):
+    case(f"pet_daily_{_m}", ["xh_pet_daily"], method=_m, T=400)(_pet)
+case("pet_daily_f64_water_budget", ["xh_pet_daily"], method="FAO_PM98", T=400, dtype=np.float64, water=True)(_pet)
+case("pet_daily_one_step", ["xh_pet_daily"], cells=(67,), method="BR65", T=1)(_pet)
+# the row loop of k_pet_daily strides by gridDim.y = min(T, 4096): more rows than that, few cells
+case("pet_daily_4100_rows", ["xh_pet_daily"], cells=(5,), method="HG85", T=4100)(_pet)
+for _m in ("TW48", "DA02"):
+    case(f"pet_monthly_{_m}", ["xh_pet_monthly"], method=_m, T=800)(_pet)
+case("pet_monthly_f64", ["xh_pet_monthly"], cells=(67,), method="TW48", T=800, dtype=np.float64)(_pet)
+case("pet_monthly_water_budget", ["xh_pet_monthly"], cells=(67,), method="TW48", T=800, water=True)(_pet)
+
+
+# ------------------------------------------------------------------------------------------ standardized indices
+def _si(rng, C, staging, dtype=np.float32):
+    import spicpu
+    from test_gpu_stdidx import assert_si_close
+
+    T, G = 36, 12   # 3 years of monthly values in MS groups: 3 values per group
+    x = rng.gamma(2.0, 30.0, (T, C)).astype(dtype)
+    x[rng.random((T, C)) < 0.02] = np.nan
+    x[:, 0] = np.nan
+    x[:, 1] = np.where(np.arange(T) % 3 == 0, 40.0, 55.0)   # ties
+    group = (np.arange(T) % G).astype(np.int32)
+
+    def run(dev):
+        d = dev.to_device(x)
+        params, _, _, _ = K().si_fit(dev, d, group, G, "gamma", "APP", floc=0.0, staging=staging)
+        return [params.get(), K().si_apply(dev, d, group, params, "gamma").get()]
+
+    def oracle():
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            with np.errstate(all="ignore"):
+                params = spicpu.fit(x, group, G, "gamma", "APP", False, 0.0)
+                params = params[0] if isinstance(params, tuple) else params
+                si = spicpu.index(x, group, params, "gamma")
+        return [(params, dict(rtol=1e-9, atol=0)), (si, assert_si_close)]
+
+    return run, oracle
+
+
+for _st in ("global", "lds"):
+    case(f"si_{_st}", ["xh_si_fit", "xh_si_apply"], staging=_st)(_si)
+    case(f"si_f64_{_st}", ["xh_si_fit_f64", "xh_si_apply_f64"], f64=True, staging=_st, dtype=np.float64)(_si)
+
+
+# ------------------------------------------------------------------------------------------------- float64 twins
+@case("f64_counts", ["xh_threshold_count_f64", "xh_domain_count_f64", "xh_bivariate_count_f64"], f64=True)
+def _f64_counts(rng, C):
+    x, y = _temp(rng, STEPS, C, np.float64), _temp(rng, STEPS, C).astype(np.float32)
+    ta, ot = _axes()
+    seg, _ = ta.segments("MS")
+    table = _doy_table(rng, C, np.float64)
+    tidx = (ta.doy - 1).astype(np.int32)
+
+    def run(dev):
+        k, d = K(), dev.to_device(x)
+        return _gets(*k.threshold_count(dev, d, ">", seg, doy_table=dev.to_device(table), tidx=tidx)) + \
+            [k.threshold_count(dev, d, ">=", seg, scalar=290.0)[0].get(), k.domain_count(dev, d, ">", 285.0, "<=", 295.0, "and", seg)[0].get(),
+             k.bivariate_count(dev, d, dev.to_device(y), ">", 288.1, "<", 296.0, "all", seg)[0].get()]
+
+    def oracle():
+        with np.errstate(invalid="ignore"):
+            biv = (x > 288.1) & (y < np.float32(296.0))
+            dom = (x > 285.0) & (x <= 295.0)
+            return [(ogen.threshold_count(x, ">", table[tidx], ot, "MS"), EXACT), (ogen.select_resample_op(x, "count", ot, "MS"), EXACT),
+                    (ogen.count_occurrences(x, 290.0, ">=", ot, "MS"), EXACT), (_per(dom, seg, lambda g: g.sum(0)).astype(np.int32), EXACT),
+                    (_per(biv, seg, lambda g: g.sum(0)).astype(np.int32), EXACT)]
+
+    return run, oracle
+
+
+@case("f64_reductions", ["xh_resample_reduce_f64", "xh_thresholded_reduce_f64", "xh_range_reduce_f64", "xh_rolling_reduce_f64"], f64=True)
+def _f64_reductions(rng, C):
+    x = _temp(rng, STEPS, C, np.float64)
+    hi = (x + np.abs(rng.normal(6, 2, x.shape))).astype(np.float32)
+    ta, ot = _axes()
+    seg, _ = ta.segments("MS")
+
+    def run(dev):
+        k, d = K(), dev.to_device(x)
+        return [k.resample_reduce(dev, d, "mean", seg)[0].get(), k.resample_reduce(dev, d, "sum", seg)[0].get(),
+                k.thresholded_reduce(dev, d, ">", 289.0, 2, "sum", seg)[0].get(),
+                k.range_reduce(dev, d, dev.to_device(hi), "range", "mean", seg)[0].get(), k.rolling_reduce(dev, d, 5, "mean", True).get()]
+
+    def oracle():
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            return [(ogen.select_resample_op(x, "mean", ot, "MS"), dict(rtol=1e-12, atol=0)), (ogen.select_resample_op(x, "sum", ot, "MS"), dict(rtol=1e-12, atol=0)),
+                    (ogen.cumulative_difference(x, 289.0, ">", ot, "MS"), dict(rtol=1e-12, atol=1e-9)),
+                    (ogen.diurnal_temperature_range(x, hi.astype(np.float64), "mean", ot, "MS"), dict(rtol=1e-12, atol=0)),
+                    (ogen.rolling(x, 5, "mean", True), dict(rtol=1e-12, atol=0))]
+
+    return run, oracle
+
+
+@case("f64_runs", ["xh_compare_map_f64", "xh_run_stats_f64", "xh_spell_mask_f64", "xh_spell_run_stats_f64", "xh_run_stats_doy_f64"], f64=True)
+def _f64_runs(rng, C):
+    x, b = _temp(rng, STEPS, C, np.float64), _temp(rng, STEPS, C).astype(np.float32)
+    ta, ot = _axes()
+    seg, _ = ta.segments("MS")
+    table = _doy_table(rng, C, np.float64)
+    tidx = (ta.doy - 1).astype(np.int32)
+
+    def run(dev):
+        k, d = K(), dev.to_device(x)
+        return [k.compare_map(dev, d, ">", 289.05, "mask").get(), k.compare_map(dev, d, "<", dev.to_device(b), "events").get(),
+                k.run_stats(dev, d, "max", 1, seg, cut=True, fused_op=">", thresh=289.05)[0].get(),
+                k.spell_mask(dev, d, 3, "mean", ">", 289.05).get(), k.spell_run_stats(dev, d, 3, "mean", ">", 289.05, "max", seg)[0].get(),
+                k.run_stats_doy(dev, d, ">", dev.to_device(table), tidx, "max", 3, seg)[0].get()]
+
+    def oracle():
+        with np.errstate(invalid="ignore"):
+            c, cb, cd = x > 289.05, x < b.astype(np.float64), x > table[tidx]
+        return [(c.astype(np.uint8), EXACT), (np.where(np.isnan(x), np.nan, cb).astype(np.float32), EXACT),
+                (ogen.spell_length_statistics(x, 289.05, 1, None, ">", "max", ot, "MS", resample_before_rl=True), EXACT),
+                (ogen.spell_mask(x, 3, "mean", ">", 289.05).astype(np.float32), EXACT),
+                (ogen.spell_length_statistics(x, 289.05, 3, "mean", ">", "max", ot, "MS", resample_before_rl=True), EXACT),
+                (_per(cd, seg, lambda g: orl.rle_statistics(g, "max", 3)), EXACT)]
+
+    return run, oracle
+
+
+@case("f64_percentile_doy_1y", ["xh_percentile_doy_f64"], cells=(67,), f64=True, nyears=1)
+@case("f64_percentile_doy_3y", ["xh_percentile_doy_f64"], cells=(67,), f64=True, nyears=3)
+def _f64_percentile_doy(rng, C, nyears):
+    T = 365 * nyears
+    ta, ot = _axes(T, "1981-01-01", "noleap")
+    x = _temp(rng, T, C, np.float64)
+    tb, years, doys = ta.doy_table()
+    per = [10.0, 50.0, 90.0]
+
+    def run(dev):
+        return [K().percentile_doy(dev, dev.to_device(x), tb, 5, per).get()]
+
+    def oracle():
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")
+            return [(np.moveaxis(ocal.percentile_doy(x, ot, 5, per)[0], -1, 0), dict(rtol=1e-12, atol=0))]
+
+    return run, oracle
+
+
+# ================================================================================================== the tests
+_BUILT = {}
+
+
+def _built(dev, rng, name, C):
+    """(run, plain results) of a case, computed once per (case, cells) and never modified."""
+    key = (name, C)
+    if key not in _BUILT:
+        run, oracle = CASES[name].build(rng, C)
+        plain = run(dev)
+        for a in plain:
+            a.setflags(write=False)
+        _BUILT[key] = (run, oracle, plain)
+    return _BUILT[key]
+
+
+def _same_bits(a, b):
+    if a.dtype != b.dtype or a.shape != b.shape:
+        return False
+    if a.dtype.kind == "f":
+        return bool(((a.view(f"u{a.itemsize}") == b.view(f"u{b.itemsize}")) | (np.isnan(a) & np.isnan(b))).all())
+    return bool((a == b).all())
+
+
+def _native(monkeypatch, c):
+    if c.f64:
+        monkeypatch.setenv("XCLIM_AMD_FLOAT64", "native")
+
+
+_PLAIN = [(c.name, C) for c in CASES.values() for C in c.cells]
+_PADDED = [(c.name, C, pads, shift) for c in CASES.values() for C, pads, shift in LAYOUTS if C in c.cells]
+_PADDED += [(c.name, C, (1, 3, 5), 0) for c in CASES.values() for C in c.cells if C not in (67, 260)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,C", _PLAIN, ids=[f"{n}-{C}" for n, C in _PLAIN])
+def test_plain_result_meets_the_oracle(dev, rng, monkeypatch, name, C):
+    _native(monkeypatch, CASES[name])
+    run, oracle, plain = _built(dev, rng, name, C)
+    expected = oracle()
+    assert len(plain) == len(expected)
+    for i, (got, (exp, bar)) in enumerate(zip(plain, expected)):
+        exp = np.asarray(exp)
+        assert got.shape == exp.shape, (i, got.shape, exp.shape)
+        if bar is None:
+            np.testing.assert_array_equal(got, exp, err_msg=f"output {i}")
+        elif callable(bar):
+            bar(got, exp)
+        else:
+            np.testing.assert_allclose(got, exp, equal_nan=True, err_msg=f"output {i}", **bar)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name,C,pads,shift", _PADDED, ids=[f"{n}-{C}-pads{'_'.join(map(str, p))}-shift{s}" for n, C, p, s in _PADDED])
+def test_padded_views_give_the_same_bits(dev, rng, monkeypatch, name, C, pads, shift):
+    c = CASES[name]
+    _native(monkeypatch, c)
+    run, _, plain = _built(dev, rng, name, C)
+    with S.padded(dev, monkeypatch, pads=pads, shift=shift) as log:
+        got = run(dev)
+    assert len(got) == len(plain)
+    for i, (g, p) in enumerate(zip(got, plain)):
+        assert _same_bits(g, p), f"output {i}: {int((~np.isclose(g, p, rtol=0, atol=0, equal_nan=True)).sum())} of {g.size} elements differ under strides {log}"
+    for entry in c.reaches:
+        strided = [used for n, used in log if n == entry and any(s != w for s, w in used.values())]
+        assert strided, f"{entry} was not reached with a padded operand: {[n for n, _ in log]}"
+
+
+def _expected_probes(entry):
+    """What the refusal test must have tried for an entry point: every stride parameter of its table operands, the cell
+    stride of the time-minor form where it has one, and a cell stride of 2 where the prototype has `sc`."""
+    ops = S.TABLE[entry]
+    want = {op.stride for op in ops} | {op.minor + " (time-minor)" for op in ops if op.minor}
+    if "sc" in S.PROTOS[entry] and "C" in S.PROTOS[entry]:
+        want.add("sc = 2")
+    return want
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("entry", sorted(S.TABLE))
+def test_a_stride_below_the_width_is_refused(dev, rng, monkeypatch, entry):
+    """Every stride argument in turn one short of its operand's width (C - 1; sc = T - 1 with st = 1 for the time-minor forms
+    of the column entry points), and a cell stride of 2 on a time-major call: XH_ERR_LAYOUT, on the dense allocations of a
+    valid call (cells halved for the cell stride of 2, so that an entry point without the check would still stay inside
+    them).  Every case that reaches the entry point is probed, and together they must have handed in every operand of the
+    table and shortened every stride parameter."""
+    from xclim_amd._capi import XH_ERR_LAYOUT
+
+    cases = [c for c in CASES.values() if entry in c.reaches]
+    assert cases, f"no case reaches {entry}"
+    names = S.PROTOS[entry][1:]
+    real, tried, operands = dev.call, [], set()
+
+    def refused(args, what, **change):
+        bad = list(args)
+        for param, value in change.items():
+            bad[names.index(param)] = value
+        tried.append((what, change, getattr(dev.lib, entry)(dev.ctx, *bad)))
+
+    def probe(name, *args):
+        if name == entry:
+            env = S.arguments(name, args)
+            short = {}
+            for op in S.TABLE[name]:
+                if env[op.ptr]:
+                    operands.add(op.ptr)
+                    param, rows, width, _ = S.layout(op, env, dev)
+                    if width >= 2 and rows >= 1:
+                        short[param + (" (time-minor)" if param == op.minor else "")] = (param, width - 1)
+            done = {w for w, _, _ in tried}
+            for what, (param, value) in short.items():
+                if what not in done:
+                    refused(args, what, **{param: value})
+            if "sc" in names and "C" in names and env["sc"] == 1 and env["C"] >= 2 and "sc = 2" not in done:
+                refused(args, "sc = 2", sc=2, C=env["C"] // 2)
+        return real(name, *args)
+
+    for c in cases:
+        with monkeypatch.context() as m:
+            _native(m, c)
+            run, _ = c.build(rng, c.cells[0])
+            m.setattr(dev, "call", probe, raising=False)
+            run(dev)
+    wrong = [t for t in tried if t[2] != XH_ERR_LAYOUT]
+    assert not wrong, f"{entry}: (probe, arguments changed, return code) {wrong}, expected {XH_ERR_LAYOUT}"
+    assert {w for w, _, _ in tried} == _expected_probes(entry), (sorted(w for w, _, _ in tried), sorted(_expected_probes(entry)))
+    assert operands == {op.ptr for op in S.TABLE[entry]}, f"{entry}: operands never handed in: {sorted({op.ptr for op in S.TABLE[entry]} - operands)}"

@@ -446,7 +446,8 @@ extern "C" {
 int xh_fill_synthetic(xh_ctx* ctx, float* out, int64_t T, int64_t C, int64_t st, int kind, uint64_t seed, int64_t cell0,
                       const float* base, float amp, float p_wet, uint32_t nan_per_million) {
   XH_REQUIRE(ctx && out && base, XH_ERR_ARG, "xh_fill_synthetic: NULL argument");
-  XH_REQUIRE(T >= 0 && C >= 0 && st >= C, XH_ERR_ARG, "xh_fill_synthetic: bad shape");
+  XH_REQUIRE(T >= 0 && C >= 0, XH_ERR_ARG, "xh_fill_synthetic: bad shape");
+  XH_REQUIRE(st >= C, XH_ERR_LAYOUT, "xh_fill_synthetic: needs time-major rows of at least the row width (st)");
   XH_REQUIRE(kind == 0 || kind == 1, XH_ERR_ARG, "xh_fill_synthetic: kind must be 0 or 1");
   if (T == 0 || C == 0) return XH_OK;
   dim3 grid((unsigned)cdiv64(C, XH_BLOCK), (unsigned)(T < 64 ? T : 64));
@@ -459,8 +460,9 @@ int xh_fill_synthetic(xh_ctx* ctx, float* out, int64_t T, int64_t C, int64_t st,
 int xh_transpose_f32(xh_ctx* ctx, const float* in, int64_t rows, int64_t cols, int64_t in_stride, float* out,
                      int64_t out_stride) {
   XH_REQUIRE(ctx && in && out, XH_ERR_ARG, "xh_transpose_f32: NULL argument");
-  XH_REQUIRE(rows >= 0 && cols >= 0 && in_stride >= cols && out_stride >= rows, XH_ERR_ARG,
-             "xh_transpose_f32: bad shape/strides");
+  XH_REQUIRE(rows >= 0 && cols >= 0, XH_ERR_ARG, "xh_transpose_f32: bad shape");
+  XH_REQUIRE(in_stride >= cols && out_stride >= rows, XH_ERR_LAYOUT,
+             "xh_transpose_f32: row strides below the row widths (in_stride >= cols, out_stride >= rows)");
   if (rows == 0 || cols == 0) return XH_OK;
   const bool al16 = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) == 0 && in_stride % 4 == 0 &&
                     out_stride % 4 == 0 && cols >= 4;

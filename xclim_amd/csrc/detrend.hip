@@ -324,7 +324,8 @@ int xh_window_nanmean(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t
 int xh_poly_trend_groups(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, const int32_t* rows, const int64_t* offs, int G,
                          const double* u, int degree, double* p0, double* p1) {
   XH_REQUIRE(ctx && x && rows && offs && u && p0, XH_ERR_ARG, "xh_poly_trend_groups: NULL argument");
-  XH_REQUIRE(T >= 1 && C >= 0 && G >= 1 && st >= C, XH_ERR_ARG, "xh_poly_trend_groups: bad shape");
+  XH_REQUIRE(T >= 1 && C >= 0 && G >= 1, XH_ERR_ARG, "xh_poly_trend_groups: bad shape");
+  XH_REQUIRE(st >= C, XH_ERR_LAYOUT, "xh_poly_trend_groups: needs time-major rows of at least the row width (st)");
   XH_REQUIRE(degree == 0 || degree == 1, XH_ERR_NOTIMPL, "xh_poly_trend_groups: degree must be 0 or 1");
   XH_REQUIRE(degree == 0 || p1, XH_ERR_ARG, "xh_poly_trend_groups: p1 is NULL");
   XH_REQUIRE(offs[0] == 0, XH_ERR_ARG, "xh_poly_trend_groups: offs[0] must be 0");
@@ -356,7 +357,8 @@ int xh_poly_trend_groups(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int6
 int xh_trend_apply_groups(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, const int32_t* rows, const int64_t* offs, int G,
                           const double* u, const double* p0, const double* p1, int mode, float* out, int64_t out_st) {
   XH_REQUIRE(ctx && x && rows && offs && p0 && out, XH_ERR_ARG, "xh_trend_apply_groups: NULL argument");
-  XH_REQUIRE(T >= 1 && C >= 0 && G >= 1 && st >= C && out_st >= C, XH_ERR_ARG, "xh_trend_apply_groups: bad shape");
+  XH_REQUIRE(T >= 1 && C >= 0 && G >= 1, XH_ERR_ARG, "xh_trend_apply_groups: bad shape");
+  XH_REQUIRE(st >= C && out_st >= C, XH_ERR_LAYOUT, "xh_trend_apply_groups: needs time-major rows of at least the row width (st, out_st)");
   XH_REQUIRE(mode >= 0 && mode <= 3, XH_ERR_ARG, "xh_trend_apply_groups: mode must be 0 (+), 1 (-), 2 (*) or 3 (/)");
   XH_REQUIRE(u || !p1, XH_ERR_ARG, "xh_trend_apply_groups: a slope table needs the rows' coordinate");
   XH_REQUIRE(offs[0] == 0, XH_ERR_ARG, "xh_trend_apply_groups: offs[0] must be 0");

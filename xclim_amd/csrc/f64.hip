@@ -273,7 +273,8 @@ int xh_threshold_count_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, i
   XH_REQUIRE(thr_kind == XH_THR_SCALAR_F64 || thr_kind == XH_THR_DOY_F64 || thr_kind == XH_THR_FULL_F64, XH_ERR_ARG,
              "xh_threshold_count_f64: thr_kind must be XH_THR_SCALAR_F64, XH_THR_DOY_F64 or XH_THR_FULL_F64 (got %d)", thr_kind);
   if (thr_kind != XH_THR_SCALAR_F64) {
-    XH_REQUIRE(thr_table && thr_stride >= C, XH_ERR_ARG, "xh_threshold_count_f64: threshold table missing or stride < C");
+    XH_REQUIRE(thr_table, XH_ERR_ARG, "xh_threshold_count_f64: threshold table missing");
+    XH_REQUIRE(thr_stride >= C, XH_ERR_LAYOUT, "xh_threshold_count_f64: needs time-major rows of at least the row width (thr_stride)");
     if (thr_kind == XH_THR_DOY_F64) XH_REQUIRE(tidx, XH_ERR_ARG, "xh_threshold_count_f64: tidx required for per-doy thresholds");
   }
   size_t cur = 0;

@@ -503,7 +503,8 @@ int xh_rolling_reduce_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, in
                           int reducer, double* out, int64_t out_st) {
   int rc = check_field("xh_rolling_reduce_f64", ctx, x, T, C, st, sc);
   if (rc) return rc;
-  XH_REQUIRE(out && out_st >= C, XH_ERR_ARG, "xh_rolling_reduce_f64: out NULL or out_st < C");
+  XH_REQUIRE(out, XH_ERR_ARG, "xh_rolling_reduce_f64: out NULL");
+  XH_REQUIRE(out_st >= C, XH_ERR_LAYOUT, "xh_rolling_reduce_f64: needs time-major rows of at least the row width (out_st)");
   XH_REQUIRE(window >= 1, XH_ERR_ARG, "xh_rolling_reduce_f64: window must be >= 1");
   XH_REQUIRE(reducer >= XH_RED_SUM && reducer <= XH_RED_COUNT, XH_ERR_OP, "xh_rolling_reduce_f64: reducer %d not recognized", reducer);
   if (T == 0 || C == 0) return XH_OK;

@@ -598,7 +598,8 @@ int xh_spell_mask_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int64_
                       int op, double thr, const double* weights, float* out, int64_t out_st) {
   int rc = check_field("xh_spell_mask_f64", ctx, x, T, C, st, sc);
   if (rc) return rc;
-  XH_REQUIRE(out && out_st >= C, XH_ERR_ARG, "xh_spell_mask_f64: out NULL or out_st < C");
+  XH_REQUIRE(out, XH_ERR_ARG, "xh_spell_mask_f64: out NULL");
+  XH_REQUIRE(out_st >= C, XH_ERR_LAYOUT, "xh_spell_mask_f64: needs time-major rows of at least the row width (out_st)");
   XH_REQUIRE(window >= 1, XH_ERR_ARG, "xh_spell_mask_f64: window must be >= 1");
   XH_REQUIRE(op >= XH_OP_GT && op <= XH_OP_NE, XH_ERR_OP, "Operation `%d` not recognized.", op);
   if (weights || win_reducer == 4) {

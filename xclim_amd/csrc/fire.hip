@@ -415,8 +415,9 @@ int xh_fire_weather(xh_ctx* ctx, int64_t T, int64_t C, int64_t st, const float* 
   XH_REQUIRE((!need_tas || tas) && (!(dc || dmc || ffmc || dry_start) || pr) && (!(dmc || ffmc) || hurs) &&
                  (!(ffmc || isi) || sfcwind) && (!need_snd || snd) && (!(dc || dmc) || (month && lat)),
              XH_ERR_ARG, "xh_fire_weather: an input needed by the requested outputs is NULL");
-  XH_REQUIRE(season_method != XH_FIRE_SEASON_MASK || (season_mask && st_mask >= C), XH_ERR_ARG,
-             "xh_fire_weather: season mode 'mask' needs the mask (st_mask >= C)");
+  XH_REQUIRE(season_method != XH_FIRE_SEASON_MASK || season_mask, XH_ERR_ARG, "xh_fire_weather: season mode 'mask' needs the mask");
+  XH_REQUIRE(season_method != XH_FIRE_SEASON_MASK || st_mask >= C, XH_ERR_LAYOUT,
+             "xh_fire_weather: the season mask needs time-major rows (st_mask >= C)");
   XH_REQUIRE(!season_mask_out || season_method != XH_FIRE_SEASON_NONE, XH_ERR_ARG,
              "xh_fire_weather: no season mask without a season method");
   if (T == 0 || C == 0) {

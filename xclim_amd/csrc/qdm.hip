@@ -473,7 +473,8 @@ int xh_qdm_adjust_groups(xh_ctx* ctx, const float* sim, int64_t T, int64_t C, in
                          int G, const float* af, const double* q, int nq, int kind, int interp, int extrap, float* scen,
                          int64_t scen_st) {
   XH_REQUIRE(ctx && sim && rows && offs && af && q && scen, XH_ERR_ARG, "xh_qdm_adjust_groups: NULL argument");
-  XH_REQUIRE(T >= 1 && C >= 0 && G >= 1 && nq >= 1 && st >= C && scen_st >= C, XH_ERR_ARG, "xh_qdm_adjust_groups: bad shape");
+  XH_REQUIRE(T >= 1 && C >= 0 && G >= 1 && nq >= 1, XH_ERR_ARG, "xh_qdm_adjust_groups: bad shape");
+  XH_REQUIRE(st >= C && scen_st >= C, XH_ERR_LAYOUT, "xh_qdm_adjust_groups: needs time-major rows of at least the row width (st, scen_st)");
   XH_REQUIRE(kind >= 0 && kind <= 2, XH_ERR_ARG, "xh_qdm_adjust_groups: kind must be 0 (+), 1 (*) or 2 (the interpolated factor only)");
   XH_REQUIRE(interp == 0 || interp == 1, XH_ERR_NOTIMPL, "xh_qdm_adjust_groups: interp must be 0 (nearest) or 1 (linear)");
   XH_REQUIRE(extrap == 0 || extrap == 1, XH_ERR_ARG, "xh_qdm_adjust_groups: extrap must be 0 (constant) or 1 (nan)");

@@ -500,7 +500,8 @@ static int threshold_count_impl(xh_ctx* ctx, const float* x, int64_t T, int64_t 
   XH_REQUIRE(op >= XH_OP_GT && op <= XH_OP_NE, XH_ERR_OP, "Operation `%d` not recognized.", op);
   XH_REQUIRE(count_out, XH_ERR_ARG, "xh_threshold_count: count_out is NULL");
   if (thr_kind >= XH_THR_DOY_F64) {
-    XH_REQUIRE(thr_table && thr_stride >= C, XH_ERR_ARG, "xh_threshold_count: threshold table missing or stride < C");
+    XH_REQUIRE(thr_table, XH_ERR_ARG, "xh_threshold_count: threshold table missing");
+    XH_REQUIRE(thr_stride >= C, XH_ERR_LAYOUT, "xh_threshold_count: needs time-major rows of at least the row width (thr_stride)");
     if (thr_kind == XH_THR_DOY_F64 || thr_kind == XH_THR_DOY_F32)
       XH_REQUIRE(tidx, XH_ERR_ARG, "xh_threshold_count: tidx required for per-doy thresholds");
   }
@@ -641,7 +642,8 @@ int xh_rolling_reduce(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t
                       int reducer, float* out, int64_t out_st) {
   int rc = check_tc("xh_rolling_reduce", ctx, x, T, C, st, sc);
   if (rc) return rc;
-  XH_REQUIRE(out && out_st >= C, XH_ERR_ARG, "xh_rolling_reduce: out NULL or out_st < C");
+  XH_REQUIRE(out, XH_ERR_ARG, "xh_rolling_reduce: out NULL");
+  XH_REQUIRE(out_st >= C, XH_ERR_LAYOUT, "xh_rolling_reduce: needs time-major rows of at least the row width (out_st)");
   XH_REQUIRE(window >= 1, XH_ERR_ARG, "xh_rolling_reduce: window must be >= 1");
   if (T == 0 || C == 0) return XH_OK;
   // xarray: center=True -> window covers [t - w//2, t + w - 1 - w//2]; else trailing [t - w + 1, t]

@@ -189,7 +189,8 @@ int xh_bivariate_count(xh_ctx* ctx, const float* x1, const float* x2, int64_t T,
                        int32_t* count_out, int32_t* valid_out) {
   int rc = chk2("xh_bivariate_count", ctx, x1, T, C, st1, 1);
   if (rc) return rc;
-  XH_REQUIRE(x2 && st2 >= C, XH_ERR_ARG, "xh_bivariate_count: x2 NULL or st2 < C");
+  XH_REQUIRE(x2, XH_ERR_ARG, "xh_bivariate_count: x2 NULL");
+  XH_REQUIRE(st2 >= C, XH_ERR_LAYOUT, "xh_bivariate_count: needs time-major rows of at least the row width (st2)");
   XH_REQUIRE(op1 >= XH_OP_GT && op1 <= XH_OP_NE && op2 >= XH_OP_GT && op2 <= XH_OP_NE, XH_ERR_OP,
              "Operation `%d/%d` not recognized.", op1, op2);
   XH_REQUIRE(combine == 1 || combine == 2, XH_ERR_ARG, "xh_bivariate_count: combine must be 1 (all) or 2 (any)");
@@ -242,7 +243,8 @@ int xh_mask_rows(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, 
                  const int32_t* lo, const int32_t* hi, int invert, float* out, int64_t out_st) {
   int rc = chk2("xh_mask_rows", ctx, x, T, C, st, sc);
   if (rc) return rc;
-  XH_REQUIRE(lo && hi && out && out_st >= C, XH_ERR_ARG, "xh_mask_rows: NULL argument or out_st < C");
+  XH_REQUIRE(lo && hi && out, XH_ERR_ARG, "xh_mask_rows: NULL argument");
+  XH_REQUIRE(out_st >= C, XH_ERR_LAYOUT, "xh_mask_rows: needs time-major rows of at least the row width (out_st)");
   size_t cur = 0;
   const int64_t* d_seg = nullptr;
   rc = up_seg(ctx, &cur, seg_off, P, T, "xh_mask_rows", &d_seg);

@@ -440,7 +440,8 @@ int xh_cumsum_reset(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t s
                     float* out, int64_t out_st) {
   int rc = check_tc2("xh_cumsum_reset", ctx, x, T, C, st, sc);
   if (rc) return rc;
-  XH_REQUIRE(out && out_st >= C, XH_ERR_ARG, "xh_cumsum_reset: out NULL or out_st < C");
+  XH_REQUIRE(out, XH_ERR_ARG, "xh_cumsum_reset: out NULL");
+  XH_REQUIRE(out_st >= C, XH_ERR_LAYOUT, "xh_cumsum_reset: needs time-major rows of at least the row width (out_st)");
   if (T == 0 || C == 0) return XH_OK;
   hipLaunchKernelGGL((k_cumsum_rle<0>), dim3((unsigned)cdiv64(C, XH_BLOCK)), dim3(XH_BLOCK), 0, ctx->stream, x, T, C, st,
                      index_first, out, out_st);
@@ -452,7 +453,8 @@ int xh_rle(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, int64_
            int64_t out_st) {
   int rc = check_tc2("xh_rle", ctx, x, T, C, st, sc);
   if (rc) return rc;
-  XH_REQUIRE(out && out_st >= C, XH_ERR_ARG, "xh_rle: out NULL or out_st < C");
+  XH_REQUIRE(out, XH_ERR_ARG, "xh_rle: out NULL");
+  XH_REQUIRE(out_st >= C, XH_ERR_LAYOUT, "xh_rle: needs time-major rows of at least the row width (out_st)");
   if (T == 0 || C == 0) return XH_OK;
   hipLaunchKernelGGL((k_cumsum_rle<1>), dim3((unsigned)cdiv64(C, XH_BLOCK)), dim3(XH_BLOCK), 0, ctx->stream, x, T, C, st,
                      index_first, out, out_st);

@@ -526,7 +526,8 @@ static int spell_mask_impl(xh_ctx* ctx, const char* fn, const float* const* xs, 
     int rc = chk(fn, ctx, xs[i], T, C, st, sc);
     if (rc) return rc;
   }
-  XH_REQUIRE(out && out_st >= C, XH_ERR_ARG, "%s: out NULL or out_st < C", fn);
+  XH_REQUIRE(out, XH_ERR_ARG, "%s: out NULL", fn);
+  XH_REQUIRE(out_st >= C, XH_ERR_LAYOUT, "%s: needs time-major rows of at least the row width (out_st)", fn);
   XH_REQUIRE(window >= 1, XH_ERR_ARG, "%s: window must be >= 1", fn);
   XH_REQUIRE(win_reducer >= 0 && win_reducer <= 4, XH_ERR_OP, "%s: win_reducer %d not recognized", fn, win_reducer);
   XH_REQUIRE(op >= XH_OP_GT && op <= XH_OP_NE, XH_ERR_OP, "Operation `%d` not recognized.", op);
@@ -597,7 +598,8 @@ int xh_runs_with_holes(xh_ctx* ctx, const float* start, const float* stop, int64
                        int window_start, int window_stop, float* out, int64_t out_st) {
   int rc = chk("xh_runs_with_holes", ctx, start, T, C, st, sc);
   if (rc) return rc;
-  XH_REQUIRE(out && out_st >= C, XH_ERR_ARG, "xh_runs_with_holes: out NULL or out_st < C");
+  XH_REQUIRE(out, XH_ERR_ARG, "xh_runs_with_holes: out NULL");
+  XH_REQUIRE(out_st >= C, XH_ERR_LAYOUT, "xh_runs_with_holes: needs time-major rows of at least the row width (out_st)");
   XH_REQUIRE(window_start >= 1 && window_stop >= 1, XH_ERR_ARG, "xh_runs_with_holes: windows must be >= 1");
   if (T == 0 || C == 0) return XH_OK;
   if (window_start <= 64 && window_stop <= 64) {
@@ -624,7 +626,8 @@ int xh_keep_longest_run(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64
                         int P, float* out, int64_t out_st) {
   int rc = chk("xh_keep_longest_run", ctx, x, T, C, st, sc);
   if (rc) return rc;
-  XH_REQUIRE(out && out_st >= C, XH_ERR_ARG, "xh_keep_longest_run: out NULL or out_st < C");
+  XH_REQUIRE(out, XH_ERR_ARG, "xh_keep_longest_run: out NULL");
+  XH_REQUIRE(out_st >= C, XH_ERR_LAYOUT, "xh_keep_longest_run: needs time-major rows of at least the row width (out_st)");
   size_t cur = 0;
   const int64_t* d_seg = nullptr;
   rc = upload_seg(ctx, &cur, seg_off, P, T, "xh_keep_longest_run", &d_seg);
@@ -727,7 +730,8 @@ int xh_suspicious_run(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t
                       double thresh, uint8_t* out, int64_t out_st) {
   int rc = chk("xh_suspicious_run", ctx, x, T, C, st, sc);
   if (rc) return rc;
-  XH_REQUIRE(out && out_st >= C, XH_ERR_ARG, "xh_suspicious_run: out NULL or out_st < C");
+  XH_REQUIRE(out, XH_ERR_ARG, "xh_suspicious_run: out NULL");
+  XH_REQUIRE(out_st >= C, XH_ERR_LAYOUT, "xh_suspicious_run: needs time-major rows of at least the row width (out_st)");
   XH_REQUIRE(window >= 1, XH_ERR_ARG, "xh_suspicious_run: window must be >= 1");
   XH_REQUIRE(op >= -1 && op <= XH_OP_NE, XH_ERR_OP, "Operation `%d` not recognized.", op);
   if (C == 0 || T == 0) return XH_OK;

@@ -552,7 +552,8 @@ int ws_train(xh_ctx* ctx, const char* who, const float* ref, const float* hist, 
              int n0, const int32_t* enter, const int32_t* leave, int G, int per, const double* q, int nq, int kind, float* af,
              float* hist_q, double* scaling, double* mu_hist) {
   XH_REQUIRE(ctx && ref && hist && rows0 && q && af && hist_q && (G == 1 || (enter && leave)), XH_ERR_ARG, "%s: NULL argument", who);
-  XH_REQUIRE(T >= 1 && C >= 0 && G >= 1 && n0 >= 1 && per >= 0 && nq >= 1 && st >= C, XH_ERR_ARG, "%s: bad shape", who);
+  XH_REQUIRE(T >= 1 && C >= 0 && G >= 1 && n0 >= 1 && per >= 0 && nq >= 1, XH_ERR_ARG, "%s: bad shape", who);
+  XH_REQUIRE(st >= C, XH_ERR_LAYOUT, "%s: needs time-major rows of at least the row width (st)", who);
   XH_REQUIRE(kind == 0 || kind == 1, XH_ERR_ARG, "%s: kind must be 0 (+) or 1 (*)", who);
   if (n0 > WS_CAP || per > WS_PER || nq > WS_MAXQ) return XH_ERR_NOTIMPL;
   if (const char* e = xh_diag_env("XH_WINSEL"))
@@ -612,7 +613,8 @@ int ws_train(xh_ctx* ctx, const char* who, const float* ref, const float* hist, 
 int gq_train(xh_ctx* ctx, const char* who, const float* ref, const float* hist, int64_t T, int64_t C, int64_t st, const int32_t* rows,
              const int64_t* offs, int G, const double* q, int nq, int kind, float* af, float* hist_q, double* scaling, double* mu_hist) {
   XH_REQUIRE(ctx && ref && hist && rows && offs && q && af && hist_q, XH_ERR_ARG, "%s: NULL argument", who);
-  XH_REQUIRE(T >= 1 && C >= 0 && G >= 1 && nq >= 1 && st >= C, XH_ERR_ARG, "%s: bad shape", who);
+  XH_REQUIRE(T >= 1 && C >= 0 && G >= 1 && nq >= 1, XH_ERR_ARG, "%s: bad shape", who);
+  XH_REQUIRE(st >= C, XH_ERR_LAYOUT, "%s: needs time-major rows of at least the row width (st)", who);
   XH_REQUIRE(kind == 0 || kind == 1, XH_ERR_ARG, "%s: kind must be 0 (+) or 1 (*)", who);
   XH_REQUIRE(offs[0] == 0, XH_ERR_ARG, "%s: offs[0] must be 0", who);
   int64_t most = 0;

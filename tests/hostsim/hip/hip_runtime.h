@@ -16,6 +16,8 @@
 #define __forceinline__ inline
 #define __launch_bounds__(...)
 #define __restrict__
+#define __constant__ static const
+#define __noinline__ __attribute__((noinline))
 
 struct dim3 {
   unsigned x, y, z;
@@ -41,15 +43,54 @@ static inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) {
 template <typename F> static inline hipError_t hipFuncSetAttribute(F, int, int) { return hipSuccess; }
 enum { hipFuncAttributeMaxDynamicSharedMemorySize = 8 };
 
+// HIP's unqualified device min / max (an overload set there; kernels call them on matching types): the templates serve the
+// integer types, the float and double overloads are fminf / fmaxf / fmin / fmax as in HIP (a NaN operand gives the other one)
+template <typename T> static inline T min(T a, T b) { return b < a ? b : a; }
+template <typename T> static inline T max(T a, T b) { return a < b ? b : a; }
+static inline float min(float a, float b) { return fminf(a, b); }
+static inline float max(float a, float b) { return fmaxf(a, b); }
+static inline double min(double a, double b) { return fmin(a, b); }
+static inline double max(double a, double b) { return fmax(a, b); }
+
+// normcdfinv (the inverse of the standard normal distribution function), written from the host's erfc: the Abramowitz-Stegun
+// 26.2.23 start (4.5e-4) refined by Halley steps on Phi(x) - p, each of which cubes the error; solved in the lower tail, where
+// erfc keeps its relative precision, and mirrored (1 - p is exact for p >= 0.5)
+static inline double normcdfinv(double p) {
+  if (!(p >= 0.0 && p <= 1.0)) return NAN;
+  if (p == 0.0) return -INFINITY;
+  if (p == 1.0) return INFINITY;
+  const bool upper = p > 0.5;
+  const double q = upper ? 1.0 - p : p;
+  const double t = sqrt(-2.0 * log(q));
+  double x = -(t - (2.515517 + t * (0.802853 + t * 0.010328)) / (1.0 + t * (1.432788 + t * (0.189269 + t * 0.001308))));
+  for (int it = 0; it < 8; ++it) {
+    const double pdf = 0.3989422804014326779 * exp(-0.5 * x * x);
+    if (!(pdf > 0.0)) break;
+    const double dx = (0.5 * erfc(-x * 0.70710678118654752440) - q) / pdf;
+    const double step = dx / (1.0 + 0.5 * x * dx);
+    x -= step;
+    if (fabs(step) <= 1e-16 * fabs(x)) break;
+  }
+  return upper ? -x : x;
+}
+
 // (a macro, like the real one: kernels with default arguments are launched with fewer than they declare)
 #ifdef SIM_FIBERS
 #include "../simt.h"
-#define hipLaunchKernelGGL(kern, grid, block, lds, stream, ...) sim_launch_fibers([=]() { kern(__VA_ARGS__); }, (grid), (block))
+#define hipLaunchKernelGGL(kern, grid, block, lds, stream, ...) sim_launch_fibers([=]() { kern(__VA_ARGS__); }, (grid), (block), (size_t)(lds))
 #else
+// thread by thread: atomics are plain read-modify-writes; `extern __shared__` memory (rewritten by simdevice.py to a pointer,
+// for kernels whose lanes keep private columns in it) is a heap block of EXACTLY the launch's size, so that a sanitizer sees a
+// lane that steps past the workgroup's allocation
+template <typename T> static inline T atomicOr(T* p, T v) { const T old = *p; *p = old | v; return old; }
+extern thread_local unsigned char* g_sim_dyn_lds;
+static inline unsigned char* sim_dynamic_lds() { return g_sim_dyn_lds; }
 template <typename F>
-static inline void sim_launch_loop(F body, dim3 grid, dim3 block) {
+static inline void sim_launch_loop(F body, dim3 grid, dim3 block, size_t lds) {
   gridDim = {grid.x, grid.y, grid.z};
   blockDim = {block.x, block.y, block.z};
+  unsigned char* const outer = g_sim_dyn_lds;
+  g_sim_dyn_lds = lds ? (unsigned char*)malloc(lds) : nullptr;
   for (unsigned bz = 0; bz < grid.z; ++bz)
     for (unsigned by = 0; by < grid.y; ++by)
       for (unsigned bx = 0; bx < grid.x; ++bx) {
@@ -61,8 +102,10 @@ static inline void sim_launch_loop(F body, dim3 grid, dim3 block) {
               body();
             }
       }
+  free(g_sim_dyn_lds);
+  g_sim_dyn_lds = outer;
 }
-#define hipLaunchKernelGGL(kern, grid, block, lds, stream, ...) sim_launch_loop([=]() { kern(__VA_ARGS__); }, (grid), (block))
+#define hipLaunchKernelGGL(kern, grid, block, lds, stream, ...) sim_launch_loop([=]() { kern(__VA_ARGS__); }, (grid), (block), (size_t)(lds))
 #endif
 
 struct uint2 { unsigned x, y; };

@@ -11,14 +11,21 @@
 #include "common.h"
 
 thread_local SimIdx blockIdx, threadIdx, gridDim, blockDim;
+thread_local unsigned char* g_sim_dyn_lds = nullptr;   // the `extern __shared__` block of a thread-by-thread launch (hip_runtime.h)
 
 // ---- SIMT on fibers (simt.h) -------------------------------------------------------------------------------------------------
 thread_local SimBlockState g_sim;
 static constexpr size_t SIM_STACK = (size_t)1 << 20;   // per fiber; reserved, committed on touch
 
 static void sim_trampoline() {
+#ifdef SIM_ASAN_FIBERS
+  __sanitizer_finish_switch_fiber(nullptr, &g_sim.sched_stack, &g_sim.sched_size);
+#endif
   g_sim.entry();
   g_sim.fibers[g_sim.cur].state = 3;
+#ifdef SIM_ASAN_FIBERS
+  __sanitizer_start_switch_fiber(nullptr, g_sim.sched_stack, g_sim.sched_size);   // (nullptr: this fiber's fake stack is released)
+#endif
   swapcontext(&g_sim.fibers[g_sim.cur].ctx, &g_sim.sched);
 }
 
@@ -52,7 +59,14 @@ void sim_run_block(size_t nthreads, const SimIdx& bdim) {
       if (f.state != 0) continue;
       g_sim.cur = (int)i;
       threadIdx = f.tid;
+#ifdef SIM_ASAN_FIBERS
+      void* fake = nullptr;
+      __sanitizer_start_switch_fiber(&fake, f.stack, SIM_STACK);
+#endif
       swapcontext(&g_sim.sched, &f.ctx);
+#ifdef SIM_ASAN_FIBERS
+      __sanitizer_finish_switch_fiber(fake, nullptr, nullptr);
+#endif
       ran = true;
       if (f.state == 3) ++done;
     }

@@ -20,7 +20,17 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 from mock_device import MockDevice, _MockLib  # noqa: E402
 from xclim_amd import _capi  # noqa: E402
 
-SIMULATED_UNITS = ("detrend", "window", "runlen", "reduce", "spell", "elemwise", "eqm", "plane", "wquantile")
+SIMULATED_UNITS = ("detrend", "window", "runlen", "reduce", "spell", "elemwise", "eqm", "plane", "wquantile",
+                   # one cell (or cell pair) per lane, no traffic between lanes; stdidx.hip's k_si_fit stages every lane's sample in
+                   # a private LDS column (lds + threadIdx.x, stride FIT_BLOCK): its `extern __shared__` becomes the launch's block
+                   "fire", "ffdi", "pet", "stdidx", "f64red")
+# the units that joined together with the stand-alone sanitizer driver (tests/hostsim/standalone)
+NEW_UNITS = ("fire", "ffdi", "pet", "stdidx", "f64red", "f64run")
+NEW_ENTRY_POINTS = (
+    "xh_fire_weather", "xh_overwintering_dc", "xh_mcarthur", "xh_solar_table", "xh_pet_month_table", "xh_pet_daily", "xh_pet_monthly",
+    "xh_si_fit", "xh_si_apply", "xh_si_fit_f64", "xh_si_apply_f64", "xh_thresholded_reduce_f64", "xh_range_reduce_f64",
+    "xh_domain_count_f64", "xh_bivariate_count_f64", "xh_rolling_reduce_f64", "xh_compare_map_f64", "xh_run_stats_f64",
+    "xh_spell_mask_f64", "xh_spell_run_stats_f64", "xh_run_stats_doy_f64", "xh_percentile_doy_f64")
 # compiled, but their kernels (or the selection kernels behind them) speak to the wave: refused
 WAVE_ENTRY_POINTS = ()
 # eqm.hip votes `__all(m == nq)` only to pick between two forms that are each right for the lane that takes them
@@ -28,11 +38,16 @@ UNIT_DEFINES = {"eqm": ["-D__all(x)=((x)!=0)"],
                 # plane.hip appends to its work lists wave by wave and keeps lane-private LDS columns: see wave_of_one.h
                 "plane": ["-include", os.path.join(HERE, "wave_of_one.h")],
                 # wquantile.hip's LDS arrays are lane-private columns ([i * 64 + lane]): static arrays do
-                "wquantile": ["-D__shared__=static"]}
+                "wquantile": ["-D__shared__=static"],
+                "f64run": ["-DSIM_EXACT_DYN_LDS=1"]}
+# thread-by-thread units that declare dynamic LDS (lane-private columns): the declaration is rewritten as in the fiber units
+DYN_LDS_UNITS = ("stdidx",)
 
 
 # units whose kernels talk through LDS / the wave in WAVE-UNIFORM control flow: every workgroup as a set of fibers (simt.h)
-FIBER_UNITS = ("f64", "select", "select5", "tcount", "qdm", "quantile", "doystats", "core", "reduce2", "pdoy_top", "pdoy_quad", "pdoy_walk", "select3", "qdm2", "select2", "select4", "winsel")
+FIBER_UNITS = ("f64", "select", "select5", "tcount", "qdm", "quantile", "doystats", "core", "reduce2", "pdoy_top", "pdoy_quad", "pdoy_walk", "select3", "qdm2", "select2", "select4", "winsel",
+               # f64run.hip: k_percentile_doy_f64 sorts its columns in LDS by all threads of the workgroup (barriers, an LDS atomicAdd)
+               "f64run")
 # topnet.h (the comparator networks of the register percentile kernels) issues v_min_f32 / v_max_f32 and a NaN-replace-and-count
 # triple as inline ISA: four statements, rewritten to the C++ they stand for (NaN never enters the min / max: the callers replace
 # it first), in a copy of the header that the fiber units include instead
@@ -88,11 +103,7 @@ UNIT_REWRITES = {
 _DYN_LDS = re.compile(r"extern\s+__shared__\s+(?:__attribute__\(\(aligned\(\d+\)\)\)\s+)?([\w ]+?)\s+(\w+)\[\];")
 
 
-def build(workdir: str) -> str:
-    """g++ the simulated translation units (sources unchanged, except that an `extern __shared__ T name[];` of a fiber unit
-    becomes a pointer to the workgroup's LDS buffer) + sim_runtime.cpp into workdir/libxclimhip_hostsim.so."""
-    if shutil.which("g++") is None:
-        raise RuntimeError("no g++")
+def _prepare_headers(workdir: str) -> None:
     for header, rules in HEADER_REWRITES.items():
         text = open(os.path.join(CSRC, header)).read()
         for old, new in rules:
@@ -100,49 +111,108 @@ def build(workdir: str) -> str:
                 raise RuntimeError(f"{header}: the statement the simulation rewrites has changed: {old[:60]!r}")
             text = text.replace(old, new)
         open(os.path.join(workdir, header), "w").write(text)
+
+
+def _prepare_unit(unit: str, workdir: str, san: str = ""):
+    """(source file, extra flags) of one unit: the source unchanged, or its rewritten copy in workdir."""
+    src = os.path.join(CSRC, unit + ".hip")
+    extra = list(UNIT_DEFINES.get(unit, []))
+    if unit in DYN_LDS_UNITS:
+        text, nsub = _DYN_LDS.subn(lambda m: f"{m.group(1)}* {m.group(2)} = ({m.group(1)}*)sim_dynamic_lds();", open(src).read())
+        if nsub == 0:
+            raise RuntimeError(f"{unit}.hip: the `extern __shared__` declaration the simulation rewrites has changed")
+        src = os.path.join(workdir, unit + ".sim.cpp")
+        open(src, "w").write(text)
+    if unit in FIBER_UNITS:
+        text = open(src).read()
+        if unit == "core":   # the runtime half of core.hip is sim_runtime.cpp's job: only its kernels (synthetic fields, transposes)
+            text = '#include "common.h"\n' + text[text.index("// ---- synthetic generator"):]
+        text = _DYN_LDS.sub(lambda m: f"{m.group(1)}* {m.group(2)} = ({m.group(1)}*)sim_dynamic_lds();", text)
+        # the LDS-only workgroup barrier (s_waitcnt lgkmcnt(0); s_barrier) is a workgroup barrier; empty asm statements are
+        # compiler fences whose operand class "v" / "s" (a VGPR / SGPR) becomes "r"
+        text = text.replace('asm volatile("s_waitcnt lgkmcnt(0)\\n\\ts_barrier" ::: "memory")', "__syncthreads()")
+        text = re.sub(r'asm volatile\(""\s*:\s*"\+[vs]"', 'asm volatile("" : "+r"', text)
+        for pat, rep in UNIT_REWRITES.get(unit, []):
+            text, nsub = re.subn(pat, rep, text, flags=re.S)
+            if nsub == 0:
+                raise RuntimeError(f"{unit}.hip: the statement the simulation rewrites has changed: {pat[:50]!r}")
+        src = os.path.join(workdir, unit + ".sim.cpp")
+        open(src, "w").write(text)
+        extra += ["-DSIM_FIBERS=1", "-D__shared__=static"]
+        if unit == "select4" and san and "undefined" in san and not os.environ.get("HOSTSIM_SANITIZE_BOUNDS_ONLY"):
+            # g++ 11: with ALL of -fsanitize=undefined the index check of `v[u]` on the ring's register set (a reference to
+            # an array handed to a lambda) reads a wrong temporary and the access after it faults — with the loop variable
+            # verified intact by an explicit check in front of it.  Either half alone is clean: this build carries every
+            # check but `bounds`; HOSTSIM_SANITIZE=bounds HOSTSIM_SANITIZE_BOUNDS_ONLY=1 is the other half.
+            extra += ["-fno-sanitize=bounds"]
+    return src, extra
+
+
+def _compile_all(units, workdir, flags, san=""):
+    from concurrent.futures import ThreadPoolExecutor
+
+    def compile_unit(unit):
+        obj = os.path.join(workdir, unit + ".o")
+        src, extra = _prepare_unit(unit, workdir, san)
+        subprocess.run(["g++", "-x", "c++", *flags, *extra, "-c", src, "-o", obj], check=True)
+        return obj
+
+    with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:   # (g++ runs outside the GIL)
+        objs = list(pool.map(compile_unit, units))
+    obj = os.path.join(workdir, "sim_runtime.o")
+    subprocess.run(["g++", *flags, "-c", os.path.join(HERE, "sim_runtime.cpp"), "-o", obj], check=True)
+    return objs + [obj]
+
+
+def build(workdir: str) -> str:
+    """g++ the simulated translation units (sources unchanged, except that an `extern __shared__ T name[];` of a fiber unit
+    becomes a pointer to the workgroup's LDS buffer) + sim_runtime.cpp into workdir/libxclimhip_hostsim.so."""
+    if shutil.which("g++") is None:
+        raise RuntimeError("no g++")
+    _prepare_headers(workdir)
     flags = ["-std=c++17", "-O1", "-fPIC", "-ffp-contract=off", "-I", workdir, "-I", HERE, "-I", CSRC]
     # HOSTSIM_SANITIZE=undefined (or address,undefined with LD_PRELOAD=libasan.so): an audit build of the kernels under the
     # compiler's sanitizers — out-of-bounds LDS / scratch accesses, shifts, signed overflow
     san = os.environ.get("HOSTSIM_SANITIZE")
     if san:
         flags += ["-g", f"-fsanitize={san}", "-fno-sanitize-recover=all" if os.environ.get("HOSTSIM_SANITIZE_FATAL") else "-fsanitize-recover=all"]
-    def compile_unit(unit):
-        obj = os.path.join(workdir, unit + ".o")
-        src = os.path.join(CSRC, unit + ".hip")
-        extra = list(UNIT_DEFINES.get(unit, []))
-        if unit in FIBER_UNITS:
-            text = open(src).read()
-            if unit == "core":   # the runtime half of core.hip is sim_runtime.cpp's job: only its kernels (synthetic fields, transposes)
-                text = '#include "common.h"\n' + text[text.index("// ---- synthetic generator"):]
-            text = _DYN_LDS.sub(lambda m: f"{m.group(1)}* {m.group(2)} = ({m.group(1)}*)sim_dynamic_lds();", text)
-            # the LDS-only workgroup barrier (s_waitcnt lgkmcnt(0); s_barrier) is a workgroup barrier; empty asm statements are
-            # compiler fences whose operand class "v" / "s" (a VGPR / SGPR) becomes "r"
-            text = text.replace('asm volatile("s_waitcnt lgkmcnt(0)\\n\\ts_barrier" ::: "memory")', "__syncthreads()")
-            text = re.sub(r'asm volatile\(""\s*:\s*"\+[vs]"', 'asm volatile("" : "+r"', text)
-            for pat, rep in UNIT_REWRITES.get(unit, []):
-                text, nsub = re.subn(pat, rep, text, flags=re.S)
-                if nsub == 0:
-                    raise RuntimeError(f"{unit}.hip: the statement the simulation rewrites has changed: {pat[:50]!r}")
-            src = os.path.join(workdir, unit + ".sim.cpp")
-            open(src, "w").write(text)
-            extra += ["-DSIM_FIBERS=1", "-D__shared__=static"]
-            if unit == "select4" and san and "undefined" in san and not os.environ.get("HOSTSIM_SANITIZE_BOUNDS_ONLY"):
-                # g++ 11: with ALL of -fsanitize=undefined the index check of `v[u]` on the ring's register set (a reference to
-                # an array handed to a lambda) reads a wrong temporary and the access after it faults — with the loop variable
-                # verified intact by an explicit check in front of it.  Either half alone is clean: this build carries every
-                # check but `bounds`; HOSTSIM_SANITIZE=bounds HOSTSIM_SANITIZE_BOUNDS_ONLY=1 is the other half.
-                extra += ["-fno-sanitize=bounds"]
-        subprocess.run(["g++", "-x", "c++", *flags, *extra, "-c", src, "-o", obj], check=True)
-        return obj
-
-    from concurrent.futures import ThreadPoolExecutor
-
-    with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:   # (g++ runs outside the GIL)
-        objs = list(pool.map(compile_unit, SIMULATED_UNITS + FIBER_UNITS))
-    obj = os.path.join(workdir, "sim_runtime.o")
-    subprocess.run(["g++", *flags, "-c", os.path.join(HERE, "sim_runtime.cpp"), "-o", obj], check=True)
+    objs = _compile_all(SIMULATED_UNITS + FIBER_UNITS, workdir, flags, san or "")
     out = os.path.join(workdir, "libxclimhip_hostsim.so")
-    subprocess.run(["g++", "-shared", *([f"-fsanitize={san}"] if san else []), "-o", out, *objs, obj], check=True)
+    subprocess.run(["g++", "-shared", *([f"-fsanitize={san}"] if san else []), "-o", out, *objs], check=True)
+    return out
+
+
+def build_shared(basetemp: str) -> str:
+    """build() once per pytest session: the modules that need the library (tests/test_hostsim_cpu.py,
+    tests/test_hostsim_sanitize_cpu.py) hand in the session's base temporary directory and share one build.  A failed build is
+    not remembered: every caller sees its CalledProcessError."""
+    work = os.path.join(basetemp, "hostsim_shared")
+    out = os.path.join(work, "libxclimhip_hostsim.so")
+    if not os.path.exists(out):
+        os.makedirs(work, exist_ok=True)
+        build(work)
+    return out
+
+
+STANDALONE_SANITIZE = "address,undefined"
+
+
+def build_standalone(workdir: str) -> str:
+    """The stand-alone sanitizer driver (standalone/san_driver.cpp: a C++ program with its own main, no Python in the process,
+    nothing preloaded): the NEW_UNITS' rewritten sources + sim_runtime.cpp + the driver, all with -g -O1
+    -fsanitize=address,undefined -fno-sanitize-recover=all, linked into workdir/san_driver."""
+    if shutil.which("g++") is None:
+        raise RuntimeError("no g++")
+    _prepare_headers(workdir)
+    # (-fno-var-tracking: line tables without variable-location tracking, which alone takes a minute on f64red / f64run)
+    flags = ["-std=c++17", "-g", "-fno-var-tracking", "-O1", "-ffp-contract=off", f"-fsanitize={STANDALONE_SANITIZE}", "-fno-sanitize-recover=all",
+             "-I", workdir, "-I", HERE, "-I", CSRC, "-I", os.path.join(ROOT, "include")]
+    objs = _compile_all(NEW_UNITS, workdir, flags, STANDALONE_SANITIZE)
+    out = os.path.join(workdir, "san_driver")
+    # (the sanitizer runtimes linked statically: the program needs no particular order of shared libraries at start-up, whatever
+    # the environment it is started in loads first)
+    subprocess.run(["g++", *flags, "-static-libasan", "-static-libubsan", "-o", out, os.path.join(HERE, "standalone", "san_driver.cpp"), *objs],
+                   check=True)
     return out
 
 
@@ -188,3 +258,114 @@ class SimDevice(MockDevice):
 
     def sync(self):
         return None
+
+
+_ASAN_SWAPCONTEXT_NOTE = "WARNING: ASan doesn't fully support makecontext/swapcontext functions"
+
+
+class SanitizerReport(AssertionError):
+    """The stand-alone driver ended with a sanitizer report (or any other failure of the process)."""
+
+
+class _ReplayLib(_SimLib):
+    """The simulation library, except that every call of one of NEW_ENTRY_POINTS runs in a FRESH PROCESS of the stand-alone
+    sanitizer driver: the call's memory blocks go to a case directory as raw arrays, the driver copies each into a malloc
+    block of exactly the allocation's size, calls the entry point, dumps the blocks, and they are copied back here."""
+
+    def __init__(self, path: str, driver: str, casedir: str, dev):
+        super().__init__(path)
+        self._driver, self._casedir, self._dev, self._err = driver, casedir, dev, b""
+        self.replayed = {}   # entry point -> the int64 arguments (T, C, strides ...) of every sanitized call
+        self.in_process = ()  # entry points a test wants from the in-process library for a while (a table it only needs as input)
+
+    def __getattr__(self, name):
+        if name == "xh_last_error":   # (read once by _capi._check after a failed call: a replayed call's text, else the library's)
+            return self._last_error
+        if name in NEW_ENTRY_POINTS:
+            return lambda ctx, *args: (super(_ReplayLib, self).__getattr__(name)(ctx, *args) if name in self.in_process
+                                       else self._replay(name, args))
+        return super().__getattr__(name)
+
+    def _last_error(self):
+        err, self._err = self._err, b""
+        if err:
+            return err
+        fn = self._dll.xh_last_error
+        fn.restype = C.c_char_p
+        return fn()
+
+    def _block(self, p, blocks):
+        """(id, offset) of the memory block an address lies in: an allocation of the device, or a host array handed over with
+        np_ptr (ctypes keeps the array on the pointer)."""
+        addr = p.value if hasattr(p, "value") else int(p or 0)
+        if not addr:
+            return None
+        arr = getattr(p, "_arr", None)
+        if arr is not None:
+            base, n = arr.ctypes.data, arr.nbytes
+        else:
+            for base, n in self._dev._exact.items():
+                if base <= addr < base + max(n, 1):
+                    break
+            else:
+                raise RuntimeError(f"address {addr:#x} lies in no block the simulated device allocated")
+        if base not in blocks:
+            blocks[base] = (f"b{len(blocks)}", n)
+        return blocks[base][0], addr - base
+
+    def _replay(self, name, args):
+        case = os.path.join(self._casedir, f"{sum(len(v) for v in self.replayed.values()):05d}_{name}")
+        os.makedirs(case)
+        blocks, lines = {}, [f"entry {name}", "arg ctx"]
+        for a in args:
+            if isinstance(a, C.Array):
+                refs = [self._block(C.c_void_p(v), blocks) for v in a]
+                lines.append(f"arg v {len(refs)} " + " ".join("-" if r is None else f"{r[0]} {r[1]}" for r in refs))
+            elif isinstance(a, (C.c_void_p, C._Pointer)) or hasattr(a, "_arr"):
+                r = self._block(a, blocks)
+                lines.append("arg n" if r is None else f"arg p {r[0]} {r[1]}")
+            elif isinstance(a, (bool, int, np.integer)):
+                lines.append(f"arg i {int(a)}")
+            elif isinstance(a, (float, np.floating)):
+                lines.append(f"arg d {float(a).hex() if np.isfinite(a) else repr(float(a))}")
+            else:
+                raise TypeError(f"{name}: cannot record an argument of type {type(a).__name__}")
+        for base, (bid, n) in blocks.items():
+            lines.insert(1, f"buf {bid} {n}")
+            with open(os.path.join(case, bid + ".in"), "wb") as f:
+                f.write(C.string_at(base, n))
+        open(os.path.join(case, "manifest.txt"), "w").write("\n".join(lines) + "\n")
+        res = subprocess.run([self._driver, case], capture_output=True, text=True)
+        # (the swapcontext interceptor of g++ 11's ASan prints one fixed warning on its first call, annotated fibers or not)
+        report = "\n".join(ln for ln in res.stderr.splitlines() if ln.strip() and _ASAN_SWAPCONTEXT_NOTE not in ln)
+        if res.returncode != 0 or report:
+            raise SanitizerReport(f"{name} ({case}): exit status {res.returncode}\n{res.stderr[-4000:]}")
+        for base, (bid, n) in blocks.items():
+            data = open(os.path.join(case, bid + ".out"), "rb").read()
+            assert len(data) == n
+            C.memmove(base, data, n)
+        rc, _, msg = open(os.path.join(case, "result.txt")).read().partition("\n")
+        self._err = msg.rstrip("\n").encode()
+        self.replayed.setdefault(name, []).append(tuple(int(a) for a, t in zip(args, _capi.SIGNATURES[name][1:]) if t is C.c_int64))
+        shutil.rmtree(case)
+        return int(rc)
+
+
+class ReplayDevice(SimDevice):
+    """A SimDevice whose allocations are remembered with their EXACT sizes and whose calls of the NEW_ENTRY_POINTS run in the
+    stand-alone sanitizer driver (tests/test_hostsim_sanitize_cpu.py)."""
+
+    def __init__(self, path: str, driver: str, casedir: str):
+        super().__init__(path)
+        self._exact = {}
+        self.lib = _ReplayLib(path, driver, casedir, self)
+
+    def empty(self, shape, dtype):
+        a = super().empty(shape, dtype)
+        shape = (shape,) if np.isscalar(shape) else tuple(shape)
+        self._exact[a.ptr] = int(np.prod(shape, dtype=np.int64)) * np.dtype(dtype).itemsize
+        return a
+
+    def _release(self, ptr: int, nbytes: int) -> None:
+        self._exact.pop(ptr, None)
+        super()._release(ptr, nbytes)

@@ -17,6 +17,13 @@
 #include <functional>
 #include <vector>
 
+// Under AddressSanitizer every switch of stacks is announced (start_switch_fiber before swapcontext, finish_switch_fiber on
+// arrival), so that ASan follows the fibers' stacks and keeps one fake stack per fiber
+#if defined(__SANITIZE_ADDRESS__)
+#include <sanitizer/common_interface_defs.h>
+#define SIM_ASAN_FIBERS 1
+#endif
+
 struct SimFiber {
   ucontext_t ctx;
   char* stack = nullptr;
@@ -24,6 +31,7 @@ struct SimFiber {
   SimIdx tid{0, 0, 0};
   const void* site = nullptr;
   int orgen = 0;  // calls of __syncthreads_or so far (selects one of two flags)
+  void* fake = nullptr;  // ASan's fake stack of this fiber while it is switched out
 };
 
 struct SimBlockState {
@@ -35,6 +43,8 @@ struct SimBlockState {
   unsigned char* dyn_lds = nullptr;
   int or_acc[2] = {0, 0};
   std::vector<uint32_t> pub[4];  // registers a wave made readable for v_readlane from divergent code (sim_publish / sim_peek)
+  const void* sched_stack = nullptr;  // the scheduler's stack as ASan reported it on a fiber's arrival
+  size_t sched_size = 0;
 };
 extern thread_local SimBlockState g_sim;
 
@@ -42,7 +52,13 @@ static inline void sim_yield(int state, const void* site) {
   SimFiber& f = g_sim.fibers[g_sim.cur];
   f.state = state;
   f.site = site;
+#ifdef SIM_ASAN_FIBERS
+  __sanitizer_start_switch_fiber(&f.fake, g_sim.sched_stack, g_sim.sched_size);
+#endif
   swapcontext(&f.ctx, &g_sim.sched);
+#ifdef SIM_ASAN_FIBERS
+  __sanitizer_finish_switch_fiber(f.fake, &g_sim.sched_stack, &g_sim.sched_size);
+#endif
 }
 static inline unsigned sim_lane() { return (unsigned)g_sim.cur & 63u; }
 static inline uint64_t* sim_wave_slots() { return g_sim.slots.data() + ((size_t)g_sim.cur >> 6) * 64; }
@@ -161,15 +177,26 @@ static inline float sim_fmed3f(float a, float b, float c) {
 
 void sim_run_block(size_t nthreads, const SimIdx& bdim);
 
+// SIM_EXACT_DYN_LDS (the units that joined with the stand-alone sanitizer run): the dynamic LDS of a launch is a heap block of
+// EXACTLY the size the launcher asked for instead of the shared 160 KiB buffer, so that a sanitizer sees an index past it
 template <typename F>
-static inline void sim_launch_fibers(F body, dim3 grid, dim3 block) {
+static inline void sim_launch_fibers(F body, dim3 grid, dim3 block, size_t lds = 0) {
   gridDim = {grid.x, grid.y, grid.z};
   blockDim = {block.x, block.y, block.z};
   g_sim.entry = body;
+#ifdef SIM_EXACT_DYN_LDS
+  unsigned char* const shared_buf = g_sim.dyn_lds;
+  if (lds) g_sim.dyn_lds = (unsigned char*)malloc(lds);
+#else
+  (void)lds;
+#endif
   for (unsigned bz = 0; bz < grid.z; ++bz)
     for (unsigned by = 0; by < grid.y; ++by)
       for (unsigned bx = 0; bx < grid.x; ++bx) {
         blockIdx = {bx, by, bz};
         sim_run_block((size_t)block.x * block.y * block.z, blockDim);
       }
+#ifdef SIM_EXACT_DYN_LDS
+  if (lds) { free(g_sim.dyn_lds); g_sim.dyn_lds = shared_buf; }
+#endif
 }

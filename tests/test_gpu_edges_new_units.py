@@ -1,0 +1,210 @@
+"""Edge shapes of the entry points of fire.hip, ffdi.hip, pet.hip, stdidx.hip, f64red.hip and f64run.hip on the device: empty,
+single-cell, ragged and odd-tail grids, single steps and short series, all-NaN fields and an all-NaN cell next to valid ones,
+and the error codes of the launchers.  The checks (tests/newunit_cases.py) compare with the restatements the GPU tests of
+these entry points use, at their tolerances, and require the restatement's NaN pattern exactly; the same checks run in the
+CPU tier in the stand-alone sanitizer driver of the host simulation (tests/test_hostsim_sanitize_cpu.py).  Padded, poisoned
+row views are tests/test_gpu_strided_abi.py's."""
+import numpy as np
+import pytest
+
+import newunit_cases as nc
+from xclim_amd import kernels as K
+from xclim_amd._capi import XH_ERR_ARG, XH_ERR_LAYOUT, XclimHipError, _vp, np_ptr
+
+pytestmark = pytest.mark.gpu
+
+GRIDS = [(0,), (1,), (3,), (5, 1), (257,), (1021,)]
+# float64 marches: two cells per lane needs an even row width (f64util.h: pick_vec), an odd one takes one cell per lane
+F64_GRIDS = GRIDS + [(2,), (130,), (131,)]
+ids = lambda s: "x".join(map(str, s))  # noqa: E731
+
+
+@pytest.fixture
+def native(monkeypatch):
+    monkeypatch.setenv("XCLIM_AMD_FLOAT64", "native")
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
+@pytest.mark.parametrize("shape", GRIDS, ids=ids)
+def test_mcarthur_grids(dev, shape, dtype):
+    nc.check_mcarthur(dev, 60, shape, dtype)
+
+
+@pytest.mark.parametrize("T, lim, all_nan", [(1, "xlim", False), (19, "discrete", False), (20, "xlim", False), (21, "discrete", False),
+                                             (60, "xlim", True)])
+def test_mcarthur_short_series_and_all_nan(dev, T, lim, all_nan):
+    """T = 19: the drought factor has no defined value; T = 20: its first one; below 20 rows the public function raises like the
+    reference and the launch is reached through the module's own runner."""
+    nc.check_mcarthur(dev, T, (3,), np.float32, lim, all_nan)
+    nc.check_mcarthur(dev, T, (2,), np.float64, lim, all_nan)
+
+
+@pytest.mark.parametrize("method, dtype", [("FAO_PM98", np.float32), ("TW48", np.float32), ("HG85", np.float64), ("DA02", np.float64)],
+                         ids=lambda v: v if isinstance(v, str) else np.dtype(v).name)
+@pytest.mark.parametrize("shape", GRIDS, ids=ids)
+def test_pet_and_water_budget_grids(dev, shape, method, dtype):
+    nc.check_pet(dev, method, dtype, shape)
+
+
+@pytest.mark.parametrize("method", nc.PET_METHODS)
+def test_pet_single_step_and_all_nan(dev, method):
+    nc.check_pet(dev, method, np.float32, (3,), T=1)
+    nc.check_pet(dev, method, np.float64, (3,), T=40, all_nan=True)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
+@pytest.mark.parametrize("shape", GRIDS, ids=ids)
+def test_standardized_index_grids(dev, native, shape, dtype):
+    """36 months, gamma with floc = 0, zero-inflated; cell 1 has a group with ONE valid value (NaN parameters), cell 2 a group of
+    zeros only."""
+    nc.check_si_public(dev, dtype, shape)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
+def test_standardized_index_single_step_and_all_nan(dev, native, dtype):
+    nc.check_si_public(dev, dtype, (3,), months=1)
+    nc.check_si_public(dev, dtype, (3,), all_nan=True)
+
+
+@pytest.mark.parametrize("staging", ["global", "lds"])
+@pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
+def test_si_kernels_small_groups(dev, dtype, staging):
+    """Monthly groups of 3 values, and day-of-year-like groups (G = 3 over 9 rows) of 3 values: gamma APP, gamma ML with floc.
+    fisk ML without floc on 23 values per group, as tests/test_gpu_stdidx.py::test_random_grid_against_scipy has them: a
+    3-parameter fit of 3 values has no maximum, both walks stop at arbitrary points and nothing defines the answer."""
+    nc.check_si_kernels(dev, dtype, 65, 36, 12, "gamma", "APP", 0.0, False, staging)
+    nc.check_si_kernels(dev, dtype, 3, 9, 3, "gamma", "ML", 0.0, True, staging)
+    nc.check_si_kernels(dev, dtype, 3, 276, 12, "fisk", "ML", None, False, staging)
+
+
+def test_si_kernels_all_nan_field(dev):
+    """Every value NaN: NaN parameters, zero counts and a NaN index from both entry points, in both dtypes and stagings."""
+    for dtype in (np.float32, np.float64):
+        for staging in ("global", "lds"):
+            nc.check_si_kernels(dev, dtype, 3, 36, 12, "gamma", "ML", 0.0, True, staging, all_nan=True)
+            nc.check_si_kernels(dev, dtype, 3, 36, 12, "gamma", "APP", 0.0, False, staging, all_nan=True)
+
+
+@pytest.mark.parametrize("shape", F64_GRIDS, ids=ids)
+def test_float64_reductions_grids(dev, native, shape):
+    nc.check_f64_reductions(dev, shape, 60)
+
+
+@pytest.mark.parametrize("shape", F64_GRIDS, ids=ids)
+def test_float64_run_lengths_grids(dev, native, shape):
+    nc.check_f64_runs(dev, shape, 60)
+
+
+def test_float64_single_step_and_all_nan(dev, native):
+    for shape in ((3,), (2,)):
+        nc.check_f64_reductions(dev, shape, 1)
+        nc.check_f64_runs(dev, shape, 1)
+        nc.check_f64_reductions(dev, shape, 40, all_nan=True)
+        nc.check_f64_runs(dev, shape, 40, all_nan=True)
+
+
+@pytest.mark.parametrize("C", [1, 2, 131, 1021])
+def test_float64_rolling_grids(dev, native, C):
+    nc.check_f64_rolling(dev, C, 40)
+    nc.check_f64_rolling(dev, C, 1, windows=(1, 8))
+
+
+def test_float64_rolling_all_nan_field(dev, native):
+    for C in (2, 3):
+        nc.check_f64_rolling(dev, C, 40, windows=(1, 9), all_nan=True)
+
+
+@pytest.mark.parametrize("shape", [(1,), (2,), (131,)], ids=ids)
+def test_float64_percentile_doy_grids(dev, native, shape):
+    nc.check_f64_percentile_doy(dev, shape, 2, 5)
+
+
+def test_float64_percentile_doy_and_warm_spells_all_nan_field(dev, native):
+    """xh_percentile_doy_f64 and xh_run_stats_doy_f64 on a field without a value: a NaN table, the oracle's NaN pattern."""
+    for shape in ((2,), (3,)):
+        nc.check_f64_percentile_doy(dev, shape, 2, 5, all_nan=True)
+
+
+@pytest.mark.parametrize("mode", sorted(nc.FIRE_MODES))
+def test_fire_weather_season_modes_short_series(dev, mode):
+    for T, C in ((1, 3), (2, 63), (37, 65)):
+        nc.check_fire(dev, T, C, mode)
+
+
+@pytest.mark.parametrize("mode", sorted(nc.FIRE_MODES))
+def test_fire_weather_all_nan_field(dev, mode):
+    """xh_fire_weather and xh_overwintering_dc on fields without a value."""
+    nc.check_fire(dev, 37, 3, mode, all_nan=True)
+
+
+# ---- the launchers' argument checks: each must answer with its error code, before anything is launched -------------------
+def _raises(code, match):
+    class Ctx:
+        def __enter__(self):
+            self.cm = pytest.raises(XclimHipError, match=match)
+            self.info = self.cm.__enter__()
+            return self
+
+        def __exit__(self, *exc):
+            done = self.cm.__exit__(*exc)
+            assert self.info.value.code == code, self.info.value
+            return done
+
+    return Ctx()
+
+
+def test_launchers_refuse_bad_arguments(dev):
+    T, C = 24, 4
+    rng = np.random.default_rng(1)
+    x = dev.to_device(rng.gamma(2.0, 1.5, (T, C)).astype(np.float32))
+    x64 = dev.to_device(rng.gamma(2.0, 1.5, (T, C)))
+    out = dev.empty((T, C), np.float64)
+    group = (np.arange(T) % 12).astype(np.int32)
+    # xh_mcarthur: a row stride below the row width; a limiting function that does not exist
+    cell = dev.to_device(np.full(C, 800.0))
+
+    def mcarthur(st, lim):
+        dev.call("xh_mcarthur", T, C, st, 0, 0, 0, _vp(x.ptr), _vp(x.ptr), _vp(x.ptr), _vp(x.ptr), _vp(0), _vp(0), _vp(cell.ptr),
+                 _vp(cell.ptr), lim, np_ptr(K.MCARTHUR_N13), _vp(out.ptr), _vp(0), _vp(0), C)
+
+    with _raises(XH_ERR_LAYOUT, "xh_mcarthur"):
+        mcarthur(C - 1, 0)
+    with _raises(XH_ERR_ARG, "xh_mcarthur"):
+        mcarthur(C, 2)
+    # xh_pet_daily / xh_pet_monthly: a method outside their ranges; st < C
+    nul = _vp(0)
+
+    def pet_daily(st, method):
+        dev.call("xh_pet_daily", T, C, st, method, 0, _vp(x.ptr), _vp(x.ptr), nul, _vp(x.ptr), _vp(x.ptr), _vp(x.ptr), _vp(x.ptr),
+                 _vp(x.ptr), _vp(x.ptr), nul, nul, 0, nul, 0.0023, 0.5, _vp(out.ptr), nul, C)
+
+    with _raises(XH_ERR_ARG, "method must be 0..3"):
+        pet_daily(C, 4)
+    with _raises(XH_ERR_ARG, "method must be 0..3"):
+        pet_daily(C, -1)
+    with _raises(XH_ERR_LAYOUT, "xh_pet_daily"):
+        pet_daily(C - 1, 3)
+    with _raises(XH_ERR_ARG, r"method must be 4 \(TW48\) or 5 \(DA02\)"):
+        dev.call("xh_pet_monthly", T, C, C, 3, 0, _vp(x.ptr), _vp(x.ptr), nul, nul, 1, 0, nul, nul, nul, 1, nul, _vp(out.ptr), nul, C)
+    # xh_si_fit / xh_si_apply and the float64 twins: G = 0, a group index >= G, APP without floc, st < C
+    for d in (x, x64):
+        with _raises(XH_ERR_ARG, "bad shape"):
+            K.si_fit(dev, d, group, 0, "gamma", "ML", floc=0.0)
+        with _raises(XH_ERR_ARG, "outside -1..10"):
+            K.si_fit(dev, d, group, 11, "gamma", "ML", floc=0.0)
+        with _raises(XH_ERR_ARG, "APP method needs floc"):
+            K.si_fit(dev, d, group, 12, "gamma", "APP")
+        params = dev.empty((12, 3, C), np.float64)
+        name = "xh_si_fit_f64" if d is x64 else "xh_si_fit"
+        with _raises(XH_ERR_LAYOUT, "time-major"):
+            dev.call(name, _vp(d.ptr), T, C, C - 1, np_ptr(group), 12, 0, 1, 1, 0.0, 0, 0, _vp(params.ptr), nul, nul, nul)
+        with _raises(XH_ERR_ARG, "outside -1..10"):
+            K.si_apply(dev, d, group, dev.empty((11, 3, C), np.float64), "gamma")
+    # the float64 marches: st < C
+    seg = np.array([0, T], np.int64)
+    with _raises(XH_ERR_LAYOUT, "time-major"):
+        dev.call("xh_compare_map_f64", _vp(x64.ptr), T, C, C - 1, 0, 1.0, nul, 0, 0, 0, _vp(out.ptr), C)
+    with _raises(XH_ERR_LAYOUT, "time-major"):
+        dev.call("xh_rolling_reduce_f64", _vp(x64.ptr), T, C, C - 1, 1, 3, 0, 0, _vp(out.ptr), C)
+    with _raises(XH_ERR_LAYOUT, "time-major"):
+        dev.call("xh_thresholded_reduce_f64", _vp(x64.ptr), T, C, C - 1, 1, 0, 1.0, 0, 0, np_ptr(seg), 1, _vp(out.ptr), nul)

@@ -22,20 +22,20 @@ CASES = petcpu.golden_cases()
 METHODS = ("BR65", "HG85", "MB05", "FAO_PM98", "TW48", "DA02")
 
 
-def _device(c, wb=False):
+def _device(dev, c, wb=False):
     f = c["fields"]
-    kw = dict(c["kw"], time=c["time"], method=c["method"], time_of_day=c["time_of_day"])
+    kw = dict(c["kw"], time=c["time"], method=c["method"], time_of_day=c["time_of_day"], device=dev)
     if wb:
         return xc.water_budget(f["pr"], **{k: v for k, v in f.items() if k != "pr"}, lat=c["lat"], **kw)
     return xc.potential_evapotranspiration(**f, lat=c["lat"], **kw)
 
 
 @pytest.mark.parametrize("name", [n for n, _ in CASES])
-def test_device_matches_reference(name):
+def test_device_matches_reference(dev, name):
     c = dict(CASES)[name]
     monthly = xc.METHODS[c["method"]] in ("TW48", "DA02")
     f32, tw48 = c["dtype"] == np.float32, xc.METHODS[c["method"]] == "TW48"
-    got = _device(c)
+    got = _device(dev, c)
     pet = got[0] if monthly else got
     assert pet.dtype == np.float64
     petcpu.close(pet, c["pet"], f32, tw48)
@@ -43,12 +43,12 @@ def test_device_matches_reference(name):
         _, months = got
         assert len(months) == len(c["pet"]) and (months.day == 1).all()
     if "wb" in c:
-        wb = _device(c, wb=True)
+        wb = _device(dev, c, wb=True)
         petcpu.close(wb[0] if monthly else wb, c["wb"], f32, tw48)
     if "ra" in c:
         lat = np.asarray(c["lat"])
-        petcpu.close(xc.extraterrestrial_solar_radiation(c["time"], lat, time_of_day=c["time_of_day"]), c["ra"], False)
-        petcpu.close(xc.day_lengths(c["time"], lat, time_of_day=c["time_of_day"]), c["dl"], False)
+        petcpu.close(xc.extraterrestrial_solar_radiation(c["time"], lat, time_of_day=c["time_of_day"], device=dev), c["ra"], False)
+        petcpu.close(xc.day_lengths(c["time"], lat, time_of_day=c["time_of_day"], device=dev), c["dl"], False)
 
 
 def _grid(seed, T, ny, nx, dtype, start="2001-01-01", calendar="standard"):
@@ -71,13 +71,13 @@ def _grid(seed, T, ny, nx, dtype, start="2001-01-01", calendar="standard"):
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 @pytest.mark.parametrize("method", METHODS)
-def test_device_matches_restatement_on_random_grids(method, dtype):
+def test_device_matches_restatement_on_random_grids(dev, method, dtype):
     t, lat, f = _grid(2 * METHODS.index(method) + (dtype == np.float64), 3 * 365 + 40, 12, 9, dtype, start="2000-02-17")
     use_tas = method in ("HG85", "MB05", "TW48")
     fld = {k: v for k, v in f.items() if k != "tas" or use_tas}
     lat_c = np.broadcast_to(lat, (12, 9)).reshape(-1)
     flat = {k: v.reshape(len(t), -1) for k, v in fld.items()}
-    got = xc.potential_evapotranspiration(**fld, lat=lat, time=t, method=method, time_of_day=12.0)
+    got = xc.potential_evapotranspiration(**fld, lat=lat, time=t, method=method, time_of_day=12.0, device=dev)
     if method in ("TW48", "DA02"):
         exp, _, months = petcpu.pet_monthly(method, t, lat_c, **{k: flat.get(k) for k in ("tasmin", "tasmax", "tas", "pr")})
         got, gm = got
@@ -91,26 +91,26 @@ def test_device_matches_restatement_on_random_grids(method, dtype):
 
 
 @pytest.mark.parametrize("method", ["BR65", "FAO_PM98", "MB05"])
-def test_water_budget_is_pr_minus_pet_bitwise(method):
+def test_water_budget_is_pr_minus_pet_bitwise(dev, method):
     t, lat, f = _grid(7, 400, 6, 5, np.float32)
     pr = f.pop("pr")
-    pet = xc.potential_evapotranspiration(**f, lat=lat, time=t, method=method, keep=True).get()
-    wb = xc.water_budget(pr, **f, lat=lat, time=t, method=method, keep=True).get()
+    pet = xc.potential_evapotranspiration(**f, lat=lat, time=t, method=method, device=dev, keep=True).get()
+    wb = xc.water_budget(pr, **f, lat=lat, time=t, method=method, device=dev, keep=True).get()
     np.testing.assert_array_equal(wb, pr.reshape(len(t), -1).astype(np.float64) - pet)
 
 
-def test_water_budget_tw48_uses_the_monthly_mean_of_pr():
+def test_water_budget_tw48_uses_the_monthly_mean_of_pr(dev):
     t, lat, f = _grid(8, 500, 6, 5, np.float64, start="2001-03-09")
     pr = f.pop("pr")
-    pet, months = xc.potential_evapotranspiration(tas=f["tas"], lat=lat, time=t, method="TW48")
-    wb, _ = xc.water_budget(pr, tas=f["tas"], lat=lat, time=t, method="TW48")
+    pet, months = xc.potential_evapotranspiration(tas=f["tas"], lat=lat, time=t, method="TW48", device=dev)
+    wb, _ = xc.water_budget(pr, tas=f["tas"], lat=lat, time=t, method="TW48", device=dev)
     seg, _ = t.segments("MS")
     prm = np.stack([np.nanmean(pr[a:b], axis=0) for a, b in zip(seg[:-1], seg[1:])])
     np.testing.assert_allclose(wb, prm - pet, rtol=1e-12, atol=1e-20)
     assert len(months) == len(seg) - 1
 
 
-def test_fao_full_year_global_grid():
+def test_fao_full_year_global_grid(dev):
     T, C = 365, 720 * 1440
     rng = np.random.default_rng(11)
     t = TimeAxis.daily("2001-01-01", T)
@@ -121,13 +121,13 @@ def test_fao_full_year_global_grid():
     f = {"tasmin": field(255, 295), "hurs": field(5, 100), "rsds": field(0, 350), "rsus": field(0, 70),
          "rlds": field(230, 380), "rlus": field(300, 460), "sfcWind": field(0, 12)}
     f["tasmax"] = f["tasmin"] + field(1, 15)
-    got = xc.potential_evapotranspiration(**f, time=t, method="FAO_PM98", keep=True).get()
+    got = xc.potential_evapotranspiration(**f, time=t, method="FAO_PM98", device=dev, keep=True).get()
     idx = np.random.default_rng(1).choice(C, 64, replace=False)
     exp = petcpu.pet_daily("FAO_PM98", t, None, **{k: v[:, idx] for k, v in f.items()})[0]
     np.testing.assert_allclose(got[:, idx], exp, rtol=1e-12, atol=1e-12 * np.nanmax(np.abs(exp)))
 
 
-def test_tw48_thirty_years():
+def test_tw48_thirty_years(dev):
     T, ny, nx = 10958, 90, 1440
     C = ny * nx
     rng = np.random.default_rng(12)
@@ -138,7 +138,7 @@ def test_tw48_thirty_years():
     tas = np.empty((T, C), np.float32)
     for i in range(T):
         tas[i] = noise[i % 97] + season[i]
-    got, months = xc.potential_evapotranspiration(tas=tas, lat=lat_c, time=t, method="TW48", keep=True)
+    got, months = xc.potential_evapotranspiration(tas=tas, lat=lat_c, time=t, method="TW48", device=dev, keep=True)
     got = got.get()
     assert got.shape == (360, C) and len(months) == 360
     idx = np.random.default_rng(2).choice(C, 32, replace=False)

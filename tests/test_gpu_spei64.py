@@ -28,13 +28,6 @@ def case(name):
     return {k.split("__", 1)[1]: Z[k] for k in Z.files if k.startswith(name + "__")}, META[name]
 
 
-@pytest.fixture(scope="module")
-def dev():
-    from xclim_amd._capi import get_device
-
-    return get_device(0)
-
-
 @pytest.fixture()
 def native(monkeypatch):
     monkeypatch.setenv("XCLIM_AMD_FLOAT64", "native")
@@ -121,7 +114,7 @@ def test_float64_device_array_outside_native_is_a_type_error(dev, monkeypatch):
     monkeypatch.setenv("XCLIM_AMD_FLOAT64", "round")
     t = TimeAxis.daily("2000-01-01", 730, "noleap")
     with pytest.raises(TypeError, match="must be float32, got float64"):
-        xi.standardized_precipitation_evapotranspiration_index(dev.to_device(np.zeros((730, 3))), t)
+        xi.standardized_precipitation_evapotranspiration_index(dev.to_device(np.zeros((730, 3))), t, device=dev)
 
 
 @pytest.mark.parametrize("name", sorted(META))
@@ -303,7 +296,7 @@ def test_water_budget_to_spei_stays_on_the_device(dev, native):
          "tas": base.astype(np.float32)}
     pr = (np.where(rng.random((T, ny, nx)) < 0.45, rng.gamma(0.8, 7.0, (T, ny, nx)), 0.0) / 86400).astype(np.float32)
     lat = np.linspace(-50, 60, ny)[:, None]
-    wb = xc.water_budget(pr, **f, lat=lat, time=t, method="BR65", keep=True)
+    wb = xc.water_budget(pr, **f, lat=lat, time=t, method="BR65", device=dev, keep=True)
     assert wb.dtype == np.float64 and wb.shape == (T, ny * nx)
     on_dev = xi.standardized_precipitation_evapotranspiration_index(wb, t, window=3, device=dev)
     host = wb.get().reshape(T, ny, nx)

@@ -26,13 +26,6 @@ def case(name):
     return {k.split("__", 1)[1]: Z[k] for k in Z.files if k.startswith(name + "__")}, META[name]
 
 
-@pytest.fixture(scope="module")
-def dev():
-    from xclim_amd._capi import get_device
-
-    return get_device(0)
-
-
 def zero_opts(m):
     interp = {"center": 0.5, "upper": 1.0}.get(m["interp"], m["interp"]) if isinstance(m["interp"], str) else m["interp"]
     ab = {"ecdf": (0, 1), "weibull": (0, 0)}[m["plotting"]] if isinstance(m["plotting"], str) else m["plotting"]

@@ -5,8 +5,11 @@ with g++ against a stand-in for the HIP runtime and run on the CPU:
   * every workgroup as a set of FIBERS (simt.h: __syncthreads, wave-uniform shuffles / votes / readlane, atomics) — f64, select,
     select2, select3, select4, select5, tcount, qdm, qdm2, quantile, doystats, reduce2, pdoy_top, pdoy_quad, pdoy_walk, winsel and the
     kernels of core.hip (transposes, synthetic fields).
-70 of the 100 entry points of include/xclim_hip.h exist in that build: every compute entry point but xh_adapt_freq (rocPRIM); the
-other 30 are runtime services (memory, streams, RCCL).  The register percentile kernels (pdoy_top / pdoy_quad / pdoy_walk) run on
+How many translation units and entry points that build covers is counted once, in tests/hostsim/README.md: every compute entry
+point but xh_adapt_freq (rocPRIM); the rest are runtime services (memory, streams, RCCL).  fire, ffdi, pet, stdidx and f64red run
+thread by thread too (stdidx.hip's k_si_fit keeps a private LDS column per lane), f64run on fibers (k_percentile_doy_f64 sorts in
+LDS by the whole workgroup); their sanitizer run is tests/test_hostsim_sanitize_cpu.py.  The register percentile kernels
+(pdoy_top / pdoy_quad / pdoy_walk) run on
 fibers too, with the four ISA statements of topnet.h rewritten to the C++ they stand for, and so do the register sorting networks
 (select3 / qdm2: the DPP split across the lane pair as a shuffle), select2's wave counts on VCC and the streaming two-pass selection
 of select4.hip (DPP lane exchanges as shuffles, the execution-masked LDS appends as conditional stores, v_readlane from divergent
@@ -32,11 +35,35 @@ def sim(tmp_path_factory):
 
     import subprocess
 
+    import shutil
+
+    if shutil.which("g++") is None:   # (the one reason to skip; a unit that no longer compiles is test_the_simulation_builds's failure)
+        pytest.skip("host simulation not built here: no g++")
     try:
-        path = simdevice.build(str(tmp_path_factory.mktemp("hostsim")))
-    except (RuntimeError, subprocess.CalledProcessError) as e:   # (no g++ / a g++ that does not take the stand-in: not a product failure)
-        pytest.skip(f"host simulation not built here: {e}")
+        path = simdevice.build_shared(str(tmp_path_factory.getbasetemp()))
+    except subprocess.CalledProcessError as e:
+        _BUILD_ERROR.append(e)
+        pytest.skip(f"host simulation not built here (test_the_simulation_builds FAILS for this): {e}")
     return simdevice.SimDevice(path)
+
+
+_BUILD_ERROR = []
+
+
+def test_the_simulation_builds(tmp_path_factory, request):
+    """With g++ present a unit that stops compiling FAILS here — the tests on the `sim` fixture skip, and a whole tier that
+    skips silently is how an unchecked kernel edit gets through.  No g++ stays a skip."""
+    import shutil
+
+    if shutil.which("g++") is None:
+        pytest.skip("no g++")
+    try:
+        request.getfixturevalue("sim")
+    except pytest.skip.Exception:
+        pass
+    if _BUILD_ERROR:
+        e = _BUILD_ERROR[0]
+        pytest.fail(f"the host simulation no longer compiles: {' '.join(map(str, e.cmd))[-400:]}\n{(e.stderr or '')[-2000:]}")
 
 
 @pytest.fixture(scope="module")
@@ -51,6 +78,24 @@ def test_unsimulated_entry_points_raise(sim):
     for name in ("xh_adapt_freq", "xh_comm_allgather"):
         with pytest.raises(NotImplementedError, match="not simulated"):
             getattr(sim.lib, name)
+
+
+def test_the_newest_units_resolve_in_the_simulation(sim):
+    """The 22 entry points of fire, ffdi, pet, stdidx, f64red and f64run, by name, in the library itself (not the mock)."""
+    import ctypes
+
+    from tests.hostsim import simdevice
+
+    assert len(simdevice.NEW_ENTRY_POINTS) == 22
+    dll = ctypes.CDLL(sim.path)
+    for name in ("xh_fire_weather", "xh_overwintering_dc", "xh_mcarthur", "xh_solar_table", "xh_pet_month_table", "xh_pet_daily",
+                 "xh_pet_monthly", "xh_si_fit", "xh_si_apply", "xh_si_fit_f64", "xh_si_apply_f64", "xh_thresholded_reduce_f64",
+                 "xh_range_reduce_f64", "xh_domain_count_f64", "xh_bivariate_count_f64", "xh_rolling_reduce_f64",
+                 "xh_compare_map_f64", "xh_run_stats_f64", "xh_spell_mask_f64", "xh_spell_run_stats_f64", "xh_run_stats_doy_f64",
+                 "xh_percentile_doy_f64"):
+        assert name in simdevice.NEW_ENTRY_POINTS
+        assert hasattr(dll, name), name
+        assert getattr(sim.lib, name) is not None
 
 
 def test_detrend_pieces(sim):
@@ -159,6 +204,52 @@ def _child_run(sim, files, skip="nothing_is_skipped", deselect=(), at_least=1):
     assert res.returncode == 0, res.stdout[-3000:]
     assert " passed" in tail and "failed" not in tail, tail
     assert int(tail.split(" passed")[0].split()[-1]) >= at_least, tail
+
+
+# What the child run of the newest units leaves out, test by test, and why.
+NEW_UNITS_DESELECTED = {
+    # too slow on a CPU (full-size grids, decades of days: seconds on the device, minutes here)
+    "tests/test_gpu_fire.py::test_fuzz_ten_years": "too slow: 3650 x 2000 cells",
+    "tests/test_gpu_fire.py::test_full_size_sampled": "too slow: full-size grid",
+    "tests/test_gpu_ffdi.py::test_30_years_1440x90_chain_against_restatement": "too slow: 30 years x 129 600 cells",
+    "tests/test_gpu_pet.py::test_fao_full_year_global_grid": "too slow: 365 x 1 036 800 cells",
+    "tests/test_gpu_pet.py::test_tw48_thirty_years": "too slow: 30 years x 129 600 cells",
+    "tests/test_gpu_stdidx.py::test_full_grid_monthly_spi3": "too slow: 1440 x 720 cells",
+    "tests/test_gpu_spei64.py::test_full_grid_monthly_spei3": "too slow: 1440 x 720 cells",
+    # (23 years x 333 cells of Nelder-Mead fits; they pass here; the closed-form [gamma-0.0-True] sets of both modules run, 1 s)
+    "tests/test_gpu_stdidx.py::test_random_grid_against_scipy[fisk-None-False]": "too slow: 20 s",
+    "tests/test_gpu_stdidx.py::test_random_grid_against_scipy[gamma-None-True]": "too slow: 10 s",
+    "tests/test_gpu_spei64.py::test_random_grid_against_scipy[fisk-None-False]": "too slow: 16 s",
+    "tests/test_gpu_spei64.py::test_random_grid_against_scipy[gamma-None-False]": "too slow: 9 s",
+    "tests/test_gpu_f64_native.py::test_float64_marches_on_grids_of_several_workgroups":
+        "too slow: 20 s per grid, 365 workgroups of k_percentile_doy_f64 on fibers for 1200 cells; the same calls run on 2 to 1021 "
+        "cells in tests/test_gpu_edges_new_units.py, which IS in this child run",
+    "tests/test_gpu_f64_native.py::test_percentile_doy_in_float64[ab0-31-noleap]": "too slow: 6 s each; [ab1-31-standard] runs",
+    "tests/test_gpu_f64_native.py::test_percentile_doy_in_float64[ab0-31-standard]": "too slow: 6 s each; [ab1-31-standard] runs",
+    "tests/test_gpu_f64_native.py::test_percentile_doy_in_float64[ab1-31-noleap]": "too slow: 6 s each; [ab1-31-standard] runs",
+    # A finding about host libm, not about the kernel.  Cell 0, group 17 of this golden case is a 3-parameter gamma fit of THREE
+    # values (0.7667, 0.7, 0.8333): it has no maximum, and the walk ends on the ridge towards the normal limit at shape 1.9e12,
+    # loc -7.5e4, scale 3.9e-8 after 329 evaluations.  The simulation's parameters agree with the golden ones to 1e-5 (so
+    # test_golden_fit_and_index passes on it, in both stagings), but at that shape the cdf is a difference of numbers 1e12 apart
+    # and a 1e-6 change of the parameters moves the index by several 1e-2: golden 0.0007, simulation 0.064, restatement
+    # (tests/spicpu.py) -0.0056 at 3 rows, beyond this test's 2e-2 for every value.  Demonstrated with the restatement: math.log
+    # moved by ONE ulp takes the same sample's fit from loc -74560.69 to -74574.30 (up) / -74563.02 (down), shape 1.889e12 to
+    # 1.877e12 / 1.864e12, and the index of its first value from -0.0056 to -0.0122
+    # (tests/test_stdidx_cpu.py::test_one_ulp_of_log_moves_the_walk_of_a_three_value_gamma_fit reproduces it; the one-ulp experiment
+    # in assert_params_close's docstring is about the fits that stop at the 600-evaluation budget).  glibc's log / lgamma differ from the
+    # device's in the last bit, which is all this walk needs.  The float64 twin of the case (test_gpu_spei64.py) passes here.
+    "tests/test_gpu_stdidx.py::test_golden_host_mirror[gamma_ml_daily_w3]":
+        "host libm: a last-bit difference in log moves the Nelder-Mead walk of one degenerate 3-value fit (see above)",
+}
+
+
+def test_the_newest_units_modules_on_the_simulation(sim):
+    """fire.hip, ffdi.hip, pet.hip, stdidx.hip, f64red.hip, f64run.hip: the whole GPU modules of these units — the golden cases of
+    the reference (the golden fits in all their stagings), the restatements on random grids, the adapters — and their edge-shape
+    file, on the simulation.  NEW_UNITS_DESELECTED names every test left out and says why."""
+    _child_run(sim, ["tests/test_gpu_fire.py", "tests/test_gpu_ffdi.py", "tests/test_gpu_pet.py", "tests/test_gpu_stdidx.py",
+                     "tests/test_gpu_spei64.py", "tests/test_gpu_f64_native.py", "tests/test_gpu_f64_native_reductions.py",
+                     "tests/test_gpu_edges_new_units.py"], deselect=sorted(NEW_UNITS_DESELECTED), at_least=381)
 
 
 def test_whole_gpu_modules_on_the_simulation(sim):

@@ -225,8 +225,14 @@ def _run(method, fields, time, lat, outputs, peta, petb, time_of_day, device, ke
     _check_time(time)
     if m == "DA02" and "wb" in outputs:  # converters.py:2718-2730 calls PET without pr, which DA02 needs
         raise NotServed("water_budget with DA02: the reference does not hand pr to potential_evapotranspiration")
-    lat_u, li = _lat_table(lat, cell_shape) if m != "FAO_PM98" else (None, None)
     C_ = int(np.prod(cell_shape, dtype=np.int64))
+    if C_ == 0 and m != "FAO_PM98":  # an empty grid: latitudes of no cell make no table for the kernels (FAO_PM98 has none and launches)
+        months = None if m in K.PET_DAILY else _months(time)[1]
+        rows = T if months is None else len(months)
+        if keep:
+            return {n: (device or get_device()).empty((rows, 0), np.float64) for n in outputs}, months
+        return {n: np.empty((rows,) + tuple(cell_shape), np.float64) for n in outputs}, months
+    lat_u, li = _lat_table(lat, cell_shape) if m != "FAO_PM98" else (None, None)
     dev = device or get_device()
     d = {n: a.reshape(T, C_) if isinstance(a, DeviceArray) else dev.to_device(np.ascontiguousarray(a).reshape(T, C_))
          for n, a in got.items()}

@@ -784,6 +784,38 @@ int xh_mcarthur(xh_ctx* ctx, int64_t T, int64_t C, int64_t st, int pr_f64, int t
                 const double* pr_annual, const double* kbdi0, int lim, const double* n13 /* host */, double* kbdi_out,
                 double* df_out, double* ffdi_out, int64_t st_out);
 
+/* ---- winter chill: chill portions, chill units, hourly temperatures (indices/_agro.py, indices/helpers.py) ------ */
+/* xh_chill_hourly: the Dynamic Model of _chill_portion_one_season with _accumulate_intermediate (_agro.py:1436-1465) and the
+ *   Utah weights of chill_units (:1574-1592), one lane per (cell, period), float64 arithmetic in the reference's order.
+ *   tas (H, C) with row stride ld (DEVICE), float32 (f64 = 0) or float64, day-major: rows_per_day (24) rows per calendar day
+ *   from row 0.  seg (DEVICE int64, P + 1): first row of each period, non-decreasing within [0, H]; every period restarts
+ *   at E = 0.  row_sel (DEVICE uint8, H; NULL = every row): an unselected row is SKIPPED, not reset (select_time with
+ *   drop=True): the state carries across the gap inside a period.  The Dynamic Model sees tas + add_K [K], the Utah model
+ *   tas - sub_C [degC], subtracted and compared in the field's dtype as numpy does; one of the two offsets is 0.
+ *   positive_only: the Utah weights are summed per calendar day and only days with a sum > 0 are added (:1589-1591).
+ *   Outputs (DEVICE, row stride ld_out, NULL = not written): cp_out (P, C) float64, the sum of delta; cu_out (P, C)
+ *   float64 (0 for a period without data); valid_out (P, C) int32, the selected rows whose temperature is not NaN;
+ *   delta_out (H, C) float64, what _chill_portion_one_season returns: 0 on unselected rows, on the first selected row of a
+ *   period and wherever E is NaN (from a NaN temperature to the end of its period); rows outside [seg[0], seg[P]) are
+ *   not written.  At least one output; at most 65535 periods. */
+int xh_chill_hourly(xh_ctx* ctx, int64_t H, int64_t C, int64_t ld, int f64, const void* tas, int rows_per_day, int64_t P,
+                    const int64_t* seg, const uint8_t* row_sel, double add_K, double sub_C, int positive_only, double* cp_out,
+                    double* cu_out, int32_t* valid_out, double* delta_out, int64_t ld_out);
+/* xh_chill_daily: make_hourly_temperature (helpers.py:1059-1123 with _compute_daytime_temperature :977-1004 and
+ *   _compute_nighttime_temperature :1007-1035, no infill) fused with the hour step of xh_chill_hourly: the 24 hourly
+ *   temperatures of a day are built in registers and fed to the same step function.  tasmin, tasmax (D, C) with row stride
+ *   ld (DEVICE), both float32 (f64 = 0) or both float64; tasmax - tasmin is taken in that dtype, everything after it is
+ *   float64.  dl (DEVICE float64 (D, L)) from xh_solar_table, lat_idx (DEVICE int32, C): column of each cell's latitude.  The
+ *   night of a day runs to the NEXT day's tasmin, the last day's to its own; a NaN day length (polar day or night) gives
+ *   NaN hours.  seg (DEVICE int64, P + 1) in DAY offsets, day_sel (DEVICE uint8, D; NULL = every day), add_K, sub_C,
+ *   positive_only and cp_out / cu_out / valid_out as xh_chill_hourly (the Utah comparisons are float64 here, as on the
+ *   float64 hourly field).  hourly_out (DEVICE float64 (24 D, C), row stride ld_out, may be NULL): make_hourly_temperature
+ *   itself, in the inputs' units, for every day of [seg[0], seg[P]), selected or not.  At least one output. */
+int xh_chill_daily(xh_ctx* ctx, int64_t D, int64_t C, int64_t ld, int f64, const void* tasmin, const void* tasmax,
+                   const double* dl, int64_t L, const int32_t* lat_idx, int64_t P, const int64_t* seg, const uint8_t* day_sel,
+                   double add_K, double sub_C, int positive_only, double* cp_out, double* cu_out, int32_t* valid_out,
+                   double* hourly_out, int64_t ld_out);
+
 /* ---- standardized indices: SPI / SPEI (indices/stats.py) --------------------------------------------------------- */
 /* xh_si_fit: the per-group fits of standardized_index_fit_params (stats.py:855-964) through _fitfunc_1d (:40-113) and
  *   _fit_start (:576-684), one lane per (cell, group), float64.  x (T, C) float32 with row stride st (DEVICE): the

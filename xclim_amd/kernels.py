@@ -1208,6 +1208,76 @@ def mcarthur(dev: Device, fields: dict, pr_annual: DeviceArray | None = None, kb
     return outs
 
 
+CHILL_OUTPUTS = ("cp", "cu", "valid")
+
+
+def _chill_common(dev, who, rows, seg, sel, outputs, allowed):
+    outputs = [o for o in allowed if o in set(outputs)]
+    if not outputs:
+        raise ValueError(f"{who}: outputs must be a non-empty subset of {', '.join(allowed)}")
+    s = np.ascontiguousarray(seg, dtype=np.int64)
+    if s.ndim != 1 or len(s) < 1 or s[0] < 0 or s[-1] > rows or np.any(np.diff(s) < 0):
+        raise ValueError(f"{who}: period offsets must be non-decreasing within [0, {rows}]")
+    if len(s) - 1 > 65535:
+        raise ValueError(f"{who}: at most 65535 periods, got {len(s) - 1}")
+    d_sel = None
+    if sel is not None:
+        m = np.ascontiguousarray(sel)
+        if m.shape != (rows,) or m.dtype not in (np.dtype(bool), np.dtype(np.uint8)):
+            raise ValueError(f"{who}: the selection must be a bool or uint8 array of length {rows}")
+        d_sel = dev.to_device(m.astype(np.uint8))
+    return outputs, s, d_sel
+
+
+def chill_hourly(dev: Device, tas: DeviceArray, seg, row_sel=None, *, add_K: float = 0.0, sub_C: float = 273.15,
+                 positive_only: bool = False, outputs=("cp",), rows_per_day: int = 24) -> dict:
+    """xh_chill_hourly.  ``tas`` (H, C) float32 or float64 DeviceArray, day-major hourly rows; ``seg`` (P + 1) host ROW
+    offsets of the periods; ``row_sel`` host bool / uint8 (H) or None.  ``outputs``: a subset of cp, cu, valid ((P, C);
+    float64, float64, int32) and delta ((H, C) float64).  Returns ``{name: DeviceArray}``."""
+    if np.dtype(tas.dtype) not in (np.float32, np.float64):
+        raise TypeError(f"chill_hourly: tas must be float32 or float64, got {np.dtype(tas.dtype).name}")
+    H, C_ = _tc(tas, None)
+    outputs, s, d_sel = _chill_common(dev, "chill_hourly", H, seg, row_sel, outputs, CHILL_OUTPUTS + ("delta",))
+    P = len(s) - 1
+    outs = {o: dev.empty((H, C_) if o == "delta" else (P, C_), np.int32 if o == "valid" else np.float64) for o in outputs}
+    if "delta" in outs and (s[0] != 0 or s[-1] != H):
+        raise ValueError("chill_hourly: delta needs periods that cover every row")
+    optr = lambda n: _vp(outs[n].ptr) if n in outs else _vp(0)  # noqa: E731
+    d_s = dev.to_device(s)  # held until the launch is enqueued: a freed buffer goes back to the pool
+    dev.call("xh_chill_hourly", H, C_, C_, int(np.dtype(tas.dtype) == np.float64), _vp(tas.ptr), int(rows_per_day), P,
+             _vp(d_s.ptr), _vp(d_sel.ptr) if d_sel is not None else _vp(0), float(add_K), float(sub_C), int(bool(positive_only)),
+             optr("cp"), optr("cu"), optr("valid"), optr("delta"), C_)
+    return outs
+
+
+def chill_daily(dev: Device, tasmin: DeviceArray, tasmax: DeviceArray, dl: DeviceArray, lat_idx, seg, day_sel=None, *,
+                add_K: float = 0.0, sub_C: float = 273.15, positive_only: bool = False, outputs=("cp",)) -> dict:
+    """xh_chill_daily.  ``tasmin`` / ``tasmax`` (D, C) DeviceArrays, both float32 or both float64; ``dl`` (D, L) float64 from
+    :func:`pet_solar_table` and ``lat_idx`` (C) host indices into its columns; ``seg`` (P + 1) host DAY offsets; ``day_sel``
+    host bool / uint8 (D) or None.  ``outputs``: a subset of cp, cu, valid ((P, C)) and hourly ((24 D, C) float64, the
+    hourly temperatures).  Returns ``{name: DeviceArray}``."""
+    if np.dtype(tasmin.dtype) not in (np.float32, np.float64) or np.dtype(tasmax.dtype) != np.dtype(tasmin.dtype):
+        raise TypeError("chill_daily: tasmin and tasmax must be both float32 or both float64")
+    D, C_ = _tc(tasmin, None)
+    if _tc(tasmax, None) != (D, C_):
+        raise ValueError("chill_daily: tasmin and tasmax must have the same (D, C) shape")
+    D2, L = _tc(dl, np.float64)
+    if D2 != D:
+        raise ValueError(f"chill_daily: the day-length table has {D2} rows for {D} days")
+    outputs, s, d_sel = _chill_common(dev, "chill_daily", D, seg, day_sel, outputs, CHILL_OUTPUTS + ("hourly",))
+    P = len(s) - 1
+    if "hourly" in outputs and (s[0] != 0 or s[-1] != D):
+        raise ValueError("chill_daily: hourly needs periods that cover every day")
+    d_li = _pet_lat_idx(dev, lat_idx, C_, L)
+    outs = {o: dev.empty((24 * D, C_) if o == "hourly" else (P, C_), np.int32 if o == "valid" else np.float64) for o in outputs}
+    optr = lambda n: _vp(outs[n].ptr) if n in outs else _vp(0)  # noqa: E731
+    d_s = dev.to_device(s)
+    dev.call("xh_chill_daily", D, C_, C_, int(np.dtype(tasmin.dtype) == np.float64), _vp(tasmin.ptr), _vp(tasmax.ptr),
+             _vp(dl.ptr), L, _vp(d_li.ptr), P, _vp(d_s.ptr), _vp(d_sel.ptr) if d_sel is not None else _vp(0), float(add_K),
+             float(sub_C), int(bool(positive_only)), optr("cp"), optr("cu"), optr("valid"), optr("hourly"), C_)
+    return outs
+
+
 SI_DISTS = {"gamma": 0, "fisk": 1}
 SI_METHODS = {"APP": 0, "ML": 1}
 SI_STAGING = {"auto": 0, "global": 1, "lds": 2}

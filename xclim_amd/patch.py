@@ -109,6 +109,8 @@ _FIRE_MODULE = "xclim.indices.fire._cffwis"
 _FIRE_NAMES = ("_fire_weather_calc", "_fire_season")
 _FFDI_MODULE = "xclim.indices.fire._ffdi"
 _FFDI_NAMES = ("_keetch_byram_drought_index", "_griffiths_drought_factor")
+_CHILL_MODULE = "xclim.indices._agro"
+_CHILL_NAME = "_chill_portion_one_season"  # indices/_agro.py:1442-1465, called by name at :1473
 # PET and the water budget: water_budget calls potential_evapotranspiration by module-global name (converters.py:2718); the
 # three indicators hold the function objects as a staticmethod ``compute`` on their classes (core/indicator.py:515-517,
 # indicators/convert/_conversion.py:418-470)
@@ -243,6 +245,14 @@ def install(env=None, modules=None) -> list[str]:
         ffdi = ffdi_adapters(*(_saved.get((_FFDI_MODULE, n), getattr(dmod, n)) for n in _FFDI_NAMES))
         for name in _FFDI_NAMES:
             patch(_FFDI_MODULE, name, ffdi[name])
+    # chill portions: chill_portions reaches _chill_portion_one_season by module-global name inside xr.apply_ufunc (through
+    # resample_map); chill_units and make_hourly_temperature are xarray expressions and stay xclim's
+    amod = resolve(_CHILL_MODULE)
+    if amod is not None and hasattr(amod, _CHILL_NAME):
+        from .chill import make_adapters as chill_adapters
+
+        orig_chill = _saved.get((_CHILL_MODULE, _CHILL_NAME), getattr(amod, _CHILL_NAME))
+        patch(_CHILL_MODULE, _CHILL_NAME, chill_adapters(orig_chill)[_CHILL_NAME])
     cmod = resolve(_PET_MODULE)
     if cmod is not None and all(hasattr(cmod, n) for n in _PET_NAMES):
         from .converters import make_adapters as pet_adapters

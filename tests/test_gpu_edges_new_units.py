@@ -8,13 +8,14 @@ import numpy as np
 import pytest
 
 import newunit_cases as nc
+from refusals import raises as _raises
 from xclim_amd import kernels as K
-from xclim_amd._capi import XH_ERR_ARG, XH_ERR_LAYOUT, XclimHipError, _vp, np_ptr
+from xclim_amd._capi import XH_ERR_ARG, XH_ERR_LAYOUT, _vp, np_ptr
 
 pytestmark = pytest.mark.gpu
 
 GRIDS = [(0,), (1,), (3,), (5, 1), (257,), (1021,)]
-# float64 marches: two cells per lane needs an even row width (f64util.h: pick_vec), an odd one takes one cell per lane
+# float64 marches: two cells per lane needs an even row width (hostargs.h: xh_pick_vec64), an odd one takes one cell per lane
 F64_GRIDS = GRIDS + [(2,), (130,), (131,)]
 ids = lambda s: "x".join(map(str, s))  # noqa: E731
 
@@ -138,21 +139,6 @@ def test_fire_weather_all_nan_field(dev, mode):
 
 
 # ---- the launchers' argument checks: each must answer with its error code, before anything is launched -------------------
-def _raises(code, match):
-    class Ctx:
-        def __enter__(self):
-            self.cm = pytest.raises(XclimHipError, match=match)
-            self.info = self.cm.__enter__()
-            return self
-
-        def __exit__(self, *exc):
-            done = self.cm.__exit__(*exc)
-            assert self.info.value.code == code, self.info.value
-            return done
-
-    return Ctx()
-
-
 def test_launchers_refuse_bad_arguments(dev):
     T, C = 24, 4
     rng = np.random.default_rng(1)

@@ -1,0 +1,124 @@
+"""The argument checks of the older streaming entry points (reduce, reduce2, elemwise, runlen, spell, f64): every bad argument
+is answered with its error code on the host, before anything is uploaded or launched, and the context serves a valid call
+afterwards.  Only null pointers and valid device buffers are passed, so a check that let a case through would still read and
+write in bounds.  The table records what each entry point answers; tests/test_gpu_edges_new_units.py does the same for the
+newest units.  Re-run on the host simulation by tests/test_hostsim_cpu.py."""
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from refusals import raises  # noqa: E402
+from xclim_amd._capi import XH_ERR_ARG, XH_ERR_LAYOUT, _vp, np_ptr  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+T, C, D = 24, 4, 12
+NUL = _vp(0)
+
+# The arguments after the context, in order: a "$name" is looked up in the case's values, anything else is passed as it is.
+# $x / $x2 float32 fields, $x64 a float64 field, $tab the (D, C) float64 table, $dtidx the day-of-year index on the device and
+# $tidx on the host, $seg the host segment table, $cnt (P, C) int32, $out / $out64 (T, C) outputs, $lo / $hi host int32[P].
+ENTRY_POINTS = {
+    "xh_threshold_count": ["$x", "$T", C, "$st", "$sc", "$op", 1, 1.0, NUL, 0, NUL, "$seg", "$P", "$cnt", NUL],
+    "xh_threshold_count_doy": ["$x", "$T", C, "$st", "$sc", "$op", "$tab", C, D, "$dtidx", "$seg", "$P", "$cnt", NUL],
+    "xh_domain_count": ["$x", "$T", C, "$st", "$sc", "$op", 1.0, 1, 5.0, 1, "$seg", "$P", "$cnt", NUL],
+    "xh_resample_reduce": ["$x", "$T", C, "$st", "$sc", "$red", 1, "$seg", "$P", "$out", NUL],
+    "xh_rolling_reduce": ["$x", "$T", C, "$st", "$sc", 3, 0, "$red", "$out", "$out_st"],
+    "xh_cumsum_reset": ["$x", "$T", C, "$st", "$sc", 0, "$out", "$out_st"],
+    "xh_rle": ["$x", "$T", C, "$st", "$sc", 0, "$out", "$out_st"],
+    "xh_run_stats": ["$x", "$T", C, "$st", "$sc", "$op", 1.0, 1, "$stat", 0, "$seg", "$P", 1, "$out", NUL],
+    "xh_run_stats_doy": ["$x", "$T", C, "$st", "$sc", "$op", "$tab", D, "$tidx", 1, "$stat", "$seg", "$P", "$out", NUL],
+    "xh_range_reduce": ["$x", "$x2", "$T", C, "$st", C, 0, "$red", "$seg", "$P", "$out", NUL],
+    "xh_bivariate_count": ["$x", "$x2", "$T", C, "$st", C, "$op", 1.0, 1, 5.0, 1, "$seg", "$P", "$cnt", NUL],
+    "xh_thresholded_reduce": ["$x", "$T", C, "$st", "$sc", "$op", 1.0, 0, "$red", "$seg", "$P", "$out", NUL],
+    "xh_spell_mask": ["$x", "$T", C, "$st", "$sc", 3, "$red", "$op", 1.0, NUL, "$out", "$out_st"],
+    "xh_spell_run_stats": ["$x", "$T", C, "$st", "$sc", 3, 0, "$op", 1.0, NUL, "$stat", "$seg", "$P", "$out", NUL],
+    "xh_compare_doy": ["$x", "$T", C, "$st", "$sc", "$op", "$tab", D, "$tidx", "$out", "$out_st"],
+    "xh_mask_rows": ["$x", "$T", C, "$st", "$sc", "$seg", "$P", "$lo", "$hi", 0, "$out", "$out_st"],
+    "xh_season": ["$x", "$T", C, "$st", "$sc", 3, "$seg", NUL, "$P", "$out", "$out2", "$out3"],
+    "xh_max_run_sum": ["$x", "$T", C, "$st", "$sc", 1, "$seg", "$P", 1, "$out"],
+    "xh_keep_longest_run": ["$x", "$T", C, "$st", "$sc", "$seg", "$P", "$out", "$out_st"],
+    "xh_threshold_count_f64": ["$x64", "$T", C, "$st", "$sc", "$op", 1, 1.0, NUL, 0, NUL, "$seg", "$P", "$cnt", NUL],
+    "xh_resample_reduce_f64": ["$x64", "$T", C, "$st", "$sc", "$red", 1, "$seg", "$P", "$out64", NUL],
+    "xh_nan_quantile_f64": ["$x64", "$T", C, "$st", "$sc", "$q", 3, 1.0, 1.0, "$out64"],
+}
+
+# case -> (the values it changes, the expected code; None: XH_ERR_OP, a ValueError through Device.call).  A case applies to an
+# entry point when every name it changes is one of the entry point's arguments.
+SEG_CASES = {"seg NULL": {"seg": None}, "P = 0": {"P": 0}, "seg decreasing": {"seg": [0, 10, 5], "P": 2},
+             "seg beyond T": {"seg": [0, T + 1]}, "seg negative": {"seg": [-1, T]}}
+CASES = {
+    "field NULL": ({"x": 0}, XH_ERR_ARG), "field64 NULL": ({"x64": 0}, XH_ERR_ARG), "T = -1": ({"T": -1}, XH_ERR_ARG),
+    "sc = 2": ({"sc": 2}, XH_ERR_LAYOUT), "st = C - 1": ({"st": C - 1}, XH_ERR_LAYOUT),
+    "out NULL": ({"out": 0}, XH_ERR_ARG), "out64 NULL": ({"out64": 0}, XH_ERR_ARG), "cnt NULL": ({"cnt": 0}, XH_ERR_ARG),
+    "out_st = C - 1": ({"out_st": C - 1}, XH_ERR_LAYOUT),
+    **{k: (v, XH_ERR_ARG) for k, v in SEG_CASES.items()},
+    "tidx = D": ({"tidx": D}, XH_ERR_ARG),
+    "op = 6": ({"op": 6}, None), "unknown reducer": ({"red": 99}, None), "unknown statistic": ({"stat": 99}, None),
+}
+
+
+@pytest.fixture(scope="module")
+def values(dev):
+    rng = np.random.default_rng(3)
+    x = rng.gamma(2.0, 1.5, (T, C)).astype(np.float32)
+    v = {"x": dev.to_device(x), "x2": dev.to_device(x + 1.0), "x64": dev.to_device(x.astype(np.float64)),
+         "tab": dev.to_device(rng.gamma(2.0, 1.5, (D, C))), "dtidx": dev.to_device((np.arange(T) % D).astype(np.int32)),
+         "cnt": dev.empty((T, C), np.int32), "out": dev.empty((T, C), np.float32), "out2": dev.empty((T, C), np.float32),
+         "out3": dev.empty((T, C), np.float32), "out64": dev.empty((T, C), np.float64)}
+    return v
+
+
+def _args(spec, v, change):
+    val = {"T": T, "st": C, "sc": 1, "out_st": C, "P": 1, "op": 0, "red": 0, "stat": 0, "seg": [0, T],
+           "tidx": None, "lo": np.zeros(2, np.int32), "hi": np.full(2, 5, np.int32), "q": np.array([0.1, 0.5, 0.9]), **change}
+    keep = []   # (host arrays must outlive the call)
+    out = []
+    for a in spec:
+        if not (isinstance(a, str) and a.startswith("$")):
+            out.append(a)
+            continue
+        name = a[1:]
+        w = val.get(name, v.get(name))
+        if name == "seg":
+            w = None if w is None else np.asarray(w, np.int64)
+        if name == "tidx":
+            w = (np.arange(T) % D).astype(np.int32)
+            if val["tidx"] is not None:
+                w[T // 2] = val["tidx"]
+        if isinstance(w, np.ndarray):
+            keep.append(w)
+            w = np_ptr(w)
+        elif w is None or (name in v and w == 0):
+            w = NUL
+        elif name in v:
+            w = _vp(w.ptr)
+        out.append(w)
+    return out, keep
+
+
+@pytest.mark.parametrize("name", sorted(ENTRY_POINTS))
+def test_entry_point_refuses_bad_arguments(dev, values, name):
+    spec = ENTRY_POINTS[name]
+    names = {a[1:] for a in spec if isinstance(a, str) and a.startswith("$")}
+    ran = 0
+    for case, (change, code) in CASES.items():
+        if not set(change) <= names:
+            continue
+        args, keep = _args(spec, values, change)
+        if code is None:
+            with pytest.raises(ValueError):
+                dev.call(name, *args)
+        else:
+            with raises(code, name.replace("_count_doy", "_count")):   # (the two threshold counts share their checks)
+                dev.call(name, *args)
+        ran += 1
+    assert ran >= 4, (name, ran)
+    # the context is as good as before: the same call with valid arguments runs
+    args, keep = _args(spec, values, {})
+    dev.call(name, *args)
+    dev.sync()

@@ -261,7 +261,8 @@ def test_whole_gpu_modules_on_the_simulation(sim):
     skip = ("qdm or eqm or dqm or sdba or bootstrap or adapt or add_dims or sub_groupings or exceedance_fused or "
             "beyond or grouped or plane or quantile_cells or tx90p_on_a_float64 or refused_elsewhere")
     _child_run(sim, ["tests/test_gpu_edges.py", "tests/test_gpu_patch.py", "tests/test_gpu_api.py", "tests/test_gpu_spells.py",
-                     "tests/test_gpu_f64.py", "tests/test_gpu_adapter.py", "tests/test_gpu_blocks.py"], skip, at_least=270,
+                     "tests/test_gpu_f64.py", "tests/test_gpu_adapter.py", "tests/test_gpu_blocks.py", "tests/test_gpu_refusals.py"],
+               skip, at_least=292,
                # (the device-resident input cache is the real Device's; the simulation's buffers are host memory)
                deselect=["tests/test_gpu_adapter.py::test_inputs_and_tables_stay_on_the_device_across_wrapper_calls"])
 

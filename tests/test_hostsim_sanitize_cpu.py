@@ -10,7 +10,7 @@ case must end with exit status 0 and no sanitizer report, and the dumped outputs
 restatements (ffdicpu, petcpu, spicpu, firecpu, oracle) at the GPU tests' tolerances: a clean run with wrong numbers fails.
 
 Row widths 1, 2, 3, 63, 65, 130, 257 (and 131 for the float64 marches: two cells per lane on even widths, one on odd ones —
-f64util.h's pick_vec — each with an odd tail); k_percentile_doy_f64 runs on ucontext fibers that are announced to ASan
+hostargs.h's xh_pick_vec64 — each with an odd tail); k_percentile_doy_f64 runs on ucontext fibers that are announced to ASan
 (simt.h), so every kernel of the six units gets both sanitizers.  Run plainly (one process): the last test reads what the
 others replayed."""
 import shutil

@@ -365,9 +365,3 @@ __device__ __forceinline__ double xh_div_int(double s, double n, double inv) {
 
 __device__ __forceinline__ double xh_nan64() { return __longlong_as_double(0x7FF8000000000000LL); }
 __device__ __forceinline__ float xh_nan32() { return __uint_as_float(0x7FC00000u); }
-
-// choose cells-per-lane: 4 when rows are 16-byte aligned, else 1
-static inline int xh_pick_vec(const void* p, int64_t C, int64_t st) {
-  if ((reinterpret_cast<uintptr_t>(p) & 15) == 0 && (C % 4) == 0 && (st % 4) == 0) return 4;
-  return 1;
-}

@@ -8,6 +8,7 @@
 //                   (p1 NULL: the scaling / normalisation of dqm_train) or with the trend (detrend / retrend)
 // Both stream the time-major (T, C) field once: a lane owns VEC cells and marches along time.
 #include "common.h"
+#include "hostargs.h"
 
 namespace {
 

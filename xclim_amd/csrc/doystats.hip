@@ -9,6 +9,7 @@
 // for irregular doys (calendar gaps).
 #include <stdlib.h>
 
+#include "hostargs.h"
 #include "pdoy.h"
 
 namespace {
@@ -204,31 +205,26 @@ int xh_launch_doy_stats_sets(xh_ctx* ctx, const float* x, int64_t T, int64_t C, 
     if (gy < 1) gy = 1;
     const int ychunk = (int)cdiv64(ndoy, gy);
     const dim3 ygrid((unsigned)cblocks, (unsigned)cdiv64(ndoy, ychunk));
-#define XH_DY(W, V) \
-  hipLaunchKernelGGL((k_doy_stats_year<W, V>), ygrid, dim3(XH_BLOCK), 0, ctx->stream, x, T, C, st, year_t0, ndoy, ychunk, d_reg, mean_out, std_out)
-    if (vec == 4) { if (window == 3) XH_DY(3, 4); else if (window == 5) XH_DY(5, 4); else XH_DY(7, 4); }
-    else { if (window == 3) XH_DY(3, 1); else if (window == 5) XH_DY(5, 1); else XH_DY(7, 1); }
-#undef XH_DY
+    xh_pick<3, 5, 7>(window, [&](auto W) {
+      xh_pick<4, 1>(vec, [&](auto V) {
+        hipLaunchKernelGGL((k_doy_stats_year<decltype(W)::value, decltype(V)::value>), ygrid, dim3(XH_BLOCK), 0, ctx->stream, x, T, C,
+                           st, year_t0, ndoy, ychunk, d_reg, mean_out, std_out);
+      });
+    });
     XH_LAUNCH_CHECK();
     return XH_OK;
   }
   int chunk = 24;
   if (const char* e = xh_diag_env("XH_DOYSTATS_CHUNK")) chunk = atoi(e) > 0 ? atoi(e) : chunk;  // diagnostics
   const dim3 grid((unsigned)cdiv64(C, 64), (unsigned)((ndoy + chunk - 1) / chunk));
-#define XH_DS(W, NY)                                                                                                     \
-  hipLaunchKernelGGL((k_doy_stats_sets<W, NY>), grid, dim3(64), 0, ctx->stream, x, T, C, st, d_tb, nyears, ndoy, chunk, d_reg, \
-                     mean_out, std_out)
-#define XH_DSW(NY)                                                                   \
-  do {                                                                               \
-    if (window == 3) XH_DS(3, NY); else if (window == 5) XH_DS(5, NY); else XH_DS(7, NY); \
-  } while (0)
-  if (nyears == 1) XH_DSW(1);  // (one sample per day-set: no padded second slot to gather and mask)
-  else if (nyears <= 2) XH_DSW(2);
-  else if (nyears <= 8) XH_DSW(8);
-  else if (nyears <= 32) XH_DSW(32);
-  else XH_DSW(64);
-#undef XH_DSW
-#undef XH_DS
+  // samples per day-set the kernel is compiled for (1: no padded second slot to gather and mask)
+  const int ny = nyears == 1 ? 1 : nyears <= 2 ? 2 : nyears <= 8 ? 8 : nyears <= 32 ? 32 : 64;
+  xh_pick<3, 5, 7>(window, [&](auto W) {
+    xh_pick<1, 2, 8, 32, 64>(ny, [&](auto NY) {
+      hipLaunchKernelGGL((k_doy_stats_sets<decltype(W)::value, decltype(NY)::value>), grid, dim3(64), 0, ctx->stream, x, T, C, st, d_tb,
+                         nyears, ndoy, chunk, d_reg, mean_out, std_out);
+    });
+  });
   XH_LAUNCH_CHECK();
   return XH_OK;
 }

@@ -9,6 +9,7 @@
 // difference are formed in fp32 like the reference (fp32 arrays), sums accumulate in fp64.  All reducers skip NaN
 // (xarray's default for floats): empty / all-NaN period -> NaN, except sum -> 0.
 #include "common.h"
+#include "hostargs.h"
 
 template <int VEC>
 __global__ void __launch_bounds__(XH_BLOCK)
@@ -272,19 +273,6 @@ static dim3 time_chunk_grid(xh_ctx* ctx, int64_t T, int64_t C) {
   return dim3((unsigned)cblocks, (unsigned)gy);
 }
 
-static int upload_tidx(xh_ctx* ctx, const char* fn, const int32_t* tidx, int64_t T, int D, const int32_t** d_tidx) {
-  XH_REQUIRE(tidx, XH_ERR_ARG, "%s: tidx is NULL", fn);
-  for (int64_t t = 0; t < T; ++t)
-    XH_REQUIRE(tidx[t] >= 0 && tidx[t] < D, XH_ERR_ARG, "%s: tidx[%lld] = %d outside the table (D = %d)", fn, (long long)t,
-               tidx[t], D);
-  size_t cur = 0;
-  void* d = nullptr;
-  int rc = xh_scratch_upload(ctx, &cur, tidx, sizeof(int32_t) * (size_t)T, &d);
-  if (rc) return rc;
-  *d_tidx = (const int32_t*)d;
-  return XH_OK;
-}
-
 // select_time(doy_bounds=(start, end)) with per-cell bounds (mask_between_doys, core/calendar.py:1244-1257, the
 // "spatial dims only" case): out = x where the day of year of the step lies inside the cell's [start, end] — a span that
 // wraps over the new year when start > end — else NaN.  start / end are float32 (C,), already shifted for exclusive
@@ -376,29 +364,25 @@ extern "C" {
 
 int xh_range_reduce(xh_ctx* ctx, const float* low, const float* high, int64_t T, int64_t C, int64_t st_low, int64_t st_high,
                     int mode, int reducer, const int64_t* seg_off, int P, float* out, int32_t* valid_out) {
-  XH_REQUIRE(ctx && low && high && out, XH_ERR_ARG, "xh_range_reduce: NULL argument");
-  XH_REQUIRE(T >= 0 && C >= 0, XH_ERR_ARG, "xh_range_reduce: negative shape");
-  XH_REQUIRE(st_low >= C && st_high >= C, XH_ERR_LAYOUT, "xh_range_reduce: needs time-major views (row strides >= C)");
+  XH_REQUIRE(out, XH_ERR_ARG, "xh_range_reduce: NULL argument");
+  int rc = xh_check_fields2("xh_range_reduce", ctx, low, high, T, C, st_low, st_high);
+  if (rc) return rc;
   XH_REQUIRE(mode >= 0 && mode <= 2, XH_ERR_ARG, "xh_range_reduce: mode must be 0 (range), 1 (interday) or 2 (extreme)");
   XH_REQUIRE(mode != 0 || (reducer >= XH_RED_SUM && reducer <= XH_RED_MAX), XH_ERR_OP,
              "xh_range_reduce: reducer %d not recognized", reducer);
-  XH_REQUIRE(seg_off && P >= 1, XH_ERR_ARG, "xh_range_reduce: seg_off NULL or P < 1");
-  for (int p = 0; p < P; ++p)
-    XH_REQUIRE(seg_off[p] <= seg_off[p + 1] && seg_off[p] >= 0 && seg_off[p + 1] <= T, XH_ERR_ARG,
-               "xh_range_reduce: seg_off must be non-decreasing within [0, T]");
   size_t cur = 0;
-  void* d_seg = nullptr;
-  int rc = xh_scratch_upload(ctx, &cur, seg_off, sizeof(int64_t) * (size_t)(P + 1), &d_seg);
+  const int64_t* d_seg = nullptr;
+  rc = xh_upload_segments("xh_range_reduce", ctx, &cur, seg_off, P, T, &d_seg);
   if (rc) return rc;
   if (C == 0) return XH_OK;
   const int vec = (xh_pick_vec(low, C, st_low) == 4 && xh_pick_vec(high, C, st_high) == 4) ? 4 : 1;
-  dim3 grid((unsigned)cdiv64(cdiv64(C, vec), XH_BLOCK), (unsigned)(P > 4096 ? 4096 : P));
+  const dim3 grid = xh_period_grid(C, vec, P);
   if (vec == 4)
     hipLaunchKernelGGL((k_range_reduce<4>), grid, dim3(XH_BLOCK), 0, ctx->stream, low, high, C, st_low, st_high, mode, reducer,
-                       (const int64_t*)d_seg, P, out, valid_out);
+                       d_seg, P, out, valid_out);
   else
     hipLaunchKernelGGL((k_range_reduce<1>), grid, dim3(XH_BLOCK), 0, ctx->stream, low, high, C, st_low, st_high, mode, reducer,
-                       (const int64_t*)d_seg, P, out, valid_out);
+                       d_seg, P, out, valid_out);
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
@@ -423,15 +407,12 @@ int xh_compare_map(xh_ctx* ctx, const float* a, int64_t T, int64_t C, int64_t st
   if (gy > T) gy = T;
   if (gy > 1024) gy = 1024;
   dim3 grid((unsigned)cblocks, (unsigned)gy);
-#define XH_CM(F, V)                                                                                                   \
-  hipLaunchKernelGGL((k_compare_map<F, V>), grid, dim3(XH_BLOCK), 0, ctx->stream, a, T, C, st, op, thr, b, st_b, out_kind, \
-                     out, st_out)
-  if (thr_is_f64 && !b) {
-    if (vec == 4) XH_CM(true, 4); else XH_CM(true, 1);
-  } else {
-    if (vec == 4) XH_CM(false, 4); else XH_CM(false, 1);
-  }
-#undef XH_CM
+  xh_pick<1, 0>((thr_is_f64 && !b) ? 1 : 0, [&](auto F64) {
+    xh_pick<4, 1>(vec, [&](auto V) {
+      hipLaunchKernelGGL((k_compare_map<decltype(F64)::value != 0, decltype(V)::value>), grid, dim3(XH_BLOCK), 0, ctx->stream, a, T, C,
+                         st, op, thr, b, st_b, out_kind, out, st_out);
+    });
+  });
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
@@ -440,8 +421,9 @@ int xh_doy_broadcast(xh_ctx* ctx, const double* table, int D, int64_t C, const i
   XH_REQUIRE(ctx && table && out, XH_ERR_ARG, "xh_doy_broadcast: NULL argument");
   XH_REQUIRE(D >= 1 && C >= 0 && T >= 0, XH_ERR_ARG, "xh_doy_broadcast: bad shape");
   if (T == 0 || C == 0) return XH_OK;
+  size_t cur = 0;
   const int32_t* d_tidx = nullptr;
-  int rc = upload_tidx(ctx, "xh_doy_broadcast", tidx, T, D, &d_tidx);
+  const int rc = xh_upload_tidx("xh_doy_broadcast", ctx, &cur, tidx, T, D, &d_tidx);
   if (rc) return rc;
   hipLaunchKernelGGL(k_doy_broadcast, time_chunk_grid(ctx, T, C), dim3(XH_BLOCK), 0, ctx->stream, table, C, d_tidx, T, out);
   XH_LAUNCH_CHECK();
@@ -454,8 +436,9 @@ int xh_within_bnds_doy(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_
   XH_REQUIRE(D >= 1 && C >= 0 && T >= 0, XH_ERR_ARG, "xh_within_bnds_doy: bad shape");
   XH_REQUIRE(sc == 1 && st >= C, XH_ERR_LAYOUT, "xh_within_bnds_doy: needs a time-major view (sc == 1, st >= C)");
   if (T == 0 || C == 0) return XH_OK;
+  size_t cur = 0;
   const int32_t* d_tidx = nullptr;
-  int rc = upload_tidx(ctx, "xh_within_bnds_doy", tidx, T, D, &d_tidx);
+  const int rc = xh_upload_tidx("xh_within_bnds_doy", ctx, &cur, tidx, T, D, &d_tidx);
   if (rc) return rc;
   hipLaunchKernelGGL(k_within_bnds_doy, time_chunk_grid(ctx, T, C), dim3(XH_BLOCK), 0, ctx->stream, x, T, C, st, low, high,
                      d_tidx, out);
@@ -470,8 +453,9 @@ int xh_compare_doy(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st
   XH_REQUIRE(sc == 1 && st >= C && st_out >= C, XH_ERR_LAYOUT, "xh_compare_doy: needs time-major views (sc == 1, st >= C)");
   XH_REQUIRE(op >= XH_OP_GT && op <= XH_OP_NE, XH_ERR_OP, "Operation `%d` not recognized.", op);
   if (T == 0 || C == 0) return XH_OK;
+  size_t cur = 0;
   const int32_t* d_tidx = nullptr;
-  int rc = upload_tidx(ctx, "xh_compare_doy", tidx, T, D, &d_tidx);
+  const int rc = xh_upload_tidx("xh_compare_doy", ctx, &cur, tidx, T, D, &d_tidx);
   if (rc) return rc;
   hipLaunchKernelGGL(k_compare_doy, time_chunk_grid(ctx, T, C), dim3(XH_BLOCK), 0, ctx->stream, x, T, C, st, op, table, d_tidx,
                      out, st_out);
@@ -487,24 +471,18 @@ int xh_precip_over_doy(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_
   XH_REQUIRE(T >= 0 && C >= 0 && D >= 1, XH_ERR_ARG, "xh_precip_over_doy: bad shape");
   XH_REQUIRE(sc == 1 && st >= C, XH_ERR_LAYOUT, "xh_precip_over_doy: needs a time-major view (cell stride 1)");
   XH_REQUIRE(op == XH_OP_GT || op == XH_OP_GE, XH_ERR_OP, "xh_precip_over_doy: operator must be > or >=");
-  XH_REQUIRE(seg_off && P >= 1, XH_ERR_ARG, "xh_precip_over_doy: seg_off NULL or P < 1");
-  for (int p = 0; p < P; ++p)
-    XH_REQUIRE(seg_off[p] <= seg_off[p + 1] && seg_off[p] >= 0 && seg_off[p + 1] <= T, XH_ERR_ARG,
-               "xh_precip_over_doy: seg_off must be non-decreasing within [0, T]");
-  XH_REQUIRE(tidx, XH_ERR_ARG, "xh_precip_over_doy: tidx is NULL");
-  for (int64_t t = 0; t < T; ++t)
-    XH_REQUIRE(tidx[t] >= 0 && tidx[t] < D, XH_ERR_ARG, "xh_precip_over_doy: tidx[%lld] = %d outside the table (D = %d)",
-               (long long)t, tidx[t], D);
-  size_t cur = 0;
-  void *d_tidx = nullptr, *d_seg = nullptr;
-  int rc = xh_scratch_upload(ctx, &cur, tidx, sizeof(int32_t) * (size_t)T, &d_tidx);
+  int rc = xh_check_segments("xh_precip_over_doy", seg_off, P, T);
   if (rc) return rc;
-  rc = xh_scratch_upload(ctx, &cur, seg_off, sizeof(int64_t) * (size_t)(P + 1), &d_seg);
+  size_t cur = 0;
+  const int32_t* d_tidx = nullptr;
+  const int64_t* d_seg = nullptr;
+  rc = xh_upload_tidx("xh_precip_over_doy", ctx, &cur, tidx, T, D, &d_tidx);
+  if (rc) return rc;
+  rc = xh_upload(ctx, &cur, seg_off, (size_t)P + 1, &d_seg);
   if (rc) return rc;
   if (C == 0) return XH_OK;
-  dim3 grid((unsigned)cdiv64(C, XH_BLOCK), (unsigned)(P > 4096 ? 4096 : P));
-  hipLaunchKernelGGL(k_precip_over_doy, grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, op, thr, table, (const int32_t*)d_tidx,
-                     (const int64_t*)d_seg, P, frac, n_over, valid_out);
+  hipLaunchKernelGGL(k_precip_over_doy, xh_period_grid(C, 1, P), dim3(XH_BLOCK), 0, ctx->stream, x, C, st, op, thr, table, d_tidx,
+                     d_seg, P, frac, n_over, valid_out);
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
@@ -578,19 +556,19 @@ int xh_mask_days_cells(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_
   XH_REQUIRE(T >= 0 && C >= 0 && P >= 1, XH_ERR_ARG, "xh_mask_days_cells: bad shape");
   XH_REQUIRE(sc == 1 && st >= C && out_st >= C, XH_ERR_LAYOUT, "xh_mask_days_cells: needs time-major views (sc == 1)");
   XH_REQUIRE(seg_off[0] == 0 && seg_off[P] == T, XH_ERR_ARG, "xh_mask_days_cells: the periods must cover [0, T)");
-  for (int p = 0; p < P; ++p)
-    XH_REQUIRE(seg_off[p] <= seg_off[p + 1], XH_ERR_ARG, "xh_mask_days_cells: seg_off must be non-decreasing");
+  int rc = xh_check_segments("xh_mask_days_cells", seg_off, P, T);  // (covering [0, T) and non-decreasing: inside [0, T])
+  if (rc) return rc;
   if (T == 0 || C == 0) return XH_OK;
   size_t cur = 0;
-  void* d_seg = nullptr;
-  int rc = xh_scratch_upload(ctx, &cur, seg_off, sizeof(int64_t) * (size_t)(P + 1), &d_seg);
+  const int64_t* d_seg = nullptr;
+  rc = xh_upload(ctx, &cur, seg_off, (size_t)P + 1, &d_seg);
   if (rc) return rc;
   const int vec = (xh_pick_vec(x, C, st) == 4 && xh_pick_vec(out, C, out_st) == 4) ? 4 : 1;
-  const dim3 grid((unsigned)cdiv64(cdiv64(C, vec), XH_BLOCK), (unsigned)(P > 4096 ? 4096 : P));
+  const dim3 grid = xh_period_grid(C, vec, P);
   if (vec == 4)
-    hipLaunchKernelGGL((k_mask_days_cells<4>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, (const int64_t*)d_seg, P, lo, hi, out, out_st);
+    hipLaunchKernelGGL((k_mask_days_cells<4>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, d_seg, P, lo, hi, out, out_st);
   else
-    hipLaunchKernelGGL((k_mask_days_cells<1>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, (const int64_t*)d_seg, P, lo, hi, out, out_st);
+    hipLaunchKernelGGL((k_mask_days_cells<1>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, d_seg, P, lo, hi, out, out_st);
   XH_LAUNCH_CHECK();
   return XH_OK;
 }

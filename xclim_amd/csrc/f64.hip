@@ -7,6 +7,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "f64util.h"
 
 namespace {
 
@@ -165,18 +166,8 @@ k_resample_reduce_f64(const double* __restrict__ x, int64_t C, int64_t st, int s
 }
 
 // ---- _nan_quantile on float64 samples (utl:494-557): one wave per slice, the N samples sorted as order-preserving
-// 64-bit keys in LDS (bitonic, NaN = largest key), then the Hyndman-Fan lerp with `diff` in float64 (the data dtype)
-__device__ __forceinline__ uint64_t d2key(double d) {
-  const uint64_t u = (uint64_t)__double_as_longlong(d);
-  if (d != d) return ~0ull;
-  return (u >> 63) ? ~u : (u | (1ull << 63));
-}
-__device__ __forceinline__ double key2d(uint64_t k) {
-  if (k == ~0ull) return xh_nan64();
-  const uint64_t u = (k >> 63) ? (k & ~(1ull << 63)) : ~k;
-  return __longlong_as_double((long long)u);
-}
-
+// 64-bit keys (f64util.h: d2key / key2d) in LDS (bitonic, NaN = largest key), then the Hyndman-Fan lerp with `diff` in
+// float64 (the data dtype)
 __global__ void __launch_bounds__(64)
 k_nan_quantile_f64(const double* __restrict__ x, int N, int NP, int64_t C, int64_t sn, int64_t sc, const double* __restrict__ qs,
                    int nq, double alpha, double beta, double* __restrict__ out) {
@@ -235,30 +226,6 @@ k_nan_quantile_f64(const double* __restrict__ x, int N, int NP, int64_t C, int64
   }
 }
 
-int check_f64(const char* fn, xh_ctx* ctx, const void* x, int64_t T, int64_t C, int64_t st, int64_t sc) {
-  XH_REQUIRE(ctx && x, XH_ERR_ARG, "%s: NULL argument", fn);
-  XH_REQUIRE(T >= 0 && C >= 0, XH_ERR_ARG, "%s: negative shape", fn);
-  XH_REQUIRE(sc == 1 && st >= C, XH_ERR_LAYOUT, "%s: streaming kernels need a time-major view (sc == 1, st >= C); got st=%lld sc=%lld",
-             fn, (long long)st, (long long)sc);
-  return XH_OK;
-}
-
-int upload_seg(xh_ctx* ctx, size_t* cur, const int64_t* seg_off, int P, int64_t T, const char* fn, const int64_t** d_seg) {
-  XH_REQUIRE(seg_off && P >= 1, XH_ERR_ARG, "%s: seg_off NULL or P < 1", fn);
-  for (int p = 0; p < P; ++p)
-    XH_REQUIRE(seg_off[p] <= seg_off[p + 1] && seg_off[p] >= 0 && seg_off[p + 1] <= T, XH_ERR_ARG,
-               "%s: seg_off must be non-decreasing within [0, T]", fn);
-  void* d = nullptr;
-  const int rc = xh_scratch_upload(ctx, cur, seg_off, sizeof(int64_t) * (size_t)(P + 1), &d);
-  if (rc) return rc;
-  *d_seg = (const int64_t*)d;
-  return XH_OK;
-}
-
-inline int pick_vec64(const void* p, int64_t C, int64_t st) {
-  return ((reinterpret_cast<uintptr_t>(p) & 15) == 0 && (C % 2) == 0 && (st % 2) == 0) ? 2 : 1;
-}
-
 }  // namespace
 
 extern "C" {
@@ -266,7 +233,7 @@ extern "C" {
 int xh_threshold_count_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int64_t st, int64_t sc, int op, int thr_kind,
                            double thr_scalar, const double* thr_table, int64_t thr_stride, const int32_t* tidx,
                            const int64_t* seg_off, int P, int32_t* count_out, int32_t* valid_out) {
-  int rc = check_f64("xh_threshold_count_f64", ctx, x, T, C, st, sc);
+  int rc = xh_check_field("xh_threshold_count_f64", ctx, x, T, C, st, sc);
   if (rc) return rc;
   XH_REQUIRE(op >= XH_OP_GT && op <= XH_OP_NE, XH_ERR_OP, "Operation `%d` not recognized.", op);
   XH_REQUIRE(count_out, XH_ERR_ARG, "xh_threshold_count_f64: count_out is NULL");
@@ -274,59 +241,48 @@ int xh_threshold_count_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, i
              "xh_threshold_count_f64: thr_kind must be XH_THR_SCALAR_F64, XH_THR_DOY_F64 or XH_THR_FULL_F64 (got %d)", thr_kind);
   if (thr_kind != XH_THR_SCALAR_F64) {
     XH_REQUIRE(thr_table, XH_ERR_ARG, "xh_threshold_count_f64: threshold table missing");
-    XH_REQUIRE(thr_stride >= C, XH_ERR_LAYOUT, "xh_threshold_count_f64: needs time-major rows of at least the row width (thr_stride)");
+    rc = xh_check_rows("xh_threshold_count_f64", thr_stride, C, "thr_stride");
+    if (rc) return rc;
     if (thr_kind == XH_THR_DOY_F64) XH_REQUIRE(tidx, XH_ERR_ARG, "xh_threshold_count_f64: tidx required for per-doy thresholds");
   }
   size_t cur = 0;
   const int64_t* d_seg = nullptr;
-  rc = upload_seg(ctx, &cur, seg_off, P, T, "xh_threshold_count_f64", &d_seg);
+  rc = xh_upload_segments("xh_threshold_count_f64", ctx, &cur, seg_off, P, T, &d_seg);
   if (rc) return rc;
   if (C == 0) return XH_OK;
-  int vec = pick_vec64(x, C, st);
+  int vec = xh_pick_vec64(x, C, st);
   if (thr_kind != XH_THR_SCALAR_F64 && ((reinterpret_cast<uintptr_t>(thr_table) & 15) != 0 || (thr_stride % 2) != 0)) vec = 1;
-  const dim3 grid((unsigned)cdiv64(cdiv64(C, vec), XH_BLOCK), (unsigned)(P < 1 ? 1 : (P > 4096 ? 4096 : P)));
-#define XH_TC64(V, K)                                                                                                       \
-  hipLaunchKernelGGL((k_threshold_count_f64<V, K>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, op, thr_scalar, thr_table, \
-                     thr_stride, tidx, d_seg, P, count_out, valid_out)
-  if (vec == 2) {
-    if (thr_kind == XH_THR_SCALAR_F64) XH_TC64(2, XH_THR_SCALAR_F64);
-    else if (thr_kind == XH_THR_DOY_F64) XH_TC64(2, XH_THR_DOY_F64);
-    else XH_TC64(2, XH_THR_FULL_F64);
-  } else {
-    if (thr_kind == XH_THR_SCALAR_F64) XH_TC64(1, XH_THR_SCALAR_F64);
-    else if (thr_kind == XH_THR_DOY_F64) XH_TC64(1, XH_THR_DOY_F64);
-    else XH_TC64(1, XH_THR_FULL_F64);
-  }
-#undef XH_TC64
+  const dim3 grid = xh_period_grid(C, vec, P);
+  xh_pick<2, 1>(vec, [&](auto V) {
+    xh_pick<XH_THR_SCALAR_F64, XH_THR_DOY_F64, XH_THR_FULL_F64>(thr_kind, [&](auto K) {
+      hipLaunchKernelGGL((k_threshold_count_f64<decltype(V)::value, decltype(K)::value>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st,
+                         op, thr_scalar, thr_table, thr_stride, tidx, d_seg, P, count_out, valid_out);
+    });
+  });
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
 
 int xh_resample_reduce_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int64_t st, int64_t sc, int reducer, int skipna,
                            const int64_t* seg_off, int P, void* out, int32_t* valid_out) {
-  int rc = check_f64("xh_resample_reduce_f64", ctx, x, T, C, st, sc);
+  int rc = xh_check_field("xh_resample_reduce_f64", ctx, x, T, C, st, sc);
   if (rc) return rc;
   XH_REQUIRE(out, XH_ERR_ARG, "xh_resample_reduce_f64: out is NULL");
   size_t cur = 0;
   const int64_t* d_seg = nullptr;
-  rc = upload_seg(ctx, &cur, seg_off, P, T, "xh_resample_reduce_f64", &d_seg);
+  rc = xh_upload_segments("xh_resample_reduce_f64", ctx, &cur, seg_off, P, T, &d_seg);
   if (rc) return rc;
   if (C == 0) return XH_OK;
-  const int vec = pick_vec64(x, C, st);
-  const dim3 grid((unsigned)cdiv64(cdiv64(C, vec), XH_BLOCK), (unsigned)(P < 1 ? 1 : (P > 4096 ? 4096 : P)));
-#define XH_RR64(R)                                                                                                            \
-  case R:                                                                                                                     \
-    if (vec == 2) hipLaunchKernelGGL((k_resample_reduce_f64<2, R>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, skipna, d_seg, P, out, valid_out); \
-    else hipLaunchKernelGGL((k_resample_reduce_f64<1, R>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, skipna, d_seg, P, out, valid_out);          \
-    break;
-  switch (reducer) {
-    XH_RR64(XH_RED_SUM) XH_RR64(XH_RED_MEAN) XH_RR64(XH_RED_MIN) XH_RR64(XH_RED_MAX) XH_RR64(XH_RED_STD) XH_RR64(XH_RED_VAR)
-    XH_RR64(XH_RED_COUNT) XH_RR64(XH_RED_ARGMIN) XH_RR64(XH_RED_ARGMAX)
-    default:
-      xh_set_error("xh_resample_reduce_f64: reducer %d not recognized", reducer);
-      return XH_ERR_OP;
-  }
-#undef XH_RR64
+  const int vec = xh_pick_vec64(x, C, st);
+  const dim3 grid = xh_period_grid(C, vec, P);
+  const bool known = xh_pick<XH_RED_SUM, XH_RED_MEAN, XH_RED_MIN, XH_RED_MAX, XH_RED_STD, XH_RED_VAR, XH_RED_COUNT, XH_RED_ARGMIN,
+                             XH_RED_ARGMAX>(reducer, [&](auto R) {
+    xh_pick<2, 1>(vec, [&](auto V) {
+      hipLaunchKernelGGL((k_resample_reduce_f64<decltype(V)::value, decltype(R)::value>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st,
+                         skipna, d_seg, P, out, valid_out);
+    });
+  });
+  XH_REQUIRE(known, XH_ERR_OP, "xh_resample_reduce_f64: reducer %d not recognized", reducer);
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
@@ -339,15 +295,15 @@ int xh_nan_quantile_f64(xh_ctx* ctx, const double* x, int64_t N, int64_t C, int6
   XH_REQUIRE((sc == 1 && sn >= C) || (sn == 1 && sc >= N), XH_ERR_LAYOUT, "xh_nan_quantile_f64: one of the two strides must be 1");
   if (C == 0) return XH_OK;
   size_t cur = 0;
-  void* d_q = nullptr;
-  const int rc = xh_scratch_upload(ctx, &cur, q, sizeof(double) * nq, &d_q);
+  const double* d_q = nullptr;
+  const int rc = xh_upload(ctx, &cur, q, (size_t)nq, &d_q);
   if (rc) return rc;
   int NP = 2;
   while (NP < N) NP <<= 1;
   int64_t nblk = C;
   if (nblk > (int64_t)ctx->num_cu * 64) nblk = (int64_t)ctx->num_cu * 64;
-  hipLaunchKernelGGL(k_nan_quantile_f64, dim3((unsigned)nblk), dim3(64), (size_t)NP * 8, ctx->stream, x, (int)N, NP, C, sn, sc,
-                     (const double*)d_q, nq, alpha, beta, out);
+  hipLaunchKernelGGL(k_nan_quantile_f64, dim3((unsigned)nblk), dim3(64), (size_t)NP * 8, ctx->stream, x, (int)N, NP, C, sn, sc, d_q,
+                     nq, alpha, beta, out);
   XH_LAUNCH_CHECK();
   return XH_OK;
 }

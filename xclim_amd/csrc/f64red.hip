@@ -369,17 +369,13 @@ k_rolling_reduce_f64(const double* __restrict__ x, int64_t T, int64_t C, int64_t
   }
 }
 
-inline dim3 period_grid(int64_t C, int vec, int P) {
-  return dim3((unsigned)cdiv64(cdiv64(C, vec), XH_BLOCK), (unsigned)(P > 4096 ? 4096 : P));
-}
-
 }  // namespace
 
 extern "C" {
 
 int xh_thresholded_reduce_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int64_t st, int64_t sc, int op, double thr,
                               int mode, int reducer, const int64_t* seg_off, int P, double* out, int32_t* valid_out) {
-  int rc = check_field("xh_thresholded_reduce_f64", ctx, x, T, C, st, sc);
+  int rc = xh_check_field("xh_thresholded_reduce_f64", ctx, x, T, C, st, sc);
   if (rc) return rc;
   XH_REQUIRE(out, XH_ERR_ARG, "xh_thresholded_reduce_f64: out is NULL");
   XH_REQUIRE(mode >= 0 && mode <= 2, XH_ERR_ARG, "xh_thresholded_reduce_f64: mode must be 0, 1 or 2");
@@ -389,29 +385,26 @@ int xh_thresholded_reduce_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C
   XH_REQUIRE(mode == 0 || op <= XH_OP_LE, XH_ERR_OP, "Condition not supported: '%d'.", op);
   size_t cur = 0;
   const int64_t* d_seg = nullptr;
-  rc = upload_segs(ctx, &cur, seg_off, P, T, "xh_thresholded_reduce_f64", &d_seg);
+  rc = xh_upload_segments("xh_thresholded_reduce_f64", ctx, &cur, seg_off, P, T, &d_seg);
   if (rc) return rc;
   if (C == 0) return XH_OK;
-  const int vec = pick_vec(x, C, st);
-  const dim3 grid = period_grid(C, vec, P);
-#define XH_TR64(V, M)                                                                                                     \
-  hipLaunchKernelGGL((k_thresholded_reduce_f64<V, M>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, op, thr, reducer, d_seg, P, \
-                     out, valid_out)
-#define XH_TR64_M(M) { if (vec == 2) XH_TR64(2, M); else XH_TR64(1, M); }
-  if (mode == 0) XH_TR64_M(0)
-  else if (mode == 1) XH_TR64_M(1)
-  else XH_TR64_M(2)
-#undef XH_TR64_M
-#undef XH_TR64
+  const int vec = xh_pick_vec64(x, C, st);
+  const dim3 grid = xh_period_grid(C, vec, P);
+  xh_pick<0, 1, 2>(mode, [&](auto M) {
+    xh_pick<2, 1>(vec, [&](auto V) {
+      hipLaunchKernelGGL((k_thresholded_reduce_f64<decltype(V)::value, decltype(M)::value>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C,
+                         st, op, thr, reducer, d_seg, P, out, valid_out);
+    });
+  });
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
 
 int xh_range_reduce_f64(xh_ctx* ctx, const void* low, const void* high, int64_t T, int64_t C, int64_t st_low, int64_t st_high,
                         int dtypes, int mode, int reducer, const int64_t* seg_off, int P, double* out, int32_t* valid_out) {
-  XH_REQUIRE(ctx && low && high && out, XH_ERR_ARG, "xh_range_reduce_f64: NULL argument");
-  XH_REQUIRE(T >= 0 && C >= 0, XH_ERR_ARG, "xh_range_reduce_f64: negative shape");
-  XH_REQUIRE(st_low >= C && st_high >= C, XH_ERR_LAYOUT, "xh_range_reduce_f64: needs time-major views (row strides >= C)");
+  XH_REQUIRE(out, XH_ERR_ARG, "xh_range_reduce_f64: NULL argument");
+  int rc = xh_check_fields2("xh_range_reduce_f64", ctx, low, high, T, C, st_low, st_high);
+  if (rc) return rc;
   XH_REQUIRE(dtypes >= 0 && dtypes <= 2, XH_ERR_ARG,
              "xh_range_reduce_f64: dtypes must be 0 (low, high float64), 1 (low float32) or 2 (high float32)");
   XH_REQUIRE(mode >= 0 && mode <= 2, XH_ERR_ARG, "xh_range_reduce_f64: mode must be 0 (range), 1 (interday) or 2 (extreme)");
@@ -419,30 +412,29 @@ int xh_range_reduce_f64(xh_ctx* ctx, const void* low, const void* high, int64_t 
              "xh_range_reduce_f64: reducer %d not recognized", reducer);
   size_t cur = 0;
   const int64_t* d_seg = nullptr;
-  int rc = upload_segs(ctx, &cur, seg_off, P, T, "xh_range_reduce_f64", &d_seg);
+  rc = xh_upload_segments("xh_range_reduce_f64", ctx, &cur, seg_off, P, T, &d_seg);
   if (rc) return rc;
   if (C == 0) return XH_OK;
   const size_t el = dtypes == 1 ? 4 : 8, eh = dtypes == 2 ? 4 : 8;
-  const int vec = (pick_vec(low, C, st_low, el) == 2 && pick_vec(high, C, st_high, eh) == 2) ? 2 : 1;
-  const dim3 grid = period_grid(C, vec, P);
-#define XH_RG64(V, M, TL, TH)                                                                                               \
-  hipLaunchKernelGGL((k_range_reduce_f64<V, M, TL, TH>), grid, dim3(XH_BLOCK), 0, ctx->stream, (const TL*)low, (const TH*)high, C, \
-                     st_low, st_high, reducer, d_seg, P, out, valid_out)
-#define XH_RG64_M(V, TL, TH) { if (mode == 0) XH_RG64(V, 0, TL, TH); else if (mode == 1) XH_RG64(V, 1, TL, TH); else XH_RG64(V, 2, TL, TH); }
-#define XH_RG64_T(TL, TH) { if (vec == 2) XH_RG64_M(2, TL, TH) else XH_RG64_M(1, TL, TH) }
-  if (dtypes == 0) XH_RG64_T(double, double)
-  else if (dtypes == 1) XH_RG64_T(float, double)
-  else XH_RG64_T(double, float)
-#undef XH_RG64_T
-#undef XH_RG64_M
-#undef XH_RG64
+  const int vec = (xh_pick_vec64(low, C, st_low, el) == 2 && xh_pick_vec64(high, C, st_high, eh) == 2) ? 2 : 1;
+  const dim3 grid = xh_period_grid(C, vec, P);
+  xh_pick<0, 1, 2>(dtypes, [&](auto DT) {  // 1: low is float32, 2: high is
+    using TL = std::conditional_t<decltype(DT)::value == 1, float, double>;
+    using TH = std::conditional_t<decltype(DT)::value == 2, float, double>;
+    xh_pick<2, 1>(vec, [&](auto V) {
+      xh_pick<0, 1, 2>(mode, [&](auto M) {
+        hipLaunchKernelGGL((k_range_reduce_f64<decltype(V)::value, decltype(M)::value, TL, TH>), grid, dim3(XH_BLOCK), 0, ctx->stream,
+                           (const TL*)low, (const TH*)high, C, st_low, st_high, reducer, d_seg, P, out, valid_out);
+      });
+    });
+  });
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
 
 int xh_domain_count_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int64_t st, int64_t sc, int op1, double thr1, int op2,
                         double thr2, int combine, const int64_t* seg_off, int P, int32_t* count_out, int32_t* valid_out) {
-  int rc = check_field("xh_domain_count_f64", ctx, x, T, C, st, sc);
+  int rc = xh_check_field("xh_domain_count_f64", ctx, x, T, C, st, sc);
   if (rc) return rc;
   XH_REQUIRE(count_out, XH_ERR_ARG, "xh_domain_count_f64: count_out is NULL");
   XH_REQUIRE(op1 >= XH_OP_GT && op1 <= XH_OP_NE && op2 >= XH_OP_GT && op2 <= XH_OP_NE, XH_ERR_OP,
@@ -450,11 +442,11 @@ int xh_domain_count_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int6
   XH_REQUIRE(combine == 1 || combine == 2, XH_ERR_ARG, "xh_domain_count_f64: combine must be 1 (and) or 2 (or)");
   size_t cur = 0;
   const int64_t* d_seg = nullptr;
-  rc = upload_segs(ctx, &cur, seg_off, P, T, "xh_domain_count_f64", &d_seg);
+  rc = xh_upload_segments("xh_domain_count_f64", ctx, &cur, seg_off, P, T, &d_seg);
   if (rc) return rc;
   if (C == 0) return XH_OK;
-  const int vec = pick_vec(x, C, st);
-  const dim3 grid = period_grid(C, vec, P);
+  const int vec = xh_pick_vec64(x, C, st);
+  const dim3 grid = xh_period_grid(C, vec, P);
   if (vec == 2)
     hipLaunchKernelGGL((k_domain_count_f64<2>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, op1, thr1, op2, thr2, combine, d_seg,
                        P, count_out, valid_out);
@@ -468,9 +460,9 @@ int xh_domain_count_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int6
 int xh_bivariate_count_f64(xh_ctx* ctx, const void* x1, const void* x2, int64_t T, int64_t C, int64_t st1, int64_t st2, int dtypes,
                            int op1, double thr1, int op2, double thr2, int combine, const int64_t* seg_off, int P,
                            int32_t* count_out, int32_t* valid_out) {
-  XH_REQUIRE(ctx && x1 && x2 && count_out, XH_ERR_ARG, "xh_bivariate_count_f64: NULL argument");
-  XH_REQUIRE(T >= 0 && C >= 0, XH_ERR_ARG, "xh_bivariate_count_f64: negative shape");
-  XH_REQUIRE(st1 >= C && st2 >= C, XH_ERR_LAYOUT, "xh_bivariate_count_f64: needs time-major views (row strides >= C)");
+  XH_REQUIRE(count_out, XH_ERR_ARG, "xh_bivariate_count_f64: NULL argument");
+  int rc = xh_check_fields2("xh_bivariate_count_f64", ctx, x1, x2, T, C, st1, st2);
+  if (rc) return rc;
   XH_REQUIRE(dtypes >= 0 && dtypes <= 2, XH_ERR_ARG,
              "xh_bivariate_count_f64: dtypes must be 0 (x1, x2 float64), 1 (x1 float32) or 2 (x2 float32)");
   XH_REQUIRE(op1 >= XH_OP_GT && op1 <= XH_OP_NE && op2 >= XH_OP_GT && op2 <= XH_OP_NE, XH_ERR_OP,
@@ -478,33 +470,33 @@ int xh_bivariate_count_f64(xh_ctx* ctx, const void* x1, const void* x2, int64_t 
   XH_REQUIRE(combine == 1 || combine == 2, XH_ERR_ARG, "xh_bivariate_count_f64: combine must be 1 (all) or 2 (any)");
   size_t cur = 0;
   const int64_t* d_seg = nullptr;
-  int rc = upload_segs(ctx, &cur, seg_off, P, T, "xh_bivariate_count_f64", &d_seg);
+  rc = xh_upload_segments("xh_bivariate_count_f64", ctx, &cur, seg_off, P, T, &d_seg);
   if (rc) return rc;
   if (C == 0) return XH_OK;
   // a float32 side compares in float32 against the float32-rounded threshold (numpy: a python float is a weak scalar)
   const double t1 = dtypes == 1 ? (double)(float)thr1 : thr1, t2 = dtypes == 2 ? (double)(float)thr2 : thr2;
   const size_t e1 = dtypes == 1 ? 4 : 8, e2 = dtypes == 2 ? 4 : 8;
-  const int vec = (pick_vec(x1, C, st1, e1) == 2 && pick_vec(x2, C, st2, e2) == 2) ? 2 : 1;
-  const dim3 grid = period_grid(C, vec, P);
-#define XH_BV64(V, TA, TB)                                                                                                  \
-  hipLaunchKernelGGL((k_bivariate_count_f64<V, TA, TB>), grid, dim3(XH_BLOCK), 0, ctx->stream, (const TA*)x1, (const TB*)x2, C, \
-                     st1, st2, op1, t1, op2, t2, combine, d_seg, P, count_out, valid_out)
-#define XH_BV64_T(TA, TB) { if (vec == 2) XH_BV64(2, TA, TB); else XH_BV64(1, TA, TB); }
-  if (dtypes == 0) XH_BV64_T(double, double)
-  else if (dtypes == 1) XH_BV64_T(float, double)
-  else XH_BV64_T(double, float)
-#undef XH_BV64_T
-#undef XH_BV64
+  const int vec = (xh_pick_vec64(x1, C, st1, e1) == 2 && xh_pick_vec64(x2, C, st2, e2) == 2) ? 2 : 1;
+  const dim3 grid = xh_period_grid(C, vec, P);
+  xh_pick<0, 1, 2>(dtypes, [&](auto DT) {  // 1: x1 is float32, 2: x2 is
+    using TA = std::conditional_t<decltype(DT)::value == 1, float, double>;
+    using TB = std::conditional_t<decltype(DT)::value == 2, float, double>;
+    xh_pick<2, 1>(vec, [&](auto V) {
+      hipLaunchKernelGGL((k_bivariate_count_f64<decltype(V)::value, TA, TB>), grid, dim3(XH_BLOCK), 0, ctx->stream, (const TA*)x1,
+                         (const TB*)x2, C, st1, st2, op1, t1, op2, t2, combine, d_seg, P, count_out, valid_out);
+    });
+  });
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
 
 int xh_rolling_reduce_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int64_t st, int64_t sc, int window, int center,
                           int reducer, double* out, int64_t out_st) {
-  int rc = check_field("xh_rolling_reduce_f64", ctx, x, T, C, st, sc);
+  int rc = xh_check_field("xh_rolling_reduce_f64", ctx, x, T, C, st, sc);
   if (rc) return rc;
   XH_REQUIRE(out, XH_ERR_ARG, "xh_rolling_reduce_f64: out NULL");
-  XH_REQUIRE(out_st >= C, XH_ERR_LAYOUT, "xh_rolling_reduce_f64: needs time-major rows of at least the row width (out_st)");
+  rc = xh_check_rows("xh_rolling_reduce_f64", out_st, C, "out_st");
+  if (rc) return rc;
   XH_REQUIRE(window >= 1, XH_ERR_ARG, "xh_rolling_reduce_f64: window must be >= 1");
   XH_REQUIRE(reducer >= XH_RED_SUM && reducer <= XH_RED_COUNT, XH_ERR_OP, "xh_rolling_reduce_f64: reducer %d not recognized", reducer);
   if (T == 0 || C == 0) return XH_OK;
@@ -512,41 +504,22 @@ int xh_rolling_reduce_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, in
   const int left = center ? window / 2 : window - 1;
   const int right = window - 1 - left;
   const bool ring = window <= WMAX;
-  const int vec = (ring && pick_vec(x, C, st) == 2 && pick_vec(out, C, out_st) == 2) ? 2 : 1;
+  const int vec = (ring && xh_pick_vec64(x, C, st) == 2 && xh_pick_vec64(out, C, out_st) == 2) ? 2 : 1;
   const int64_t cblocks = cdiv64(cdiv64(C, vec), XH_BLOCK);
   int64_t gy = cdiv64((int64_t)ctx->num_cu * 8, cblocks);
   if (gy < 1) gy = 1;
   if (gy > cdiv64(T, 64)) gy = cdiv64(T, 64);  // chunks of >= 64 rows: the halo stays a small share
   if (gy > 1024) gy = 1024;
   const dim3 grid((unsigned)cblocks, (unsigned)gy);
-#define XH_RO64(V, R, W)                                                                                                  \
-  hipLaunchKernelGGL((k_rolling_reduce_f64<V, R, W>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, T, C, st, window, left, right, out, \
-                     out_st)
-#define XH_RO64_W(R, W) { if (vec == 2) XH_RO64(2, R, W); else XH_RO64(1, R, W); }
-#define XH_RO64_R(R)                                                                                                      \
-  switch (ring ? window : 0) {                                                                                            \
-    case 1: XH_RO64_W(R, 1) break;                                                                                         \
-    case 2: XH_RO64_W(R, 2) break;                                                                                         \
-    case 3: XH_RO64_W(R, 3) break;                                                                                         \
-    case 4: XH_RO64_W(R, 4) break;                                                                                         \
-    case 5: XH_RO64_W(R, 5) break;                                                                                         \
-    case 6: XH_RO64_W(R, 6) break;                                                                                         \
-    case 7: XH_RO64_W(R, 7) break;                                                                                         \
-    case 8: XH_RO64_W(R, 8) break;                                                                                         \
-    default: XH_RO64(1, R, 0); break;                                                                                      \
-  }
-  switch (reducer) {
-    case XH_RED_SUM: XH_RO64_R(XH_RED_SUM) break;
-    case XH_RED_MEAN: XH_RO64_R(XH_RED_MEAN) break;
-    case XH_RED_MIN: XH_RO64_R(XH_RED_MIN) break;
-    case XH_RED_MAX: XH_RO64_R(XH_RED_MAX) break;
-    case XH_RED_STD: XH_RO64_R(XH_RED_STD) break;
-    case XH_RED_VAR: XH_RO64_R(XH_RED_VAR) break;
-    default: XH_RO64_R(XH_RED_COUNT) break;
-  }
-#undef XH_RO64_R
-#undef XH_RO64_W
-#undef XH_RO64
+  // (compile-time window, cells per lane) as one code: the windows of the register ring with two cells or one, else the
+  // re-reading kernel with one
+  const int wv = ring ? window * 10 + vec : 1;
+  xh_pick<XH_RED_SUM, XH_RED_MEAN, XH_RED_MIN, XH_RED_MAX, XH_RED_STD, XH_RED_VAR, XH_RED_COUNT>(reducer, [&](auto R) {
+    xh_pick<12, 11, 22, 21, 32, 31, 42, 41, 52, 51, 62, 61, 72, 71, 82, 81, 1>(wv, [&](auto WV) {
+      hipLaunchKernelGGL((k_rolling_reduce_f64<decltype(WV)::value % 10, decltype(R)::value, decltype(WV)::value / 10>), grid,
+                         dim3(XH_BLOCK), 0, ctx->stream, x, T, C, st, window, left, right, out, out_st);
+    });
+  });
   XH_LAUNCH_CHECK();
   return XH_OK;
 }

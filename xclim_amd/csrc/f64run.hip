@@ -413,18 +413,7 @@ k_run_stats_doy_f64(const double* __restrict__ x, int64_t C, int64_t st, int op,
 }
 
 // ---- percentile_doy on float64 samples ----------------------------------------------------------------------------
-// order-preserving 64-bit keys (f64.hip d2key / key2d): NaN -> the largest key, sorted last and not counted
-__device__ __forceinline__ uint64_t dkey(double d) {
-  const uint64_t u = (uint64_t)__double_as_longlong(d);
-  if (d != d) return ~0ull;
-  return (u >> 63) ? ~u : (u | (1ull << 63));
-}
-__device__ __forceinline__ double kdbl(uint64_t k) {
-  if (k == ~0ull) return xh_nan64();
-  const uint64_t u = (k >> 63) ? (k & ~(1ull << 63)) : ~k;
-  return __longlong_as_double((long long)u);
-}
-
+// order-preserving 64-bit keys (f64util.h: d2key / key2d): NaN -> the largest key, sorted last and not counted
 constexpr int PD_THREADS = 256;
 constexpr int PD_LDS = 64 * 1024;  // bytes of keys per workgroup: L columns of NP keys
 
@@ -455,7 +444,7 @@ k_percentile_doy_f64(const double* __restrict__ x, int64_t T, int64_t C, int64_t
       const int y = i / window, k = i - y * window;
       const int32_t tb = tbase[(int64_t)y * ndoy + d];
       const int64_t t = (int64_t)tb - half + k;
-      if (tb >= 0 && t >= 0 && t < T) kk = dkey(x[t * st + c]);
+      if (tb >= 0 && t >= 0 && t < T) kk = d2key(x[t * st + c]);
     }
     key[e] = kk;
     if (kk != ~0ull) atomicAdd(&nvs[col], 1);
@@ -488,22 +477,22 @@ k_percentile_doy_f64(const double* __restrict__ x, int64_t T, int64_t C, int64_t
     const int nv = nvs[col];
     const double q = qs[jq];
     double r;
-    if (N == 1) r = kdbl(key[col]);
-    else if (nv < 2) r = nv == 1 ? kdbl(key[col]) : xh_nan64();
+    if (N == 1) r = key2d(key[col]);
+    else if (nv < 2) r = nv == 1 ? key2d(key[col]) : xh_nan64();
     else {
       const double nn = (double)nv;
       const double vi = nn * q + (alpha + q * (1.0 - alpha - beta)) - 1.0;
-      if (vi >= nn - 1.0) r = kdbl(key[(nv - 1) * L + col]);
-      else if (vi < 0.0) r = kdbl(key[col]);
+      if (vi >= nn - 1.0) r = key2d(key[(nv - 1) * L + col]);
+      else if (vi < 0.0) r = key2d(key[col]);
       else {
         const double prev = floor(vi);
         const int ip = (int)prev;
         const double gamma = vi - prev;
-        const double left = kdbl(key[ip * L + col]), right = kdbl(key[(ip + 1) * L + col]);
+        const double left = key2d(key[ip * L + col]), right = key2d(key[(ip + 1) * L + col]);
         const double diff = right - left;
         r = left + diff * gamma;
         if (gamma >= 0.5) r = right - diff * (1.0 - gamma);
-        if (r != r) r = kdbl(key[(nv - 1) * L + col]);
+        if (r != r) r = key2d(key[(nv - 1) * L + col]);
       }
     }
     out[((int64_t)jq * ndoy + d) * C + c] = r;
@@ -558,7 +547,7 @@ int xh_compare_map_f64(xh_ctx* ctx, const void* a, int64_t T, int64_t C, int64_t
 int xh_run_stats_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int64_t st, int64_t sc, int fused_op, double thr,
                      int window, int stat, int index_first, const int64_t* seg_off, int P, int cut_at_segments, float* out,
                      int32_t* valid_out) {
-  int rc = check_field("xh_run_stats_f64", ctx, x, T, C, st, sc);
+  int rc = xh_check_field("xh_run_stats_f64", ctx, x, T, C, st, sc);
   if (rc) return rc;
   XH_REQUIRE(fused_op <= XH_OP_NE, XH_ERR_OP, "Operation `%d` not recognized.", fused_op);
   XH_REQUIRE(window >= 1, XH_ERR_ARG, "xh_run_stats_f64: window must be >= 1");
@@ -571,35 +560,38 @@ int xh_run_stats_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int64_t
   }
   size_t cur = 0;
   const int64_t* d_seg = nullptr;
-  rc = upload_segs(ctx, &cur, seg_off, P, T, "xh_run_stats_f64", &d_seg);
+  rc = xh_upload_segments("xh_run_stats_f64", ctx, &cur, seg_off, P, T, &d_seg);
   if (rc) return rc;
   if (!cut_at_segments)
     XH_REQUIRE(seg_off[0] == 0 && seg_off[P] == T, XH_ERR_ARG, "xh_run_stats_f64: resample-after mode needs segments covering [0, T)");
   if (C == 0) return XH_OK;
   // resample-after: one serial march over all periods per cell (gridDim.y = 1), one cell per lane — the grid is sized
   // with the VEC that is launched
-  const int vec = cut_at_segments ? pick_vec(x, C, st) : 1;
+  const int vec = cut_at_segments ? xh_pick_vec64(x, C, st) : 1;
   const int sg = stat_group(stat);
-  const unsigned py = (unsigned)(P > 4096 ? 4096 : P);
+  const unsigned py = xh_period_blocks(P);
   const dim3 grid((unsigned)cdiv64(cdiv64(C, vec), XH_BLOCK), cut_at_segments ? py : 1u);
-#define XH_RS64(V, CU, G)                                                                                                 \
-  hipLaunchKernelGGL((k_run_stats_f64<V, CU, G>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, fused_op, thr, window, stat, \
-                     index_first, d_seg, P, out, valid_out)
-#define XH_RS64_G(V, CU) { if (sg == 1) XH_RS64(V, CU, 1); else if (sg == 2) XH_RS64(V, CU, 2); else XH_RS64(V, CU, 0); }
-  if (cut_at_segments) { if (vec == 2) XH_RS64_G(2, true) else XH_RS64_G(1, true) }
-  else XH_RS64_G(1, false)
-#undef XH_RS64_G
-#undef XH_RS64
+  xh_pick<2, 1>(vec, [&](auto V) {
+    xh_pick<1, 2, 0>(sg, [&](auto G) {
+      if (cut_at_segments)
+        hipLaunchKernelGGL((k_run_stats_f64<decltype(V)::value, true, decltype(G)::value>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C,
+                           st, fused_op, thr, window, stat, index_first, d_seg, P, out, valid_out);
+      else if constexpr (decltype(V)::value == 1)  // resample-after: one cell per lane
+        hipLaunchKernelGGL((k_run_stats_f64<1, false, decltype(G)::value>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, fused_op,
+                           thr, window, stat, index_first, d_seg, P, out, valid_out);
+    });
+  });
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
 
 int xh_spell_mask_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int64_t st, int64_t sc, int window, int win_reducer,
                       int op, double thr, const double* weights, float* out, int64_t out_st) {
-  int rc = check_field("xh_spell_mask_f64", ctx, x, T, C, st, sc);
+  int rc = xh_check_field("xh_spell_mask_f64", ctx, x, T, C, st, sc);
   if (rc) return rc;
   XH_REQUIRE(out, XH_ERR_ARG, "xh_spell_mask_f64: out NULL");
-  XH_REQUIRE(out_st >= C, XH_ERR_LAYOUT, "xh_spell_mask_f64: needs time-major rows of at least the row width (out_st)");
+  rc = xh_check_rows("xh_spell_mask_f64", out_st, C, "out_st");
+  if (rc) return rc;
   XH_REQUIRE(window >= 1, XH_ERR_ARG, "xh_spell_mask_f64: window must be >= 1");
   XH_REQUIRE(op >= XH_OP_GT && op <= XH_OP_NE, XH_ERR_OP, "Operation `%d` not recognized.", op);
   if (weights || win_reducer == 4) {
@@ -609,24 +601,20 @@ int xh_spell_mask_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int64_
   XH_REQUIRE(win_reducer >= 0 && win_reducer <= 3, XH_ERR_OP, "xh_spell_mask_f64: win_reducer %d not recognized", win_reducer);
   if (T == 0 || C == 0) return XH_OK;
   const bool ring = window <= WMAX;
-  const int vec = ring ? pick_vec(x, C, st) : 1;  // windows longer than the ring: one cell per lane (the grid follows)
+  const int vec = ring ? xh_pick_vec64(x, C, st) : 1;  // windows longer than the ring: one cell per lane (the grid follows)
   const int64_t cblocks = cdiv64(cdiv64(C, vec), XH_BLOCK);
   int64_t gy = cdiv64((int64_t)ctx->num_cu * 8, cblocks);
   if (gy < 1) gy = 1;
   if (gy > cdiv64(T, 64)) gy = cdiv64(T, 64);  // chunks of >= 64 rows: the halo stays a small share
   if (gy > 1024) gy = 1024;
   const dim3 grid((unsigned)cblocks, (unsigned)gy);
-#define XH_SM64(V, R, RG)                                                                                                 \
-  hipLaunchKernelGGL((k_spell_mask_f64<V, R, RG>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, T, C, st, window, op, thr, out, out_st)
-#define XH_SM64_R(R) { if (!ring) XH_SM64(1, R, false); else if (vec == 2) XH_SM64(2, R, true); else XH_SM64(1, R, true); }
-  switch (win_reducer) {
-    case 0: XH_SM64_R(XH_RED_SUM) break;
-    case 1: XH_SM64_R(XH_RED_MEAN) break;
-    case 2: XH_SM64_R(XH_RED_MIN) break;
-    default: XH_SM64_R(XH_RED_MAX) break;
-  }
-#undef XH_SM64_R
-#undef XH_SM64
+  // win_reducer 0 sum, 1 mean, 2 min, 3 max: the values of XH_RED_SUM .. XH_RED_MAX
+  xh_pick<XH_RED_SUM, XH_RED_MEAN, XH_RED_MIN, XH_RED_MAX>(win_reducer, [&](auto R) {
+    xh_pick<10, 21, 11>(ring ? vec * 10 + 1 : 10, [&](auto VR) {  // (cells per lane, register ring): the instances that exist
+      hipLaunchKernelGGL((k_spell_mask_f64<decltype(VR)::value / 10, decltype(R)::value, decltype(VR)::value % 10 != 0>), grid,
+                         dim3(XH_BLOCK), 0, ctx->stream, x, T, C, st, window, op, thr, out, out_st);
+    });
+  });
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
@@ -634,7 +622,7 @@ int xh_spell_mask_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int64_
 int xh_spell_run_stats_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int64_t st, int64_t sc, int window, int win_reducer,
                            int op, double thr, const double* weights, int stat, const int64_t* seg_off, int P, float* out,
                            int32_t* valid_out) {
-  int rc = check_field("xh_spell_run_stats_f64", ctx, x, T, C, st, sc);
+  int rc = xh_check_field("xh_spell_run_stats_f64", ctx, x, T, C, st, sc);
   if (rc) return rc;
   XH_REQUIRE(out, XH_ERR_ARG, "xh_spell_run_stats_f64: out is NULL");
   XH_REQUIRE(window >= 1, XH_ERR_ARG, "xh_spell_run_stats_f64: window must be >= 1");
@@ -651,29 +639,23 @@ int xh_spell_run_stats_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, i
   }
   size_t cur = 0;
   const int64_t* d_seg = nullptr;
-  rc = upload_segs(ctx, &cur, seg_off, P, T, "xh_spell_run_stats_f64", &d_seg);
+  rc = xh_upload_segments("xh_spell_run_stats_f64", ctx, &cur, seg_off, P, T, &d_seg);
   if (rc) return rc;
   if (C == 0) return XH_OK;
-  const unsigned py = (unsigned)(P > 4096 ? 4096 : P);
+  const unsigned py = xh_period_blocks(P);
   // two cells per lane (~155 VGPRs, 3 waves per SIMD) only when that still leaves >= 8 workgroups per CU; else one cell per
   // lane (~87 VGPRs, 5 waves per SIMD).  A period cannot be cut into time chunks, so the cells carry the parallelism.
-  const int vec = (pick_vec(x, C, st) == 2 && cdiv64(cdiv64(C, 2), XH_BLOCK) * (int64_t)py >= 8 * (int64_t)ctx->num_cu) ? 2 : 1;
+  const int vec = (xh_pick_vec64(x, C, st) == 2 && cdiv64(cdiv64(C, 2), XH_BLOCK) * (int64_t)py >= 8 * (int64_t)ctx->num_cu) ? 2 : 1;
   const int sg = stat_group(stat);
   const dim3 grid((unsigned)cdiv64(cdiv64(C, vec), XH_BLOCK), py);
-#define XH_SR64(V, R, G)                                                                                                 \
-  hipLaunchKernelGGL((k_spell_runs_f64<V, R, G>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, T, C, st, window, op, thr, stat, d_seg, \
-                     P, out, valid_out)
-#define XH_SR64_G(V, R) { if (sg == 1) XH_SR64(V, R, 1); else if (sg == 2) XH_SR64(V, R, 2); else XH_SR64(V, R, 0); }
-#define XH_SR64_R(R) { if (vec == 2) XH_SR64_G(2, R) else XH_SR64_G(1, R) }
-  switch (win_reducer) {
-    case 0: XH_SR64_R(XH_RED_SUM) break;
-    case 1: XH_SR64_R(XH_RED_MEAN) break;
-    case 2: XH_SR64_R(XH_RED_MIN) break;
-    default: XH_SR64_R(XH_RED_MAX) break;
-  }
-#undef XH_SR64_R
-#undef XH_SR64_G
-#undef XH_SR64
+  xh_pick<XH_RED_SUM, XH_RED_MEAN, XH_RED_MIN, XH_RED_MAX>(win_reducer, [&](auto R) {  // (as in xh_spell_mask_f64)
+    xh_pick<2, 1>(vec, [&](auto V) {
+      xh_pick<1, 2, 0>(sg, [&](auto G) {
+        hipLaunchKernelGGL((k_spell_runs_f64<decltype(V)::value, decltype(R)::value, decltype(G)::value>), grid, dim3(XH_BLOCK), 0,
+                           ctx->stream, x, T, C, st, window, op, thr, stat, d_seg, P, out, valid_out);
+      });
+    });
+  });
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
@@ -681,7 +663,7 @@ int xh_spell_run_stats_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, i
 int xh_run_stats_doy_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int64_t st, int64_t sc, int op, const double* table,
                          int D, const int32_t* tidx, int window, int stat, const int64_t* seg_off, int P, float* out,
                          int32_t* valid_out) {
-  int rc = check_field("xh_run_stats_doy_f64", ctx, x, T, C, st, sc);
+  int rc = xh_check_field("xh_run_stats_doy_f64", ctx, x, T, C, st, sc);
   if (rc) return rc;
   XH_REQUIRE(table && out && tidx, XH_ERR_ARG, "xh_run_stats_doy_f64: NULL argument");
   XH_REQUIRE(D >= 1, XH_ERR_ARG, "xh_run_stats_doy_f64: bad shape");
@@ -689,27 +671,26 @@ int xh_run_stats_doy_f64(xh_ctx* ctx, const double* x, int64_t T, int64_t C, int
   XH_REQUIRE(window >= 1, XH_ERR_ARG, "xh_run_stats_doy_f64: window must be >= 1");
   XH_REQUIRE((stat >= XH_RUN_MAX && stat <= XH_RUN_STD) || stat == XH_RUN_PLAINSUM, XH_ERR_OP,
              "xh_run_stats_doy_f64: statistic %d not supported (run-length reducers only)", stat);
-  for (int64_t t = 0; t < T; ++t)
-    XH_REQUIRE(tidx[t] >= 0 && tidx[t] < D, XH_ERR_ARG, "xh_run_stats_doy_f64: tidx[%lld] = %d outside the table (D = %d)",
-               (long long)t, tidx[t], D);
+  rc = xh_check_tidx("xh_run_stats_doy_f64", tidx, T, D);
+  if (rc) return rc;
   size_t cur = 0;
-  void* d_tidx = nullptr;
+  const int32_t* d_tidx = nullptr;
   const int64_t* d_seg = nullptr;
-  rc = upload_segs(ctx, &cur, seg_off, P, T, "xh_run_stats_doy_f64", &d_seg);
+  rc = xh_upload_segments("xh_run_stats_doy_f64", ctx, &cur, seg_off, P, T, &d_seg);
   if (rc) return rc;
   if (T > 0) {
-    rc = xh_scratch_upload(ctx, &cur, tidx, sizeof(int32_t) * (size_t)T, &d_tidx);
+    rc = xh_upload(ctx, &cur, tidx, (size_t)T, &d_tidx);
     if (rc) return rc;
   }
   if (C == 0) return XH_OK;
-  const int vec = (pick_vec(x, C, st) == 2 && (reinterpret_cast<uintptr_t>(table) & 15) == 0) ? 2 : 1;
-  const dim3 grid((unsigned)cdiv64(cdiv64(C, vec), XH_BLOCK), (unsigned)(P > 4096 ? 4096 : P));
+  const int vec = (xh_pick_vec64(x, C, st) == 2 && (reinterpret_cast<uintptr_t>(table) & 15) == 0) ? 2 : 1;
+  const dim3 grid = xh_period_grid(C, vec, P);
   if (vec == 2)
-    hipLaunchKernelGGL((k_run_stats_doy_f64<2>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, op, table, (const int32_t*)d_tidx,
-                       window, stat, d_seg, P, out, valid_out);
+    hipLaunchKernelGGL((k_run_stats_doy_f64<2>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, op, table, d_tidx, window, stat,
+                       d_seg, P, out, valid_out);
   else
-    hipLaunchKernelGGL((k_run_stats_doy_f64<1>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, op, table, (const int32_t*)d_tidx,
-                       window, stat, d_seg, P, out, valid_out);
+    hipLaunchKernelGGL((k_run_stats_doy_f64<1>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, op, table, d_tidx, window, stat,
+                       d_seg, P, out, valid_out);
   XH_LAUNCH_CHECK();
   return XH_OK;
 }

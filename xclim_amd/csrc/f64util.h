@@ -1,8 +1,10 @@
-// f64util.h — helpers shared by the float64 FIELD twins (f64run.hip, f64red.hip): the 2-element vector loads, the
-// double-buffered row marches, argument checks, the segment upload and the choice of two cells per lane.
+// f64util.h — device helpers shared by the float64 FIELD units (f64.hip, f64run.hip, f64red.hip): the 2-element vector loads,
+// the double-buffered row marches and the sort keys of a double.  Their host side (argument checks, uploads, cells per lane)
+// is hostargs.h.
 #pragma once
 
 #include "common.h"
+#include "hostargs.h"
 
 namespace {
 
@@ -100,30 +102,16 @@ __device__ __forceinline__ void march2(const TA* __restrict__ pa, int64_t sa, co
   for (; t < t1; ++t) f(t, ldv<VEC>(pa + t * sa), ldv<VEC>(pb + t * sb));
 }
 
-inline int check_field(const char* fn, xh_ctx* ctx, const void* x, int64_t T, int64_t C, int64_t st, int64_t sc) {
-  XH_REQUIRE(ctx && x, XH_ERR_ARG, "%s: NULL argument", fn);
-  XH_REQUIRE(T >= 0 && C >= 0, XH_ERR_ARG, "%s: negative shape", fn);
-  XH_REQUIRE(sc == 1 && st >= C, XH_ERR_LAYOUT, "%s: streaming kernels need a time-major view (sc == 1, st >= C); got st=%lld sc=%lld",
-             fn, (long long)st, (long long)sc);
-  return XH_OK;
+// order-preserving double <-> uint64 key (ascending; NaN maps to the largest key, so it sorts last like numpy)
+__device__ __forceinline__ uint64_t d2key(double d) {
+  const uint64_t u = (uint64_t)__double_as_longlong(d);
+  if (d != d) return ~0ull;
+  return (u >> 63) ? ~u : (u | (1ull << 63));
 }
-
-// validates the segment table (host), then copies it to the context's scratch: nothing touches the device before the checks
-inline int upload_segs(xh_ctx* ctx, size_t* cur, const int64_t* seg_off, int P, int64_t T, const char* fn, const int64_t** d_seg) {
-  XH_REQUIRE(seg_off && P >= 1, XH_ERR_ARG, "%s: seg_off NULL or P < 1", fn);
-  for (int p = 0; p < P; ++p)
-    XH_REQUIRE(seg_off[p] <= seg_off[p + 1] && seg_off[p] >= 0 && seg_off[p + 1] <= T, XH_ERR_ARG,
-               "%s: seg_off must be non-decreasing within [0, T]", fn);
-  void* d = nullptr;
-  const int rc = xh_scratch_upload(ctx, cur, seg_off, sizeof(int64_t) * (size_t)(P + 1), &d);
-  if (rc) return rc;
-  *d_seg = (const int64_t*)d;
-  return XH_OK;
-}
-
-// two cells per lane when the view allows 2-element vector loads of `esz`-byte elements
-inline int pick_vec(const void* p, int64_t C, int64_t st, size_t esz = 8) {
-  return ((reinterpret_cast<uintptr_t>(p) & (2 * esz - 1)) == 0 && (C % 2) == 0 && (st % 2) == 0) ? 2 : 1;
+__device__ __forceinline__ double key2d(uint64_t k) {
+  if (k == ~0ull) return xh_nan64();
+  const uint64_t u = (k >> 63) ? (k & ~(1ull << 63)) : ~k;
+  return __longlong_as_double((long long)u);
 }
 
 }  // namespace

@@ -24,6 +24,7 @@
 
 #include <type_traits>
 
+#include "hostargs.h"
 #include "pdoy.h"
 
 // Hyndman-Fan quantile from a sorted sample (ascending, NaN last).  `get(i)` returns sorted element i as float.

@@ -4,6 +4,7 @@
 // 64*VEC*4 contiguous bytes per time step (1 KiB at VEC = 4).  Periods (resample segments) are mapped to
 // blockIdx.y so that P periods give P-fold more workgroups.  All kernels are HBM-bound.
 #include "common.h"
+#include "hostargs.h"
 #include "window.h"
 
 // ---- threshold_count ------------------------------------------------------------------------------
@@ -71,28 +72,15 @@ template <int VEC>
 static int launch_threshold_count(xh_ctx* ctx, int kind, dim3 grid, const float* x, int64_t C, int64_t st, int op,
                                   double thr, const void* table, int64_t tstride, const int32_t* tidx,
                                   const int64_t* seg, int P, int32_t* count_out, int32_t* valid_out, int period_fast) {
-#define XH_TC(K)                                                                                                      \
-  case K:                                                                                                             \
-    hipLaunchKernelGGL((k_threshold_count<VEC, K>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, op, (float)thr, thr, \
-                       table, tstride, tidx, seg, P, count_out, valid_out, period_fast);                              \
-    break;
-  switch (kind) {
-    XH_TC(XH_THR_SCALAR_F32)
-    XH_TC(XH_THR_SCALAR_F64)
-    XH_TC(XH_THR_DOY_F64)
-    XH_TC(XH_THR_DOY_F32)
-    XH_TC(XH_THR_FULL_F64)
-    XH_TC(XH_THR_FULL_F32)
-    default:
-      xh_set_error("xh_threshold_count: unknown thr_kind %d", kind);
-      return XH_ERR_ARG;
-  }
-#undef XH_TC
+  const bool known = xh_pick<XH_THR_SCALAR_F32, XH_THR_SCALAR_F64, XH_THR_DOY_F64, XH_THR_DOY_F32, XH_THR_FULL_F64, XH_THR_FULL_F32>(
+      kind, [&](auto K) {
+        hipLaunchKernelGGL((k_threshold_count<VEC, decltype(K)::value>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, op,
+                           (float)thr, thr, table, tstride, tidx, seg, P, count_out, valid_out, period_fast);
+      });
+  XH_REQUIRE(known, XH_ERR_ARG, "xh_threshold_count: unknown thr_kind %d", kind);
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
-
-static inline unsigned period_grid(int P) { return (unsigned)(P < 1 ? 1 : (P > 4096 ? 4096 : P)); }
 
 // ---- threshold_count, per-doy fp64 table, one or two years (the tx90p chain) ---------------------------------------
 // k_threshold_count waits once per ROW on this path: the doy index of a row is a scalar load, the table row a dependent
@@ -345,19 +333,12 @@ k_resample_reduce(const float* __restrict__ x, int64_t C, int64_t st, int skipna
 template <int VEC>
 static int launch_resample_reduce(xh_ctx* ctx, int reducer, dim3 grid, const float* x, int64_t C, int64_t st, int skipna,
                                   const int64_t* seg, int P, void* out, int32_t* valid_out) {
-#define XH_RR(R)                                                                                                   \
-  case R:                                                                                                          \
-    hipLaunchKernelGGL((k_resample_reduce<VEC, R>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, skipna, seg, P, out, \
-                       valid_out);                                                                                 \
-    break;
-  switch (reducer) {
-    XH_RR(XH_RED_SUM) XH_RR(XH_RED_MEAN) XH_RR(XH_RED_MIN) XH_RR(XH_RED_MAX) XH_RR(XH_RED_STD) XH_RR(XH_RED_VAR)
-    XH_RR(XH_RED_COUNT) XH_RR(XH_RED_ARGMIN) XH_RR(XH_RED_ARGMAX)
-    default:
-      xh_set_error("xh_resample_reduce: reducer %d not recognized", reducer);
-      return XH_ERR_OP;
-  }
-#undef XH_RR
+  const bool known = xh_pick<XH_RED_SUM, XH_RED_MEAN, XH_RED_MIN, XH_RED_MAX, XH_RED_STD, XH_RED_VAR, XH_RED_COUNT, XH_RED_ARGMIN,
+                             XH_RED_ARGMAX>(reducer, [&](auto R) {
+    hipLaunchKernelGGL((k_resample_reduce<VEC, decltype(R)::value>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, skipna, seg, P,
+                       out, valid_out);
+  });
+  XH_REQUIRE(known, XH_ERR_OP, "xh_resample_reduce: reducer %d not recognized", reducer);
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
@@ -439,34 +420,6 @@ k_rolling_reduce(const float* __restrict__ x, int64_t T, int64_t C, int64_t st, 
   }
 }
 
-static int check_tc(const char* fn, xh_ctx* ctx, const void* x, int64_t T, int64_t C, int64_t st, int64_t sc) {
-  XH_REQUIRE(ctx && x, XH_ERR_ARG, "%s: NULL argument", fn);
-  XH_REQUIRE(T >= 0 && C >= 0, XH_ERR_ARG, "%s: negative shape", fn);
-  XH_REQUIRE(sc == 1 && st >= C, XH_ERR_LAYOUT,
-             "%s: streaming kernels need a time-major view (sc == 1, st >= C); got st=%lld sc=%lld — transpose first",
-             fn, (long long)st, (long long)sc);
-  return XH_OK;
-}
-
-static int check_segments(const int64_t* seg_off, int P, int64_t T, const char* fn) {
-  XH_REQUIRE(seg_off && P >= 1, XH_ERR_ARG, "%s: seg_off NULL or P < 1", fn);
-  for (int p = 0; p < P; ++p)
-    XH_REQUIRE(seg_off[p] <= seg_off[p + 1] && seg_off[p] >= 0 && seg_off[p + 1] <= T, XH_ERR_ARG,
-               "%s: seg_off must be non-decreasing within [0, T]", fn);
-  return XH_OK;
-}
-
-static int upload_segments(xh_ctx* ctx, size_t* cur, const int64_t* seg_off, int P, int64_t T, const char* fn,
-                           const int64_t** d_seg) {
-  int rc = check_segments(seg_off, P, T, fn);
-  if (rc) return rc;
-  void* d = nullptr;
-  rc = xh_scratch_upload(ctx, cur, seg_off, sizeof(int64_t) * (size_t)(P + 1), &d);
-  if (rc) return rc;
-  *d_seg = (const int64_t*)d;
-  return XH_OK;
-}
-
 // d_seg == NULL: the period bounds travel in the kernel arguments (P <= XH_SEG_ARG_MAX)
 static int launch_tcount_year(xh_ctx* ctx, dim3 grid, const float* x, int64_t C, int64_t st, int op, const double* table,
                               int64_t tstride, const int32_t* tidx, const int64_t* d_seg, const int64_t* h_seg, int P,
@@ -474,18 +427,12 @@ static int launch_tcount_year(xh_ctx* ctx, dim3 grid, const float* x, int64_t C,
   XhSegArg sv;
   memset(&sv, 0, sizeof(sv));
   if (!d_seg) memcpy(sv.off, h_seg, sizeof(int64_t) * (size_t)(P + 1));
-#define XH_TCY2(OPV, BYVAL)                                                                                              \
-  hipLaunchKernelGGL((k_tcount_year<OPV, BYVAL>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, table, tstride, tidx, d_seg, \
-                     sv, P, count_out, valid_out, period_fast)
-#define XH_TCY(OPV)                                  \
-  case OPV:                                          \
-    if (d_seg) XH_TCY2(OPV, false); else XH_TCY2(OPV, true); \
-    break;
-  switch (op) {
-    XH_TCY(XH_OP_GT) XH_TCY(XH_OP_LT) XH_TCY(XH_OP_GE) XH_TCY(XH_OP_LE) XH_TCY(XH_OP_EQ) XH_TCY(XH_OP_NE)
-  }
-#undef XH_TCY
-#undef XH_TCY2
+  xh_pick<XH_OP_GT, XH_OP_LT, XH_OP_GE, XH_OP_LE, XH_OP_EQ, XH_OP_NE>(op, [&](auto OP) {
+    xh_pick<0, 1>(d_seg ? 0 : 1, [&](auto BYVAL) {
+      hipLaunchKernelGGL((k_tcount_year<decltype(OP)::value, decltype(BYVAL)::value != 0>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C,
+                         st, table, tstride, tidx, d_seg, sv, P, count_out, valid_out, period_fast);
+    });
+  });
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
@@ -495,17 +442,18 @@ extern "C" {
 static int threshold_count_impl(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, int64_t sc, int op, int thr_kind,
                                 double thr_scalar, const void* thr_table, int64_t thr_stride, const int32_t* tidx,
                                 const int64_t* seg_off, int P, int32_t* count_out, int32_t* valid_out, int ndoy) {
-  int rc = check_tc("xh_threshold_count", ctx, x, T, C, st, sc);
+  int rc = xh_check_field("xh_threshold_count", ctx, x, T, C, st, sc);
   if (rc) return rc;
   XH_REQUIRE(op >= XH_OP_GT && op <= XH_OP_NE, XH_ERR_OP, "Operation `%d` not recognized.", op);
   XH_REQUIRE(count_out, XH_ERR_ARG, "xh_threshold_count: count_out is NULL");
   if (thr_kind >= XH_THR_DOY_F64) {
     XH_REQUIRE(thr_table, XH_ERR_ARG, "xh_threshold_count: threshold table missing");
-    XH_REQUIRE(thr_stride >= C, XH_ERR_LAYOUT, "xh_threshold_count: needs time-major rows of at least the row width (thr_stride)");
+    rc = xh_check_rows("xh_threshold_count", thr_stride, C, "thr_stride");
+    if (rc) return rc;
     if (thr_kind == XH_THR_DOY_F64 || thr_kind == XH_THR_DOY_F32)
       XH_REQUIRE(tidx, XH_ERR_ARG, "xh_threshold_count: tidx required for per-doy thresholds");
   }
-  rc = check_segments(seg_off, P, T, "xh_threshold_count");
+  rc = xh_check_segments("xh_threshold_count", seg_off, P, T);
   if (rc) return rc;
   size_t cur = 0;
   const int64_t* d_seg = nullptr;
@@ -517,7 +465,7 @@ static int threshold_count_impl(xh_ctx* ctx, const float* x, int64_t T, int64_t 
     size_t lds = 0;
     int narrow = 0;
     if (xh_tcount_plan(T, C, st, op, P, ndoy, longest, &lds, &narrow) == XH_OK) {  // (else: no upload before the choice below)
-      rc = upload_segments(ctx, &cur, seg_off, P, T, "xh_threshold_count", &d_seg);
+      rc = xh_upload_segments("xh_threshold_count", ctx, &cur, seg_off, P, T, &d_seg);
       if (rc) return rc;
       rc = xh_launch_tcount_doy(ctx, x, T, C, st, op, static_cast<const double*>(thr_table), thr_stride, tidx, d_seg, seg_off, P,
                                 ndoy, count_out, valid_out);
@@ -533,14 +481,14 @@ static int threshold_count_impl(xh_ctx* ctx, const float* x, int64_t T, int64_t 
   // XH_TCOUNT_LEGACY / XH_TCOUNT_ROWWISE (diagnostics) keep k_threshold_count, which is also the fallback for VEC = 1
   const bool year = thr_kind == XH_THR_DOY_F64 && vec == 4 && !legacy && !xh_diag_env("XH_TCOUNT_ROWWISE");
   if (!d_seg && !(year && P <= XH_SEG_ARG_MAX)) {
-    rc = upload_segments(ctx, &cur, seg_off, P, T, "xh_threshold_count", &d_seg);
+    rc = xh_upload_segments("xh_threshold_count", ctx, &cur, seg_off, P, T, &d_seg);
     if (rc) return rc;
   }
   if (C == 0) return XH_OK;
   unsigned tiles = (unsigned)cdiv64(cdiv64(C, vec), XH_BLOCK);
   const bool doy = thr_kind == XH_THR_DOY_F64 || thr_kind == XH_THR_DOY_F32;
   const int period_fast = (doy && P > 1 && tiles <= 65535u) ? 1 : 0;
-  dim3 grid = period_fast ? dim3(period_grid(P), tiles) : dim3(tiles, period_grid(P));
+  dim3 grid = period_fast ? dim3(xh_period_blocks(P), tiles) : dim3(tiles, xh_period_blocks(P));
   if (year)
     return launch_tcount_year(ctx, grid, x, C, st, op, static_cast<const double*>(thr_table), thr_stride, tidx, d_seg, seg_off, P,
                               count_out, valid_out, period_fast);
@@ -569,7 +517,7 @@ int xh_threshold_count_doy(xh_ctx* ctx, const float* x, int64_t T, int64_t C, in
 int xh_domain_count(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, int64_t sc, int op1, double thr1,
                     int op2, double thr2, int combine, const int64_t* seg_off, int P, int32_t* count_out,
                     int32_t* valid_out) {
-  int rc = check_tc("xh_domain_count", ctx, x, T, C, st, sc);
+  int rc = xh_check_field("xh_domain_count", ctx, x, T, C, st, sc);
   if (rc) return rc;
   XH_REQUIRE(op1 >= XH_OP_GT && op1 <= XH_OP_NE && op2 >= XH_OP_GT && op2 <= XH_OP_NE, XH_ERR_OP,
              "Operation `%d/%d` not recognized.", op1, op2);
@@ -577,11 +525,11 @@ int xh_domain_count(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t s
   XH_REQUIRE(count_out, XH_ERR_ARG, "xh_domain_count: count_out is NULL");
   size_t cur = 0;
   const int64_t* d_seg = nullptr;
-  rc = upload_segments(ctx, &cur, seg_off, P, T, "xh_domain_count", &d_seg);
+  rc = xh_upload_segments("xh_domain_count", ctx, &cur, seg_off, P, T, &d_seg);
   if (rc) return rc;
   if (C == 0) return XH_OK;
   int vec = xh_pick_vec(x, C, st);
-  dim3 grid((unsigned)cdiv64(cdiv64(C, vec), XH_BLOCK), period_grid(P));
+  const dim3 grid = xh_period_grid(C, vec, P);
   const XhOneCmp c1 = xh_one_cmp(op1, (float)thr1), c2 = xh_one_cmp(op2, (float)thr2);
   if (vec == 4 && c1.ok && c2.ok) {
     int s1, s2;
@@ -601,16 +549,16 @@ int xh_domain_count(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t s
 
 int xh_resample_reduce(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, int64_t sc, int reducer, int skipna,
                        const int64_t* seg_off, int P, void* out, int32_t* valid_out) {
-  int rc = check_tc("xh_resample_reduce", ctx, x, T, C, st, sc);
+  int rc = xh_check_field("xh_resample_reduce", ctx, x, T, C, st, sc);
   if (rc) return rc;
   XH_REQUIRE(out, XH_ERR_ARG, "xh_resample_reduce: out is NULL");
   size_t cur = 0;
   const int64_t* d_seg = nullptr;
-  rc = upload_segments(ctx, &cur, seg_off, P, T, "xh_resample_reduce", &d_seg);
+  rc = xh_upload_segments("xh_resample_reduce", ctx, &cur, seg_off, P, T, &d_seg);
   if (rc) return rc;
   if (C == 0) return XH_OK;
   int vec = xh_pick_vec(x, C, st);
-  dim3 grid((unsigned)cdiv64(cdiv64(C, vec), XH_BLOCK), period_grid(P));
+  const dim3 grid = xh_period_grid(C, vec, P);
   if (vec == 4) return launch_resample_reduce<4>(ctx, reducer, grid, x, C, st, skipna, d_seg, P, out, valid_out);
   return launch_resample_reduce<1>(ctx, reducer, grid, x, C, st, skipna, d_seg, P, out, valid_out);
 }
@@ -640,10 +588,11 @@ int xh_apply_missing_mask(xh_ctx* ctx, const void* value, int value_kind, const 
 
 int xh_rolling_reduce(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, int64_t sc, int window, int center,
                       int reducer, float* out, int64_t out_st) {
-  int rc = check_tc("xh_rolling_reduce", ctx, x, T, C, st, sc);
+  int rc = xh_check_field("xh_rolling_reduce", ctx, x, T, C, st, sc);
   if (rc) return rc;
   XH_REQUIRE(out, XH_ERR_ARG, "xh_rolling_reduce: out NULL");
-  XH_REQUIRE(out_st >= C, XH_ERR_LAYOUT, "xh_rolling_reduce: needs time-major rows of at least the row width (out_st)");
+  rc = xh_check_rows("xh_rolling_reduce", out_st, C, "out_st");
+  if (rc) return rc;
   XH_REQUIRE(window >= 1, XH_ERR_ARG, "xh_rolling_reduce: window must be >= 1");
   if (T == 0 || C == 0) return XH_OK;
   // xarray: center=True -> window covers [t - w//2, t + w - 1 - w//2]; else trailing [t - w + 1, t]
@@ -655,19 +604,11 @@ int xh_rolling_reduce(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t
   }
   unsigned ny = (unsigned)(T < 64 ? T : 64);
   dim3 grid((unsigned)cdiv64(C, XH_BLOCK), ny);
-#define XH_RO(R)                                                                                                      \
-  case R:                                                                                                             \
-    hipLaunchKernelGGL((k_rolling_reduce<R>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, T, C, st, window, left, right, out, \
-                       out_st);                                                                                       \
-    break;
-  switch (reducer) {
-    XH_RO(XH_RED_SUM) XH_RO(XH_RED_MEAN) XH_RO(XH_RED_MIN) XH_RO(XH_RED_MAX) XH_RO(XH_RED_STD) XH_RO(XH_RED_VAR)
-    XH_RO(XH_RED_COUNT)
-    default:
-      xh_set_error("xh_rolling_reduce: reducer %d not recognized", reducer);
-      return XH_ERR_OP;
-  }
-#undef XH_RO
+  const bool known = xh_pick<XH_RED_SUM, XH_RED_MEAN, XH_RED_MIN, XH_RED_MAX, XH_RED_STD, XH_RED_VAR, XH_RED_COUNT>(reducer, [&](auto R) {
+    hipLaunchKernelGGL((k_rolling_reduce<decltype(R)::value>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, T, C, st, window, left, right,
+                       out, out_st);
+  });
+  XH_REQUIRE(known, XH_ERR_OP, "xh_rolling_reduce: reducer %d not recognized", reducer);
   XH_LAUNCH_CHECK();
   return XH_OK;
 }

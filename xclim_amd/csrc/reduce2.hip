@@ -2,6 +2,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "hostargs.h"
 #include "pdoy.h"
 
 // ---- bivariate counts ---------------------------------------------------------------------------------------
@@ -163,45 +164,27 @@ k_mask_rows(const float* __restrict__ x, int64_t C, int64_t st, const int64_t* _
   }
 }
 
-static int chk2(const char* fn, xh_ctx* ctx, const void* x, int64_t T, int64_t C, int64_t st, int64_t sc) {
-  XH_REQUIRE(ctx && x, XH_ERR_ARG, "%s: NULL argument", fn);
-  XH_REQUIRE(T >= 0 && C >= 0, XH_ERR_ARG, "%s: negative shape", fn);
-  XH_REQUIRE(sc == 1 && st >= C, XH_ERR_LAYOUT, "%s: needs a time-major view (sc == 1, st >= C)", fn);
-  return XH_OK;
-}
-
-static int up_seg(xh_ctx* ctx, size_t* cur, const int64_t* seg_off, int P, int64_t T, const char* fn, const int64_t** d_seg) {
-  XH_REQUIRE(seg_off && P >= 1, XH_ERR_ARG, "%s: seg_off NULL or P < 1", fn);
-  for (int p = 0; p < P; ++p)
-    XH_REQUIRE(seg_off[p] <= seg_off[p + 1] && seg_off[p] >= 0 && seg_off[p + 1] <= T, XH_ERR_ARG,
-               "%s: seg_off must be non-decreasing within [0, T]", fn);
-  void* d = nullptr;
-  int rc = xh_scratch_upload(ctx, cur, seg_off, sizeof(int64_t) * (size_t)(P + 1), &d);
-  if (rc) return rc;
-  *d_seg = (const int64_t*)d;
-  return XH_OK;
-}
-
 extern "C" {
 
 int xh_bivariate_count(xh_ctx* ctx, const float* x1, const float* x2, int64_t T, int64_t C, int64_t st1, int64_t st2,
                        int op1, double thr1, int op2, double thr2, int combine, const int64_t* seg_off, int P,
                        int32_t* count_out, int32_t* valid_out) {
-  int rc = chk2("xh_bivariate_count", ctx, x1, T, C, st1, 1);
+  int rc = xh_check_field("xh_bivariate_count", ctx, x1, T, C, st1, 1);
   if (rc) return rc;
   XH_REQUIRE(x2, XH_ERR_ARG, "xh_bivariate_count: x2 NULL");
-  XH_REQUIRE(st2 >= C, XH_ERR_LAYOUT, "xh_bivariate_count: needs time-major rows of at least the row width (st2)");
+  rc = xh_check_rows("xh_bivariate_count", st2, C, "st2");
+  if (rc) return rc;
   XH_REQUIRE(op1 >= XH_OP_GT && op1 <= XH_OP_NE && op2 >= XH_OP_GT && op2 <= XH_OP_NE, XH_ERR_OP,
              "Operation `%d/%d` not recognized.", op1, op2);
   XH_REQUIRE(combine == 1 || combine == 2, XH_ERR_ARG, "xh_bivariate_count: combine must be 1 (all) or 2 (any)");
   XH_REQUIRE(count_out, XH_ERR_ARG, "xh_bivariate_count: count_out is NULL");
   size_t cur = 0;
   const int64_t* d_seg = nullptr;
-  rc = up_seg(ctx, &cur, seg_off, P, T, "xh_bivariate_count", &d_seg);
+  rc = xh_upload_segments("xh_bivariate_count", ctx, &cur, seg_off, P, T, &d_seg);
   if (rc) return rc;
   if (C == 0) return XH_OK;
   int vec = (xh_pick_vec(x1, C, st1) == 4 && xh_pick_vec(x2, C, st2) == 4) ? 4 : 1;
-  dim3 grid((unsigned)cdiv64(cdiv64(C, vec), XH_BLOCK), (unsigned)(P > 4096 ? 4096 : P));
+  const dim3 grid = xh_period_grid(C, vec, P);
   if (vec == 4)
     hipLaunchKernelGGL((k_bivariate_count<4>), grid, dim3(XH_BLOCK), 0, ctx->stream, x1, x2, C, st1, st2, op1, (float)thr1,
                        op2, (float)thr2, combine, d_seg, P, count_out, valid_out);
@@ -214,7 +197,7 @@ int xh_bivariate_count(xh_ctx* ctx, const float* x1, const float* x2, int64_t T,
 
 int xh_thresholded_reduce(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, int64_t sc, int op, double thr,
                           int mode, int reducer, const int64_t* seg_off, int P, float* out, int32_t* valid_out) {
-  int rc = chk2("xh_thresholded_reduce", ctx, x, T, C, st, sc);
+  int rc = xh_check_field("xh_thresholded_reduce", ctx, x, T, C, st, sc);
   if (rc) return rc;
   XH_REQUIRE(op >= XH_OP_GT && op <= XH_OP_NE, XH_ERR_OP, "Operation `%d` not recognized.", op);
   XH_REQUIRE(mode >= 0 && mode <= 2, XH_ERR_ARG, "xh_thresholded_reduce: mode must be 0, 1 or 2");
@@ -224,11 +207,11 @@ int xh_thresholded_reduce(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int
   XH_REQUIRE(out, XH_ERR_ARG, "xh_thresholded_reduce: out is NULL");
   size_t cur = 0;
   const int64_t* d_seg = nullptr;
-  rc = up_seg(ctx, &cur, seg_off, P, T, "xh_thresholded_reduce", &d_seg);
+  rc = xh_upload_segments("xh_thresholded_reduce", ctx, &cur, seg_off, P, T, &d_seg);
   if (rc) return rc;
   if (C == 0) return XH_OK;
   int vec = xh_pick_vec(x, C, st);
-  dim3 grid((unsigned)cdiv64(cdiv64(C, vec), XH_BLOCK), (unsigned)(P > 4096 ? 4096 : P));
+  const dim3 grid = xh_period_grid(C, vec, P);
   if (vec == 4)
     hipLaunchKernelGGL((k_thresholded_reduce<4>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, op, (float)thr, mode,
                        reducer, d_seg, P, out, valid_out);
@@ -241,30 +224,30 @@ int xh_thresholded_reduce(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int
 
 int xh_mask_rows(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, int64_t sc, const int64_t* seg_off, int P,
                  const int32_t* lo, const int32_t* hi, int invert, float* out, int64_t out_st) {
-  int rc = chk2("xh_mask_rows", ctx, x, T, C, st, sc);
+  int rc = xh_check_field("xh_mask_rows", ctx, x, T, C, st, sc);
   if (rc) return rc;
   XH_REQUIRE(lo && hi && out, XH_ERR_ARG, "xh_mask_rows: NULL argument");
-  XH_REQUIRE(out_st >= C, XH_ERR_LAYOUT, "xh_mask_rows: needs time-major rows of at least the row width (out_st)");
+  rc = xh_check_rows("xh_mask_rows", out_st, C, "out_st");
+  if (rc) return rc;
   size_t cur = 0;
   const int64_t* d_seg = nullptr;
-  rc = up_seg(ctx, &cur, seg_off, P, T, "xh_mask_rows", &d_seg);
+  rc = xh_upload_segments("xh_mask_rows", ctx, &cur, seg_off, P, T, &d_seg);
   if (rc) return rc;
-  void *d_lo = nullptr, *d_hi = nullptr;
-  rc = xh_scratch_upload(ctx, &cur, lo, sizeof(int32_t) * (size_t)P, &d_lo);
+  const int32_t *d_lo = nullptr, *d_hi = nullptr;
+  rc = xh_upload(ctx, &cur, lo, (size_t)P, &d_lo);
   if (rc) return rc;
-  rc = xh_scratch_upload(ctx, &cur, hi, sizeof(int32_t) * (size_t)P, &d_hi);
+  rc = xh_upload(ctx, &cur, hi, (size_t)P, &d_hi);
   if (rc) return rc;
   if (C == 0) return XH_OK;
-  dim3 grid((unsigned)cdiv64(C, XH_BLOCK), (unsigned)(P > 4096 ? 4096 : P));
-  hipLaunchKernelGGL(k_mask_rows, grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, d_seg, P, (const int32_t*)d_lo,
-                     (const int32_t*)d_hi, invert, out, out_st);
+  const dim3 grid = xh_period_grid(C, 1, P);
+  hipLaunchKernelGGL(k_mask_rows, grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, d_seg, P, d_lo, d_hi, invert, out, out_st);
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
 
 int xh_doy_mean_std(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, int64_t sc, const int32_t* tbase,
                     int nyears, int ndoy, int window, float* mean_out, float* std_out) {
-  int rc = chk2("xh_doy_mean_std", ctx, x, T, C, st, sc);
+  int rc = xh_check_field("xh_doy_mean_std", ctx, x, T, C, st, sc);
   if (rc) return rc;
   XH_REQUIRE(tbase && mean_out && std_out, XH_ERR_ARG, "xh_doy_mean_std: NULL argument");
   XH_REQUIRE(nyears >= 1 && ndoy >= 1 && window >= 1, XH_ERR_ARG, "xh_doy_mean_std: bad shape");
@@ -310,11 +293,10 @@ int xh_doy_mean_std(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t s
   }
   const int nloop = generic_all ? ndoy : ndl;
   dim3 grid((unsigned)cdiv64(C, XH_BLOCK), (unsigned)(nloop > 1024 ? 1024 : nloop));
-#define XH_DMS(W)                                                                                                        \
-  hipLaunchKernelGGL((k_doy_mean_std<W>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, T, C, st, (const int32_t*)d_tb, nyears, ndoy, \
-                     window, mean_out, std_out, generic_all ? (const int32_t*)nullptr : d_list, ndl)
-  if (window == 5) XH_DMS(5); else if (window == 3) XH_DMS(3); else if (window == 7) XH_DMS(7); else XH_DMS(0);
-#undef XH_DMS
+  xh_pick<5, 3, 7, 0>((window == 5 || window == 3 || window == 7) ? window : 0, [&](auto W) {
+    hipLaunchKernelGGL((k_doy_mean_std<decltype(W)::value>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, T, C, st, (const int32_t*)d_tb,
+                       nyears, ndoy, window, mean_out, std_out, generic_all ? (const int32_t*)nullptr : d_list, ndl);
+  });
   XH_LAUNCH_CHECK();
   return XH_OK;
 }

@@ -13,6 +13,7 @@
 // Layout: time-major (T, C); a lane owns VEC consecutive cells; state lives in registers; HBM traffic is the
 // compulsory 4 B per cell-timestep read plus the (P, C) outputs.
 #include "common.h"
+#include "hostargs.h"
 
 #include "runacc.h"
 
@@ -379,15 +380,6 @@ k_cumsum_rle(const float* __restrict__ x, int64_t T, int64_t C, int64_t st, int 
   }
 }
 
-static int check_tc2(const char* fn, xh_ctx* ctx, const void* x, int64_t T, int64_t C, int64_t st, int64_t sc) {
-  XH_REQUIRE(ctx && x, XH_ERR_ARG, "%s: NULL argument", fn);
-  XH_REQUIRE(T >= 0 && C >= 0, XH_ERR_ARG, "%s: negative shape", fn);
-  XH_REQUIRE(sc == 1 && st >= C, XH_ERR_LAYOUT,
-             "%s: streaming kernels need a time-major view (sc == 1, st >= C); got st=%lld sc=%lld — transpose first",
-             fn, (long long)st, (long long)sc);
-  return XH_OK;
-}
-
 // Percentile-spell indices (warm / cold_spell_duration_index, indices/_multivariate.py:66-152, 1693-1793) with
 // resample_before_rl: the daily condition x[t] op table[tidx[t]] (fp64 compare against the per-doy percentile, i.e.
 // compare(da, op, resample_doy(per, da))) feeds the run state machine directly — neither the (T, C) fp64 threshold
@@ -438,10 +430,11 @@ extern "C" {
 
 int xh_cumsum_reset(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, int64_t sc, int index_first,
                     float* out, int64_t out_st) {
-  int rc = check_tc2("xh_cumsum_reset", ctx, x, T, C, st, sc);
+  int rc = xh_check_field("xh_cumsum_reset", ctx, x, T, C, st, sc);
   if (rc) return rc;
   XH_REQUIRE(out, XH_ERR_ARG, "xh_cumsum_reset: out NULL");
-  XH_REQUIRE(out_st >= C, XH_ERR_LAYOUT, "xh_cumsum_reset: needs time-major rows of at least the row width (out_st)");
+  rc = xh_check_rows("xh_cumsum_reset", out_st, C, "out_st");
+  if (rc) return rc;
   if (T == 0 || C == 0) return XH_OK;
   hipLaunchKernelGGL((k_cumsum_rle<0>), dim3((unsigned)cdiv64(C, XH_BLOCK)), dim3(XH_BLOCK), 0, ctx->stream, x, T, C, st,
                      index_first, out, out_st);
@@ -451,10 +444,11 @@ int xh_cumsum_reset(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t s
 
 int xh_rle(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, int64_t sc, int index_first, float* out,
            int64_t out_st) {
-  int rc = check_tc2("xh_rle", ctx, x, T, C, st, sc);
+  int rc = xh_check_field("xh_rle", ctx, x, T, C, st, sc);
   if (rc) return rc;
   XH_REQUIRE(out, XH_ERR_ARG, "xh_rle: out NULL");
-  XH_REQUIRE(out_st >= C, XH_ERR_LAYOUT, "xh_rle: needs time-major rows of at least the row width (out_st)");
+  rc = xh_check_rows("xh_rle", out_st, C, "out_st");
+  if (rc) return rc;
   if (T == 0 || C == 0) return XH_OK;
   hipLaunchKernelGGL((k_cumsum_rle<1>), dim3((unsigned)cdiv64(C, XH_BLOCK)), dim3(XH_BLOCK), 0, ctx->stream, x, T, C, st,
                      index_first, out, out_st);
@@ -465,56 +459,41 @@ int xh_rle(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, int64_
 int xh_run_stats(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, int64_t sc, int fused_op, double thr,
                  int window, int stat, int index_first, const int64_t* seg_off, int P, int cut_at_segments, float* out,
                  int32_t* valid_out) {
-  int rc = check_tc2("xh_run_stats", ctx, x, T, C, st, sc);
+  int rc = xh_check_field("xh_run_stats", ctx, x, T, C, st, sc);
   if (rc) return rc;
   XH_REQUIRE(fused_op <= XH_OP_NE, XH_ERR_OP, "Operation `%d` not recognized.", fused_op);
   XH_REQUIRE(window >= 1, XH_ERR_ARG, "xh_run_stats: window must be >= 1");
   XH_REQUIRE(stat >= XH_RUN_MAX && stat <= XH_RUN_PLAINSUM, XH_ERR_OP, "xh_run_stats: stat %d not recognized", stat);
-  XH_REQUIRE(out && seg_off && P >= 1, XH_ERR_ARG, "xh_run_stats: NULL out/seg_off or P < 1");
-  for (int p = 0; p < P; ++p)
-    XH_REQUIRE(seg_off[p] <= seg_off[p + 1] && seg_off[p] >= 0 && seg_off[p + 1] <= T, XH_ERR_ARG,
-               "xh_run_stats: seg_off must be non-decreasing within [0, T]");
+  XH_REQUIRE(out, XH_ERR_ARG, "xh_run_stats: out NULL");
   size_t cur = 0;
-  void* d = nullptr;
-  rc = xh_scratch_upload(ctx, &cur, seg_off, sizeof(int64_t) * (size_t)(P + 1), &d);
+  const int64_t* d_seg = nullptr;
+  rc = xh_upload_segments("xh_run_stats", ctx, &cur, seg_off, P, T, &d_seg);
   if (rc) return rc;
-  const int64_t* d_seg = (const int64_t*)d;
   if (C == 0) return XH_OK;
-  unsigned py = (unsigned)(P > 4096 ? 4096 : P);
+  const unsigned py = xh_period_blocks(P);
   if (stat == XH_RUN_FIRST || stat == XH_RUN_LAST) {
     const int bvec = (xh_pick_vec(x, C, st) == 4 && cdiv64(cdiv64(C, 4), XH_BLOCK) * (cut_at_segments ? py : 1u) >= 2u * (unsigned)ctx->num_cu) ? 4 : 1;
     dim3 grid((unsigned)cdiv64(cdiv64(C, bvec), XH_BLOCK), cut_at_segments ? py : 1u);
-#define XH_BR(V, F, CU)                                                                                                 \
-  hipLaunchKernelGGL((k_boundary_run<V, F, CU>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, fused_op, (float)thr, window, \
-                     d_seg, P, out, valid_out)
-    const bool first = stat == XH_RUN_FIRST;
-    if (bvec == 4) {
-      if (first) { if (cut_at_segments) XH_BR(4, true, true); else XH_BR(4, true, false); }
-      else { if (cut_at_segments) XH_BR(4, false, true); else XH_BR(4, false, false); }
-    } else {
-      if (first) { if (cut_at_segments) XH_BR(1, true, true); else XH_BR(1, true, false); }
-      else { if (cut_at_segments) XH_BR(1, false, true); else XH_BR(1, false, false); }
-    }
-#undef XH_BR
+    xh_pick<4, 1>(bvec, [&](auto V) {
+      xh_pick<1, 0>(stat == XH_RUN_FIRST ? 1 : 0, [&](auto FIRST) {
+        xh_pick<1, 0>(cut_at_segments ? 1 : 0, [&](auto CUT) {
+          hipLaunchKernelGGL((k_boundary_run<decltype(V)::value, decltype(FIRST)::value != 0, decltype(CUT)::value != 0>), grid,
+                             dim3(XH_BLOCK), 0, ctx->stream, x, C, st, fused_op, (float)thr, window, d_seg, P, out, valid_out);
+        });
+      });
+    });
     XH_LAUNCH_CHECK();
     return XH_OK;
   }
   int vec = xh_pick_vec(x, C, st);
   if (cut_at_segments && fused_op >= 0 && stat == XH_RUN_MAX) {
     dim3 grid((unsigned)cdiv64(cdiv64(C, vec), XH_BLOCK), py);
-#define XH_RMF(V, O)                                                                                                   \
-  case O:                                                                                                              \
-    hipLaunchKernelGGL((k_run_max_fused<V, O>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, (float)thr, window, d_seg, \
-                       P, out, valid_out);                                                                             \
-    break;
-    if (vec == 4) {
-      switch (fused_op) { XH_RMF(4, XH_OP_GT) XH_RMF(4, XH_OP_LT) XH_RMF(4, XH_OP_GE) XH_RMF(4, XH_OP_LE) XH_RMF(4, XH_OP_EQ)
-        XH_RMF(4, XH_OP_NE) }
-    } else {
-      switch (fused_op) { XH_RMF(1, XH_OP_GT) XH_RMF(1, XH_OP_LT) XH_RMF(1, XH_OP_GE) XH_RMF(1, XH_OP_LE) XH_RMF(1, XH_OP_EQ)
-        XH_RMF(1, XH_OP_NE) }
-    }
-#undef XH_RMF
+    xh_pick<4, 1>(vec, [&](auto V) {
+      xh_pick<XH_OP_GT, XH_OP_LT, XH_OP_GE, XH_OP_LE, XH_OP_EQ, XH_OP_NE>(fused_op, [&](auto O) {
+        hipLaunchKernelGGL((k_run_max_fused<decltype(V)::value, decltype(O)::value>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st,
+                           (float)thr, window, d_seg, P, out, valid_out);
+      });
+    });
     XH_LAUNCH_CHECK();
     return XH_OK;
   }
@@ -524,26 +503,20 @@ int xh_run_stats(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, 
     // mode and statistic group at compile time)
     dim3 grid((unsigned)cdiv64(cdiv64(C, vec), XH_BLOCK), py);
     const int sg = stat == XH_RUN_MAX ? 1 : ((stat == XH_RUN_SUM || stat == XH_RUN_COUNT || stat == XH_RUN_MEAN) ? 2 : 0);
-#define XH_RSM(V, I, G)                                                                                                \
-  hipLaunchKernelGGL((k_run_stats_mask<V, I, G>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, window, stat, d_seg, P, out, \
-                     valid_out, 1.0f, 0.0f)
-#define XH_RSF(V, I, G)                                                                                                \
-  hipLaunchKernelGGL((k_run_stats_mask<V, I, G, true>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, window, stat, d_seg, P, \
-                     out, valid_out, oc.sgn, oc.thr)
-#define XH_RSM_G(V, I) { if (sg == 1) XH_RSM(V, I, 1); else if (sg == 2) XH_RSM(V, I, 2); else XH_RSM(V, I, 0); }
-#define XH_RSF_G(V, I) { if (sg == 1) XH_RSF(V, I, 1); else if (sg == 2) XH_RSF(V, I, 2); else XH_RSF(V, I, 0); }
-#define XH_RSM_I(V)                                                                         \
-  {                                                                                         \
-    if (fused_op >= 0) { if (index_first == 3) XH_RSF_G(V, 3) else XH_RSF_G(V, 2) }         \
-    else if (index_first == 0) XH_RSM_G(V, 0) else if (index_first == 1) XH_RSM_G(V, 1)     \
-    else if (index_first == 2) XH_RSM_G(V, 2) else XH_RSM_G(V, 3)                           \
-  }
-    if (vec == 4) XH_RSM_I(4) else XH_RSM_I(1)
-#undef XH_RSM_I
-#undef XH_RSM_G
-#undef XH_RSF_G
-#undef XH_RSM
-#undef XH_RSF
+    xh_pick<4, 1>(vec, [&](auto V) {
+      xh_pick<1, 2, 0>(sg, [&](auto G) {
+        if (fused_op >= 0)  // the condition on the data: index modes 2 and 3 only
+          xh_pick<3, 2>(index_first == 3 ? 3 : 2, [&](auto I) {
+            hipLaunchKernelGGL((k_run_stats_mask<decltype(V)::value, decltype(I)::value, decltype(G)::value, true>), grid,
+                               dim3(XH_BLOCK), 0, ctx->stream, x, C, st, window, stat, d_seg, P, out, valid_out, oc.sgn, oc.thr);
+          });
+        else
+          xh_pick<0, 1, 2, 3>(index_first, [&](auto I) {
+            hipLaunchKernelGGL((k_run_stats_mask<decltype(V)::value, decltype(I)::value, decltype(G)::value>), grid, dim3(XH_BLOCK),
+                               0, ctx->stream, x, C, st, window, stat, d_seg, P, out, valid_out, 1.0f, 0.0f);
+          });
+      });
+    });
     XH_LAUNCH_CHECK();
     return XH_OK;
   }
@@ -553,15 +526,12 @@ int xh_run_stats(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, 
     // (measured at 365 x 1440 x 720: max 0.55 -> 0.50 ms; the sum / count group came out SLOWER than the generic body,
     //  0.68 vs 0.54 ms, so only max is specialised)
     const int sg = stat == XH_RUN_MAX ? 1 : 0;
-#define XH_RS(V, G)                                                                                                    \
-  hipLaunchKernelGGL((k_run_stats<V, true, G>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, T, C, st, fused_op, (float)thr, \
-                     window, stat, index_first, d_seg, P, out, valid_out)
-    if (vec == 4) {
-      if (sg == 1) XH_RS(4, 1); else XH_RS(4, 0);
-    } else {
-      if (sg == 1) XH_RS(1, 1); else XH_RS(1, 0);
-    }
-#undef XH_RS
+    xh_pick<4, 1>(vec, [&](auto V) {
+      xh_pick<1, 0>(sg, [&](auto G) {
+        hipLaunchKernelGGL((k_run_stats<decltype(V)::value, true, decltype(G)::value>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, T, C,
+                           st, fused_op, (float)thr, window, stat, index_first, d_seg, P, out, valid_out);
+      });
+    });
   } else {
     XH_REQUIRE(seg_off[0] == 0 && seg_off[P] == T, XH_ERR_ARG,
                "xh_run_stats: resample-after mode needs segments covering [0, T)");
@@ -573,15 +543,12 @@ int xh_run_stats(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, 
     // stat group: 1 max, 2 sum / count / mean, 3 min, 0 all (std)
     const int sg = stat == XH_RUN_MAX ? 1 : (stat == XH_RUN_SUM || stat == XH_RUN_COUNT || stat == XH_RUN_MEAN || stat == XH_RUN_PLAINSUM) ? 2
                    : stat == XH_RUN_MIN ? 3 : 0;
-#define XH_RSN(V, G)                                                                                                          \
-  hipLaunchKernelGGL((k_run_stats<V, false, G>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, T, C, st, fused_op, (float)thr, \
-                     window, stat, index_first, d_seg, P, out, valid_out)
-    if (nvec == 4) {
-      if (sg == 1) XH_RSN(4, 1); else if (sg == 2) XH_RSN(4, 2); else if (sg == 3) XH_RSN(4, 3); else XH_RSN(4, 0);
-    } else {
-      if (sg == 1) XH_RSN(1, 1); else if (sg == 2) XH_RSN(1, 2); else if (sg == 3) XH_RSN(1, 3); else XH_RSN(1, 0);
-    }
-#undef XH_RSN
+    xh_pick<4, 1>(nvec, [&](auto V) {
+      xh_pick<1, 2, 3, 0>(sg, [&](auto G) {
+        hipLaunchKernelGGL((k_run_stats<decltype(V)::value, false, decltype(G)::value>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, T, C,
+                           st, fused_op, (float)thr, window, stat, index_first, d_seg, P, out, valid_out);
+      });
+    });
   }
   XH_LAUNCH_CHECK();
   return XH_OK;
@@ -590,30 +557,26 @@ int xh_run_stats(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, 
 int xh_run_stats_doy(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, int64_t sc, int op, const double* table,
                      int D, const int32_t* tidx, int window, int stat, const int64_t* seg_off, int P, float* out,
                      int32_t* valid_out) {
-  XH_REQUIRE(ctx && x && table && out, XH_ERR_ARG, "xh_run_stats_doy: NULL argument");
-  XH_REQUIRE(T >= 0 && C >= 0 && D >= 1, XH_ERR_ARG, "xh_run_stats_doy: bad shape");
-  XH_REQUIRE(sc == 1 && st >= C, XH_ERR_LAYOUT, "xh_run_stats_doy: needs a time-major view (cell stride 1)");
+  XH_REQUIRE(table && out, XH_ERR_ARG, "xh_run_stats_doy: NULL argument");
+  XH_REQUIRE(D >= 1, XH_ERR_ARG, "xh_run_stats_doy: bad shape");
+  int rc = xh_check_field("xh_run_stats_doy", ctx, x, T, C, st, sc);
+  if (rc) return rc;
   XH_REQUIRE(op >= XH_OP_GT && op <= XH_OP_NE, XH_ERR_OP, "xh_run_stats_doy: operator %d not recognized", op);
   XH_REQUIRE(window >= 1, XH_ERR_ARG, "xh_run_stats_doy: window must be >= 1");
   XH_REQUIRE((stat >= XH_RUN_MAX && stat <= XH_RUN_STD) || stat == XH_RUN_PLAINSUM, XH_ERR_OP,
              "xh_run_stats_doy: statistic %d not supported (run-length reducers only)", stat);
-  XH_REQUIRE(seg_off && P >= 1 && tidx, XH_ERR_ARG, "xh_run_stats_doy: seg_off / tidx NULL or P < 1");
-  for (int p = 0; p < P; ++p)
-    XH_REQUIRE(seg_off[p] <= seg_off[p + 1] && seg_off[p] >= 0 && seg_off[p + 1] <= T, XH_ERR_ARG,
-               "xh_run_stats_doy: seg_off must be non-decreasing within [0, T]");
-  for (int64_t t = 0; t < T; ++t)
-    XH_REQUIRE(tidx[t] >= 0 && tidx[t] < D, XH_ERR_ARG, "xh_run_stats_doy: tidx[%lld] = %d outside the table (D = %d)",
-               (long long)t, tidx[t], D);
-  size_t cur = 0;
-  void *d_tidx = nullptr, *d_seg = nullptr;
-  int rc = xh_scratch_upload(ctx, &cur, tidx, sizeof(int32_t) * (size_t)T, &d_tidx);
+  rc = xh_check_segments("xh_run_stats_doy", seg_off, P, T);
   if (rc) return rc;
-  rc = xh_scratch_upload(ctx, &cur, seg_off, sizeof(int64_t) * (size_t)(P + 1), &d_seg);
+  size_t cur = 0;
+  const int32_t* d_tidx = nullptr;
+  const int64_t* d_seg = nullptr;
+  rc = xh_upload_tidx("xh_run_stats_doy", ctx, &cur, tidx, T, D, &d_tidx);
+  if (rc) return rc;
+  rc = xh_upload(ctx, &cur, seg_off, (size_t)P + 1, &d_seg);
   if (rc) return rc;
   if (C == 0) return XH_OK;
-  dim3 grid((unsigned)cdiv64(C, XH_BLOCK), (unsigned)(P > 4096 ? 4096 : P));
-  hipLaunchKernelGGL(k_run_stats_doy, grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, op, table, (const int32_t*)d_tidx, window,
-                     stat, (const int64_t*)d_seg, P, out, valid_out);
+  hipLaunchKernelGGL(k_run_stats_doy, xh_period_grid(C, 1, P), dim3(XH_BLOCK), 0, ctx->stream, x, C, st, op, table, d_tidx, window,
+                     stat, d_seg, P, out, valid_out);
   XH_LAUNCH_CHECK();
   return XH_OK;
 }

@@ -56,6 +56,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "hostargs.h"
 #include "qdmrank.h"
 
 namespace {

@@ -4,6 +4,7 @@
 // (keep_longest_run), 891-1145 (season_start / season_end / season / season_length), 491-540 (windowed_max_run_sum).
 // Same layout as runlen.hip: time-major (T, C), one lane per cell marching along time, periods on blockIdx.y.
 #include "common.h"
+#include "hostargs.h"
 #include "window.h"
 
 // ---- spell_mask ------------------------------------------------------------------------------------------
@@ -494,26 +495,6 @@ k_suspicious_run(const float* __restrict__ x, int64_t T, int64_t C, int64_t st, 
   }
 }
 
-static int chk(const char* fn, xh_ctx* ctx, const void* x, int64_t T, int64_t C, int64_t st, int64_t sc) {
-  XH_REQUIRE(ctx && x, XH_ERR_ARG, "%s: NULL argument", fn);
-  XH_REQUIRE(T >= 0 && C >= 0, XH_ERR_ARG, "%s: negative shape", fn);
-  XH_REQUIRE(sc == 1 && st >= C, XH_ERR_LAYOUT, "%s: needs a time-major view (sc == 1, st >= C)", fn);
-  return XH_OK;
-}
-
-static int upload_seg(xh_ctx* ctx, size_t* cur, const int64_t* seg_off, int P, int64_t T, const char* fn,
-                      const int64_t** d_seg) {
-  XH_REQUIRE(seg_off && P >= 1, XH_ERR_ARG, "%s: seg_off NULL or P < 1", fn);
-  for (int p = 0; p < P; ++p)
-    XH_REQUIRE(seg_off[p] <= seg_off[p + 1] && seg_off[p] >= 0 && seg_off[p + 1] <= T, XH_ERR_ARG,
-               "%s: seg_off must be non-decreasing within [0, T]", fn);
-  void* d = nullptr;
-  int rc = xh_scratch_upload(ctx, cur, seg_off, sizeof(int64_t) * (size_t)(P + 1), &d);
-  if (rc) return rc;
-  *d_seg = (const int64_t*)d;
-  return XH_OK;
-}
-
 extern "C" {
 
 static int spell_mask_impl(xh_ctx* ctx, const char* fn, const float* const* xs, int nvar, const double* thrs, int combine,
@@ -523,11 +504,11 @@ static int spell_mask_impl(xh_ctx* ctx, const char* fn, const float* const* xs, 
   XH_REQUIRE(nvar >= 1 && nvar <= 8, XH_ERR_LIMIT, "%s: 1 to 8 variables are supported (got %d)", fn, nvar);
   XH_REQUIRE(combine == 1 || combine == 2, XH_ERR_ARG, "%s: combine must be 1 (all) or 2 (any)", fn);
   for (int i = 0; i < nvar; ++i) {
-    int rc = chk(fn, ctx, xs[i], T, C, st, sc);
+    int rc = xh_check_field(fn, ctx, xs[i], T, C, st, sc);
     if (rc) return rc;
   }
   XH_REQUIRE(out, XH_ERR_ARG, "%s: out NULL", fn);
-  XH_REQUIRE(out_st >= C, XH_ERR_LAYOUT, "%s: needs time-major rows of at least the row width (out_st)", fn);
+  if (const int rc = xh_check_rows(fn, out_st, C, "out_st")) return rc;
   XH_REQUIRE(window >= 1, XH_ERR_ARG, "%s: window must be >= 1", fn);
   XH_REQUIRE(win_reducer >= 0 && win_reducer <= 4, XH_ERR_OP, "%s: win_reducer %d not recognized", fn, win_reducer);
   XH_REQUIRE(op >= XH_OP_GT && op <= XH_OP_NE, XH_ERR_OP, "Operation `%d` not recognized.", op);
@@ -536,10 +517,8 @@ static int spell_mask_impl(xh_ctx* ctx, const char* fn, const float* const* xs, 
   const float* d_w = nullptr;
   if (win_reducer == 4) {
     size_t cur = 0;
-    void* d = nullptr;
-    int rc = xh_scratch_upload(ctx, &cur, weights, sizeof(float) * (size_t)window, &d);
+    const int rc = xh_upload(ctx, &cur, weights, (size_t)window, &d_w);
     if (rc) return rc;
-    d_w = (const float*)d;
   }
   if (nvar == 1) {  // one variable, window <= 8: register ring (window.hip)
     int rr = xh_launch_spell_ring(ctx, xs[0], T, C, st, window, win_reducer, op, (float)thrs[0], d_w, out, out_st);
@@ -571,7 +550,7 @@ int xh_spell_mask_multi(xh_ctx* ctx, const float* const* xs, int nvar, const dou
 int xh_spell_run_stats(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, int64_t sc, int window, int win_reducer,
                        int op, double thr, const float* weights, int stat, const int64_t* seg_off, int P, float* out,
                        int32_t* valid_out) {
-  int rc = chk("xh_spell_run_stats", ctx, x, T, C, st, sc);
+  int rc = xh_check_field("xh_spell_run_stats", ctx, x, T, C, st, sc);
   if (rc) return rc;
   XH_REQUIRE(out, XH_ERR_ARG, "xh_spell_run_stats: out is NULL");
   XH_REQUIRE(window >= 1, XH_ERR_ARG, "xh_spell_run_stats: window must be >= 1");
@@ -581,14 +560,12 @@ int xh_spell_run_stats(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_
   XH_REQUIRE(stat >= XH_RUN_MAX && stat <= XH_RUN_STD, XH_ERR_OP, "xh_spell_run_stats: statistic %d not supported", stat);
   size_t cur = 0;
   const int64_t* d_seg = nullptr;
-  rc = upload_seg(ctx, &cur, seg_off, P, T, "xh_spell_run_stats", &d_seg);
+  rc = xh_upload_segments("xh_spell_run_stats", ctx, &cur, seg_off, P, T, &d_seg);
   if (rc) return rc;
   const float* d_w = nullptr;
   if (win_reducer == 4) {
-    void* d = nullptr;
-    rc = xh_scratch_upload(ctx, &cur, weights, sizeof(float) * (size_t)window, &d);
+    rc = xh_upload(ctx, &cur, weights, (size_t)window, &d_w);
     if (rc) return rc;
-    d_w = (const float*)d;
   }
   if (C == 0) return XH_OK;
   return xh_launch_spell_runs(ctx, x, T, C, st, window, win_reducer, op, (float)thr, d_w, stat, d_seg, P, out, valid_out);
@@ -596,10 +573,11 @@ int xh_spell_run_stats(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_
 
 int xh_runs_with_holes(xh_ctx* ctx, const float* start, const float* stop, int64_t T, int64_t C, int64_t st, int64_t sc,
                        int window_start, int window_stop, float* out, int64_t out_st) {
-  int rc = chk("xh_runs_with_holes", ctx, start, T, C, st, sc);
+  int rc = xh_check_field("xh_runs_with_holes", ctx, start, T, C, st, sc);
   if (rc) return rc;
   XH_REQUIRE(out, XH_ERR_ARG, "xh_runs_with_holes: out NULL");
-  XH_REQUIRE(out_st >= C, XH_ERR_LAYOUT, "xh_runs_with_holes: needs time-major rows of at least the row width (out_st)");
+  rc = xh_check_rows("xh_runs_with_holes", out_st, C, "out_st");
+  if (rc) return rc;
   XH_REQUIRE(window_start >= 1 && window_stop >= 1, XH_ERR_ARG, "xh_runs_with_holes: windows must be >= 1");
   if (T == 0 || C == 0) return XH_OK;
   if (window_start <= 64 && window_stop <= 64) {
@@ -607,12 +585,12 @@ int xh_runs_with_holes(xh_ctx* ctx, const float* start, const float* stop, int64
     const bool v4 = xh_pick_vec(start, C, st) == 4 && (!stop || xh_pick_vec(stop, C, st) == 4) && xh_pick_vec(out, C, out_st) == 4 &&
                     cdiv64(cdiv64(C, 4), XH_BLOCK) >= 4 * (int64_t)ctx->num_cu;
     const dim3 grid((unsigned)cdiv64(cdiv64(C, v4 ? 4 : 1), XH_BLOCK));
-#define XH_RWH(V, TW)                                                                                                   \
-  hipLaunchKernelGGL((k_runs_with_holes_fwd<V, TW>), grid, dim3(XH_BLOCK), 0, ctx->stream, start, stop ? stop : start, T, C, st, \
-                     st, window_start, window_stop, out, out_st)
-    if (v4) { if (stop) XH_RWH(4, true); else XH_RWH(4, false); }
-    else { if (stop) XH_RWH(1, true); else XH_RWH(1, false); }
-#undef XH_RWH
+    xh_pick<4, 1>(v4 ? 4 : 1, [&](auto V) {
+      xh_pick<1, 0>(stop ? 1 : 0, [&](auto TWO) {
+        hipLaunchKernelGGL((k_runs_with_holes_fwd<decltype(V)::value, decltype(TWO)::value != 0>), grid, dim3(XH_BLOCK), 0, ctx->stream,
+                           start, stop ? stop : start, T, C, st, st, window_start, window_stop, out, out_st);
+      });
+    });
     XH_LAUNCH_CHECK();
     return XH_OK;
   }
@@ -624,13 +602,14 @@ int xh_runs_with_holes(xh_ctx* ctx, const float* start, const float* stop, int64
 
 int xh_keep_longest_run(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, int64_t sc, const int64_t* seg_off,
                         int P, float* out, int64_t out_st) {
-  int rc = chk("xh_keep_longest_run", ctx, x, T, C, st, sc);
+  int rc = xh_check_field("xh_keep_longest_run", ctx, x, T, C, st, sc);
   if (rc) return rc;
   XH_REQUIRE(out, XH_ERR_ARG, "xh_keep_longest_run: out NULL");
-  XH_REQUIRE(out_st >= C, XH_ERR_LAYOUT, "xh_keep_longest_run: needs time-major rows of at least the row width (out_st)");
+  rc = xh_check_rows("xh_keep_longest_run", out_st, C, "out_st");
+  if (rc) return rc;
   size_t cur = 0;
   const int64_t* d_seg = nullptr;
-  rc = upload_seg(ctx, &cur, seg_off, P, T, "xh_keep_longest_run", &d_seg);
+  rc = xh_upload_segments("xh_keep_longest_run", ctx, &cur, seg_off, P, T, &d_seg);
   if (rc) return rc;
   if (C == 0) return XH_OK;
   XH_REQUIRE(seg_off[0] == 0 && seg_off[P] == T, XH_ERR_ARG, "xh_keep_longest_run: segments must cover [0, T)");
@@ -646,63 +625,56 @@ int xh_keep_longest_run(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64
 
 int xh_season(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, int64_t sc, int window,
               const int64_t* seg_off, const int32_t* mid_idx, int P, float* start_out, float* end_out, float* len_out) {
-  int rc = chk("xh_season", ctx, x, T, C, st, sc);
+  int rc = xh_check_field("xh_season", ctx, x, T, C, st, sc);
   if (rc) return rc;
   XH_REQUIRE(start_out && end_out && len_out, XH_ERR_ARG, "xh_season: NULL output");
   XH_REQUIRE(window >= 1, XH_ERR_ARG, "xh_season: window must be >= 1");
   size_t cur = 0;
   const int64_t* d_seg = nullptr;
-  rc = upload_seg(ctx, &cur, seg_off, P, T, "xh_season", &d_seg);
+  rc = xh_upload_segments("xh_season", ctx, &cur, seg_off, P, T, &d_seg);
   if (rc) return rc;
-  void* d_mid = nullptr;
+  const int32_t* d_mid = nullptr;
   if (mid_idx) {
-    rc = xh_scratch_upload(ctx, &cur, mid_idx, sizeof(int32_t) * (size_t)P, &d_mid);
+    rc = xh_upload(ctx, &cur, mid_idx, (size_t)P, &d_mid);
     if (rc) return rc;
   }
   if (C == 0) return XH_OK;
-  if (window >= 2 && xh_pick_vec(x, C, st) == 4)
-    hipLaunchKernelGGL((k_season_w<4>), dim3((unsigned)cdiv64(cdiv64(C, 4), XH_BLOCK), (unsigned)(P > 4096 ? 4096 : P)),
-                       dim3(XH_BLOCK), 0, ctx->stream, x, C, st, window, d_seg, (const int32_t*)d_mid, mid_idx ? 1 : 0, P,
-                       start_out, end_out, len_out);
-  else if (window >= 2)
-    hipLaunchKernelGGL((k_season_w<1>), dim3((unsigned)cdiv64(C, XH_BLOCK), (unsigned)(P > 4096 ? 4096 : P)), dim3(XH_BLOCK), 0,
-                       ctx->stream, x, C, st, window, d_seg, (const int32_t*)d_mid, mid_idx ? 1 : 0, P, start_out, end_out,
-                       len_out);
-  else if (xh_pick_vec(x, C, st) == 4)
-    hipLaunchKernelGGL((k_season<4>), dim3((unsigned)cdiv64(cdiv64(C, 4), XH_BLOCK), (unsigned)(P > 4096 ? 4096 : P)),
-                       dim3(XH_BLOCK), 0, ctx->stream, x, C, st, window, d_seg, (const int32_t*)d_mid, mid_idx ? 1 : 0, P,
-                       start_out, end_out, len_out);
-  else
-    hipLaunchKernelGGL((k_season<1>), dim3((unsigned)cdiv64(C, XH_BLOCK), (unsigned)(P > 4096 ? 4096 : P)), dim3(XH_BLOCK), 0,
-                       ctx->stream, x, C, st, window, d_seg, (const int32_t*)d_mid, mid_idx ? 1 : 0, P, start_out, end_out,
-                       len_out);
+  const int vec = xh_pick_vec(x, C, st);
+  const dim3 grid = xh_period_grid(C, vec, P);
+  xh_pick<4, 1>(vec, [&](auto V) {
+    if (window >= 2)
+      hipLaunchKernelGGL((k_season_w<decltype(V)::value>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, window, d_seg, d_mid,
+                         mid_idx ? 1 : 0, P, start_out, end_out, len_out);
+    else
+      hipLaunchKernelGGL((k_season<decltype(V)::value>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, window, d_seg, d_mid,
+                         mid_idx ? 1 : 0, P, start_out, end_out, len_out);
+  });
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
 
 int xh_max_run_sum(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, int64_t sc, int window,
                    const int64_t* seg_off, int P, int cut_at_segments, float* out) {
-  int rc = chk("xh_max_run_sum", ctx, x, T, C, st, sc);
+  int rc = xh_check_field("xh_max_run_sum", ctx, x, T, C, st, sc);
   if (rc) return rc;
   XH_REQUIRE(out, XH_ERR_ARG, "xh_max_run_sum: out is NULL");
   XH_REQUIRE(window >= 1, XH_ERR_ARG, "xh_max_run_sum: window must be >= 1");
   size_t cur = 0;
   const int64_t* d_seg = nullptr;
-  rc = upload_seg(ctx, &cur, seg_off, P, T, "xh_max_run_sum", &d_seg);
+  rc = xh_upload_segments("xh_max_run_sum", ctx, &cur, seg_off, P, T, &d_seg);
   if (rc) return rc;
   if (C == 0) return XH_OK;
-  const unsigned py = cut_at_segments ? (unsigned)(P > 4096 ? 4096 : P) : 1u;
+  const unsigned py = cut_at_segments ? xh_period_blocks(P) : 1u;
   if (!cut_at_segments)
     XH_REQUIRE(seg_off[0] == 0 && seg_off[P] == T, XH_ERR_ARG, "xh_max_run_sum: resample-after mode needs segments covering [0, T)");
   const bool v4 = xh_pick_vec(x, C, st) == 4 && (cut_at_segments || cdiv64(cdiv64(C, 4), XH_BLOCK) >= 2 * (int64_t)ctx->num_cu);
   dim3 grid((unsigned)cdiv64(cdiv64(C, v4 ? 4 : 1), XH_BLOCK), py);
-  if (v4) {
-    if (cut_at_segments) hipLaunchKernelGGL((k_max_run_sum<4, true>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, window, d_seg, P, out);
-    else hipLaunchKernelGGL((k_max_run_sum<4, false>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, window, d_seg, P, out);
-  } else {
-    if (cut_at_segments) hipLaunchKernelGGL((k_max_run_sum<1, true>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, window, d_seg, P, out);
-    else hipLaunchKernelGGL((k_max_run_sum<1, false>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st, window, d_seg, P, out);
-  }
+  xh_pick<4, 1>(v4 ? 4 : 1, [&](auto V) {
+    xh_pick<1, 0>(cut_at_segments ? 1 : 0, [&](auto CUT) {
+      hipLaunchKernelGGL((k_max_run_sum<decltype(V)::value, decltype(CUT)::value != 0>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, C, st,
+                         window, d_seg, P, out);
+    });
+  });
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
@@ -710,28 +682,29 @@ int xh_max_run_sum(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st
 int xh_run_events(xh_ctx* ctx, const float* runs, const float* eff, const float* data, int64_t T, int64_t C, int64_t st,
                   int64_t sc, const int64_t* seg_off, int P, int maxev, float* start_out, float* end_out, float* len_out,
                   float* eff_out, float* sum_out) {
-  int rc = chk("xh_run_events", ctx, runs, T, C, st, sc);
+  int rc = xh_check_field("xh_run_events", ctx, runs, T, C, st, sc);
   if (rc) return rc;
   XH_REQUIRE(start_out, XH_ERR_ARG, "xh_run_events: start_out is NULL");
   XH_REQUIRE(maxev >= 0, XH_ERR_ARG, "xh_run_events: maxev must be >= 0");
   XH_REQUIRE(!sum_out || data, XH_ERR_ARG, "xh_run_events: sum_out needs data");
   size_t cur = 0;
   const int64_t* d_seg = nullptr;
-  rc = upload_seg(ctx, &cur, seg_off, P, T, "xh_run_events", &d_seg);
+  rc = xh_upload_segments("xh_run_events", ctx, &cur, seg_off, P, T, &d_seg);
   if (rc) return rc;
   if (C == 0 || maxev == 0) return XH_OK;
-  hipLaunchKernelGGL(k_run_events, dim3((unsigned)cdiv64(C, XH_BLOCK), (unsigned)(P > 4096 ? 4096 : P)), dim3(XH_BLOCK), 0,
-                     ctx->stream, runs, eff, data, C, st, d_seg, P, maxev, start_out, end_out, len_out, eff_out, sum_out);
+  hipLaunchKernelGGL(k_run_events, xh_period_grid(C, 1, P), dim3(XH_BLOCK), 0, ctx->stream, runs, eff, data, C, st, d_seg, P, maxev,
+                     start_out, end_out, len_out, eff_out, sum_out);
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
 
 int xh_suspicious_run(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, int64_t sc, int window, int op,
                       double thresh, uint8_t* out, int64_t out_st) {
-  int rc = chk("xh_suspicious_run", ctx, x, T, C, st, sc);
+  int rc = xh_check_field("xh_suspicious_run", ctx, x, T, C, st, sc);
   if (rc) return rc;
   XH_REQUIRE(out, XH_ERR_ARG, "xh_suspicious_run: out NULL");
-  XH_REQUIRE(out_st >= C, XH_ERR_LAYOUT, "xh_suspicious_run: needs time-major rows of at least the row width (out_st)");
+  rc = xh_check_rows("xh_suspicious_run", out_st, C, "out_st");
+  if (rc) return rc;
   XH_REQUIRE(window >= 1, XH_ERR_ARG, "xh_suspicious_run: window must be >= 1");
   XH_REQUIRE(op >= -1 && op <= XH_OP_NE, XH_ERR_OP, "Operation `%d` not recognized.", op);
   if (C == 0 || T == 0) return XH_OK;

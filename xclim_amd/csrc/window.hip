@@ -8,6 +8,7 @@
 // accumulation) so the results are bit-identical to the generic kernels.  A lane owns VEC consecutive cells; the time
 // axis is cut into chunks over blockIdx.y, each chunk re-reads its (w - 1)-row halo.
 #include "common.h"
+#include "hostargs.h"
 #include "runacc.h"
 #include "window.h"
 
@@ -292,28 +293,16 @@ int xh_launch_rolling_ring(xh_ctx* ctx, const float* x, int64_t T, int64_t C, in
   if (window > WMAX) return XH_ERR_NOTIMPL;
   const int vec = (xh_pick_vec(x, C, st) == 4 && xh_pick_vec(out, C, out_st) == 4) ? 4 : 1;
   const dim3 grid = window_grid(ctx, T, C, vec);
-#define XH_RR(R)                                                                                                          \
-  case R:                                                                                                                 \
-    if (vec == 4 && window == 3)                                                                                          \
-      hipLaunchKernelGGL((k_rolling_ring<4, R, 3>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, T, C, st, window, left, right, out, \
-                         out_st);                                                                                         \
-    else if (vec == 4 && window == 5)                                                                                     \
-      hipLaunchKernelGGL((k_rolling_ring<4, R, 5>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, T, C, st, window, left, right, out, \
-                         out_st);                                                                                         \
-    else if (vec == 4)                                                                                                    \
-      hipLaunchKernelGGL((k_rolling_ring<4, R>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, T, C, st, window, left, right, out, \
-                         out_st);                                                                                         \
-    else                                                                                                                  \
-      hipLaunchKernelGGL((k_rolling_ring<1, R>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, T, C, st, window, left, right, out, \
-                         out_st);                                                                                         \
-    break;
-  switch (reducer) {
-    XH_RR(XH_RED_SUM) XH_RR(XH_RED_MEAN) XH_RR(XH_RED_MIN) XH_RR(XH_RED_MAX) XH_RR(XH_RED_STD) XH_RR(XH_RED_VAR)
-    XH_RR(XH_RED_COUNT)
-    default:
-      return XH_ERR_NOTIMPL;
-  }
-#undef XH_RR
+  // (cells per lane, compile-time window) as one code: the four instances that exist
+  const int vw = vec * 10 + ((vec == 4 && (window == 3 || window == 5)) ? window : 0);
+  const bool known = xh_pick<XH_RED_SUM, XH_RED_MEAN, XH_RED_MIN, XH_RED_MAX, XH_RED_STD, XH_RED_VAR, XH_RED_COUNT>(reducer, [&](auto R) {
+    xh_pick<43, 45, 40, 10>(vw, [&](auto VW) {
+      constexpr int V = decltype(VW)::value / 10, W = decltype(VW)::value % 10;
+      hipLaunchKernelGGL((k_rolling_ring<V, decltype(R)::value, W>), grid, dim3(XH_BLOCK), 0, ctx->stream, x, T, C, st, window, left,
+                         right, out, out_st);
+    });
+  });
+  if (!known) return XH_ERR_NOTIMPL;
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
@@ -328,43 +317,6 @@ struct SpellArgs {
   double thr64, sgn64;  // the same condition on the fp64 window sum (sum / mean reducers, compile-time windows)
   const float* d_weights;
 };
-
-template <int VEC, int RED, int WT>
-void launch_spell_ring_t(xh_ctx* ctx, dim3 grid, const SpellArgs& a, float* out, int64_t out_st) {
-  hipLaunchKernelGGL((k_spell_ring<VEC, RED, WT>), grid, dim3(XH_BLOCK), 0, ctx->stream, a.x, a.T, a.C, a.st, a.window, a.op,
-                     a.thr, a.sgn, a.thr64, a.sgn64, a.d_weights, out, out_st);
-}
-
-template <int RED>
-void launch_spell_ring_r(xh_ctx* ctx, dim3 grid, int vec, int wt, const SpellArgs& a, float* out, int64_t out_st) {
-  if (vec == 4 && wt == 3) launch_spell_ring_t<4, RED, 3>(ctx, grid, a, out, out_st);
-  else if (vec == 4 && wt == 5) launch_spell_ring_t<4, RED, 5>(ctx, grid, a, out, out_st);
-  else if (vec == 4) launch_spell_ring_t<4, RED, 0>(ctx, grid, a, out, out_st);
-  else launch_spell_ring_t<1, RED, 0>(ctx, grid, a, out, out_st);
-}
-
-template <int VEC, int RED, int WT, int SG>
-void launch_spell_runs_t(xh_ctx* ctx, dim3 grid, const SpellArgs& a, int stat, const int64_t* d_seg, int P, float* out,
-                         int32_t* valid_out) {
-  hipLaunchKernelGGL((k_spell_runs<VEC, RED, WT, SG>), grid, dim3(XH_BLOCK), 0, ctx->stream, a.x, a.T, a.C, a.st, a.window,
-                     a.op, a.thr, a.sgn, a.thr64, a.sgn64, a.d_weights, stat, d_seg, P, out, valid_out);
-}
-
-template <int RED>
-void launch_spell_runs_r(xh_ctx* ctx, dim3 grid, int vec, int wt, int sg, const SpellArgs& a, int stat, const int64_t* d_seg,
-                         int P, float* out, int32_t* valid_out) {
-#define XH_SRN(V, W)                                                                      \
-  do {                                                                                    \
-    if (sg == 1) launch_spell_runs_t<V, RED, W, 1>(ctx, grid, a, stat, d_seg, P, out, valid_out);      \
-    else if (sg == 2) launch_spell_runs_t<V, RED, W, 2>(ctx, grid, a, stat, d_seg, P, out, valid_out); \
-    else launch_spell_runs_t<V, RED, W, 0>(ctx, grid, a, stat, d_seg, P, out, valid_out);              \
-  } while (0)
-  if (vec == 1 && wt == 3) XH_SRN(1, 3);
-  else if (vec == 1 && wt == 5) XH_SRN(1, 5);
-  else if (vec == 4) launch_spell_runs_t<4, RED, 0, 0>(ctx, grid, a, stat, d_seg, P, out, valid_out);
-  else launch_spell_runs_t<1, RED, 0, 0>(ctx, grid, a, stat, d_seg, P, out, valid_out);
-#undef XH_SRN
-}
 
 // Threshold of the one-compare condition `F(s) * sgn > t` (F(s) = float(s / w) for the mean, float(s) for the sum, s the
 // fp64 window sum) moved into sum space: sgn = +1: F(s) > t  <=>  s > S+,  S+ = the largest double with F(S+) <= t;
@@ -423,14 +375,16 @@ int xh_launch_spell_ring(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int6
   const dim3 grid = window_grid(ctx, T, C, vec);
   int wt;
   const SpellArgs a = spell_args(x, T, C, st, window, win_red, op, thr, d_weights, vec == 4, &wt);
-  switch (win_red) {  // win_red (spell.hip): 0 sum, 1 mean, 2 min, 3 max, 4 weighted mean
-    case 0: launch_spell_ring_r<XH_RED_SUM>(ctx, grid, vec, wt, a, out, out_st); break;
-    case 1: launch_spell_ring_r<XH_RED_MEAN>(ctx, grid, vec, wt, a, out, out_st); break;
-    case 2: launch_spell_ring_r<XH_RED_MIN>(ctx, grid, vec, wt, a, out, out_st); break;
-    case 3: launch_spell_ring_r<XH_RED_MAX>(ctx, grid, vec, wt, a, out, out_st); break;
-    case 4: launch_spell_ring_r<100>(ctx, grid, vec, wt, a, out, out_st); break;
-    default: return XH_ERR_NOTIMPL;
-  }
+  // win_red (spell.hip): 0 sum, 1 mean, 2 min, 3 max — the values of XH_RED_SUM .. XH_RED_MAX — and 4 weighted mean
+  const bool known = xh_pick<XH_RED_SUM, XH_RED_MEAN, XH_RED_MIN, XH_RED_MAX, 4>(win_red, [&](auto R) {
+    constexpr int RED = decltype(R)::value == 4 ? 100 : decltype(R)::value;
+    xh_pick<43, 45, 40, 10>(vec * 10 + wt, [&](auto VW) {  // (cells per lane, compile-time window): the instances that exist
+      constexpr int V = decltype(VW)::value / 10, W = decltype(VW)::value % 10;
+      hipLaunchKernelGGL((k_spell_ring<V, RED, W>), grid, dim3(XH_BLOCK), 0, ctx->stream, a.x, a.T, a.C, a.st, a.window, a.op, a.thr,
+                         a.sgn, a.thr64, a.sgn64, a.d_weights, out, out_st);
+    });
+  });
+  if (!known) return XH_ERR_NOTIMPL;
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
@@ -438,7 +392,7 @@ int xh_launch_spell_ring(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int6
 int xh_launch_spell_runs(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t st, int window, int win_red, int op, float thr,
                          const float* d_weights, int stat, const int64_t* d_seg, int P, float* out, int32_t* valid_out) {
   if (window > WMAX) return XH_ERR_NOTIMPL;
-  const unsigned py = (unsigned)(P > 4096 ? 4096 : P);
+  const unsigned py = xh_period_blocks(P);
   // four cells per lane only when that still leaves >= 8 workgroups per CU (a period cannot be cut into time chunks)
   const int vec = (xh_pick_vec(x, C, st) == 4 && cdiv64(cdiv64(C, 4), XH_BLOCK) * py >= 8 * (int64_t)ctx->num_cu) ? 4 : 1;
   const dim3 grid((unsigned)cdiv64(cdiv64(C, vec), XH_BLOCK), py);
@@ -446,14 +400,17 @@ int xh_launch_spell_runs(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int6
   const SpellArgs a = spell_args(x, T, C, st, window, win_red, op, thr, d_weights, vec == 1, &wt);
   // fields of the run accumulator the statistic reads (runacc.h): 1 max, 2 sum / count / mean / plain sum, 0 all
   const int sg = stat == XH_RUN_MAX ? 1 : (stat == XH_RUN_SUM || stat == XH_RUN_COUNT || stat == XH_RUN_MEAN || stat == XH_RUN_PLAINSUM) ? 2 : 0;
-  switch (win_red) {
-    case 0: launch_spell_runs_r<XH_RED_SUM>(ctx, grid, vec, wt, sg, a, stat, d_seg, P, out, valid_out); break;
-    case 1: launch_spell_runs_r<XH_RED_MEAN>(ctx, grid, vec, wt, sg, a, stat, d_seg, P, out, valid_out); break;
-    case 2: launch_spell_runs_r<XH_RED_MIN>(ctx, grid, vec, wt, sg, a, stat, d_seg, P, out, valid_out); break;
-    case 3: launch_spell_runs_r<XH_RED_MAX>(ctx, grid, vec, wt, sg, a, stat, d_seg, P, out, valid_out); break;
-    case 4: launch_spell_runs_r<100>(ctx, grid, vec, wt, sg, a, stat, d_seg, P, out, valid_out); break;
-    default: return XH_ERR_NOTIMPL;
-  }
+  // (cells per lane, compile-time window, statistic group): the group is compiled in for the windows 3 and 5 only
+  const int vws = vec * 100 + wt * 10 + (wt ? sg : 0);
+  const bool known = xh_pick<XH_RED_SUM, XH_RED_MEAN, XH_RED_MIN, XH_RED_MAX, 4>(win_red, [&](auto R) {
+    constexpr int RED = decltype(R)::value == 4 ? 100 : decltype(R)::value;
+    xh_pick<131, 132, 130, 151, 152, 150, 400, 100>(vws, [&](auto VWS) {
+      constexpr int V = decltype(VWS)::value / 100, W = decltype(VWS)::value / 10 % 10, SG = decltype(VWS)::value % 10;
+      hipLaunchKernelGGL((k_spell_runs<V, RED, W, SG>), grid, dim3(XH_BLOCK), 0, ctx->stream, a.x, a.T, a.C, a.st, a.window, a.op,
+                         a.thr, a.sgn, a.thr64, a.sgn64, a.d_weights, stat, d_seg, P, out, valid_out);
+    });
+  });
+  if (!known) return XH_ERR_NOTIMPL;
   XH_LAUNCH_CHECK();
   return XH_OK;
 }

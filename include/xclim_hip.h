@@ -816,6 +816,36 @@ int xh_chill_daily(xh_ctx* ctx, int64_t D, int64_t C, int64_t ld, int f64, const
                    double add_K, double sub_C, int positive_only, double* cp_out, double* cu_out, int32_t* valid_out,
                    double* hourly_out, int64_t ld_out);
 
+/* ---- ANUCLIM bioclimatic variables BIO1-BIO19 (indices/_anuclim.py) ----------------------------------------------- */
+/* xh_bioclim: the nineteen variables of _anuclim.py:66-625 in one launch, one lane per (cell, period).
+ *   Fields (T, C) with row pitch ld (DEVICE), all float32 (f64 = 0) or all float64: tas, tasmin, tasmax, pr; a field that no
+ *   requested output reads may be NULL and is not read.
+ *   Tables (HOST): step_off (S + 1), the first row of every STEP (_to_quarter :562-625: the 7-day bins of a daily series
+ *   counted from its first day, or one row per step for weekly and monthly series), non-decreasing within [0, T];
+ *   factor (T), what turns a row of pr into its amount (seconds per day, the month's length times that, or 1);
+ *   binned: 1 = steps are bins of daily rows, a bin without a present pr sums to 0 (precip_accumulation), 0 = every row is
+ *   its own step and a NaN row is a NaN step; seg_rows, seg_steps (P + 1 each), the first row and the first step of every
+ *   period (a step belongs to the period its first row lies in), non-decreasing within [0, T] and [0, S].
+ *   W: steps per quarter, 13 or 3.  The tas quarter at step k is the mean of the tas steps k - W + 1 .. k (a step is the
+ *   mean of its present rows, NaN without one), the pr quarter their sum of amounts, each summed in step order; NaN when
+ *   k < W - 1 or a step of the window is NaN.  A period reduces the quarters of ITS steps; its first ones reach back W - 1
+ *   steps into the rows before it.
+ *   outputs (HOST, 19 device pointers BIO1 .. BIO19, (P, C) float64 with row pitch ld_out, NULL = not requested):
+ *   1 mean tas; 2 mean (tasmax - tasmin); 3 BIO2 / BIO7 * 100; 4 100 * std / mean of tas + kelvin_offset (ddof 0);
+ *   5 max tasmax; 6 min tasmin; 7 BIO5 - BIO6; 8 / 9 tas quarter at the first maximum / minimum of the pr quarters;
+ *   10 / 11 max / min tas quarter; 12 sum of the amounts of rows with pr >= thresh; 13 / 14 max / min amount of a row;
+ *   15 as 4 for pr * cv_scale; 16 / 17 max / min pr quarter; 18 / 19 pr quarter at the first maximum / minimum of the
+ *   tas quarters.  NaN is skipped everywhere; 1 - 7 and 12 - 15 reduce the period's rows.  tasmax - tasmin and BIO7 are
+ *   taken in the fields' dtype, everything else in float64; 4 and 15 are Welford accumulations.
+ *   which_out (HOST, 4 device pointers, (P, C) int32, ld_out; the array or an entry may be NULL): the step index of the
+ *   wettest, driest, warmest, coldest quarter, -1 without one.  count_out (likewise): the period's rows with a value of tas,
+ *   tasmin, tasmax, pr.  At least one output; at most 65535 periods.  Every check answers before anything is launched. */
+int xh_bioclim(xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int f64, const void* tas, const void* tasmin, const void* tasmax,
+               const void* pr, int64_t S, const int64_t* step_off /* host */, const double* factor /* host */, int binned,
+               int64_t P, const int64_t* seg_rows /* host */, const int64_t* seg_steps /* host */, int W, double kelvin_offset,
+               double cv_scale, double thresh, double* const* outputs /* host */, int32_t* const* which_out /* host */,
+               int32_t* const* count_out /* host */, int64_t ld_out);
+
 /* ---- standardized indices: SPI / SPEI (indices/stats.py) --------------------------------------------------------- */
 /* xh_si_fit: the per-group fits of standardized_index_fit_params (stats.py:855-964) through _fitfunc_1d (:40-113) and
  *   _fit_start (:576-684), one lane per (cell, group), float64.  x (T, C) float32 with row stride st (DEVICE): the

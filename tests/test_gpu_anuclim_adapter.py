@@ -1,0 +1,146 @@
+"""The xarray adapter of the ANUCLIM quarter and seasonality functions, EXECUTED: ``patch.install(env, modules)`` on stand-in
+modules wired like the reference — ``xclim.indices._anuclim`` defines the six functions and ``xclim.indices`` re-exports the
+same objects — with the DataArray stand-in of tests/fakexr.py.  The stand-in originals only record that they were reached
+(the forwarded forms)."""
+
+import types
+
+import numpy as np
+import pytest
+
+import fakexr
+from xclim_amd import anuclim, patch
+from xclim_amd.timeaxis import TimeAxis
+
+pytestmark = pytest.mark.gpu
+DAY = 86400.0
+
+
+@pytest.fixture()
+def wired(dev):
+    import xclim_amd._capi as capi
+
+    reached = []
+
+    def original(name):
+        def fn(*a, **k):
+            reached.append(name)
+            return "original " + name
+
+        fn.__name__ = name
+        return fn
+
+    sigs = {"temperature_seasonality": "tas, freq='YS'", "precip_seasonality": "pr, freq='YS'",
+            "tg_mean_warmcold_quarter": "tas, op, freq='YS'", "tg_mean_wetdry_quarter": "tas, pr, op, freq='YS'",
+            "prcptot_wetdry_quarter": "pr, op, freq='YS'", "prcptot_warmcold_quarter": "pr, tas, op, freq='YS'"}
+    mod, pkg = types.ModuleType("xclim.indices._anuclim"), types.ModuleType("xclim.indices")
+    originals = {}
+    for name, sig in sigs.items():   # the reference's signatures: the adapters bind their arguments against them
+        ns = {"reached": reached}
+        exec(f"def {name}({sig}):\n    reached.append({name!r})\n    return 'original {name}'\n", ns)
+        originals[name] = ns[name]
+        setattr(mod, name, ns[name])
+        setattr(pkg, name, ns[name])
+    mod.isothermality = pkg.isothermality = original("isothermality")   # not replaced
+    pkg.tg_mean = original("tg_mean")
+    mods = {"xclim.indices._anuclim": mod, "xclim.indices": pkg}
+    old = capi._default_device
+    capi._default_device = dev
+    names = patch.install(fakexr.make_env(), mods)
+    try:
+        yield mods, names, reached, originals
+    finally:
+        patch.uninstall()
+        capi._default_device = old
+
+
+def _fields(T=800, start="1999-03-15", ny=3, nx=4, tunits="K"):
+    rng = np.random.default_rng(9)
+    t = TimeAxis.daily(start, T)
+    doy = t.doy[:, None, None]
+    tas = (283 + 10 * np.sin(2 * np.pi * (doy - 100) / 365) + rng.normal(0, 3, (T, ny, nx)) - (273.15 if tunits == "degC" else 0)).astype(np.float32)
+    pr = (np.maximum(rng.normal(2, 4, (T, ny, nx)), 0) / DAY).astype(np.float32)
+    tas[5, 0, 0] = np.nan
+    da = {"tas": fakexr.field(tas, t, attrs={"units": tunits, "standard_name": "air_temperature"}),
+          "pr": fakexr.field(pr, t, attrs={"units": "kg m-2 s-1"})}
+    return t, {"tas": tas, "pr": pr}, da
+
+
+def test_install_replaces_the_six_where_defined_and_where_re_exported(wired):
+    mods, names, _, originals = wired
+    for modname, m in mods.items():
+        for n, fn in originals.items():
+            assert f"{modname}.{n}" in names
+            assert getattr(m, n) is not fn and getattr(m, n).__wrapped__ is fn
+        assert not any(n.endswith(".isothermality") for n in names)
+    assert mods["xclim.indices"].tg_mean.__name__ == "tg_mean"
+
+
+@pytest.mark.parametrize("tunits", ["K", "degC"])
+def test_served_calls_are_one_launch_each(dev, wired, tunits):
+    mods, _, reached, _ = wired
+    m, pkg = mods["xclim.indices._anuclim"], mods["xclim.indices"]
+    t, f, da = _fields(tunits=tunits)
+    kw = dict(device=dev)
+    calls = [(lambda: m.temperature_seasonality(da["tas"], freq="YS-JUL"), anuclim.temperature_seasonality(f["tas"], t, "YS-JUL", units=tunits, **kw), "%", "YS-JUL"),
+             (lambda: pkg.precip_seasonality(da["pr"]), anuclim.precip_seasonality(f["pr"], t, **kw), "%"),
+             (lambda: m.tg_mean_warmcold_quarter(da["tas"], "coldest"), anuclim.tg_mean_warmcold_quarter(f["tas"], t, "coldest", **kw), tunits),
+             (lambda: m.tg_mean_wetdry_quarter(da["tas"], da["pr"], op="wettest"), anuclim.tg_mean_wetdry_quarter(f["tas"], f["pr"], t, "wettest", **kw), tunits),
+             (lambda: pkg.prcptot_wetdry_quarter(pr=da["pr"], op="dryest", freq="YS"), anuclim.prcptot_wetdry_quarter(f["pr"], t, "driest", **kw), "mm"),
+             (lambda: m.prcptot_warmcold_quarter(da["pr"], da["tas"], "warmest"), anuclim.prcptot_warmcold_quarter(f["pr"], f["tas"], t, "warmest", **kw), "mm")]
+    for call, want, units, *freq in calls:
+        trace = dev.start_trace()
+        try:
+            out = call()
+        finally:
+            dev.stop_trace()
+        assert [n for n, _ in trace if n.startswith("xh_")] == ["xh_bioclim"]
+        assert out.dims == ("time", "lat", "lon") and out.attrs["units"] == units
+        np.testing.assert_array_equal(out.values, want)
+        seg, _ = t.segments(freq[0] if freq else "YS")
+        np.testing.assert_array_equal(out["time"].dt.year.values, t.year[seg[:-1]])
+        assert set(out.coords) >= {"lat", "lon"}
+    assert out.attrs.get("standard_name") is None          # prcptot_warmcold_quarter: the attributes of pr
+    assert m.tg_mean_warmcold_quarter(da["tas"], "warmest").attrs["standard_name"] == "air_temperature"
+    assert not reached
+
+
+@pytest.mark.parametrize("form", ["chunked", "gappy", "units", "dims", "array"])
+def test_forwarded_forms_reach_the_original(wired, form):
+    mods, _, reached, _ = wired
+    m = mods["xclim.indices._anuclim"]
+    t, f, da = _fields(T=400)
+    tas, pr = da["tas"], da["pr"]
+    if form == "chunked":
+        tas = fakexr.field(f["tas"], t, attrs={"units": "K"}, chunks={"lat": 2})
+    elif form == "gappy":
+        keep = np.r_[0:10, 11:400]
+        t2 = t.subset(keep)
+        tas, pr = fakexr.field(f["tas"][keep], t2, attrs={"units": "K"}), fakexr.field(f["pr"][keep], t2, attrs={"units": "kg m-2 s-1"})
+    elif form == "units":
+        pr = fakexr.field(f["pr"], t, attrs={"units": "in/h"})
+    elif form == "dims":
+        pr = fakexr.field(f["pr"][:, :, :2], t, attrs={"units": "kg m-2 s-1"})
+    elif form == "array":
+        tas = f["tas"]
+    assert m.tg_mean_wetdry_quarter(tas, pr, "wettest") == "original tg_mean_wetdry_quarter"
+    assert reached == ["tg_mean_wetdry_quarter"]
+
+
+def test_an_unknown_op_raises_as_upstream(wired):
+    mods, _, reached, _ = wired
+    m = mods["xclim.indices._anuclim"]
+    _, _, da = _fields(T=400)
+    with pytest.raises(NotImplementedError):
+        m.tg_mean_warmcold_quarter(da["tas"], "wettest")
+    with pytest.raises(NotImplementedError):
+        m.prcptot_wetdry_quarter(da["pr"], op="toto")
+    assert not reached
+
+
+def test_uninstall_restores_by_identity(wired):
+    mods, _, _, originals = wired
+    patch.uninstall()
+    for m in mods.values():
+        for n, fn in originals.items():
+            assert getattr(m, n) is fn

@@ -238,6 +238,8 @@ SIGNATURES: dict[str, list] = {
     "xh_chill_hourly": [_vp, _i64, _i64, _i64, _int, _vp, _int, _i64, _vp, _vp, _dbl, _dbl, _int, _vp, _vp, _vp, _vp, _i64],
     "xh_chill_daily": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _dbl, _dbl, _int, _vp, _vp, _vp, _vp,
                        _i64],
+    "xh_bioclim": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _int, _i64, _vp, _vp, _int, _dbl, _dbl, _dbl,
+                   _vp, _vp, _vp, _i64],
 }
 _RESTYPES = {"xh_last_error": C.c_char_p}
 

@@ -1,0 +1,365 @@
+"""Host mirror of the ANUCLIM bioclimatic variables BIO1-BIO19 (reference: src/xclim/indices/_anuclim.py:66-625, P1-P19 of
+data/anuclim.yml).
+
+All nineteen are functions of one walk down (tas, tasmin, tasmax, pr) per cell and period, and run as ONE launch of
+``xh_bioclim`` (xclim_amd/csrc/bioclim.hip): one lane per (cell, period) bins a daily series into the 7-day steps
+``_to_quarter`` makes (counted from the first day of the series), keeps the last 13 steps (3 for monthly input) in registers
+for the quarter means and sums, and reduces the period's source rows on the way.  The launch reads only the fields its
+requested outputs need; every function here requests its own output, ``bioclim()`` any subset of the nineteen.
+
+Inputs are numpy arrays (or ``(T, C)`` device arrays) with TIME ON AXIS 0 and a gap-free daily, weekly (7-day) or monthly
+:class:`~xclim_amd.timeaxis.TimeAxis`; anything else — a gap, an irregular axis, fewer than three rows, from which no source
+frequency can be told — raises :class:`NotServed`.  float32 and float64 fields are read natively (a mixed set is widened to
+float64); ``tasmax - tasmin`` and BIO7 are taken in the fields' dtype as numpy does, everything else in float64.  Results are
+float64 ``(P, *cells)`` on the periods of ``time.segments(freq)``, or ``(P, C)`` device arrays with ``keep=True`` (which
+needs ``mask_missing=False``: the mask is applied on the host).
+
+Units.  ``units`` of the temperatures is "K" or "degC" (only BIO4 depends on it: the reference converts to kelvin first).
+``pr_units`` is a rate: "kg m-2 s-1" (= "mm/s"), "mm/d", "mm/week" or "mm/month"; the amount of a row is the rate times the
+row's duration (a day, 7 days, the month's length), as ``rate2amount`` gives it, in mm.  BIO15 turns a per-second rate into
+mm/d first, as the reference does.  ``thresh`` of ``prcptot`` is in ``pr_units``.
+
+``mask_missing=True`` applies MissingAny over the period's source rows of every field an output reads: daily rows against
+``time.expected_count(freq)``, monthly rows against the months of a period, weekly rows against the rows present (a NaN row
+masks, an incomplete first or last period does not).  The default is False, the reference's index functions.
+"""
+
+from __future__ import annotations
+
+import numpy as np
+
+from . import kernels as K
+from ._capi import DeviceArray, get_device
+from .converters import NotServed
+from .timeaxis import TimeAxis, parse_freq
+
+__all__ = ["isothermality", "temperature_seasonality", "precip_seasonality", "tg_mean_warmcold_quarter", "tg_mean_wetdry_quarter",
+           "prcptot_wetdry_quarter", "prcptot_warmcold_quarter", "prcptot", "prcptot_wetdry_period", "bioclim", "quarter_steps",
+           "axis_tables", "NotServed", "VARIABLES"]
+
+VARIABLES = K.BIOCLIM_VARS
+KELVIN_OFFSET = 273.15          # pint's degC <-> K offset
+SECONDS_PER_DAY = 86400.0
+PINT_MONTH_DAYS = 365.25 / 12   # pint's month
+
+_T_UNITS = {"K": 0.0, "degC": KELVIN_OFFSET}
+# rate unit -> (amount in mm per unit of rate and DAY of duration, the factor that takes the rate to mm/d for BIO15)
+_PR_UNITS = {"kg m-2 s-1": (SECONDS_PER_DAY, SECONDS_PER_DAY), "mm/s": (SECONDS_PER_DAY, SECONDS_PER_DAY), "mm/d": (1.0, 1.0),
+             "mm/week": (1.0 / 7.0, 1.0), "mm/month": (1.0 / PINT_MONTH_DAYS, 1.0)}
+_ARGMAX = {"wettest": True, "warmest": True, "dryest": False, "driest": False, "coldest": False}
+# what each variable reads
+_READS = {1: ("tas",), 2: ("tasmin", "tasmax"), 3: ("tasmin", "tasmax"), 4: ("tas",), 5: ("tasmax",), 6: ("tasmin",),
+          7: ("tasmin", "tasmax"), 8: ("tas", "pr"), 9: ("tas", "pr"), 10: ("tas",), 11: ("tas",), 12: ("pr",), 13: ("pr",),
+          14: ("pr",), 15: ("pr",), 16: ("pr",), 17: ("pr",), 18: ("tas", "pr"), 19: ("tas", "pr")}
+_WHICH_READS = {"wettest": ("pr",), "driest": ("pr",), "warmest": ("tas",), "coldest": ("tas",)}
+
+
+def source_kind(time: TimeAxis) -> str:
+    """"D", "W" or "M": the source frequency ``xarray.infer_freq`` would tell (:590-609), from a gap-free axis."""
+    if not isinstance(time, TimeAxis):
+        raise TypeError("time must be a TimeAxis")
+    if len(time) < 3:
+        raise NotServed("anuclim: the source frequency cannot be told from fewer than three rows")
+    step = np.diff(time.ordinal())
+    if np.all(step == 1):
+        return "D"
+    if np.all(step == 7):
+        return "W"
+    m0 = time.year * 12 + time.month
+    if np.all(np.diff(m0) == 1) and np.all(time.day == time.day[0]) and time.day[0] <= 28:
+        return "M"
+    raise NotServed("anuclim: a gap-free daily, weekly (7-day) or monthly time axis is needed")
+
+
+def axis_tables(time: TimeAxis, freq: str = "YS") -> dict:
+    """The host tables of ``xh_bioclim`` for an axis: ``step_off`` (S + 1), ``seg_rows`` / ``seg_steps`` (P + 1), ``W``,
+    ``binned``, ``days`` (the duration of every row in days) and ``kind``."""
+    kind = source_kind(time)
+    if parse_freq(freq)[0] not in ("Y", "Q", "M"):
+        raise NotServed(f"anuclim: periods of {freq!r} are not served")
+    T = len(time)
+    if kind == "D":
+        step_off = np.append(np.arange(0, T, 7), T).astype(np.int64)
+        days = np.ones(T)
+    elif kind == "W":
+        step_off, days = np.arange(T + 1, dtype=np.int64), np.full(T, 7.0)
+    else:
+        step_off, days = np.arange(T + 1, dtype=np.int64), time.days_in_month().astype(np.float64)
+    seg_rows = np.asarray(time.segments(freq)[0], np.int64)
+    seg_steps = np.searchsorted(step_off[:-1], seg_rows, side="left").astype(np.int64)   # a step belongs to the period of its first row
+    return dict(kind=kind, step_off=step_off, seg_rows=seg_rows, seg_steps=seg_steps, W=3 if kind == "M" else 13,
+                binned=kind == "D", days=days)
+
+
+def quarter_steps(time: TimeAxis) -> TimeAxis:
+    """The axis of the steps: the first day of every step, which the ``wettest`` ... step indices of ``bioclim`` point into."""
+    return time.subset(axis_tables(time)["step_off"][:-1])
+
+
+def _expected(time, freq, tab):
+    if tab["kind"] == "D":
+        return np.asarray(time.expected_count(freq), np.int64)
+    if tab["kind"] == "M":
+        return np.full(len(tab["seg_rows"]) - 1, {"Y": 12, "Q": 3, "M": 1}[parse_freq(freq)[0]], np.int64)
+    return np.diff(tab["seg_rows"])
+
+
+def _native(fields):
+    """The fields as float32 or float64 arrays of one dtype and shape: ({name: array}, f64, shape)."""
+    got = {}
+    for n, a in fields.items():
+        if a is None:
+            continue
+        if isinstance(a, DeviceArray):
+            if np.dtype(a.dtype) not in (np.float32, np.float64):
+                raise TypeError(f"{n}: device arrays must be float32 or float64, got {np.dtype(a.dtype).name}")
+        else:
+            a = np.asarray(a)
+            if a.dtype not in (np.float32, np.float64):
+                a = a.astype(np.float64)
+        got[n] = a
+    kinds = {np.dtype(a.dtype) for a in got.values()}
+    if len(kinds) > 1:
+        if any(isinstance(a, DeviceArray) for a in got.values()):
+            raise TypeError("anuclim: device arrays must share one dtype")
+        got = {n: a.astype(np.float64) for n, a in got.items()}
+    shapes = {tuple(a.shape) for a in got.values()}
+    if len(shapes) != 1:
+        raise ValueError(f"anuclim: the fields must have one shape, got {sorted(shapes)}")
+    shape = shapes.pop()
+    if len(shape) < 1:
+        raise ValueError("fields must have a time axis (axis 0)")
+    return got, shape
+
+
+def _run(fields, time, freq, variables, which, units, pr_units, thresh, device, keep, mask_missing):
+    """One launch: ``{name: (P, *cells)}`` for ``variables`` (BIO numbers) and ``which`` (quarter names)."""
+    if keep and mask_missing:
+        raise ValueError("keep=True returns the device arrays as computed: pass mask_missing=False")
+    try:
+        kelvin = _T_UNITS[units]
+    except KeyError:
+        raise ValueError(f"units must be one of {sorted(_T_UNITS)}, got {units!r}") from None
+    try:
+        per_day, cv_scale = _PR_UNITS[pr_units]
+    except KeyError:
+        raise ValueError(f"pr_units must be one of {sorted(_PR_UNITS)}, got {pr_units!r}") from None
+    reads = sorted({f for k in variables for f in _READS[k]} | {f for w in which for f in _WHICH_READS[w]})
+    for f in reads:
+        if fields.get(f) is None:
+            raise TypeError(f"anuclim: {f} is needed for the requested variables")
+    got, shape = _native({f: fields[f] for f in reads})
+    if shape[0] != len(time):
+        raise ValueError(f"time has {len(time)} rows, the fields {shape[0]}")
+    tab = axis_tables(time, freq)
+    T, cell_shape = shape[0], tuple(shape[1:])
+    C_ = int(np.prod(cell_shape, dtype=np.int64))
+    P = len(tab["seg_rows"]) - 1
+    names = [f"bio{k}" for k in variables] + list(which)
+    dev = device or get_device()
+    if P == 0 or C_ == 0:
+        dt = lambda n: np.float64 if n.startswith("bio") else np.int32  # noqa: E731
+        if keep:
+            return {n: dev.empty((P, C_), dt(n)) for n in names}
+        return {n: np.empty((P,) + cell_shape, dt(n)) for n in names}
+    d = {n: a.reshape(T, C_) if isinstance(a, DeviceArray) else dev.to_device(np.ascontiguousarray(a).reshape(T, C_))
+         for n, a in got.items()}
+    counts = ["n_" + f for f in reads] if mask_missing else []
+    outs = K.bioclim(dev, d, tab["step_off"], per_day * tab["days"], tab["seg_rows"], tab["seg_steps"], tab["W"],
+                     binned=tab["binned"], kelvin_offset=kelvin, cv_scale=cv_scale, thresh=float(thresh),
+                     outputs=names + counts)
+    if keep:
+        return {n: outs[n] for n in names}
+    res = {n: outs[n].get() for n in names}
+    if mask_missing:
+        expected = _expected(time, freq, tab)
+        bad = {f: outs["n_" + f].get() != expected[:, None] for f in reads}
+        for k in variables:
+            for f in _READS[k]:
+                res[f"bio{k}"][bad[f]] = np.nan
+    return {n: a.reshape((P,) + cell_shape) for n, a in res.items()}
+
+
+def _op(op, allowed, what):
+    if op not in allowed:
+        raise NotImplementedError(f'op parameter ({op}) may only be one of {what}')
+    return _ARGMAX[op]
+
+
+def _one(k, fields, time, freq, units="K", pr_units="kg m-2 s-1", thresh=0.0, device=None, keep=False, mask_missing=False):
+    return _run(fields, time, freq, (k,), (), units, pr_units, thresh, device, keep, mask_missing)[f"bio{k}"]
+
+
+def isothermality(tasmin, tasmax, time: TimeAxis, freq: str = "YS", *, device=None, keep: bool = False,
+                  mask_missing: bool = False):
+    """_anuclim.py:66-101 (BIO3): mean diurnal range over the extreme temperature range of the period [%]."""
+    return _one(3, dict(tasmin=tasmin, tasmax=tasmax), time, freq, device=device, keep=keep, mask_missing=mask_missing)
+
+
+def temperature_seasonality(tas, time: TimeAxis, freq: str = "YS", *, units: str = "K", device=None, keep: bool = False,
+                            mask_missing: bool = False):
+    """_anuclim.py:104-154 (BIO4): 100 * std / mean of tas in kelvin (ddof = 0) [%]."""
+    return _one(4, dict(tas=tas), time, freq, units=units, device=device, keep=keep, mask_missing=mask_missing)
+
+
+def precip_seasonality(pr, time: TimeAxis, freq: str = "YS", *, pr_units: str = "kg m-2 s-1", device=None, keep: bool = False,
+                       mask_missing: bool = False):
+    """_anuclim.py:157-211 (BIO15): 100 * std / mean of pr, a per-second rate in mm/d first [%]."""
+    return _one(15, dict(pr=pr), time, freq, pr_units=pr_units, device=device, keep=keep, mask_missing=mask_missing)
+
+
+def tg_mean_warmcold_quarter(tas, time: TimeAxis, op: str, freq: str = "YS", *, device=None, keep: bool = False,
+                             mask_missing: bool = False):
+    """_anuclim.py:214-271 (BIO10 / BIO11): mean temperature of the warmest / coldest quarter, in the units of tas."""
+    k = 10 if _op(op, ("warmest", "coldest"), '"warmest", "coldest"') else 11
+    return _one(k, dict(tas=tas), time, freq, device=device, keep=keep, mask_missing=mask_missing)
+
+
+def tg_mean_wetdry_quarter(tas, pr, time: TimeAxis, op: str, freq: str = "YS", *, pr_units: str = "kg m-2 s-1", device=None,
+                           keep: bool = False, mask_missing: bool = False):
+    """_anuclim.py:274-327 (BIO8 / BIO9): mean temperature of the wettest / driest quarter."""
+    k = 8 if _op(op, ("wettest", "driest", "dryest"), '"wettest" or "driest"') else 9
+    return _one(k, dict(tas=tas, pr=pr), time, freq, pr_units=pr_units, device=device, keep=keep, mask_missing=mask_missing)
+
+
+def prcptot_wetdry_quarter(pr, time: TimeAxis, op: str, freq: str = "YS", *, pr_units: str = "kg m-2 s-1", device=None,
+                           keep: bool = False, mask_missing: bool = False):
+    """_anuclim.py:330-385 (BIO16 / BIO17): precipitation of the wettest / driest quarter [mm]."""
+    k = 16 if _op(op, ("wettest", "driest", "dryest"), '"wettest" or "driest"') else 17
+    return _one(k, dict(pr=pr), time, freq, pr_units=pr_units, device=device, keep=keep, mask_missing=mask_missing)
+
+
+def prcptot_warmcold_quarter(pr, tas, time: TimeAxis, op: str, freq: str = "YS", *, pr_units: str = "kg m-2 s-1", device=None,
+                             keep: bool = False, mask_missing: bool = False):
+    """_anuclim.py:388-442 (BIO18 / BIO19): precipitation of the warmest / coldest quarter [mm]."""
+    k = 18 if _op(op, ("warmest", "coldest"), '"warmest", "coldest"') else 19
+    return _one(k, dict(tas=tas, pr=pr), time, freq, pr_units=pr_units, device=device, keep=keep, mask_missing=mask_missing)
+
+
+def prcptot(pr, time: TimeAxis, thresh: float = 0.0, freq: str = "YS", *, pr_units: str = "kg m-2 s-1", device=None,
+            keep: bool = False, mask_missing: bool = False):
+    """_anuclim.py:445-470 (BIO12): the amounts of the rows with ``pr >= thresh`` (``thresh`` in ``pr_units``) [mm]."""
+    return _one(12, dict(pr=pr), time, freq, pr_units=pr_units, thresh=thresh, device=device, keep=keep, mask_missing=mask_missing)
+
+
+def prcptot_wetdry_period(pr, time: TimeAxis, *, op: str, freq: str = "YS", pr_units: str = "kg m-2 s-1", device=None,
+                          keep: bool = False, mask_missing: bool = False):
+    """_anuclim.py:473-517 (BIO13 / BIO14): the amount of the wettest / driest single row (day, week or month) [mm]."""
+    k = 13 if _op(op, ("wettest", "driest", "dryest"), '"wettest" or "driest"') else 14
+    return _one(k, dict(pr=pr), time, freq, pr_units=pr_units, device=device, keep=keep, mask_missing=mask_missing)
+
+
+def bioclim(tas=None, tasmin=None, tasmax=None, pr=None, time: TimeAxis = None, freq: str = "YS", variables=None, *,
+            which=(), units: str = "K", pr_units: str = "kg m-2 s-1", thresh: float = 0.0, device=None, keep: bool = False,
+            mask_missing: bool = False) -> dict:
+    """``{"bio1": ..., "bio19": ...}`` from ONE launch.  ``variables``: BIO numbers or names (None = all nineteen; the
+    fields they read must be given).  ``which``: any of "wettest", "driest", "warmest", "coldest" adds the int32 step index
+    of that quarter (-1 without one) under that name; :func:`quarter_steps` gives the dates the indices point at."""
+    if time is None:
+        raise TypeError("bioclim: time is needed")
+    if variables is None:
+        variables = range(1, 20)
+    ks = sorted({int(str(v).lower().replace("bio", "")) for v in variables})
+    if not ks and not which or any(not 1 <= k <= 19 for k in ks):
+        raise ValueError("bioclim: variables must be a non-empty subset of bio1 .. bio19")
+    which = tuple("driest" if w == "dryest" else w for w in which)
+    if set(which) - set(K.BIOCLIM_WHICH):
+        raise ValueError(f"bioclim: which must be among {K.BIOCLIM_WHICH}")
+    return _run(dict(tas=tas, tasmin=tasmin, tasmax=tasmax, pr=pr), time, freq, ks, which, units, pr_units, thresh, device, keep,
+                mask_missing)
+
+
+# ---- the xarray adapter (patch.install) ------------------------------------------------------------------------------
+ADAPTED = ("temperature_seasonality", "precip_seasonality", "tg_mean_warmcold_quarter", "tg_mean_wetdry_quarter",
+           "prcptot_wetdry_quarter", "prcptot_warmcold_quarter")
+_T_SPELLINGS = {"K": "K", "kelvin": "K", "degK": "K", "degC": "degC", "°C": "degC", "celsius": "degC", "degree_Celsius": "degC", "C": "degC"}
+_PR_SPELLINGS = {"kg m-2 s-1": "kg m-2 s-1", "kg/m2/s": "kg m-2 s-1", "mm/s": "mm/s", "mm s-1": "mm/s", "mm/d": "mm/d", "mm/day": "mm/d",
+                 "mm d-1": "mm/d", "mm day-1": "mm/d", "mm / d": "mm/d", "mm/week": "mm/week", "mm week-1": "mm/week",
+                 "mm/month": "mm/month", "mm month-1": "mm/month"}
+
+
+def make_adapters(env, originals: dict, device=None) -> dict:
+    """Same-signature replacements of the four quarter functions and the two seasonality functions of
+    ``xclim.indices._anuclim`` (:104-442) on DataArrays with a time dimension: each is ONE launch of ``xh_bioclim``.  The
+    result keeps the cell dimensions and coordinates of the (first) field, the period starts of ``resample(time=freq)`` as
+    its time coordinate and the units the reference gives it ("%", the units of ``tas``, "mm").  Chunked or time-less fields,
+    fields on different dimensions, units this module has no factor for and every axis :class:`NotServed` refuses go to the
+    saved originals; an unknown ``op`` raises NotImplementedError, as upstream."""
+    from .xr_adapter import _cell_coords, _cell_dims, _tfirst, is_chunked, time_axis_of
+
+    DA = env.DataArray
+
+    def _serve(fields, spellings):
+        """(time-first reference array, {name: values}, TimeAxis, {name: unit keyword})"""
+        a, vals, units = None, {}, {}
+        for (name, da), table in zip(fields.items(), spellings):
+            if not isinstance(da, DA) or "time" not in da.dims or is_chunked(da):
+                raise NotServed("chunked or time-less fields")
+            u = table.get(str(da.attrs.get("units", "")).strip())
+            if u is None:
+                raise NotServed(f"{name}: units {da.attrs.get('units')!r}")
+            b, x = _tfirst(da)
+            if a is None:
+                a = b
+            elif tuple(b.dims) != tuple(a.dims) or b.shape != a.shape:
+                raise NotServed("fields on different dimensions")
+            vals[name], units[name] = x, u
+        return a, vals, time_axis_of(a), units
+
+    def _wrap(a, values, freq, attrs):
+        coords = dict(_cell_coords(a))
+        coords["time"] = a["time"].resample(time=freq).first()["time"]
+        return DA(np.asarray(values), coords=coords, dims=("time",) + _cell_dims(a), attrs=attrs)
+
+    def _adapter(name, fields_of, spellings, call, out_units):
+        orig = originals[name]
+
+        def fn(*args, **kwargs):
+            import inspect
+
+            try:
+                bound = inspect.signature(fn.__wrapped__).bind(*args, **kwargs)
+            except (TypeError, ValueError):
+                return orig(*args, **kwargs)
+            bound.apply_defaults()
+            p = bound.arguments
+            if "op" in p:   # upstream checks op after _to_quarter; an unknown op is its NotImplementedError either way
+                _op(p["op"], *_OPS[name])
+            try:
+                a, vals, time, units = _serve({k: p[k] for k in fields_of}, spellings)
+                values = call(vals, time, units, p, device)
+            except NotServed:
+                return orig(*args, **kwargs)
+            first = p[fields_of[0]]
+            return _wrap(a, values, p.get("freq", "YS"), dict(first.attrs, units=out_units(p)))
+
+        fn.__wrapped__ = orig
+        fn.__name__, fn.__doc__ = name, getattr(orig, "__doc__", None)
+        return fn
+
+    wetdry, warmcold = (("wettest", "driest", "dryest"), '"wettest" or "driest"'), (("warmest", "coldest"), '"warmest", "coldest"')
+    _OPS = {"tg_mean_warmcold_quarter": warmcold, "tg_mean_wetdry_quarter": wetdry, "prcptot_wetdry_quarter": wetdry,
+            "prcptot_warmcold_quarter": warmcold}
+    T, PR = _T_SPELLINGS, _PR_SPELLINGS
+    kw = lambda u, d: dict(pr_units=u.get("pr", "kg m-2 s-1"), device=d)  # noqa: E731
+    return {
+        "temperature_seasonality": _adapter(
+            "temperature_seasonality", ("tas",), (T,),
+            lambda v, t, u, p, d: temperature_seasonality(v["tas"], t, p["freq"], units=u["tas"], device=d), lambda p: "%"),
+        "precip_seasonality": _adapter(
+            "precip_seasonality", ("pr",), (PR,),
+            lambda v, t, u, p, d: precip_seasonality(v["pr"], t, p["freq"], **kw(u, d)), lambda p: "%"),
+        "tg_mean_warmcold_quarter": _adapter(
+            "tg_mean_warmcold_quarter", ("tas",), (T,),
+            lambda v, t, u, p, d: tg_mean_warmcold_quarter(v["tas"], t, p["op"], p["freq"], device=d), lambda p: p["tas"].attrs["units"]),
+        "tg_mean_wetdry_quarter": _adapter(
+            "tg_mean_wetdry_quarter", ("tas", "pr"), (T, PR),
+            lambda v, t, u, p, d: tg_mean_wetdry_quarter(v["tas"], v["pr"], t, p["op"], p["freq"], **kw(u, d)),
+            lambda p: p["tas"].attrs["units"]),
+        "prcptot_wetdry_quarter": _adapter(
+            "prcptot_wetdry_quarter", ("pr",), (PR,),
+            lambda v, t, u, p, d: prcptot_wetdry_quarter(v["pr"], t, p["op"], p["freq"], **kw(u, d)), lambda p: "mm"),
+        "prcptot_warmcold_quarter": _adapter(
+            "prcptot_warmcold_quarter", ("pr", "tas"), (PR, T),
+            lambda v, t, u, p, d: prcptot_warmcold_quarter(v["pr"], v["tas"], t, p["op"], p["freq"], **kw(u, d)), lambda p: "mm"),
+    }

@@ -1278,6 +1278,57 @@ def chill_daily(dev: Device, tasmin: DeviceArray, tasmax: DeviceArray, dl: Devic
     return outs
 
 
+BIOCLIM_FIELDS = ("tas", "tasmin", "tasmax", "pr")
+BIOCLIM_VARS = tuple(f"bio{k}" for k in range(1, 20))
+BIOCLIM_WHICH = ("wettest", "driest", "warmest", "coldest")
+BIOCLIM_COUNTS = tuple("n_" + f for f in BIOCLIM_FIELDS)
+
+
+def bioclim(dev: Device, fields: dict, step_off, factor, seg_rows, seg_steps, W: int, *, binned: bool = True,
+            kelvin_offset: float = 0.0, cv_scale: float = 1.0, thresh: float = 0.0, outputs=BIOCLIM_VARS) -> dict:
+    """xh_bioclim.  ``fields``: name -> (T, C) DeviceArray for tas / tasmin / tasmax / pr (the ones the requested outputs
+    read), all float32 or all float64.  Host tables: ``step_off`` (S + 1) first rows of the steps, ``factor`` (T) amount per
+    unit of pr, ``seg_rows`` / ``seg_steps`` (P + 1) first row / first step of the periods.  ``outputs``: a subset of
+    bio1 .. bio19 ((P, C) float64), wettest / driest / warmest / coldest (the step index of that quarter, int32, -1 without
+    one) and n_tas / n_tasmin / n_tasmax / n_pr (rows with a value, int32).  Returns ``{name: DeviceArray}``; one launch."""
+    allowed = BIOCLIM_VARS + BIOCLIM_WHICH + BIOCLIM_COUNTS
+    unknown = set(outputs) - set(allowed)
+    if unknown:
+        raise ValueError(f"bioclim: unknown outputs {sorted(unknown)}")
+    outputs = [o for o in allowed if o in set(outputs)]
+    got = {n: fields[n] for n in BIOCLIM_FIELDS if fields.get(n) is not None}
+    if not got:
+        raise TypeError("bioclim: no field given")
+    kinds = {np.dtype(v.dtype) for v in got.values()}
+    if len(kinds) > 1 or not kinds <= {np.dtype(np.float32), np.dtype(np.float64)}:
+        raise TypeError("bioclim: the fields must be all float32 or all float64")
+    shapes = {_tc(v, None) for v in got.values()}
+    if len(shapes) > 1:
+        raise ValueError("bioclim: every field must have the same (T, C) shape")
+    (T, C_), = shapes
+    so = np.ascontiguousarray(step_off, dtype=np.int64)
+    fa = np.ascontiguousarray(factor, dtype=np.float64)
+    sr = np.ascontiguousarray(seg_rows, dtype=np.int64)
+    ss = np.ascontiguousarray(seg_steps, dtype=np.int64)
+    if so.ndim != 1 or len(so) < 1 or fa.shape != (T,) or sr.ndim != 1 or sr.shape != ss.shape or len(sr) < 1:
+        raise ValueError("bioclim: step_off (S + 1), factor (T), seg_rows and seg_steps (P + 1 each) expected")
+    S, P = len(so) - 1, len(sr) - 1
+    outs = {o: dev.empty((P, C_), np.float64 if o in BIOCLIM_VARS else np.int32) for o in outputs}
+
+    def table(names):
+        arr = (_vp * len(names))()
+        for k, n in enumerate(names):
+            if n in outs:
+                arr[k] = outs[n].ptr
+        return arr
+
+    ptr = lambda n: _vp(got[n].ptr) if n in got else _vp(0)  # noqa: E731
+    dev.call("xh_bioclim", T, C_, C_, int(kinds.pop() == np.float64), ptr("tas"), ptr("tasmin"), ptr("tasmax"), ptr("pr"), S,
+             np_ptr(so), np_ptr(fa if T else np.zeros(1)), int(bool(binned)), P, np_ptr(sr), np_ptr(ss), int(W), float(kelvin_offset),
+             float(cv_scale), float(thresh), table(BIOCLIM_VARS), table(BIOCLIM_WHICH), table(BIOCLIM_COUNTS), C_)
+    return outs
+
+
 SI_DISTS = {"gamma": 0, "fisk": 1}
 SI_METHODS = {"APP": 0, "ML": 1}
 SI_STAGING = {"auto": 0, "global": 1, "lds": 2}

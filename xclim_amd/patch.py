@@ -114,6 +114,9 @@ _CHILL_NAME = "_chill_portion_one_season"  # indices/_agro.py:1442-1465, called 
 # PET and the water budget: water_budget calls potential_evapotranspiration by module-global name (converters.py:2718); the
 # three indicators hold the function objects as a staticmethod ``compute`` on their classes (core/indicator.py:515-517,
 # indicators/convert/_conversion.py:418-470)
+# the ANUCLIM quarter and seasonality functions: public functions of _anuclim.py (:104-442) that xclim.indices re-exports
+# (indices/__init__.py: ``from ._anuclim import *``) and the anuclim.yml indicators reach through that namespace
+_ANUCLIM_MODULES = ("xclim.indices._anuclim", "xclim.indices")
 _PET_MODULE = "xclim.indices.converters"
 _PET_NAMES = ("potential_evapotranspiration", "water_budget")
 _PET_INDICATORS = {"xclim.indicators.convert._conversion": ("potential_evapotranspiration", "water_budget_from_tas",
@@ -253,6 +256,20 @@ def install(env=None, modules=None) -> list[str]:
 
         orig_chill = _saved.get((_CHILL_MODULE, _CHILL_NAME), getattr(amod, _CHILL_NAME))
         patch(_CHILL_MODULE, _CHILL_NAME, chill_adapters(orig_chill)[_CHILL_NAME])
+    # BIO4, BIO8-BIO11 and BIO15-BIO19: one launch of xh_bioclim each; replaced where they are defined and, by identity, where
+    # xclim.indices re-exports them
+    bmod = resolve(_ANUCLIM_MODULES[0])
+    if bmod is not None:
+        from .anuclim import ADAPTED, make_adapters as anuclim_adapters
+
+        if all(hasattr(bmod, n) for n in ADAPTED):
+            origs = {n: _saved.get((_ANUCLIM_MODULES[0], n), getattr(bmod, n)) for n in ADAPTED}
+            bio = anuclim_adapters(env, origs)
+            for modname in _ANUCLIM_MODULES:
+                m = resolve(modname)
+                for name in ADAPTED:
+                    if m is not None and _saved.get((modname, name), getattr(m, name, None)) is origs[name]:
+                        patch(modname, name, bio[name])
     cmod = resolve(_PET_MODULE)
     if cmod is not None and all(hasattr(cmod, n) for n in _PET_NAMES):
         from .converters import make_adapters as pet_adapters

@@ -28,9 +28,10 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import fields as F
 from . import kernels as K
-from ._capi import DeviceArray, get_device
-from .converters import NotServed
+from ._capi import get_device
+from .fields import NotServed
 from .timeaxis import TimeAxis, parse_freq
 
 __all__ = ["isothermality", "temperature_seasonality", "precip_seasonality", "tg_mean_warmcold_quarter", "tg_mean_wetdry_quarter",
@@ -104,34 +105,6 @@ def _expected(time, freq, tab):
     return np.diff(tab["seg_rows"])
 
 
-def _native(fields):
-    """The fields as float32 or float64 arrays of one dtype and shape: ({name: array}, f64, shape)."""
-    got = {}
-    for n, a in fields.items():
-        if a is None:
-            continue
-        if isinstance(a, DeviceArray):
-            if np.dtype(a.dtype) not in (np.float32, np.float64):
-                raise TypeError(f"{n}: device arrays must be float32 or float64, got {np.dtype(a.dtype).name}")
-        else:
-            a = np.asarray(a)
-            if a.dtype not in (np.float32, np.float64):
-                a = a.astype(np.float64)
-        got[n] = a
-    kinds = {np.dtype(a.dtype) for a in got.values()}
-    if len(kinds) > 1:
-        if any(isinstance(a, DeviceArray) for a in got.values()):
-            raise TypeError("anuclim: device arrays must share one dtype")
-        got = {n: a.astype(np.float64) for n, a in got.items()}
-    shapes = {tuple(a.shape) for a in got.values()}
-    if len(shapes) != 1:
-        raise ValueError(f"anuclim: the fields must have one shape, got {sorted(shapes)}")
-    shape = shapes.pop()
-    if len(shape) < 1:
-        raise ValueError("fields must have a time axis (axis 0)")
-    return got, shape
-
-
 def _run(fields, time, freq, variables, which, units, pr_units, thresh, device, keep, mask_missing):
     """One launch: ``{name: (P, *cells)}`` for ``variables`` (BIO numbers) and ``which`` (quarter names)."""
     if keep and mask_missing:
@@ -148,36 +121,32 @@ def _run(fields, time, freq, variables, which, units, pr_units, thresh, device, 
     for f in reads:
         if fields.get(f) is None:
             raise TypeError(f"anuclim: {f} is needed for the requested variables")
-    got, shape = _native({f: fields[f] for f in reads})
-    if shape[0] != len(time):
-        raise ValueError(f"time has {len(time)} rows, the fields {shape[0]}")
+    got = F.native_set({f: fields[f] for f in reads})
+    T, cell_shape, C_ = F.shape_of(got)
+    if T != len(time):
+        raise ValueError(f"time has {len(time)} rows, the fields {T}")
     tab = axis_tables(time, freq)
-    T, cell_shape = shape[0], tuple(shape[1:])
-    C_ = int(np.prod(cell_shape, dtype=np.int64))
     P = len(tab["seg_rows"]) - 1
     names = [f"bio{k}" for k in variables] + list(which)
-    dev = device or get_device()
     if P == 0 or C_ == 0:
-        dt = lambda n: np.float64 if n.startswith("bio") else np.int32  # noqa: E731
-        if keep:
-            return {n: dev.empty((P, C_), dt(n)) for n in names}
-        return {n: np.empty((P,) + cell_shape, dt(n)) for n in names}
-    d = {n: a.reshape(T, C_) if isinstance(a, DeviceArray) else dev.to_device(np.ascontiguousarray(a).reshape(T, C_))
-         for n, a in got.items()}
+        dtypes = {n: np.float64 if n.startswith("bio") else np.int32 for n in names}
+        return F.empty_result(dtypes, P, cell_shape, keep, device)
+    dev = device or get_device()
+    d = {n: F.rows_on_device(dev, a, T, C_) for n, a in got.items()}
     counts = ["n_" + f for f in reads] if mask_missing else []
     outs = K.bioclim(dev, d, tab["step_off"], per_day * tab["days"], tab["seg_rows"], tab["seg_steps"], tab["W"],
                      binned=tab["binned"], kelvin_offset=kelvin, cv_scale=cv_scale, thresh=float(thresh),
                      outputs=names + counts)
     if keep:
         return {n: outs[n] for n in names}
-    res = {n: outs[n].get() for n in names}
+    res = F.host_result({n: outs[n] for n in names + counts}, P, cell_shape)
     if mask_missing:
-        expected = _expected(time, freq, tab)
-        bad = {f: outs["n_" + f].get() != expected[:, None] for f in reads}
+        expected = _expected(time, freq, tab).reshape((P,) + (1,) * len(cell_shape))
+        bad = {f: res.pop("n_" + f) != expected for f in reads}
         for k in variables:
             for f in _READS[k]:
                 res[f"bio{k}"][bad[f]] = np.nan
-    return {n: a.reshape((P,) + cell_shape) for n, a in res.items()}
+    return res
 
 
 def _op(op, allowed, what):
@@ -285,31 +254,21 @@ def make_adapters(env, originals: dict, device=None) -> dict:
     its time coordinate and the units the reference gives it ("%", the units of ``tas``, "mm").  Chunked or time-less fields,
     fields on different dimensions, units this module has no factor for and every axis :class:`NotServed` refuses go to the
     saved originals; an unknown ``op`` raises NotImplementedError, as upstream."""
-    from .xr_adapter import _cell_coords, _cell_dims, _tfirst, is_chunked, time_axis_of
+    from .xr_adapter import _tfirst_fields, _wrap_cells, time_axis_of
 
     DA = env.DataArray
 
     def _serve(fields, spellings):
         """(time-first reference array, {name: values}, TimeAxis, {name: unit keyword})"""
-        a, vals, units = None, {}, {}
+        a, vals = _tfirst_fields(DA, fields)
+        if any(x.shape != a.shape for x in vals.values()):
+            raise NotServed("fields on different dimensions")
+        units = {}
         for (name, da), table in zip(fields.items(), spellings):
-            if not isinstance(da, DA) or "time" not in da.dims or is_chunked(da):
-                raise NotServed("chunked or time-less fields")
-            u = table.get(str(da.attrs.get("units", "")).strip())
-            if u is None:
+            units[name] = table.get(str(da.attrs.get("units", "")).strip())
+            if units[name] is None:
                 raise NotServed(f"{name}: units {da.attrs.get('units')!r}")
-            b, x = _tfirst(da)
-            if a is None:
-                a = b
-            elif tuple(b.dims) != tuple(a.dims) or b.shape != a.shape:
-                raise NotServed("fields on different dimensions")
-            vals[name], units[name] = x, u
         return a, vals, time_axis_of(a), units
-
-    def _wrap(a, values, freq, attrs):
-        coords = dict(_cell_coords(a))
-        coords["time"] = a["time"].resample(time=freq).first()["time"]
-        return DA(np.asarray(values), coords=coords, dims=("time",) + _cell_dims(a), attrs=attrs)
 
     def _adapter(name, fields_of, spellings, call, out_units):
         orig = originals[name]
@@ -331,7 +290,8 @@ def make_adapters(env, originals: dict, device=None) -> dict:
             except NotServed:
                 return orig(*args, **kwargs)
             first = p[fields_of[0]]
-            return _wrap(a, values, p.get("freq", "YS"), dict(first.attrs, units=out_units(p)))
+            starts = a["time"].resample(time=p.get("freq", "YS")).first()["time"]
+            return _wrap_cells(DA, a, values, starts, dict(first.attrs, units=out_units(p)))
 
         fn.__wrapped__ = orig
         fn.__name__, fn.__doc__ = name, getattr(orig, "__doc__", None)

@@ -27,8 +27,9 @@ from collections import namedtuple
 
 import numpy as np
 
+from . import fields as F
 from . import kernels as K
-from ._capi import DeviceArray, get_device
+from ._capi import get_device
 from .converters import NotServed, _check_time, _lat_table, day_angle
 from .timeaxis import TimeAxis
 
@@ -49,33 +50,6 @@ def _offsets(units):
         return _UNITS[units]
     except KeyError:
         raise ValueError(f"units must be one of {sorted(_UNITS)}, got {units!r}") from None
-
-
-def _native(a, name):
-    if isinstance(a, DeviceArray):
-        if np.dtype(a.dtype) not in (np.float32, np.float64):
-            raise TypeError(f"{name}: device arrays must be float32 or float64, got {np.dtype(a.dtype).name}")
-        return a
-    a = np.asarray(a)
-    return a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
-
-
-def _pair(tasmin, tasmax):
-    """tasmin / tasmax sharing one dtype (a mixed pair is widened to float64, which is what their difference would be)."""
-    tn, tx = _native(tasmin, "tasmin"), _native(tasmax, "tasmax")
-    if np.dtype(tn.dtype) != np.dtype(tx.dtype):
-        if isinstance(tn, DeviceArray) or isinstance(tx, DeviceArray):
-            raise TypeError("tasmin and tasmax: device arrays must share one dtype")
-        tn, tx = tn.astype(np.float64), tx.astype(np.float64)
-    if tuple(tn.shape) != tuple(tx.shape):
-        raise ValueError(f"tasmax: shape {tuple(tx.shape)} differs from {tuple(tn.shape)}")
-    return tn, tx
-
-
-def _upload(dev, a, rows, C_):
-    if isinstance(a, DeviceArray):
-        return a.reshape(rows, C_)
-    return dev.to_device(np.ascontiguousarray(a).reshape(rows, C_))
 
 
 def day_selection(time: TimeAxis, **indexer):
@@ -105,13 +79,11 @@ def hourly_expected_count(time: TimeAxis, freq: str, **indexer):
     return HOURS * np.asarray(time.expected_count(freq, **indexer), np.int64)
 
 
-def _check_hourly(tas, time):
+def _check_hourly(rows, time):
     if not isinstance(time, TimeAxis):
         raise TypeError("time must be the daily TimeAxis of the days")
-    if len(tas.shape) < 1:
-        raise ValueError("fields must have a time axis (axis 0)")
-    if tas.shape[0] != HOURS * len(time):
-        raise ValueError(f"the hourly field has {tas.shape[0]} rows; {HOURS} * {len(time)} days = {HOURS * len(time)} expected "
+    if rows != HOURS * len(time):
+        raise ValueError(f"the hourly field has {rows} rows; {HOURS} * {len(time)} days = {HOURS * len(time)} expected "
                          "(day-major from hour 0)")
 
 
@@ -127,32 +99,27 @@ def _reduce(run, names, time, freq, indexer, cell_shape, C_, P, nsel, keep, mask
     if keep and mask_missing:
         raise ValueError("keep=True returns the device arrays as computed: pass mask_missing=False")
     if P == 0 or C_ == 0:
-        if keep:
-            dev = device or get_device()
-            return {n: dev.empty((P, C_), np.float64) for n in names}
-        return {n: np.empty((P,) + tuple(cell_shape), np.float64) for n in names}
+        return F.empty_result(dict.fromkeys(names, np.float64), P, cell_shape, keep, device)
     outs = run(list(names) + ([] if keep else ["valid"]))
     if keep:
         return {n: outs[n] for n in names}
-    valid = outs["valid"].get()
-    res = {}
-    for n in names:
-        a = outs[n].get()
+    res = F.host_result({n: outs[n] for n in ("valid",) + tuple(names)}, P, cell_shape)
+    valid = res.pop("valid")
+    if mask_missing:
+        expected = hourly_expected_count(time, freq, **indexer).reshape((P,) + (1,) * len(cell_shape))
+    for n, a in res.items():
         if n == "cp":
-            a[nsel == 0, :] = np.nan  # a period without a selected hour (see the module text)
+            a[nsel == 0] = np.nan  # a period without a selected hour (see the module text)
         if mask_missing:
-            expected = hourly_expected_count(time, freq, **indexer)
-            a[valid != expected[:, None]] = np.nan
-        res[n] = a.reshape((P,) + tuple(cell_shape))
+            a[valid != expected] = np.nan
     return res
 
 
 def _hourly(tas, time, freq, units, names, positive_only, indexer, device, keep, mask_missing):
     add_K, sub_C = _offsets(units)
-    tas = _native(tas, "tas")
-    _check_hourly(tas, time)
-    cell_shape = tuple(tas.shape[1:])
-    C_ = int(np.prod(cell_shape, dtype=np.int64))
+    tas = F.native(tas, "tas")
+    H, cell_shape, C_ = F.shape_of({"tas": tas})
+    _check_hourly(H, time)
     seg = hourly_segments(time, freq)
     P = len(seg) - 1
     sel = row_selection(time, **indexer)
@@ -160,7 +127,7 @@ def _hourly(tas, time, freq, units, names, positive_only, indexer, device, keep,
 
     def run(outputs):
         dev = device or get_device()
-        return K.chill_hourly(dev, _upload(dev, tas, tas.shape[0], C_), seg, sel, add_K=add_K, sub_C=sub_C,
+        return K.chill_hourly(dev, F.rows_on_device(dev, tas, H, C_), seg, sel, add_K=add_K, sub_C=sub_C,
                               positive_only=positive_only, outputs=outputs)
 
     return _reduce(run, names, time, freq, indexer, cell_shape, C_, P, nsel, keep, mask_missing, device)
@@ -185,27 +152,24 @@ def chill_units(tas, time: TimeAxis, positive_only: bool = False, freq: str = "Y
 def _daily_inputs(tasmin, tasmax, lat, time, infill_polar_days):
     if infill_polar_days:
         raise NotServed("make_hourly_temperature: infill_polar_days=True is not served")
-    tn, tx = _pair(tasmin, tasmax)
+    tn, tx = F.native_set({"tasmin": tasmin, "tasmax": tasmax}).values()  # (a mixed pair is float64, as its difference would be)
+    D, cell_shape, C_ = F.shape_of({"tasmin": tn, "tasmax": tx})
     if not isinstance(time, TimeAxis):
         raise TypeError("time must be the daily TimeAxis of the days")
-    if len(tn.shape) < 1:
-        raise ValueError("fields must have a time axis (axis 0)")
-    if tn.shape[0] != len(time):
-        raise ValueError(f"time has {len(time)} rows, the fields {tn.shape[0]}")
+    if D != len(time):
+        raise ValueError(f"time has {len(time)} rows, the fields {D}")
     try:
         _check_time(time)
     except NotServed as e:
         raise NotServed(str(e).replace("potential evapotranspiration", "make_hourly_temperature")) from None
-    cell_shape = tuple(tn.shape[1:])
     lat_u, li = _lat_table(lat, cell_shape)
-    return tn, tx, cell_shape, lat_u, li
+    return tn, tx, cell_shape, C_, lat_u, li
 
 
 def _daily(tasmin, tasmax, lat, time, freq, units, names, positive_only, indexer, device, keep, mask_missing,
            infill_polar_days=False):
     add_K, sub_C = _offsets(units)
-    tn, tx, cell_shape, lat_u, li = _daily_inputs(tasmin, tasmax, lat, time, infill_polar_days)
-    C_ = int(np.prod(cell_shape, dtype=np.int64))
+    tn, tx, cell_shape, C_, lat_u, li = _daily_inputs(tasmin, tasmax, lat, time, infill_polar_days)
     D = len(time)
     seg = np.asarray(time.segments(freq)[0], np.int64)
     P = len(seg) - 1
@@ -215,8 +179,8 @@ def _daily(tasmin, tasmax, lat, time, freq, units, names, positive_only, indexer
     def run(outputs):
         dev = device or get_device()
         _, dl = K.pet_solar_table(dev, day_angle(time), lat_u, ra=False, dl=True)
-        return K.chill_daily(dev, _upload(dev, tn, D, C_), _upload(dev, tx, D, C_), dl, li, seg, sel, add_K=add_K, sub_C=sub_C,
-                             positive_only=positive_only, outputs=outputs)
+        return K.chill_daily(dev, F.rows_on_device(dev, tn, D, C_), F.rows_on_device(dev, tx, D, C_), dl, li, seg, sel,
+                             add_K=add_K, sub_C=sub_C, positive_only=positive_only, outputs=outputs)
 
     return _reduce(run, names, time, freq, indexer, cell_shape, C_, P, nsel, keep, mask_missing, device)
 
@@ -227,15 +191,15 @@ def make_hourly_temperature(tasmin, tasmax, lat, time: TimeAxis, infill_polar_da
     daily, gap-free axis, ``lat`` [degrees north] broadcasts to the cells.  Sunrise is at hour 0 of every day and sunset
     ``day_lengths`` hours later; the night runs to the next day's ``tasmin`` (the last day's to its own).  Polar days and
     nights have a NaN day length and give NaN hours; ``infill_polar_days=True`` raises :class:`NotServed`."""
-    tn, tx, cell_shape, lat_u, li = _daily_inputs(tasmin, tasmax, lat, time, infill_polar_days)
-    C_ = int(np.prod(cell_shape, dtype=np.int64))
+    tn, tx, cell_shape, C_, lat_u, li = _daily_inputs(tasmin, tasmax, lat, time, infill_polar_days)
     D = len(time)
-    dev = device or get_device()
     if C_ == 0:
-        return dev.empty((HOURS * D, 0), np.float64) if keep else np.empty((HOURS * D,) + cell_shape, np.float64)
+        return F.empty_result({"hourly": np.float64}, HOURS * D, cell_shape, keep, device)["hourly"]
+    dev = device or get_device()
     _, dl = K.pet_solar_table(dev, day_angle(time), lat_u, ra=False, dl=True)
-    out = K.chill_daily(dev, _upload(dev, tn, D, C_), _upload(dev, tx, D, C_), dl, li, [0, D], outputs=("hourly",))["hourly"]
-    return out if keep else out.get().reshape((HOURS * D,) + cell_shape)
+    out = K.chill_daily(dev, F.rows_on_device(dev, tn, D, C_), F.rows_on_device(dev, tx, D, C_), dl, li, [0, D],
+                        outputs=("hourly",))
+    return (out if keep else F.host_result(out, HOURS * D, cell_shape))["hourly"]
 
 
 def chill_portions_from_daily(tasmin, tasmax, lat, time: TimeAxis, freq: str = "YS", *, units: str = "K", device=None,
@@ -261,8 +225,7 @@ def chill_from_daily(tasmin, tasmax, lat, time: TimeAxis, positive_only: bool = 
 
 
 # ---- the adapter callee (patch.install): the reference's numpy function, time LAST ------------------------------------
-class _Forward(Exception):
-    """A form the device path does not take: the adapter hands the call to the reference's own function."""
+_Forward = F.Forward
 
 
 def chill_portion_one_season(tas_K, *, device=None):
@@ -270,14 +233,12 @@ def chill_portion_one_season(tas_K, *, device=None):
     time last, any loop shape, temperatures in K; returns ``delta`` in the input's shape and dtype (for float32 the
     float64 ``delta`` rounded once).  Raises ``_Forward`` for other dtypes, 0-d and empty arrays."""
     a = np.asarray(tas_K)
-    if a.dtype not in (np.float32, np.float64) or a.ndim < 1 or a.size == 0:
+    if a.dtype not in F.SERVED or a.ndim < 1 or a.size == 0:
         raise _Forward("dtype or shape")
-    n, loop = a.shape[-1], a.shape[:-1]
-    C_ = int(np.prod(loop, dtype=np.int64))
-    field = np.ascontiguousarray(np.moveaxis(a, -1, 0)).reshape(n, C_)
     dev = device or get_device()
-    out = K.chill_hourly(dev, dev.to_device(field), [0, n], add_K=0.0, sub_C=KELVIN_OFFSET, outputs=("delta",))["delta"]
-    return np.moveaxis(out.get().reshape((n,) + tuple(loop)), 0, -1).astype(a.dtype)
+    out = K.chill_hourly(dev, dev.to_device(F.time_first(a)), [0, a.shape[-1]], add_K=0.0, sub_C=KELVIN_OFFSET,
+                         outputs=("delta",))["delta"]
+    return F.time_last(out.get(), a.shape[:-1]).astype(a.dtype)
 
 
 def make_adapters(orig):

@@ -26,17 +26,16 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import fields as F
 from . import kernels as K
-from ._capi import DeviceArray, get_device
+from ._capi import get_device
 from .timeaxis import TimeAxis, _MLEN_NOLEAP
 
 __all__ = ["NotServed", "potential_evapotranspiration", "water_budget", "extraterrestrial_solar_radiation", "day_lengths",
            "day_angle", "METHODS"]
 
 
-class NotServed(NotImplementedError):
-    """A form the device path does not take (non-daily or gappy time axes, other calendars); the adapter forwards it."""
-
+NotServed = F.NotServed
 
 # converters.py:1999-2147: the accepted spellings of each method
 METHODS = {"baierrobertson65": "BR65", "BR65": "BR65", "hargreaves85": "HG85", "HG85": "HG85",
@@ -109,11 +108,7 @@ def _lat_table(lat, cell_shape):
     """The distinct latitudes (L) and each cell's int32 index into them (C)."""
     if lat is None:
         raise ValueError("potential evapotranspiration: lat is required")
-    try:
-        b = np.broadcast_to(np.asarray(lat, dtype=np.float64), cell_shape)
-    except ValueError:
-        raise ValueError(f"lat: shape {np.shape(lat)} does not broadcast to the cell shape {tuple(cell_shape)}") from None
-    u, inv = np.unique(b.reshape(-1), return_inverse=True)
+    u, inv = np.unique(F.per_cell(lat, cell_shape, "lat"), return_inverse=True)
     return u, inv.astype(np.int32).reshape(-1)
 
 
@@ -138,38 +133,6 @@ def day_lengths(time: TimeAxis, lat, *, time_of_day: float = 0.0, device=None) -
     """helpers.py:450-525 with method "spencer" and no infill: ``(T, L)`` float64 hours, NaN in the polar day and
     night."""
     return _solar(time, lat, "dl", time_of_day, 1361.0, device)
-
-
-def _native(fields: dict):
-    """Fields as float32 / float64 sharing one dtype (a mixed set widened to float64; device arrays must share it)."""
-    out = {}
-    for n, a in fields.items():
-        if a is None:
-            continue
-        if isinstance(a, DeviceArray):
-            if np.dtype(a.dtype) not in (np.float32, np.float64):
-                raise TypeError(f"{n}: device arrays must be float32 or float64, got {np.dtype(a.dtype).name}")
-            out[n] = a
-        else:
-            a = np.asarray(a)
-            out[n] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
-    kinds = {np.dtype(a.dtype) for a in out.values()}
-    if len(kinds) > 1:
-        if any(isinstance(a, DeviceArray) for a in out.values()):
-            raise TypeError("device fields must share one dtype")
-        out = {n: a.astype(np.float64) for n, a in out.items()}
-    return out
-
-
-def _shape(fields: dict):
-    shapes = {n: tuple(a.shape) for n, a in fields.items()}
-    first = next(iter(shapes.values()))
-    if len(first) < 1:
-        raise ValueError("fields must have a time axis (axis 0)")
-    for n, s in shapes.items():
-        if s != first:
-            raise ValueError(f"{n}: shape {s} differs from {first}")
-    return first[0], first[1:]
 
 
 def _need(m, got, water):
@@ -218,24 +181,20 @@ def _run(method, fields, time, lat, outputs, peta, petb, time_of_day, device, ke
         raise ValueError("Wind speed is required for Allen98 method.")
     _need(m, {k for k, v in fields.items() if v is not None}, "wb" in outputs)
     fields = {k: v for k, v in fields.items() if k in _reads(m, fields.get("tas") is not None, "wb" in outputs)}
-    got = _native(fields)
-    T, cell_shape = _shape(got)
+    got = F.native_set(fields)
+    T, cell_shape, C_ = F.shape_of(got)
     if len(time) != T:
         raise ValueError(f"time has {len(time)} rows, the fields {T}")
     _check_time(time)
     if m == "DA02" and "wb" in outputs:  # converters.py:2718-2730 calls PET without pr, which DA02 needs
         raise NotServed("water_budget with DA02: the reference does not hand pr to potential_evapotranspiration")
-    C_ = int(np.prod(cell_shape, dtype=np.int64))
     if C_ == 0 and m != "FAO_PM98":  # an empty grid: latitudes of no cell make no table for the kernels (FAO_PM98 has none and launches)
         months = None if m in K.PET_DAILY else _months(time)[1]
         rows = T if months is None else len(months)
-        if keep:
-            return {n: (device or get_device()).empty((rows, 0), np.float64) for n in outputs}, months
-        return {n: np.empty((rows,) + tuple(cell_shape), np.float64) for n in outputs}, months
+        return F.empty_result(dict.fromkeys(outputs, np.float64), rows, cell_shape, keep, device), months
     lat_u, li = _lat_table(lat, cell_shape) if m != "FAO_PM98" else (None, None)
     dev = device or get_device()
-    d = {n: a.reshape(T, C_) if isinstance(a, DeviceArray) else dev.to_device(np.ascontiguousarray(a).reshape(T, C_))
-         for n, a in got.items()}
+    d = {n: F.rows_on_device(dev, a, T, C_) for n, a in got.items()}
     if m in K.PET_DAILY:
         months = ra = None
         if m != "FAO_PM98":
@@ -248,9 +207,7 @@ def _run(method, fields, time, lat, outputs, peta, petb, time_of_day, device, ke
         tab = K.pet_month_table(dev, dl if m == "TW48" else ra, dseg, 0 if m == "TW48" else 1)
         outs = K.pet_monthly(dev, m, d, seg, int(months.month[0]) - 1, tab, ndays * 86400.0, li, outputs=outputs)
         rows = len(months)
-    if not keep:
-        outs = {n: v.get().reshape((rows,) + tuple(cell_shape)) for n, v in outs.items()}
-    return outs, months
+    return (outs if keep else F.host_result(outs, rows, cell_shape)), months
 
 
 _FIELD_DOC = """``tasmin`` / ``tasmax`` / ``tas`` [K], ``hurs`` [%], ``rsds`` / ``rsus`` / ``rlds`` / ``rlus`` [W m-2], ``sfcWind``
@@ -296,7 +253,7 @@ def make_adapters(env, orig_pet, orig_wb, gather_lat=None, device=None) -> dict:
     no-op for CF units); ``lat`` comes from ``gather_lat`` (the reference's ``_gather_lat``) when not passed.  Chunked
     fields, non-daily or gappy time axes (monthly inputs among them), ``evspsblpot`` and unknown methods go to the
     originals."""
-    from .xr_adapter import _cell_coords, _cell_dims, _tfirst, is_chunked, time_axis_of
+    from .xr_adapter import _cell_dims, _tfirst_fields, _wrap_cells, time_axis_of
 
     DA = env.DataArray
 
@@ -323,20 +280,12 @@ def make_adapters(env, orig_pet, orig_wb, gather_lat=None, device=None) -> dict:
             return v.reshape(shape)
         return np.asarray(lat, np.float64)
 
+    def _cf_units(k, v):
+        return v if v.attrs.get("units") == _CF_UNITS[k] else env.convert_units_to(v, _CF_UNITS[k], context="hydro")
+
     def _serve(fields, lat, pr_first):
         named = {k: v for k, v in fields.items() if v is not None}
-        if any(not isinstance(v, DA) or "time" not in v.dims or is_chunked(v) for v in named.values()):
-            raise NotServed("chunked or time-less fields")
-        ref = named["pr"] if pr_first else next(iter(named.values()))
-        a, _ = _tfirst(ref)
-        conv = {}
-        for k, v in named.items():
-            if v.attrs.get("units") != _CF_UNITS[k]:
-                v = env.convert_units_to(v, _CF_UNITS[k], context="hydro")
-            b, x = _tfirst(v)
-            if tuple(b.dims) != tuple(a.dims):
-                raise NotServed("fields on different dimensions")
-            conv[k] = x
+        a, conv = _tfirst_fields(DA, named, _cf_units)
         if lat is None:
             if gather_lat is None:
                 raise NotServed("no lat")
@@ -345,9 +294,8 @@ def make_adapters(env, orig_pet, orig_wb, gather_lat=None, device=None) -> dict:
         return a, conv, _lat_cells(lat, a), time_axis_of(a), _time_of_day(a)
 
     def _wrap(a, values, months, attrs):
-        coords = dict(_cell_coords(a))
-        coords["time"] = a["time"] if months is None else a["time"].resample(time="MS").first()["time"]
-        return DA(np.asarray(values), coords=coords, dims=("time",) + _cell_dims(a), attrs=attrs)
+        time = a["time"] if months is None else a["time"].resample(time="MS").first()["time"]
+        return _wrap_cells(DA, a, values, time, attrs)
 
     def potential_evapotranspiration(tasmin=None, tasmax=None, tas=None, lat=None, hurs=None, rsds=None, rsus=None,
                                      rlds=None, rlus=None, sfcWind=None, pr=None, method="BR65", peta=0.00516409319477,

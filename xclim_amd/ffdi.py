@@ -23,6 +23,7 @@ from collections import namedtuple
 
 import numpy as np
 
+from . import fields as F
 from . import kernels as K
 from ._capi import DeviceArray, get_device
 
@@ -32,16 +33,6 @@ __all__ = ["keetch_byram_drought_index", "griffiths_drought_factor", "mcarthur_f
 DF_WINDOW = 20  # _ffdi.py:118: the first drought factor is that of row 19
 
 McArthurIndices = namedtuple("McArthurIndices", ["KBDI", "DF", "FFDI"])
-
-
-def _native(a, name):
-    """A field as float32 / float64 (other dtypes widened to float64); device arrays must already be one of the two."""
-    if isinstance(a, DeviceArray):
-        if np.dtype(a.dtype) not in (np.float32, np.float64):
-            raise TypeError(f"{name}: device arrays must be float32 or float64, got {np.dtype(a.dtype).name}")
-        return a
-    a = np.asarray(a)
-    return a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
 
 
 def _limit(limiting_func):
@@ -57,59 +48,26 @@ def _met_dtype(tasmax, hurs, sfcWind):
     """FFDI's fields as given: all float32 or all float64 (TypeError otherwise)."""
     tasmax, hurs, sfcWind = (x if isinstance(x, DeviceArray) else np.asarray(x) for x in (tasmax, hurs, sfcWind))
     kinds = {np.dtype(x.dtype) for x in (tasmax, hurs, sfcWind)}
-    if len(kinds) != 1 or kinds.pop() not in (np.float32, np.float64):
+    if len(kinds) != 1 or kinds.pop() not in F.SERVED:
         raise TypeError("tasmax, hurs and sfcWind must be all float32 or all float64, got "
                         f"{', '.join(np.dtype(x.dtype).name for x in (tasmax, hurs, sfcWind))}")
 
 
-def _shape(fields: dict):
-    """(T, cell_shape) of the fields; every field must have it."""
-    shapes = {n: tuple(a.shape) for n, a in fields.items()}
-    first = next(iter(shapes.values()))
-    if len(first) < 1:
-        raise ValueError("fields must have a time axis (axis 0)")
-    for n, s in shapes.items():
-        if s != first:
-            raise ValueError(f"{n}: shape {s} differs from {first}")
-    return first[0], first[1:]
-
-
-def _upload(dev, a, T, C_):
-    if isinstance(a, DeviceArray):
-        return a.reshape(T, C_)
-    return dev.to_device(np.ascontiguousarray(a).reshape(T, C_))
-
-
-def _cells(a, cell_shape, name):
-    """A per-cell input broadcast to the cell shape, as a float64 (C) array (None stays None)."""
-    if a is None:
-        return None
-    try:
-        b = np.broadcast_to(np.asarray(a, dtype=np.float64), cell_shape)
-    except ValueError:
-        raise ValueError(f"{name}: shape {np.shape(a)} does not broadcast to the cell shape {tuple(cell_shape)}") from None
-    return np.ascontiguousarray(b).reshape(-1)
-
-
 def _run(fields: dict, outputs, pr_annual=None, kbdi0=None, lim=0, device=None, keep=False):
-    T, cell_shape = _shape(fields)
-    C_ = int(np.prod(cell_shape, dtype=np.int64))
+    T, cell_shape, C_ = F.shape_of(fields)
     if T == 0 or C_ == 0:
-        empty = {o: np.empty((T,) + tuple(cell_shape), np.float64) for o in outputs}
-        return empty if not keep else {o: (device or get_device()).empty((T, C_), np.float64) for o in outputs}
-    pa, k0 = _cells(pr_annual, cell_shape, "pr_annual"), _cells(kbdi0, cell_shape, "kbdi0")
+        return F.empty_result(dict.fromkeys(outputs, np.float64), T, cell_shape, keep, device)
+    pa, k0 = F.per_cell(pr_annual, cell_shape, "pr_annual"), F.per_cell(kbdi0, cell_shape, "kbdi0")
     dev = device or get_device()
-    d = {n: _upload(dev, a, T, C_) for n, a in fields.items()}
+    d = {n: F.rows_on_device(dev, a, T, C_) for n, a in fields.items()}
     outs = K.mcarthur(dev, d, dev.to_device(pa) if pa is not None else None, dev.to_device(k0) if k0 is not None else None,
                       outputs=outputs, lim=lim)
-    if keep:
-        return outs
-    return {n: v.get().reshape((T,) + tuple(cell_shape)) for n, v in outs.items()}
+    return outs if keep else F.host_result(outs, T, cell_shape)
 
 
 def keetch_byram_drought_index(pr, tasmax, pr_annual, kbdi0=None, *, device=None, keep=False):
     """_ffdi.py:188-270: KBDI [mm/day], float64 ``(T, *cells)``.  ``kbdi0`` None = 0 (:252)."""
-    fields = {"pr": _native(pr, "pr"), "tasmax": _native(tasmax, "tasmax")}
+    fields = {"pr": F.native(pr, "pr"), "tasmax": F.native(tasmax, "tasmax")}
     return _run(fields, ["KBDI"], pr_annual, kbdi0, device=device, keep=keep)["KBDI"]
 
 
@@ -117,8 +75,8 @@ def griffiths_drought_factor(pr, smd, limiting_func="xlim", *, device=None, keep
     """_ffdi.py:273-350: DF, float64 ``(T, *cells)``; rows 0..18 are NaN (the reference's ``.where``, :350).  Fewer than
     20 rows raise IndexError, as the reference's ``isel(time=19)`` does."""
     lim = _limit(limiting_func)
-    fields = {"pr": _native(pr, "pr"), "smd": _native(smd, "smd")}
-    T, _ = _shape(fields)
+    fields = {"pr": F.native(pr, "pr"), "smd": F.native(smd, "smd")}
+    T = F.shape_of(fields)[0]
     if T < DF_WINDOW:
         raise IndexError(f"index {DF_WINDOW - 1} is out of bounds for axis 0 with size {T}")
     return _run(fields, ["DF"], lim=lim, device=device, keep=keep)["DF"]
@@ -129,8 +87,8 @@ def mcarthur_forest_fire_danger_index(drought_factor, tasmax, hurs, sfcWind, *, 
     0.243147)`` with numpy's dtypes (float32 when the drought factor and the three fields are float32, float64 otherwise;
     ``keep=True`` returns the float64 device array, which holds the float32 values exactly)."""
     _met_dtype(tasmax, hurs, sfcWind)
-    met = {"tasmax": _native(tasmax, "tasmax"), "hurs": _native(hurs, "hurs"), "sfcWind": _native(sfcWind, "sfcWind")}
-    df = _native(drought_factor, "drought_factor")
+    met = {"tasmax": F.native(tasmax, "tasmax"), "hurs": F.native(hurs, "hurs"), "sfcWind": F.native(sfcWind, "sfcWind")}
+    df = F.native(drought_factor, "drought_factor")
     out = _run({"df": df, **met}, ["FFDI"], device=device, keep=keep)["FFDI"]
     if keep:
         return out
@@ -144,9 +102,9 @@ def mcarthur_indices(pr, tasmax, hurs, sfcWind, pr_annual, kbdi0=None, limiting_
     kbdi0), limiting_func), tasmax, hurs, sfcWind)`` gives, bit for bit; the three are float64."""
     lim = _limit(limiting_func)
     _met_dtype(tasmax, hurs, sfcWind)
-    fields = {"pr": _native(pr, "pr"), "tasmax": _native(tasmax, "tasmax"), "hurs": _native(hurs, "hurs"),
-              "sfcWind": _native(sfcWind, "sfcWind")}
-    T, _ = _shape(fields)
+    fields = {"pr": F.native(pr, "pr"), "tasmax": F.native(tasmax, "tasmax"), "hurs": F.native(hurs, "hurs"),
+              "sfcWind": F.native(sfcWind, "sfcWind")}
+    T = F.shape_of(fields)[0]
     if T < DF_WINDOW:
         raise IndexError(f"index {DF_WINDOW - 1} is out of bounds for axis 0 with size {T}")
     out = _run(fields, ["KBDI", "DF", "FFDI"], pr_annual, kbdi0, lim=lim, device=device, keep=keep)
@@ -154,11 +112,7 @@ def mcarthur_indices(pr, tasmax, hurs, sfcWind, pr_annual, kbdi0=None, limiting_
 
 
 # ---- the adapter callees (patch.install): the reference's gufuncs, time LAST ----------------------------------------
-class _Forward(Exception):
-    """A form the device path does not take: the adapter hands the call to the reference's own gufunc."""
-
-
-_SERVED = (np.float32, np.float64)
+_Forward = F.Forward
 
 
 def _loop_fields(named: dict, scalars: dict):
@@ -167,29 +121,19 @@ def _loop_fields(named: dict, scalars: dict):
     arrs = {k: np.asarray(v) for k, v in named.items()}
     sc = {k: np.asarray(v) for k, v in scalars.items() if v is not None}
     for k, a in list(arrs.items()) + list(sc.items()):
-        if a.dtype not in _SERVED:
+        if a.dtype not in F.SERVED:
             raise _Forward(k)
     if any(a.ndim < 1 for a in arrs.values()):
         raise _Forward("core dimension")
     n = {a.shape[-1] for a in arrs.values()}
     if len(n) != 1:
         raise _Forward("core dimension")
-    n = n.pop()
     try:
         loop = np.broadcast_shapes(*[a.shape[:-1] for a in arrs.values()], *[a.shape for a in sc.values()])
     except ValueError:
         raise _Forward("loop shape") from None
-    C_ = int(np.prod(loop, dtype=np.int64))
-    fields = {}
-    for k, a in arrs.items():
-        b = np.broadcast_to(a, loop + (n,))
-        fields[k] = np.ascontiguousarray(np.moveaxis(b, -1, 0)).reshape(n, C_)
-    cells = {k: np.ascontiguousarray(np.broadcast_to(a, loop), dtype=np.float64).reshape(-1) for k, a in sc.items()}
-    return n, loop, fields, cells
-
-
-def _time_last(out, n, loop):
-    return np.moveaxis(out.get().reshape((n,) + tuple(loop)), 0, -1)
+    fields = {k: F.time_first(a, loop) for k, a in arrs.items()}
+    return n.pop(), loop, fields, {k: F.per_cell(a, loop, k) for k, a in sc.items()}
 
 
 def kbdi_ufunc(p, t, pa, kbdi0, *, device=None):
@@ -203,7 +147,7 @@ def kbdi_ufunc(p, t, pa, kbdi0, *, device=None):
     d = {k: dev.to_device(v) for k, v in f.items()}
     outs = K.mcarthur(dev, d, dev.to_device(c["pa"]), dev.to_device(c["kbdi0"]) if "kbdi0" in c else None,
                       outputs=["KBDI"])
-    return _time_last(outs["KBDI"], n, loop)
+    return F.time_last(outs["KBDI"].get(), loop)
 
 
 def df_ufunc(p, smd, lim, *, device=None):
@@ -217,7 +161,7 @@ def df_ufunc(p, smd, lim, *, device=None):
         raise _Forward("empty")
     dev = device or get_device()
     outs = K.mcarthur(dev, {k: dev.to_device(v) for k, v in f.items()}, outputs=["DF"], lim=int(lim))
-    return _time_last(outs["DF"], n, loop)
+    return F.time_last(outs["DF"].get(), loop)
 
 
 def make_adapters(orig_kbdi, orig_df):

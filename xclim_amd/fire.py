@@ -19,6 +19,7 @@ from collections.abc import Sequence
 
 import numpy as np
 
+from . import fields as F
 from . import kernels as K
 from ._capi import DeviceArray, get_device, handle_float64
 from .calendar import _flatten
@@ -189,15 +190,11 @@ def fire_weather_ufunc(  # noqa: C901
                           want_mask=want_mask, want_winter_pr=bool(overwintering))
     if keep:
         return outs
-    res = {}
-    for name, d in outs.items():
-        a = d.get()
-        if name == "winter_pr":
-            res[name] = a.reshape(cell_shape)
-        elif name == "season_mask":
-            res[name] = a.reshape((T,) + cell_shape).astype(bool)
-        else:
-            res[name] = a.reshape((T,) + cell_shape)
+    res = F.host_result({n: d for n, d in outs.items() if n != "winter_pr"}, T, cell_shape)
+    if "season_mask" in res:
+        res["season_mask"] = res["season_mask"].astype(bool)
+    if "winter_pr" in outs:
+        res["winter_pr"] = outs["winter_pr"].get().reshape(cell_shape)
     return res
 
 
@@ -311,8 +308,7 @@ def overwintering_drought_code(last_dc, winter_pr, carry_over_fraction=default_p
 
 
 # ---- the adapter callees (patch.install): the reference's numpy iterators, time LAST ---------------------------------
-class _Forward(Exception):
-    """A form the device path does not take: the adapter hands the call to the reference's own function."""
+_Forward = F.Forward
 
 
 def _tfirst(a, shape, name):
@@ -322,7 +318,7 @@ def _tfirst(a, shape, name):
     a = np.asarray(a)
     if a.shape != shape or a.dtype != np.float32:
         raise _Forward(name)
-    return np.ascontiguousarray(np.moveaxis(a, -1, 0)).reshape(shape[-1], -1)
+    return F.time_first(a)
 
 
 def _cells_f32(a, cell_shape, name):
@@ -354,7 +350,6 @@ def fire_weather_calc(tas, pr, rh, ws, snd, mth, lat, season_mask, dc0, dmc0, ff
     if tas.ndim < 1:
         raise _Forward("tas")
     T, cell_shape = shape[-1], shape[:-1]
-    C_ = int(np.prod(cell_shape, dtype=np.int64))
     idx = [o for o in outputs if o in _ORDER]
     fields = {"tas": _tfirst(tas, shape, "tas"), "pr": _tfirst(pr, shape, "pr"), "hurs": _tfirst(rh, shape, "hurs"),
               "sfcWind": _tfirst(ws, shape, "sfcWind"),
@@ -368,7 +363,7 @@ def fire_weather_calc(tas, pr, rh, ws, snd, mth, lat, season_mask, dc0, dmc0, ff
     lat_c = None
     if lat is not None and set(idx) & {"DC", "DMC"}:
         try:
-            lat_c = np.ascontiguousarray(np.broadcast_to(np.asarray(lat, dtype=np.float64), cell_shape)).reshape(-1)
+            lat_c = F.per_cell(lat, cell_shape, "lat")
         except ValueError:
             raise _Forward("lat") from None
     starts = {"dc0": _cells_f32(dc0, cell_shape, "dc0"), "dmc0": _cells_f32(dmc0, cell_shape, "dmc0"),
@@ -380,10 +375,10 @@ def fire_weather_calc(tas, pr, rh, ws, snd, mth, lat, season_mask, dc0, dmc0, ff
         m = np.asarray(season_mask)
         if m.shape != shape:
             raise _Forward("season_mask")
-        m16 = np.moveaxis(m, -1, 0).astype(np.int16)
+        m16 = m.astype(np.int16)
         if m16.size and (m16.min() < 0 or m16.max() > 1):
             raise _Forward("season_mask values")
-        mask = m16.astype(np.uint8).reshape(T, C_)
+        mask = F.time_first(m16.astype(np.uint8))
     dev = device or get_device()
     d = {k: dev.to_device(v) for k, v in fields.items() if v is not None}
     ds = {k: (dev.to_device(v) if v is not None else None) for k, v in starts.items()}
@@ -401,11 +396,11 @@ def fire_weather_calc(tas, pr, rh, ws, snd, mth, lat, season_mask, dc0, dmc0, ff
             elif season_method == "mask":
                 res.append(season_mask)
             else:
-                res.append(np.moveaxis(outs[name].get().reshape((T,) + cell_shape).view(bool), 0, -1))
+                res.append(F.time_last(outs[name].get().view(bool), cell_shape))
         elif name == "winter_pr":
             res.append(outs[name].get().reshape(cell_shape) if name in outs else np.asarray(winter_pr).copy())
         else:
-            res.append(np.moveaxis(outs[name].get().reshape((T,) + cell_shape), 0, -1))
+            res.append(F.time_last(outs[name].get(), cell_shape))
     return res[0] if len(res) == 1 else tuple(res)
 
 
@@ -438,7 +433,7 @@ def fire_season_np(tas, snd=None, method="WF93", temp_start_thresh=12.0, temp_en
                          "snow_condition_days": int(snow_condition_days)})
     outs = K.fire_weather(dev, {k: dev.to_device(v) for k, v in fields.items()}, np.ones(T, np.int32), None, {}, [], kw,
                           season_method=method, want_mask=True)
-    return np.moveaxis(outs["season_mask"].get().reshape((T,) + shape[:-1]).view(bool), 0, -1)
+    return F.time_last(outs["season_mask"].get().view(bool), shape[:-1])
 
 
 def make_adapters(orig_calc, orig_season):

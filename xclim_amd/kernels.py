@@ -52,6 +52,39 @@ def _seg(seg_off):
     return s, len(s) - 1
 
 
+def _same_fields(who: str, fields: dict):
+    """(T, C, is_float64) of a dict of device fields: all float32 or all float64, and of one (T, C) shape."""
+    kinds = {np.dtype(v.dtype) for v in fields.values()}
+    if len(kinds) != 1 or not kinds <= {np.dtype(np.float32), np.dtype(np.float64)}:
+        raise TypeError(f"{who}: {', '.join(fields) or 'the fields'} must be all float32 or all float64")
+    shapes = {_tc(v, None) for v in fields.values()}
+    if len(shapes) != 1:
+        raise ValueError(f"{who}: every field must have the same (T, C) shape")
+    return (*shapes.pop(), int(kinds.pop() == np.float64))
+
+
+def _offsets(who: str, seg, rows: int, what: str = "period"):
+    """Host offsets as int64: 1-D, non-decreasing, within [0, rows]."""
+    s = np.ascontiguousarray(seg, dtype=np.int64)
+    if s.ndim != 1 or len(s) < 1 or s[0] < 0 or s[-1] > rows or np.any(np.diff(s) < 0):
+        raise ValueError(f"{who}: {what} offsets must be non-decreasing within [0, {rows}]")
+    return s
+
+
+def _subset(who: str, outputs, allowed):
+    """The requested outputs in the order of ``allowed``; none is a ValueError."""
+    outputs = [o for o in allowed if o in set(outputs)]
+    if not outputs:
+        raise ValueError(f"{who}: outputs must be a non-empty subset of {', '.join(allowed)}")
+    return outputs
+
+
+def _ptr(arrays: dict, name: str):
+    """The device pointer of a dict entry, NULL for a name it does not hold."""
+    a = arrays.get(name)
+    return _vp(a.ptr) if a is not None else _vp(0)
+
+
 def op_code(op: str) -> int:
     if op == "gteq":
         op = "ge"
@@ -1048,18 +1081,11 @@ def pet_solar_table(dev: Device, day_angle, lat_deg, solar_constant: float = 136
     return o_ra, o_dl
 
 
-def _pet_seg(seg, n, what):
-    s = np.ascontiguousarray(seg, dtype=np.int64)
-    if s.ndim != 1 or len(s) < 1 or s[0] < 0 or s[-1] > n or np.any(np.diff(s) < 0):
-        raise ValueError(f"{what}: month offsets must be non-decreasing within [0, {n}]")
-    return s
-
-
 def pet_month_table(dev: Device, daily: DeviceArray, seg, kind: int) -> DeviceArray:
     """xh_pet_month_table: (M, L) float64 from the (D, L) daily table; ``seg`` (M + 1) host offsets of the months' days.
     kind 0: mean of day length / 12 over the non-NaN days (TW48); 1: 0.408 x the sum of Ra in MJ (DA02)."""
     D, L = _tc(daily, np.float64)
-    s = _pet_seg(seg, D, "pet_month_table")
+    s = _offsets("pet_month_table", seg, D, "month")
     if kind not in (0, 1):
         raise ValueError(f"pet_month_table: kind must be 0 or 1, got {kind!r}")
     M = len(s) - 1
@@ -1074,14 +1100,7 @@ def _pet_fields(fields: dict, need):
     for n in need:
         if n not in got:
             raise TypeError(f"pet: {n} is needed")
-    kinds = {np.dtype(v.dtype) for v in got.values()}
-    if not got or len(kinds) != 1 or next(iter(kinds)) not in (np.float32, np.float64):
-        raise TypeError("pet: the fields must be all float32 or all float64")
-    shapes = {_tc(v, None) for v in got.values()}
-    if len(shapes) != 1:
-        raise ValueError("pet: every field must have the same (T, C) shape")
-    T, C_ = shapes.pop()
-    return got, T, C_, int(kinds.pop() == np.float64)
+    return (got, *_same_fields("pet", got))
 
 
 def _pet_lat_idx(dev, lat_idx, C_, L):
@@ -1092,9 +1111,7 @@ def _pet_lat_idx(dev, lat_idx, C_, L):
 
 
 def _pet_outs(dev, outputs, rows, C_, got):
-    outputs = [o for o in ("pet", "wb") if o in set(outputs)]
-    if not outputs:
-        raise ValueError("pet: outputs must be a non-empty subset of pet, wb")
+    outputs = _subset("pet", outputs, ("pet", "wb"))
     if "wb" in outputs and "pr" not in got:
         raise TypeError("pet: the water budget needs pr")
     return {o: dev.empty((rows, C_), np.float64) for o in outputs}
@@ -1119,10 +1136,8 @@ def pet_daily(dev: Device, method: str, fields: dict, ra: DeviceArray | None = N
         if T2 != T:
             raise ValueError(f"pet_daily: the Ra table has {T2} rows for {T} field rows")
         d_li = _pet_lat_idx(dev, lat_idx, C_, L)
-    ptr = lambda n: _vp(got[n].ptr) if n in got else _vp(0)  # noqa: E731
-    optr = lambda n: _vp(outs[n].ptr) if n in outs else _vp(0)  # noqa: E731
-    dev.call("xh_pet_daily", T, C_, C_, code, f64, *(ptr(n) for n in _PET_FIELDS), _vp(ra.ptr) if code != 3 else _vp(0), L,
-             _vp(d_li.ptr) if d_li is not None else _vp(0), float(peta), float(petb), optr("pet"), optr("wb"), C_)
+    dev.call("xh_pet_daily", T, C_, C_, code, f64, *(_ptr(got, n) for n in _PET_FIELDS), _vp(ra.ptr) if code != 3 else _vp(0), L,
+             _vp(d_li.ptr) if d_li is not None else _vp(0), float(peta), float(petb), _ptr(outs, "pet"), _ptr(outs, "wb"), C_)
     return outs
 
 
@@ -1134,7 +1149,7 @@ def pet_monthly(dev: Device, method: str, fields: dict, seg, first_month: int, m
     code = PET_MONTHLY[method]
     need = ("tasmin", "tasmax", "pr") if code == 5 else (() if fields.get("tas") is not None else ("tasmin", "tasmax"))
     got, T, C_, f64 = _pet_fields(fields, need)
-    s = _pet_seg(seg, T, "pet_monthly")
+    s = _offsets("pet_monthly", seg, T, "month")
     M = len(s) - 1
     M2, L = _tc(month_table, np.float64)
     sec = np.ascontiguousarray(month_seconds, dtype=np.float64)
@@ -1144,11 +1159,10 @@ def pet_monthly(dev: Device, method: str, fields: dict, seg, first_month: int, m
         raise ValueError(f"pet_monthly: first_month must be 0..11, got {first_month!r}")
     outs = _pet_outs(dev, outputs, M, C_, got)
     d_li = _pet_lat_idx(dev, lat_idx, C_, L)
-    ptr = lambda n: _vp(got[n].ptr) if n in got else _vp(0)  # noqa: E731
-    optr = lambda n: _vp(outs[n].ptr) if n in outs else _vp(0)  # noqa: E731
     d_s, d_sec = dev.to_device(s), dev.to_device(sec)
-    dev.call("xh_pet_monthly", T, C_, C_, code, f64, ptr("tasmin"), ptr("tasmax"), ptr("tas"), ptr("pr"), M, int(first_month),
-             _vp(d_s.ptr), _vp(month_table.ptr), _vp(d_sec.ptr), L, _vp(d_li.ptr), optr("pet"), optr("wb"), C_)
+    dev.call("xh_pet_monthly", T, C_, C_, code, f64, *(_ptr(got, n) for n in ("tasmin", "tasmax", "tas", "pr")), M,
+             int(first_month), _vp(d_s.ptr), _vp(month_table.ptr), _vp(d_sec.ptr), L, _vp(d_li.ptr), _ptr(outs, "pet"),
+             _ptr(outs, "wb"), C_)
     return outs
 
 
@@ -1162,9 +1176,7 @@ def mcarthur(dev: Device, fields: dict, pr_annual: DeviceArray | None = None, kb
     (the ones the requested ``outputs`` read; hurs and sfcWind of tasmax's dtype, smd and df of one dtype); ``pr_annual``
     and ``kbdi0`` float64 (C) (kbdi0 None = 0).  DF reads the KBDI of the same launch when both are requested (smd
     otherwise), FFDI the DF of the same launch (df otherwise).  Returns ``{name: (T, C) float64 DeviceArray}``."""
-    outputs = [o for o in ("KBDI", "DF", "FFDI") if o in set(outputs)]
-    if not outputs or len(outputs) != len(set(outputs)):
-        raise ValueError("mcarthur: outputs must be a non-empty subset of KBDI, DF, FFDI")
+    outputs = _subset("mcarthur", outputs, ("KBDI", "DF", "FFDI"))
     if lim not in (0, 1):
         raise ValueError(f"mcarthur: lim must be 0 (xlim) or 1 (discrete), got {lim!r}")
     k, d, f = "KBDI" in outputs, "DF" in outputs, "FFDI" in outputs
@@ -1173,22 +1185,13 @@ def mcarthur(dev: Device, fields: dict, pr_annual: DeviceArray | None = None, kb
         if used and fields.get(name) is None:
             raise TypeError(f"mcarthur: {name} is needed for {outputs}")
     got = {n: fields[n] for n, used in need.items() if used}
-    T, C_ = None, None
-    for n, v in got.items():
-        if np.dtype(v.dtype) not in (np.float32, np.float64):
-            raise TypeError(f"mcarthur: {n} must be float32 or float64, got {np.dtype(v.dtype).name}")
-        if (T, C_) == (None, None):
-            T, C_ = _tc(v, None)
-        elif _tc(v, None) != (T, C_):
-            raise ValueError("mcarthur: every field must have the same (T, C) shape")
-
-    def f64(*names):
-        kinds = {np.dtype(got[n].dtype) == np.float64 for n in names if n in got}
-        if len(kinds) > 1:
-            raise TypeError(f"mcarthur: {' / '.join(n for n in names if n in got)} must share one dtype")
-        return int(kinds.pop()) if kinds else 0
-
-    pr64, tas64, smd64 = f64("pr"), f64("tasmax", "hurs", "sfcWind"), f64("smd", "df")
+    # a dtype per group: pr | tasmax, hurs, sfcWind | smd, df; one shape for all
+    groups = [{n: got[n] for n in names if n in got} for names in (("pr",), ("tasmax", "hurs", "sfcWind"), ("smd", "df"))]
+    tcf = [_same_fields("mcarthur", g) if g else None for g in groups]
+    if len({g[:2] for g in tcf if g}) != 1:
+        raise ValueError("mcarthur: every field must have the same (T, C) shape")
+    T, C_ = next(g[:2] for g in tcf if g)
+    pr64, tas64, smd64 = (g[2] if g else 0 for g in tcf)
 
     def cell(a, name):
         if a is None:
@@ -1200,11 +1203,9 @@ def mcarthur(dev: Device, fields: dict, pr_annual: DeviceArray | None = None, kb
     if k and pr_annual is None:
         raise TypeError("mcarthur: KBDI needs pr_annual")
     outs = {o: dev.empty((T, C_), np.float64) for o in outputs}
-    ptr = lambda n: _vp(got[n].ptr) if n in got else _vp(0)  # noqa: E731
-    optr = lambda n: _vp(outs[n].ptr) if n in outs else _vp(0)  # noqa: E731
-    dev.call("xh_mcarthur", T, C_, C_, pr64, tas64, smd64, ptr("pr"), ptr("tasmax"), ptr("hurs"), ptr("sfcWind"), ptr("smd"),
-             ptr("df"), cell(pr_annual, "pr_annual") if k else _vp(0), cell(kbdi0, "kbdi0") if k else _vp(0), int(lim),
-             np_ptr(MCARTHUR_N13), optr("KBDI"), optr("DF"), optr("FFDI"), C_)
+    dev.call("xh_mcarthur", T, C_, C_, pr64, tas64, smd64, *(_ptr(got, n) for n in need),  # (need: in the order of the arguments)
+             cell(pr_annual, "pr_annual") if k else _vp(0), cell(kbdi0, "kbdi0") if k else _vp(0), int(lim),
+             np_ptr(MCARTHUR_N13), *(_ptr(outs, o) for o in ("KBDI", "DF", "FFDI")), C_)
     return outs
 
 
@@ -1212,12 +1213,8 @@ CHILL_OUTPUTS = ("cp", "cu", "valid")
 
 
 def _chill_common(dev, who, rows, seg, sel, outputs, allowed):
-    outputs = [o for o in allowed if o in set(outputs)]
-    if not outputs:
-        raise ValueError(f"{who}: outputs must be a non-empty subset of {', '.join(allowed)}")
-    s = np.ascontiguousarray(seg, dtype=np.int64)
-    if s.ndim != 1 or len(s) < 1 or s[0] < 0 or s[-1] > rows or np.any(np.diff(s) < 0):
-        raise ValueError(f"{who}: period offsets must be non-decreasing within [0, {rows}]")
+    outputs = _subset(who, outputs, allowed)
+    s = _offsets(who, seg, rows)
     if len(s) - 1 > 65535:
         raise ValueError(f"{who}: at most 65535 periods, got {len(s) - 1}")
     d_sel = None
@@ -1234,19 +1231,16 @@ def chill_hourly(dev: Device, tas: DeviceArray, seg, row_sel=None, *, add_K: flo
     """xh_chill_hourly.  ``tas`` (H, C) float32 or float64 DeviceArray, day-major hourly rows; ``seg`` (P + 1) host ROW
     offsets of the periods; ``row_sel`` host bool / uint8 (H) or None.  ``outputs``: a subset of cp, cu, valid ((P, C);
     float64, float64, int32) and delta ((H, C) float64).  Returns ``{name: DeviceArray}``."""
-    if np.dtype(tas.dtype) not in (np.float32, np.float64):
-        raise TypeError(f"chill_hourly: tas must be float32 or float64, got {np.dtype(tas.dtype).name}")
-    H, C_ = _tc(tas, None)
+    H, C_, f64 = _same_fields("chill_hourly", {"tas": tas})
     outputs, s, d_sel = _chill_common(dev, "chill_hourly", H, seg, row_sel, outputs, CHILL_OUTPUTS + ("delta",))
     P = len(s) - 1
     outs = {o: dev.empty((H, C_) if o == "delta" else (P, C_), np.int32 if o == "valid" else np.float64) for o in outputs}
     if "delta" in outs and (s[0] != 0 or s[-1] != H):
         raise ValueError("chill_hourly: delta needs periods that cover every row")
-    optr = lambda n: _vp(outs[n].ptr) if n in outs else _vp(0)  # noqa: E731
     d_s = dev.to_device(s)  # held until the launch is enqueued: a freed buffer goes back to the pool
-    dev.call("xh_chill_hourly", H, C_, C_, int(np.dtype(tas.dtype) == np.float64), _vp(tas.ptr), int(rows_per_day), P,
-             _vp(d_s.ptr), _vp(d_sel.ptr) if d_sel is not None else _vp(0), float(add_K), float(sub_C), int(bool(positive_only)),
-             optr("cp"), optr("cu"), optr("valid"), optr("delta"), C_)
+    dev.call("xh_chill_hourly", H, C_, C_, f64, _vp(tas.ptr), int(rows_per_day), P, _vp(d_s.ptr),
+             _vp(d_sel.ptr) if d_sel is not None else _vp(0), float(add_K), float(sub_C), int(bool(positive_only)),
+             *(_ptr(outs, o) for o in CHILL_OUTPUTS + ("delta",)), C_)
     return outs
 
 
@@ -1256,11 +1250,7 @@ def chill_daily(dev: Device, tasmin: DeviceArray, tasmax: DeviceArray, dl: Devic
     :func:`pet_solar_table` and ``lat_idx`` (C) host indices into its columns; ``seg`` (P + 1) host DAY offsets; ``day_sel``
     host bool / uint8 (D) or None.  ``outputs``: a subset of cp, cu, valid ((P, C)) and hourly ((24 D, C) float64, the
     hourly temperatures).  Returns ``{name: DeviceArray}``."""
-    if np.dtype(tasmin.dtype) not in (np.float32, np.float64) or np.dtype(tasmax.dtype) != np.dtype(tasmin.dtype):
-        raise TypeError("chill_daily: tasmin and tasmax must be both float32 or both float64")
-    D, C_ = _tc(tasmin, None)
-    if _tc(tasmax, None) != (D, C_):
-        raise ValueError("chill_daily: tasmin and tasmax must have the same (D, C) shape")
+    D, C_, f64 = _same_fields("chill_daily", {"tasmin": tasmin, "tasmax": tasmax})
     D2, L = _tc(dl, np.float64)
     if D2 != D:
         raise ValueError(f"chill_daily: the day-length table has {D2} rows for {D} days")
@@ -1270,11 +1260,10 @@ def chill_daily(dev: Device, tasmin: DeviceArray, tasmax: DeviceArray, dl: Devic
         raise ValueError("chill_daily: hourly needs periods that cover every day")
     d_li = _pet_lat_idx(dev, lat_idx, C_, L)
     outs = {o: dev.empty((24 * D, C_) if o == "hourly" else (P, C_), np.int32 if o == "valid" else np.float64) for o in outputs}
-    optr = lambda n: _vp(outs[n].ptr) if n in outs else _vp(0)  # noqa: E731
     d_s = dev.to_device(s)
-    dev.call("xh_chill_daily", D, C_, C_, int(np.dtype(tasmin.dtype) == np.float64), _vp(tasmin.ptr), _vp(tasmax.ptr),
-             _vp(dl.ptr), L, _vp(d_li.ptr), P, _vp(d_s.ptr), _vp(d_sel.ptr) if d_sel is not None else _vp(0), float(add_K),
-             float(sub_C), int(bool(positive_only)), optr("cp"), optr("cu"), optr("valid"), optr("hourly"), C_)
+    dev.call("xh_chill_daily", D, C_, C_, f64, _vp(tasmin.ptr), _vp(tasmax.ptr), _vp(dl.ptr), L, _vp(d_li.ptr), P, _vp(d_s.ptr),
+             _vp(d_sel.ptr) if d_sel is not None else _vp(0), float(add_K), float(sub_C), int(bool(positive_only)),
+             *(_ptr(outs, o) for o in CHILL_OUTPUTS + ("hourly",)), C_)
     return outs
 
 
@@ -1295,17 +1284,9 @@ def bioclim(dev: Device, fields: dict, step_off, factor, seg_rows, seg_steps, W:
     unknown = set(outputs) - set(allowed)
     if unknown:
         raise ValueError(f"bioclim: unknown outputs {sorted(unknown)}")
-    outputs = [o for o in allowed if o in set(outputs)]
+    outputs = _subset("bioclim", outputs, allowed)
     got = {n: fields[n] for n in BIOCLIM_FIELDS if fields.get(n) is not None}
-    if not got:
-        raise TypeError("bioclim: no field given")
-    kinds = {np.dtype(v.dtype) for v in got.values()}
-    if len(kinds) > 1 or not kinds <= {np.dtype(np.float32), np.dtype(np.float64)}:
-        raise TypeError("bioclim: the fields must be all float32 or all float64")
-    shapes = {_tc(v, None) for v in got.values()}
-    if len(shapes) > 1:
-        raise ValueError("bioclim: every field must have the same (T, C) shape")
-    (T, C_), = shapes
+    T, C_, f64 = _same_fields("bioclim", got)
     so = np.ascontiguousarray(step_off, dtype=np.int64)
     fa = np.ascontiguousarray(factor, dtype=np.float64)
     sr = np.ascontiguousarray(seg_rows, dtype=np.int64)
@@ -1322,8 +1303,7 @@ def bioclim(dev: Device, fields: dict, step_off, factor, seg_rows, seg_steps, W:
                 arr[k] = outs[n].ptr
         return arr
 
-    ptr = lambda n: _vp(got[n].ptr) if n in got else _vp(0)  # noqa: E731
-    dev.call("xh_bioclim", T, C_, C_, int(kinds.pop() == np.float64), ptr("tas"), ptr("tasmin"), ptr("tasmax"), ptr("pr"), S,
+    dev.call("xh_bioclim", T, C_, C_, f64, *(_ptr(got, n) for n in BIOCLIM_FIELDS), S,
              np_ptr(so), np_ptr(fa if T else np.zeros(1)), int(bool(binned)), P, np_ptr(sr), np_ptr(ss), int(W), float(kelvin_offset),
              float(cv_scale), float(thresh), table(BIOCLIM_VARS), table(BIOCLIM_WHICH), table(BIOCLIM_COUNTS), C_)
     return outs

@@ -42,16 +42,13 @@ import numpy as np
 from . import kernels as K
 from ._capi import DeviceArray, float64_native, float64_policy, get_device, handle_float64
 from .calendar import _flatten
+from .fields import NotServed
 from .timeaxis import TimeAxis
 
 __all__ = ["NotServed", "SIParams", "standardized_index_fit_params", "standardized_index", "preprocessed_time"]
 
 DIST_PARAMS = {"gamma": ("a", "loc", "scale"), "fisk": ("c", "loc", "scale")}
 _MAX_DOY = {"360_day": 360, "noleap": 365, "365_day": 365}  # every other calendar: 366
-
-
-class NotServed(NotImplementedError):
-    """A form of the standardized indices the HIP path does not compute (the adapter forwards it to the reference)."""
 
 
 class SIParams:

@@ -50,6 +50,7 @@ from . import generic as hgen
 from . import run_length as hrl
 from . import utils as hutl
 from ._capi import Float64FieldError, get_device
+from .fields import NotServed
 from .timeaxis import TimeAxis
 
 __all__ = ["Env", "DoyThreshold", "LazyCompare", "make_wrappers", "time_axis_of"]
@@ -169,6 +170,29 @@ def _cell_dims(a):
 
 def _cell_coords(a):
     return {k: v for k, v in a.coords.items() if "time" not in getattr(v, "dims", ())}
+
+
+def _tfirst_fields(DA, fields: dict, convert=None):
+    """The admission test of the multi-field adapters (converters, anuclim): every field is a DataArray with a time
+    dimension, not chunked, and on the dimensions of the first one (:class:`NotServed` otherwise).  ``convert(name, da)`` is
+    the caller's unit handling; it only sees admitted fields.  Returns the first field time first and ``{name: values}``."""
+    if any(not isinstance(v, DA) or "time" not in v.dims or is_chunked(v) for v in fields.values()):
+        raise NotServed("chunked or time-less fields")
+    a, vals = None, {}
+    for k, v in fields.items():
+        b, vals[k] = _tfirst(convert(k, v) if convert else v)
+        if a is None:
+            a = b
+        elif tuple(b.dims) != tuple(a.dims):
+            raise NotServed("fields on different dimensions")
+    return a, vals
+
+
+def _wrap_cells(DA, a, values, time_coord, attrs):
+    """``values`` (rows, *cells) as a DataArray on ``time_coord`` and the cell dimensions and coordinates of ``a``."""
+    coords = dict(_cell_coords(a))
+    coords["time"] = time_coord
+    return DA(np.asarray(values), coords=coords, dims=("time",) + _cell_dims(a), attrs=attrs)
 
 
 class _LazyBase:

@@ -20,8 +20,12 @@ launch over the whole series); "cubic" with a sub-grouping (griddata's Clough-To
 silently differ from it.  "nearest" with a month / day-of-year grouping
 follows xsdba since round 4: ``griddata(method="nearest")`` in the (hist_q, group coordinate) plane over the nodes of ALL
 groups — where the own group's nearest node is more than one unit away a node of a NEIGHBOURING group can win — and the
-own group's end factors outside its nodes (``xh_eqm_adjust_g2d``; ``grouped_nearest="group"`` restores the own-group rule of
-rounds 2-3, which "time.season" still uses).
+own group's end factors outside its nodes (``xh_plane_nearest``: one launch over the whole series;
+``grouped_nearest="group"`` restores the own-group rule of rounds 2-3, which "time.season" still uses).
+
+The host plumbing exists once ("sdba host plumbing"): :class:`_GroupMajor` (the group-major layout of the rows),
+:func:`_group` (the one view cut out of a table), :func:`_result`, :func:`_grouper`, :func:`_train_front` / :func:`_train_groups` and
+``_adjust_front``.
 
 :class:`QuantileDeltaMapping` (``group="time"`` or a sub-grouping: the ranks are then taken inside each group's own steps):
 trained like EQM; ``adjust`` looks the factor up at the QUANTILE of every sim value within the sim series itself
@@ -91,6 +95,24 @@ class Grouper:
         C_ = int(np.prod(cells)) if cells else 1
         return x.reshape(x.shape[0] * R, C_), R, cells   # (a view that keeps its parent alive: the caller drops `x`)
 
+    def _ring(self, time):
+        """``(tb, rows_at)`` when the samples of consecutive day-of-year groups form a ring — a window, and every year holds every
+        day (noleap, 360_day ...) — else None.  ``tb``: the (years, doys) table of time steps; ``rows_at(d, off)``: the rows
+        ``tb[:, d] + off`` of every year, -1 beyond the series."""
+        if not (self.prop == "dayofyear" and self.window > 1):
+            return None
+        tb = np.asarray(time.doy_table()[0], dtype=np.int64)      # (years, doys) -> time index
+        if not (tb.shape[1] == len(self.labels(time)) and tb.shape[1] > 1 and tb.min() >= 0
+                and bool((tb[:, 1:] == tb[:, :-1] + 1).all())):
+            return None
+        T = len(time)
+
+        def rows_at(d, off):
+            r = tb[:, d] + off
+            return np.where((r < 0) | (r >= T), -1, r)
+
+        return tb, rows_at
+
     def group_samples(self, dev, fields, time, R: int = 1):
         """For every group (in label order) the training sample of each field of ``fields`` ((T * R, C) device matrices) as a
         (rows, C) device matrix: the gathered rows of :meth:`sample_rows`.  The matrices of one group are only valid until the
@@ -100,23 +122,15 @@ class Grouper:
         day d + 1 is the sample of day d with ONE row per year replaced (the order of a sample's rows does not matter), so
         the matrix is kept as a ring — ``window`` slots per year — and 1 / window of it is gathered per group (30 years,
         window 31: 930 rows -> 30)."""
-        rows_of = self.sample_rows(time)
-        ring = False
-        if self.prop == "dayofyear" and self.window > 1 and R == 1 and len(rows_of) > 1:
-            tb = np.asarray(time.doy_table()[0], dtype=np.int64)      # (years, doys) -> time index
-            ring = tb.shape[1] == len(rows_of) and tb.min() >= 0 and bool((tb[:, 1:] == tb[:, :-1] + 1).all())
-        if not ring:
-            for g, rows in enumerate(rows_of):
+        ring = self._ring(time) if R == 1 else None
+        if ring is None:
+            for g, rows in enumerate(self.sample_rows(time)):
                 rows = self.pooled_rows(rows, R)
                 yield g, [K.select_rows(dev, f, rows) for f in fields]
             return
-        T, W, half, ny = len(time), self.window, self.window // 2, tb.shape[0]
+        tb, rows_at = ring
+        W, half, ny = self.window, self.window // 2, tb.shape[0]
         bufs = [dev.empty((ny * W, f.shape[1]), np.float32) for f in fields]
-
-        def rows_at(d, off):  # the rows tb[:, d] + off of every year, -1 beyond the series
-            r = tb[:, d] + off
-            return np.where((r < 0) | (r >= T), -1, r)
-
         first = np.full(ny * W, -1, dtype=np.int64)
         for off in range(-half, half + 1):
             first[np.arange(ny) * W + (off % W)] = rows_at(0, off)       # slot of day d + off: (d + off) mod W, d = 0
@@ -133,18 +147,11 @@ class Grouper:
         """The sliding form of the day-of-year samples (see :meth:`group_samples`): ``(rows0, enter, leave)`` — the time steps of
         group 0's sample (years x window, -1 beyond the series) and, per step from group d to d + 1, the steps that enter and
         leave (one per year) — or None when the grouping is not a ring (no window, another property, calendar gaps)."""
-        if not (self.prop == "dayofyear" and self.window > 1):
+        ring = self._ring(time)
+        if ring is None:
             return None
-        tb = np.asarray(time.doy_table()[0], dtype=np.int64)      # (years, doys) -> time index
-        if not (tb.shape[1] == len(self.sample_rows(time)) and tb.shape[1] > 1 and tb.min() >= 0
-                and bool((tb[:, 1:] == tb[:, :-1] + 1).all())):
-            return None
-        T, half = len(time), self.window // 2
-
-        def rows_at(d, off):
-            r = tb[:, d] + off
-            return np.where((r < 0) | (r >= T), -1, r)
-
+        tb, rows_at = ring
+        half = self.window // 2
         rows0 = np.concatenate([rows_at(0, off) for off in range(-half, half + 1)])
         enter = np.stack([rows_at(d, half) for d in range(1, tb.shape[1])])
         leave = np.stack([rows_at(d - 1, -half) for d in range(1, tb.shape[1])])
@@ -239,13 +246,8 @@ class Grouper:
         shape of the one-launch training kernels (xh_eqm_train_groups)."""
         if self.prop == "group" or self.window != 1:
             return None
-        gi = self.index(time)
-        G = len(self.labels(time))
-        counts = np.bincount(gi[gi >= 0], minlength=G)
-        if counts.max(initial=0) > most:
-            return None
-        order = np.argsort(gi, kind="stable")
-        return order[gi[order] >= 0].astype(np.int64), np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+        lay = _GroupMajor(self.index(time), len(self.labels(time)))
+        return None if lay.counts.max(initial=0) > most else (lay.perm.astype(np.int64), lay.offs)
 
     def sample_rows(self, time) -> list:
         """For every group the rows of its training sample: the centred window around each of its time steps, -1 (NaN)
@@ -288,6 +290,59 @@ def _check_group_interp(group: "Grouper", interp: str, who: str, labels=None, ex
             "griddata's NaN outside the convex hull of all nodes)")
 
 
+class _GroupMajor:
+    """The group-major layout of T rows with group index ``gi`` (every entry in 0 .. G - 1: callers refuse or never produce a
+    -1): ``perm`` lists the rows group after group (in time order inside a group: a stable sort), ``counts`` / ``offs``
+    (G + 1) say where each group lies in it.  Iterating yields ``(g, off, n)`` for the non-empty groups; the rows
+    [off, off + n) of a group-major (T, C) matrix are ``_group(x, off, n)``."""
+
+    def __init__(self, gi, G: int):
+        self.perm = np.argsort(gi, kind="stable")
+        self.counts = np.bincount(gi, minlength=G)
+        self.offs = np.concatenate([[0], np.cumsum(self.counts)]).astype(np.int64)
+
+    def __iter__(self):
+        return ((g, int(self.offs[g]), int(n)) for g, n in enumerate(self.counts) if n)
+
+    def rows(self, off: int, n: int) -> np.ndarray:
+        """The time steps of the block [off, off + n)."""
+        return self.perm[off:off + n]
+
+    def gather(self, dev, x: DeviceArray) -> DeviceArray:
+        """A (T, C) field in time order -> group-major."""
+        return K.select_rows(dev, x, self.perm)
+
+    def scatter(self, dev, x: DeviceArray) -> DeviceArray:
+        """A group-major (T, C) result -> time order (a gather by the inverse permutation)."""
+        inv = np.empty(len(self.perm), dtype=np.int64)
+        inv[self.perm] = np.arange(len(self.perm))
+        return K.select_rows(dev, x, inv)
+
+
+def _group(tab: DeviceArray, g: int, n: int | None = None) -> DeviceArray:
+    """Group ``g`` of a (G, ..., C) device table as a (..., C) view — with ``n`` the groups g .. g + n - 1 as (n, ..., C), which
+    for a (T, C) matrix are its rows [g, g + n).  The one place where a view is cut out of a buffer by pointer arithmetic; it keeps its buffer alive."""
+    step = int(np.prod(tab.shape[1:], dtype=np.int64)) * tab.dtype.itemsize
+    view = tab.dev.wrap(tab.ptr + g * step, tab.shape[1:] if n is None else (n,) + tab.shape[1:], tab.dtype)
+    view._owner = tab
+    return view
+
+
+def _result(scen: DeviceArray, keep: bool, shape, sync: bool = False):
+    """What a public call returns: the device array (``keep``) or its host copy in the caller's shape.  ``sync``: wait for
+    the device first (every sub-grouping path does; ``group="time"`` is one launch and the download orders itself)."""
+    if sync:
+        scen.dev.sync()
+    return scen if keep else scen.get().reshape(shape)
+
+
+def _tile_members(dev, tab: DeviceArray, E: int) -> DeviceArray:
+    """(..., C) -> (..., E * C): row i of the (rows, C) view repeated E times IS row i of (rows, E * C)."""
+    lead, C_ = int(np.prod(tab.shape[:-1])), tab.shape[-1]
+    out = K.select_rows(dev, tab.reshape(lead, C_), np.repeat(np.arange(lead), E))
+    return out.reshape(*(tuple(tab.shape[:-1]) + (E * C_,)))
+
+
 def equally_spaced_nodes(n: int, eps=None) -> np.ndarray:
     """xsdba.utils.equally_spaced_nodes: n nodes q_i = (i + 1/2) / n; with ``eps`` the end points eps and 1 - eps are
     added (n + 2 nodes), so that the adjustment factors are also defined near the ends of the distribution."""
@@ -305,7 +360,36 @@ def quantile(da, q, dim="time", *, device=None, keep=False):
     dev = device or get_device()
     x, cell_shape = _flatten(da, dev)
     out = K.quantile_series(dev, x, np.asarray(q, dtype=np.float64))
-    return out if keep else out.get().reshape((out.shape[0],) + tuple(cell_shape))
+    return _result(out, keep, (out.shape[0],) + tuple(cell_shape))
+
+
+def _grouper(group, window) -> Grouper:
+    return group if isinstance(group, Grouper) else Grouper(group, 1 if window is None else window)
+
+
+def _train_front(grp, ref, hist, kind, nquantiles, time, device, adapt_freq_thresh=None, adapt_freq_seed=0):
+    """What ``train`` does before any arithmetic: the kind, both fields flattened to (T, cells) and compared, the quantile
+    nodes, the members of ``grp.add_dims`` pooled with the time steps (rows t * R + r of a (T * R, C) view), and — for a
+    sub-grouping — the ``time`` axis.  ``adapt_freq_thresh``: hist goes through :func:`adapt_freq` against ref first.
+    Returns ``(dev, ref, hist, cell shape, R, nodes)``."""
+    if kind not in (ADDITIVE, MULTIPLICATIVE):
+        raise ValueError(f"kind must be '+' or '*', got {kind!r}")
+    dev = device or get_device()
+    r, cell_shape = _flatten(ref, dev)
+    h, cell_shape_h = _flatten(hist, dev)
+    if tuple(cell_shape) != tuple(cell_shape_h) or r.shape != h.shape:
+        raise ValueError("ref and hist must have the same shape")  # _check_matching_time_sizes analogue
+    if adapt_freq_thresh is not None:
+        if grp.add_dims:
+            raise NotImplementedError("adapt_freq_thresh with Grouper(add_dims=...) is not built")
+        h, _, _ = adapt_freq(r, h, adapt_freq_thresh, group=grp, time=time, seed=adapt_freq_seed, device=dev, keep=True)
+    q = equally_spaced_nodes(nquantiles) if np.isscalar(nquantiles) else np.asarray(nquantiles, dtype=np.float64)
+    T = r.shape[0]
+    r, R, cells = grp.pool(dev, r, cell_shape)
+    h, _, _ = grp.pool(dev, h, cell_shape_h)
+    if grp.prop != "group" and (time is None or len(time) != T):
+        raise ValueError(f"group={grp.name!r} needs time=TimeAxis of the training series")
+    return dev, r, h, cells, R, q
 
 
 def adapt_freq(ref, sim, thresh: float, *, group="time", window: int | None = None, time=None, seed: int = 0, device=None,
@@ -325,7 +409,7 @@ def adapt_freq(ref, sim, thresh: float, *, group="time", window: int | None = No
     generator (not reproducible across runs); here a counter-based uniform keyed by ``(seed, time step, cell)`` —
     ``xh_adapt_freq``, restated in oracle/sdba.py.  ``ref`` and ``sim`` need the same number of time steps only with a
     sub-grouping (one ``time`` axis for both).  Parity unpinned (xsdba is not in the reference tree)."""
-    grp = group if isinstance(group, Grouper) else Grouper(group, 1 if window is None else window)
+    grp = _grouper(group, window)
     if grp.add_dims:
         raise NotImplementedError("adapt_freq with Grouper(add_dims=...) is not built")
     dev = device or get_device()
@@ -333,7 +417,7 @@ def adapt_freq(ref, sim, thresh: float, *, group="time", window: int | None = No
     s_, cell_shape_s = _flatten(sim, dev)
     if tuple(cell_shape) != tuple(cell_shape_s):
         raise ValueError("ref and sim must have the same grid")
-    C_ = s_.shape[1]
+    T, C_ = s_.shape
     thresh = float(thresh)
 
     def one_group(ref_sample, sim_sample, sim_main, tindex, out):
@@ -355,35 +439,92 @@ def adapt_freq(ref, sim, thresh: float, *, group="time", window: int | None = No
     if grp.prop == "group":
         out = dev.empty(tuple(s_.shape), np.float32)
         pth, dp0 = one_group(r, s_, s_, None, out)
-        res = out if keep else out.get().reshape((s_.shape[0],) + tuple(cell_shape))
-        return res, pth.reshape(cell_shape), dp0.reshape(cell_shape)
-    if time is None or len(time) != s_.shape[0] or r.shape[0] != s_.shape[0]:
+        return _result(out, keep, (T,) + tuple(cell_shape)), pth.reshape(cell_shape), dp0.reshape(cell_shape)
+    if time is None or len(time) != T or r.shape[0] != T:
         raise ValueError(f"group={grp.name!r} needs time=TimeAxis common to ref and sim")
-    gi = grp.index(time)
-    labels = grp.labels(time)
-    T = s_.shape[0]
     # group-major blocks (every group's own steps contiguous), one gather back at the end — like the grouped adjust
-    perm = np.argsort(gi, kind="stable")
-    counts = np.bincount(gi, minlength=len(labels))
-    s_perm = K.select_rows(dev, s_, perm)
+    G = len(grp.labels(time))
+    lay = _GroupMajor(grp.index(time), G)
+    s_perm = lay.gather(dev, s_)
     ad_perm = dev.empty((T, C_), np.float32)
-    pths, dp0s, off = [], [], 0
-    for g, rows in enumerate(grp.sample_rows(time)):
-        n = int(counts[g])
-        main = perm[off:off + n]
-        sim_main = dev.wrap(s_perm.ptr + off * C_ * 4, (n, C_), np.float32)
-        blk = dev.wrap(ad_perm.ptr + off * C_ * 4, (n, C_), np.float32)
-        pth, dp0 = one_group(K.select_rows(dev, r, rows), K.select_rows(dev, s_, rows), sim_main, main, blk)
+    rows_of = grp.sample_rows(time)
+    pths, dp0s = [], []
+    for g, off, n in lay:
+        pth, dp0 = one_group(K.select_rows(dev, r, rows_of[g]), K.select_rows(dev, s_, rows_of[g]), _group(s_perm, off, n),
+                             lay.rows(off, n), _group(ad_perm, off, n))
         pths.append(pth)
         dp0s.append(dp0)
-        off += n
-    inv = np.empty(T, dtype=np.int64)
-    inv[perm] = np.arange(T)
-    out = K.select_rows(dev, ad_perm, inv)
-    dev.sync()
-    res = out if keep else out.get().reshape((T,) + tuple(cell_shape))
-    G = len(labels)
+    res = _result(lay.scatter(dev, ad_perm), keep, (T,) + tuple(cell_shape), sync=True)
     return res, np.stack(pths).reshape((G,) + tuple(cell_shape)), np.stack(dp0s).reshape((G,) + tuple(cell_shape))
+
+
+def _dqm_train_sample(dev, rg, hg, q, kind, out=None):
+    """dqm_train on one sample: ``(af, hist_q, scaling)`` — the tables of the series normalised by their means, and
+    scaling = get_correction(mu_hist, mu_ref): a (C,) HOST table — O(C) arithmetic on the two mean vectors."""
+    inv = "-" if kind == ADDITIVE else "/"
+    mu_r, _ = K.poly_trend(dev, rg, 0)
+    mu_h, _ = K.poly_trend(dev, hg, 0)
+    af, hq = K.eqm_train(dev, K.trend_apply(dev, rg, mu_r, None, inv), K.trend_apply(dev, hg, mu_h, None, inv), q, kind, out=out)
+    mr, mh = mu_r.get(), mu_h.get()
+    with np.errstate(all="ignore"):
+        return af, hq, (mr - mh if kind == ADDITIVE else mr / mh)
+
+
+def _train_groups(dev, grp, time, r, h, q, kind, R: int = 1, normalised: bool = False):
+    """The training of a sub-grouping: ``(af, hist_q, scaling)`` as (G, nq, C) float32 / (G, C) float64 device tables.
+    ``normalised`` (dqm_train): every sample is normalised by its own mean first and ``scaling`` is returned (else None).
+    Three routes, all bit-identical to the last one: all (small) groups in one launch, a sorted window that slides from one
+    day of the year to the next, the gathered sample of every group.  None for a normalised training WITHOUT a window whose
+    groups are too large for the one launch: the caller has a cheaper route than the gathered samples for it."""
+    small = grp.small_groups(time) if R == 1 else None
+    if small is not None:
+        # no window, small groups (365 days of the year x one row per year): all groups in ONE launch per field, keys in
+        # registers (xh_eqm_train_groups, round 6: 121 -> ~10 ms for 30 years x 1440 x 90; xh_dqm_train_groups: 470 -> ~10 ms)
+        res = K.eqm_train_groups(dev, r, h, small[0], small[1], q, kind, normalised=normalised)
+        if res is not None:
+            dev.sync()
+            return res[0], res[1], (res[2] if normalised else None)
+    if normalised and grp.window == 1:
+        return None
+    G, nq, C_ = len(grp.labels(time)), len(q), r.shape[1]
+    af = dev.empty((G, nq, C_), np.float32)
+    hq = dev.empty((G, nq, C_), np.float32)
+
+    def sample(g, rg, hg):  # the tables of group g from its gathered sample; normalised: its scaling row (host)
+        out = (_group(af, g), _group(hq, g))
+        if normalised:
+            return _dqm_train_sample(dev, rg, hg, q, kind, out)[2]
+        K.eqm_train(dev, rg, hg, q, kind, out=out)
+
+    stretches, rest, rows_of = grp.sliding_stretches(time) if R == 1 else ([], None, None)
+    if stretches:
+        # day-of-year groups with a window: every cell keeps its window sorted from one day to the next (xh_eqm_train_window,
+        # round 6: 508 -> ~60 ms for 30 years x 1440 x 90).  Normalised, the sorted window also carries the mean of every
+        # group's sample and normalises the samples it picks (xh_dqm_train_window: 3 970 -> ~190 ms; per group otherwise: a
+        # gather, two means, two normalisations, two selections and a host round trip of the means)
+        scal_d, muh = (dev.empty((G, C_), np.float64), dev.empty((G, C_), np.float64)) if normalised else (None, None)
+        done = True
+        for g0, rows0, en, lv in stretches:
+            n = en.shape[0] + 1
+            out = (_group(af, g0, n), _group(hq, g0, n)) + ((_group(scal_d, g0, n), _group(muh, g0, n)) if normalised else ())
+            if K.eqm_train_window(dev, r, h, rows0, en, lv, q, kind, normalised=normalised, out=out) is None:
+                done = False   # (not the kernel's shape after all: everything through the per-group path below)
+                break
+        if done:
+            for g in rest:     # the groups no stretch covers (day 366 of a standard calendar): from their gathered sample
+                sg = sample(g, K.select_rows(dev, r, rows_of[g]), K.select_rows(dev, h, rows_of[g]))
+                if normalised:
+                    row = dev.to_device(np.ascontiguousarray(sg), dtype=np.float64)
+                    dev.copy_d2d(_group(scal_d, g).ptr, row.ptr, C_ * 8)
+            dev.sync()
+            return af, hq, scal_d
+    scal = np.empty((G, C_), np.float64) if normalised else None
+    for g, (rg, hg) in grp.group_samples(dev, (r, h), time, R):
+        sg = sample(g, rg, hg)
+        if normalised:
+            scal[g] = sg
+    dev.sync()
+    return af, hq, (dev.to_device(scal, dtype=np.float64) if normalised else None)
 
 
 class EmpiricalQuantileMapping:
@@ -400,29 +541,58 @@ class EmpiricalQuantileMapping:
         self.adj_params = {"group": self.group.name if self.group.window == 1 else repr(self.group), "kind": kind,
                            "nquantiles": len(self.quantiles)}
 
-    def _for_members(self, sim):
-        """A ``sim`` with extra axes right behind time — the members that ``Grouper(add_dims=...)`` pooled in training, or any
-        other axis the factors do not have (xsdba: the factors broadcast against it in ``interp_on_quantiles``): the model
-        whose tables are repeated for every member, so that the (time, members x cells) matrix goes through the same
-        kernels.  None when sim has the trained shape."""
+    def _member_axes(self, sim):
+        """The extra axes of a ``sim`` right behind time — the members that ``Grouper(add_dims=...)`` pooled in training, or any
+        other axis the factors do not have (xsdba: the factors broadcast against it in ``interp_on_quantiles``).  None when
+        sim has the trained shape (or one that fits in no way: the grid check refuses it)."""
         shp = tuple(sim.shape[1:])
         n = len(self.cell_shape)
         if shp == self.cell_shape or len(shp) <= n or (n and shp[len(shp) - n:] != self.cell_shape):
             return None
-        extra = shp[:len(shp) - n]
-        E = int(np.prod(extra))
+        return shp[:len(shp) - n]
+
+    def _member_model(self, extra):
+        """The model whose tables are repeated for every member, so that the (time, members x cells) matrix goes through the
+        same kernels."""
         cache = self.__dict__.setdefault("_member_models", {})
         if extra not in cache:
-            dev = self._dev
-
-            def tile(tab):  # (..., C) -> (..., E * C): row i of the (rows, C) view repeated E times IS row i of (rows, E * C)
-                lead, C_ = int(np.prod(tab.shape[:-1])), tab.shape[-1]
-                out = K.select_rows(dev, tab.reshape(lead, C_), np.repeat(np.arange(lead), E))
-                return out.reshape(*(tuple(tab.shape[:-1]) + (E * C_,)))
-
-            cache[extra] = type(self)(dev, tile(self._af), tile(self._hist_q), self.quantiles, self.kind, extra + self.cell_shape,
-                                      self.group, None if self.group.prop == "group" else self.group_labels)
+            E = int(np.prod(extra))
+            cache[extra] = type(self)(self._dev, _tile_members(self._dev, self._af, E), _tile_members(self._dev, self._hist_q, E),
+                                      self.quantiles, self.kind, extra + self.cell_shape, self.group,
+                                      None if self.group.prop == "group" else self.group_labels)
         return cache[extra]
+
+    def _adjust_front(self, sim, interp, extrapolation, time, *, grouped_nearest="griddata", detrend=1, dqm_order=False,
+                      untrained="sim holds time steps whose group was not trained (e.g. day 366 with a 365-day training set)"):
+        """What every ``adjust`` checks before it launches anything.  Returns ``(extra, s, gi)``: the member axes of a sim that
+        has some (then s and gi are None: the caller maps the members), else the flattened sim and — for a sub-grouping — the
+        group index of every time step, all of them trained.  ``dqm_order``: DetrendedQuantileMapping looks at the (quantile,
+        group) interpolation only after the grid, and maps members itself only for ``group="time"``."""
+        who = f"{type(self).__name__}.adjust"
+        if interp not in ("nearest", "linear", "cubic"):
+            raise ValueError(f"interp={interp!r} not in ('nearest', 'linear', 'cubic')")
+        if grouped_nearest not in ("griddata", "group"):
+            raise ValueError("grouped_nearest must be 'griddata' or 'group'")
+        if detrend not in (0, 1):
+            raise NotImplementedError(f"{who}: detrend must be 0 or 1 (polynomial degree)")
+        if not dqm_order:
+            _check_group_interp(self.group, interp, who, self.group_labels, extrapolation)
+        extra = self._member_axes(sim)
+        if extra is not None and (self.group.prop == "group" or not dqm_order):
+            return extra, None, None
+        s, cell_shape = _flatten(sim, self._dev)
+        if tuple(cell_shape) != self.cell_shape:
+            raise ValueError("sim does not match the trained grid")
+        if self.group.prop == "group":
+            return None, s, None
+        if dqm_order:
+            _check_group_interp(self.group, interp, who, self.group_labels, extrapolation)
+        if time is None or len(time) != s.shape[0]:
+            raise ValueError(f"group={self.group.name!r} needs time=TimeAxis of sim")
+        gi = self.group.index(time, self.group_labels)
+        if (gi < 0).any():
+            raise ValueError(untrained)
+        return None, s, gi
 
     @classmethod
     def train(cls, ref, hist, *, nquantiles=20, kind: str = ADDITIVE, group="time", window: int | None = None, time=None,
@@ -431,65 +601,13 @@ class EmpiricalQuantileMapping:
         common ``time`` axis (TimeAxis) of ref and hist.  ``adapt_freq_thresh`` (in the units of the data): hist goes
         through :func:`adapt_freq` against ref (same grouping) before the quantiles are taken — xsdba's
         ``EmpiricalQuantileMapping.train(adapt_freq_thresh=...)`` (``_adjustment.eqm_train`` -> ``_adapt_freq_hist``)."""
-        grp = group if isinstance(group, Grouper) else Grouper(group, 1 if window is None else window)
-        if kind not in (ADDITIVE, MULTIPLICATIVE):
-            raise ValueError(f"kind must be '+' or '*', got {kind!r}")
-        dev = device or get_device()
-        r, cell_shape = _flatten(ref, dev)
-        h, cell_shape_h = _flatten(hist, dev)
-        if tuple(cell_shape) != tuple(cell_shape_h) or r.shape != h.shape:
-            raise ValueError("ref and hist must have the same shape")  # _check_matching_time_sizes analogue
-        if adapt_freq_thresh is not None:
-            if grp.add_dims:
-                raise NotImplementedError("adapt_freq_thresh with Grouper(add_dims=...) is not built")
-            h, _, _ = adapt_freq(r, h, adapt_freq_thresh, group=grp, time=time, seed=adapt_freq_seed, device=dev, keep=True)
-        q = equally_spaced_nodes(nquantiles) if np.isscalar(nquantiles) else np.asarray(nquantiles, dtype=np.float64)
-        T = r.shape[0]
-        # Grouper(add_dims=...): the members' samples are pooled with the time steps (rows t * R + r of a (T * R, C) view)
-        r, R, cell_shape = grp.pool(dev, r, cell_shape)
-        h, _, _ = grp.pool(dev, h, cell_shape_h)
+        grp = _grouper(group, window)
+        dev, r, h, cell_shape, R, q = _train_front(grp, ref, hist, kind, nquantiles, time, device, adapt_freq_thresh, adapt_freq_seed)
         if grp.prop == "group":
             af, hq = K.eqm_train(dev, r, h, q, kind)
             return cls(dev, af, hq, q, kind, cell_shape, grp)
-        if time is None or len(time) != T:
-            raise ValueError(f"group={grp.name!r} needs time=TimeAxis of the training series")
-        labels = grp.labels(time)
-        G, C_ = len(labels), r.shape[1]
-        af = dev.empty((G, len(q), C_), np.float32)
-        hq = dev.empty((G, len(q), C_), np.float32)
-        plane = len(q) * C_ * 4
-        # day-of-year groups with a window on gap-free years: every cell keeps its window sorted from one day to the next
-        # (xh_eqm_train_window, round 6: 508 -> ~60 ms for 30 years x 1440 x 90) — bit-identical to the per-group selection below
-        small = grp.small_groups(time) if R == 1 else None
-        if small is not None:
-            # no window, small groups (365 days of the year x one row per year): all groups in ONE launch per field, keys in
-            # registers (xh_eqm_train_groups, round 6: 121 -> ~10 ms for 30 years x 1440 x 90) — bit-identical to the loop below
-            res = K.eqm_train_groups(dev, r, h, small[0], small[1], q, kind)
-            if res is not None:
-                dev.sync()
-                return cls(dev, res[0], res[1], q, kind, cell_shape, grp, labels)
-        stretches, rest, rows_of = grp.sliding_stretches(time) if R == 1 else ([], None, None)
-        if stretches:
-            def slab(a, g0, n):
-                return dev.wrap(a.ptr + g0 * plane, (n, len(q), C_), np.float32)
-
-            done = True
-            for g0, rows0, en, lv in stretches:
-                n = en.shape[0] + 1
-                if K.eqm_train_window(dev, r, h, rows0, en, lv, q, kind, out=(slab(af, g0, n), slab(hq, g0, n))) is None:
-                    done = False   # (not the kernel's shape after all: everything through the per-group path below)
-                    break
-            if done:
-                for g in rest:     # the groups no stretch covers (day 366 of a standard calendar): selected from their gathered sample
-                    K.eqm_train(dev, K.select_rows(dev, r, rows_of[g]), K.select_rows(dev, h, rows_of[g]), q, kind,
-                                out=(slab(af, g, 1).reshape(len(q), C_), slab(hq, g, 1).reshape(len(q), C_)))
-                dev.sync()
-                return cls(dev, af, hq, q, kind, cell_shape, grp, labels)
-        for g, (rg, hg) in grp.group_samples(dev, (r, h), time, R):
-            out_g = tuple(dev.wrap(a.ptr + g * plane, (len(q), C_), np.float32) for a in (af, hq))
-            K.eqm_train(dev, rg, hg, q, kind, out=out_g)
-        dev.sync()
-        return cls(dev, af, hq, q, kind, cell_shape, grp, labels)
+        af, hq, _ = _train_groups(dev, grp, time, r, h, q, kind, R)
+        return cls(dev, af, hq, q, kind, cell_shape, grp, grp.labels(time))
 
     def adjust(self, sim, *, interp: str = "nearest", extrapolation: str = "constant", time=None, keep=False,
                grouped_nearest: str = "griddata"):
@@ -502,64 +620,31 @@ class EmpiricalQuantileMapping:
 
         ``interp="linear"`` with a month / day-of-year grouping is xsdba's interpolation over the (quantile, group) plane
         (``xh_plane_linear``; :func:`_check_group_interp`): months at their fractional coordinate, days of year on their row."""
-        if interp not in ("nearest", "linear", "cubic"):
-            raise ValueError(f"interp={interp!r} not in ('nearest', 'linear', 'cubic')")
-        if grouped_nearest not in ("griddata", "group"):
-            raise ValueError("grouped_nearest must be 'griddata' or 'group'")
-        _check_group_interp(self.group, interp, "EmpiricalQuantileMapping.adjust", self.group_labels, extrapolation)
-        members = self._for_members(sim)
-        if members is not None:
-            return members.adjust(sim, interp=interp, extrapolation=extrapolation, time=time, keep=keep, grouped_nearest=grouped_nearest)
-        s, cell_shape = _flatten(sim, self._dev)
-        if tuple(cell_shape) != self.cell_shape:
-            raise ValueError("sim does not match the trained grid")
-        dev = self._dev
-        if self.group.prop == "group":
-            scen = K.eqm_adjust(dev, s, self._af, self._hist_q, self.kind, interp, extrapolation)
-            return scen if keep else scen.get().reshape((s.shape[0],) + self.cell_shape)
-        if time is None or len(time) != s.shape[0]:
-            raise ValueError(f"group={self.group.name!r} needs time=TimeAxis of sim")
-        gi = self.group.index(time, self.group_labels)
-        if (gi < 0).any():
-            raise ValueError("sim holds time steps whose group was not trained (e.g. day 366 with a 365-day training set)")
+        extra, s, gi = self._adjust_front(sim, interp, extrapolation, time, grouped_nearest=grouped_nearest)
+        if extra is not None:
+            return self._member_model(extra).adjust(sim, interp=interp, extrapolation=extrapolation, time=time, keep=keep,
+                                                    grouped_nearest=grouped_nearest)
+        dev, shape = self._dev, (s.shape[0],) + self.cell_shape
+        if gi is None:
+            return _result(K.eqm_adjust(dev, s, self._af, self._hist_q, self.kind, interp, extrapolation), keep, shape)
         if interp == "linear":
             # xsdba's 2-D branch: ONE launch over the whole series, every step at its (fractional) group coordinate
             scen = K.plane_linear(dev, s, self.group.coordinate(time, interp=True), self._af, xq_all=self._hist_q, kind=self.kind)
-            dev.sync()
-            return scen if keep else scen.get().reshape((s.shape[0],) + self.cell_shape)
-        plane2d = self._plane_nearest(grouped_nearest)
-        if plane2d:
+            return _result(scen, keep, shape, sync=True)
+        if self._plane_nearest(grouped_nearest):
             # xsdba's nearest node in the (hist_q, group) plane: ONE launch over the whole series (round 5; rounds 3-4 permuted
             # the rows group-major and launched xh_eqm_adjust_g2d per group: 145 ms against 15 for a 30-year 1440 x 90 band
             # with 365 groups)
             scen = K.plane_nearest(dev, s, gi + 1.0, self._af, self._hist_q, self.kind, extrapolation)
-            dev.sync()
-            return scen if keep else scen.get().reshape((s.shape[0],) + self.cell_shape)
-        # group-major permutation of the rows: every group becomes one contiguous block
-        perm = np.argsort(gi, kind="stable")
-        counts = np.bincount(gi, minlength=len(self.group_labels))
-        T, C_ = s.shape
-        nq = len(self.quantiles)
-        s_perm = K.select_rows(dev, s, perm)
-        scen_perm = dev.empty((T, C_), np.float32)
-        off = 0
-        for g, n in enumerate(counts):
-            if n == 0:
-                continue
-            blk = dev.wrap(s_perm.ptr + off * C_ * 4, (int(n), C_), np.float32)
-            out = dev.wrap(scen_perm.ptr + off * C_ * 4, (int(n), C_), np.float32)
-            if plane2d:
-                K.eqm_adjust_g2d(dev, blk, self._af, self._hist_q, g + 1, self.kind, extrapolation, out=out)
-            else:
-                af_g = dev.wrap(self._af.ptr + g * nq * C_ * 4, (nq, C_), np.float32)
-                hq_g = dev.wrap(self._hist_q.ptr + g * nq * C_ * 4, (nq, C_), np.float32)
-                K.eqm_adjust(dev, blk, af_g, hq_g, self.kind, interp, extrapolation, out=out)
-            off += int(n)
-        inv = np.empty(T, dtype=np.int64)
-        inv[perm] = np.arange(T)
-        scen = K.select_rows(dev, scen_perm, inv)
-        dev.sync()
-        return scen if keep else scen.get().reshape((T,) + self.cell_shape)
+            return _result(scen, keep, shape, sync=True)
+        # every step through the nodes of its OWN group: group-major row blocks, one xh_eqm_adjust per group
+        lay = _GroupMajor(gi, len(self.group_labels))
+        s_perm = lay.gather(dev, s)
+        scen_perm = dev.empty(s.shape, np.float32)
+        for g, off, n in lay:
+            K.eqm_adjust(dev, _group(s_perm, off, n), _group(self._af, g), _group(self._hist_q, g), self.kind, interp, extrapolation,
+                         out=_group(scen_perm, off, n))
+        return _result(lay.scatter(dev, scen_perm), keep, shape, sync=True)
 
     def _plane_nearest(self, grouped_nearest: str) -> bool:
         """xsdba's 2-D nearest applies: a month / day-of-year grouping whose labels are 1 .. G (the coordinates upstream's
@@ -605,17 +690,11 @@ class QuantileDeltaMapping(EmpiricalQuantileMapping):
     ``scipy.stats.rankdata``."""
 
     def adjust(self, sim, *, interp: str = "nearest", extrapolation: str = "constant", time=None, keep=False):
-        if interp not in ("nearest", "linear", "cubic"):
-            raise ValueError(f"interp={interp!r} not in ('nearest', 'linear', 'cubic')")
-        _check_group_interp(self.group, interp, "QuantileDeltaMapping.adjust", self.group_labels, extrapolation)
-        members = self._for_members(sim)
-        if members is not None:   # (the ranks are taken along time only — group.apply(rank, sim, main_only=True): per member)
-            return members.adjust(sim, interp=interp, extrapolation=extrapolation, time=time, keep=keep)
-        dev = self._dev
-        s, cell_shape = _flatten(sim, dev)
-        if tuple(cell_shape) != self.cell_shape:
-            raise ValueError("sim does not match the trained grid")
-        if self.group.prop == "group" and interp == "cubic":
+        extra, s, gi = self._adjust_front(sim, interp, extrapolation, time)
+        if extra is not None:   # (the ranks are taken along time only — group.apply(rank, sim, main_only=True): per member)
+            return self._member_model(extra).adjust(sim, interp=interp, extrapolation=extrapolation, time=time, keep=keep)
+        dev, shape = self._dev, (s.shape[0],) + self.cell_shape
+        if gi is None and interp == "cubic":
             # interp_on_quantiles(sim_q, quantiles, af, method="cubic"): scipy interp1d(kind="cubic") over the quantile nodes —
             # the rank kernels give sim_q (kind "factor" on a table whose factors are the nodes themselves, "linear": the
             # rank itself inside the node range; outside it the first / last node for "constant" — where the spline returns
@@ -626,31 +705,20 @@ class QuantileDeltaMapping(EmpiricalQuantileMapping):
             qrows = dev.to_device(np.repeat(self.quantiles.astype(np.float32)[:, None], s.shape[1], axis=1))
             sim_q = K.qdm_adjust(dev, s, qrows, self.quantiles, "factor", "linear", extrapolation)
             af_t = K.eqm_adjust(dev, sim_q, self._af, qrows, "factor", "cubic", extrapolation)
-            scen = K.apply_factor(dev, s, af_t, self.kind, out=sim_q)
-            return scen if keep else scen.get().reshape((s.shape[0],) + self.cell_shape)
-        if self.group.prop == "group":
-            scen = K.qdm_adjust(dev, s, self._af, self.quantiles, self.kind, interp, extrapolation)
-            return scen if keep else scen.get().reshape((s.shape[0],) + self.cell_shape)
-        if time is None or len(time) != s.shape[0]:
-            raise ValueError(f"group={self.group.name!r} needs time=TimeAxis of sim")
-        gi = self.group.index(time, self.group_labels)
-        if (gi < 0).any():
-            raise ValueError("sim holds time steps whose group was not trained (e.g. day 366 with a 365-day training set)")
-        perm = np.argsort(gi, kind="stable")  # group-major: every group one contiguous row block, ranked on its own
-        counts = np.bincount(gi, minlength=len(self.group_labels))
-        T, C_ = s.shape
-        nq = len(self.quantiles)
-        if not (interp == "linear" and self.group.prop == "month"):
+            return _result(K.apply_factor(dev, s, af_t, self.kind, out=sim_q), keep, shape)
+        if gi is None:
+            return _result(K.qdm_adjust(dev, s, self._af, self.quantiles, self.kind, interp, extrapolation), keep, shape)
+        lay = _GroupMajor(gi, len(self.group_labels))  # group-major: every group one contiguous row block, ranked on its own
+        plane = interp == "linear" and self.group.prop == "month"
+        if not plane:
             # small groups (a day-of-year grouping: one step per year, up to 64): every group ranked in registers, ONE launch over
             # the series where it lies (xh_qdm_adjust_groups, round 6: 80 -> ~8 ms for 365 groups of a 30-year 1440 x 90 band;
             # the loop below gathers and launches per group) — bit-identical
-            offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-            scen = K.qdm_adjust_groups(dev, s, perm, offs, self._af, self.quantiles, self.kind, interp, extrapolation)
+            scen = K.qdm_adjust_groups(dev, s, lay.perm, lay.offs, self._af, self.quantiles, self.kind, interp, extrapolation)
             if scen is not None:
-                dev.sync()
-                return scen if keep else scen.get().reshape((T,) + self.cell_shape)
-        s_perm = K.select_rows(dev, s, perm)
-        scen_perm = dev.empty((T, C_), np.float32)
+                return _result(scen, keep, shape, sync=True)
+        s_perm = lay.gather(dev, s)
+        scen_perm = dev.empty(s.shape, np.float32)
         # "linear" over the (quantile, group) plane (xsdba: interp_on_quantiles(sim_q, quantiles, af) with the quantile
         # nodes THEMSELVES as abscissa, the same in every group: a regular grid).  Day of year: the group coordinate is an
         # integer, every query lies ON its group's row, and the row's edges belong to every Delaunay triangulation of a grid
@@ -658,30 +726,20 @@ class QuantileDeltaMapping(EmpiricalQuantileMapping):
         # inside the own group: the loop below.  Month: the coordinate is fractional; the percentage ranks come from the
         # same rank kernels (kind "factor" on a table whose "factors" are the nodes themselves: sim_q clamped to the node
         # range, which is all the plane needs — outside it the row-interpolated end factor applies), then one plane launch.
-        plane = interp == "linear" and self.group.prop == "month"
         qrows = None
         if plane:
-            qrows = dev.to_device(np.repeat(self.quantiles.astype(np.float32)[:, None], C_, axis=1))
-        off = 0
-        for g, n in enumerate(counts):
-            if n == 0:
-                continue
-            blk = dev.wrap(s_perm.ptr + off * C_ * 4, (int(n), C_), np.float32)
-            out = dev.wrap(scen_perm.ptr + off * C_ * 4, (int(n), C_), np.float32)
+            qrows = dev.to_device(np.repeat(self.quantiles.astype(np.float32)[:, None], s.shape[1], axis=1))
+        for g, off, n in lay:
+            blk, out = _group(s_perm, off, n), _group(scen_perm, off, n)
             if plane:
                 K.qdm_adjust(dev, blk, qrows, self.quantiles, "factor", "linear", "constant", out=out)
             else:
-                af_g = dev.wrap(self._af.ptr + g * nq * C_ * 4, (nq, C_), np.float32)
-                K.qdm_adjust(dev, blk, af_g, self.quantiles, self.kind, interp, extrapolation, out=out)
-            off += int(n)
-        inv = np.empty(T, dtype=np.int64)
-        inv[perm] = np.arange(T)
-        scen = K.select_rows(dev, scen_perm, inv)
+                K.qdm_adjust(dev, blk, _group(self._af, g), self.quantiles, self.kind, interp, extrapolation, out=out)
+        scen = lay.scatter(dev, scen_perm)
         if plane:  # scen holds sim_q so far
             scen = K.plane_linear(dev, scen, self.group.coordinate(time, interp=True), self._af, xq_common=self.quantiles, base=s,
                                   kind=self.kind)
-        dev.sync()
-        return scen if keep else scen.get().reshape((T,) + self.cell_shape)
+        return _result(scen, keep, shape, sync=True)
 
 
 class DetrendedQuantileMapping(EmpiricalQuantileMapping):
@@ -703,101 +761,38 @@ class DetrendedQuantileMapping(EmpiricalQuantileMapping):
 
     @classmethod
     def train(cls, ref, hist, *, nquantiles=20, kind: str = ADDITIVE, group="time", window=None, time=None, device=None):
-        grp = group if isinstance(group, Grouper) else Grouper(group, 1 if window is None else window)
+        # Grouper(add_dims=...): means and quantiles over the time steps AND the members (ds.ref.mean(dim), dim = [time, *add_dims])
+        grp = _grouper(group, window)
         if grp.add_dims and grp.prop != "group":
             raise NotImplementedError("DetrendedQuantileMapping with Grouper(add_dims=...) is built for group='time' only")
-        if kind not in (ADDITIVE, MULTIPLICATIVE):
-            raise ValueError(f"kind must be '+' or '*', got {kind!r}")
-        dev = device or get_device()
-        r, cell_shape = _flatten(ref, dev)
-        h, cell_shape_h = _flatten(hist, dev)
-        if tuple(cell_shape) != tuple(cell_shape_h) or r.shape != h.shape:
-            raise ValueError("ref and hist must have the same shape")
-        q = equally_spaced_nodes(nquantiles) if np.isscalar(nquantiles) else np.asarray(nquantiles, dtype=np.float64)
-        inv = "-" if kind == ADDITIVE else "/"
-        # Grouper(add_dims=...): means and quantiles over the time steps AND the members (ds.ref.mean(dim), dim = [time, *add_dims])
-        r, _, cell_shape = grp.pool(dev, r, cell_shape)
-        h, _, _ = grp.pool(dev, h, cell_shape_h)
+        dev, r, h, cell_shape, _, q = _train_front(grp, ref, hist, kind, nquantiles, time, device)
 
-        def one(rg, hg, out=None):
-            mu_r, _ = K.poly_trend(dev, rg, 0)
-            mu_h, _ = K.poly_trend(dev, hg, 0)
-            af, hq = K.eqm_train(dev, K.trend_apply(dev, rg, mu_r, None, inv), K.trend_apply(dev, hg, mu_h, None, inv), q, kind, out=out)
-            # scaling = get_correction(mu_hist, mu_ref): a (C,) table — O(C) host arithmetic on the two mean vectors
-            mr, mh = mu_r.get(), mu_h.get()
-            with np.errstate(all="ignore"):
-                return af, hq, (mr - mh if kind == ADDITIVE else mr / mh)
+        def model(af, hq, scaling, labels=None):
+            if not isinstance(scaling, DeviceArray):
+                scaling = dev.to_device(np.ascontiguousarray(scaling), dtype=np.float64)
+            return cls(dev, af, hq, q, kind, cell_shape, grp, labels, scaling=scaling)
 
         if grp.prop == "group":
-            af, hq, scaling = one(r, h)
-            return cls(dev, af, hq, q, kind, cell_shape, grp, scaling=dev.to_device(np.ascontiguousarray(scaling), dtype=np.float64))
-        if time is None or len(time) != r.shape[0]:
-            raise ValueError(f"group={grp.name!r} needs time=TimeAxis of the training series")
+            return model(*_dqm_train_sample(dev, r, h, q, kind))
         labels = grp.labels(time)
-        G, C_ = len(labels), r.shape[1]
-        af = dev.empty((G, len(q), C_), np.float32)
-        hq = dev.empty((G, len(q), C_), np.float32)
-        plane = len(q) * C_ * 4
-        # day-of-year groups with a window on gap-free years: the sorted window of the EQM training (xh_eqm_train_window) also
-        # carries the mean of every group's sample and normalises the samples it picks (xh_dqm_train_window, round 6: 3 970 ->
-        # ~190 ms for 30 years x 1440 x 90; per group otherwise: a gather, two means, two normalisations, two selections and a
-        # host round trip of the means)
-        small = grp.small_groups(time)
-        if small is not None:   # (no window, small groups: one launch per field — xh_dqm_train_groups, 470 -> ~10 ms)
-            res = K.eqm_train_groups(dev, r, h, small[0], small[1], q, kind, normalised=True)
-            if res is not None:
-                dev.sync()
-                return cls(dev, res[0], res[1], q, kind, cell_shape, grp, labels, scaling=res[2])
-        if grp.window == 1:
-            # no window: every step is in exactly one group, so the group means are ONE xh_poly_trend_groups per field over the
-            # series where it lies (summed in time order: what xh_poly_trend gives on the gathered block), the normalisation is
-            # ONE xh_trend_apply_groups per field, and the tables are the grouped EQM training of the normalised series —
-            # bit-identical to the per-group loop below (month groups of a 30-year 1440 x 90 band: 128 -> ~40 ms)
-            gi = grp.index(time, labels)
-            order = np.argsort(gi, kind="stable")
-            offs = np.concatenate([[0], np.cumsum(np.bincount(gi, minlength=G))]).astype(np.int64)
-            zero_u = dev.zeros((r.shape[0],), np.float64)
-            mu_r, _ = K.poly_trend_groups(dev, r, order, offs, zero_u, 0)
-            mu_h, _ = K.poly_trend_groups(dev, h, order, offs, zero_u, 0)
-            rn = K.trend_apply_groups(dev, r, order, offs, mu_r, None, inv)
-            hn = K.trend_apply_groups(dev, h, order, offs, mu_h, None, inv)
-            eq = EmpiricalQuantileMapping.train(rn, hn, nquantiles=q, kind=kind, group=grp, time=time, device=dev)
-            mr, mh = mu_r.get(), mu_h.get()
-            with np.errstate(all="ignore"):
-                scal = mr - mh if kind == ADDITIVE else mr / mh
-            return cls(dev, eq._af, eq._hist_q, q, kind, cell_shape, grp, labels, scaling=dev.to_device(np.ascontiguousarray(scal), dtype=np.float64))
-        stretches, rest, rows_of = grp.sliding_stretches(time)
-        if stretches:
-            scal_d = dev.empty((G, C_), np.float64)
-            muh = dev.empty((G, C_), np.float64)
-
-            def slab(a, g0, n):
-                return dev.wrap(a.ptr + g0 * plane, (n, len(q), C_), np.float32)
-
-            def rows64(a, g0, n):
-                return dev.wrap(a.ptr + g0 * C_ * 8, (n, C_), np.float64)
-
-            done = True
-            for g0, rows0, en, lv in stretches:
-                n = en.shape[0] + 1
-                if K.eqm_train_window(dev, r, h, rows0, en, lv, q, kind, normalised=True,
-                                      out=(slab(af, g0, n), slab(hq, g0, n), rows64(scal_d, g0, n), rows64(muh, g0, n))) is None:
-                    done = False   # (not the kernel's shape after all: everything through the per-group path below)
-                    break
-            if done:
-                for g in rest:     # the groups no stretch covers (day 366 of a standard calendar): from their gathered sample
-                    _, _, sg = one(K.select_rows(dev, r, rows_of[g]), K.select_rows(dev, h, rows_of[g]),
-                                   out=(slab(af, g, 1).reshape(len(q), C_), slab(hq, g, 1).reshape(len(q), C_)))
-                    row = dev.to_device(np.ascontiguousarray(sg), dtype=np.float64)
-                    dev.copy_d2d(scal_d.ptr + g * C_ * 8, row.ptr, C_ * 8)
-                dev.sync()
-                return cls(dev, af, hq, q, kind, cell_shape, grp, labels, scaling=scal_d)
-        scal = np.empty((G, C_), np.float64)
-        for g, (rg, hg) in grp.group_samples(dev, (r, h), time):
-            out_g = tuple(dev.wrap(a.ptr + g * plane, (len(q), C_), np.float32) for a in (af, hq))
-            _, _, scal[g] = one(rg, hg, out=out_g)
-        dev.sync()
-        return cls(dev, af, hq, q, kind, cell_shape, grp, labels, scaling=dev.to_device(scal, dtype=np.float64))
+        res = _train_groups(dev, grp, time, r, h, q, kind, normalised=True)
+        if res is not None:
+            return model(*res, labels)
+        # no window: every step is in exactly one group, so the group means are ONE xh_poly_trend_groups per field over the
+        # series where it lies (summed in time order: what xh_poly_trend gives on the gathered block), the normalisation is
+        # ONE xh_trend_apply_groups per field, and the tables are the grouped EQM training of the normalised series —
+        # bit-identical to the per-group samples (month groups of a 30-year 1440 x 90 band: 128 -> ~40 ms)
+        inv = "-" if kind == ADDITIVE else "/"
+        lay = _GroupMajor(grp.index(time, labels), len(labels))
+        zero_u = dev.zeros((r.shape[0],), np.float64)
+        mu_r, _ = K.poly_trend_groups(dev, r, lay.perm, lay.offs, zero_u, 0)
+        mu_h, _ = K.poly_trend_groups(dev, h, lay.perm, lay.offs, zero_u, 0)
+        rn = K.trend_apply_groups(dev, r, lay.perm, lay.offs, mu_r, None, inv)
+        hn = K.trend_apply_groups(dev, h, lay.perm, lay.offs, mu_h, None, inv)
+        eq = EmpiricalQuantileMapping.train(rn, hn, nquantiles=q, kind=kind, group=grp, time=time, device=dev)
+        mr, mh = mu_r.get(), mu_h.get()
+        with np.errstate(all="ignore"):
+            return model(eq._af, eq._hist_q, mr - mh if kind == ADDITIVE else mr / mh, labels)
 
     @property
     def scaling(self) -> np.ndarray:
@@ -806,28 +801,21 @@ class DetrendedQuantileMapping(EmpiricalQuantileMapping):
 
     def adjust(self, sim, *, interp: str = "nearest", extrapolation: str = "constant", detrend: int = 1, time=None, keep=False,
                grouped_nearest: str = "griddata"):
-        if interp not in ("nearest", "linear", "cubic"):
-            raise ValueError(f"interp={interp!r} not in ('nearest', 'linear', 'cubic')")
-        if detrend not in (0, 1):
-            raise NotImplementedError("DetrendedQuantileMapping.adjust: detrend must be 0 or 1 (polynomial degree)")
+        extra, s, gi = self._adjust_front(sim, interp, extrapolation, time, detrend=detrend, dqm_order=True,
+                                          untrained="sim holds time steps whose group was not trained")
         dev = self._dev
-        s, cell_shape = _flatten(sim, dev)
         fwd, inv = ("+", "-") if self.kind == ADDITIVE else ("*", "/")
-        n = len(self.cell_shape)
-        if tuple(cell_shape) != self.cell_shape and self.group.prop == "group" and len(cell_shape) > n and \
-                (n == 0 or tuple(cell_shape[len(cell_shape) - n:]) == self.cell_shape):
-            return self._adjust_members(s, tuple(cell_shape[:len(cell_shape) - n]), interp, extrapolation, detrend, keep, fwd, inv)
-        if tuple(cell_shape) != self.cell_shape:
-            raise ValueError("sim does not match the trained grid")
-        if self.group.prop != "group":
-            return self._adjust_grouped(s, interp, extrapolation, detrend, time, keep, fwd, inv, grouped_nearest)
+        if extra is not None:
+            return self._adjust_members(_flatten(sim, dev)[0], extra, interp, extrapolation, detrend, keep, fwd, inv)
+        if gi is not None:
+            return self._adjust_grouped(s, gi, interp, extrapolation, detrend, time, keep, fwd, inv, grouped_nearest)
         scaled = K.trend_apply(dev, s, self._scaling, None, fwd)
         p0, p1 = K.poly_trend(dev, scaled, detrend)
         detr = K.trend_apply(dev, scaled, p0, p1, inv)
         del scaled
         scen0 = K.eqm_adjust(dev, detr, self._af, self._hist_q, self.kind, interp, extrapolation)
         scen = K.trend_apply(dev, scen0, p0, p1, fwd, out=detr)  # (distinct buffers: the kernels' pointers are __restrict__)
-        return scen if keep else scen.get().reshape((s.shape[0],) + self.cell_shape)
+        return _result(scen, keep, (s.shape[0],) + self.cell_shape)
 
     def _adjust_members(self, s, extra, interp, extrapolation, detrend, keep, fwd, inv):
         """group="time", a sim with member axes right behind time ((T, members x cells) here).  Every member is scaled and mapped
@@ -842,10 +830,6 @@ class DetrendedQuantileMapping(EmpiricalQuantileMapping):
         def tile64(a):   # (C,) float64 table -> (E * C,)
             return dev.to_device(np.tile(a.get().reshape(-1), E), dtype=np.float64)
 
-        def tile32(tab):  # (nq, C) -> (nq, E * C)
-            lead = tab.shape[0]
-            return K.select_rows(dev, tab.reshape(lead, C_), np.repeat(np.arange(lead), E)).reshape(lead, E * C_)
-
         scaled = K.trend_apply(dev, s, tile64(self._scaling), None, fwd)
         if self.group.add_dims:
             # the mean over the members of every step: the (T, E x C) matrix is (T x E, C) with E rows per step
@@ -856,70 +840,54 @@ class DetrendedQuantileMapping(EmpiricalQuantileMapping):
             p0, p1 = K.poly_trend(dev, scaled, detrend)
         detr = K.trend_apply(dev, scaled, p0, p1, inv)
         del scaled
-        scen0 = K.eqm_adjust(dev, detr, tile32(self._af), tile32(self._hist_q), self.kind, interp, extrapolation)
+        scen0 = K.eqm_adjust(dev, detr, _tile_members(dev, self._af, E), _tile_members(dev, self._hist_q, E), self.kind, interp,
+                             extrapolation)
         scen = K.trend_apply(dev, scen0, p0, p1, fwd, out=detr)
-        return scen if keep else scen.get().reshape((T,) + tuple(extra) + self.cell_shape)
+        return _result(scen, keep, (T,) + tuple(extra) + self.cell_shape)
 
-    def _adjust_grouped(self, s, interp, extrapolation, detrend, time, keep, fwd, inv, grouped_nearest="griddata"):
+    def _interpolated_scaling(self, s, gcoord, fwd):
+        """xsdba: u.broadcast(scaling, sim, group=group, interp=interp) — for every interpolation but "nearest" (and every
+        grouping but the day of year) the scaling of a step is INTERPOLATED over the group coordinate (cyclic copies at
+        0 and G + 1, DataArray.interp "linear"): scaling_t = S[r0] + (S[r0 + 1] - S[r0]) (g_t - r0).  Steps are handled
+        interval by interval of the coordinate (G + 1 of them, group-major like the groups): x OP (p0 + p1 u) is
+        xh_trend_apply_u.  Returns the scaled series in time order."""
+        dev = self._dev
+        G = len(self.group_labels)
+        S = self._scaling.get().reshape(G, s.shape[1])
+        r0 = np.clip(np.floor(gcoord).astype(np.int64), 0, G)
+        row = lambda r: (r - 1) % G                                  # coordinate 0 .. G + 1 -> group (cyclic)
+        lay = _GroupMajor(r0, G + 1)
+        s_perm = lay.gather(dev, s)
+        sc_perm = dev.empty(s.shape, np.float32)
+        for r, off, n in lay:
+            a0, a1 = S[row(r)], S[row(r + 1)]
+            p0 = dev.to_device(np.ascontiguousarray(a0), dtype=np.float64)
+            p1 = dev.to_device(np.ascontiguousarray(a1 - a0), dtype=np.float64)
+            uf = dev.to_device(np.ascontiguousarray(gcoord[lay.rows(off, n)] - r), dtype=np.float64)
+            K.trend_apply(dev, _group(s_perm, off, n), p0, p1, fwd, out=_group(sc_perm, off, n), u=uf)
+        return lay.scatter(dev, sc_perm)
+
+    def _adjust_grouped(self, s, gi, interp, extrapolation, detrend, time, keep, fwd, inv, grouped_nearest="griddata"):
         """dqm_adjust with a sub-grouping: group-major row blocks like the grouped EQM; per block the group's
         scaling (``u.broadcast``), the trend fitted over the group's OWN steps on their time coordinate (days since the
         group's mean date: ``PolyDetrend(group=...)`` -> polyfit along time), the group's nodes, the trend put back."""
-        _check_group_interp(self.group, interp, "DetrendedQuantileMapping.adjust", self.group_labels, extrapolation)
-        dev = self._dev
-        if time is None or len(time) != s.shape[0]:
-            raise ValueError(f"group={self.group.name!r} needs time=TimeAxis of sim")
-        gi = self.group.index(time, self.group_labels)
-        if (gi < 0).any():
-            raise ValueError("sim holds time steps whose group was not trained")
-        perm = np.argsort(gi, kind="stable")
-        counts = np.bincount(gi, minlength=len(self.group_labels))
-        T, C_ = s.shape
-        nq = len(self.quantiles)
+        dev, shape = self._dev, (s.shape[0],) + self.cell_shape
+        lay = _GroupMajor(gi, len(self.group_labels))
         days = np.asarray(time.ordinal(), dtype=np.float64)
         gcoord = self.group.coordinate(time, interp=True) if interp == "linear" else None
-        src = s
         prescaled = interp == "linear" and self.group.prop == "month"
-        if prescaled:
-            # xsdba: u.broadcast(scaling, sim, group=group, interp=interp) — for every interpolation but "nearest" (and every
-            # grouping but the day of year) the scaling of a step is INTERPOLATED over the group coordinate (cyclic copies at
-            # 0 and G + 1, DataArray.interp "linear"): scaling_t = S[r0] + (S[r0 + 1] - S[r0]) (g_t - r0).  Steps are handled
-            # interval by interval of the coordinate (G + 1 of them): x OP (p0 + p1 u) is xh_trend_apply_u.
-            G = len(self.group_labels)
-            S = self._scaling.get().reshape(G, C_)
-            r0 = np.clip(np.floor(gcoord).astype(np.int64), 0, G)
-            row = lambda r: (r - 1) % G                                  # coordinate 0 .. G + 1 -> group (cyclic)
-            perm2 = np.argsort(r0, kind="stable")
-            cnt2 = np.bincount(r0, minlength=G + 1)
-            s_p2 = K.select_rows(dev, s, perm2)
-            sc_p2 = dev.empty((T, C_), np.float32)
-            o2 = 0
-            for r in range(G + 1):
-                n2 = int(cnt2[r])
-                if n2 == 0:
-                    continue
-                rows2 = perm2[o2:o2 + n2]
-                a0, a1 = S[row(r)], S[row(r + 1)]
-                p0 = dev.to_device(np.ascontiguousarray(a0), dtype=np.float64)
-                p1 = dev.to_device(np.ascontiguousarray(a1 - a0), dtype=np.float64)
-                uf = dev.to_device(np.ascontiguousarray(gcoord[rows2] - r), dtype=np.float64)
-                K.trend_apply(dev, dev.wrap(s_p2.ptr + o2 * C_ * 4, (n2, C_), np.float32), p0, p1, fwd,
-                              out=dev.wrap(sc_p2.ptr + o2 * C_ * 4, (n2, C_), np.float32), u=uf)
-                o2 += n2
-            inv2 = np.empty(T, dtype=np.int64)
-            inv2[perm2] = np.arange(T)
-            src = K.select_rows(dev, sc_p2, inv2)
+        src = self._interpolated_scaling(s, gcoord, fwd) if prescaled else s
         windowed = self.group.window > 1
         if interp == "linear" or self._plane_nearest(grouped_nearest):
             # the (quantile, group) plane serves the whole series in one launch, and so do the scaling, the per-group fit and the
             # trend (xh_trend_apply_groups / xh_poly_trend_groups, round 6: a group is a list of rows, the coefficients are
             # (G, C) tables, nothing is permuted) — bit-identical to the per-group loop below, which launched four kernels per
             # group on gathered blocks (365 groups: 87 ms for a 30-year 1440 x 90 band, now ~20)
-            offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-            u_time = np.zeros(T, dtype=np.float64)
-            for g in range(len(counts)):
-                r = perm[offs[g]:offs[g + 1]]
-                if len(r):
-                    u_time[r] = days[r] - days[r].mean()
+            perm, offs = lay.perm, lay.offs
+            u_time = np.zeros(s.shape[0], dtype=np.float64)
+            for g, off, n in lay:
+                r = lay.rows(off, n)
+                u_time[r] = days[r] - days[r].mean()
             u_d = dev.to_device(u_time, dtype=np.float64)
             scaled = src if prescaled else K.trend_apply_groups(dev, s, perm, offs, self._scaling, None, fwd)
             fit_on = K.window_nanmean(dev, scaled, self.group.window) if windowed else scaled
@@ -932,12 +900,9 @@ class DetrendedQuantileMapping(EmpiricalQuantileMapping):
             else:
                 scen0 = K.plane_nearest(dev, detr, gi + 1.0, self._af, self._hist_q, self.kind, extrapolation)
             scen = K.trend_apply_groups(dev, scen0, perm, offs, p0, p1, fwd, u=u_d, out=detr)
-            dev.sync()
-            return scen if keep else scen.get().reshape((T,) + self.cell_shape)
-        s_perm = K.select_rows(dev, src, perm)
-        scen_perm = dev.empty((T, C_), np.float32)
-        inv_perm = np.empty(T, dtype=np.int64)
-        inv_perm[perm] = np.arange(T)
+            return _result(scen, keep, shape, sync=True)
+        s_perm = lay.gather(dev, src)
+        scen_perm = dev.empty(s.shape, np.float32)
         wm_perm = None
         if windowed:
             # PolyDetrend with a windowed Grouper (xsdba.detrending._polydetrend_get_trend: ``da.mean(dim[1:])`` before polyfit):
@@ -945,38 +910,21 @@ class DetrendedQuantileMapping(EmpiricalQuantileMapping):
             # carry the scaling of their own groups, so the whole series is scaled first (group-major blocks), brought back to
             # time order, averaged, and permuted again
             if not prescaled:
-                off = 0
-                for g, n in enumerate(counts):
-                    n = int(n)
-                    if n:
-                        sc_g = dev.wrap(self._scaling.ptr + g * C_ * 8, (C_,), np.float64)
-                        blk = dev.wrap(s_perm.ptr + off * C_ * 4, (n, C_), np.float32)
-                        K.trend_apply(dev, blk, sc_g, None, fwd, out=dev.wrap(scen_perm.ptr + off * C_ * 4, (n, C_), np.float32))
-                    off += n
+                for g, off, n in lay:
+                    K.trend_apply(dev, _group(s_perm, off, n), _group(self._scaling, g), None, fwd, out=_group(scen_perm, off, n))
                 s_perm, scen_perm = scen_perm, s_perm          # s_perm: the scaled series, group-major
-                src = K.select_rows(dev, s_perm, inv_perm)     # ... and in time order
-            wm_perm = K.select_rows(dev, K.window_nanmean(dev, src, self.group.window), perm)
-        off = 0
+                src = lay.scatter(dev, s_perm)                 # ... and in time order
+            wm_perm = lay.gather(dev, K.window_nanmean(dev, src, self.group.window))
         # (what is left here: every step through the nodes of its OWN group — grouped_nearest="group", seasons, more than 32
         # nodes, "cubic": one xh_eqm_adjust per group on its gathered block)
-        for g, n in enumerate(counts):
-            n = int(n)
-            if n == 0:
-                continue
-            rows = perm[off:off + n]
+        for g, off, n in lay:
+            rows = lay.rows(off, n)
             u = dev.to_device(np.ascontiguousarray(days[rows] - days[rows].mean()), dtype=np.float64)
-            blk = dev.wrap(s_perm.ptr + off * C_ * 4, (n, C_), np.float32)
-            out = dev.wrap(scen_perm.ptr + off * C_ * 4, (n, C_), np.float32)
-            sc_g = dev.wrap(self._scaling.ptr + g * C_ * 8, (C_,), np.float64)
-            af_g = dev.wrap(self._af.ptr + g * nq * C_ * 4, (nq, C_), np.float32)
-            hq_g = dev.wrap(self._hist_q.ptr + g * nq * C_ * 4, (nq, C_), np.float32)
-            scaled = blk if (prescaled or windowed) else K.trend_apply(dev, blk, sc_g, None, fwd)
-            fit_on = scaled if not windowed else dev.wrap(wm_perm.ptr + off * C_ * 4, (n, C_), np.float32)
+            blk = _group(s_perm, off, n)
+            scaled = blk if (prescaled or windowed) else K.trend_apply(dev, blk, _group(self._scaling, g), None, fwd)
+            fit_on = scaled if not windowed else _group(wm_perm, off, n)
             p0, p1 = K.poly_trend(dev, fit_on, detrend, u=u)
             detr = K.trend_apply(dev, scaled, p0, p1, inv, u=u)
-            scen0 = K.eqm_adjust(dev, detr, af_g, hq_g, self.kind, interp, extrapolation)
-            K.trend_apply(dev, scen0, p0, p1, fwd, out=out, u=u)
-            off += n
-        scen = K.select_rows(dev, scen_perm, inv_perm)
-        dev.sync()
-        return scen if keep else scen.get().reshape((T,) + self.cell_shape)
+            scen0 = K.eqm_adjust(dev, detr, _group(self._af, g), _group(self._hist_q, g), self.kind, interp, extrapolation)
+            K.trend_apply(dev, scen0, p0, p1, fwd, out=_group(scen_perm, off, n), u=u)
+        return _result(lay.scatter(dev, scen_perm), keep, shape, sync=True)

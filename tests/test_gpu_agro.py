@@ -1,0 +1,390 @@
+"""The agroclimatic heat-sum unit on the device (xclim_amd/csrc/agro.hip, xclim_amd.agro) against tests/golden/agro_vectors.npz
+and, at the cell counts and lengths no golden value exists for, against the numpy restatement tests/agrocpu.py; the host mirrors
+bit for bit against the kernel calls; empty periods; on padded, poisoned row views (tests/stridedabi.py); cross-checks against
+the project's own kernels; the refusals.  Every test runs on poisoned output buffers, and after every call of an entry point no
+output element may still hold the poison (tests/unwritten.py: watch, on the operand table of tests/test_agro_cpu.py).
+
+Tolerance (tests/test_agro_cpu.py: check): |got - want| <= 1e-12 * scale; counts, the EGDD bound days and the NaN patterns
+exactly.  The mirrors take the Gladstones and Jones coefficients from xh_solar_table, which carries its own 1e-12 against
+tests/petcpu.py: against the golden values (made from tests/petcpu.py) they get 2e-12 * scale."""
+
+import warnings
+
+import numpy as np
+import pytest
+
+import agrocpu as A
+import stridedabi as S
+import unwritten as U
+from test_agro_cpu import (AGRO_TABLE, BEDD_ANSWERS, HEADER, K2C, RTOL, RUNS, bedd_inputs, check, check_bedd, check_known_answers,
+                           check_run, golden_case, refusals, spec_of)
+from xclim_amd import agro
+from xclim_amd import kernels as K
+from xclim_amd.calendar import select_time_mask
+from xclim_amd.timeaxis import TimeAxis
+from poisoned import poisoned_outputs  # noqa: F401  (autouse: the tests of this module that use the device run on poisoned output buffers)
+
+pytestmark = pytest.mark.gpu
+DAY = 86400.0
+
+
+@pytest.fixture(autouse=True)
+def watched(request, monkeypatch):
+    """The operand table of the new header joins stridedabi's for the duration of a test, and every call of an entry point through
+    ``dev.call`` is followed by the check that it wrote every element of its outputs."""
+    protos = S.prototypes(HEADER)
+    for name, ops in AGRO_TABLE.items():
+        monkeypatch.setitem(S.TABLE, name, ops)
+        monkeypatch.setitem(S.PROTOS, name, protos[name])
+    if "dev" not in request.fixturenames:
+        yield None
+        return
+    with U.watch(request.getfixturevalue("dev"), monkeypatch) as log:
+        yield log
+
+
+def _host(outs):
+    return {k: v.get() for k, v in outs.items()}
+
+
+# ---- one run, through kernels.py and through the mirror ---------------------------------------------------------------
+def _factors(dev, c, s, mirror):
+    """The factor arguments of K.agro_degree_sum: from the restatement's tables, or from the mirror's own (xh_solar_table)."""
+    f = A.factors(s, c.time, c.lat, c.season)
+    kw = dict(tr_adj=f["tr_adj"])
+    lat_u = np.unique(c.lat)
+    if "k_cell" in f:
+        kw["k_cell"] = dev.to_device(f["k_cell"])
+    if "k_day" in f:
+        kw.update(k_day=dev.to_device(agro._gladstones_table(c.time, lat_u, dev) if mirror else f["k_day"]), lat_idx=f["lat_idx"])
+    if "k_period" in f:
+        table = agro._jones_table(c.time, lat_u, c.season[0], s["end_date"], s["freq"], dev) if mirror else f["k_period"]
+        kw.update(k_period=dev.to_device(table), lat_idx=f["lat_idx"])
+    return kw
+
+
+def launch(dev, c, run, mirror_tables=False):
+    s = spec_of(c, run)
+    kind, freq, t = s["kind"], s["freq"], c.time
+    d = {k: dev.to_device(v) for k, v in c.fields.items()}
+    if kind in ("hi", "bedd", "both"):
+        sel = select_time_mask(t, date_bounds=(c.season[0], s["end_date"]), include_bounds=(True, False))
+        names = {"hi": ["hi"], "bedd": ["bedd"], "both": ["hi", "bedd"]}[kind]
+        return _host(K.agro_degree_sum(dev, d, t.segments(freq)[0], sel, sub_C=c.sub_C, outputs=names + ["valid"],
+                                       **_factors(dev, c, s, mirror_tables)))
+    if kind == "egdd":
+        return _host(K.egdd(dev, d["tasmin"], d["tasmax"], *A.egdd_tables(t, freq), method=s["method"], sub_C=c.sub_C,
+                            outputs=K.EGDD_OUTPUTS))
+    names = [n for n in K.AGRO_MONTHLY_OUTPUTS if n in c.expected[run]]
+    return _host(K.agro_monthly(dev, d, *A.month_tables(t, freq), lat=dev.to_device(c.lat), sub_C=c.sub_C, per_day=c.per_day,
+                                outputs=names))
+
+
+def mirror(dev, c, run):
+    s = spec_of(c, run)
+    kind, freq, f = s["kind"], s["freq"], c.fields
+    kw = dict(freq=freq, time=c.time, device=dev)
+    if kind in ("hi", "bedd", "both"):
+        kw.update(start_date=c.season[0], end_date=s["end_date"], units=c.units)
+        if kind == "hi":
+            return {"hi": agro.huglin_index(f["tas"], f["tasmax"], c.lat, method=s["method"], **kw)}
+        if kind == "bedd":
+            lat = None if s["method"] == "icclim" else c.lat
+            return {"bedd": agro.biologically_effective_degree_days(f["tasmin"], f["tasmax"], lat, method=s["method"], **kw)}
+        both = agro.heat_sums(f["tas"], f["tasmin"], f["tasmax"], c.lat, method=s["method"], **kw)
+        return {"hi": both.huglin_index, "bedd": both.biologically_effective_degree_days}
+    if kind == "egdd":
+        e, a, b = agro.effective_growing_degree_days(f["tasmax"], f["tasmin"], method=s["method"], units=c.units, bounds=True, **kw)
+        return {"egdd": e, "start": a, "end": b}
+    out = {"lti": agro.latitude_temperature_index(f["tas"], c.lat, 60, units=c.units, **kw)}
+    if freq == "YS":
+        out["cni"] = agro.cool_night_index(f["tasmin"], c.lat, units=c.units, **kw)
+    if "pr" in f:
+        out["di"] = agro.dryness_index(f["pr"], f["evspsblpot"], c.lat, **kw)
+    return out
+
+
+def _bits(a):
+    return np.asarray(a, np.float64).view(np.int64)
+
+
+@pytest.mark.parametrize("name,run", RUNS)
+def test_golden_cases(dev, name, run):
+    c = golden_case(name)
+    exp = c.expected[run]
+    got = launch(dev, c, run)
+    assert set(got) == {k for k in exp if not k.endswith("_scale")}
+    check_run(got, exp, f"{name} {run}")
+    # the host mirror: the same bits as the kernel call on the mirror's own tables, and the golden values within the bound
+    s = spec_of(c, run)
+    own = s.get("method") in ("gladstones", "jones")
+    same = launch(dev, c, run, mirror_tables=True) if own else got
+    for k, v in mirror(dev, c, run).items():
+        if k == "lti":
+            la = np.abs(c.lat)
+            v, k, want = v, "mtwm", same["mtwm"] * np.where(la <= 60, 60 - la, 0)
+        else:
+            want = same[k]
+        np.testing.assert_array_equal(_bits(v), _bits(want), err_msg=f"{name} {run} {k}: mirror")
+        if k in exp and own:
+            check(v, exp[k], 2 * exp[k + "_scale"], f"{name} {run} {k}: mirror against the golden value")
+
+
+def test_a_season_that_selects_nothing_in_a_period(dev):
+    """Monthly periods outside April - October: HI and BEDD are 0 there and valid is 0."""
+    c = golden_case("midyear_f64")
+    got = launch(dev, c, "both.interpolated.MS")
+    seg, starts = c.time.segments("MS")
+    winter = np.array([m in (11, 12, 1, 2, 3) for _, m in starts])
+    assert winter.sum() >= 10
+    for k in ("hi", "bedd", "valid"):
+        assert (got[k][winter] == 0).all() and got[k].dtype == (np.int32 if k == "valid" else np.float64)
+    assert (got["valid"][~winter] > 0).all()
+
+
+# ---- cell counts and lengths: one lane, a partial wave past a full one, more than one workgroup -------------------------
+_SYNTH = {}
+_STARTS = {1: "2000-06-28", 7: "2000-06-28", 366: "2000-01-01", 1002: "1999-03-15", 1248: "1992-01-01"}
+
+
+def _synth(C, T, dtype):
+    """Seeded fields on T days and C cells, and the restatement's values for them: once per (C, T, dtype)."""
+    key = (C, T, np.dtype(dtype).name)
+    if key not in _SYNTH:
+        rng = np.random.default_rng(7000 + 13 * C + T)
+        t = TimeAxis.daily(_STARTS[T], T)
+        lat = np.round(np.linspace(-58, 58, C) if C > 1 else np.array([46.5]), 1)
+        doy = t.doy[:, None].astype(np.float64)
+        phase = np.where(lat >= 0, 105.0, 287.0)[None, :]
+        tas = 284 + 11 * np.sin(2 * np.pi * (doy - phase) / 365) + rng.normal(0, 3, (T, C))
+        f = dict(tas=tas, tasmin=tas - rng.uniform(2, 9, (T, C)), tasmax=tas + rng.uniform(2, 9, (T, C)),
+                 pr=np.maximum(rng.normal(2.5, 4, (T, C)), 0) / DAY, evspsblpot=np.maximum(rng.normal(2.5, 1, (T, C)), 0) / DAY)
+        f = {k: v.astype(dtype) for k, v in f.items()}
+        for v in f.values():
+            v[rng.random((T, C)) < 0.004] = np.nan
+        exp = {}
+        for s in (dict(kind="both", method="interpolated", freq="YS", end_date="11-01"), dict(kind="bedd", method="gladstones", freq="YS", end_date="11-01"),
+                  dict(kind="egdd", method="bootsma", freq="YS"), dict(kind="egdd", method="qian", freq="YS-JUL"), dict(kind="monthly", freq="YS")):
+            r = A.run(s, f, lat, t, K2C, DAY, ("04-01",))
+            gap = r.pop("min_gap", 1.0)
+            assert gap > 1e-9, "the seeded field puts a value within 1e-9 of a threshold: change the seed"
+            exp[".".join(str(s[k]) for k in ("kind", "method", "freq") if k in s)] = (s, r)
+        exp["chu"], exp["qian"] = A.corn_heat_units(f["tasmin"], f["tasmax"]), A.qian_wma(f["tas"])
+        _SYNTH[key] = (t, lat, f, exp)
+    return _SYNTH[key]
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("T", [1, 7, 366, 1002, 1248])
+@pytest.mark.parametrize("C", [1, 67, 260])
+def test_cell_counts_and_lengths_against_restatement(dev, C, T, dtype):
+    t, lat, f, exp = _synth(C, T, dtype)
+    c = golden_case("midyear_f64")
+    c.time, c.lat, c.fields, c.sub_C, c.season, c.units = t, lat, f, K2C, ("04-01",), "K"
+    for run, val in exp.items():
+        if run in ("chu", "qian"):
+            continue
+        s, want = val
+        c.runs, c.expected = [s], {run: want}
+        check_run(launch(dev, c, run), want, f"C={C} T={T} {run}")
+    d = {k: dev.to_device(v) for k, v in f.items()}
+    chu, q = K.corn_heat_units(dev, d["tasmin"], d["tasmax"]).get(), K.qian_wma(dev, d["tas"]).get()
+    dn, dx = np.nan_to_num(A.widen(f["tasmin"], K2C) - 4.44), np.nan_to_num(A.widen(f["tasmax"], K2C) - 10.0)
+    # the degC terms of the halves that count: the subtractions are the kernel's own, only the products can round differently
+    check(chu, exp["chu"], np.where(dn > 0, 1.8 * dn, 0) + np.where(dx > 0, 3.33 * dx + 0.084 * dx * dx, 0), "chu")
+    check(q, exp["qian"], np.abs(np.nan_to_num(A.widen(f["tas"]))).max(), "qian")
+    assert np.isnan(q[:2]).all() and np.isnan(q[-2:]).all()
+
+
+# ---- empty first, middle and last periods ------------------------------------------------------------------------------
+def test_empty_first_middle_and_last_periods(dev):
+    t, lat, f, _ = _synth(67, 366, np.float32)
+    C, T = 67, 366
+    d = {k: dev.to_device(v) for k, v in f.items()}
+    seg = np.array([0, 0, 150, 150, T, T], np.int64)
+    empty = np.array([True, False, True, False, True])
+    sel = select_time_mask(t, date_bounds=("04-01", "11-01"), include_bounds=(True, False))
+    k = A.huglin_coefficient(lat, "huglin", 1.0)
+    got = _host(K.agro_degree_sum(dev, d, seg, sel, k_cell=dev.to_device(k), outputs=K.AGRO_DEGREE_OUTPUTS))
+    check_run(got, A.degree_sum(f["tas"], f["tasmin"], f["tasmax"], seg, sel, k), "empty periods: degree sums")
+    assert (got["hi"][empty] == 0).all() and (got["bedd"][empty] == 0).all() and (got["valid"][empty] == 0).all()
+
+    tabs = list(A.egdd_tables(t, "YS"))                                  # one year: spread its tables over the five periods
+    sf, ef = np.array([-1, 0, -1, -1, -1], np.int64), np.array([-1, -1, -1, int(tabs[3][0]), -1], np.int64)
+    day0 = np.array([0, 0, 0, 150, 0], np.int64)
+    per = lambda a: np.repeat(a, 5)  # noqa: E731
+    for method in ("bootsma", "qian"):
+        args = (seg, tabs[1], sf, ef, day0, per(tabs[5]), per(tabs[6]))
+        got = _host(K.egdd(dev, d["tasmin"], d["tasmax"], *args, method=method, outputs=K.EGDD_OUTPUTS))
+        check_run(got, A.egdd(f["tasmin"], f["tasmax"], *args, method=method), f"empty periods: egdd {method}")
+        assert np.isnan(got["egdd"]).all() and (got["valid"][empty] == 0).all()      # no period holds both of its dates
+        assert not np.isnan(got["start"][1]).all() and not np.isnan(got["end"][3]).all()
+
+    mo, mc, md, _ = A.month_tables(t, "YS")
+    sm = np.array([0, 0, 5, 5, 12, 12], np.int64)
+    got = _host(K.agro_monthly(dev, d, mo, mc, md, sm, lat=dev.to_device(lat), outputs=K.AGRO_MONTHLY_OUTPUTS))
+    check_run(got, A.monthly(f["tasmin"], f["tas"], f["pr"], f["evspsblpot"], lat, mo, mc, md, sm), "empty periods: monthly")
+    assert np.isnan(got["cni"][empty]).all() and np.isnan(got["mtwm"][empty]).all() and (got["valid"][empty] == 0).all()
+    assert (got["di"][0][lat >= 0] == 200).all()
+
+
+# ---- padded, poisoned row views ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("C,pitch", [(67, 80), (260, 272)])
+def test_padded_views_give_the_same_bits(dev, monkeypatch, C, pitch, dtype):
+    """Every strided operand of the five entry points in rows of `pitch` elements, NaN / 1e30 in the extra columns of the inputs and
+    in front of their first row, 0xA5 bytes in those of the outputs (tests/stridedabi.py: padded, which asserts that they stay)."""
+    for name, ops in AGRO_TABLE.items():
+        for op in ops:
+            assert {op.ptr, op.stride} <= set(S.PROTOS[name]), (name, op)
+    t, lat, f, _ = _synth(C, 366, dtype)
+    seg = t.segments("MS")[0]
+    sel = select_time_mask(t, date_bounds=("04-01", "11-01"), include_bounds=(True, False))
+
+    def run():
+        d = {k: dev.to_device(v) for k, v in f.items()}
+        out = {"deg." + k: v for k, v in K.agro_degree_sum(dev, d, seg, sel, k_cell=dev.to_device(np.ones(C)), outputs=K.AGRO_DEGREE_OUTPUTS).items()}
+        out.update({"mon." + k: v for k, v in K.agro_monthly(dev, d, *A.month_tables(t, "YS"), lat=dev.to_device(lat),
+                                                             outputs=K.AGRO_MONTHLY_OUTPUTS).items()})
+        out.update({"egdd." + k: v for k, v in K.egdd(dev, d["tasmin"], d["tasmax"], *A.egdd_tables(t, "YS"), method="qian",
+                                                      outputs=K.EGDD_OUTPUTS).items()})
+        out["chu"], out["qian"] = K.corn_heat_units(dev, d["tasmin"], d["tasmax"]), K.qian_wma(dev, d["tas"])
+        return _host(out)
+
+    plain = run()
+    with S.padded(dev, monkeypatch, pads=(pitch - C, pitch - C), shift=5) as log:
+        got = run()
+    assert set(got) == set(plain) and len(got) == 13
+    for k, g in got.items():
+        p = plain[k]
+        same = (g == p) | (np.isnan(g) & np.isnan(p)) if g.dtype.kind == "f" else g == p
+        assert g.shape == p.shape and same.all(), f"{k} differs under row pitches {log}"
+    assert [n for n, _ in log] == list(AGRO_TABLE)
+    assert all(used == {"ld": (pitch, C), "ld_out": (pitch, C)} for _, used in log), log
+
+
+def test_every_output_operand_was_armed_and_checked(dev, watched):
+    """The watch of this module sees the outputs of all five entry points poisoned before the call (they come from Device.empty
+    under the fixture) and written after it."""
+    t, lat, f, _ = _synth(67, 366, np.float32)
+    d = {k: dev.to_device(v) for k, v in f.items()}
+    K.agro_degree_sum(dev, d, t.segments("YS")[0], None, outputs=K.AGRO_DEGREE_OUTPUTS)
+    K.agro_monthly(dev, d, *A.month_tables(t, "YS"), hemisphere="south", outputs=K.AGRO_MONTHLY_OUTPUTS)
+    K.egdd(dev, d["tasmin"], d["tasmax"], *A.egdd_tables(t, "YS"), outputs=K.EGDD_OUTPUTS)
+    K.corn_heat_units(dev, d["tasmin"], d["tasmax"])
+    K.qian_wma(dev, d["tas"])
+    seen = {n: armed for n, armed in watched if n in AGRO_TABLE}
+    assert set(seen) == set(AGRO_TABLE)
+    for name, armed in seen.items():
+        assert set(armed) == {op.ptr for op in AGRO_TABLE[name] if op.mode == "w"} and all(armed.values()), (name, armed)
+
+
+# ---- cross-checks --------------------------------------------------------------------------------------------------------
+def test_both_sums_from_one_launch_equal_the_separate_launches(dev):
+    for name, run in (("midyear_f64", "both.interpolated.YS-JUL"), ("midyear_f32", "both.interpolated.YS")):
+        c = golden_case(name)
+        s = spec_of(c, run)
+        both = launch(dev, c, run)
+        d = {k: dev.to_device(v) for k, v in c.fields.items()}
+        sel = select_time_mask(c.time, date_bounds=(c.season[0], s["end_date"]), include_bounds=(True, False))
+        seg = c.time.segments(s["freq"])[0]
+        for k in ("hi", "bedd"):
+            one = _host(K.agro_degree_sum(dev, d, seg, sel, sub_C=c.sub_C, outputs=(k,), **_factors(dev, c, s, False)))[k]
+            np.testing.assert_array_equal(_bits(both[k]), _bits(one), err_msg=f"{name} {k}")
+        assert (both["hi"] != both["bedd"]).any()
+
+
+def test_egdd_qian_from_the_output_of_xh_qian_wma(dev):
+    """EGDD "qian" equals the restatement's bound search and sum on the smoothed series that xh_qian_wma itself gives."""
+    c = golden_case("midyear_f64")
+    for freq in ("YS", "YS-JUL"):
+        tn, tx = c.fields["tasmin"], c.fields["tasmax"]
+        tas = (A.widen(tn, c.sub_C) + A.widen(tx, c.sub_C)) / 2
+        smooth = K.qian_wma(dev, dev.to_device(tas)).get()
+        tabs = A.egdd_tables(c.time, freq)
+        want = A.egdd(tn, tx, *tabs, method="qian", sub_C=c.sub_C, qian=smooth)
+        got = _host(K.egdd(dev, dev.to_device(tn), dev.to_device(tx), *tabs, method="qian", sub_C=c.sub_C, outputs=K.EGDD_OUTPUTS))
+        check_run(got, want, f"egdd qian {freq}")
+        assert freq != "YS" or not np.isnan(got["egdd"]).all()      # (from July on a northern cell finds its frost before its start)
+
+
+def test_warmest_month_against_the_float64_monthly_mean(dev):
+    """mtwm equals the maximum over the period's months of xh_resample_reduce_f64's monthly mean."""
+    c = golden_case("360day_f64")                       # degC fields: no offset between the two routes
+    assert c.sub_C == 0.0
+    x = dev.to_device(c.fields["tas"])
+    mo, mc, md, sm = A.month_tables(c.time, "YS")
+    got = _host(K.agro_monthly(dev, {"tas": x}, mo, mc, md, sm, hemisphere="north", sub_C=0.0, outputs=("mtwm",)))["mtwm"]
+    mean, _ = K.resample_reduce(dev, x, "mean", mo, want_valid=False)
+    mean = mean.get()
+    want = np.array([np.nanmax(mean[a:b], axis=0) for a, b in zip(sm[:-1], sm[1:])])
+    check(got, want, np.abs(want), "mtwm against the monthly mean")
+
+
+def test_bedd_icclim_without_a_cap_is_the_huglin_sum_with_k_one(dev):
+    c = golden_case("midyear_f64")
+    d = {k: dev.to_device(v) for k, v in c.fields.items()}
+    sel = select_time_mask(c.time, date_bounds=("04-01", "10-01"), include_bounds=(True, False))
+    seg = c.time.segments("YS")[0]
+    hi = _host(K.agro_degree_sum(dev, d, seg, sel, sub_C=c.sub_C, outputs=("hi", "valid")))
+    bedd = _host(K.agro_degree_sum(dev, dict(tasmin=d["tas"], tasmax=d["tasmax"]), seg, sel, sub_C=c.sub_C, tr_adj=False, max_dd=np.inf,
+                                   outputs=("bedd", "valid")))
+    check(bedd["bedd"], hi["hi"], np.abs(hi["hi"]), "bedd icclim against hi")
+    np.testing.assert_array_equal(bedd["valid"], hi["valid"])
+    assert (hi["hi"] > 100).any()
+
+
+# ---- the reference's known answers, the missing mask, the refusals ---------------------------------------------------------
+def test_known_answers_on_the_device(dev):
+    egdd = lambda t, tn, tx, m: agro.effective_growing_degree_days(tx, tn, method=m, time=t, device=dev)   # noqa: E731
+    check_known_answers(chu=lambda tn, tx: agro.corn_heat_units(tn, tx, device=dev), qian=lambda x: agro.qian_weighted_mean_average(x, device=dev),
+                        egdd=egdd, huglin=agro.huglin_day_length_latitude_coefficient, tables=False)
+
+
+@pytest.mark.parametrize("method,end_date,freq,deg_days,max_deg_days", BEDD_ANSWERS)
+def test_bedd_known_answers_on_the_device(dev, method, end_date, freq, deg_days, max_deg_days):
+    t, lat, tn, _ = bedd_inputs()
+
+    def run(method, end_date, freq, offset):
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", UserWarning)      # (icclim with lat, as the reference's test calls it)
+            return agro.biologically_effective_degree_days(tn, tn + offset, lat, method=method, end_date=end_date,
+                                                           freq=freq, time=t, device=dev).T
+
+    check_bedd(method, end_date, freq, deg_days, max_deg_days, run=run)
+
+
+def test_missing_mask_and_keep(dev):
+    c = golden_case("midyear_f64")
+    f, e = c.fields, c.expected["bedd.huglin.YS"]
+    kw = dict(method="huglin", time=c.time, device=dev)
+    m = agro.biologically_effective_degree_days(f["tasmin"], f["tasmax"], c.lat, mask_missing=True, **kw)
+    full = c.time.expected_count("YS", date_bounds=("04-01", "11-01"), include_bounds=(True, False))[:, None]
+    want = np.where(e["valid"] != full, np.nan, e["bedd"])
+    assert np.isnan(want).any() and not np.isnan(want).all()
+    check(m, want, e["bedd_scale"], "masked bedd")
+    kept = agro.biologically_effective_degree_days(f["tasmin"], f["tasmax"], c.lat, keep=True, **kw)
+    check(kept.get(), e["bedd"], e["bedd_scale"], "kept bedd")
+    with pytest.raises(ValueError, match="keep=True"):
+        agro.biologically_effective_degree_days(f["tasmin"], f["tasmax"], c.lat, keep=True, mask_missing=True, **kw)
+    assert agro.huglin_index(f["tas"][:, :0], f["tasmax"][:, :0], c.lat[:0], **kw).shape == (3, 0)
+
+
+def test_warnings_of_the_reference(dev):
+    c = golden_case("midyear_f64")
+    f = c.fields
+    with pytest.warns(DeprecationWarning, match="icclim"):
+        a = agro.huglin_index(f["tas"], f["tasmax"], c.lat, method="icclim", time=c.time, device=dev)
+    np.testing.assert_array_equal(_bits(a), _bits(agro.huglin_index(f["tas"], f["tasmax"], c.lat, method="huglin", time=c.time, device=dev)))
+    with pytest.warns(UserWarning, match="not used for method 'icclim'"):
+        agro.biologically_effective_degree_days(f["tasmin"], f["tasmax"], c.lat, method="icclim", time=c.time, device=dev)
+    with pytest.raises(NotImplementedError):
+        agro.huglin_index(f["tas"], f["tasmax"], c.lat, method="jones", freq="MS", time=c.time, device=dev)
+    with pytest.raises(agro.NotServed):         # 67.5 degrees: a polar day inside the season
+        n = golden_case("noleap_f32")
+        agro.huglin_index(n.fields["tas"], n.fields["tasmax"], n.lat, method="jones", time=n.time, device=dev)
+
+
+def test_refusals(dev):
+    refusals(dev)
+    assert RTOL == 1e-12

@@ -241,6 +241,17 @@ SIGNATURES: dict[str, list] = {
     "xh_bioclim": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _int, _i64, _vp, _vp, _int, _dbl, _dbl, _dbl,
                    _vp, _vp, _vp, _i64],
 }
+# The entry points of include/xclim_hip_agro.h (xclim_amd/csrc/agro.hip): a table of its own next to the one of the main header.
+UNIT_SIGNATURES: dict[str, list] = {
+    "xh_agro_degree_sum": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _dbl, _dbl, _dbl,
+                           _int, _dbl, _dbl, _dbl, _vp, _vp, _vp, _i64],
+    "xh_agro_monthly": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _int, _dbl, _dbl, _dbl,
+                        _vp, _vp, _vp, _vp, _i64],
+    "xh_egdd": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _dbl, _dbl, _vp, _vp, _vp, _vp,
+                _i64],
+    "xh_corn_heat_units": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _dbl, _dbl, _dbl, _vp, _i64],
+    "xh_qian_wma": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _i64],
+}
 _RESTYPES = {"xh_last_error": C.c_char_p}
 
 _lib = None
@@ -252,7 +263,8 @@ def library_path() -> str:
 
 
 def load_library() -> C.CDLL:
-    """Load libxclimhip.so and declare every prototype of include/xclim_hip.h.  Raises BackendUnavailable."""
+    """Load libxclimhip.so and declare every prototype of include/xclim_hip.h and include/xclim_hip_agro.h.  Raises
+    BackendUnavailable."""
     global _lib
     with _lib_lock:
         if _lib is not None:
@@ -266,7 +278,7 @@ def load_library() -> C.CDLL:
             lib = C.CDLL(_LIB_PATH)
         except OSError as err:  # pragma: no cover
             raise BackendUnavailable(f"cannot load {_LIB_PATH}: {err}") from err
-        for name, argtypes in SIGNATURES.items():
+        for name, argtypes in {**SIGNATURES, **UNIT_SIGNATURES}.items():
             fn = getattr(lib, name)  # AttributeError if the header and the library diverge
             fn.argtypes = argtypes
             fn.restype = _RESTYPES.get(name, _int)
@@ -677,8 +689,13 @@ class Device:
         """Invoke an entry point with this context as first argument and raise on error."""
         if self.trace is not None:  # launch log for the adapter tests: (entry point, arguments as passed)
             self.trace.append((name, args))
+        fn = getattr(self.lib, name)
+        if name in UNIT_SIGNATURES and not getattr(fn, "argtypes", None):
+            # a library object that declares the prototypes of SIGNATURES only (the host simulation's): without argtypes ctypes
+            # would pass a python int as a C int and refuse a float
+            fn.argtypes = UNIT_SIGNATURES[name]
         with self.lock:
-            _check(self.lib, getattr(self.lib, name)(self.ctx, *args))
+            _check(self.lib, fn(self.ctx, *args))
 
     def start_trace(self) -> list:
         """Record every C-ABI call made through this context from now on: returns the (growing) list of

@@ -1353,3 +1353,161 @@ def si_apply(dev: Device, x: DeviceArray, group, params: DeviceArray, dist: str,
              _vp(nzeros.ptr if nzeros is not None else 0), _vp(nnotnull.ptr if nnotnull is not None else 0), SI_DISTS[dist],
              float(alpha), float(beta), float(interp), _vp(out.ptr), C_)
     return out
+
+
+# ---- the agroclimatic heat-sum unit (include/xclim_hip_agro.h, xclim_amd/csrc/agro.hip) ------------------------------
+AGRO_DEGREE_OUTPUTS = ("hi", "bedd", "valid")
+AGRO_MONTHLY_OUTPUTS = ("cni", "mtwm", "di", "valid")
+EGDD_OUTPUTS = ("egdd", "start", "end", "valid")
+EGDD_METHODS = {"bootsma": 0, "qian": 1}
+AGRO_HEMISPHERES = {None: 0, "north": 1, "south": 2}
+
+
+def _agro_outs(dev, outputs, P, C_):
+    return {o: dev.empty((P, C_), np.int32 if o == "valid" else np.float64) for o in outputs}
+
+
+def _agro_table(who, a, dtype, n, what):
+    t = np.ascontiguousarray(a, dtype=dtype)
+    if t.shape != (n,):
+        raise ValueError(f"{who}: {what} must have {n} entries, got {t.shape}")
+    return t
+
+
+def _agro_f64(who, a, shape, what):
+    if a is None:
+        return None
+    if not isinstance(a, DeviceArray) or np.dtype(a.dtype) != np.float64 or tuple(a.shape) != shape:
+        raise TypeError(f"{who}: {what} must be a float64 {shape} device array")
+    return a
+
+
+def agro_degree_sum(dev: Device, fields: dict, seg, day_sel=None, *, k_cell: DeviceArray | None = None,
+                    k_day: DeviceArray | None = None, k_period: DeviceArray | None = None, lat_idx=None, sub_C: float = 273.15,
+                    thresh_hi: float = 10.0, thresh_bedd: float = 10.0, tr_adj: bool = True, low_dtr: float = 10.0,
+                    high_dtr: float = 13.0, max_dd: float = 9.0, outputs=("hi", "bedd")) -> dict:
+    """xh_agro_degree_sum.  ``fields``: name -> (T, C) DeviceArray, all float32 or all float64: tasmax always, tas for "hi",
+    tasmin for "bedd".  ``seg`` (P + 1) host row offsets, ``day_sel`` host bool / uint8 (T) or None.  The day factor: at most
+    one of ``k_cell`` (C) and ``k_day`` (T, L); ``k_period`` (P, L) scales the sum; ``lat_idx`` (C) host indices into the L
+    columns.  ``outputs``: a subset of hi, bedd ((P, C) float64) and valid (int32).  Returns ``{name: DeviceArray}``."""
+    who = "agro_degree_sum"
+    outputs = _subset(who, outputs, AGRO_DEGREE_OUTPUTS)
+    if not {"hi", "bedd"} & set(outputs):
+        raise ValueError(f"{who}: valid comes with hi or bedd")
+    need = ["tasmax"] + (["tas"] if "hi" in outputs else []) + (["tasmin"] if "bedd" in outputs else [])
+    for n in need:
+        if fields.get(n) is None:
+            raise TypeError(f"{who}: {n} is needed for {outputs}")
+    got = {n: fields[n] for n in need}
+    T, C_, f64 = _same_fields(who, got)
+    s = _offsets(who, seg, T)
+    P = len(s) - 1
+    if P > 65535:
+        raise ValueError(f"{who}: at most 65535 periods, got {P}")
+    if day_sel is not None:
+        m = np.asarray(day_sel)
+        if m.shape != (T,) or m.dtype not in (np.dtype(bool), np.dtype(np.uint8)):
+            raise ValueError(f"{who}: the selection must be a bool or uint8 array of length {T}")
+    if k_cell is not None and k_day is not None:
+        raise ValueError(f"{who}: at most one day factor (k_cell or k_day)")
+    L, d_li = 0, None
+    if k_day is not None or k_period is not None:
+        L = int((k_day if k_day is not None else k_period).shape[-1])
+        d_li = _pet_lat_idx(dev, lat_idx, C_, L)
+    k_cell = _agro_f64(who, k_cell, (C_,), "k_cell")
+    k_day = _agro_f64(who, k_day, (T, L), "k_day")
+    k_period = _agro_f64(who, k_period, (P, L), "k_period")
+    sel = None if day_sel is None else np.ascontiguousarray(day_sel).astype(np.uint8)
+    outs = _agro_outs(dev, outputs, P, C_)
+    dev.call("xh_agro_degree_sum", T, C_, C_, f64, *(_ptr(got, n) for n in ("tas", "tasmin", "tasmax")), P, np_ptr(s),
+             np_ptr(sel) if sel is not None else _vp(0), *(_vp(a.ptr) if a is not None else _vp(0) for a in (k_cell, k_day, k_period)),
+             L, _vp(d_li.ptr) if d_li is not None else _vp(0), float(sub_C), float(thresh_hi), float(thresh_bedd),
+             int(bool(tr_adj)), float(low_dtr), float(high_dtr), float(max_dd), *(_ptr(outs, o) for o in AGRO_DEGREE_OUTPUTS), C_)
+    return outs
+
+
+def agro_monthly(dev: Device, fields: dict, month_off, month_cal, month_days, seg_months, *, lat: DeviceArray | None = None,
+                 hemisphere: str | None = None, sub_C: float = 273.15, per_day: float = 86400.0, wo: float = 200.0,
+                 outputs=("cni", "mtwm", "di")) -> dict:
+    """xh_agro_monthly.  ``fields``: name -> (T, C) DeviceArray, one dtype: tasmin for "cni", tas for "mtwm", pr and
+    evspsblpot for "di".  Host tables: ``month_off`` (M + 1) first row of every month, ``month_cal`` / ``month_days`` (M),
+    ``seg_months`` (P + 1) first month of every period.  ``lat`` (C) float64 DeviceArray, or ``hemisphere`` "north" / "south"
+    for every cell.  ``outputs``: a subset of cni, mtwm, di ((P, C) float64) and valid (int32).  Returns ``{name:
+    DeviceArray}``; one launch."""
+    who = "agro_monthly"
+    outputs = _subset(who, outputs, AGRO_MONTHLY_OUTPUTS)
+    reads = {"cni": ("tasmin",), "mtwm": ("tas",), "di": ("pr", "evspsblpot")}
+    need = [f for o in ("cni", "mtwm", "di") if o in outputs for f in reads[o]]
+    if not need:
+        raise ValueError(f"{who}: valid comes with cni, mtwm or di")
+    for n in need:
+        if fields.get(n) is None:
+            raise TypeError(f"{who}: {n} is needed for {outputs}")
+    got = {n: fields[n] for n in need}
+    T, C_, f64 = _same_fields(who, got)
+    mo = _offsets(who, month_off, T, "month")
+    M = len(mo) - 1
+    sm = _offsets(who, seg_months, M)
+    P = len(sm) - 1
+    if P > 65535:
+        raise ValueError(f"{who}: at most 65535 periods, got {P}")
+    mc = _agro_table(who, month_cal, np.int32, M, "month_cal")
+    md = _agro_table(who, month_days, np.int32, M, "month_days")
+    if hemisphere not in AGRO_HEMISPHERES:
+        raise ValueError(f"{who}: hemisphere must be None, 'north' or 'south', got {hemisphere!r}")
+    if hemisphere is None and {"cni", "di"} & set(outputs):
+        lat = _agro_f64(who, lat, (C_,), "lat")
+        if lat is None:
+            raise TypeError(f"{who}: lat is needed unless hemisphere is given")
+    outs = _agro_outs(dev, outputs, P, C_)
+    one = np.ones(1, np.int32)
+    dev.call("xh_agro_monthly", T, C_, C_, f64, *(_ptr(got, n) for n in ("tasmin", "tas", "pr", "evspsblpot")), M, np_ptr(mo),
+             np_ptr(mc if M else one), np_ptr(md if M else one), P, np_ptr(sm), _vp(lat.ptr) if lat is not None else _vp(0),
+             AGRO_HEMISPHERES[hemisphere], float(sub_C), float(per_day), float(wo), *(_ptr(outs, o) for o in AGRO_MONTHLY_OUTPUTS), C_)
+    return outs
+
+
+def egdd(dev: Device, tasmin: DeviceArray, tasmax: DeviceArray, seg, doy, start_from, end_from, day0, label_doy, label_days, *,
+         method: str = "bootsma", sub_C: float = 273.15, thresh: float = 5.0, outputs=("egdd",)) -> dict:
+    """xh_egdd.  ``tasmin`` / ``tasmax`` (T, C) DeviceArrays of one dtype.  Host tables: ``seg`` (P + 1) row offsets, ``doy``
+    (T) day of year of every row, and per period ``start_from`` / ``end_from`` (row of the date the bound is looked for from,
+    -1 = not in the period), ``day0`` (days from the label to the first row), ``label_doy``, ``label_days``.  ``outputs``: a
+    subset of egdd, start, end ((P, C) float64) and valid (int32).  Returns ``{name: DeviceArray}``."""
+    who = "egdd"
+    outputs = _subset(who, outputs, EGDD_OUTPUTS)
+    if outputs == ["valid"]:
+        raise ValueError(f"{who}: valid comes with egdd, start or end")
+    if method not in EGDD_METHODS:
+        raise NotImplementedError(f"Method: {method}.")
+    T, C_, f64 = _same_fields(who, {"tasmin": tasmin, "tasmax": tasmax})
+    s = _offsets(who, seg, T)
+    P = len(s) - 1
+    if P > 65535:
+        raise ValueError(f"{who}: at most 65535 periods, got {P}")
+    d = _agro_table(who, doy, np.int32, T, "doy")
+    tabs = [_agro_table(who, a, dt, P, n) for a, dt, n in ((start_from, np.int64, "start_from"), (end_from, np.int64, "end_from"),
+                                                            (day0, np.int64, "day0"), (label_doy, np.int32, "label_doy"),
+                                                            (label_days, np.int32, "label_days"))]
+    outs = _agro_outs(dev, outputs, P, C_)
+    pad = lambda a: a if a.size else np.zeros(1, a.dtype)  # noqa: E731  (a pointer the entry point may check against NULL)
+    dev.call("xh_egdd", T, C_, C_, f64, _vp(tasmin.ptr), _vp(tasmax.ptr), P, np_ptr(s), np_ptr(pad(d)), *(np_ptr(pad(t)) for t in tabs),
+             EGDD_METHODS[method], float(sub_C), float(thresh), *(_ptr(outs, o) for o in EGDD_OUTPUTS), C_)
+    return outs
+
+
+def corn_heat_units(dev: Device, tasmin: DeviceArray, tasmax: DeviceArray, *, sub_C: float = 273.15, thresh_tasmin: float = 4.44,
+                    thresh_tasmax: float = 10.0) -> DeviceArray:
+    """xh_corn_heat_units: (T, C) float64 from two fields of one dtype; thresholds in degC."""
+    T, C_, f64 = _same_fields("corn_heat_units", {"tasmin": tasmin, "tasmax": tasmax})
+    out = dev.empty((T, C_), np.float64)
+    dev.call("xh_corn_heat_units", T, C_, C_, f64, _vp(tasmin.ptr), _vp(tasmax.ptr), float(sub_C), float(thresh_tasmin),
+             float(thresh_tasmax), _vp(out.ptr), C_)
+    return out
+
+
+def qian_wma(dev: Device, tas: DeviceArray) -> DeviceArray:
+    """xh_qian_wma: the five-day binomial mean (T, C) float64 of a float32 or float64 field, NaN within 2 rows of the ends."""
+    T, C_, f64 = _same_fields("qian_wma", {"tas": tas})
+    out = dev.empty((T, C_), np.float64)
+    dev.call("xh_qian_wma", T, C_, C_, f64, _vp(tas.ptr), _vp(out.ptr), C_)
+    return out

@@ -117,6 +117,7 @@ _CHILL_NAME = "_chill_portion_one_season"  # indices/_agro.py:1442-1465, called 
 # the ANUCLIM quarter and seasonality functions: public functions of _anuclim.py (:104-442) that xclim.indices re-exports
 # (indices/__init__.py: ``from ._anuclim import *``) and the anuclim.yml indicators reach through that namespace
 _ANUCLIM_MODULES = ("xclim.indices._anuclim", "xclim.indices")
+_AGRO_MODULES = ("xclim.indices._agro", "xclim.indices")   # indices/__init__.py: ``from ._agro import *``
 _PET_MODULE = "xclim.indices.converters"
 _PET_NAMES = ("potential_evapotranspiration", "water_budget")
 _PET_INDICATORS = {"xclim.indicators.convert._conversion": ("potential_evapotranspiration", "water_budget_from_tas",
@@ -270,6 +271,21 @@ def install(env=None, modules=None) -> list[str]:
                 for name in ADAPTED:
                     if m is not None and _saved.get((modname, name), getattr(m, name, None)) is origs[name]:
                         patch(modname, name, bio[name])
+    # the six period functions of the viticulture / agroclimatic unit (huglin_index ... effective_growing_degree_days): one launch
+    # each; replaced where they are defined and, by identity, where xclim.indices re-exports them.  corn_heat_units and
+    # qian_weighted_mean_average are lazy xarray expressions and stay xclim's
+    gmod = resolve(_AGRO_MODULES[0])
+    if gmod is not None:
+        from .agro import ADAPTED as AGRO_ADAPTED, make_adapters as agro_adapters
+
+        if all(hasattr(gmod, n) for n in AGRO_ADAPTED):
+            origs = {n: _saved.get((_AGRO_MODULES[0], n), getattr(gmod, n)) for n in AGRO_ADAPTED}
+            agr = agro_adapters(env, origs, getattr(gmod, "_gather_lat", None))
+            for modname in _AGRO_MODULES:
+                m = resolve(modname)
+                for name in AGRO_ADAPTED:
+                    if m is not None and _saved.get((modname, name), getattr(m, name, None)) is origs[name]:
+                        patch(modname, name, agr[name])
     cmod = resolve(_PET_MODULE)
     if cmod is not None and all(hasattr(cmod, n) for n in _PET_NAMES):
         from .converters import make_adapters as pet_adapters

@@ -252,6 +252,15 @@ UNIT_SIGNATURES: dict[str, list] = {
     "xh_corn_heat_units": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _dbl, _dbl, _dbl, _vp, _i64],
     "xh_qian_wma": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _i64],
 }
+# The entry points of include/xclim_hip_hydro.h (xclim_amd/csrc/hydro.hip): again a table of its own.
+HYDRO_SIGNATURES: dict[str, list] = {
+    "xh_flow_period_stats": [_vp, _i64, _i64, _i64, _int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64],
+    "xh_melt_period_max": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _dbl, _int, _i64, _vp, _vp, _i64],
+    "xh_antecedent_precip": [_vp, _i64, _i64, _i64, _int, _vp, _dbl, _int, _vp, _vp, _i64],
+    "xh_sen_slope": [_vp, _i64, _i64, _i64, _int, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64],
+}
+HYDRO_MAX_WINDOW = 32   # XH_HYDRO_MAX_WINDOW
+SEN_MAX_YEARS = 181     # XH_SEN_MAX_YEARS
 _RESTYPES = {"xh_last_error": C.c_char_p}
 
 _lib = None
@@ -263,7 +272,8 @@ def library_path() -> str:
 
 
 def load_library() -> C.CDLL:
-    """Load libxclimhip.so and declare every prototype of include/xclim_hip.h and include/xclim_hip_agro.h.  Raises
+    """Load libxclimhip.so and declare every prototype of include/xclim_hip.h, include/xclim_hip_agro.h and
+    include/xclim_hip_hydro.h.  Raises
     BackendUnavailable."""
     global _lib
     with _lib_lock:
@@ -278,7 +288,7 @@ def load_library() -> C.CDLL:
             lib = C.CDLL(_LIB_PATH)
         except OSError as err:  # pragma: no cover
             raise BackendUnavailable(f"cannot load {_LIB_PATH}: {err}") from err
-        for name, argtypes in {**SIGNATURES, **UNIT_SIGNATURES}.items():
+        for name, argtypes in {**SIGNATURES, **UNIT_SIGNATURES, **HYDRO_SIGNATURES}.items():
             fn = getattr(lib, name)  # AttributeError if the header and the library diverge
             fn.argtypes = argtypes
             fn.restype = _RESTYPES.get(name, _int)
@@ -690,10 +700,11 @@ class Device:
         if self.trace is not None:  # launch log for the adapter tests: (entry point, arguments as passed)
             self.trace.append((name, args))
         fn = getattr(self.lib, name)
-        if name in UNIT_SIGNATURES and not getattr(fn, "argtypes", None):
+        unit = UNIT_SIGNATURES.get(name) or HYDRO_SIGNATURES.get(name)
+        if unit is not None and not getattr(fn, "argtypes", None):
             # a library object that declares the prototypes of SIGNATURES only (the host simulation's): without argtypes ctypes
             # would pass a python int as a C int and refuse a float
-            fn.argtypes = UNIT_SIGNATURES[name]
+            fn.argtypes = unit
         with self.lock:
             _check(self.lib, fn(self.ctx, *args))
 

@@ -35,10 +35,9 @@ import numpy as np
 from . import fields as F
 from . import kernels as K
 from ._capi import get_device
-from .anuclim import _PR_UNITS
 from .calendar import select_time_mask
-from .converters import _check_time, day_angle
-from .fields import NotServed
+from .converters import day_angle
+from .fields import FLUX_UNITS as _FLUX_UNITS, NotServed, daily_axis as _axis, per_day as _per_day
 from .timeaxis import TimeAxis, _is_leap, parse_freq
 
 __all__ = ["corn_heat_units", "huglin_index", "biologically_effective_degree_days", "heat_sums", "cool_night_index",
@@ -48,7 +47,6 @@ __all__ = ["corn_heat_units", "huglin_index", "biologically_effective_degree_day
 
 KELVIN_OFFSET = 273.15  # pint's degC <-> K offset
 _SUB_C = {"K": KELVIN_OFFSET, "degC": 0.0}
-_FLUX_UNITS = ("kg m-2 s-1", "mm/s", "mm/d")
 HeatSums = namedtuple("HeatSums", ["huglin_index", "biologically_effective_degree_days"])
 
 
@@ -57,23 +55,6 @@ def _sub_c(units):
         return _SUB_C[units]
     except KeyError:
         raise ValueError(f"units must be one of {sorted(_SUB_C)}, got {units!r}") from None
-
-
-def _per_day(flux_units):
-    if flux_units not in _FLUX_UNITS:
-        raise ValueError(f"flux_units must be one of {list(_FLUX_UNITS)}, got {flux_units!r}")
-    return _PR_UNITS[flux_units][0]
-
-
-def _axis(time, T, who):
-    if not isinstance(time, TimeAxis):
-        raise TypeError("time must be the daily TimeAxis of the rows")
-    if T is not None and T != len(time):
-        raise ValueError(f"time has {len(time)} rows, the fields {T}")
-    try:
-        _check_time(time)
-    except NotServed as e:
-        raise NotServed(str(e).replace("potential evapotranspiration", who)) from None
 
 
 def _lats(lat, cell_shape, who):

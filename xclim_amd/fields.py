@@ -4,7 +4,8 @@ the time-last arrays ``xr.apply_ufunc`` hands over.
 
 float32 and float64 fields are taken as given and every other dtype is widened to float64 (exact), so nothing here depends on
 ``XCLIM_AMD_FLOAT64``; the single-field float32 indices keep ``calendar._flatten``, which carries that policy.  This module
-imports numpy and ``_capi`` only: every mirror and ``xr_adapter`` can import it.
+imports numpy and ``_capi`` only (``daily_axis`` reaches for ``converters`` when it is called): every mirror and ``xr_adapter``
+can import it.
 """
 
 from __future__ import annotations
@@ -14,9 +15,17 @@ import numpy as np
 from ._capi import DeviceArray, get_device
 
 __all__ = ["NotServed", "Forward", "SERVED", "native", "native_set", "shape_of", "rows_on_device", "per_cell", "empty_result",
-           "host_result", "time_first", "time_last"]
+           "host_result", "time_first", "time_last", "FLUX_UNITS", "FLUX_SPELLINGS", "per_day", "daily_axis"]
 
 SERVED = (np.float32, np.float64)
+
+
+# the precipitation-rate units of the daily units (agro, hydrology): the factor that makes a rate a daily amount in mm (kg m-2),
+# and the spellings of the ``units`` attribute their adapters take for them
+FLUX_UNITS = ("kg m-2 s-1", "mm/s", "mm/d")
+_FLUX_PER_DAY = {"kg m-2 s-1": 86400.0, "mm/s": 86400.0, "mm/d": 1.0}
+FLUX_SPELLINGS = {"kg m-2 s-1": "kg m-2 s-1", "kg/m2/s": "kg m-2 s-1", "mm/s": "mm/s", "mm s-1": "mm/s", "mm/d": "mm/d", "mm/day": "mm/d",
+                  "mm d-1": "mm/d", "mm day-1": "mm/d", "mm / d": "mm/d"}
 
 
 class NotServed(NotImplementedError):
@@ -26,6 +35,29 @@ class NotServed(NotImplementedError):
 
 class Forward(Exception):
     """A form an ``apply_ufunc`` callee does not take: the adapter hands the call to the reference's own function."""
+
+
+def per_day(flux_units):
+    """Seconds (or days) per day of a precipitation rate in ``flux_units``: rate * per_day = the daily amount in mm."""
+    if flux_units not in FLUX_UNITS:
+        raise ValueError(f"flux_units must be one of {list(FLUX_UNITS)}, got {flux_units!r}")
+    return _FLUX_PER_DAY[flux_units]
+
+
+def daily_axis(time, T, who):
+    """``time`` is the daily, gap-free TimeAxis of the ``T`` rows (``T`` None: any length); :class:`NotServed` for an axis that is
+    not, in the name of ``who``."""
+    from .converters import _check_time
+    from .timeaxis import TimeAxis
+
+    if not isinstance(time, TimeAxis):
+        raise TypeError("time must be the daily TimeAxis of the rows")
+    if T is not None and T != len(time):
+        raise ValueError(f"time has {len(time)} rows, the fields {T}")
+    try:
+        _check_time(time)
+    except NotServed as e:
+        raise NotServed(str(e).replace("potential evapotranspiration", who)) from None
 
 
 def native(a, name):

@@ -1511,3 +1511,85 @@ def qian_wma(dev: Device, tas: DeviceArray) -> DeviceArray:
     out = dev.empty((T, C_), np.float64)
     dev.call("xh_qian_wma", T, C_, C_, f64, _vp(tas.ptr), _vp(out.ptr), C_)
     return out
+
+
+# ---- the streamflow and snow-melt unit (include/xclim_hip_hydro.h, xclim_amd/csrc/hydro.hip) -------------------------
+FLOW_OUTPUTS = ("bfi", "rbi", "mean", "sum", "valid")
+SEN_OUTPUTS = ("slope", "p", "n")
+
+
+def _hydro_window(who, window):
+    if not isinstance(window, (int, np.integer)) or isinstance(window, bool) or window < 1:
+        raise ValueError(f"{who}: window must be an integer of at least 1, got {window!r}")
+    if window > capi.HYDRO_MAX_WINDOW:
+        raise ValueError(f"{who}: windows of up to {capi.HYDRO_MAX_WINDOW} rows are served, got {window}")
+    return int(window)
+
+
+def flow_period_stats(dev: Device, q: DeviceArray, seg, outputs=("bfi", "rbi")) -> dict:
+    """xh_flow_period_stats.  ``q`` (T, C) float32 or float64 DeviceArray, ``seg`` (P + 1) host row offsets.  ``outputs``: a
+    subset of bfi, rbi, mean, sum ((P, C) float64) and valid (int32).  Returns ``{name: DeviceArray}``; one launch."""
+    who = "flow_period_stats"
+    outputs = _subset(who, outputs, FLOW_OUTPUTS)
+    T, C_, f64 = _same_fields(who, {"q": q})
+    s = _offsets(who, seg, T)
+    P = len(s) - 1
+    if P > 65535:
+        raise ValueError(f"{who}: at most 65535 periods, got {P}")
+    outs = _agro_outs(dev, outputs, P, C_)
+    dev.call("xh_flow_period_stats", T, C_, C_, f64, _vp(q.ptr), P, np_ptr(s), *(_ptr(outs, o) for o in FLOW_OUTPUTS), C_)
+    return outs
+
+
+def melt_period_max(dev: Device, snw: DeviceArray, seg, pr: DeviceArray | None = None, *, window: int = 3,
+                    per_day: float = 86400.0) -> DeviceArray:
+    """xh_melt_period_max: the period maximum of the ``window``-row sums of ``pr * per_day - diff(snw)`` (without ``pr``: of
+    ``-diff(snw)``), (P, C) float64.  ``snw`` / ``pr`` (T, C) DeviceArrays of one dtype."""
+    who = "melt_period_max"
+    T, C_, f64 = _same_fields(who, {"snw": snw, "pr": pr} if pr is not None else {"snw": snw})
+    s = _offsets(who, seg, T)
+    P = len(s) - 1
+    if P > 65535:
+        raise ValueError(f"{who}: at most 65535 periods, got {P}")
+    window = _hydro_window(who, window)
+    out = dev.empty((P, C_), np.float64)
+    dev.call("xh_melt_period_max", T, C_, C_, f64, _vp(snw.ptr), _vp(pr.ptr) if pr is not None else _vp(0), float(per_day), window, P,
+             np_ptr(s), _vp(out.ptr), C_)
+    return out
+
+
+def antecedent_precip(dev: Device, pr: DeviceArray, weights, *, per_day: float = 86400.0) -> DeviceArray:
+    """xh_antecedent_precip: the trailing weighted sum ``sum_k weights[k] * (pr[i - window + 1 + k] * per_day)`` with
+    ``window = len(weights)``, (T, C) float64, NaN until the window is full."""
+    who = "antecedent_precip"
+    T, C_, f64 = _same_fields(who, {"pr": pr})
+    w = np.ascontiguousarray(weights, dtype=np.float64)
+    if w.ndim != 1:
+        raise ValueError(f"{who}: weights must be one-dimensional")
+    window = _hydro_window(who, len(w))
+    out = dev.empty((T, C_), np.float64)
+    dev.call("xh_antecedent_precip", T, C_, C_, f64, _vp(pr.ptr), float(per_day), window, np_ptr(w), _vp(out.ptr), C_)
+    return out
+
+
+def sen_slope(dev: Device, x: DeviceArray, period_of, outputs=("slope", "p")) -> dict:
+    """xh_sen_slope.  ``x`` (P, C) float32 or float64 DeviceArray of period values; ``period_of`` host int (Y, K): the row of
+    ``x`` of year y of season k, -1 for none.  ``outputs``: a subset of slope, p ((K, C) float64) and n (int32, the values
+    used).  Returns ``{name: DeviceArray}``; one launch."""
+    who = "sen_slope"
+    outputs = _subset(who, outputs, SEN_OUTPUTS)
+    if outputs == ["n"]:
+        raise ValueError(f"{who}: n comes with slope or p")
+    P, C_, f64 = _same_fields(who, {"x": x})
+    po = np.ascontiguousarray(period_of, dtype=np.int64)
+    if po.ndim != 2:
+        raise ValueError(f"{who}: period_of must be a (years, seasons) table")
+    Y, K_ = po.shape
+    if Y > capi.SEN_MAX_YEARS:
+        raise ValueError(f"{who}: series of up to {capi.SEN_MAX_YEARS} years are served, got {Y}")
+    if po.size and (po.min() < -1 or po.max() >= P):
+        raise ValueError(f"{who}: period_of must hold rows of x (0 .. {P - 1}) or -1")
+    outs = {o: dev.empty((K_, C_), np.int32 if o == "n" else np.float64) for o in outputs}
+    dev.call("xh_sen_slope", P, C_, C_, f64, _vp(x.ptr), Y, K_, np_ptr(po if po.size else np.full(1, -1, np.int64)),
+             *(_ptr(outs, o) for o in SEN_OUTPUTS), C_)
+    return outs

@@ -118,6 +118,7 @@ _CHILL_NAME = "_chill_portion_one_season"  # indices/_agro.py:1442-1465, called 
 # (indices/__init__.py: ``from ._anuclim import *``) and the anuclim.yml indicators reach through that namespace
 _ANUCLIM_MODULES = ("xclim.indices._anuclim", "xclim.indices")
 _AGRO_MODULES = ("xclim.indices._agro", "xclim.indices")   # indices/__init__.py: ``from ._agro import *``
+_HYDRO_MODULES = ("xclim.indices._hydrology", "xclim.indices")   # indices/__init__.py: ``from ._hydrology import *``
 _PET_MODULE = "xclim.indices.converters"
 _PET_NAMES = ("potential_evapotranspiration", "water_budget")
 _PET_INDICATORS = {"xclim.indicators.convert._conversion": ("potential_evapotranspiration", "water_budget_from_tas",
@@ -286,6 +287,22 @@ def install(env=None, modules=None) -> list[str]:
                 for name in AGRO_ADAPTED:
                     if m is not None and _saved.get((modname, name), getattr(m, name, None)) is origs[name]:
                         patch(modname, name, agr[name])
+    # the streamflow and snow-melt functions of _hydrology.py (base_flow_index ... base_flow_index_seasonal_ratio): replaced where
+    # they are defined and, by identity, where xclim.indices re-exports them; sen_slope also where pymannkendall is absent (it no
+    # longer needs it).  runoff_ratio is unit conversion around two means and stays xclim's, as do lag_snowpack_flow_peaks and
+    # the snd_max / snw_max family (select_resample_op, served by the generic wrappers)
+    hmod = resolve(_HYDRO_MODULES[0])
+    if hmod is not None:
+        from .hydrology import ADAPTED as HYDRO_ADAPTED, make_adapters as hydro_adapters
+
+        if all(hasattr(hmod, n) for n in HYDRO_ADAPTED):
+            origs = {n: _saved.get((_HYDRO_MODULES[0], n), getattr(hmod, n)) for n in HYDRO_ADAPTED}
+            hyd = hydro_adapters(env, origs)
+            for modname in _HYDRO_MODULES:
+                m = resolve(modname)
+                for name in HYDRO_ADAPTED:
+                    if m is not None and _saved.get((modname, name), getattr(m, name, None)) is origs[name]:
+                        patch(modname, name, hyd[name])
     cmod = resolve(_PET_MODULE)
     if cmod is not None and all(hasattr(cmod, n) for n in _PET_NAMES):
         from .converters import make_adapters as pet_adapters

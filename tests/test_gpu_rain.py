@@ -1,0 +1,235 @@
+"""The rain-season and hardiness-zone unit on the device (xclim_amd/csrc/rainseason.hip, xclim_amd.rainseason) against
+tests/golden/rain_vectors.npz, the values of the numpy restatement tests/raincpu.py: every family of decisions, the sum windows
+at 1, 2 and 32, all four method combinations, float32 and float64 fields, one period and three (a leap year, a short last one, a
+July year), 1 to 257 cells, every subset of the outputs, padded and poisoned row views; the host mirrors bit for bit against the
+kernel calls; the refusals.  Every test runs on poisoned output buffers, and after every call of an entry point no output element
+may still hold the poison (tests/unwritten.py: watch, on the operand table of tests/test_rain_cpu.py).
+
+Every result is an integer or NaN and every comparison is ``assert_array_equal``: the built amounts lie on a 0.25 mm grid (every
+window sum is exact in any order and precision), and the random float32 fields keep 1e-6 relative between every sum and its
+threshold, which is asserted when they are loaded."""
+
+import numpy as np
+import pytest
+
+import raincpu as R
+import stridedabi as S
+import unwritten as U
+from test_rain_cpu import (CASES, HEADER, META, OUTPUTS, RAIN_TABLE, ZONE_CASES, _Z, check_known_answers, golden_case, golden_time, mirror_api,
+                           refusals, same)
+from xclim_amd import kernels as K
+from xclim_amd import rainseason
+from xclim_amd.timeaxis import TimeAxis
+from poisoned import poisoned_outputs  # noqa: F401  (autouse: the tests of this module that use the device run on poisoned output buffers)
+
+pytestmark = pytest.mark.gpu
+CELLS = (1, 63, 64, 65, 257)       # one lane, a wave less one, a wave, a wave and one, more than two workgroups of 128
+
+
+@pytest.fixture(autouse=True)
+def watched(request, monkeypatch):
+    """The operand table of the new header joins stridedabi's for the duration of a test, and every call of an entry point through
+    ``dev.call`` is followed by the check that it wrote every element of its outputs."""
+    protos = S.prototypes(HEADER)
+    for name, ops in RAIN_TABLE.items():
+        monkeypatch.setitem(S.TABLE, name, ops)
+        monkeypatch.setitem(S.PROTOS, name, protos[name])
+    if "dev" not in request.fixturenames:
+        yield None
+        return
+    with U.watch(request.getfixturevalue("dev"), monkeypatch) as log:
+        yield log
+
+
+def launch(dev, name, cells=None, outputs=OUTPUTS):
+    """One case through kernels.py on its own columns, or tiled to ``cells`` columns: ({output: array}, {output: expected})."""
+    m, pr, seg, flags, doy, exp = golden_case(name)
+    idx = np.arange(pr.shape[1] if cells is None else cells) % pr.shape[1]
+    outs = K.rain_season(dev, dev.to_device(np.ascontiguousarray(pr[:, idx])), seg, flags, doy, per_day=R.PER_DAY[m["flux_units"]],
+                         outputs=outputs, **m["params"])
+    return {k: v.get() for k, v in outs.items()}, {k: exp[k][:, idx] for k in outputs}
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_golden_cases(dev, name):
+    m = META[name]
+    if "random" in m["family"]:
+        _, pr, seg, flags, _, _ = golden_case(name)
+        assert (R.margin(pr, seg, flags, m["flux_units"], **m["params"]) > 1e-6).all()
+    got, want = launch(dev, name)
+    assert list(got) == list(OUTPUTS)
+    for k in OUTPUTS:
+        same(got[k], want[k], f"{name} {k}")
+    if m["dates"] is not None:      # the mirror: flags from the dates, one launch, the same bits
+        _, pr, seg, flags, _, _ = golden_case(name)
+        r = rainseason.rain_season(pr, freq=m["time"]["freq"], time=golden_time(m, len(flags)), flux_units=m["flux_units"], device=dev,
+                                   **m["params"], **m["dates"])
+        for k, v in zip(OUTPUTS, r):
+            same(v, want[k], f"{name} {k}: mirror")
+
+
+@pytest.mark.parametrize("cells", CELLS)
+@pytest.mark.parametrize("name", ["built.default", "built.total.total", "built.all32.total", "built.wd33.per_day", "random.july"])
+def test_cell_counts(dev, name, cells):
+    """float64 and float32 fields, three periods, both rings and the second read of the decision row, at every cell count."""
+    got, want = launch(dev, name, cells)
+    for k in OUTPUTS:
+        same(got[k], want[k], f"{name} C={cells} {k}")
+
+
+@pytest.mark.parametrize("name", ["built.per_day.total", "built.total.per_day"])
+def test_every_subset_of_the_outputs_equals_the_full_launch(dev, name):
+    full, _ = launch(dev, name, 65)
+    for mask in range(1, 8):
+        names = [o for i, o in enumerate(OUTPUTS) if mask >> i & 1]
+        got, _ = launch(dev, name, 65, names)
+        assert list(got) == names
+        for k in names:
+            same(got[k], full[k], f"{name} {names}: {k}")
+
+
+def test_the_other_precision_gives_the_same_answers(dev):
+    """The built amounts are exact in float32 and float64: a float32 copy of a float64 case (and the reverse) has the same answers;
+    so has the field in kg m-2 s-1 ... as long as the division by 86400 is undone exactly, which a power of two guarantees."""
+    for name in ("built.per_day.per_day", "built.total.total", "same_row"):
+        m, pr, seg, flags, doy, exp = golden_case(name)
+        other = np.float32 if pr.dtype == np.float64 else np.float64
+        for field, per_day in ((pr.astype(other), 1.0), (pr / 64.0, 64.0), ((pr / 64.0).astype(other), 64.0)):
+            outs = K.rain_season(dev, dev.to_device(np.ascontiguousarray(field)), seg, flags, doy, per_day=per_day, **m["params"])
+            for k in OUTPUTS:
+                same(outs[k].get(), exp[k], f"{name} {field.dtype} per_day={per_day} {k}")
+
+
+def test_empty_periods_and_no_cells(dev):
+    m, pr, seg, flags, doy, exp = golden_case("built.per_day.per_day")
+    seg2 = np.array([0, 0, seg[1], seg[1], seg[2], seg[3], seg[3]])
+    outs = K.rain_season(dev, dev.to_device(pr), seg2, flags, doy, per_day=1.0, **m["params"])
+    for k in OUTPUTS:
+        got = outs[k].get()
+        assert np.isnan(got[[0, 2, 5]]).all()
+        same(got[[1, 3, 4]], exp[k], f"empty periods {k}")
+    t = golden_time(m, len(flags))
+    r = rainseason.rain_season(pr[:, :0], freq="YS-JUL", time=t, flux_units="mm/d", device=dev, **m["params"], **m["dates"])
+    assert all(v.shape == (3, 0) for v in r)
+
+
+# ---- xh_rolling_zones and hardiness_zones -----------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", [np.float64, np.float32], ids=["float64", "float32"])
+@pytest.mark.parametrize("name", ZONE_CASES)
+def test_zones_on_every_edge(dev, name, dtype):
+    """31 periods; a value on every bin edge, one ulp above and below it, the two outer edges, far outside, NaN, a NaN period
+    inside a window; windows 1, 2 and 30.  A float32 field is its own case: the restatement widens the same float32 values."""
+    method, units = name.split(".")[1:]
+    e = R.zone_edges(method, units)
+    x = _Z[f"{name}/x"].astype(dtype)
+    for w in (1, 2, 30):
+        got = K.rolling_zones(dev, dev.to_device(x), w, e).get()
+        same(got, _Z[f"{name}/w{w}"] if dtype == np.float64 else R.rolling_zones(x, w, e), f"{name} window {w}")
+        assert np.isnan(got[:w - 1]).all() and not np.isnan(got[w - 1:]).all()
+
+
+@pytest.mark.parametrize("cells", CELLS)
+def test_zones_cell_counts_and_a_window_longer_than_the_series(dev, cells):
+    x = _Z["zones.usda.degC/x"]
+    idx = np.arange(cells) % x.shape[1]
+    e = R.zone_edges("usda", "degC")
+    xs = np.ascontiguousarray(x[:, idx])
+    same(K.rolling_zones(dev, dev.to_device(xs), 30, e).get(), _Z["zones.usda.degC/w30"][:, idx], f"C={cells}")
+    assert np.isnan(K.rolling_zones(dev, dev.to_device(xs), 32, e).get()).all()
+    same(K.rolling_zones(dev, dev.to_device(xs[:1]), 1, e).get(), _Z["zones.usda.degC/w1"][:1, idx], "one period")
+
+
+@pytest.mark.parametrize("dtype,units", [(np.float64, "K"), (np.float32, "degC")])
+def test_hardiness_zones_of_the_mirror(dev, dtype, units):
+    """The period minimum in the field's dtype (xh_resample_reduce / its float64 twin), then xh_rolling_zones: two launches."""
+    t = TimeAxis.daily("1990-01-01", 365 * 12 + 3)
+    rng = np.random.default_rng(5)
+    base = 285.0 if units == "K" else 12.0
+    x = (base + 14 * np.cos(2 * np.pi * t.doy / 365.25)[:, None] + rng.normal(0, 6, (len(t), 65)) + np.linspace(-25, 20, 65)).astype(dtype)
+    x[400:420, 3] = np.nan
+    x[:, 4] = np.nan
+    for method, window, freq in (("usda", 5, "YS"), ("anbg", 3, "YS-JUL"), ("usda", 1, "YS")):
+        trace = dev.start_trace()
+        try:
+            got = rainseason.hardiness_zones(x, window, method, freq, time=t, units=units, device=dev)
+        finally:
+            dev.stop_trace()
+        assert [n for n, _ in trace if n.startswith("xh_")] == ["xh_resample_reduce_f64" if dtype == np.float64 else "xh_resample_reduce", "xh_rolling_zones"]
+        want = R.hardiness_zones(x, t, window, method, freq, units)
+        same(got, want, f"{method} {window} {freq}")
+        assert np.isnan(got[:, 4]).all() and 0 < np.isnan(got[window - 1:]).sum() < got[window - 1:].size
+    kept = rainseason.hardiness_zones(x, 5, time=t, units=units, device=dev, keep=True)
+    same(kept.get(), R.hardiness_zones(x, t, 5, "usda", "YS", units), "kept")
+    assert rainseason.hardiness_zones(x[:, :0], time=t, units=units, device=dev).shape == (len(t.segments("YS")[0]) - 1, 0)
+
+
+# ---- padded, poisoned row views ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,C,pitch", [("built.total.total", 65, 80), ("built.wd33.per_day", 130, 144), ("built.default", 65, 96)])
+def test_padded_views_give_the_same_bits(dev, monkeypatch, name, C, pitch):
+    """Every strided operand of the two entry points in rows of `pitch` elements, NaN / 1e30 in the extra columns of the inputs and
+    in front of their first row, 0xA5 bytes in those of the outputs (tests/stridedabi.py: padded, which asserts that they stay)."""
+    for entry, ops in RAIN_TABLE.items():
+        for op in ops:
+            assert {op.ptr, op.stride} <= set(S.PROTOS[entry]), (entry, op)
+    e = R.zone_edges("usda", "degC")
+    x = np.ascontiguousarray(_Z["zones.usda.degC/x"][:, np.arange(C) % 40]).astype(np.float32 if C == 130 else np.float64)
+
+    def run():
+        out, _ = launch(dev, name, C)
+        out["zones"] = K.rolling_zones(dev, dev.to_device(x), 2, e).get()
+        return out
+
+    plain = run()
+    with S.padded(dev, monkeypatch, pads=(pitch - C, pitch - C), shift=5) as log:
+        got = run()
+    assert set(got) == set(plain) and len(got) == 4
+    for k, g in got.items():
+        same(g, plain[k], f"{k} differs under row pitches {log}")
+    assert [n for n, _ in log] == list(RAIN_TABLE)
+    assert all(used == {"ld": (pitch, C), "ld_out": (pitch, C)} for _, used in log), log
+
+
+def test_every_output_operand_was_armed_and_checked(dev, watched):
+    """The watch of this module sees the outputs of both entry points poisoned before the call (they come from Device.empty under
+    the fixture) and written after it."""
+    launch(dev, "built.per_day.per_day", 65)
+    K.rolling_zones(dev, dev.to_device(_Z["zones.anbg.K/x"]), 2, R.zone_edges("anbg", "K"))
+    seen = {n: armed for n, armed in watched if n in RAIN_TABLE}
+    assert set(seen) == set(RAIN_TABLE)
+    for name, armed in seen.items():
+        assert set(armed) == {op.ptr for op in RAIN_TABLE[name] if op.mode == "w"} and all(armed.values()), (name, armed)
+
+
+# ---- the reference's known answers, the missing mask, the refusals ---------------------------------------------------------
+def test_known_answers_on_the_device(dev):
+    check_known_answers(mirror_api(dev))
+
+
+def test_missing_mask_keep_and_limits(dev):
+    m, pr, seg, flags, doy, exp = golden_case("built.per_day.per_day")
+    t = golden_time(m, len(flags))
+    kw = dict(freq="YS-JUL", time=t, flux_units="mm/d", device=dev, **m["params"], **m["dates"])
+    full = pr.copy()
+    full[np.isnan(full)] = 7.5          # (a value that is neither wet nor dry: only the count of present rows changes)
+    full[5, 1] = np.nan
+    plain = rainseason.rain_season(full, **kw)
+    masked = rainseason.rain_season(full, mask_missing=True, **kw)
+    assert not np.isnan(plain.rain_season_start[:, 1]).all()
+    for a, b in zip(plain, masked):
+        assert np.isnan(b[-1]).all() and np.isnan(b[0, 1])                  # the partial last year; the period with a NaN row
+        same(b[:2, 2:], a[:2, 2:], "complete periods are kept")
+    kept = rainseason.rain_season(pr, keep=True, **kw)
+    for k, v in zip(OUTPUTS, kept):
+        same(v.get(), exp[k], f"kept {k}")
+    with pytest.raises(ValueError, match="up to 32"):          # kernels.py refuses before the call; the mirror says NotServed
+        K.rain_season(dev, dev.to_device(pr), seg, flags, doy, window_wet_start=33)
+    with pytest.raises(ValueError, match="up to 32"):
+        K.rain_season(dev, dev.to_device(pr), seg, flags, doy, window_dry_end=33, method_dry_end="total")
+    with pytest.raises(ValueError, match="Unknown method_dry_start: weekly."):
+        K.rain_season(dev, dev.to_device(pr), seg, flags, doy, method_dry_start="weekly")
+    with pytest.raises(ValueError, match="at most 32 bin edges"):
+        K.rolling_zones(dev, dev.to_device(pr), 2, np.arange(33.0))
+
+
+def test_refusals(dev):
+    refusals(dev)

@@ -261,6 +261,15 @@ HYDRO_SIGNATURES: dict[str, list] = {
 }
 HYDRO_MAX_WINDOW = 32   # XH_HYDRO_MAX_WINDOW
 SEN_MAX_YEARS = 181     # XH_SEN_MAX_YEARS
+# The entry points of include/xclim_hip_rain.h (xclim_amd/csrc/rainseason.hip): a table of its own as well.
+RAIN_SIGNATURES: dict[str, list] = {
+    "xh_rain_season": [_vp, _i64, _i64, _i64, _int, _vp, _dbl, _i64, _vp, _vp, _vp, _dbl, _int, _int, _dbl, _int, _int, _dbl, _int, _int,
+                       _vp, _vp, _vp, _i64],
+    "xh_rolling_zones": [_vp, _i64, _i64, _i64, _int, _vp, _int, _i64, _vp, _vp, _i64],
+}
+RAIN_MAX_WINDOW = 32    # XH_RAIN_MAX_WINDOW
+ZONES_MAX_EDGES = 32    # XH_ZONES_MAX_EDGES
+RAIN_START_WINDOW, RAIN_START_BOUNDS, RAIN_END_BOUNDS = 1, 2, 4   # the XH_RAIN_* flag bits
 _RESTYPES = {"xh_last_error": C.c_char_p}
 
 _lib = None
@@ -272,8 +281,8 @@ def library_path() -> str:
 
 
 def load_library() -> C.CDLL:
-    """Load libxclimhip.so and declare every prototype of include/xclim_hip.h, include/xclim_hip_agro.h and
-    include/xclim_hip_hydro.h.  Raises
+    """Load libxclimhip.so and declare every prototype of include/xclim_hip.h, include/xclim_hip_agro.h,
+    include/xclim_hip_hydro.h and include/xclim_hip_rain.h.  Raises
     BackendUnavailable."""
     global _lib
     with _lib_lock:
@@ -288,7 +297,7 @@ def load_library() -> C.CDLL:
             lib = C.CDLL(_LIB_PATH)
         except OSError as err:  # pragma: no cover
             raise BackendUnavailable(f"cannot load {_LIB_PATH}: {err}") from err
-        for name, argtypes in {**SIGNATURES, **UNIT_SIGNATURES, **HYDRO_SIGNATURES}.items():
+        for name, argtypes in {**SIGNATURES, **UNIT_SIGNATURES, **HYDRO_SIGNATURES, **RAIN_SIGNATURES}.items():
             fn = getattr(lib, name)  # AttributeError if the header and the library diverge
             fn.argtypes = argtypes
             fn.restype = _RESTYPES.get(name, _int)
@@ -700,7 +709,7 @@ class Device:
         if self.trace is not None:  # launch log for the adapter tests: (entry point, arguments as passed)
             self.trace.append((name, args))
         fn = getattr(self.lib, name)
-        unit = UNIT_SIGNATURES.get(name) or HYDRO_SIGNATURES.get(name)
+        unit = UNIT_SIGNATURES.get(name) or HYDRO_SIGNATURES.get(name) or RAIN_SIGNATURES.get(name)
         if unit is not None and not getattr(fn, "argtypes", None):
             # a library object that declares the prototypes of SIGNATURES only (the host simulation's): without argtypes ctypes
             # would pass a python int as a C int and refuse a float

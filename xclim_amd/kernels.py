@@ -1593,3 +1593,64 @@ def sen_slope(dev: Device, x: DeviceArray, period_of, outputs=("slope", "p")) ->
     dev.call("xh_sen_slope", P, C_, C_, f64, _vp(x.ptr), Y, K_, np_ptr(po if po.size else np.full(1, -1, np.int64)),
              *(_ptr(outs, o) for o in SEN_OUTPUTS), C_)
     return outs
+
+
+# ---- the rain-season and hardiness-zone unit (include/xclim_hip_rain.h, xclim_amd/csrc/rainseason.hip) ---------------
+RAIN_OUTPUTS = ("start", "end", "length")
+RAIN_METHODS = ("per_day", "total")
+
+
+def _rain_window(who, name, window, least=1):
+    if not isinstance(window, (int, np.integer)) or isinstance(window, bool) or window < least:
+        raise ValueError(f"{who}: {name} must be an integer of at least {least}, got {window!r}")
+    return int(window)
+
+
+def rain_season(dev: Device, pr: DeviceArray, seg, flags, doy, *, per_day: float = 86400.0, thresh_wet_start: float = 25.0,
+                window_wet_start: int = 3, window_not_dry_start: int = 30, thresh_dry_start: float = 1.0, window_dry_start: int = 7,
+                method_dry_start: str = "per_day", thresh_dry_end: float = 0.0, window_dry_end: int = 20,
+                method_dry_end: str = "per_day", outputs=RAIN_OUTPUTS) -> dict:
+    """xh_rain_season.  ``pr`` (T, C) float32 or float64 DeviceArray, ``seg`` (P + 1) host row offsets, ``flags`` host uint8 (T)
+    of the ``capi.RAIN_*`` bits, ``doy`` host int (T).  Thresholds in mm per day of ``pr * per_day``.  ``outputs``: a subset of
+    start, end (day of year) and length (days), (P, C) float64 with NaN.  Returns ``{name: DeviceArray}``; one launch."""
+    who = "rain_season"
+    outputs = _subset(who, outputs, RAIN_OUTPUTS)
+    T, C_, f64 = _same_fields(who, {"pr": pr})
+    s = _offsets(who, seg, T)
+    P = len(s) - 1
+    if P > 65535:
+        raise ValueError(f"{who}: at most 65535 periods, got {P}")
+    for name, m in (("method_dry_start", method_dry_start), ("method_dry_end", method_dry_end)):
+        if m not in RAIN_METHODS:
+            raise ValueError(f"Unknown {name}: {m}.")
+    ww = _rain_window(who, "window_wet_start", window_wet_start)
+    wnd = _rain_window(who, "window_not_dry_start", window_not_dry_start, 0)
+    wd = _rain_window(who, "window_dry_start", window_dry_start)
+    we = _rain_window(who, "window_dry_end", window_dry_end)
+    sums = [ww] + [w for w, m in ((wd, method_dry_start), (we, method_dry_end)) if m == "total"]
+    if max(sums) > capi.RAIN_MAX_WINDOW:
+        raise ValueError(f"{who}: sum windows of up to {capi.RAIN_MAX_WINDOW} rows are served, got {max(sums)}")
+    fl = _agro_table(who, flags, np.uint8, T, "flags")
+    dy = _agro_table(who, doy, np.int32, T, "doy")
+    outs = {o: dev.empty((P, C_), np.float64) for o in outputs}
+    dev.call("xh_rain_season", T, C_, C_, f64, _vp(pr.ptr), float(per_day), P, np_ptr(s), np_ptr(fl), np_ptr(dy), float(thresh_wet_start), ww,
+             wnd, float(thresh_dry_start), wd, int(method_dry_start == "total"), float(thresh_dry_end), we, int(method_dry_end == "total"),
+             *(_ptr(outs, o) for o in RAIN_OUTPUTS), C_)
+    return outs
+
+
+def rolling_zones(dev: Device, x: DeviceArray, window: int, edges) -> DeviceArray:
+    """xh_rolling_zones: the zone (``np.digitize(mean, edges) - 1``, the last zone closed on the right, NaN outside the edges) of
+    the mean of the last ``window`` rows of ``x`` (P, C) float32 or float64; (P, C) float64, NaN for the first ``window - 1``
+    rows."""
+    who = "rolling_zones"
+    P, C_, f64 = _same_fields(who, {"x": x})
+    window = _rain_window(who, "window", window)
+    e = np.ascontiguousarray(edges, dtype=np.float64)
+    if e.ndim != 1 or len(e) < 2 or not np.all(np.diff(e) > 0):
+        raise ValueError(f"{who}: at least two strictly increasing bin edges")
+    if len(e) > capi.ZONES_MAX_EDGES:
+        raise ValueError(f"{who}: at most {capi.ZONES_MAX_EDGES} bin edges, got {len(e)}")
+    out = dev.empty((P, C_), np.float64)
+    dev.call("xh_rolling_zones", P, C_, C_, f64, _vp(x.ptr), window, len(e), np_ptr(e), _vp(out.ptr), C_)
+    return out

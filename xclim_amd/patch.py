@@ -287,6 +287,18 @@ def install(env=None, modules=None) -> list[str]:
                 for name in AGRO_ADAPTED:
                     if m is not None and _saved.get((modname, name), getattr(m, name, None)) is origs[name]:
                         patch(modname, name, agr[name])
+        # rain_season and hardiness_zones, the last two functions of _agro.py (xclim_amd.rainseason): one launch of xh_rain_season;
+        # the period minimum + xh_rolling_zones.  Replaced only where both are present
+        from .rainseason import ADAPTED as RAIN_ADAPTED, make_adapters as rain_adapters
+
+        if all(hasattr(gmod, n) for n in RAIN_ADAPTED):
+            origs = {n: _saved.get((_AGRO_MODULES[0], n), getattr(gmod, n)) for n in RAIN_ADAPTED}
+            rain = rain_adapters(env, origs)
+            for modname in _AGRO_MODULES:
+                m = resolve(modname)
+                for name in RAIN_ADAPTED:
+                    if m is not None and _saved.get((modname, name), getattr(m, name, None)) is origs[name]:
+                        patch(modname, name, rain[name])
     # the streamflow and snow-melt functions of _hydrology.py (base_flow_index ... base_flow_index_seasonal_ratio): replaced where
     # they are defined and, by identity, where xclim.indices re-exports them; sen_slope also where pymannkendall is absent (it no
     # longer needs it).  runoff_ratio is unit conversion around two means and stays xclim's, as do lag_snowpack_flow_peaks and

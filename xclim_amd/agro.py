@@ -37,7 +37,7 @@ from . import kernels as K
 from ._capi import get_device
 from .calendar import select_time_mask
 from .converters import day_angle
-from .fields import FLUX_UNITS as _FLUX_UNITS, NotServed, daily_axis as _axis, per_day as _per_day
+from .fields import KELVIN_OFFSET, NotServed, daily_axis as _axis, per_day as _per_day
 from .timeaxis import TimeAxis, _is_leap, parse_freq
 
 __all__ = ["corn_heat_units", "huglin_index", "biologically_effective_degree_days", "heat_sums", "cool_night_index",
@@ -45,7 +45,6 @@ __all__ = ["corn_heat_units", "huglin_index", "biologically_effective_degree_day
            "huglin_day_length_latitude_coefficient", "gladstones_day_length_latitude_coefficient",
            "jones_day_length_latitude_coefficient", "month_tables", "egdd_tables", "HeatSums", "NotServed"]
 
-KELVIN_OFFSET = 273.15  # pint's degC <-> K offset
 _SUB_C = {"K": KELVIN_OFFSET, "degC": 0.0}
 HeatSums = namedtuple("HeatSums", ["huglin_index", "biologically_effective_degree_days"])
 
@@ -159,19 +158,16 @@ def _finish(outs, names, valid_expected, P, cell_shape, keep):
     if keep:
         return {n: outs[n] for n in names}
     res = F.host_result({n: outs[n] for n in list(names) + (["valid"] if valid_expected is not None else [])}, P, cell_shape)
-    if valid_expected is not None:
-        bad = res.pop("valid") != np.asarray(valid_expected).reshape((P,) + (1,) * len(cell_shape))
-        for n in names:
-            res[n][bad] = np.nan
-    return res
+    if valid_expected is None:
+        return res
+    valid = res.pop("valid")
+    return F.mask_incomplete(res, valid, valid_expected)
 
 
 def _degree(names, fields, lat, time, factor, cap_value, tr_adj, thresh_hi, thresh_bedd, low_dtr, high_dtr, max_dd, start_date,
             end_date, freq, units, device, keep, mask_missing, who):
-    if not isinstance(freq, str):
-        raise TypeError("Freq must be a string.")
-    if keep and mask_missing:
-        raise ValueError("keep=True returns the device arrays as computed: pass mask_missing=False")
+    F.check_freq(freq)
+    F.no_keep_with_mask(keep, mask_missing)
     sub_C = _sub_c(units)
     got = F.native_set(fields)
     T, cell_shape, C_ = F.shape_of(got)
@@ -212,8 +208,7 @@ def huglin_index(tas, tasmax, lat=None, thresh: float = 10.0, method: str = "smo
     """_agro.py:151-263: the sum over the season of ``max((tas + tasmax) / 2 - thresh, 0) * k``, float64 ``(P, *cells)``.
     ``method``: "huglin" / "icclim" (deprecated, the same) / "interpolated" (k per cell from |lat|, ``cap_value`` beyond 50
     degrees) or "jones" (k per period and latitude).  ``lat`` [degrees north] broadcasts to the cells."""
-    if not isinstance(freq, str):
-        raise TypeError("Freq must be a string.")
+    F.check_freq(freq)
     method = method.lower()
     if method == "icclim":
         warnings.warn("Method 'icclim' is deprecated. Use 'stepwise' instead.", DeprecationWarning, stacklevel=2)
@@ -233,8 +228,7 @@ def biologically_effective_degree_days(tasmin, tasmax, lat=None, thresh_tasmin: 
     max_daily_degree_days)``, float64 ``(P, *cells)`` [K days].  ``method``: "gladstones" (k per day and latitude), "huglin" /
     "interpolated" (k per cell), "jones" (k per period and latitude) or "icclim" (k = 1, no range adjustment; a ``lat`` given
     with it is not used, UserWarning)."""
-    if not isinstance(freq, str):
-        raise TypeError("Freq must be a string.")
+    F.check_freq(freq)
     if method.lower() == "icclim":
         if lat is not None:
             warnings.warn("Lat coordinate is not used for method 'icclim' in 'biologically_effective_degree_days' calculation.",
@@ -290,8 +284,7 @@ def _hemisphere(lat, cell_shape, who, error):
 
 
 def _monthly(names, fields, lat, time, freq, sub_C, per_day, wo, device, keep, mask_missing, who, error=ValueError, check=None):
-    if keep and mask_missing:
-        raise ValueError("keep=True returns the device arrays as computed: pass mask_missing=False")
+    F.no_keep_with_mask(keep, mask_missing)
     got = F.native_set(fields)
     T, cell_shape, C_ = F.shape_of(got)
     _axis(time, T, who)
@@ -314,8 +307,7 @@ def cool_night_index(tasmin, lat=None, freq: str = "YS", *, time: TimeAxis = Non
                      keep: bool = False, mask_missing: bool = False):
     """_agro.py:447-528: the mean of ``tasmin`` [degC] over September (cells with lat > 0) or March (the others) of each year,
     float64 ``(P, *cells)``.  ``lat``: an array that broadcasts to the cells, or "north" / "south" for every cell."""
-    if not isinstance(freq, str):
-        raise TypeError("Freq must be a string.")
+    F.check_freq(freq)
     if parse_freq(freq) != ("Y", 1):
         raise ValueError(f"Freq not allowed: {freq}. Must be `YS` or `YS-JAN`")
     if not isinstance(lat, str) and lat is None:
@@ -335,8 +327,7 @@ def dryness_index(pr, evspsblpot, lat=None, wo: float = 200.0, freq: str = "YS",
     """_agro.py:532-724: ``wo`` plus the sum over the year's months of ``P k' - E k - (E / N) (1 - k) min(P k' / 5, N)`` [mm],
     float64 ``(P, *cells)``; the year is January - December for cells with lat >= 0 and July of the year before - June for the
     others.  ``pr`` / ``evspsblpot`` are rates in ``flux_units``; ``lat``: an array, or "north" / "south" for every cell."""
-    if not isinstance(freq, str):
-        raise TypeError("Freq must be a string.")
+    F.check_freq(freq)
     if parse_freq(freq) != ("Y", 1):
         raise ValueError(f"Freq not allowed: {freq}. Must be `YS` or `YS-JAN`")
     if not isinstance(lat, str) and lat is None:
@@ -436,8 +427,7 @@ def effective_growing_degree_days(tasmax, tasmin, *, thresh: float = 5.0, method
         raise NotImplementedError(f"Method: {method}.")
     if dim != "time":
         raise NotServed("effective_growing_degree_days: the time dimension (axis 0) only")
-    if keep and mask_missing:
-        raise ValueError("keep=True returns the device arrays as computed: pass mask_missing=False")
+    F.no_keep_with_mask(keep, mask_missing)
     sub_C = _sub_c(units)
     got = F.native_set(dict(tasmin=tasmin, tasmax=tasmax))
     T, cell_shape, C_ = F.shape_of(got)
@@ -469,26 +459,13 @@ def make_adapters(env, originals: dict, gather_lat=None, device=None) -> dict:
     period without a day of the season (the reference's ``select_time`` keeps the whole axis, ``drop=False``) — and the
     attributes the reference gives it.  Chunked or time-less fields, fields on different dimensions, units this module has no keyword for and everything
     :class:`NotServed` refuses go to the saved originals."""
-    import inspect
-
-    from .anuclim import _PR_SPELLINGS, _T_SPELLINGS
-    from .xr_adapter import _cell_dims, _tfirst_fields, _wrap_cells, time_axis_of
+    from .fields import FLUX_SPELLINGS, T_SPELLINGS
+    from .xr_adapter import _cell_dims, forwarding_adapter, on_period_starts, served_fields, threshold_number, units_keyword
 
     DA = env.DataArray
 
-    def _unit(da, table, name):
-        u = table.get(str(da.attrs.get("units", "")).strip())
-        if u is None:
-            raise NotServed(f"{name}: units {da.attrs.get('units')!r}")
-        return u
-
     def _number(q, units):
-        """A threshold ("10 degC", or a number already in ``units``) as a float in ``units``."""
-        if isinstance(q, str):
-            return float(env.convert_units_to(q, DA(np.zeros(1), dims=("x",), attrs={"units": units})))
-        if isinstance(q, (int, float, np.integer, np.floating)):
-            return float(q)
-        raise NotServed("a threshold that is neither a string nor a number")
+        return threshold_number(env, q, units)
 
     def _lat_cells(lat, a, first):
         """lat (a DataArray over some cell dims, array-like, or None = gathered from ``first``) broadcast to the cell dims."""
@@ -504,84 +481,55 @@ def make_adapters(env, originals: dict, gather_lat=None, device=None) -> dict:
             return v.reshape([a.shape[a.dims.index(d)] if d in lat.dims else 1 for d in dims])
         return np.asarray(lat, np.float64)
 
-    def _serve(p, names, tables):
-        fields = {n: p[n] for n in names}
-        a, vals = _tfirst_fields(DA, fields)
-        if any(v.shape != a.shape for v in vals.values()):
-            raise NotServed("fields on different dimensions")
-        units = {_unit(fields[n], tables, n) for n in names}
+    def _serve(p, names, table):
+        a, vals, time = served_fields(DA, p, names)
+        units = {units_keyword(p[n], table, n) for n in names}
         if len(units) != 1:
             raise NotServed("fields in different units")
-        return a, vals, time_axis_of(a), units.pop()
+        return a, vals, time, units.pop()
 
     def _hi(p):
-        a, v, time, units = _serve(p, ("tas", "tasmax"), _T_SPELLINGS)
+        a, v, time, units = _serve(p, ("tas", "tasmax"), T_SPELLINGS)
         lat = _lat_cells(p["lat"], a, p["tas"])
         out = huglin_index(v["tas"], v["tasmax"], lat, _number(p["thresh"], "degC"), p["method"], p["cap_value"], p["start_date"],
                            p["end_date"], p["freq"], time=time, units=units, device=device)
-        return a, out, {"units": ""}
+        return on_period_starts(DA, a, out, p["freq"], {"units": ""})
 
     def _bedd(p):
-        a, v, time, units = _serve(p, ("tasmin", "tasmax"), _T_SPELLINGS)
+        a, v, time, units = _serve(p, ("tasmin", "tasmax"), T_SPELLINGS)
         icclim = str(p["method"]).lower() == "icclim"
         lat = p["lat"] if icclim and p["lat"] is None else _lat_cells(p["lat"], a, p["tasmin"])
         out = biologically_effective_degree_days(
             v["tasmin"], v["tasmax"], lat, _number(p["thresh_tasmin"], "degC"), p["method"], p["cap_value"], _number(p["low_dtr"], "degC"),
             _number(p["high_dtr"], "degC"), _number(p["max_daily_degree_days"], "degC"), p["start_date"], p["end_date"], p["freq"],
             time=time, units=units, device=device)
-        return a, out, {"units": "K days"}
+        return on_period_starts(DA, a, out, p["freq"], {"units": "K days"})
 
     def _cni(p):
-        a, v, time, units = _serve(p, ("tasmin",), _T_SPELLINGS)
+        a, v, time, units = _serve(p, ("tasmin",), T_SPELLINGS)
         lat = p["lat"] if isinstance(p["lat"], str) else _lat_cells(p["lat"], a, p["tasmin"])
         out = cool_night_index(v["tasmin"], lat, p["freq"], time=time, units=units, device=device)
-        return a, out, dict(p["tasmin"].attrs, units="degC")
+        return on_period_starts(DA, a, out, p["freq"], dict(p["tasmin"].attrs, units="degC"))
 
     def _di(p):
-        a, v, time, units = _serve(p, ("pr", "evspsblpot"), _PR_SPELLINGS)
-        if units not in _FLUX_UNITS:
-            raise NotServed(f"pr: units {units!r}")
+        a, v, time, units = _serve(p, ("pr", "evspsblpot"), FLUX_SPELLINGS)
         lat = p["lat"] if isinstance(p["lat"], str) else _lat_cells(p["lat"], a, p["pr"])
         out = dryness_index(v["pr"], v["evspsblpot"], lat, _number(p["wo"], "mm"), p["freq"], time=time, flux_units=units, device=device)
-        return a, out, {"units": "mm"}
+        return on_period_starts(DA, a, out, p["freq"], {"units": "mm"})
 
     def _lti(p):
-        a, v, time, units = _serve(p, ("tas",), _T_SPELLINGS)
+        a, v, time, units = _serve(p, ("tas",), T_SPELLINGS)
         out = latitude_temperature_index(v["tas"], _lat_cells(p["lat"], a, p["tas"]), p["lat_factor"], p["freq"], time=time, units=units,
                                          device=device)
-        return a, out, {"units": ""}
+        return on_period_starts(DA, a, out, p["freq"], {"units": ""})
 
     def _egdd(p):
-        a, v, time, units = _serve(p, ("tasmax", "tasmin"), _T_SPELLINGS)
+        a, v, time, units = _serve(p, ("tasmax", "tasmin"), T_SPELLINGS)
         out = effective_growing_degree_days(v["tasmax"], v["tasmin"], thresh=_number(p["thresh"], "degC"), method=p["method"],
                                             after_date=p["after_date"], dim=p["dim"], freq=p["freq"], time=time, units=units, device=device)
-        return a, out, None
+        # to_agg_units(egdd, tas [degC], op="integral") (_agro.py:1383)
+        return env.to_agg_units(on_period_starts(DA, a, out, p["freq"], {}), DA(np.zeros(1), dims=("x",), attrs={"units": "degC"}), "integral")
 
     runners = {"huglin_index": _hi, "biologically_effective_degree_days": _bedd, "cool_night_index": _cni, "dryness_index": _di,
                "latitude_temperature_index": _lti, "effective_growing_degree_days": _egdd}
-
-    def _adapter(name):
-        orig, runner = originals[name], runners[name]
-
-        def fn(*args, **kwargs):
-            try:
-                bound = inspect.signature(orig).bind(*args, **kwargs)
-            except (TypeError, ValueError):
-                return orig(*args, **kwargs)
-            bound.apply_defaults()
-            p = bound.arguments
-            try:
-                a, values, attrs = runner(p)
-            except NotServed:
-                return orig(*args, **kwargs)
-            starts = a["time"].resample(time=p["freq"]).first()["time"]
-            out = _wrap_cells(DA, a, values, starts, attrs or {})
-            if attrs is None:    # effective_growing_degree_days: to_agg_units(egdd, tas [degC], op="integral") (_agro.py:1383)
-                out = env.to_agg_units(out, DA(np.zeros(1), dims=("x",), attrs={"units": "degC"}), "integral")
-            return out
-
-        fn.__wrapped__ = orig
-        fn.__name__, fn.__doc__ = name, getattr(orig, "__doc__", None)
-        return fn
-
-    return {name: _adapter(name) for name in ADAPTED}
+    return {name: forwarding_adapter(name, originals[name], runners[name]) for name in ADAPTED}

@@ -31,7 +31,7 @@ import numpy as np
 from . import fields as F
 from . import kernels as K
 from ._capi import get_device
-from .fields import NotServed
+from .fields import KELVIN_OFFSET, NotServed
 from .timeaxis import TimeAxis, parse_freq
 
 __all__ = ["isothermality", "temperature_seasonality", "precip_seasonality", "tg_mean_warmcold_quarter", "tg_mean_wetdry_quarter",
@@ -39,7 +39,6 @@ __all__ = ["isothermality", "temperature_seasonality", "precip_seasonality", "tg
            "axis_tables", "NotServed", "VARIABLES"]
 
 VARIABLES = K.BIOCLIM_VARS
-KELVIN_OFFSET = 273.15          # pint's degC <-> K offset
 SECONDS_PER_DAY = 86400.0
 PINT_MONTH_DAYS = 365.25 / 12   # pint's month
 
@@ -48,6 +47,8 @@ _T_UNITS = {"K": 0.0, "degC": KELVIN_OFFSET}
 _PR_UNITS = {"kg m-2 s-1": (SECONDS_PER_DAY, SECONDS_PER_DAY), "mm/s": (SECONDS_PER_DAY, SECONDS_PER_DAY), "mm/d": (1.0, 1.0),
              "mm/week": (1.0 / 7.0, 1.0), "mm/month": (1.0 / PINT_MONTH_DAYS, 1.0)}
 _ARGMAX = {"wettest": True, "warmest": True, "dryest": False, "driest": False, "coldest": False}
+# the ``op`` values of the quarter functions and the wording of upstream's complaint about another
+_WETDRY, _WARMCOLD = (("wettest", "driest", "dryest"), '"wettest" or "driest"'), (("warmest", "coldest"), '"warmest", "coldest"')
 # what each variable reads
 _READS = {1: ("tas",), 2: ("tasmin", "tasmax"), 3: ("tasmin", "tasmax"), 4: ("tas",), 5: ("tasmax",), 6: ("tasmin",),
           7: ("tasmin", "tasmax"), 8: ("tas", "pr"), 9: ("tas", "pr"), 10: ("tas",), 11: ("tas",), 12: ("pr",), 13: ("pr",),
@@ -107,8 +108,7 @@ def _expected(time, freq, tab):
 
 def _run(fields, time, freq, variables, which, units, pr_units, thresh, device, keep, mask_missing):
     """One launch: ``{name: (P, *cells)}`` for ``variables`` (BIO numbers) and ``which`` (quarter names)."""
-    if keep and mask_missing:
-        raise ValueError("keep=True returns the device arrays as computed: pass mask_missing=False")
+    F.no_keep_with_mask(keep, mask_missing)
     try:
         kelvin = _T_UNITS[units]
     except KeyError:
@@ -180,28 +180,28 @@ def precip_seasonality(pr, time: TimeAxis, freq: str = "YS", *, pr_units: str = 
 def tg_mean_warmcold_quarter(tas, time: TimeAxis, op: str, freq: str = "YS", *, device=None, keep: bool = False,
                              mask_missing: bool = False):
     """_anuclim.py:214-271 (BIO10 / BIO11): mean temperature of the warmest / coldest quarter, in the units of tas."""
-    k = 10 if _op(op, ("warmest", "coldest"), '"warmest", "coldest"') else 11
+    k = 10 if _op(op, *_WARMCOLD) else 11
     return _one(k, dict(tas=tas), time, freq, device=device, keep=keep, mask_missing=mask_missing)
 
 
 def tg_mean_wetdry_quarter(tas, pr, time: TimeAxis, op: str, freq: str = "YS", *, pr_units: str = "kg m-2 s-1", device=None,
                            keep: bool = False, mask_missing: bool = False):
     """_anuclim.py:274-327 (BIO8 / BIO9): mean temperature of the wettest / driest quarter."""
-    k = 8 if _op(op, ("wettest", "driest", "dryest"), '"wettest" or "driest"') else 9
+    k = 8 if _op(op, *_WETDRY) else 9
     return _one(k, dict(tas=tas, pr=pr), time, freq, pr_units=pr_units, device=device, keep=keep, mask_missing=mask_missing)
 
 
 def prcptot_wetdry_quarter(pr, time: TimeAxis, op: str, freq: str = "YS", *, pr_units: str = "kg m-2 s-1", device=None,
                            keep: bool = False, mask_missing: bool = False):
     """_anuclim.py:330-385 (BIO16 / BIO17): precipitation of the wettest / driest quarter [mm]."""
-    k = 16 if _op(op, ("wettest", "driest", "dryest"), '"wettest" or "driest"') else 17
+    k = 16 if _op(op, *_WETDRY) else 17
     return _one(k, dict(pr=pr), time, freq, pr_units=pr_units, device=device, keep=keep, mask_missing=mask_missing)
 
 
 def prcptot_warmcold_quarter(pr, tas, time: TimeAxis, op: str, freq: str = "YS", *, pr_units: str = "kg m-2 s-1", device=None,
                              keep: bool = False, mask_missing: bool = False):
     """_anuclim.py:388-442 (BIO18 / BIO19): precipitation of the warmest / coldest quarter [mm]."""
-    k = 18 if _op(op, ("warmest", "coldest"), '"warmest", "coldest"') else 19
+    k = 18 if _op(op, *_WARMCOLD) else 19
     return _one(k, dict(tas=tas, pr=pr), time, freq, pr_units=pr_units, device=device, keep=keep, mask_missing=mask_missing)
 
 
@@ -214,7 +214,7 @@ def prcptot(pr, time: TimeAxis, thresh: float = 0.0, freq: str = "YS", *, pr_uni
 def prcptot_wetdry_period(pr, time: TimeAxis, *, op: str, freq: str = "YS", pr_units: str = "kg m-2 s-1", device=None,
                           keep: bool = False, mask_missing: bool = False):
     """_anuclim.py:473-517 (BIO13 / BIO14): the amount of the wettest / driest single row (day, week or month) [mm]."""
-    k = 13 if _op(op, ("wettest", "driest", "dryest"), '"wettest" or "driest"') else 14
+    k = 13 if _op(op, *_WETDRY) else 14
     return _one(k, dict(pr=pr), time, freq, pr_units=pr_units, device=device, keep=keep, mask_missing=mask_missing)
 
 
@@ -241,10 +241,8 @@ def bioclim(tas=None, tasmin=None, tasmax=None, pr=None, time: TimeAxis = None, 
 # ---- the xarray adapter (patch.install) ------------------------------------------------------------------------------
 ADAPTED = ("temperature_seasonality", "precip_seasonality", "tg_mean_warmcold_quarter", "tg_mean_wetdry_quarter",
            "prcptot_wetdry_quarter", "prcptot_warmcold_quarter")
-_T_SPELLINGS = {"K": "K", "kelvin": "K", "degK": "K", "degC": "degC", "°C": "degC", "celsius": "degC", "degree_Celsius": "degC", "C": "degC"}
-_PR_SPELLINGS = {"kg m-2 s-1": "kg m-2 s-1", "kg/m2/s": "kg m-2 s-1", "mm/s": "mm/s", "mm s-1": "mm/s", "mm/d": "mm/d", "mm/day": "mm/d",
-                 "mm d-1": "mm/d", "mm day-1": "mm/d", "mm / d": "mm/d", "mm/week": "mm/week", "mm week-1": "mm/week",
-                 "mm/month": "mm/month", "mm month-1": "mm/month"}
+# the rate units of anuclim: those of the daily units and the two that go with weekly and monthly rows
+_PR_SPELLINGS = {**F.FLUX_SPELLINGS, "mm/week": "mm/week", "mm week-1": "mm/week", "mm/month": "mm/month", "mm month-1": "mm/month"}
 
 
 def make_adapters(env, originals: dict, device=None) -> dict:
@@ -254,72 +252,41 @@ def make_adapters(env, originals: dict, device=None) -> dict:
     its time coordinate and the units the reference gives it ("%", the units of ``tas``, "mm").  Chunked or time-less fields,
     fields on different dimensions, units this module has no factor for and every axis :class:`NotServed` refuses go to the
     saved originals; an unknown ``op`` raises NotImplementedError, as upstream."""
-    from .xr_adapter import _tfirst_fields, _wrap_cells, time_axis_of
+    from .xr_adapter import forwarding_adapter, on_period_starts, served_fields, units_keyword
 
     DA = env.DataArray
 
-    def _serve(fields, spellings):
-        """(time-first reference array, {name: values}, TimeAxis, {name: unit keyword})"""
-        a, vals = _tfirst_fields(DA, fields)
-        if any(x.shape != a.shape for x in vals.values()):
-            raise NotServed("fields on different dimensions")
-        units = {}
-        for (name, da), table in zip(fields.items(), spellings):
-            units[name] = table.get(str(da.attrs.get("units", "")).strip())
-            if units[name] is None:
-                raise NotServed(f"{name}: units {da.attrs.get('units')!r}")
-        return a, vals, time_axis_of(a), units
+    def _runner(fields, ops, call, out_units):
+        """``fields``: (name, spellings table) of every field; ``ops``: the ``op`` values the function takes and their wording."""
+        names = tuple(n for n, _ in fields)
 
-    def _adapter(name, fields_of, spellings, call, out_units):
-        orig = originals[name]
+        def run(p):
+            if ops:   # upstream checks op after _to_quarter; an unknown op is its NotImplementedError either way, never forwarded
+                _op(p["op"], *ops)
+            a, vals, time = served_fields(DA, p, names)
+            units = {n: units_keyword(p[n], table, n) for n, table in fields}
+            values = call(vals, time, units, p, device)
+            return on_period_starts(DA, a, values, p["freq"], dict(p[names[0]].attrs, units=out_units(p)))
 
-        def fn(*args, **kwargs):
-            import inspect
+        return run
 
-            try:
-                bound = inspect.signature(fn.__wrapped__).bind(*args, **kwargs)
-            except (TypeError, ValueError):
-                return orig(*args, **kwargs)
-            bound.apply_defaults()
-            p = bound.arguments
-            if "op" in p:   # upstream checks op after _to_quarter; an unknown op is its NotImplementedError either way
-                _op(p["op"], *_OPS[name])
-            try:
-                a, vals, time, units = _serve({k: p[k] for k in fields_of}, spellings)
-                values = call(vals, time, units, p, device)
-            except NotServed:
-                return orig(*args, **kwargs)
-            first = p[fields_of[0]]
-            starts = a["time"].resample(time=p.get("freq", "YS")).first()["time"]
-            return _wrap_cells(DA, a, values, starts, dict(first.attrs, units=out_units(p)))
-
-        fn.__wrapped__ = orig
-        fn.__name__, fn.__doc__ = name, getattr(orig, "__doc__", None)
-        return fn
-
-    wetdry, warmcold = (("wettest", "driest", "dryest"), '"wettest" or "driest"'), (("warmest", "coldest"), '"warmest", "coldest"')
-    _OPS = {"tg_mean_warmcold_quarter": warmcold, "tg_mean_wetdry_quarter": wetdry, "prcptot_wetdry_quarter": wetdry,
-            "prcptot_warmcold_quarter": warmcold}
-    T, PR = _T_SPELLINGS, _PR_SPELLINGS
+    T, PR = ("tas", F.T_SPELLINGS), ("pr", _PR_SPELLINGS)
     kw = lambda u, d: dict(pr_units=u.get("pr", "kg m-2 s-1"), device=d)  # noqa: E731
-    return {
-        "temperature_seasonality": _adapter(
-            "temperature_seasonality", ("tas",), (T,),
-            lambda v, t, u, p, d: temperature_seasonality(v["tas"], t, p["freq"], units=u["tas"], device=d), lambda p: "%"),
-        "precip_seasonality": _adapter(
-            "precip_seasonality", ("pr",), (PR,),
-            lambda v, t, u, p, d: precip_seasonality(v["pr"], t, p["freq"], **kw(u, d)), lambda p: "%"),
-        "tg_mean_warmcold_quarter": _adapter(
-            "tg_mean_warmcold_quarter", ("tas",), (T,),
-            lambda v, t, u, p, d: tg_mean_warmcold_quarter(v["tas"], t, p["op"], p["freq"], device=d), lambda p: p["tas"].attrs["units"]),
-        "tg_mean_wetdry_quarter": _adapter(
-            "tg_mean_wetdry_quarter", ("tas", "pr"), (T, PR),
-            lambda v, t, u, p, d: tg_mean_wetdry_quarter(v["tas"], v["pr"], t, p["op"], p["freq"], **kw(u, d)),
+    runners = {
+        "temperature_seasonality": _runner(
+            (T,), None, lambda v, t, u, p, d: temperature_seasonality(v["tas"], t, p["freq"], units=u["tas"], device=d), lambda p: "%"),
+        "precip_seasonality": _runner(
+            (PR,), None, lambda v, t, u, p, d: precip_seasonality(v["pr"], t, p["freq"], **kw(u, d)), lambda p: "%"),
+        "tg_mean_warmcold_quarter": _runner(
+            (T,), _WARMCOLD, lambda v, t, u, p, d: tg_mean_warmcold_quarter(v["tas"], t, p["op"], p["freq"], device=d),
             lambda p: p["tas"].attrs["units"]),
-        "prcptot_wetdry_quarter": _adapter(
-            "prcptot_wetdry_quarter", ("pr",), (PR,),
-            lambda v, t, u, p, d: prcptot_wetdry_quarter(v["pr"], t, p["op"], p["freq"], **kw(u, d)), lambda p: "mm"),
-        "prcptot_warmcold_quarter": _adapter(
-            "prcptot_warmcold_quarter", ("pr", "tas"), (PR, T),
-            lambda v, t, u, p, d: prcptot_warmcold_quarter(v["pr"], v["tas"], t, p["op"], p["freq"], **kw(u, d)), lambda p: "mm"),
+        "tg_mean_wetdry_quarter": _runner(
+            (T, PR), _WETDRY, lambda v, t, u, p, d: tg_mean_wetdry_quarter(v["tas"], v["pr"], t, p["op"], p["freq"], **kw(u, d)),
+            lambda p: p["tas"].attrs["units"]),
+        "prcptot_wetdry_quarter": _runner(
+            (PR,), _WETDRY, lambda v, t, u, p, d: prcptot_wetdry_quarter(v["pr"], t, p["op"], p["freq"], **kw(u, d)), lambda p: "mm"),
+        "prcptot_warmcold_quarter": _runner(
+            (PR, T), _WARMCOLD, lambda v, t, u, p, d: prcptot_warmcold_quarter(v["pr"], v["tas"], t, p["op"], p["freq"], **kw(u, d)),
+            lambda p: "mm"),
     }
+    return {name: forwarding_adapter(name, originals[name], runners[name]) for name in ADAPTED}

@@ -31,13 +31,13 @@ from . import fields as F
 from . import kernels as K
 from ._capi import get_device
 from .converters import NotServed, _check_time, _lat_table, day_angle
+from .fields import KELVIN_OFFSET
 from .timeaxis import TimeAxis
 
 __all__ = ["make_hourly_temperature", "chill_portions", "chill_units", "chill_portions_from_daily", "chill_units_from_daily",
            "chill_from_daily", "ChillIndices", "NotServed", "HOURS"]
 
 HOURS = 24
-KELVIN_OFFSET = 273.15  # pint's degC <-> K offset
 ChillIndices = namedtuple("ChillIndices", ["chill_portions", "chill_units"])
 
 _UNITS = {"K": (0.0, KELVIN_OFFSET), "degC": (KELVIN_OFFSET, 0.0)}
@@ -96,8 +96,7 @@ def _selected_days(time, seg, sel):
 
 def _reduce(run, names, time, freq, indexer, cell_shape, C_, P, nsel, keep, mask_missing, device):
     """Shared tail: ``run(outputs) -> {name: DeviceArray}`` with cp / cu / valid, then the period rules."""
-    if keep and mask_missing:
-        raise ValueError("keep=True returns the device arrays as computed: pass mask_missing=False")
+    F.no_keep_with_mask(keep, mask_missing)
     if P == 0 or C_ == 0:
         return F.empty_result(dict.fromkeys(names, np.float64), P, cell_shape, keep, device)
     outs = run(list(names) + ([] if keep else ["valid"]))

@@ -1,6 +1,8 @@
-"""The host front end of a unit that takes several named ``(T, *cells)`` fields (ffdi, converters, chill, anuclim and the
-adapter callees of fire): dtypes, shapes, uploads, per-cell inputs, the empty result, the download, and the transposition of
-the time-last arrays ``xr.apply_ufunc`` hands over.
+"""The host front end of a unit that takes several named ``(T, *cells)`` fields (ffdi, converters, chill, anuclim, agro,
+hydrology, rainseason and the adapter callees of fire): dtypes, shapes, uploads, per-cell inputs, the empty result, the
+download, and the transposition of the time-last arrays ``xr.apply_ufunc`` hands over.  The period units (chill, anuclim,
+agro, hydrology, rainseason) also take their period front end from here: the ``freq`` check, the period offsets, the
+``keep`` / ``mask_missing`` guard, the MissingAny mask of downloaded results, and the unit tables their adapters share.
 
 float32 and float64 fields are taken as given and every other dtype is widened to float64 (exact), so nothing here depends on
 ``XCLIM_AMD_FLOAT64``; the single-field float32 indices keep ``calendar._flatten``, which carries that policy.  This module
@@ -15,7 +17,8 @@ import numpy as np
 from ._capi import DeviceArray, get_device
 
 __all__ = ["NotServed", "Forward", "SERVED", "native", "native_set", "shape_of", "rows_on_device", "per_cell", "empty_result",
-           "host_result", "time_first", "time_last", "FLUX_UNITS", "FLUX_SPELLINGS", "per_day", "daily_axis"]
+           "host_result", "time_first", "time_last", "FLUX_UNITS", "FLUX_SPELLINGS", "T_SPELLINGS", "KELVIN_OFFSET", "per_day", "daily_axis",
+           "check_freq", "period_segments", "no_keep_with_mask", "mask_incomplete"]
 
 SERVED = (np.float32, np.float64)
 
@@ -26,6 +29,9 @@ FLUX_UNITS = ("kg m-2 s-1", "mm/s", "mm/d")
 _FLUX_PER_DAY = {"kg m-2 s-1": 86400.0, "mm/s": 86400.0, "mm/d": 1.0}
 FLUX_SPELLINGS = {"kg m-2 s-1": "kg m-2 s-1", "kg/m2/s": "kg m-2 s-1", "mm/s": "mm/s", "mm s-1": "mm/s", "mm/d": "mm/d", "mm/day": "mm/d",
                   "mm d-1": "mm/d", "mm day-1": "mm/d", "mm / d": "mm/d"}
+KELVIN_OFFSET = 273.15  # pint's degC <-> K offset
+# the spellings of a temperature's ``units`` attribute the adapters take for the kernels' "K" / "degC"
+T_SPELLINGS = {"K": "K", "kelvin": "K", "degK": "K", "degC": "degC", "°C": "degC", "celsius": "degC", "degree_Celsius": "degC", "C": "degC"}
 
 
 class NotServed(NotImplementedError):
@@ -58,6 +64,38 @@ def daily_axis(time, T, who):
         _check_time(time)
     except NotServed as e:
         raise NotServed(str(e).replace("potential evapotranspiration", who)) from None
+
+
+def check_freq(freq):
+    """The reference's own complaint about a ``freq`` that is not a string."""
+    if not isinstance(freq, str):
+        raise TypeError("Freq must be a string.")
+
+
+def period_segments(time, freq):
+    """The int64 row offsets (P + 1) of the periods of ``time.segments(freq)``; :class:`NotServed` for a ``freq`` the axis does not
+    parse."""
+    try:
+        return np.asarray(time.segments(freq)[0], np.int64)
+    except NotImplementedError as e:
+        raise NotServed(str(e)) from None
+
+
+def no_keep_with_mask(keep, mask_missing):
+    """The mask is applied on the host, to downloaded results: ``keep`` cannot have it."""
+    if keep and mask_missing:
+        raise ValueError("keep=True returns the device arrays as computed: pass mask_missing=False")
+
+
+def mask_incomplete(res: dict, valid, expected) -> dict:
+    """The MissingAny rule on downloaded results: float64 copies of ``{name: (P, *cells)}`` with NaN where ``valid`` (P, *cells), the
+    rows with a value, differs from ``expected`` (P), the rows of a complete period.  An integer count becomes float64."""
+    bad = valid != np.asarray(expected).reshape((valid.shape[0],) + (1,) * (valid.ndim - 1))
+    out = {}
+    for n, v in res.items():
+        out[n] = v.astype(np.float64)
+        out[n][bad] = np.nan
+    return out
 
 
 def native(a, name):

@@ -39,7 +39,7 @@ import numpy as np
 from . import fields as F
 from . import kernels as K
 from ._capi import HYDRO_MAX_WINDOW, SEN_MAX_YEARS, get_device
-from .fields import FLUX_SPELLINGS, FLUX_UNITS, NotServed, daily_axis
+from .fields import FLUX_SPELLINGS, NotServed, daily_axis
 from .fields import per_day as _per_day
 from .timeaxis import MONTHS, TimeAxis, parse_freq
 
@@ -54,25 +54,12 @@ SenSlopeRatio = namedtuple("SenSlopeRatio", ["sen_slope", "p_value", "sen_slope_
 SeasonalBFI = namedtuple("SeasonalBFI", ["bfi", "ratio", "seasons", "years"])
 
 
-def _freq(freq):
-    if not isinstance(freq, str):
-        raise TypeError("Freq must be a string.")
-    return freq
-
-
 def _open(fields, time, who):
     """The admitted fields: ``(native fields, T, cell_shape, C)`` on a daily, gap-free axis."""
     got = F.native_set(fields)
     T, cell_shape, C_ = F.shape_of(got)
     daily_axis(time, T, who)
     return got, T, cell_shape, C_
-
-
-def _segments(time, freq):
-    try:
-        return np.asarray(time.segments(freq)[0], np.int64)
-    except NotImplementedError as e:
-        raise NotServed(str(e)) from None
 
 
 def _window(window, who):
@@ -83,29 +70,17 @@ def _window(window, who):
     return int(window)
 
 
-def _no_keep_mask(keep, mask_missing):
-    if keep and mask_missing:
-        raise ValueError("keep=True returns the device arrays as computed: pass mask_missing=False")
-
-
 def _masked(res, valid, time, freq):
     """The MissingAny rule on downloaded results: ``valid`` (P, *cells) against the expected count of every period."""
-    P = valid.shape[0]
-    bad = valid != np.asarray(time.expected_count(freq)).reshape((P,) + (1,) * (valid.ndim - 1))
-    out = {}
-    for n, v in res.items():
-        v = v.astype(np.float64)
-        v[bad] = np.nan
-        out[n] = v
-    return out
+    return F.mask_incomplete(res, valid, time.expected_count(freq))
 
 
 # ---- base_flow_index / rb_flashiness_index ----------------------------------------------------------------------------
 def _flow(names, q, freq, time, device, keep, mask_missing, who):
-    _freq(freq)
-    _no_keep_mask(keep, mask_missing)
+    F.check_freq(freq)
+    F.no_keep_with_mask(keep, mask_missing)
     got, T, cell_shape, C_ = _open(dict(q=q), time, who)
-    seg = _segments(time, freq)
+    seg = F.period_segments(time, freq)
     P = len(seg) - 1
     if P == 0 or C_ == 0:
         return F.empty_result(dict.fromkeys(names, np.float64), P, cell_shape, keep, device)
@@ -138,11 +113,11 @@ def flow_stats(q, freq: str = "YS", *, time: TimeAxis = None, device=None, keep:
 
 # ---- snow_melt_we_max / melt_and_precip_max ---------------------------------------------------------------------------
 def _melt(snw, pr, window, freq, time, per_day, device, keep, mask_missing, who):
-    _freq(freq)
-    _no_keep_mask(keep, mask_missing)
+    F.check_freq(freq)
+    F.no_keep_with_mask(keep, mask_missing)
     got, T, cell_shape, C_ = _open(dict(snw=snw, pr=pr), time, who)
     window = _window(window, who)
-    seg = _segments(time, freq)
+    seg = F.period_segments(time, freq)
     P = len(seg) - 1
     if P == 0 or C_ == 0:
         return F.empty_result({"out": np.float64}, P, cell_shape, keep, device)["out"]
@@ -239,7 +214,7 @@ def sen_slope(q, freq: str = "YS", *, time: TimeAxis = None, device=None, keep: 
     field's dtype), per season of ``freq``: ``SenSlope(sen_slope, p_value, seasons)`` with two float64 ``(K, *cells)`` arrays and
     the K season labels ("annual" for a yearly ``freq``).  Does not need pymannkendall."""
     who = "sen_slope"
-    _freq(freq)
+    F.check_freq(freq)
     got, T, cell_shape, C_ = _open(dict(q=q), time, who)
     period_of, seasons, _ = season_year_table(time, freq)
     Y, K_ = period_of.shape
@@ -249,7 +224,7 @@ def sen_slope(q, freq: str = "YS", *, time: TimeAxis = None, device=None, keep: 
         e = F.empty_result({"slope": np.float64, "p": np.float64}, K_, cell_shape, keep, device)
         return SenSlope(e["slope"], e["p"], seasons)
     dev = device or get_device()
-    means, _ = K.resample_reduce(dev, F.rows_on_device(dev, got["q"], T, C_), "mean", _segments(time, freq), want_valid=False)
+    means, _ = K.resample_reduce(dev, F.rows_on_device(dev, got["q"], T, C_), "mean", F.period_segments(time, freq), want_valid=False)
     outs = K.sen_slope(dev, means, period_of)
     if keep:
         return SenSlope(outs["slope"], outs["p"], seasons)
@@ -312,10 +287,10 @@ def flow_index(q, p: float = 0.95, *, device=None):
 
 
 def _flow_frequency(q, op, threshold_of, freq, time, device, keep, mask_missing, who):
-    _freq(freq)
-    _no_keep_mask(keep, mask_missing)
+    F.check_freq(freq)
+    F.no_keep_with_mask(keep, mask_missing)
     got, T, cell_shape, C_ = _open(dict(q=q), time, who)
-    seg = _segments(time, freq)
+    seg = F.period_segments(time, freq)
     P = len(seg) - 1
     if P == 0 or C_ == 0:
         return F.empty_result({"n": np.int32}, P, cell_shape, keep, device)["n"]
@@ -359,9 +334,9 @@ def aridity_index(pr, evspsblpot, freq: str = "YS", *, time: TimeAxis = None, de
     """_hydrology.py:772-814: the period mean of ``pr`` over the period mean of ``evspsblpot`` (both in the same units; the means
     by ``xh_resample_reduce`` in the fields' dtype, the division on the host in float64), ``(P, *cells)``."""
     who = "aridity_index"
-    _freq(freq)
+    F.check_freq(freq)
     got, T, cell_shape, C_ = _open(dict(pr=pr, evspsblpot=evspsblpot), time, who)
-    seg = _segments(time, freq)
+    seg = F.period_segments(time, freq)
     P = len(seg) - 1
     if P == 0 or C_ == 0:
         return np.empty((P,) + tuple(cell_shape))
@@ -393,27 +368,11 @@ def make_adapters(env, originals: dict, device=None) -> dict:
     ``split_time_to_season_year`` labels it — and ``season``) and the units and attributes the reference gives it.
     Chunked or time-less fields, fields on different dimensions, units this module has no keyword for and everything
     :class:`NotServed` refuses go to the saved originals."""
-    import inspect
     import re
 
-    from .xr_adapter import _cell_coords, _cell_dims, _tfirst_fields, _wrap_cells, time_axis_of
+    from .xr_adapter import _cell_coords, _cell_dims, _wrap_cells, forwarding_adapter, on_period_starts, served_fields, units_keyword
 
     DA = env.DataArray
-
-    def _flux(da, name):
-        u = FLUX_SPELLINGS.get(str(da.attrs.get("units", "")).strip())
-        if u not in FLUX_UNITS:
-            raise NotServed(f"{name}: units {da.attrs.get('units')!r}")
-        return u
-
-    def _serve(p, names):
-        a, vals = _tfirst_fields(DA, {n: p[n] for n in names})
-        if any(v.shape != a.shape for v in vals.values()):
-            raise NotServed("fields on different dimensions")
-        return a, vals, time_axis_of(a)
-
-    def _periods(a, values, freq, attrs):
-        return _wrap_cells(DA, a, values, a["time"].resample(time=freq).first()["time"], attrs)
 
     def _cells(a, values, attrs, tail=None):
         """``values`` (*cells, *tail) on the cell dimensions of ``a`` followed by the trailing ``(dim, coordinate)`` pairs: the
@@ -424,47 +383,49 @@ def make_adapters(env, originals: dict, device=None) -> dict:
         return DA(np.asarray(values), coords=coords, dims=_cell_dims(a) + tuple(d for d, _ in tail), attrs=attrs)
 
     def _bfi(p):
-        a, v, t = _serve(p, ("q",))
-        return _periods(a, base_flow_index(v["q"], p["freq"], time=t, device=device), p["freq"], {"units": ""})
+        a, v, t = served_fields(DA, p, ("q",))
+        return on_period_starts(DA, a, base_flow_index(v["q"], p["freq"], time=t, device=device), p["freq"], {"units": ""})
 
     def _rbi(p):
-        a, v, t = _serve(p, ("q",))
-        return _periods(a, rb_flashiness_index(v["q"], p["freq"], time=t, device=device), p["freq"], {"units": ""})
+        a, v, t = served_fields(DA, p, ("q",))
+        return on_period_starts(DA, a, rb_flashiness_index(v["q"], p["freq"], time=t, device=device), p["freq"], {"units": ""})
 
     def _swe(p):
-        a, v, t = _serve(p, ("snw",))
-        return _periods(a, snow_melt_we_max(v["snw"], p["window"], p["freq"], time=t, device=device), p["freq"],
-                        {"units": p["snw"].attrs.get("units", "")})
+        a, v, t = served_fields(DA, p, ("snw",))
+        return on_period_starts(DA, a, snow_melt_we_max(v["snw"], p["window"], p["freq"], time=t, device=device), p["freq"],
+                                {"units": p["snw"].attrs.get("units", "")})
 
     def _mpm(p):
-        a, v, t = _serve(p, ("snw", "pr"))
-        out = melt_and_precip_max(v["snw"], v["pr"], p["window"], p["freq"], time=t, flux_units=_flux(p["pr"], "pr"), device=device)
-        return _periods(a, out, p["freq"], {"units": p["snw"].attrs.get("units", "")})
+        a, v, t = served_fields(DA, p, ("snw", "pr"))
+        flux = units_keyword(p["pr"], FLUX_SPELLINGS, "pr")
+        out = melt_and_precip_max(v["snw"], v["pr"], p["window"], p["freq"], time=t, flux_units=flux, device=device)
+        return on_period_starts(DA, a, out, p["freq"], {"units": p["snw"].attrs.get("units", "")})
 
     def _api(p):
-        a, v, t = _serve(p, ("pr",))
-        out = antecedent_precipitation_index(v["pr"], p["window"], p["p_exp"], time=t, flux_units=_flux(p["pr"], "pr"), device=device)
+        a, v, t = served_fields(DA, p, ("pr",))
+        flux = units_keyword(p["pr"], FLUX_SPELLINGS, "pr")
+        out = antecedent_precipitation_index(v["pr"], p["window"], p["p_exp"], time=t, flux_units=flux, device=device)
         return _wrap_cells(DA, a, out, a["time"], {"units": "mm"})
 
     def _fi(p):
-        a, v, _ = _serve(p, ("q",))
+        a, v, _ = served_fields(DA, p, ("q",))
         return _cells(a, flow_index(v["q"], p["p"], device=device), {"units": "1"})
 
     def _hff(p):
-        a, v, t = _serve(p, ("q",))
-        out = _periods(a, high_flow_frequency(v["q"], p["threshold_factor"], p["freq"], time=t, device=device), p["freq"], {})
+        a, v, t = served_fields(DA, p, ("q",))
+        out = on_period_starts(DA, a, high_flow_frequency(v["q"], p["threshold_factor"], p["freq"], time=t, device=device), p["freq"], {})
         return env.to_agg_units(out, p["q"], "count")
 
     def _lff(p):
-        a, v, t = _serve(p, ("q",))
-        out = _periods(a, low_flow_frequency(v["q"], p["threshold_factor"], p["freq"], time=t, device=device), p["freq"], {})
+        a, v, t = served_fields(DA, p, ("q",))
+        out = on_period_starts(DA, a, low_flow_frequency(v["q"], p["threshold_factor"], p["freq"], time=t, device=device), p["freq"], {})
         return env.to_agg_units(out, p["q"], "count")
 
     def _ai(p):
-        a, v, t = _serve(p, ("pr", "evspsblpot"))
+        a, v, t = served_fields(DA, p, ("pr", "evspsblpot"))
         if str(p["pr"].attrs.get("units", "")).strip() != str(p["evspsblpot"].attrs.get("units", "")).strip():
             raise NotServed("pr and evspsblpot in different units")
-        return _periods(a, aridity_index(v["pr"], v["evspsblpot"], p["freq"], time=t, device=device), p["freq"], {"units": ""})
+        return on_period_starts(DA, a, aridity_index(v["pr"], v["evspsblpot"], p["freq"], time=t, device=device), p["freq"], {"units": ""})
 
     def _split_freq(freq):
         """(base, anchor) of a start-anchored ``freq`` the season split serves ("MS", "QS[-MMM]", "YS[-MMM]" / "AS[-MMM]")."""
@@ -493,21 +454,21 @@ def make_adapters(env, originals: dict, device=None) -> dict:
         return np.moveaxis(np.asarray(x), list(range(n)), list(range(-n, 0)))
 
     def _sen(p):
-        a, v, t = _serve(p, ("q",))
+        a, v, t = served_fields(DA, p, ("q",))
         _split_freq(p["freq"])
         s = sen_slope(v["q"], p["freq"], time=t, device=device)
         season = _season(s.seasons, p["freq"])
         return tuple(_cells(a, _last(x), {"units": ""}, [season]) for x in (s.sen_slope, s.p_value))
 
     def _senr(p):
-        a, v, t = _serve(p, ("q", "qsim"))
+        a, v, t = served_fields(DA, p, ("q", "qsim"))
         _split_freq(p["freq"])
         s = sen_slope_ratio(v["q"], v["qsim"], p["freq"], time=t, device=device)
         season = _season(s.seasons, p["freq"])
         return tuple(_cells(a, _last(x), {"units": ""}, [season]) for x in s[:5])
 
     def _bfis(p):
-        a, v, t = _serve(p, ("q",))
+        a, v, t = served_fields(DA, p, ("q",))
         _split_freq(p["freq"])
         seasons = season_year_table(t, p["freq"])[1]
         if p["numerator"] not in seasons or p["denominator"] not in seasons:
@@ -522,22 +483,4 @@ def make_adapters(env, originals: dict, device=None) -> dict:
                "antecedent_precipitation_index": _api, "flow_index": _fi, "high_flow_frequency": _hff, "low_flow_frequency": _lff,
                "aridity_index": _ai, "sen_slope": _sen, "sen_slope_ratio": _senr, "base_flow_index_seasonal_ratio": _bfis}
 
-    def _adapter(name):
-        orig, runner = originals[name], runners[name]
-
-        def fn(*args, **kwargs):
-            try:
-                bound = inspect.signature(orig).bind(*args, **kwargs)
-            except (TypeError, ValueError):
-                return orig(*args, **kwargs)
-            bound.apply_defaults()
-            try:
-                return runner(bound.arguments)
-            except NotServed:
-                return orig(*args, **kwargs)
-
-        fn.__wrapped__ = orig
-        fn.__name__, fn.__doc__ = name, getattr(orig, "__doc__", None)
-        return fn
-
-    return {name: _adapter(name) for name in ADAPTED}
+    return {name: forwarding_adapter(name, originals[name], runners[name]) for name in ADAPTED}

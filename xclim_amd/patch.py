@@ -152,6 +152,7 @@ def install(env=None, modules=None) -> list[str]:
     by default the real packages are used.  Functions the HIP path does not serve are forwarded to the saved originals."""
     import importlib
 
+    from . import agro, anuclim, hydrology, rainseason
     from .xr_adapter import make_wrappers
 
     env = env or real_env()
@@ -187,6 +188,21 @@ def install(env=None, modules=None) -> list[str]:
             _saved.setdefault((modname, attr), getattr(mod, attr))
             setattr(mod, attr, fn)
             done.append(f"{modname}.{attr}")
+
+    def install_mirror(modnames, mirror, *extra):
+        """The functions ``mirror.ADAPTED`` replaced where they are defined (``modnames[0]``, which must hold every one of them) and,
+        by identity, where the other modules re-export them.  ``extra``: attributes of the defining module (None where it has none)
+        that ``mirror.make_adapters`` takes after the originals."""
+        defining = resolve(modnames[0])
+        if defining is None or not all(hasattr(defining, n) for n in mirror.ADAPTED):
+            return
+        origs = {n: _saved.get((modnames[0], n), getattr(defining, n)) for n in mirror.ADAPTED}
+        adapters = mirror.make_adapters(env, origs, *(getattr(defining, x, None) for x in extra))
+        for modname in modnames:
+            m = resolve(modname)
+            for name in mirror.ADAPTED:
+                if m is not None and _saved.get((modname, name), getattr(m, name, None)) is origs[name]:
+                    patch(modname, name, adapters[name])
 
     for modname, names in _BY_NAME.items():
         for name in names:
@@ -258,63 +274,19 @@ def install(env=None, modules=None) -> list[str]:
 
         orig_chill = _saved.get((_CHILL_MODULE, _CHILL_NAME), getattr(amod, _CHILL_NAME))
         patch(_CHILL_MODULE, _CHILL_NAME, chill_adapters(orig_chill)[_CHILL_NAME])
-    # BIO4, BIO8-BIO11 and BIO15-BIO19: one launch of xh_bioclim each; replaced where they are defined and, by identity, where
-    # xclim.indices re-exports them
-    bmod = resolve(_ANUCLIM_MODULES[0])
-    if bmod is not None:
-        from .anuclim import ADAPTED, make_adapters as anuclim_adapters
-
-        if all(hasattr(bmod, n) for n in ADAPTED):
-            origs = {n: _saved.get((_ANUCLIM_MODULES[0], n), getattr(bmod, n)) for n in ADAPTED}
-            bio = anuclim_adapters(env, origs)
-            for modname in _ANUCLIM_MODULES:
-                m = resolve(modname)
-                for name in ADAPTED:
-                    if m is not None and _saved.get((modname, name), getattr(m, name, None)) is origs[name]:
-                        patch(modname, name, bio[name])
+    # the period-index mirrors, all installed the same way
+    # BIO4, BIO8-BIO11 and BIO15-BIO19: one launch of xh_bioclim each
+    install_mirror(_ANUCLIM_MODULES, anuclim)
     # the six period functions of the viticulture / agroclimatic unit (huglin_index ... effective_growing_degree_days): one launch
-    # each; replaced where they are defined and, by identity, where xclim.indices re-exports them.  corn_heat_units and
-    # qian_weighted_mean_average are lazy xarray expressions and stay xclim's
-    gmod = resolve(_AGRO_MODULES[0])
-    if gmod is not None:
-        from .agro import ADAPTED as AGRO_ADAPTED, make_adapters as agro_adapters
-
-        if all(hasattr(gmod, n) for n in AGRO_ADAPTED):
-            origs = {n: _saved.get((_AGRO_MODULES[0], n), getattr(gmod, n)) for n in AGRO_ADAPTED}
-            agr = agro_adapters(env, origs, getattr(gmod, "_gather_lat", None))
-            for modname in _AGRO_MODULES:
-                m = resolve(modname)
-                for name in AGRO_ADAPTED:
-                    if m is not None and _saved.get((modname, name), getattr(m, name, None)) is origs[name]:
-                        patch(modname, name, agr[name])
-        # rain_season and hardiness_zones, the last two functions of _agro.py (xclim_amd.rainseason): one launch of xh_rain_season;
-        # the period minimum + xh_rolling_zones.  Replaced only where both are present
-        from .rainseason import ADAPTED as RAIN_ADAPTED, make_adapters as rain_adapters
-
-        if all(hasattr(gmod, n) for n in RAIN_ADAPTED):
-            origs = {n: _saved.get((_AGRO_MODULES[0], n), getattr(gmod, n)) for n in RAIN_ADAPTED}
-            rain = rain_adapters(env, origs)
-            for modname in _AGRO_MODULES:
-                m = resolve(modname)
-                for name in RAIN_ADAPTED:
-                    if m is not None and _saved.get((modname, name), getattr(m, name, None)) is origs[name]:
-                        patch(modname, name, rain[name])
-    # the streamflow and snow-melt functions of _hydrology.py (base_flow_index ... base_flow_index_seasonal_ratio): replaced where
-    # they are defined and, by identity, where xclim.indices re-exports them; sen_slope also where pymannkendall is absent (it no
-    # longer needs it).  runoff_ratio is unit conversion around two means and stays xclim's, as do lag_snowpack_flow_peaks and
-    # the snd_max / snw_max family (select_resample_op, served by the generic wrappers)
-    hmod = resolve(_HYDRO_MODULES[0])
-    if hmod is not None:
-        from .hydrology import ADAPTED as HYDRO_ADAPTED, make_adapters as hydro_adapters
-
-        if all(hasattr(hmod, n) for n in HYDRO_ADAPTED):
-            origs = {n: _saved.get((_HYDRO_MODULES[0], n), getattr(hmod, n)) for n in HYDRO_ADAPTED}
-            hyd = hydro_adapters(env, origs)
-            for modname in _HYDRO_MODULES:
-                m = resolve(modname)
-                for name in HYDRO_ADAPTED:
-                    if m is not None and _saved.get((modname, name), getattr(m, name, None)) is origs[name]:
-                        patch(modname, name, hyd[name])
+    # each.  corn_heat_units and qian_weighted_mean_average are lazy xarray expressions and stay xclim's
+    install_mirror(_AGRO_MODULES, agro, "_gather_lat")
+    # rain_season and hardiness_zones, the last two functions of _agro.py: one launch of xh_rain_season; the period minimum +
+    # xh_rolling_zones.  Replaced only where both are present
+    install_mirror(_AGRO_MODULES, rainseason)
+    # the streamflow and snow-melt functions of _hydrology.py (base_flow_index ... base_flow_index_seasonal_ratio); sen_slope also
+    # where pymannkendall is absent (it no longer needs it).  runoff_ratio is unit conversion around two means and stays xclim's,
+    # as do lag_snowpack_flow_peaks and the snd_max / snw_max family (select_resample_op, served by the generic wrappers)
+    install_mirror(_HYDRO_MODULES, hydrology)
     cmod = resolve(_PET_MODULE)
     if cmod is not None and all(hasattr(cmod, n) for n in _PET_NAMES):
         from .converters import make_adapters as pet_adapters

@@ -33,7 +33,7 @@ from . import fields as F
 from . import kernels as K
 from ._capi import RAIN_END_BOUNDS, RAIN_MAX_WINDOW, RAIN_START_BOUNDS, RAIN_START_WINDOW, get_device
 from .calendar import select_time_mask
-from .fields import NotServed, daily_axis
+from .fields import KELVIN_OFFSET, NotServed, daily_axis
 from .fields import per_day as _per_day
 from .timeaxis import TimeAxis
 
@@ -41,21 +41,7 @@ __all__ = ["rain_season", "hardiness_zones", "rain_flags", "zone_edges", "RainSe
            "make_adapters"]
 
 RainSeason = namedtuple("RainSeason", ["rain_season_start", "rain_season_end", "rain_season_length"])
-KELVIN_OFFSET = 273.15  # pint's degC <-> K offset
 _METHODS = ("per_day", "total")
-
-
-def _freq(freq):
-    if not isinstance(freq, str):
-        raise TypeError("Freq must be a string.")
-    return freq
-
-
-def _segments(time, freq):
-    try:
-        return np.asarray(time.segments(freq)[0], np.int64)
-    except NotImplementedError as e:
-        raise NotServed(str(e)) from None
 
 
 def _int(name, v, least):
@@ -103,9 +89,8 @@ def rain_season(pr, thresh_wet_start: float = 25.0, window_wet_start: int = 3, w
     of the end of the rain season of every period and its length in days, float64 ``(P, *cells)`` with NaN.  ``pr`` is a rate in
     ``flux_units``; the thresholds are daily amounts in mm.  One launch of ``xh_rain_season``."""
     who = "rain_season"
-    _freq(freq)
-    if keep and mask_missing:
-        raise ValueError("keep=True returns the device arrays as computed: pass mask_missing=False")
+    F.check_freq(freq)
+    F.no_keep_with_mask(keep, mask_missing)
     if method_dry_start not in _METHODS:
         raise ValueError(f"Unknown method_dry_start: {method_dry_start}.")
     if method_dry_end not in _METHODS:
@@ -122,7 +107,7 @@ def rain_season(pr, thresh_wet_start: float = 25.0, window_wet_start: int = 3, w
     a = F.native(pr, "pr")
     T, cell_shape, C_ = F.shape_of({"pr": a})
     daily_axis(time, T, who)
-    seg = _segments(time, freq)
+    seg = F.period_segments(time, freq)
     P = len(seg) - 1
     flags = rain_flags(time, seg, date_min_start, date_max_start, date_min_end, date_max_end)
     names = RainSeason._fields
@@ -140,9 +125,7 @@ def rain_season(pr, thresh_wet_start: float = 25.0, window_wet_start: int = 3, w
     res = F.host_result(outs, P, cell_shape)
     if mask_missing:   # MissingAny: a period whose rows with a value are not all the days of the period
         valid = K.resample_reduce(dev, x, "count", seg, want_valid=False)[0].get().reshape((P,) + tuple(cell_shape))
-        bad = valid != np.asarray(time.expected_count(freq)).reshape((P,) + (1,) * len(cell_shape))
-        for v in res.values():
-            v[bad] = np.nan
+        res = F.mask_incomplete(res, valid, time.expected_count(freq))
     return RainSeason(**res)
 
 
@@ -166,13 +149,13 @@ def hardiness_zones(tasmin, window: int = 30, method: str = "usda", freq: str = 
     ``(P, *cells)``; NaN for the first ``window - 1`` periods, where a minimum of the window is NaN and outside the zones.  Zones
     count from 0 ("usda": half zones, 26 of them; "anbg": 7).  ``xh_resample_reduce`` (min) + ``xh_rolling_zones``."""
     who = "hardiness_zones"
-    _freq(freq)
+    F.check_freq(freq)
     edges = zone_edges(method, units)
     window = _int("window", window, 1)
     a = F.native(tasmin, "tasmin")
     T, cell_shape, C_ = F.shape_of({"tasmin": a})
     daily_axis(time, T, who)
-    seg = _segments(time, freq)
+    seg = F.period_segments(time, freq)
     P = len(seg) - 1
     if P == 0 or C_ == 0:
         return F.empty_result({"zones": np.float64}, P, cell_shape, keep, device)["zones"]
@@ -193,64 +176,28 @@ def make_adapters(env, originals: dict, device=None) -> dict:
     starts of ``resample(time=freq)`` as their time coordinate and the reference's attributes (:977-979, :1432).  Chunked or
     time-less fields, units this module has no keyword for and everything :class:`NotServed` refuses go to the saved originals;
     no other exception is caught."""
-    import inspect
-
-    from .anuclim import _T_SPELLINGS
-    from .fields import FLUX_SPELLINGS, FLUX_UNITS
-    from .xr_adapter import _tfirst_fields, _wrap_cells, time_axis_of
+    from .fields import FLUX_SPELLINGS, T_SPELLINGS
+    from .xr_adapter import forwarding_adapter, on_period_starts, served_fields, threshold_number, units_keyword
 
     DA = env.DataArray
 
-    def _number(q):
-        """A threshold ("25.0 mm", or a number already in mm) as a float in mm."""
-        if isinstance(q, str):
-            return float(env.convert_units_to(q, DA(np.zeros(1), dims=("x",), attrs={"units": "mm"})))
-        if isinstance(q, (int, float, np.integer, np.floating)):
-            return float(q)
-        raise NotServed("a threshold that is neither a string nor a number")
-
-    def _periods(a, values, freq, attrs):
-        return _wrap_cells(DA, a, values, a["time"].resample(time=freq).first()["time"], attrs)
-
     def _rain(p):
-        a, v = _tfirst_fields(DA, {"pr": p["pr"]})
-        flux = FLUX_SPELLINGS.get(str(p["pr"].attrs.get("units", "")).strip())
-        if flux not in FLUX_UNITS:
-            raise NotServed(f"pr: units {p['pr'].attrs.get('units')!r}")
-        out = rain_season(v["pr"], _number(p["thresh_wet_start"]), p["window_wet_start"], p["window_not_dry_start"],
-                          _number(p["thresh_dry_start"]), p["window_dry_start"], p["method_dry_start"], p["date_min_start"],
-                          p["date_max_start"], _number(p["thresh_dry_end"]), p["window_dry_end"], p["method_dry_end"], p["date_min_end"],
-                          p["date_max_end"], p["freq"], time=time_axis_of(a), flux_units=flux, device=device)
+        a, v, time = served_fields(DA, p, ("pr",))
+        flux = units_keyword(p["pr"], FLUX_SPELLINGS, "pr")
+        mm = [threshold_number(env, p[n], "mm") for n in ("thresh_wet_start", "thresh_dry_start", "thresh_dry_end")]
+        out = rain_season(v["pr"], mm[0], p["window_wet_start"], p["window_not_dry_start"], mm[1], p["window_dry_start"],
+                          p["method_dry_start"], p["date_min_start"], p["date_max_start"], mm[2], p["window_dry_end"], p["method_dry_end"],
+                          p["date_min_end"], p["date_max_end"], p["freq"], time=time, flux_units=flux, device=device)
         doy = {"units": "", "is_dayofyear": np.int32(1)}
-        return (_periods(a, out.rain_season_start, p["freq"], dict(doy)), _periods(a, out.rain_season_end, p["freq"], dict(doy)),
-                _periods(a, out.rain_season_length, p["freq"], {"units": "days"}))
+        return (on_period_starts(DA, a, out.rain_season_start, p["freq"], dict(doy)),
+                on_period_starts(DA, a, out.rain_season_end, p["freq"], dict(doy)),
+                on_period_starts(DA, a, out.rain_season_length, p["freq"], {"units": "days"}))
 
     def _zones(p):
-        a, v = _tfirst_fields(DA, {"tasmin": p["tasmin"]})
-        units = _T_SPELLINGS.get(str(p["tasmin"].attrs.get("units", "")).strip())
-        if units is None:
-            raise NotServed(f"tasmin: units {p['tasmin'].attrs.get('units')!r}")
-        out = hardiness_zones(v["tasmin"], p["window"], p["method"], p["freq"], time=time_axis_of(a), units=units, device=device)
-        return _periods(a, out, p["freq"], {"units": ""})
+        a, v, time = served_fields(DA, p, ("tasmin",))
+        units = units_keyword(p["tasmin"], T_SPELLINGS, "tasmin")
+        out = hardiness_zones(v["tasmin"], p["window"], p["method"], p["freq"], time=time, units=units, device=device)
+        return on_period_starts(DA, a, out, p["freq"], {"units": ""})
 
     runners = {"rain_season": _rain, "hardiness_zones": _zones}
-
-    def _adapter(name):
-        orig, runner = originals[name], runners[name]
-
-        def fn(*args, **kwargs):
-            try:
-                bound = inspect.signature(orig).bind(*args, **kwargs)
-            except (TypeError, ValueError):
-                return orig(*args, **kwargs)
-            bound.apply_defaults()
-            try:
-                return runner(bound.arguments)
-            except NotServed:
-                return orig(*args, **kwargs)
-
-        fn.__wrapped__ = orig
-        fn.__name__, fn.__doc__ = name, getattr(orig, "__doc__", None)
-        return fn
-
-    return {name: _adapter(name) for name in ADAPTED}
+    return {name: forwarding_adapter(name, originals[name], runners[name]) for name in ADAPTED}

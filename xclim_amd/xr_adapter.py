@@ -40,6 +40,7 @@ in-memory DataArray when no resampling is asked for (the DataArray is transposed
 
 from __future__ import annotations
 
+import inspect
 import itertools
 import operator
 
@@ -193,6 +194,59 @@ def _wrap_cells(DA, a, values, time_coord, attrs):
     coords = dict(_cell_coords(a))
     coords["time"] = time_coord
     return DA(np.asarray(values), coords=coords, dims=("time",) + _cell_dims(a), attrs=attrs)
+
+
+# ---- what the adapters of the period-index mirrors (anuclim, agro, hydrology, rainseason) share: a new unit writes runners only --
+def forwarding_adapter(name, orig, runner):
+    """The same-signature replacement of ``orig``: ``runner(p)`` gets the arguments bound against the signature of ``orig``, defaults
+    applied, and returns the finished result.  Arguments that do not bind, and whatever ``runner`` refuses with
+    :class:`NotServed`, go to ``orig`` as they came; every other exception is the caller's."""
+
+    def fn(*args, **kwargs):
+        try:
+            bound = inspect.signature(orig).bind(*args, **kwargs)
+        except (TypeError, ValueError):
+            return orig(*args, **kwargs)
+        bound.apply_defaults()
+        try:
+            return runner(bound.arguments)
+        except NotServed:
+            return orig(*args, **kwargs)
+
+    fn.__wrapped__ = orig
+    fn.__name__, fn.__doc__ = name, getattr(orig, "__doc__", None)
+    return fn
+
+
+def units_keyword(da, table, name):
+    """The kernel's keyword for the ``units`` attribute of the field ``name``, from a spellings table."""
+    try:
+        return table[str(da.attrs.get("units", "")).strip()]
+    except KeyError:
+        raise NotServed(f"{name}: units {da.attrs.get('units')!r}") from None
+
+
+def threshold_number(env, q, units):
+    """A threshold ("10 degC", or a number already in ``units``) as a float in ``units``."""
+    if isinstance(q, str):
+        return float(env.convert_units_to(q, env.DataArray(np.zeros(1), dims=("x",), attrs={"units": units})))
+    if isinstance(q, (int, float, np.integer, np.floating)):
+        return float(q)
+    raise NotServed("a threshold that is neither a string nor a number")
+
+
+def on_period_starts(DA, a, values, freq, attrs):
+    """``values`` (P, *cells) on the period starts of ``resample(time=freq)`` and the cell dimensions and coordinates of ``a``."""
+    return _wrap_cells(DA, a, values, a["time"].resample(time=freq).first()["time"], attrs)
+
+
+def served_fields(DA, p, names):
+    """The fields ``names`` of the arguments ``p``, admitted by :func:`_tfirst_fields` and of one shape: ``(the first field time
+    first, {name: values}, its TimeAxis)``."""
+    a, vals = _tfirst_fields(DA, {n: p[n] for n in names})
+    if any(v.shape != a.shape for v in vals.values()):
+        raise NotServed("fields on different dimensions")
+    return a, vals, time_axis_of(a)
 
 
 class _LazyBase:

@@ -39,15 +39,43 @@ UNIT_DEFINES = {"eqm": ["-D__all(x)=((x)!=0)"],
                 "plane": ["-include", os.path.join(HERE, "wave_of_one.h")],
                 # wquantile.hip's LDS arrays are lane-private columns ([i * 64 + lane]): static arrays do
                 "wquantile": ["-D__shared__=static"],
-                "f64run": ["-DSIM_EXACT_DYN_LDS=1"]}
+                # (the dynamic LDS of a launch as a heap block of exactly its size: simt.h)
+                "f64run": ["-DSIM_EXACT_DYN_LDS=1"], "hydro": ["-DSIM_EXACT_DYN_LDS=1"], "rainseason": ["-DSIM_EXACT_DYN_LDS=1"]}
 # thread-by-thread units that declare dynamic LDS (lane-private columns): the declaration is rewritten as in the fiber units
 DYN_LDS_UNITS = ("stdidx",)
 
 
-# units whose kernels talk through LDS / the wave in WAVE-UNIFORM control flow: every workgroup as a set of fibers (simt.h)
+# units whose kernels talk through LDS / the wave in WAVE-UNIFORM control flow: every workgroup as a set of fibers (simt.h).
+# This is also the fiber half of the shared library that build() makes.
 FIBER_UNITS = ("f64", "select", "select5", "tcount", "qdm", "quantile", "doystats", "core", "reduce2", "pdoy_top", "pdoy_quad", "pdoy_walk", "select3", "qdm2", "select2", "select4", "winsel",
                # f64run.hip: k_percentile_doy_f64 sorts its columns in LDS by all threads of the workgroup (barriers, an LDS atomicAdd)
                "f64run")
+# How a unit is compiled is one thing, which library holds it another: these are compiled on fibers as well, but only the unit
+# libraries below hold them.  unit -> the number of `extern __shared__` declarations that must be rewritten, no more and no fewer.
+#   hydro.hip: k_sen_slope sorts its slopes in LDS by the whole workgroup (barriers)
+#   rainseason.hip: the ring of k_rain_season is dynamic LDS, so that a ring slot past the ring lands outside the heap block
+UNIT_LIBRARY_FIBER_UNITS = {"hydro": 3, "rainseason": 1}
+
+# The small simulation libraries of single units (libxclimhip_hostsim_<name>.so: the unit, unchanged, the units of the entry points
+# its GPU tests also call, and sim_runtime.cpp; the shared library of build() is left as it is) and their stand-alone sanitizer
+# programs: name -> (units of the library, units of the driver, driver source under standalone/).
+UNIT_LIBRARIES = {
+    # chill.hip has one lane per (cell, period) and no traffic between lanes: thread by thread.  pet.hip: xh_solar_table gives
+    # the day lengths.
+    "chill": (("chill", "pet"), (), None),
+    # bioclim.hip: one lane per (cell, period), thread by thread.  f64.hip (xh_resample_reduce_f64) and f64red.hip
+    # (xh_range_reduce_f64) hold the entry points the cross-checks call.
+    "bioclim": (("bioclim", "f64", "f64red"), ("bioclim",), "bioclim_driver.cpp"),
+    # agro.hip: one lane per (cell, period) or per cell, thread by thread.  pet.hip: the solar table behind the Gladstones and
+    # Jones coefficients; f64.hip: xh_resample_reduce_f64 of the warmest-month cross-check.
+    "agro": (("agro", "pet", "f64"), ("agro",), "agro_driver.cpp"),
+    # hydro.hip on fibers (above).  f64.hip and reduce.hip + tcount.hip + window.hip: the period means, the per-cell threshold
+    # counts and the float64 quantiles the other indices are built from.
+    "hydro": (("hydro", "f64", "reduce", "tcount", "window"), ("hydro",), "hydro_driver.cpp"),
+    # rainseason.hip on fibers (above).  f64.hip and reduce.hip + tcount.hip + window.hip: the period minima of hardiness_zones
+    # and the counts of the missing mask (reduce.hip links against the launchers of tcount.hip, f64.hip against window.hip).
+    "rain": (("rainseason", "f64", "reduce", "tcount", "window"), ("rainseason",), "rain_driver.cpp"),
+}
 # topnet.h (the comparator networks of the register percentile kernels) issues v_min_f32 / v_max_f32 and a NaN-replace-and-count
 # triple as inline ISA: four statements, rewritten to the C++ they stand for (NaN never enters the min / max: the callers replace
 # it first), in a copy of the header that the fiber units include instead
@@ -117,17 +145,16 @@ def _prepare_unit(unit: str, workdir: str, san: str = ""):
     """(source file, extra flags) of one unit: the source unchanged, or its rewritten copy in workdir."""
     src = os.path.join(CSRC, unit + ".hip")
     extra = list(UNIT_DEFINES.get(unit, []))
-    if unit in DYN_LDS_UNITS:
-        text, nsub = _DYN_LDS.subn(lambda m: f"{m.group(1)}* {m.group(2)} = ({m.group(1)}*)sim_dynamic_lds();", open(src).read())
-        if nsub == 0:
-            raise RuntimeError(f"{unit}.hip: the `extern __shared__` declaration the simulation rewrites has changed")
-        src = os.path.join(workdir, unit + ".sim.cpp")
-        open(src, "w").write(text)
-    if unit in FIBER_UNITS:
-        text = open(src).read()
-        if unit == "core":   # the runtime half of core.hip is sim_runtime.cpp's job: only its kernels (synthetic fields, transposes)
-            text = '#include "common.h"\n' + text[text.index("// ---- synthetic generator"):]
-        text = _DYN_LDS.sub(lambda m: f"{m.group(1)}* {m.group(2)} = ({m.group(1)}*)sim_dynamic_lds();", text)
+    fibers = unit in FIBER_UNITS or unit in UNIT_LIBRARY_FIBER_UNITS
+    if not fibers and unit not in DYN_LDS_UNITS:
+        return src, extra
+    text = open(src).read()
+    if unit == "core":   # the runtime half of core.hip is sim_runtime.cpp's job: only its kernels (synthetic fields, transposes)
+        text = '#include "common.h"\n' + text[text.index("// ---- synthetic generator"):]
+    text, nsub = _DYN_LDS.subn(lambda m: f"{m.group(1)}* {m.group(2)} = ({m.group(1)}*)sim_dynamic_lds();", text)
+    if nsub != UNIT_LIBRARY_FIBER_UNITS.get(unit, nsub) or (nsub == 0 and unit in DYN_LDS_UNITS):
+        raise RuntimeError(f"{unit}.hip: an `extern __shared__` declaration the simulation rewrites has changed ({nsub} rewritten)")
+    if fibers:
         # the LDS-only workgroup barrier (s_waitcnt lgkmcnt(0); s_barrier) is a workgroup barrier; empty asm statements are
         # compiler fences whose operand class "v" / "s" (a VGPR / SGPR) becomes "r"
         text = text.replace('asm volatile("s_waitcnt lgkmcnt(0)\\n\\ts_barrier" ::: "memory")', "__syncthreads()")
@@ -136,8 +163,6 @@ def _prepare_unit(unit: str, workdir: str, san: str = ""):
             text, nsub = re.subn(pat, rep, text, flags=re.S)
             if nsub == 0:
                 raise RuntimeError(f"{unit}.hip: the statement the simulation rewrites has changed: {pat[:50]!r}")
-        src = os.path.join(workdir, unit + ".sim.cpp")
-        open(src, "w").write(text)
         extra += ["-DSIM_FIBERS=1", "-D__shared__=static"]
         if unit == "select4" and san and "undefined" in san and not os.environ.get("HOSTSIM_SANITIZE_BOUNDS_ONLY"):
             # g++ 11: with ALL of -fsanitize=undefined the index check of `v[u]` on the ring's register set (a reference to
@@ -145,7 +170,15 @@ def _prepare_unit(unit: str, workdir: str, san: str = ""):
             # verified intact by an explicit check in front of it.  Either half alone is clean: this build carries every
             # check but `bounds`; HOSTSIM_SANITIZE=bounds HOSTSIM_SANITIZE_BOUNDS_ONLY=1 is the other half.
             extra += ["-fno-sanitize=bounds"]
+    src = os.path.join(workdir, unit + ".sim.cpp")
+    open(src, "w").write(text)
     return src, extra
+
+
+def _gxx(args) -> None:
+    """One g++ run.  A failure carries the compiler's stderr on its CalledProcessError (for the caller's failure text); the
+    warnings of a run that succeeds are passed on."""
+    sys.stderr.write(subprocess.run(["g++", *args], check=True, stderr=subprocess.PIPE, text=True).stderr)
 
 
 def _compile_all(units, workdir, flags, san=""):
@@ -154,32 +187,43 @@ def _compile_all(units, workdir, flags, san=""):
     def compile_unit(unit):
         obj = os.path.join(workdir, unit + ".o")
         src, extra = _prepare_unit(unit, workdir, san)
-        subprocess.run(["g++", "-x", "c++", *flags, *extra, "-c", src, "-o", obj], check=True)
+        _gxx(["-x", "c++", *flags, *extra, "-c", src, "-o", obj])
         return obj
 
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:   # (g++ runs outside the GIL)
         objs = list(pool.map(compile_unit, units))
     obj = os.path.join(workdir, "sim_runtime.o")
-    subprocess.run(["g++", *flags, "-c", os.path.join(HERE, "sim_runtime.cpp"), "-o", obj], check=True)
+    _gxx([*flags, "-c", os.path.join(HERE, "sim_runtime.cpp"), "-o", obj])
     return objs + [obj]
+
+
+def _library(units, workdir: str, name: str, san: str = "") -> str:
+    """g++ the units + sim_runtime.cpp into the shared library workdir/name: the one flag list of everything loaded into Python."""
+    if shutil.which("g++") is None:
+        raise RuntimeError("no g++")
+    os.makedirs(workdir, exist_ok=True)
+    _prepare_headers(workdir)
+    flags = ["-std=c++17", "-O1", "-fPIC", "-ffp-contract=off", "-I", workdir, "-I", HERE, "-I", CSRC]
+    if san:
+        flags += ["-g", f"-fsanitize={san}", "-fno-sanitize-recover=all" if os.environ.get("HOSTSIM_SANITIZE_FATAL") else "-fsanitize-recover=all"]
+    objs = _compile_all(units, workdir, flags, san)
+    out = os.path.join(workdir, name)
+    _gxx(["-shared", *([f"-fsanitize={san}"] if san else []), "-o", out, *objs])
+    return out
 
 
 def build(workdir: str) -> str:
     """g++ the simulated translation units (sources unchanged, except that an `extern __shared__ T name[];` of a fiber unit
     becomes a pointer to the workgroup's LDS buffer) + sim_runtime.cpp into workdir/libxclimhip_hostsim.so."""
-    if shutil.which("g++") is None:
-        raise RuntimeError("no g++")
-    _prepare_headers(workdir)
-    flags = ["-std=c++17", "-O1", "-fPIC", "-ffp-contract=off", "-I", workdir, "-I", HERE, "-I", CSRC]
-    # HOSTSIM_SANITIZE=undefined (or address,undefined with LD_PRELOAD=libasan.so): an audit build of the kernels under the
-    # compiler's sanitizers — out-of-bounds LDS / scratch accesses, shifts, signed overflow
-    san = os.environ.get("HOSTSIM_SANITIZE")
-    if san:
-        flags += ["-g", f"-fsanitize={san}", "-fno-sanitize-recover=all" if os.environ.get("HOSTSIM_SANITIZE_FATAL") else "-fsanitize-recover=all"]
-    objs = _compile_all(SIMULATED_UNITS + FIBER_UNITS, workdir, flags, san or "")
-    out = os.path.join(workdir, "libxclimhip_hostsim.so")
-    subprocess.run(["g++", "-shared", *([f"-fsanitize={san}"] if san else []), "-o", out, *objs], check=True)
-    return out
+    # HOSTSIM_SANITIZE=undefined (the switches are in README.md): an audit build of the kernels under the compiler's sanitizers —
+    # out-of-bounds LDS / scratch accesses, shifts, signed overflow
+    return _library(SIMULATED_UNITS + FIBER_UNITS, workdir, "libxclimhip_hostsim.so", os.environ.get("HOSTSIM_SANITIZE") or "")
+
+
+def build_unit_library(name: str, workdir: str) -> str:
+    """One of UNIT_LIBRARIES into workdir/libxclimhip_hostsim_<name>.so.  It is loaded into Python, so it never carries a
+    sanitizer: HOSTSIM_SANITIZE reaches build() alone, and the sanitizers of these units run in build_unit_driver's programs."""
+    return _library(UNIT_LIBRARIES[name][0], workdir, f"libxclimhip_hostsim_{name}.so")
 
 
 def build_shared(basetemp: str) -> str:
@@ -197,23 +241,34 @@ def build_shared(basetemp: str) -> str:
 STANDALONE_SANITIZE = "address,undefined"
 
 
-def build_standalone(workdir: str) -> str:
-    """The stand-alone sanitizer driver (standalone/san_driver.cpp: a C++ program with its own main, no Python in the process,
-    nothing preloaded): the NEW_UNITS' rewritten sources + sim_runtime.cpp + the driver, all with -g -O1
-    -fsanitize=address,undefined -fno-sanitize-recover=all, linked into workdir/san_driver."""
+def _program(units, workdir: str, source: str) -> str:
+    """A stand-alone sanitizer program (a C++ program with its own main, no Python in the process, nothing preloaded): the
+    units' rewritten sources + sim_runtime.cpp + standalone/<source>, all with -g -O1 -fsanitize=address,undefined
+    -fno-sanitize-recover=all, linked into workdir/<source without .cpp>."""
     if shutil.which("g++") is None:
         raise RuntimeError("no g++")
+    os.makedirs(workdir, exist_ok=True)
     _prepare_headers(workdir)
     # (-fno-var-tracking: line tables without variable-location tracking, which alone takes a minute on f64red / f64run)
     flags = ["-std=c++17", "-g", "-fno-var-tracking", "-O1", "-ffp-contract=off", f"-fsanitize={STANDALONE_SANITIZE}", "-fno-sanitize-recover=all",
              "-I", workdir, "-I", HERE, "-I", CSRC, "-I", os.path.join(ROOT, "include")]
-    objs = _compile_all(NEW_UNITS, workdir, flags, STANDALONE_SANITIZE)
-    out = os.path.join(workdir, "san_driver")
+    objs = _compile_all(units, workdir, flags, STANDALONE_SANITIZE)
+    out = os.path.join(workdir, source[:-len(".cpp")])
     # (the sanitizer runtimes linked statically: the program needs no particular order of shared libraries at start-up, whatever
     # the environment it is started in loads first)
-    subprocess.run(["g++", *flags, "-static-libasan", "-static-libubsan", "-o", out, os.path.join(HERE, "standalone", "san_driver.cpp"), *objs],
-                   check=True)
+    _gxx([*flags, "-static-libasan", "-static-libubsan", "-o", out, os.path.join(HERE, "standalone", source), *objs])
     return out
+
+
+def build_standalone(workdir: str) -> str:
+    """The manifest replayer of the NEW_UNITS (standalone/san_driver.cpp) as workdir/san_driver."""
+    return _program(NEW_UNITS, workdir, "san_driver.cpp")
+
+
+def build_unit_driver(name: str, workdir: str) -> str:
+    """The stand-alone sanitizer program of one of UNIT_LIBRARIES as workdir/<name>_driver."""
+    _, units, source = UNIT_LIBRARIES[name]
+    return _program(units, workdir, source)
 
 
 class _SimLib:
@@ -239,7 +294,7 @@ class _SimLib:
                 return getattr(self._mock, name)
             raise NotImplementedError(f"{name}: not simulated on the host (kernels written at ISA level, or a runtime service the "
                                       "simulation does not provide)") from None
-        fn.argtypes = _capi.SIGNATURES.get(name)
+        fn.argtypes = _capi.argtypes_of(name)
         fn.restype = _capi._RESTYPES.get(name, C.c_int)
         setattr(self, name, fn)
         return fn

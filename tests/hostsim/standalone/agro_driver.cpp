@@ -1,5 +1,5 @@
 // agro_driver — the five entry points of agro.hip on the host simulation under the compiler's sanitizers (TEST INFRASTRUCTURE
-// ONLY).  A program of its own: no Python in the process, nothing preloaded.  tests/test_hostsim_agro_cpu.py links it with
+// ONLY).  A program of its own: no Python in the process, nothing preloaded.  tests/test_hostsim_units_cpu.py links it with
 // agro.hip and sim_runtime.cpp, everything compiled with -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all.
 //
 // Every field is a malloc block of EXACTLY T * C elements, every output one of exactly its rows * C and every table one of
@@ -10,55 +10,12 @@
 // so that the season span ends on the last row; float32 and float64; 5 and 260 cells.  The program checks the return codes
 // and a few properties that need no reference (the ends of the Qian mean are NaN, sums are not negative, counts stay within
 // the rows selected); a sanitizer report aborts it.
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <vector>
-
+#include "driver_common.h"
 #include "xclim_hip_agro.h"
 
+const char* const kProgram = "agro_driver";
+
 namespace {
-
-int g_cases = 0;
-
-void fail(const char* what) {
-  fprintf(stderr, "agro_driver: %s\n", what);
-  exit(4);
-}
-
-void ok(int rc, const char* fn) {
-  if (rc != XH_OK) {
-    fprintf(stderr, "agro_driver: %s returned %d: %s\n", fn, rc, xh_last_error());
-    exit(3);
-  }
-}
-
-template <typename V>
-V* exact(const std::vector<V>& v) {   // a heap block of exactly the table (one element for an empty one)
-  V* p = (V*)malloc(sizeof(V) * (v.empty() ? 1 : v.size()));
-  if (!v.empty()) memcpy(p, v.data(), sizeof(V) * v.size());
-  return p;
-}
-
-template <typename V>
-V* block(int64_t n) {
-  return (V*)malloc(sizeof(V) * (size_t)(n > 0 ? n : 1));
-}
-
-template <typename TE>
-TE* field(int64_t T, int64_t C, unsigned seed, double base, double amp) {
-  TE* p = (TE*)malloc(sizeof(TE) * (size_t)(T * C));   // EXACTLY the field
-  unsigned s = seed;
-  for (int64_t i = 0; i < T * C; ++i) {
-    s = s * 1664525u + 1013904223u;
-    const double u = (double)(s >> 8) / (double)(1u << 24);
-    p[i] = (s >> 8) % 97 == 0 ? (TE)NAN : (TE)(base + amp * u);
-  }
-  return p;
-}
 
 struct Axis {   // a daily standard-calendar axis and the host tables the entry points take
   std::vector<int> year, month, day, doy;

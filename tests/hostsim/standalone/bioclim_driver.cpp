@@ -1,5 +1,5 @@
 // bioclim_driver — xh_bioclim of the host simulation under the compiler's sanitizers (TEST INFRASTRUCTURE ONLY).
-// A program of its own: no Python in the process, nothing preloaded.  tests/test_hostsim_bioclim_cpu.py links it with
+// A program of its own: no Python in the process, nothing preloaded.  tests/test_hostsim_units_cpu.py links it with
 // bioclim.hip and sim_runtime.cpp, everything compiled with -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all.
 //
 // Every field is a malloc block of EXACTLY T * C elements and every output one of exactly P * C, so that a read one row before
@@ -9,30 +9,11 @@
 // series with W = 3; float32 and float64; every output requested, and the quarter outputs alone.  The program checks the
 // return code and two properties that need no reference (the quarters of the short series are NaN, their step indices -1);
 // a sanitizer report aborts it.
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
+#include "driver_common.h"
 
-#include <vector>
-
-#include "xclim_hip.h"
+const char* const kProgram = "bioclim_driver";
 
 namespace {
-
-int g_cases = 0;
-
-template <typename TE>
-TE* field(int64_t T, int64_t C, unsigned seed, double base, double amp) {
-  TE* p = (TE*)malloc(sizeof(TE) * (size_t)(T * C));   // EXACTLY the field
-  unsigned s = seed;
-  for (int64_t i = 0; i < T * C; ++i) {
-    s = s * 1664525u + 1013904223u;
-    const double u = (double)(s >> 8) / (double)(1u << 24);
-    p[i] = (s >> 8) % 97 == 0 ? (TE)NAN : (TE)(base + amp * u);
-  }
-  return p;
-}
 
 template <typename TE>
 void run(int64_t T, int64_t C, const std::vector<int64_t>& step_off, const std::vector<int64_t>& seg_rows, int binned, int W,

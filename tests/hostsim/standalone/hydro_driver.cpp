@@ -1,5 +1,5 @@
 // hydro_driver — the four entry points of hydro.hip on the host simulation under the compiler's sanitizers (TEST INFRASTRUCTURE
-// ONLY).  A program of its own: no Python in the process, nothing preloaded.  tests/test_hostsim_hydro_cpu.py links it with
+// ONLY).  A program of its own: no Python in the process, nothing preloaded.  tests/test_hostsim_units_cpu.py links it with
 // hydro.hip (on fibers: k_sen_slope sorts in LDS behind barriers) and sim_runtime.cpp, everything compiled with -g -O1
 // -fsanitize=address,undefined -fno-sanitize-recover=all.
 //
@@ -10,57 +10,12 @@
 // series of 1, 5, 400 and 800 rows, windows 1, 3, 7, 31 and 32 (all five at 65 cells, 3 and 32 everywhere), Sen series of 0, 1,
 // 2, 3, 30, 64 and 181 years with absent years; float32 and float64; 1, 65 and 260 cells (1, 5 and 9 for the Sen slope: a workgroup of 64 fibers per series).  The program checks the return codes and a few properties that need no
 // reference; a sanitizer report aborts it.
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <vector>
-
+#include "driver_common.h"
 #include "xclim_hip_hydro.h"
 
+const char* const kProgram = "hydro_driver";
+
 namespace {
-
-int g_cases = 0;
-
-void fail(const char* what) {
-  fprintf(stderr, "hydro_driver: %s\n", what);
-  exit(4);
-}
-
-void ok(int rc, const char* fn) {
-  if (rc != XH_OK) {
-    fprintf(stderr, "hydro_driver: %s returned %d: %s\n", fn, rc, xh_last_error());
-    exit(3);
-  }
-}
-
-template <typename V>
-V* exact(const std::vector<V>& v) {   // a heap block of exactly the table (one element for an empty one)
-  V* p = (V*)malloc(sizeof(V) * (v.empty() ? 1 : v.size()));
-  if (!v.empty()) memcpy(p, v.data(), sizeof(V) * v.size());
-  return p;
-}
-
-template <typename V>
-V* block(int64_t n, int fill = 0x7B) {
-  V* p = (V*)malloc(sizeof(V) * (size_t)(n > 0 ? n : 1));
-  memset(p, fill, sizeof(V) * (size_t)(n > 0 ? n : 1));
-  return p;
-}
-
-template <typename TE>
-TE* field(int64_t T, int64_t C, unsigned seed, double base, double amp) {
-  TE* p = (TE*)malloc(sizeof(TE) * (size_t)(T * C > 0 ? T * C : 1));   // EXACTLY the field
-  unsigned s = seed;
-  for (int64_t i = 0; i < T * C; ++i) {
-    s = s * 1664525u + 1013904223u;
-    const double u = (double)(s >> 8) / (double)(1u << 24);
-    p[i] = (s >> 8) % 97 == 0 ? (TE)NAN : (TE)(base + amp * u);
-  }
-  return p;
-}
 
 template <typename TE>
 void run_fields(int64_t T, int64_t C, const std::vector<int64_t>& seg, bool every_window) {

@@ -1,5 +1,5 @@
 // rain_driver — the two entry points of rainseason.hip on the host simulation under the compiler's sanitizers (TEST
-// INFRASTRUCTURE ONLY).  A program of its own: no Python in the process, nothing preloaded.  tests/test_hostsim_rain_cpu.py links
+// INFRASTRUCTURE ONLY).  A program of its own: no Python in the process, nothing preloaded.  tests/test_hostsim_units_cpu.py links
 // it with rainseason.hip (compiled like the fiber units: its ring is dynamic LDS) and sim_runtime.cpp, everything compiled with -g
 // -O1 -fsanitize=address,undefined -fno-sanitize-recover=all.
 //
@@ -11,47 +11,14 @@
 // 400 rows (the second read of the decision row, a lag longer than the period), float32 and float64, 1, 65 and 260 cells, each
 // output alone; the zones with windows 1, 30 and one longer than the series, two edges and XH_ZONES_MAX_EDGES.  The program
 // checks the return codes and a few properties that need no reference; a sanitizer report aborts it.
-#include <math.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <vector>
-
+#include "driver_common.h"
 #include "xclim_hip_rain.h"
+
+const char* const kProgram = "rain_driver";
 
 namespace {
 
-int g_cases = 0;
-
-void fail(const char* what) {
-  fprintf(stderr, "rain_driver: %s\n", what);
-  exit(4);
-}
-
-void ok(int rc, const char* fn) {
-  if (rc != XH_OK) {
-    fprintf(stderr, "rain_driver: %s returned %d: %s\n", fn, rc, xh_last_error());
-    exit(3);
-  }
-}
-
-template <typename V>
-V* exact(const std::vector<V>& v) {   // a heap block of exactly the table (one element for an empty one)
-  V* p = (V*)malloc(sizeof(V) * (v.empty() ? 1 : v.size()));
-  if (!v.empty()) memcpy(p, v.data(), sizeof(V) * v.size());
-  return p;
-}
-
-template <typename V>
-V* block(int64_t n, int fill = 0x7B) {
-  V* p = (V*)malloc(sizeof(V) * (size_t)(n > 0 ? n : 1));
-  memset(p, fill, sizeof(V) * (size_t)(n > 0 ? n : 1));
-  return p;
-}
-
-// wet spells of a few rows, long moist stretches, dry stretches and a few NaN, in mm per day
+// (this driver's own field, not the uniform one of driver_common.h)  wet spells of a few rows, long moist stretches, dry stretches and a few NaN, in mm per day
 template <typename TE>
 TE* field(int64_t T, int64_t C, unsigned seed) {
   TE* p = (TE*)malloc(sizeof(TE) * (size_t)(T * C > 0 ? T * C : 1));   // EXACTLY the field

@@ -498,9 +498,9 @@ def refusals(dev):
 
 @pytest.fixture(scope="module")
 def sim(tmp_path_factory):
-    from test_hostsim_agro_cpu import sim_device
+    from test_hostsim_units_cpu import sim_device
 
-    return sim_device(tmp_path_factory)     # the one build of the session
+    return sim_device("agro", tmp_path_factory)    # the one build of the session
 
 
 def test_refusals_answer_before_any_launch(sim):

@@ -2,7 +2,7 @@
 reference's own tests (tests/golden/rain_known_answers.json: eight for rain_season, six for hardiness_zones) and the golden file
 tests/golden/rain_vectors.npz; the flag byte of ``xclim_amd.rainseason.rain_flags`` against ``select_time_mask`` applied period by
 period; what the mirror does not serve; header, ctypes table and library agree.  ``refusals`` and ``check_known_answers`` are
-shared with tests/test_gpu_rain.py (the device) and tests/test_hostsim_rain_cpu.py (the host simulation).
+shared with tests/test_gpu_rain.py (the device) and tests/test_hostsim_units_cpu.py (the host simulation).
 
 Every result is an integer (a day of year, a number of days, a zone) or NaN: every comparison is exact."""
 import ctypes

@@ -12,7 +12,7 @@ programme are cut to five pairs in which every length and every width occurs (so
 width there, not at every width x length pair); the strided cases run at 65 cells only, those of more than 60 s on fibers
 (the 31-day sliding-window trainings) not at all — xh_eqm_train_window / xh_dqm_train_window run in the "window_training"
 programme at 3 cells; xh_adapt_freq (rocPRIM) and the chill and BIO1-BIO19 units (simulation libraries of their own:
-tests/test_hostsim_chill_cpu.py, tests/test_hostsim_bioclim_cpu.py, which re-run their poisoned GPU modules) are not in this
+tests/test_hostsim_units_cpu.py, which re-runs their poisoned GPU modules) are not in this
 library."""
 import os
 import re

@@ -271,6 +271,13 @@ RAIN_MAX_WINDOW = 32    # XH_RAIN_MAX_WINDOW
 ZONES_MAX_EDGES = 32    # XH_ZONES_MAX_EDGES
 RAIN_START_WINDOW, RAIN_START_BOUNDS, RAIN_END_BOUNDS = 1, 2, 4   # the XH_RAIN_* flag bits
 _RESTYPES = {"xh_last_error": C.c_char_p}
+_SIGNATURE_TABLES = (SIGNATURES, UNIT_SIGNATURES, HYDRO_SIGNATURES, RAIN_SIGNATURES)
+
+
+def argtypes_of(name: str):
+    """The argtypes of an entry point, whichever header's table declares it; None for a name that no table holds."""
+    return next((table[name] for table in _SIGNATURE_TABLES if name in table), None)
+
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -297,9 +304,9 @@ def load_library() -> C.CDLL:
             lib = C.CDLL(_LIB_PATH)
         except OSError as err:  # pragma: no cover
             raise BackendUnavailable(f"cannot load {_LIB_PATH}: {err}") from err
-        for name, argtypes in {**SIGNATURES, **UNIT_SIGNATURES, **HYDRO_SIGNATURES, **RAIN_SIGNATURES}.items():
+        for name in (name for table in _SIGNATURE_TABLES for name in table):
             fn = getattr(lib, name)  # AttributeError if the header and the library diverge
-            fn.argtypes = argtypes
+            fn.argtypes = argtypes_of(name)
             fn.restype = _RESTYPES.get(name, _int)
         _lib = lib
         return lib
@@ -709,11 +716,6 @@ class Device:
         if self.trace is not None:  # launch log for the adapter tests: (entry point, arguments as passed)
             self.trace.append((name, args))
         fn = getattr(self.lib, name)
-        unit = UNIT_SIGNATURES.get(name) or HYDRO_SIGNATURES.get(name) or RAIN_SIGNATURES.get(name)
-        if unit is not None and not getattr(fn, "argtypes", None):
-            # a library object that declares the prototypes of SIGNATURES only (the host simulation's): without argtypes ctypes
-            # would pass a python int as a C int and refuse a float
-            fn.argtypes = unit
         with self.lock:
             _check(self.lib, fn(self.ctx, *args))
 

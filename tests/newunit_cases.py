@@ -473,3 +473,28 @@ def check_f64_percentile_doy_days(dev, C, years, window, days=(0, 1, 58, 180, 36
     exp = np.moveaxis(p_o[days], -1, 0)
     same_nan(got, exp, "percentile_doy")
     np.testing.assert_array_equal(got, exp)
+
+
+# ---- the checks every pitched (ctx, T, C, ld, ..., ld_out) entry point shares (hostargs.h) --------------------------------------
+def shared_refusals(call, T, C, tables=(), expect=None):
+    """One fault at a time, each answered with its code.  `call(**kw)` is the entry point on a valid call of T rows and C cells
+    with the given keywords changed: ctx (None = NULL), T, C, ld, ld_out, and for every host offset table of `tables` =
+    [(key, offsets, rows, too_many)] the table under `key` (None = NULL); `too_many` holds the keywords of the call with 65536
+    periods, or None where the table has no such limit.  `expect` = {fault: code} where an entry point answers otherwise.
+    The callers check afterwards that their outputs still hold the fill value."""
+    from xclim_amd._capi import XH_ERR_ARG as ARG, XH_ERR_LAYOUT as LAYOUT, XH_ERR_LIMIT as LIMIT
+
+    cases = [("NULL context", dict(ctx=None), ARG), ("T = -1", dict(T=-1), ARG), ("C = -1", dict(C=-1), ARG),
+             ("ld = C - 1", dict(ld=C - 1), LAYOUT), ("ld_out = C - 1", dict(ld_out=C - 1), LAYOUT),
+             ("T * ld + C >= 2^40", dict(ld=(1 << 40) // T + 1), LIMIT)]   # (needs no memory: the call refuses first)
+    for key, good, rows, too_many in tables:
+        assert good[0] == 0 and good[-1] <= rows and good[0] < good[-1]
+        low, high, back = good.copy(), good.copy(), good[::-1].copy()     # (back: inside [0, rows], and it goes down)
+        low[0], high[-1] = -1, rows + 1
+        cases += [(f"{key} NULL", {key: None}, ARG), (f"{key}[0] < 0", {key: low}, ARG), (f"{key}[-1] > rows", {key: high}, ARG),
+                  (f"{key} decreasing", {key: back}, ARG)]
+        if too_many is not None:
+            cases.append((f"{key}: 65536 periods", too_many, LIMIT))
+    for what, kw, code in cases:
+        got = call(**kw)
+        assert got == (expect or {}).get(what, code), (what, got)

@@ -421,6 +421,8 @@ def entry(dev, name):
 def refusals(dev):
     """Every refusal is a code that answers before anything is launched: the sentinel in the outputs is intact afterwards, and the
     same call with nothing wrong then runs.  On the device (tests/test_gpu_agro.py) and on the host simulation (below)."""
+    from newunit_cases import shared_refusals
+
     ARG, LAYOUT, LIMIT = _capi.XH_ERR_ARG, _capi.XH_ERR_LAYOUT, _capi.XH_ERR_LIMIT
     T, C, P = 40, 8, 2
     x = dev.to_device(np.full((T, C), 290.0))
@@ -436,8 +438,9 @@ def refusals(dev):
 
     deg = entry(dev, "xh_agro_degree_sum")
 
-    def degree(ld=C, ld_out=C, seg=seg, P=P, tas=x, tasmin=x, tasmax=x, k_cell=None, k_day=None, lat_idx=None, L=0, hi=out, bedd=out):
-        return deg(dev.ctx, T, C, ld, 1, d(tas), d(tasmin), d(tasmax), P, p(seg), _vp(0), d(k_cell), d(k_day), _vp(0), L, d(lat_idx), K2C,
+    def degree(ld=C, ld_out=C, seg=seg, P=P, tas=x, tasmin=x, tasmax=x, k_cell=None, k_day=None, lat_idx=None, L=0, hi=out, bedd=out,
+               T=T, C=C, ctx=dev.ctx):
+        return deg(ctx, T, C, ld, 1, d(tas), d(tasmin), d(tasmax), P, p(seg), _vp(0), d(k_cell), d(k_day), _vp(0), L, d(lat_idx), K2C,
                    10.0, 10.0, 1, 10.0, 13.0, 9.0, d(hi), d(bedd), d(cnt), ld_out)
 
     assert degree(ld=C - 1) == LAYOUT and degree(ld_out=C - 1) == LAYOUT                   # a pitch below the row width
@@ -448,13 +451,14 @@ def refusals(dev):
     assert degree(hi=None, bedd=None) == ARG                                               # no output requested
     assert degree(k_cell=kc, k_day=kd, lat_idx=li, L=1) == ARG                             # both k_cell and k_day
     assert degree(k_day=kd, L=1) == ARG                                                    # k_day without lat_idx
+    shared_refusals(degree, T, C, [("seg", seg, T, dict(seg=many, P=65536))])
 
     mo, mc, md, sm = np.array([0, 31, T], np.int64), np.array([1, 2], np.int32), np.array([31, 28], np.int32), np.array([0, 1, 2], np.int64)
     mon = entry(dev, "xh_agro_monthly")
 
-    def monthly(mo=mo, mc=mc, md=md, sm=sm, lat=kc, hemisphere=0, cni=out, di=out, pr=x, ld=C):
-        return mon(dev.ctx, T, C, ld, 1, d(x), d(x), d(pr), d(x), 2, p(mo), p(mc), p(md), P, p(sm), d(lat), hemisphere, K2C, 86400.0, 200.0,
-                   d(cni), _vp(0), d(di), d(cnt), C)
+    def monthly(mo=mo, mc=mc, md=md, sm=sm, lat=kc, hemisphere=0, cni=out, di=out, pr=x, ld=C, ld_out=C, P=P, T=T, C=C, ctx=dev.ctx):
+        return mon(ctx, T, C, ld, 1, d(x), d(x), d(pr), d(x), 2, p(mo), p(mc), p(md), P, p(sm), d(lat), hemisphere, K2C, 86400.0, 200.0,
+                   d(cni), _vp(0), d(di), d(cnt), ld_out)
 
     assert monthly(ld=C - 1) == LAYOUT
     for k in ("mo", "mc", "md", "sm"):
@@ -464,14 +468,16 @@ def refusals(dev):
     assert monthly(mc=np.array([1, 13], np.int32)) == ARG and monthly(md=np.array([31, 0], np.int32)) == ARG
     assert monthly(cni=None, di=None) == ARG and monthly(pr=None) == ARG
     assert monthly(hemisphere=3) == ARG and monthly(lat=None) == ARG
+    shared_refusals(monthly, T, C, [("sm", sm, 2, dict(sm=many, P=65536)), ("mo", mo, T, None)])
 
     doy = np.arange(1, T + 1, dtype=np.int32)
     sf, ef, d0 = np.array([0, 20], np.int64), np.array([5, -1], np.int64), np.zeros(P, np.int64)
     ldoy, ldays = np.ones(P, np.int32), np.full(P, 365, np.int32)
     eg = entry(dev, "xh_egdd")
 
-    def egdd(seg=seg, doy=doy, sf=sf, ef=ef, d0=d0, ldoy=ldoy, ldays=ldays, method=0, o=out, tasmin=x, ld_out=C):
-        return eg(dev.ctx, T, C, C, 1, d(tasmin), d(x), P, p(seg), p(doy), p(sf), p(ef), p(d0), p(ldoy), p(ldays), method, K2C, 5.0, d(o),
+    def egdd(seg=seg, doy=doy, sf=sf, ef=ef, d0=d0, ldoy=ldoy, ldays=ldays, method=0, o=out, tasmin=x, ld_out=C, ld=C, P=P, T=T, C=C,
+             ctx=dev.ctx):
+        return eg(ctx, T, C, ld, 1, d(tasmin), d(x), P, p(seg), p(doy), p(sf), p(ef), p(d0), p(ldoy), p(ldays), method, K2C, 5.0, d(o),
                   _vp(0), _vp(0), d(cnt), ld_out)
 
     assert egdd(ld_out=C - 1) == LAYOUT and egdd(tasmin=None) == ARG and egdd(o=None) == ARG and egdd(method=2) == ARG
@@ -480,6 +486,7 @@ def refusals(dev):
     assert egdd(seg=np.array([0, 30, 20], np.int64)) == ARG
     assert egdd(sf=np.array([0, 5], np.int64)) == ARG and egdd(ef=np.array([25, -1], np.int64)) == ARG     # a row outside its period
     assert egdd(doy=np.zeros(T, np.int32)) == ARG and egdd(ldays=np.full(P, 300, np.int32)) == ARG
+    shared_refusals(egdd, T, C, [("seg", seg, T, dict(seg=many, P=65536))])
 
     chu, qian = entry(dev, "xh_corn_heat_units"), entry(dev, "xh_qian_wma")
     assert chu(dev.ctx, T, C, C - 1, 1, d(x), d(x), K2C, 4.44, 10.0, d(out), C) == LAYOUT
@@ -487,6 +494,8 @@ def refusals(dev):
     assert chu(dev.ctx, T, C, C, 1, d(x), d(x), K2C, 4.44, 10.0, _vp(0), C) == ARG
     assert qian(dev.ctx, T, C, C, 1, d(x), d(out), C - 1) == LAYOUT and qian(dev.ctx, T, C, C, 1, _vp(0), d(out), C) == ARG
     assert qian(dev.ctx, -1, C, C, 1, d(x), d(out), C) == ARG
+    shared_refusals(lambda ctx=dev.ctx, T=T, C=C, ld=C, ld_out=C: chu(ctx, T, C, ld, 1, d(x), d(x), K2C, 4.44, 10.0, d(out), ld_out), T, C)
+    shared_refusals(lambda ctx=dev.ctx, T=T, C=C, ld=C, ld_out=C: qian(ctx, T, C, ld, 1, d(x), d(out), ld_out), T, C)
 
     dev.sync()
     np.testing.assert_array_equal(out.get(), np.full((T, C), -7.0))          # nothing was launched: the sentinels are intact

@@ -234,6 +234,8 @@ def test_padded_views_give_the_same_bits(dev, monkeypatch, C, pitch, dtype):
 
 # ---- refusals: every one a code, before anything is launched --------------------------------------------------------
 def test_refusals(dev):
+    from newunit_cases import shared_refusals
+
     T, C, S_, P = 30, 8, 5, 1
     x = dev.to_device(np.full((T, C), 280.0))
     out = dev.to_device(np.full((P, C), -7.0))
@@ -245,9 +247,9 @@ def test_refusals(dev):
     none = (_vp * 19)()
     p = lambda a: a.ctypes.data_as(_vp)  # noqa: E731
 
-    def call(ld=C, ld_out=C, so=so, fa=fa, sr=sr, ss=ss, W=13, outputs=outs, tas=_vp(x.ptr), S=S_):
+    def call(ld=C, ld_out=C, so=so, fa=fa, sr=sr, ss=ss, W=13, outputs=outs, tas=_vp(x.ptr), S=S_, P=P, T=T, C=C, ctx=dev.ctx):
         tab = [p(a) if a is not None else _vp(0) for a in (so, fa, sr, ss)]
-        return dev.lib.xh_bioclim(dev.ctx, T, C, ld, 1, tas, _vp(0), _vp(0), _vp(0), S, tab[0], tab[1], 1, P, tab[2], tab[3], W, 0.0, 1.0,
+        return dev.lib.xh_bioclim(ctx, T, C, ld, 1, tas, _vp(0), _vp(0), _vp(0), S, tab[0], tab[1], 1, P, tab[2], tab[3], W, 0.0, 1.0,
                                   0.0, outputs, _vp(0), _vp(0), ld_out)
 
     assert call(ld=C - 1) == XH_ERR_LAYOUT and call(ld_out=C - 1) == XH_ERR_LAYOUT
@@ -263,6 +265,8 @@ def test_refusals(dev):
     quarters = (_vp * 19)()
     quarters[9] = out.ptr
     assert call(outputs=quarters, sr=np.array([0, T], np.int64), ss=np.array([0, 4], np.int64)) == XH_ERR_ARG   # steps that stop before the rows
+    many = dict(sr=np.zeros(65538, np.int64), ss=np.zeros(65538, np.int64), P=65536)
+    shared_refusals(call, T, C, [("sr", sr, T, many), ("ss", ss, S_, many), ("so", so, T, None)])
     dev.sync()
     np.testing.assert_array_equal(out.get(), np.full((P, C), -7.0))                # nothing was launched: the sentinel is intact
     assert call() == 0                                                             # and the same call with nothing wrong runs

@@ -302,6 +302,45 @@ def test_a_stride_below_the_width_is_refused(dev):
                                       _vp(0), 0.0, K2C, 0, _vp(0), _vp(0), _vp(0), _vp(out.ptr), ld_out) == XH_ERR_LAYOUT
 
 
+def test_refusals_answer_before_any_launch(dev):
+    """The faults every pitched entry point answers (tests/newunit_cases.py: shared_refusals), one at a time; seg is a device
+    pointer here, so of a table's faults only NULL and the 65535 limit apply.  The sentinel is intact afterwards, and the same
+    calls with nothing wrong then run."""
+    from newunit_cases import shared_refusals
+    from xclim_amd._capi import XH_ERR_ARG, XH_ERR_LIMIT
+
+    C, D, P = 8, 2, 2
+    x = dev.to_device(np.full((24 * D, C), 280.0))
+    tn = dev.to_device(np.full((D, C), 275.0))
+    seg = dev.to_device(np.array([0, 24, 24 * D], np.int64))
+    dseg = dev.to_device(np.array([0, 1, D], np.int64))
+    dl = dev.to_device(np.full((D, 1), 12.0))
+    li = dev.to_device(np.zeros(C, np.int32))
+    out = dev.to_device(np.full((24 * D, C), -7.0))
+
+    def hourly(ctx=dev.ctx, T=24 * D, C=C, ld=C, ld_out=C, P=P, seg=_vp(seg.ptr)):
+        return dev.lib.xh_chill_hourly(ctx, T, C, ld, 1, _vp(x.ptr), 24, P, seg, _vp(0), 0.0, K2C, 0, _vp(0), _vp(0), _vp(0), _vp(out.ptr),
+                                       ld_out)
+
+    def daily(ctx=dev.ctx, T=D, C=C, ld=C, ld_out=C, P=P, seg=_vp(dseg.ptr)):
+        return dev.lib.xh_chill_daily(ctx, T, C, ld, 1, _vp(tn.ptr), _vp(tn.ptr), _vp(dl.ptr), 1, _vp(li.ptr), P, seg, _vp(0), 0.0, K2C, 0,
+                                      _vp(0), _vp(0), _vp(0), _vp(out.ptr), ld_out)
+
+    shared_refusals(hourly, 24 * D, C)
+    shared_refusals(daily, D, C)
+    for call in (hourly, daily):
+        assert call(seg=_vp(0)) == XH_ERR_ARG and call(P=-1) == XH_ERR_ARG and call(P=65536) == XH_ERR_LIMIT
+    dev.sync()
+    np.testing.assert_array_equal(out.get(), np.full((24 * D, C), -7.0))
+    assert hourly() == 0
+    dev.sync()
+    assert (out.get() != -7.0).all()
+    out = dev.to_device(np.full((24 * D, C), -7.0))
+    assert daily() == 0
+    dev.sync()
+    assert (out.get() != -7.0).all()
+
+
 # ---- the adapter ---------------------------------------------------------------------------------------------------
 @pytest.fixture()
 def agromod(dev):

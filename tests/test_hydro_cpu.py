@@ -399,6 +399,8 @@ def entry(dev, name):
 def refusals(dev):
     """Every refusal is a code that answers before anything is launched: the sentinel in the outputs is intact afterwards, and the
     same call with nothing wrong then runs.  On the device (tests/test_gpu_hydro.py) and on the host simulation (below)."""
+    from newunit_cases import shared_refusals
+
     ARG, LAYOUT, LIMIT = _capi.XH_ERR_ARG, _capi.XH_ERR_LAYOUT, _capi.XH_ERR_LIMIT
     T, C, P = 40, 8, 2
     x = dev.to_device(np.linspace(1.0, 9.0, T * C).reshape(T, C))
@@ -410,8 +412,8 @@ def refusals(dev):
     many = np.zeros(65538, np.int64)
     fl, me, ap, se = (entry(dev, n) for n in HYDRO_TABLE)
 
-    def flow(ld=C, ld_out=C, seg=seg, P=P, q=x, bfi=out, rbi=out, valid=cnt, T=T):
-        return fl(dev.ctx, T, C, ld, 1, d(q), P, p(seg), d(bfi), d(rbi), _vp(0), _vp(0), d(valid), ld_out)
+    def flow(ld=C, ld_out=C, seg=seg, P=P, q=x, bfi=out, rbi=out, valid=cnt, T=T, C=C, ctx=dev.ctx):
+        return fl(ctx, T, C, ld, 1, d(q), P, p(seg), d(bfi), d(rbi), _vp(0), _vp(0), d(valid), ld_out)
 
     assert flow(ld=C - 1) == LAYOUT and flow(ld_out=C - 1) == LAYOUT                       # a pitch below the row width
     assert flow(seg=None) == ARG and flow(q=None) == ARG and flow(T=-1) == ARG              # NULL arguments, a negative shape
@@ -419,30 +421,33 @@ def refusals(dev):
     assert flow(seg=np.array([0, 20, T + 1], np.int64)) == ARG and flow(seg=np.array([-1, 20, T], np.int64)) == ARG
     assert flow(seg=many, P=65536) == LIMIT                                                  # more than 65535 periods
     assert flow(bfi=None, rbi=None, valid=None) == ARG                                       # no output requested
+    shared_refusals(flow, T, C, [("seg", seg, T, dict(seg=many, P=65536))])
 
-    def melt(ld=C, ld_out=C, seg=seg, P=P, snw=x, pr=x, window=3, o=out):
-        return me(dev.ctx, T, C, ld, 1, d(snw), d(pr), 86400.0, window, P, p(seg), d(o), ld_out)
+    def melt(ld=C, ld_out=C, seg=seg, P=P, snw=x, pr=x, window=3, o=out, T=T, C=C, ctx=dev.ctx):
+        return me(ctx, T, C, ld, 1, d(snw), d(pr), 86400.0, window, P, p(seg), d(o), ld_out)
 
     assert melt(ld=C - 1) == LAYOUT and melt(ld_out=C - 1) == LAYOUT
     assert melt(seg=None) == ARG and melt(snw=None) == ARG and melt(o=None) == ARG and melt(window=0) == ARG
     assert melt(seg=np.array([0, 30, 20], np.int64)) == ARG and melt(seg=many, P=65536) == LIMIT
     assert melt(window=hydrology.HYDRO_MAX_WINDOW + 1) == LIMIT
+    shared_refusals(melt, T, C, [("seg", seg, T, dict(seg=many, P=65536))])
 
     w = H.api_weights(7, 0.935)
 
-    def api(ld=C, ld_out=C, pr=x, window=7, weights=w, o=out):
-        return ap(dev.ctx, T, C, ld, 1, d(pr), 1.0, window, p(weights), d(o), ld_out)
+    def api(ld=C, ld_out=C, pr=x, window=7, weights=w, o=out, T=T, C=C, ctx=dev.ctx):
+        return ap(ctx, T, C, ld, 1, d(pr), 1.0, window, p(weights), d(o), ld_out)
 
     assert api(ld=C - 1) == LAYOUT and api(ld_out=C - 1) == LAYOUT
     assert api(pr=None) == ARG and api(weights=None) == ARG and api(o=None) == ARG and api(window=0) == ARG
     assert api(window=hydrology.HYDRO_MAX_WINDOW + 1, weights=np.ones(40)) == LIMIT
+    shared_refusals(api, T, C)
 
     Y = 10
     po = np.arange(Y, dtype=np.int64).reshape(Y, 1)
     slope, pv, n1 = dev.to_device(np.full((1, C), -7.0)), dev.to_device(np.full((1, C), -7.0)), dev.to_device(np.full((1, C), -7, np.int32))
 
-    def sen(ld=C, ld_out=C, xx=x, po=po, Y=Y, K=1, s=slope, pp=pv):
-        return se(dev.ctx, T, C, ld, 1, d(xx), Y, K, p(po), d(s), d(pp), d(n1), ld_out)
+    def sen(ld=C, ld_out=C, xx=x, po=po, Y=Y, K=1, s=slope, pp=pv, T=T, C=C, ctx=dev.ctx):
+        return se(ctx, T, C, ld, 1, d(xx), Y, K, p(po), d(s), d(pp), d(n1), ld_out)
 
     assert sen(ld=C - 1) == LAYOUT and sen(ld_out=C - 1) == LAYOUT
     assert sen(xx=None) == ARG and sen(po=None) == ARG and sen(s=None, pp=None) == ARG and sen(Y=-1) == ARG
@@ -454,6 +459,7 @@ def refusals(dev):
     big = hydrology.SEN_MAX_YEARS + 1
     assert sen(po=np.zeros((big, 1), np.int64), Y=big) == LIMIT                              # one year beyond the limit
     assert sen(po=np.zeros((1, 65536), np.int64), Y=1, K=65536) == LIMIT
+    shared_refusals(sen, T, C)
 
     dev.sync()
     np.testing.assert_array_equal(out.get(), np.full((T, C), -7.0))          # nothing was launched: the sentinels are intact

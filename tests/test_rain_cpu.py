@@ -356,6 +356,8 @@ def entry(dev, name):
 def refusals(dev):
     """Every refusal is a code that answers before anything is launched: the sentinel in the outputs is intact afterwards, and the
     same call with nothing wrong then runs.  On the device (tests/test_gpu_rain.py) and, through it, on the host simulation."""
+    from newunit_cases import shared_refusals
+
     ARG, LAYOUT, LIMIT = _capi.XH_ERR_ARG, _capi.XH_ERR_LAYOUT, _capi.XH_ERR_LIMIT
     T, C, P = 40, 8, 2
     x = dev.to_device(np.linspace(1.0, 9.0, T * C).reshape(T, C))
@@ -368,8 +370,9 @@ def refusals(dev):
     doy = np.arange(1, T + 1, dtype=np.int32)
     rs, rz = (entry(dev, n) for n in RAIN_TABLE)
 
-    def rain(ld=C, ld_out=C, seg=seg, P=P, pr=x, flags=flags, doy=doy, ww=3, wnd=5, wd=4, ts=0, we=3, te=0, s=out, e=out, ln=out, T=T):
-        return rs(dev.ctx, T, C, ld, 1, d(pr), 1.0, P, p(seg), p(flags), p(doy), 25.0, ww, wnd, 1.0, wd, ts, 0.0, we, te, d(s), d(e), d(ln), ld_out)
+    def rain(ld=C, ld_out=C, seg=seg, P=P, pr=x, flags=flags, doy=doy, ww=3, wnd=5, wd=4, ts=0, we=3, te=0, s=out, e=out, ln=out, T=T, C=C,
+             ctx=dev.ctx):
+        return rs(ctx, T, C, ld, 1, d(pr), 1.0, P, p(seg), p(flags), p(doy), 25.0, ww, wnd, 1.0, wd, ts, 0.0, we, te, d(s), d(e), d(ln), ld_out)
 
     assert rain(ld=C - 1) == LAYOUT and rain(ld_out=C - 1) == LAYOUT                       # a pitch below the row width
     assert rain(seg=None) == ARG and rain(pr=None) == ARG and rain(flags=None) == ARG and rain(doy=None) == ARG and rain(T=-1) == ARG
@@ -388,16 +391,18 @@ def refusals(dev):
     assert rain(doy=bad) == ARG
     bad[7] = 0
     assert rain(doy=bad) == ARG
+    shared_refusals(rain, T, C, [("seg", seg, T, dict(seg=many, P=65536))])
 
     edges = np.array([0.0, 2.0, 4.0, 6.0])
 
-    def zones(ld=C, ld_out=C, xx=x, window=3, n=4, e=edges, o=out, P=T):
-        return rz(dev.ctx, P, C, ld, 1, d(xx), window, n, p(e), d(o), ld_out)
+    def zones(ld=C, ld_out=C, xx=x, window=3, n=4, e=edges, o=out, P=T, C=C, ctx=dev.ctx):
+        return rz(ctx, P, C, ld, 1, d(xx), window, n, p(e), d(o), ld_out)
 
     assert zones(ld=C - 1) == LAYOUT and zones(ld_out=C - 1) == LAYOUT
     assert zones(xx=None) == ARG and zones(e=None) == ARG and zones(o=None) == ARG and zones(window=0) == ARG and zones(P=-1) == ARG
     assert zones(n=1) == ARG and zones(e=np.array([0.0, 2.0, 2.0, 6.0])) == ARG and zones(e=np.array([0.0, np.nan, 2.0, 6.0])) == ARG
     assert zones(n=_capi.ZONES_MAX_EDGES + 1, e=np.arange(40.0)) == LIMIT
+    shared_refusals(lambda T=T, **kw: zones(P=T, **kw), T, C)
 
     dev.sync()
     np.testing.assert_array_equal(out.get(), np.full((T, C), -7.0))          # nothing was launched: the sentinels are intact

@@ -36,15 +36,6 @@ namespace {
 
 constexpr int AGRO_BATCH = 8;
 
-template <typename TE>
-__device__ __forceinline__ TE ldr(const void* p, int64_t i) {
-  return reinterpret_cast<const TE*>(p)[i];
-}
-template <typename TE>
-__device__ __forceinline__ double ldw(const void* p, int64_t i) {
-  return (double)ldr<TE>(p, i);
-}
-
 // ---- xh_agro_degree_sum ---------------------------------------------------------------------------------------------
 struct DegArgs {
   const void *tas, *tasmin, *tasmax;
@@ -81,9 +72,9 @@ __global__ void __launch_bounds__(XH_BLOCK) k_agro_degree_sum(DegArgs a) {
         kd[u] = kc;
         if (on[u]) {
           const int64_t i = r * a.ld + c;
-          tx[u] = ldr<TE>(a.tasmax, i);
-          if (HI) tg[u] = ldr<TE>(a.tas, i);
-          if (BEDD) tn[u] = ldr<TE>(a.tasmin, i);
+          tx[u] = xh_ld<TE>(a.tasmax, i);
+          if (HI) tg[u] = xh_ld<TE>(a.tas, i);
+          if (BEDD) tn[u] = xh_ld<TE>(a.tasmin, i);
           if (a.k_day) kd[u] = a.k_day[r * a.L + li];
         }
       }
@@ -165,17 +156,17 @@ __global__ void __launch_bounds__(XH_BLOCK) k_agro_monthly(MonArgs a) {
       const int64_t i = r * a.ld + c;
       bool present = true;
       if (a.tasmin && (cni_m || a.valid_out)) {
-        const double x = ldw<TE>(a.tasmin, i) - a.sub_C;
+        const double x = xh_ldw<TE>(a.tasmin, i) - a.sub_C;
         present = present && x == x;
         if (cni_m && x == x) cni_s += x, cni_n += 1;
       }
       if (a.tas) {
-        const double x = ldw<TE>(a.tas, i) - a.sub_C;
+        const double x = xh_ldw<TE>(a.tas, i) - a.sub_C;
         present = present && x == x;
         if (x == x) ts += x, tn += 1;
       }
       if (a.valid_out && a.pr) {
-        const double x = ldw<TE>(a.pr, i), e = ldw<TE>(a.evspsblpot, i);
+        const double x = xh_ldw<TE>(a.pr, i), e = xh_ldw<TE>(a.evspsblpot, i);
         present = present && x == x && e == e;
       }
       valid += present ? 1 : 0;
@@ -196,7 +187,7 @@ __global__ void __launch_bounds__(XH_BLOCK) k_agro_monthly(MonArgs a) {
       double E = 0.0, Pm = 0.0;
       for (int64_t r = r0; r < r1; ++r) {
         const int64_t i = r * a.ld + c;
-        const double e = ldw<TE>(a.evspsblpot, i) * a.per_day, x = ldw<TE>(a.pr, i) * a.per_day;
+        const double e = xh_ldw<TE>(a.evspsblpot, i) * a.per_day, x = xh_ldw<TE>(a.pr, i) * a.per_day;
         if (e == e) E += e;
         if (x == x) Pm += x;
       }
@@ -235,8 +226,8 @@ struct EgddArgs {
 template <typename TE>
 __device__ __forceinline__ double egdd_tas(const EgddArgs& a, int64_t r, int64_t c, double& tn) {
   const int64_t i = r * a.ld + c;
-  tn = ldw<TE>(a.tasmin, i) - a.sub_C;
-  return (tn + (ldw<TE>(a.tasmax, i) - a.sub_C)) / 2;
+  tn = xh_ldw<TE>(a.tasmin, i) - a.sub_C;
+  return (tn + (xh_ldw<TE>(a.tasmax, i) - a.sub_C)) / 2;
 }
 
 // doy_to_days_since(da) with start=None (calendar.py:1050-1059): days since the period's label
@@ -320,7 +311,7 @@ __global__ void __launch_bounds__(XH_BLOCK) k_corn_heat_units(ElemArgs e) {
   const int64_t c = (int64_t)blockIdx.x * XH_BLOCK + threadIdx.x;
   if (c >= e.C) return;
   for (int64_t r = blockIdx.y; r < e.T; r += gridDim.y) {
-    const double tn = ldw<TE>(e.a, r * e.ld + c) - e.sub_C, tx = ldw<TE>(e.b, r * e.ld + c) - e.sub_C;
+    const double tn = xh_ldw<TE>(e.a, r * e.ld + c) - e.sub_C, tx = xh_ldw<TE>(e.b, r * e.ld + c) - e.sub_C;
     const double dn = tn - e.thresh_a, dx = tx - e.thresh_b;
     // :129-139: each half is 0 where its own comparison is false, and a comparison with NaN is false
     const double yn = tn > e.thresh_a ? 1.8 * dn : 0.0;
@@ -336,8 +327,8 @@ __global__ void __launch_bounds__(XH_BLOCK) k_qian_wma(ElemArgs e) {
   for (int64_t r = blockIdx.y; r < e.T; r += gridDim.y) {
     double v = xh_nan64();  // rolling(5, center=True).construct pads with NaN: NaN within 2 rows of either end
     if (r >= 2 && r + 2 < e.T) {
-      const double w0 = ldw<TE>(e.a, (r - 2) * e.ld + c), w1 = ldw<TE>(e.a, (r - 1) * e.ld + c), w2 = ldw<TE>(e.a, r * e.ld + c),
-                   w3 = ldw<TE>(e.a, (r + 1) * e.ld + c), w4 = ldw<TE>(e.a, (r + 2) * e.ld + c);
+      const double w0 = xh_ldw<TE>(e.a, (r - 2) * e.ld + c), w1 = xh_ldw<TE>(e.a, (r - 1) * e.ld + c), w2 = xh_ldw<TE>(e.a, r * e.ld + c),
+                   w3 = xh_ldw<TE>(e.a, (r + 1) * e.ld + c), w4 = xh_ldw<TE>(e.a, (r + 2) * e.ld + c);
       v = (((w0 * 0.0625 + w1 * 0.25) + w2 * 0.375) + w3 * 0.25) + w4 * 0.0625;
     }
     e.out[r * e.ld_out + c] = v;
@@ -345,27 +336,6 @@ __global__ void __launch_bounds__(XH_BLOCK) k_qian_wma(ElemArgs e) {
 }
 
 // ---- host front end -------------------------------------------------------------------------------------------------
-int agro_shape_checks(const char* fn, xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int64_t out_rows, int64_t ld_out) {
-  XH_REQUIRE(ctx, XH_ERR_ARG, "%s: NULL context", fn);
-  XH_REQUIRE(T >= 0 && C >= 0 && out_rows >= 0, XH_ERR_ARG, "%s: negative shape", fn);
-  int rc = xh_check_rows(fn, ld, C, "ld");
-  if (!rc) rc = xh_check_rows(fn, ld_out, C, "ld_out");
-  if (rc) return rc;
-  XH_REQUIRE(T * ld + C < ((int64_t)1 << 40) && out_rows * ld_out + C < ((int64_t)1 << 40), XH_ERR_LIMIT, "%s: field too large", fn);
-  return XH_OK;
-}
-
-// a period table: non-NULL, at most 65535 periods, offsets non-decreasing within [0, rows]
-int agro_periods(const char* fn, const int64_t* seg, int64_t P, int64_t rows, const char* what) {
-  XH_REQUIRE(seg, XH_ERR_ARG, "%s: NULL %s offsets", fn, what);
-  XH_REQUIRE(P >= 0, XH_ERR_ARG, "%s: negative shape", fn);
-  XH_REQUIRE(P <= 65535, XH_ERR_LIMIT, "%s: at most 65535 periods, got %lld", fn, (long long)P);
-  XH_REQUIRE(seg[0] >= 0 && seg[P] <= rows, XH_ERR_ARG, "%s: %s offsets outside [0, %lld]", fn, what, (long long)rows);
-  for (int64_t p = 0; p < P; ++p)
-    XH_REQUIRE(seg[p] <= seg[p + 1], XH_ERR_ARG, "%s: %s offsets must be non-decreasing", fn, what);
-  return XH_OK;
-}
-
 dim3 agro_grid(int64_t C, int64_t rows) {
   return dim3((unsigned)cdiv64(C, XH_BLOCK), (unsigned)(rows < 1 ? 1 : (rows > 65535 ? 65535 : rows)));
 }
@@ -378,8 +348,8 @@ int xh_agro_degree_sum(xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int f64, c
                        double thresh_hi, double thresh_bedd, int tr_adj, double low_dtr, double high_dtr, double max_dd,
                        double* hi_out, double* bedd_out, int32_t* valid_out, int64_t ld_out) {
   const char* fn = "xh_agro_degree_sum";
-  int rc = agro_shape_checks(fn, ctx, T, C, ld, P, ld_out);
-  if (!rc) rc = agro_periods(fn, seg, P, T, "period");
+  int rc = xh_check_pitched(fn, ctx, T, C, ld, P, ld_out);
+  if (!rc) rc = xh_check_offsets(fn, seg, P, T, "period");
   if (rc) return rc;
   XH_REQUIRE(hi_out || bedd_out, XH_ERR_ARG, "%s: no output requested (hi_out or bedd_out)", fn);
   XH_REQUIRE(tasmax && (!hi_out || tas) && (!bedd_out || tasmin), XH_ERR_ARG, "%s: a field needed by the requested outputs is NULL", fn);
@@ -419,15 +389,11 @@ int xh_agro_degree_sum(xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int f64, c
   a.sub_C = sub_C, a.thresh_hi = thresh_hi, a.thresh_bedd = thresh_bedd;
   a.low_dtr = low_dtr, a.high_dtr = high_dtr, a.max_dd = max_dd, a.tr_adj = tr_adj != 0;
   const dim3 g((unsigned)cdiv64(C, XH_BLOCK), (unsigned)P), b(XH_BLOCK);
-#define AGRO_LAUNCH(TE)                                                                                              \
-  do {                                                                                                               \
-    if (hi_out && bedd_out) hipLaunchKernelGGL((k_agro_degree_sum<TE, true, true>), g, b, 0, ctx->stream, a);         \
-    else if (hi_out) hipLaunchKernelGGL((k_agro_degree_sum<TE, true, false>), g, b, 0, ctx->stream, a);               \
-    else hipLaunchKernelGGL((k_agro_degree_sum<TE, false, true>), g, b, 0, ctx->stream, a);                           \
-  } while (0)
-  if (f64) AGRO_LAUNCH(double);
-  else AGRO_LAUNCH(float);
-#undef AGRO_LAUNCH
+  xh_by_width(f64, [&](auto w) {
+    if (hi_out && bedd_out) hipLaunchKernelGGL((k_agro_degree_sum<XH_WIDTH(w), true, true>), g, b, 0, ctx->stream, a);
+    else if (hi_out) hipLaunchKernelGGL((k_agro_degree_sum<XH_WIDTH(w), true, false>), g, b, 0, ctx->stream, a);
+    else hipLaunchKernelGGL((k_agro_degree_sum<XH_WIDTH(w), false, true>), g, b, 0, ctx->stream, a);
+  });
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
@@ -438,19 +404,16 @@ int xh_agro_monthly(xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int f64, cons
                     double sub_C, double per_day, double wo, double* cni_out, double* mtwm_out, double* di_out,
                     int32_t* valid_out, int64_t ld_out) {
   const char* fn = "xh_agro_monthly";
-  int rc = agro_shape_checks(fn, ctx, T, C, ld, P, ld_out);
+  int rc = xh_check_pitched(fn, ctx, T, C, ld, P, ld_out);
   if (rc) return rc;
   XH_REQUIRE(M >= 0 && M < ((int64_t)1 << 31), XH_ERR_ARG, "%s: bad month count", fn);
   XH_REQUIRE(month_cal && month_days, XH_ERR_ARG, "%s: NULL month table", fn);
-  rc = agro_periods(fn, seg_months, P, M, "period (month)");
+  rc = xh_check_offsets(fn, seg_months, P, M, "month period");
+  if (!rc) rc = xh_check_offsets(fn, month_off, M, T, "month", M);  // (the month count has its own check above)
   if (rc) return rc;
-  XH_REQUIRE(month_off, XH_ERR_ARG, "%s: NULL month offsets", fn);
-  XH_REQUIRE(month_off[0] >= 0 && month_off[M] <= T, XH_ERR_ARG, "%s: month offsets outside [0, T]", fn);
-  for (int64_t m = 0; m < M; ++m) {
-    XH_REQUIRE(month_off[m] <= month_off[m + 1], XH_ERR_ARG, "%s: month offsets must be non-decreasing", fn);
+  for (int64_t m = 0; m < M; ++m)
     XH_REQUIRE(month_cal[m] >= 1 && month_cal[m] <= 12 && month_days[m] >= 1, XH_ERR_ARG, "%s: month %lld: calendar month %d, %d days", fn,
                (long long)m, month_cal[m], month_days[m]);
-  }
   XH_REQUIRE(cni_out || mtwm_out || di_out, XH_ERR_ARG, "%s: no output requested (cni_out, mtwm_out or di_out)", fn);
   XH_REQUIRE((!cni_out || tasmin) && (!mtwm_out || tas) && (!di_out || (pr && evspsblpot)), XH_ERR_ARG,
              "%s: a field needed by the requested outputs is NULL", fn);
@@ -474,8 +437,7 @@ int xh_agro_monthly(xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int f64, cons
   a.M = M, a.C = C, a.ld = ld, a.ld_out = ld_out;
   a.sub_C = sub_C, a.per_day = per_day, a.wo = wo, a.hemisphere = hemisphere;
   const dim3 g((unsigned)cdiv64(C, XH_BLOCK), (unsigned)P);
-  if (f64) hipLaunchKernelGGL(k_agro_monthly<double>, g, dim3(XH_BLOCK), 0, ctx->stream, a);
-  else hipLaunchKernelGGL(k_agro_monthly<float>, g, dim3(XH_BLOCK), 0, ctx->stream, a);
+  xh_by_width(f64, [&](auto w) { hipLaunchKernelGGL(k_agro_monthly<XH_WIDTH(w)>, g, dim3(XH_BLOCK), 0, ctx->stream, a); });
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
@@ -485,8 +447,8 @@ int xh_egdd(xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int f64, const void* 
             const int32_t* label_doy, const int32_t* label_days, int method, double sub_C, double thresh, double* egdd_out,
             double* start_out, double* end_out, int32_t* valid_out, int64_t ld_out) {
   const char* fn = "xh_egdd";
-  int rc = agro_shape_checks(fn, ctx, T, C, ld, P, ld_out);
-  if (!rc) rc = agro_periods(fn, seg, P, T, "period");
+  int rc = xh_check_pitched(fn, ctx, T, C, ld, P, ld_out);
+  if (!rc) rc = xh_check_offsets(fn, seg, P, T, "period");
   if (rc) return rc;
   XH_REQUIRE(tasmin && tasmax, XH_ERR_ARG, "%s: NULL field", fn);
   XH_REQUIRE(doy && start_from && end_from && day0 && label_doy && label_days, XH_ERR_ARG, "%s: NULL table", fn);
@@ -518,8 +480,7 @@ int xh_egdd(xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int f64, const void* 
   a.T = T, a.C = C, a.ld = ld, a.ld_out = ld_out;
   a.sub_C = sub_C, a.thresh = thresh, a.method = method;
   const dim3 g((unsigned)cdiv64(C, XH_BLOCK), (unsigned)P);
-  if (f64) hipLaunchKernelGGL(k_egdd<double>, g, dim3(XH_BLOCK), 0, ctx->stream, a);
-  else hipLaunchKernelGGL(k_egdd<float>, g, dim3(XH_BLOCK), 0, ctx->stream, a);
+  xh_by_width(f64, [&](auto w) { hipLaunchKernelGGL(k_egdd<XH_WIDTH(w)>, g, dim3(XH_BLOCK), 0, ctx->stream, a); });
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
@@ -527,26 +488,24 @@ int xh_egdd(xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int f64, const void* 
 int xh_corn_heat_units(xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int f64, const void* tasmin, const void* tasmax,
                        double sub_C, double thresh_tasmin, double thresh_tasmax, double* out, int64_t ld_out) {
   const char* fn = "xh_corn_heat_units";
-  const int rc = agro_shape_checks(fn, ctx, T, C, ld, T, ld_out);
+  const int rc = xh_check_pitched(fn, ctx, T, C, ld, T, ld_out);
   if (rc) return rc;
   XH_REQUIRE(tasmin && tasmax && out, XH_ERR_ARG, "%s: NULL argument", fn);
   if (T == 0 || C == 0) return XH_OK;
   ElemArgs e{tasmin, tasmax, out, T, C, ld, ld_out, sub_C, thresh_tasmin, thresh_tasmax};
-  if (f64) hipLaunchKernelGGL(k_corn_heat_units<double>, agro_grid(C, T), dim3(XH_BLOCK), 0, ctx->stream, e);
-  else hipLaunchKernelGGL(k_corn_heat_units<float>, agro_grid(C, T), dim3(XH_BLOCK), 0, ctx->stream, e);
+  xh_by_width(f64, [&](auto w) { hipLaunchKernelGGL(k_corn_heat_units<XH_WIDTH(w)>, agro_grid(C, T), dim3(XH_BLOCK), 0, ctx->stream, e); });
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
 
 int xh_qian_wma(xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int f64, const void* tas, double* out, int64_t ld_out) {
   const char* fn = "xh_qian_wma";
-  const int rc = agro_shape_checks(fn, ctx, T, C, ld, T, ld_out);
+  const int rc = xh_check_pitched(fn, ctx, T, C, ld, T, ld_out);
   if (rc) return rc;
   XH_REQUIRE(tas && out, XH_ERR_ARG, "%s: NULL argument", fn);
   if (T == 0 || C == 0) return XH_OK;
   ElemArgs e{tas, nullptr, out, T, C, ld, ld_out, 0.0, 0.0, 0.0};
-  if (f64) hipLaunchKernelGGL(k_qian_wma<double>, agro_grid(C, T), dim3(XH_BLOCK), 0, ctx->stream, e);
-  else hipLaunchKernelGGL(k_qian_wma<float>, agro_grid(C, T), dim3(XH_BLOCK), 0, ctx->stream, e);
+  xh_by_width(f64, [&](auto w) { hipLaunchKernelGGL(k_qian_wma<XH_WIDTH(w)>, agro_grid(C, T), dim3(XH_BLOCK), 0, ctx->stream, e); });
   XH_LAUNCH_CHECK();
   return XH_OK;
 }

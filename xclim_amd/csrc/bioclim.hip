@@ -36,11 +36,6 @@ struct BioArgs {
   bool quarters;  // any output that reads a quarter series
 };
 
-template <typename TE>
-__device__ __forceinline__ TE ld(const void* p, int64_t i) {
-  return reinterpret_cast<const TE*>(p)[i];
-}
-
 // Welford's single pass: mean and the sum of squared deviations of the values seen so far
 struct Welford {
   double n, mean, m2;
@@ -82,7 +77,7 @@ __device__ __forceinline__ void bio_row(const BioArgs& a, int64_t r, int64_t c, 
                                         double& ps, int& pn) {
   const int64_t i = r * a.ld + c;
   if (a.tas) {
-    const double x = (double)ld<TE>(a.tas, i);
+    const double x = (double)xh_ld<TE>(a.tas, i);
     if (x == x) {
       ts += x;
       tn += 1;
@@ -94,7 +89,7 @@ __device__ __forceinline__ void bio_row(const BioArgs& a, int64_t r, int64_t c, 
     }
   }
   if (a.pr) {
-    const double x = (double)ld<TE>(a.pr, i);
+    const double x = (double)xh_ld<TE>(a.pr, i);
     const double amt = x * a.factor[r];
     if (x == x) {
       ps += amt;
@@ -110,7 +105,7 @@ __device__ __forceinline__ void bio_row(const BioArgs& a, int64_t r, int64_t c, 
   }
   if (inp && (a.tasmin || a.tasmax)) {
     const TE nan = (TE)xh_nan64();
-    const TE l = a.tasmin ? ld<TE>(a.tasmin, i) : nan, h = a.tasmax ? ld<TE>(a.tasmax, i) : nan;
+    const TE l = a.tasmin ? xh_ld<TE>(a.tasmin, i) : nan, h = a.tasmax ? xh_ld<TE>(a.tasmax, i) : nan;
     if (h == h) {
       m.tx = (m.ntx == 0 || h > m.tx) ? h : m.tx;
       m.ntx += 1;
@@ -219,24 +214,16 @@ int xh_bioclim(xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int f64, const voi
                const int64_t* seg_rows, const int64_t* seg_steps, int W, double kelvin_offset, double cv_scale, double thresh,
                double* const* outputs, int32_t* const* which_out, int32_t* const* count_out, int64_t ld_out) {
   const char* fn = "xh_bioclim";
-  XH_REQUIRE(ctx, XH_ERR_ARG, "%s: NULL context", fn);
-  XH_REQUIRE(T >= 0 && C >= 0 && P >= 0 && S >= 0, XH_ERR_ARG, "%s: negative shape", fn);
-  XH_REQUIRE(ld >= C && ld_out >= C, XH_ERR_LAYOUT, "%s: needs time-major views (ld >= C, ld_out >= C)", fn);
+  int rc = xh_check_pitched(fn, ctx, T, C, ld, P, ld_out);
+  if (rc) return rc;
   XH_REQUIRE(step_off && factor && seg_rows && seg_steps, XH_ERR_ARG, "%s: NULL table", fn);
   XH_REQUIRE(W == 3 || W == 13, XH_ERR_ARG, "%s: the window is 13 steps (daily, weekly) or 3 (monthly), got %d", fn, W);
-  XH_REQUIRE(P <= 65535, XH_ERR_LIMIT, "%s: at most 65535 periods, got %lld", fn, (long long)P);
-  XH_REQUIRE(S < ((int64_t)1 << 31), XH_ERR_LIMIT, "%s: too many steps", fn);
-  XH_REQUIRE(T * ld + C < ((int64_t)1 << 40) && P * ld_out + C < ((int64_t)1 << 40), XH_ERR_LIMIT, "%s: field too large", fn);
-  // the steps partition rows [step_off[0], step_off[S]) of the field
-  XH_REQUIRE(step_off[0] >= 0 && step_off[S] <= T, XH_ERR_ARG, "%s: step offsets outside [0, T]", fn);
-  for (int64_t s = 0; s < S; ++s)
-    XH_REQUIRE(step_off[s] <= step_off[s + 1], XH_ERR_ARG, "%s: step offsets must be non-decreasing", fn);
-  // the periods: rows and steps non-decreasing in range, and the walk of a period (its steps and the lead-in) passes its rows
-  XH_REQUIRE(seg_rows[0] >= 0 && seg_rows[P] <= T && seg_steps[0] >= 0 && seg_steps[P] <= S, XH_ERR_ARG,
-             "%s: period offsets out of range", fn);
-  for (int64_t p = 0; p < P; ++p)
-    XH_REQUIRE(seg_rows[p] <= seg_rows[p + 1] && seg_steps[p] <= seg_steps[p + 1], XH_ERR_ARG,
-               "%s: period offsets must be non-decreasing", fn);
+  // the steps partition rows [step_off[0], step_off[S]) of the field; the periods: rows and steps non-decreasing in range, and
+  // (below) the walk of a period (its steps and the lead-in) passes its rows
+  rc = xh_check_offsets(fn, step_off, S, T, "step", INT32_MAX);
+  if (!rc) rc = xh_check_offsets(fn, seg_rows, P, T, "period");
+  if (!rc) rc = xh_check_offsets(fn, seg_steps, P, S, "period step");
+  if (rc) return rc;
   unsigned want = 0;
   bool any = false;
   if (outputs)
@@ -262,7 +249,7 @@ int xh_bioclim(xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int f64, const voi
 
   BioArgs a{};
   size_t cur = 0;
-  int rc = xh_upload(ctx, &cur, step_off, (size_t)S + 1, &a.step_off);
+  rc = xh_upload(ctx, &cur, step_off, (size_t)S + 1, &a.step_off);
   if (!rc) rc = xh_upload(ctx, &cur, factor, (size_t)(T > 0 ? T : 1), &a.factor);
   if (!rc) rc = xh_upload(ctx, &cur, seg_rows, (size_t)P + 1, &a.seg_rows);
   if (!rc) rc = xh_upload(ctx, &cur, seg_steps, (size_t)P + 1, &a.seg_steps);
@@ -286,8 +273,9 @@ int xh_bioclim(xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int f64, const voi
   a.quarters = quarters;
   const dim3 g((unsigned)cdiv64(C, XH_BLOCK), (unsigned)P);
   const bool launched = xh_pick<3, 13>(W, [&](auto Wc) {
-    if (f64) hipLaunchKernelGGL((k_bioclim<double, decltype(Wc)::value>), g, dim3(XH_BLOCK), 0, ctx->stream, a);
-    else hipLaunchKernelGGL((k_bioclim<float, decltype(Wc)::value>), g, dim3(XH_BLOCK), 0, ctx->stream, a);
+    xh_by_width(f64, [&](auto w) {
+      hipLaunchKernelGGL((k_bioclim<XH_WIDTH(w), decltype(Wc)::value>), g, dim3(XH_BLOCK), 0, ctx->stream, a);
+    });
   });
   XH_REQUIRE(launched, XH_ERR_ARG, "%s: no kernel for a window of %d steps", fn, W);
   XH_LAUNCH_CHECK();

@@ -14,14 +14,9 @@
 // both false, so delta is 0 from there on (never NaN), exactly as np.where does in the reference.
 // The Utah comparisons run in the dtype of the temperature they see (numpy compares a float32 field against the float32
 // roundings of 1.4, 2.4 ...); the fused path compares in float64, because its hourly temperatures are float64.
-#include "common.h"
+#include "hostargs.h"
 
 namespace {
-
-template <typename TE>
-__device__ __forceinline__ TE ld(const void* p, int64_t i) {
-  return reinterpret_cast<const TE*>(p)[i];
-}
 
 // _chill_portion_one_season's constants (_agro.py:1445-1452)
 constexpr double E0 = 4153.5;
@@ -128,7 +123,7 @@ __global__ void __launch_bounds__(XH_BLOCK) k_chill_hourly(ChillArgs a) {
   for (int64_t r = r0; r < r1; ++r) {
     double delta = 0.0;
     if (!a.sel || a.sel[r]) {
-      const TE t = ld<TE>(a.tas, r * a.ld + c);
+      const TE t = xh_ld<TE>(a.tas, r * a.ld + c);
       double w;
       bool nanw;
       delta = chill_step<TE>((double)t + a.add_K, t - (TE)a.sub_C, a.dyn, a.utah, s, w, nanw);
@@ -155,9 +150,9 @@ __global__ void __launch_bounds__(XH_BLOCK) k_chill_daily(ChillArgs a) {
   for (int64_t d = d0; d < d1; ++d) {
     const bool sel = !a.sel || a.sel[d];
     if (!sel && !a.row_out) continue;
-    const TE tn = ld<TE>(a.tas, d * a.ld + c), tx = ld<TE>(a.tasmax, d * a.ld + c);
+    const TE tn = xh_ld<TE>(a.tas, d * a.ld + c), tx = xh_ld<TE>(a.tasmax, d * a.ld + c);
     // helpers.py:1093-1106: the last day's next tasmin is its own (the appended copy of the last day)
-    const double tnn = d + 1 < a.T ? (double)ld<TE>(a.tas, (d + 1) * a.ld + c) : (double)tn;
+    const double tnn = d + 1 < a.T ? (double)xh_ld<TE>(a.tas, (d + 1) * a.ld + c) : (double)tn;
     const double dl = a.dl[d * a.L + li];
     const TE range = tx - tn;  // in the field's dtype, as two DataArrays of it subtract
     const double rng = (double)range, tnd = (double)tn;
@@ -186,15 +181,14 @@ __global__ void __launch_bounds__(XH_BLOCK) k_chill_daily(ChillArgs a) {
   if (a.cp_out || a.cu_out || a.valid_out) chill_store(a, p, c, m);
 }
 
+// seg is a DEVICE table here: its offsets cannot be walked on the host (the kernels clamp them to [0, T])
 int chill_checks(const char* who, xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int64_t P, const void* seg, int64_t ld_out,
                  int64_t out_rows) {
-  XH_REQUIRE(ctx, XH_ERR_ARG, "%s: NULL context", who);
-  XH_REQUIRE(T >= 0 && C >= 0 && P >= 0, XH_ERR_ARG, "%s: negative shape", who);
-  XH_REQUIRE(ld >= C && ld_out >= C, XH_ERR_LAYOUT, "%s: needs time-major views (ld >= C, ld_out >= C)", who);
+  const int rc = xh_check_pitched(who, ctx, T, C, ld, out_rows, ld_out);
+  if (rc) return rc;
+  XH_REQUIRE(P >= 0, XH_ERR_ARG, "%s: negative shape", who);
   XH_REQUIRE(seg, XH_ERR_ARG, "%s: NULL period offsets", who);
-  XH_REQUIRE(P <= 65535, XH_ERR_LIMIT, "%s: at most 65535 periods, got %lld", who, (long long)P);
-  XH_REQUIRE(T * ld + C < ((int64_t)1 << 40) && out_rows * ld_out + C < ((int64_t)1 << 40), XH_ERR_LIMIT, "%s: field too large",
-             who);
+  XH_REQUIRE(P <= XH_MAX_PERIODS, XH_ERR_LIMIT, "%s: at most 65535 periods, got %lld", who, (long long)P);
   return XH_OK;
 }
 
@@ -228,8 +222,7 @@ int xh_chill_hourly(xh_ctx* ctx, int64_t H, int64_t C, int64_t ld, int f64, cons
   a.dyn = cp_out || delta_out;
   a.utah = cu_out != nullptr;
   const dim3 g((unsigned)cdiv64(C, XH_BLOCK), (unsigned)P);
-  if (f64) hipLaunchKernelGGL(k_chill_hourly<double>, g, dim3(XH_BLOCK), 0, ctx->stream, a);
-  else hipLaunchKernelGGL(k_chill_hourly<float>, g, dim3(XH_BLOCK), 0, ctx->stream, a);
+  xh_by_width(f64, [&](auto w) { hipLaunchKernelGGL(k_chill_hourly<XH_WIDTH(w)>, g, dim3(XH_BLOCK), 0, ctx->stream, a); });
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
@@ -267,8 +260,7 @@ int xh_chill_daily(xh_ctx* ctx, int64_t D, int64_t C, int64_t ld, int f64, const
   a.dyn = cp_out != nullptr;
   a.utah = cu_out != nullptr;
   const dim3 g((unsigned)cdiv64(C, XH_BLOCK), (unsigned)P);
-  if (f64) hipLaunchKernelGGL(k_chill_daily<double>, g, dim3(XH_BLOCK), 0, ctx->stream, a);
-  else hipLaunchKernelGGL(k_chill_daily<float>, g, dim3(XH_BLOCK), 0, ctx->stream, a);
+  xh_by_width(f64, [&](auto w) { hipLaunchKernelGGL(k_chill_daily<XH_WIDTH(w)>, g, dim3(XH_BLOCK), 0, ctx->stream, a); });
   XH_LAUNCH_CHECK();
   return XH_OK;
 }

@@ -363,5 +363,15 @@ __device__ __forceinline__ double xh_div_int(double s, double n, double inv) {
   return (r == r) ? fma(r, inv, q) : q;
 }
 
+// element i of a float32 or float64 field behind const void*; xh_ldw: widened to float64
+template <typename TE>
+__device__ __forceinline__ TE xh_ld(const void* p, int64_t i) {
+  return reinterpret_cast<const TE*>(p)[i];
+}
+template <typename TE>
+__device__ __forceinline__ double xh_ldw(const void* p, int64_t i) {
+  return (double)xh_ld<TE>(p, i);
+}
+
 __device__ __forceinline__ double xh_nan64() { return __longlong_as_double(0x7FF8000000000000LL); }
 __device__ __forceinline__ float xh_nan32() { return __uint_as_float(0x7FC00000u); }

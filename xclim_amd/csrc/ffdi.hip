@@ -10,7 +10,7 @@
 // indices only (a runtime-indexed register array would live in scratch).  N ** 1.3 comes from a host table (Python's pow).
 // FFDI follows numpy on the given dtypes (NEP 50): float32 tasmax / hurs / sfcWind give a float32 exponent with float32
 // constants, a float32 DF gives a float32 power; exp / pow are evaluated in float64 and rounded once.
-#include "common.h"
+#include "hostargs.h"
 #include "pyminmax.h"
 
 namespace {
@@ -33,11 +33,6 @@ struct FfdiArgs {
   double n13[WL];  // n13[k] = (k + 1) ** 1.3
   int lim;
 };
-
-template <typename TE>
-__device__ __forceinline__ TE ld(const void* p, int64_t i) {
-  return reinterpret_cast<const TE*>(p)[i];
-}
 
 // KBDI of one day (_ffdi.py:67-89); rr and k are carried
 __device__ __forceinline__ double kbdi_day(double p, double t, double den, double& rr, double k) {
@@ -137,8 +132,8 @@ __global__ void __launch_bounds__(XH_BLOCK) k_mcarthur(FfdiArgs a) {
 
   for (int64_t t = 0; t < a.T; ++t) {
     const int64_t ro = t * a.st + c, oo = t * a.st_out + c;
-    const TP pv = need_p ? ld<TP>(a.pr, ro) : (TP)0;
-    const TT tv = need_t ? ld<TT>(a.tas, ro) : (TT)0;
+    const TP pv = need_p ? xh_ld<TP>(a.pr, ro) : (TP)0;
+    const TT tv = need_t ? xh_ld<TT>(a.tas, ro) : (TT)0;
     if (do_k) {
       k = kbdi_day((double)pv, (double)tv, den, rr, k);
       a.out_k[oo] = k;
@@ -148,29 +143,17 @@ __global__ void __launch_bounds__(XH_BLOCK) k_mcarthur(FfdiArgs a) {
 #pragma unroll
       for (int i = 0; i < WL - 1; ++i) w[i] = w[i + 1];
       w[WL - 1] = pv;
-      if (t >= WL - 1) dfv = df_day(w, do_k ? k : (double)ld<TS>(a.smd, ro), a.lim, a.n13);
+      if (t >= WL - 1) dfv = df_day(w, do_k ? k : (double)xh_ld<TS>(a.smd, ro), a.lim, a.n13);
       a.out_df[oo] = dfv;
     }
     if (do_f) {
-      const TT hv = ld<TT>(a.hurs, ro), wv = ld<TT>(a.ws, ro);
+      const TT hv = xh_ld<TT>(a.hurs, ro), wv = xh_ld<TT>(a.ws, ro);
       double f;
-      if (!do_d && sizeof(TS) == 4) f = ffdi_day<TT, true>((double)ld<TS>(a.df, ro), tv, hv, wv);
-      else f = ffdi_day<TT, false>(do_d ? dfv : (double)ld<TS>(a.df, ro), tv, hv, wv);
+      if (!do_d && sizeof(TS) == 4) f = ffdi_day<TT, true>((double)xh_ld<TS>(a.df, ro), tv, hv, wv);
+      else f = ffdi_day<TT, false>(do_d ? dfv : (double)xh_ld<TS>(a.df, ro), tv, hv, wv);
       a.out_ff[oo] = f;
     }
   }
-}
-
-template <typename TP, typename TT>
-void launch2(bool smd64, const FfdiArgs& a, dim3 g, hipStream_t s) {
-  if (smd64) hipLaunchKernelGGL((k_mcarthur<TP, TT, double>), g, dim3(XH_BLOCK), 0, s, a);
-  else hipLaunchKernelGGL((k_mcarthur<TP, TT, float>), g, dim3(XH_BLOCK), 0, s, a);
-}
-
-template <typename TP>
-void launch1(bool tas64, bool smd64, const FfdiArgs& a, dim3 g, hipStream_t s) {
-  if (tas64) launch2<TP, double>(smd64, a, g, s);
-  else launch2<TP, float>(smd64, a, g, s);
 }
 
 }  // namespace
@@ -211,8 +194,13 @@ int xh_mcarthur(xh_ctx* ctx, int64_t T, int64_t C, int64_t st, int pr_f64, int t
   for (int i = 0; i < WL; ++i) a.n13[i] = n13[i];
   a.lim = lim;
   const dim3 g((unsigned)cdiv64(C, XH_BLOCK));
-  if (pr_f64) launch1<double>(tas_f64 != 0, smd_f64 != 0, a, g, ctx->stream);
-  else launch1<float>(tas_f64 != 0, smd_f64 != 0, a, g, ctx->stream);
+  xh_by_width(pr_f64, [&](auto wp) {
+    xh_by_width(tas_f64, [&](auto wt) {
+      xh_by_width(smd_f64, [&](auto ws) {
+        hipLaunchKernelGGL((k_mcarthur<XH_WIDTH(wp), XH_WIDTH(wt), XH_WIDTH(ws)>), g, dim3(XH_BLOCK), 0, ctx->stream, a);
+      });
+    });
+  });
   XH_LAUNCH_CHECK();
   return XH_OK;
 }

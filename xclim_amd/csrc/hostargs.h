@@ -1,8 +1,10 @@
-// hostargs.h — the host-side front end of a streaming entry point, i.e. one that takes a time-major field (x, T, C, st, sc),
-// usually with a period table seg_off[P + 1], and marches it one cell or cell group per lane: the argument checks, the tables
-// it uploads, cells per lane, the (cells, periods) grid, and run-time integers turned into template arguments.  Host code only.
-// Every check answers through XH_REQUIRE with the entry point's name `fn` first; nothing here touches the device before the
-// checks of its own call have passed.
+// hostargs.h — the host-side front end of an entry point.  Two families: the STREAMING one takes a time-major field
+// (x, T, C, st, sc), usually with a period table seg_off[P + 1], and marches it one cell or cell group per lane: the argument
+// checks, the tables it uploads, cells per lane, the (cells, periods) grid, and run-time integers turned into template
+// arguments.  The PITCHED one takes (ctx, T, C, ld, f64, fields..., P, seg, ..., outs..., ld_out) with float32 or float64 fields
+// behind const void* and one lane per (cell, period): its shape checks, its host offset tables, the element width turned into a
+// template argument, and launches with dynamic LDS.  Host code only.  Every check answers through XH_REQUIRE with the entry
+// point's name `fn` first; nothing here touches the device before the checks of its own call have passed.
 #pragma once
 
 #include <type_traits>
@@ -92,4 +94,50 @@ static inline dim3 xh_period_grid(int64_t C, int vec, int P) {
 template <int... Vs, typename F>
 static inline bool xh_pick(int v, F&& f) {
   return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+
+// ---- the pitched family ---------------------------------------------------------------------------------------------
+// the shape: a context, nothing negative, rows of the fields (ld) and of the outputs (ld_out) at least the row width, and both
+// index ranges below 2^40
+static inline int xh_check_pitched(const char* fn, xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int64_t out_rows, int64_t ld_out) {
+  XH_REQUIRE(ctx, XH_ERR_ARG, "%s: NULL context", fn);
+  XH_REQUIRE(T >= 0 && C >= 0 && out_rows >= 0, XH_ERR_ARG, "%s: negative shape", fn);
+  int rc = xh_check_rows(fn, ld, C, "ld");
+  if (!rc) rc = xh_check_rows(fn, ld_out, C, "ld_out");
+  if (rc) return rc;
+  XH_REQUIRE(T * ld + C < ((int64_t)1 << 40) && out_rows * ld_out + C < ((int64_t)1 << 40), XH_ERR_LIMIT, "%s: field too large", fn);
+  return XH_OK;
+}
+
+// a HOST offset table seg[P + 1] (`what`: "period", "month" ...): non-NULL, at most max_P entries (periods lie along the
+// second grid axis: 65535), offsets non-decreasing within [0, rows]
+constexpr int64_t XH_MAX_PERIODS = 65535;
+static inline int xh_check_offsets(const char* fn, const int64_t* seg, int64_t P, int64_t rows, const char* what,
+                                   int64_t max_P = XH_MAX_PERIODS) {
+  XH_REQUIRE(seg, XH_ERR_ARG, "%s: NULL %s offsets", fn, what);
+  XH_REQUIRE(P >= 0, XH_ERR_ARG, "%s: negative shape", fn);
+  XH_REQUIRE(P <= max_P, XH_ERR_LIMIT, "%s: at most %lld %ss, got %lld", fn, (long long)max_P, what, (long long)P);
+  XH_REQUIRE(seg[0] >= 0 && seg[P] <= rows, XH_ERR_ARG, "%s: %s offsets outside [0, %lld]", fn, what, (long long)rows);
+  for (int64_t p = 0; p < P; ++p) XH_REQUIRE(seg[p] <= seg[p + 1], XH_ERR_ARG, "%s: %s offsets must be non-decreasing", fn, what);
+  return XH_OK;
+}
+
+// f(tag) with XH_WIDTH(tag) = double when f64, float otherwise; returns what f returns
+template <typename TE>
+struct xh_width {
+  using type = TE;
+};
+#define XH_WIDTH(tag) typename decltype(tag)::type
+template <typename F>
+static inline auto xh_by_width(int f64, F&& f) {
+  if (f64) return f(xh_width<double>{});
+  return f(xh_width<float>{});
+}
+
+// a launch with dynamic LDS: more than 64 KiB has to be allowed per kernel first
+template <typename A>
+static inline int xh_launch_lds(void (*kernel)(A), dim3 g, dim3 b, size_t lds, hipStream_t stream, const A& a) {
+  if (lds > 64 * 1024) XH_CHECK_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kernel, g, b, lds, stream, a);
+  return XH_OK;
 }

@@ -30,11 +30,6 @@ constexpr int HYDRO_BATCH = 8;
 constexpr int API_TILE = 128;
 constexpr int SEN_BLOCK = 64;
 
-template <typename TE>
-__device__ __forceinline__ TE ldr(const void* p, int64_t i) {
-  return reinterpret_cast<const TE*>(p)[i];
-}
-
 __device__ __forceinline__ double hydro_inf() { return __longlong_as_double(0x7FF0000000000000LL); }
 
 // ---- xh_flow_period_stats -------------------------------------------------------------------------------------------
@@ -61,7 +56,7 @@ __global__ void __launch_bounds__(XH_BLOCK) k_flow(FlowArgs a) {
 #pragma unroll
     for (int k = 1; k < 7; ++k) {
       const int64_t r = r0 - 4 + k;
-      if (r >= 0 && r < a.T) w[k] = (double)ldr<TE>(a.q, r * a.ld + c);
+      if (r >= 0 && r < a.T) w[k] = (double)xh_ld<TE>(a.q, r * a.ld + c);
     }
   }
   double sum = 0.0, dsum = 0.0, m7min = nan;
@@ -72,7 +67,7 @@ __global__ void __launch_bounds__(XH_BLOCK) k_flow(FlowArgs a) {
     for (int u = 0; u < HYDRO_BATCH; ++u) {
       const int64_t r = i0 + u + 3;
       nx[u] = (TE)nan;
-      if (i0 + u < r1 && r < a.T) nx[u] = ldr<TE>(a.q, r * a.ld + c);
+      if (i0 + u < r1 && r < a.T) nx[u] = xh_ld<TE>(a.q, r * a.ld + c);
     }
 #pragma unroll
     for (int u = 0; u < HYDRO_BATCH; ++u) {
@@ -120,7 +115,7 @@ __global__ void __launch_bounds__(XH_BLOCK) k_melt(MeltArgs a) {
   if (r0 < r1 && r1 > 1) {
     // total[j] exists for j >= 1; agg[i] needs total[i - W + 1 .. i]: the walk starts W - 1 rows before the period
     const int64_t j0 = r0 - W + 1 > 1 ? r0 - W + 1 : 1;
-    double prev = (double)ldr<TE>(a.snw, (j0 - 1) * a.ld + c);
+    double prev = (double)xh_ld<TE>(a.snw, (j0 - 1) * a.ld + c);
     int slot = 0, have = 0;  // the next ring slot (the oldest total once the ring is full); totals in the ring
     for (int64_t jb = j0; jb < r1; jb += HYDRO_BATCH) {
       TE s[HYDRO_BATCH], f[HYDRO_BATCH];
@@ -128,8 +123,8 @@ __global__ void __launch_bounds__(XH_BLOCK) k_melt(MeltArgs a) {
       for (int u = 0; u < HYDRO_BATCH; ++u) {
         s[u] = f[u] = (TE)0;
         if (jb + u < r1) {
-          s[u] = ldr<TE>(a.snw, (jb + u) * a.ld + c);
-          if (PR) f[u] = ldr<TE>(a.pr, (jb + u) * a.ld + c);
+          s[u] = xh_ld<TE>(a.snw, (jb + u) * a.ld + c);
+          if (PR) f[u] = xh_ld<TE>(a.pr, (jb + u) * a.ld + c);
         }
       }
 #pragma unroll
@@ -187,7 +182,7 @@ __global__ void __launch_bounds__(XH_BLOCK) k_api(ApiArgs a) {
     for (int64_t jb = j0; jb < t1; jb += HYDRO_BATCH) {
       TE f[HYDRO_BATCH];
 #pragma unroll
-      for (int u = 0; u < HYDRO_BATCH; ++u) f[u] = jb + u < t1 ? ldr<TE>(a.pr, (jb + u) * a.ld + c) : (TE)0;
+      for (int u = 0; u < HYDRO_BATCH; ++u) f[u] = jb + u < t1 ? xh_ld<TE>(a.pr, (jb + u) * a.ld + c) : (TE)0;
 #pragma unroll
       for (int u = 0; u < HYDRO_BATCH; ++u) {
         const int64_t j = jb + u;
@@ -236,7 +231,7 @@ __global__ void __launch_bounds__(SEN_BLOCK) k_sen_slope(SenArgs a) {
   int n_part = 0;
   for (int y = lane; y < Y; y += SEN_BLOCK) {
     const int64_t row = a.period_of[(int64_t)y * a.K + k];
-    const double v = row >= 0 ? (double)ldr<TE>(a.x, row * a.ld + c) : nan;
+    const double v = row >= 0 ? (double)xh_ld<TE>(a.x, row * a.ld + c) : nan;
     vals[y] = v;
     n_part += v == v ? 1 : 0;
   }
@@ -316,26 +311,6 @@ __global__ void __launch_bounds__(SEN_BLOCK) k_sen_slope(SenArgs a) {
 }
 
 // ---- host front end -------------------------------------------------------------------------------------------------
-int hydro_shape_checks(const char* fn, xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int64_t out_rows, int64_t ld_out) {
-  XH_REQUIRE(ctx, XH_ERR_ARG, "%s: NULL context", fn);
-  XH_REQUIRE(T >= 0 && C >= 0 && out_rows >= 0, XH_ERR_ARG, "%s: negative shape", fn);
-  int rc = xh_check_rows(fn, ld, C, "ld");
-  if (!rc) rc = xh_check_rows(fn, ld_out, C, "ld_out");
-  if (rc) return rc;
-  XH_REQUIRE(T * ld + C < ((int64_t)1 << 40) && out_rows * ld_out + C < ((int64_t)1 << 40), XH_ERR_LIMIT, "%s: field too large", fn);
-  return XH_OK;
-}
-
-// a period table: non-NULL, at most 65535 periods, offsets non-decreasing within [0, rows]
-int hydro_periods(const char* fn, const int64_t* seg, int64_t P, int64_t rows) {
-  XH_REQUIRE(seg, XH_ERR_ARG, "%s: NULL period offsets", fn);
-  XH_REQUIRE(P >= 0, XH_ERR_ARG, "%s: negative shape", fn);
-  XH_REQUIRE(P <= 65535, XH_ERR_LIMIT, "%s: at most 65535 periods, got %lld", fn, (long long)P);
-  XH_REQUIRE(seg[0] >= 0 && seg[P] <= rows, XH_ERR_ARG, "%s: period offsets outside [0, %lld]", fn, (long long)rows);
-  for (int64_t p = 0; p < P; ++p) XH_REQUIRE(seg[p] <= seg[p + 1], XH_ERR_ARG, "%s: period offsets must be non-decreasing", fn);
-  return XH_OK;
-}
-
 int hydro_window(const char* fn, int window) {
   XH_REQUIRE(window >= 1, XH_ERR_ARG, "%s: window must be at least 1, got %d", fn, window);
   XH_REQUIRE(window <= XH_HYDRO_MAX_WINDOW, XH_ERR_LIMIT, "%s: windows of up to %d rows are served, got %d", fn, XH_HYDRO_MAX_WINDOW,
@@ -348,8 +323,8 @@ int hydro_window(const char* fn, int window) {
 int xh_flow_period_stats(xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int f64, const void* q, int64_t P, const int64_t* seg,
                          double* bfi_out, double* rbi_out, double* mean_out, double* sum_out, int32_t* valid_out, int64_t ld_out) {
   const char* fn = "xh_flow_period_stats";
-  int rc = hydro_shape_checks(fn, ctx, T, C, ld, P, ld_out);
-  if (!rc) rc = hydro_periods(fn, seg, P, T);
+  int rc = xh_check_pitched(fn, ctx, T, C, ld, P, ld_out);
+  if (!rc) rc = xh_check_offsets(fn, seg, P, T, "period");
   if (rc) return rc;
   XH_REQUIRE(q, XH_ERR_ARG, "%s: NULL field", fn);
   XH_REQUIRE(bfi_out || rbi_out || mean_out || sum_out || valid_out, XH_ERR_ARG, "%s: no output requested", fn);
@@ -363,8 +338,7 @@ int xh_flow_period_stats(xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int f64,
   a.bfi_out = bfi_out, a.rbi_out = rbi_out, a.mean_out = mean_out, a.sum_out = sum_out, a.valid_out = valid_out;
   a.T = T, a.C = C, a.ld = ld, a.ld_out = ld_out;
   const dim3 g((unsigned)cdiv64(C, XH_BLOCK), (unsigned)P);
-  if (f64) hipLaunchKernelGGL(k_flow<double>, g, dim3(XH_BLOCK), 0, ctx->stream, a);
-  else hipLaunchKernelGGL(k_flow<float>, g, dim3(XH_BLOCK), 0, ctx->stream, a);
+  xh_by_width(f64, [&](auto w) { hipLaunchKernelGGL(k_flow<XH_WIDTH(w)>, g, dim3(XH_BLOCK), 0, ctx->stream, a); });
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
@@ -372,8 +346,8 @@ int xh_flow_period_stats(xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int f64,
 int xh_melt_period_max(xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int f64, const void* snw, const void* pr, double per_day,
                        int window, int64_t P, const int64_t* seg, double* out, int64_t ld_out) {
   const char* fn = "xh_melt_period_max";
-  int rc = hydro_shape_checks(fn, ctx, T, C, ld, P, ld_out);
-  if (!rc) rc = hydro_periods(fn, seg, P, T);
+  int rc = xh_check_pitched(fn, ctx, T, C, ld, P, ld_out);
+  if (!rc) rc = xh_check_offsets(fn, seg, P, T, "period");
   if (rc) return rc;
   XH_REQUIRE(snw && out, XH_ERR_ARG, "%s: NULL argument", fn);
   rc = hydro_window(fn, window);
@@ -389,14 +363,10 @@ int xh_melt_period_max(xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int f64, c
   a.per_day = per_day, a.window = window;
   const dim3 g((unsigned)cdiv64(C, XH_BLOCK), (unsigned)P), b(XH_BLOCK);
   const size_t lds = (size_t)window * XH_BLOCK * sizeof(double);
-#define HYDRO_MELT(TE)                                                                        \
-  do {                                                                                        \
-    if (pr) hipLaunchKernelGGL((k_melt<TE, true>), g, b, lds, ctx->stream, a);                \
-    else hipLaunchKernelGGL((k_melt<TE, false>), g, b, lds, ctx->stream, a);                  \
-  } while (0)
-  if (f64) HYDRO_MELT(double);
-  else HYDRO_MELT(float);
-#undef HYDRO_MELT
+  xh_by_width(f64, [&](auto w) {
+    if (pr) hipLaunchKernelGGL((k_melt<XH_WIDTH(w), true>), g, b, lds, ctx->stream, a);
+    else hipLaunchKernelGGL((k_melt<XH_WIDTH(w), false>), g, b, lds, ctx->stream, a);
+  });
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
@@ -404,7 +374,7 @@ int xh_melt_period_max(xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int f64, c
 int xh_antecedent_precip(xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int f64, const void* pr, double per_day, int window,
                          const double* weights, double* out, int64_t ld_out) {
   const char* fn = "xh_antecedent_precip";
-  int rc = hydro_shape_checks(fn, ctx, T, C, ld, T, ld_out);
+  int rc = xh_check_pitched(fn, ctx, T, C, ld, T, ld_out);
   if (rc) return rc;
   XH_REQUIRE(pr && out && weights, XH_ERR_ARG, "%s: NULL argument", fn);
   rc = hydro_window(fn, window);
@@ -421,13 +391,8 @@ int xh_antecedent_precip(xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int f64,
   const int64_t tiles = cdiv64(T, API_TILE);
   const dim3 g((unsigned)cdiv64(C, XH_BLOCK), (unsigned)(tiles > 65535 ? 65535 : tiles)), b(XH_BLOCK);
   const size_t lds = ((size_t)window * XH_BLOCK + (size_t)window) * sizeof(double);  // (the largest window: 256 bytes over 64 KiB)
-  if (f64) {
-    if (lds > 64 * 1024) XH_CHECK_HIP(hipFuncSetAttribute((const void*)k_api<double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_api<double>, g, b, lds, ctx->stream, a);
-  } else {
-    if (lds > 64 * 1024) XH_CHECK_HIP(hipFuncSetAttribute((const void*)k_api<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_api<float>, g, b, lds, ctx->stream, a);
-  }
+  rc = xh_by_width(f64, [&](auto w) { return xh_launch_lds(k_api<XH_WIDTH(w)>, g, b, lds, ctx->stream, a); });
+  if (rc) return rc;
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
@@ -435,7 +400,7 @@ int xh_antecedent_precip(xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int f64,
 int xh_sen_slope(xh_ctx* ctx, int64_t P, int64_t C, int64_t ld, int f64, const void* x, int64_t Y, int64_t K,
                  const int64_t* period_of, double* slope_out, double* p_out, int32_t* n_out, int64_t ld_out) {
   const char* fn = "xh_sen_slope";
-  int rc = hydro_shape_checks(fn, ctx, P, C, ld, K, ld_out);
+  int rc = xh_check_pitched(fn, ctx, P, C, ld, K, ld_out);
   if (rc) return rc;
   XH_REQUIRE(Y >= 0 && K >= 0, XH_ERR_ARG, "%s: negative shape", fn);
   XH_REQUIRE(x && period_of, XH_ERR_ARG, "%s: NULL argument", fn);
@@ -461,13 +426,8 @@ int xh_sen_slope(xh_ctx* ctx, int64_t P, int64_t C, int64_t ld, int f64, const v
   while (a.npad < pairs) a.npad <<= 1;
   const size_t lds = ((size_t)Y + (size_t)a.npad + 4 * SEN_BLOCK) * sizeof(double);
   const dim3 g((unsigned)C, (unsigned)K), b(SEN_BLOCK);
-  if (f64) {
-    if (lds > 64 * 1024) XH_CHECK_HIP(hipFuncSetAttribute((const void*)k_sen_slope<double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_sen_slope<double>, g, b, lds, ctx->stream, a);
-  } else {
-    if (lds > 64 * 1024) XH_CHECK_HIP(hipFuncSetAttribute((const void*)k_sen_slope<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_sen_slope<float>, g, b, lds, ctx->stream, a);
-  }
+  rc = xh_by_width(f64, [&](auto w) { return xh_launch_lds(k_sen_slope<XH_WIDTH(w)>, g, b, lds, ctx->stream, a); });
+  if (rc) return rc;
   XH_LAUNCH_CHECK();
   return XH_OK;
 }

@@ -9,7 +9,7 @@
 // (NaN-skipping means, as xarray's resample().mean()); TW48 keeps the months of one year in registers for its heat index.
 // Arithmetic is float64 in the reference's order after widening the fields; the means of float32 fields are float64 sums
 // rounded once to float32 (the convention of stdidx.hip).  Results are kg m-2 s-1 (amount2rate, then the hydro context).
-#include "common.h"
+#include "hostargs.h"
 #include "pyminmax.h"
 
 #include <cmath>
@@ -131,11 +131,6 @@ struct PetArgs {
 
 enum { BR65 = 0, HG85 = 1, MB05 = 2, FAO = 3, TW48 = 4, DA02 = 5 };
 
-template <typename TF>
-__device__ __forceinline__ double ld(const void* p, int64_t i) {
-  return (double)reinterpret_cast<const TF*>(p)[i];
-}
-
 __device__ __forceinline__ double clip0(double x) { return x < 0.0 ? 0.0 : x; }  // np.clip(x, 0, None): NaN stays
 
 // pint's K -> degF: (K - offset) / scale with degF = 5/9 K, offset 233.15 + 200/9
@@ -155,29 +150,29 @@ __global__ void __launch_bounds__(XH_BLOCK) k_pet_daily(PetArgs a) {
     const int64_t i = t * a.st + c;
     double pet;
     if (a.method == BR65) {
-      const double tn = k2f(ld<TF>(a.tn, i)), tx = k2f(ld<TF>(a.tx, i));
+      const double tn = k2f(xh_ldw<TF>(a.tn, i)), tx = k2f(xh_ldw<TF>(a.tx, i));
       const double re = a.tab[t * a.L + li] * (1e-4 / 4.184);  // J m-2 d-1 -> cal cm-2 day-1
       pet = clip0(0.094 * (-87.03 + 0.928 * tx + 0.933 * (tx - tn) + 0.0486 * re));
     } else if (a.method == HG85) {
-      const double tn = ld<TF>(a.tn, i) - 273.15, tx = ld<TF>(a.tx, i) - 273.15;
-      const double tm = a.tas ? ld<TF>(a.tas, i) - 273.15 : (tn + tx) / 2;
+      const double tn = xh_ldw<TF>(a.tn, i) - 273.15, tx = xh_ldw<TF>(a.tx, i) - 273.15;
+      const double tm = a.tas ? xh_ldw<TF>(a.tas, i) - 273.15 : (tn + tx) / 2;
       const double ra = a.tab[t * a.L + li] * 1e-6 * 0.408;
       pet = clip0(0.0023 * ra * (tm + 17.8) * sqrt(tx - tn));
     } else if (a.method == MB05) {
-      const double tm = a.tas ? ld<TF>(a.tas, i) - 273.15 : ((ld<TF>(a.tn, i) - 273.15) + (ld<TF>(a.tx, i) - 273.15)) / 2;
+      const double tm = a.tas ? xh_ldw<TF>(a.tas, i) - 273.15 : ((xh_ldw<TF>(a.tn, i) - 273.15) + (xh_ldw<TF>(a.tx, i) - 273.15)) / 2;
       const double tk = tm + 273.15;
       const double rl = a.tab[t * a.L + li] / (4185.5 * (751.78 - 0.5655 * tk));
       pet = rl * a.peta * tm + rl * a.petb;
     } else {  // FAO_PM98 (converters.py:2121-2145, fao_allen98 :1867-1874)
-      const double tx = ld<TF>(a.tx, i) - 273.15, tn = ld<TF>(a.tn, i) - 273.15;
-      const double hu = ld<TF>(a.hurs, i) / 100;
-      const double w2 = ld<TF>(a.ws, i) * a.wlog2 / a.wlog10;
+      const double tx = xh_ldw<TF>(a.tx, i) - 273.15, tn = xh_ldw<TF>(a.tn, i) - 273.15;
+      const double hu = xh_ldw<TF>(a.hurs, i) / 100;
+      const double w2 = xh_ldw<TF>(a.ws, i) * a.wlog2 / a.wlog10;
       const double tm = (tx + tn) / 2;
       const double es = (1.0 / 2) * (svp(tx + 273.15) + svp(tn + 273.15)) * 1e-3;
       const double ea = es * hu;
       const double dt = tm + 237.3;
       const double delta = 4098 * es / (dt * dt);
-      const double rn = (ld<TF>(a.rsds, i) - ld<TF>(a.rsus, i) - (ld<TF>(a.rlus, i) - ld<TF>(a.rlds, i))) * 0.0864;
+      const double rn = (xh_ldw<TF>(a.rsds, i) - xh_ldw<TF>(a.rsus, i) - (xh_ldw<TF>(a.rlus, i) - xh_ldw<TF>(a.rlds, i))) * 0.0864;
       const double gamma = 0.665e-03 * 101.325;
       const double a1 = 0.408 * delta * (rn - 0.0);
       const double a2 = gamma * 900 / (tm + 273.15) * w2 * (es - ea);
@@ -187,7 +182,7 @@ __global__ void __launch_bounds__(XH_BLOCK) k_pet_daily(PetArgs a) {
     const double rate = pet / 86400;  // mm/d -> kg m-2 s-1
     const int64_t o = t * a.st_out + c;
     if (a.pet) a.pet[o] = rate;
-    if (a.wb) a.wb[o] = ld<TF>(a.pr, i) - rate;
+    if (a.wb) a.wb[o] = xh_ldw<TF>(a.pr, i) - rate;
   }
 }
 
@@ -213,8 +208,8 @@ __global__ void __launch_bounds__(XH_BLOCK) k_pet_monthly(PetArgs a) {
         int nn = 0, nx = 0, nt = 0, np = 0, nw = 0;
         for (int64_t t = a.seg[m + j]; t < a.seg[m + j + 1]; ++t) {
           const int64_t i = t * a.st + c;
-          const double tn = ld<TF>(a.tn, i) - 273.15, tx = ld<TF>(a.tx, i) - 273.15, p = ld<TF>(a.pr, i);
-          const double tm = a.tas ? ld<TF>(a.tas, i) - 273.15 : (tn + tx) / 2;
+          const double tn = xh_ldw<TF>(a.tn, i) - 273.15, tx = xh_ldw<TF>(a.tx, i) - 273.15, p = xh_ldw<TF>(a.pr, i);
+          const double tm = a.tas ? xh_ldw<TF>(a.tas, i) - 273.15 : (tn + tx) / 2;
           const double pm = p * 2629800.0;  // kg m-2 s-1 -> mm/month (pint's month: 365.25 / 12 days)
           if (!isnan(tn)) { sn += tn; ++nn; }
           if (!isnan(tx)) { sx += tx; ++nx; }
@@ -246,8 +241,8 @@ __global__ void __launch_bounds__(XH_BLOCK) k_pet_monthly(PetArgs a) {
           int n = 0;
           for (int64_t t = a.seg[m + j]; t < a.seg[m + j + 1]; ++t) {
             const int64_t i = t * a.st + c;
-            const double tm = clip0(a.tas ? ld<TF>(a.tas, i) - 273.15
-                                          : ((ld<TF>(a.tn, i) - 273.15) + (ld<TF>(a.tx, i) - 273.15)) / 2);
+            const double tm = clip0(a.tas ? xh_ldw<TF>(a.tas, i) - 273.15
+                                          : ((xh_ldw<TF>(a.tn, i) - 273.15) + (xh_ldw<TF>(a.tx, i) - 273.15)) / 2);
             if (!isnan(tm)) { s += tm; ++n; }
           }
           tmv[j] = mean_of<F32>(s, n);
@@ -268,7 +263,7 @@ __global__ void __launch_bounds__(XH_BLOCK) k_pet_monthly(PetArgs a) {
             double sw = 0;
             int nw = 0;
             for (int64_t t = a.seg[m + j]; t < a.seg[m + j + 1]; ++t) {
-              const double p = ld<TF>(a.pr, t * a.st + c);
+              const double p = xh_ldw<TF>(a.pr, t * a.st + c);
               if (!isnan(p)) { sw += p; ++nw; }
             }
             a.wb[o] = mean_of<F32>(sw, nw) - rate;
@@ -352,8 +347,7 @@ int xh_pet_daily(xh_ctx* ctx, int64_t T, int64_t C, int64_t st, int method, int 
   a.wlog10 = std::log(67.8 * 10 - 5.42);
   a.method = method;
   const dim3 g((unsigned)cdiv64(C, XH_BLOCK), (unsigned)(T < 4096 ? T : 4096));
-  if (f64) hipLaunchKernelGGL(k_pet_daily<double>, g, dim3(XH_BLOCK), 0, ctx->stream, a);
-  else hipLaunchKernelGGL(k_pet_daily<float>, g, dim3(XH_BLOCK), 0, ctx->stream, a);
+  xh_by_width(f64, [&](auto w) { hipLaunchKernelGGL(k_pet_daily<XH_WIDTH(w)>, g, dim3(XH_BLOCK), 0, ctx->stream, a); });
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
@@ -396,8 +390,7 @@ int xh_pet_monthly(xh_ctx* ctx, int64_t T, int64_t C, int64_t st, int method, in
   a.method = method;
   a.m0 = first_month;
   const dim3 g((unsigned)cdiv64(C, XH_BLOCK));
-  if (f64) hipLaunchKernelGGL(k_pet_monthly<double>, g, dim3(XH_BLOCK), 0, ctx->stream, a);
-  else hipLaunchKernelGGL(k_pet_monthly<float>, g, dim3(XH_BLOCK), 0, ctx->stream, a);
+  xh_by_width(f64, [&](auto w) { hipLaunchKernelGGL(k_pet_monthly<XH_WIDTH(w)>, g, dim3(XH_BLOCK), 0, ctx->stream, a); });
   XH_LAUNCH_CHECK();
   return XH_OK;
 }

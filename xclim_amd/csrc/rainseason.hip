@@ -38,11 +38,6 @@ namespace {
 constexpr int RAIN_BLOCK = 128;
 constexpr int RAIN_BATCH = 8;
 
-template <typename TE>
-__device__ __forceinline__ TE ldr(const void* p, int64_t i) {
-  return reinterpret_cast<const TE*>(p)[i];
-}
-
 struct RainArgs {
   const void* pr;
   const int64_t* seg;   // (P + 1)
@@ -87,12 +82,12 @@ __global__ void __launch_bounds__(RAIN_BLOCK) k_rain_season(RainArgs a) {
       xf[u] = xd[u] = (TE)nan;
       mf[u] = md[u] = 0;
       if (f < n) {
-        xf[u] = ldr<TE>(a.pr, (r0 + f) * a.ld + c);
+        xf[u] = xh_ld<TE>(a.pr, (r0 + f) * a.ld + c);
         mf[u] = a.meta[r0 + f];
       }
       if (i >= 0 && i < n) {
         md[u] = a.meta[r0 + i];
-        if (REREAD) xd[u] = ldr<TE>(a.pr, (r0 + i) * a.ld + c);
+        if (REREAD) xd[u] = xh_ld<TE>(a.pr, (r0 + i) * a.ld + c);
       }
     }
 #pragma unroll
@@ -213,8 +208,8 @@ __global__ void __launch_bounds__(XH_BLOCK) k_rolling_zones(ZoneArgs a) {
   for (int64_t t = 0; t < a.P; ++t) {
     double zone = nan;
     if (t >= W - 1) {
-      double s = (double)ldr<TE>(a.x, (t - W + 1) * a.ld + c);
-      for (int k = 1; k < W; ++k) s += (double)ldr<TE>(a.x, (t - W + 1 + k) * a.ld + c);
+      double s = (double)xh_ld<TE>(a.x, (t - W + 1) * a.ld + c);
+      for (int k = 1; k < W; ++k) s += (double)xh_ld<TE>(a.x, (t - W + 1 + k) * a.ld + c);
       const double mean = s / (double)W;
       int cnt = 0;  // np.digitize(mean, edges): the edges <= mean (none for a NaN mean)
       for (int k = 0; k < a.nedges; ++k) cnt += a.edges[k] <= mean ? 1 : 0;
@@ -226,16 +221,6 @@ __global__ void __launch_bounds__(XH_BLOCK) k_rolling_zones(ZoneArgs a) {
   }
 }
 
-int rain_shape_checks(const char* fn, xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int64_t out_rows, int64_t ld_out) {
-  XH_REQUIRE(ctx, XH_ERR_ARG, "%s: NULL context", fn);
-  XH_REQUIRE(T >= 0 && C >= 0 && out_rows >= 0, XH_ERR_ARG, "%s: negative shape", fn);
-  int rc = xh_check_rows(fn, ld, C, "ld");
-  if (!rc) rc = xh_check_rows(fn, ld_out, C, "ld_out");
-  if (rc) return rc;
-  XH_REQUIRE(T * ld + C < ((int64_t)1 << 40) && out_rows * ld_out + C < ((int64_t)1 << 40), XH_ERR_LIMIT, "%s: field too large", fn);
-  return XH_OK;
-}
-
 }  // namespace
 
 int xh_rain_season(xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int f64, const void* pr, double per_day, int64_t P,
@@ -243,11 +228,10 @@ int xh_rain_season(xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int f64, const
                    int window_not_dry_start, double thresh_dry_start, int window_dry_start, int total_dry_start, double thresh_dry_end,
                    int window_dry_end, int total_dry_end, double* start_out, double* end_out, double* length_out, int64_t ld_out) {
   const char* fn = "xh_rain_season";
-  int rc = rain_shape_checks(fn, ctx, T, C, ld, P, ld_out);
+  int rc = xh_check_pitched(fn, ctx, T, C, ld, P, ld_out);
   if (rc) return rc;
   XH_REQUIRE(pr && seg && flags && doy, XH_ERR_ARG, "%s: NULL argument", fn);
   XH_REQUIRE(start_out || end_out || length_out, XH_ERR_ARG, "%s: no output requested", fn);
-  XH_REQUIRE(P <= 65535, XH_ERR_LIMIT, "%s: at most 65535 periods, got %lld", fn, (long long)P);
   XH_REQUIRE(window_wet_start >= 1 && window_dry_start >= 1 && window_dry_end >= 1 && window_not_dry_start >= 0, XH_ERR_ARG,
              "%s: windows must be at least 1 (window_not_dry_start at least 0)", fn);
   XH_REQUIRE(window_not_dry_start <= (1 << 30) && window_dry_start <= (1 << 30) && window_dry_end <= (1 << 30), XH_ERR_LIMIT,
@@ -256,9 +240,9 @@ int xh_rain_season(xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int f64, const
                  (!total_dry_end || window_dry_end <= XH_RAIN_MAX_WINDOW),
              XH_ERR_LIMIT, "%s: sum windows of up to %d rows are served, got %d, %d, %d", fn, XH_RAIN_MAX_WINDOW, window_wet_start,
              window_dry_start, window_dry_end);
-  XH_REQUIRE(seg[0] >= 0 && seg[P] <= T, XH_ERR_ARG, "%s: period offsets outside [0, %lld]", fn, (long long)T);
+  rc = xh_check_offsets(fn, seg, P, T, "period");
+  if (rc) return rc;
   for (int64_t p = 0; p < P; ++p) {
-    XH_REQUIRE(seg[p] <= seg[p + 1], XH_ERR_ARG, "%s: period offsets must be non-decreasing", fn);
     XH_REQUIRE(seg[p + 1] - seg[p] < ((int64_t)1 << 30), XH_ERR_LIMIT, "%s: period too long", fn);
     for (int64_t r = seg[p]; r + 1 < seg[p + 1]; ++r)   // P is the amounts on every row the end search looks at
       XH_REQUIRE(!(flags[r] & XH_RAIN_START_WINDOW) || (flags[r + 1] & XH_RAIN_START_WINDOW), XH_ERR_ARG,
@@ -286,14 +270,10 @@ int xh_rain_season(xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int f64, const
   a.ring = (reread ? 0 : window_dry_start - 1) + behind;
   const size_t lds = ((size_t)a.ring * RAIN_BLOCK * (f64 ? 8 : 4) + 7) & ~(size_t)7;  // at most 63 * 128 * 8 = 64 512 bytes
   const dim3 g((unsigned)cdiv64(C, RAIN_BLOCK), (unsigned)P), b(RAIN_BLOCK);
-#define RAIN_LAUNCH(TE)                                                                      \
-  do {                                                                                       \
-    if (reread) hipLaunchKernelGGL((k_rain_season<TE, true>), g, b, lds, ctx->stream, a);    \
-    else hipLaunchKernelGGL((k_rain_season<TE, false>), g, b, lds, ctx->stream, a);          \
-  } while (0)
-  if (f64) RAIN_LAUNCH(double);
-  else RAIN_LAUNCH(float);
-#undef RAIN_LAUNCH
+  xh_by_width(f64, [&](auto w) {
+    if (reread) hipLaunchKernelGGL((k_rain_season<XH_WIDTH(w), true>), g, b, lds, ctx->stream, a);
+    else hipLaunchKernelGGL((k_rain_season<XH_WIDTH(w), false>), g, b, lds, ctx->stream, a);
+  });
   XH_LAUNCH_CHECK();
   return XH_OK;
 }
@@ -301,7 +281,7 @@ int xh_rain_season(xh_ctx* ctx, int64_t T, int64_t C, int64_t ld, int f64, const
 int xh_rolling_zones(xh_ctx* ctx, int64_t P, int64_t C, int64_t ld, int f64, const void* x, int window, int64_t nedges,
                      const double* edges, double* out, int64_t ld_out) {
   const char* fn = "xh_rolling_zones";
-  int rc = rain_shape_checks(fn, ctx, P, C, ld, P, ld_out);
+  int rc = xh_check_pitched(fn, ctx, P, C, ld, P, ld_out);
   if (rc) return rc;
   XH_REQUIRE(x && edges && out, XH_ERR_ARG, "%s: NULL argument", fn);
   XH_REQUIRE(window >= 1, XH_ERR_ARG, "%s: window must be at least 1, got %d", fn, window);
@@ -317,8 +297,7 @@ int xh_rolling_zones(xh_ctx* ctx, int64_t P, int64_t C, int64_t ld, int f64, con
   a.window = window, a.nedges = (int)nedges;
   for (int64_t k = 0; k < nedges; ++k) a.edges[k] = edges[k];
   const dim3 g((unsigned)cdiv64(C, XH_BLOCK)), b(XH_BLOCK);
-  if (f64) hipLaunchKernelGGL(k_rolling_zones<double>, g, b, 0, ctx->stream, a);
-  else hipLaunchKernelGGL(k_rolling_zones<float>, g, b, 0, ctx->stream, a);
+  xh_by_width(f64, [&](auto w) { hipLaunchKernelGGL(k_rolling_zones<XH_WIDTH(w)>, g, b, 0, ctx->stream, a); });
   XH_LAUNCH_CHECK();
   return XH_OK;
 }

@@ -71,6 +71,24 @@ def _offsets(who: str, seg, rows: int, what: str = "period"):
     return s
 
 
+def _periods(who: str, seg, rows: int, what: str = "period"):
+    """(offsets, P) of a period table: _offsets, and no more periods than the second grid axis holds."""
+    s = _offsets(who, seg, rows, what)
+    if len(s) - 1 > 65535:
+        raise ValueError(f"{who}: at most 65535 periods, got {len(s) - 1}")
+    return s, len(s) - 1
+
+
+def _row_selection(who: str, sel, rows: int):
+    """A row selection as uint8 (None stays None): a bool or uint8 array with one entry per row."""
+    if sel is None:
+        return None
+    m = np.ascontiguousarray(sel)
+    if m.shape != (rows,) or m.dtype not in (np.dtype(bool), np.dtype(np.uint8)):
+        raise ValueError(f"{who}: the selection must be a bool or uint8 array of length {rows}")
+    return m.astype(np.uint8)
+
+
 def _subset(who: str, outputs, allowed):
     """The requested outputs in the order of ``allowed``; none is a ValueError."""
     outputs = [o for o in allowed if o in set(outputs)]
@@ -1214,16 +1232,9 @@ CHILL_OUTPUTS = ("cp", "cu", "valid")
 
 def _chill_common(dev, who, rows, seg, sel, outputs, allowed):
     outputs = _subset(who, outputs, allowed)
-    s = _offsets(who, seg, rows)
-    if len(s) - 1 > 65535:
-        raise ValueError(f"{who}: at most 65535 periods, got {len(s) - 1}")
-    d_sel = None
-    if sel is not None:
-        m = np.ascontiguousarray(sel)
-        if m.shape != (rows,) or m.dtype not in (np.dtype(bool), np.dtype(np.uint8)):
-            raise ValueError(f"{who}: the selection must be a bool or uint8 array of length {rows}")
-        d_sel = dev.to_device(m.astype(np.uint8))
-    return outputs, s, d_sel
+    s, _ = _periods(who, seg, rows)
+    sel = _row_selection(who, sel, rows)
+    return outputs, s, None if sel is None else dev.to_device(sel)
 
 
 def chill_hourly(dev: Device, tas: DeviceArray, seg, row_sel=None, *, add_K: float = 0.0, sub_C: float = 273.15,
@@ -1363,11 +1374,11 @@ EGDD_METHODS = {"bootsma": 0, "qian": 1}
 AGRO_HEMISPHERES = {None: 0, "north": 1, "south": 2}
 
 
-def _agro_outs(dev, outputs, P, C_):
+def _period_outs(dev, outputs, P, C_):
     return {o: dev.empty((P, C_), np.int32 if o == "valid" else np.float64) for o in outputs}
 
 
-def _agro_table(who, a, dtype, n, what):
+def _host_table(who, a, dtype, n, what):
     t = np.ascontiguousarray(a, dtype=dtype)
     if t.shape != (n,):
         raise ValueError(f"{who}: {what} must have {n} entries, got {t.shape}")
@@ -1400,14 +1411,8 @@ def agro_degree_sum(dev: Device, fields: dict, seg, day_sel=None, *, k_cell: Dev
             raise TypeError(f"{who}: {n} is needed for {outputs}")
     got = {n: fields[n] for n in need}
     T, C_, f64 = _same_fields(who, got)
-    s = _offsets(who, seg, T)
-    P = len(s) - 1
-    if P > 65535:
-        raise ValueError(f"{who}: at most 65535 periods, got {P}")
-    if day_sel is not None:
-        m = np.asarray(day_sel)
-        if m.shape != (T,) or m.dtype not in (np.dtype(bool), np.dtype(np.uint8)):
-            raise ValueError(f"{who}: the selection must be a bool or uint8 array of length {T}")
+    s, P = _periods(who, seg, T)
+    sel = _row_selection(who, day_sel, T)
     if k_cell is not None and k_day is not None:
         raise ValueError(f"{who}: at most one day factor (k_cell or k_day)")
     L, d_li = 0, None
@@ -1417,8 +1422,7 @@ def agro_degree_sum(dev: Device, fields: dict, seg, day_sel=None, *, k_cell: Dev
     k_cell = _agro_f64(who, k_cell, (C_,), "k_cell")
     k_day = _agro_f64(who, k_day, (T, L), "k_day")
     k_period = _agro_f64(who, k_period, (P, L), "k_period")
-    sel = None if day_sel is None else np.ascontiguousarray(day_sel).astype(np.uint8)
-    outs = _agro_outs(dev, outputs, P, C_)
+    outs = _period_outs(dev, outputs, P, C_)
     dev.call("xh_agro_degree_sum", T, C_, C_, f64, *(_ptr(got, n) for n in ("tas", "tasmin", "tasmax")), P, np_ptr(s),
              np_ptr(sel) if sel is not None else _vp(0), *(_vp(a.ptr) if a is not None else _vp(0) for a in (k_cell, k_day, k_period)),
              L, _vp(d_li.ptr) if d_li is not None else _vp(0), float(sub_C), float(thresh_hi), float(thresh_bedd),
@@ -1447,19 +1451,16 @@ def agro_monthly(dev: Device, fields: dict, month_off, month_cal, month_days, se
     T, C_, f64 = _same_fields(who, got)
     mo = _offsets(who, month_off, T, "month")
     M = len(mo) - 1
-    sm = _offsets(who, seg_months, M)
-    P = len(sm) - 1
-    if P > 65535:
-        raise ValueError(f"{who}: at most 65535 periods, got {P}")
-    mc = _agro_table(who, month_cal, np.int32, M, "month_cal")
-    md = _agro_table(who, month_days, np.int32, M, "month_days")
+    sm, P = _periods(who, seg_months, M)
+    mc = _host_table(who, month_cal, np.int32, M, "month_cal")
+    md = _host_table(who, month_days, np.int32, M, "month_days")
     if hemisphere not in AGRO_HEMISPHERES:
         raise ValueError(f"{who}: hemisphere must be None, 'north' or 'south', got {hemisphere!r}")
     if hemisphere is None and {"cni", "di"} & set(outputs):
         lat = _agro_f64(who, lat, (C_,), "lat")
         if lat is None:
             raise TypeError(f"{who}: lat is needed unless hemisphere is given")
-    outs = _agro_outs(dev, outputs, P, C_)
+    outs = _period_outs(dev, outputs, P, C_)
     one = np.ones(1, np.int32)
     dev.call("xh_agro_monthly", T, C_, C_, f64, *(_ptr(got, n) for n in ("tasmin", "tas", "pr", "evspsblpot")), M, np_ptr(mo),
              np_ptr(mc if M else one), np_ptr(md if M else one), P, np_ptr(sm), _vp(lat.ptr) if lat is not None else _vp(0),
@@ -1480,15 +1481,12 @@ def egdd(dev: Device, tasmin: DeviceArray, tasmax: DeviceArray, seg, doy, start_
     if method not in EGDD_METHODS:
         raise NotImplementedError(f"Method: {method}.")
     T, C_, f64 = _same_fields(who, {"tasmin": tasmin, "tasmax": tasmax})
-    s = _offsets(who, seg, T)
-    P = len(s) - 1
-    if P > 65535:
-        raise ValueError(f"{who}: at most 65535 periods, got {P}")
-    d = _agro_table(who, doy, np.int32, T, "doy")
-    tabs = [_agro_table(who, a, dt, P, n) for a, dt, n in ((start_from, np.int64, "start_from"), (end_from, np.int64, "end_from"),
+    s, P = _periods(who, seg, T)
+    d = _host_table(who, doy, np.int32, T, "doy")
+    tabs = [_host_table(who, a, dt, P, n) for a, dt, n in ((start_from, np.int64, "start_from"), (end_from, np.int64, "end_from"),
                                                             (day0, np.int64, "day0"), (label_doy, np.int32, "label_doy"),
                                                             (label_days, np.int32, "label_days"))]
-    outs = _agro_outs(dev, outputs, P, C_)
+    outs = _period_outs(dev, outputs, P, C_)
     pad = lambda a: a if a.size else np.zeros(1, a.dtype)  # noqa: E731  (a pointer the entry point may check against NULL)
     dev.call("xh_egdd", T, C_, C_, f64, _vp(tasmin.ptr), _vp(tasmax.ptr), P, np_ptr(s), np_ptr(pad(d)), *(np_ptr(pad(t)) for t in tabs),
              EGDD_METHODS[method], float(sub_C), float(thresh), *(_ptr(outs, o) for o in EGDD_OUTPUTS), C_)
@@ -1532,11 +1530,8 @@ def flow_period_stats(dev: Device, q: DeviceArray, seg, outputs=("bfi", "rbi")) 
     who = "flow_period_stats"
     outputs = _subset(who, outputs, FLOW_OUTPUTS)
     T, C_, f64 = _same_fields(who, {"q": q})
-    s = _offsets(who, seg, T)
-    P = len(s) - 1
-    if P > 65535:
-        raise ValueError(f"{who}: at most 65535 periods, got {P}")
-    outs = _agro_outs(dev, outputs, P, C_)
+    s, P = _periods(who, seg, T)
+    outs = _period_outs(dev, outputs, P, C_)
     dev.call("xh_flow_period_stats", T, C_, C_, f64, _vp(q.ptr), P, np_ptr(s), *(_ptr(outs, o) for o in FLOW_OUTPUTS), C_)
     return outs
 
@@ -1547,10 +1542,7 @@ def melt_period_max(dev: Device, snw: DeviceArray, seg, pr: DeviceArray | None =
     ``-diff(snw)``), (P, C) float64.  ``snw`` / ``pr`` (T, C) DeviceArrays of one dtype."""
     who = "melt_period_max"
     T, C_, f64 = _same_fields(who, {"snw": snw, "pr": pr} if pr is not None else {"snw": snw})
-    s = _offsets(who, seg, T)
-    P = len(s) - 1
-    if P > 65535:
-        raise ValueError(f"{who}: at most 65535 periods, got {P}")
+    s, P = _periods(who, seg, T)
     window = _hydro_window(who, window)
     out = dev.empty((P, C_), np.float64)
     dev.call("xh_melt_period_max", T, C_, C_, f64, _vp(snw.ptr), _vp(pr.ptr) if pr is not None else _vp(0), float(per_day), window, P,
@@ -1616,10 +1608,7 @@ def rain_season(dev: Device, pr: DeviceArray, seg, flags, doy, *, per_day: float
     who = "rain_season"
     outputs = _subset(who, outputs, RAIN_OUTPUTS)
     T, C_, f64 = _same_fields(who, {"pr": pr})
-    s = _offsets(who, seg, T)
-    P = len(s) - 1
-    if P > 65535:
-        raise ValueError(f"{who}: at most 65535 periods, got {P}")
+    s, P = _periods(who, seg, T)
     for name, m in (("method_dry_start", method_dry_start), ("method_dry_end", method_dry_end)):
         if m not in RAIN_METHODS:
             raise ValueError(f"Unknown {name}: {m}.")
@@ -1630,8 +1619,8 @@ def rain_season(dev: Device, pr: DeviceArray, seg, flags, doy, *, per_day: float
     sums = [ww] + [w for w, m in ((wd, method_dry_start), (we, method_dry_end)) if m == "total"]
     if max(sums) > capi.RAIN_MAX_WINDOW:
         raise ValueError(f"{who}: sum windows of up to {capi.RAIN_MAX_WINDOW} rows are served, got {max(sums)}")
-    fl = _agro_table(who, flags, np.uint8, T, "flags")
-    dy = _agro_table(who, doy, np.int32, T, "doy")
+    fl = _host_table(who, flags, np.uint8, T, "flags")
+    dy = _host_table(who, doy, np.int32, T, "doy")
     outs = {o: dev.empty((P, C_), np.float64) for o in outputs}
     dev.call("xh_rain_season", T, C_, C_, f64, _vp(pr.ptr), float(per_day), P, np_ptr(s), np_ptr(fl), np_ptr(dy), float(thresh_wet_start), ww,
              wnd, float(thresh_dry_start), wd, int(method_dry_start == "total"), float(thresh_dry_end), we, int(method_dry_end == "total"),

@@ -270,8 +270,18 @@ RAIN_SIGNATURES: dict[str, list] = {
 RAIN_MAX_WINDOW = 32    # XH_RAIN_MAX_WINDOW
 ZONES_MAX_EDGES = 32    # XH_ZONES_MAX_EDGES
 RAIN_START_WINDOW, RAIN_START_BOUNDS, RAIN_END_BOUNDS = 1, 2, 4   # the XH_RAIN_* flag bits
+# The entry points of include/xclim_hip_flags.h (xclim_amd/csrc/dataflags.hip): the fifth table.
+FLAGS_SIGNATURES: dict[str, list] = {
+    "xh_data_flags": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _i64, _vp, _i64, _int, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _int, _vp,
+                      _i64],
+    "xh_doy_bounds": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _int, _int, _int, _dbl, _vp, _vp, _i64],
+}
+FLAGS_MAX_CHECKS = 16   # XH_FLAGS_MAX_CHECKS
+FLAG_CMP, FLAG_OUTSIDE, FLAG_PAIR, FLAG_REPEAT, FLAG_CLIM = 0, 1, 2, 3, 4   # the XH_FLAG_* check kinds
+# struct xh_flag_check { int32_t kind, op, n, other; double a, b; }
+FLAG_CHECK_DTYPE = np.dtype([("kind", np.int32), ("op", np.int32), ("n", np.int32), ("other", np.int32), ("a", np.float64), ("b", np.float64)])
 _RESTYPES = {"xh_last_error": C.c_char_p}
-_SIGNATURE_TABLES = (SIGNATURES, UNIT_SIGNATURES, HYDRO_SIGNATURES, RAIN_SIGNATURES)
+_SIGNATURE_TABLES = (SIGNATURES, UNIT_SIGNATURES, HYDRO_SIGNATURES, RAIN_SIGNATURES, FLAGS_SIGNATURES)
 
 
 def argtypes_of(name: str):
@@ -289,7 +299,7 @@ def library_path() -> str:
 
 def load_library() -> C.CDLL:
     """Load libxclimhip.so and declare every prototype of include/xclim_hip.h, include/xclim_hip_agro.h,
-    include/xclim_hip_hydro.h and include/xclim_hip_rain.h.  Raises
+    include/xclim_hip_hydro.h, include/xclim_hip_rain.h and include/xclim_hip_flags.h.  Raises
     BackendUnavailable."""
     global _lib
     with _lib_lock:

@@ -1643,3 +1643,73 @@ def rolling_zones(dev: Device, x: DeviceArray, window: int, edges) -> DeviceArra
     out = dev.empty((P, C_), np.float64)
     dev.call("xh_rolling_zones", P, C_, C_, f64, _vp(x.ptr), window, len(e), np_ptr(e), _vp(out.ptr), C_)
     return out
+
+
+# ---- the data-quality-flag unit (include/xclim_hip_flags.h, xclim_amd/csrc/dataflags.hip) ----------------------------
+FLAG_KINDS = {"cmp": capi.FLAG_CMP, "outside": capi.FLAG_OUTSIDE, "pair": capi.FLAG_PAIR, "repeat": capi.FLAG_REPEAT, "clim": capi.FLAG_CLIM}
+
+
+def flag_check(kind: str, op=None, a: float = 0.0, b: float = 0.0, n: int = 0, other: int = 0) -> tuple:
+    """One entry of the check list of :func:`data_flags`: ``("cmp", op, a)``, ``("outside", None, a, b)``, ``("pair", op,
+    other=0 | 1)``, ``("repeat", op | None, a, n=...)`` or ``("clim",)`` as the tuple ``(kind, op, n, other, a, b)`` of
+    ``xh_flag_check``."""
+    if kind not in FLAG_KINDS:
+        raise ValueError(f"data_flags: unknown check kind {kind!r}")
+    code = -1 if op is None else op_code(op)
+    if kind == "repeat" and (isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1):
+        raise ValueError(f"data_flags: n must be an integer of at least 1, got {n!r}")
+    return (FLAG_KINDS[kind], code, int(n), int(other), float(a), float(b))
+
+
+def data_flags(dev: Device, x: DeviceArray, checks, seg, *, y0: DeviceArray | None = None, y1: DeviceArray | None = None, tidx=None,
+               lo: DeviceArray | None = None, hi: DeviceArray | None = None, reduce_cells: bool = False) -> DeviceArray:
+    """xh_data_flags.  ``x`` and the companions ``y0`` / ``y1`` (T, C) DeviceArrays of one dtype, ``checks`` a list of
+    :func:`flag_check` tuples (at most ``capi.FLAGS_MAX_CHECKS``), ``seg`` (P + 1) host row offsets covering [0, T]; for a
+    "clim" check ``tidx`` host int (T) and the bound tables ``lo`` / ``hi`` (D, C) in the fields' dtype.  Returns the uint8
+    flags (K, P, C), or (K, P) with ``reduce_cells``; one launch."""
+    who = "data_flags"
+    fields = {"x": x, **({"y0": y0} if y0 is not None else {}), **({"y1": y1} if y1 is not None else {})}
+    T, C_, f64 = _same_fields(who, fields)
+    s = _offsets(who, seg, T)
+    P = len(s) - 1
+    if s[0] != 0 or s[-1] != T:
+        raise ValueError(f"{who}: the periods must cover [0, {T}]")
+    chk = np.array(list(checks), dtype=capi.FLAG_CHECK_DTYPE).reshape(-1)
+    K_ = len(chk)
+    if K_ > capi.FLAGS_MAX_CHECKS:
+        raise ValueError(f"{who}: at most {capi.FLAGS_MAX_CHECKS} checks in one launch, got {K_}")
+    clim = bool((chk["kind"] == capi.FLAG_CLIM).any())
+    D = 0
+    ti = None
+    if clim:
+        if lo is None or hi is None or tidx is None:
+            raise ValueError(f"{who}: the climatology check needs tidx and both bound tables")
+        for t_ in (lo, hi):
+            if np.dtype(t_.dtype) != np.dtype(x.dtype) or len(t_.shape) != 2 or t_.shape[1] != C_ or t_.shape != lo.shape:
+                raise TypeError(f"{who}: the bound tables must be (D, {C_}) device arrays of the field's dtype")
+        D = int(lo.shape[0])
+        ti = _host_table(who, tidx, np.int32, T, "tidx")
+    out = dev.empty((K_, P) if reduce_cells else (K_, P, C_), np.uint8)
+    p = lambda d: _vp(d.ptr) if d is not None else _vp(0)  # noqa: E731
+    dev.call("xh_data_flags", T, C_, C_, f64, _vp(x.ptr), p(y0), C_, p(y1), C_, K_, np_ptr(chk) if K_ else _vp(0), P, np_ptr(s),
+             np_ptr(ti) if ti is not None else _vp(0), D, p(lo if clim else None), p(hi if clim else None), C_, int(bool(reduce_cells)),
+             _vp(out.ptr), C_)
+    return out
+
+
+def doy_bounds(dev: Device, x: DeviceArray, tbase, window: int, n: float):
+    """xh_doy_bounds: ``(lo, hi)``, the (ndoy, C) tables ``mean -+ n * std`` of the day-of-year climatology over all years and the
+    centred ``window``, in the dtype of ``x`` (T, C) float32 or float64.  ``tbase`` host int (nyears, ndoy) as for
+    :func:`doy_mean_std`."""
+    who = "doy_bounds"
+    T, C_, f64 = _same_fields(who, {"x": x})
+    tb = np.ascontiguousarray(tbase, dtype=np.int32)
+    if tb.ndim != 2 or tb.shape[0] < 1:
+        raise ValueError(f"{who}: tbase must be a (years, days of year) table")
+    if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or window < 1:
+        raise ValueError(f"{who}: window must be an integer of at least 1, got {window!r}")
+    nyears, ndoy = tb.shape
+    lo, hi = dev.empty((ndoy, C_), x.dtype), dev.empty((ndoy, C_), x.dtype)
+    dev.call("xh_doy_bounds", T, C_, C_, f64, _vp(x.ptr), np_ptr(tb if tb.size else np.full(1, -1, np.int32)), nyears, ndoy, int(window),
+             float(n), _vp(lo.ptr), _vp(hi.ptr), C_)
+    return lo, hi

@@ -152,7 +152,7 @@ def install(env=None, modules=None) -> list[str]:
     by default the real packages are used.  Functions the HIP path does not serve are forwarded to the saved originals."""
     import importlib
 
-    from . import agro, anuclim, hydrology, rainseason
+    from . import agro, anuclim, dataflags, hydrology, rainseason
     from .xr_adapter import make_wrappers
 
     env = env or real_env()
@@ -287,6 +287,9 @@ def install(env=None, modules=None) -> list[str]:
     # where pymannkendall is absent (it no longer needs it).  runoff_ratio is unit conversion around two means and stays xclim's,
     # as do lag_snowpack_flow_peaks and the snd_max / snw_max family (select_resample_op, served by the generic wrappers)
     install_mirror(_HYDRO_MODULES, hydrology)
+    # data_flags of core/dataflags.py: the whole list of checks of a variable in one launch; ecad_compliant calls it through the
+    # module global and is thereby served
+    install_mirror(("xclim.core.dataflags",), dataflags, "xarray", "VARIABLES", "_REGISTRY", "DataQualityException")
     cmod = resolve(_PET_MODULE)
     if cmod is not None and all(hasattr(cmod, n) for n in _PET_NAMES):
         from .converters import make_adapters as pet_adapters

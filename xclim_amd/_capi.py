@@ -280,13 +280,26 @@ FLAGS_MAX_CHECKS = 16   # XH_FLAGS_MAX_CHECKS
 FLAG_CMP, FLAG_OUTSIDE, FLAG_PAIR, FLAG_REPEAT, FLAG_CLIM = 0, 1, 2, 3, 4   # the XH_FLAG_* check kinds
 # struct xh_flag_check { int32_t kind, op, n, other; double a, b; }
 FLAG_CHECK_DTYPE = np.dtype([("kind", np.int32), ("op", np.int32), ("n", np.int32), ("other", np.int32), ("a", np.float64), ("b", np.float64)])
+# The entry points of include/xclim_hip_phase.h (xclim_amd/csrc/phase.hip): the sixth table.
+PHASE_SIGNATURES: dict[str, list] = {
+    "xh_precip_phase_map": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64],
+    "xh_precip_phase_period": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _dbl, _i64, _vp, _vp, _int, _vp, _vp, _i64, _vp, _vp, _vp, _int,
+                               C.c_uint32, _vp, _i64],
+}
+PHASE_METHODS = {"binary": 0, "brown": 1, "auer": 2, "dai_annual": 3, "dai_seasonal": 4, "given": 5}   # the XH_PHASE_* methods
+PHASE_NPAR, PHASE_DAI_NTAB, PHASE_NLIM = 6, 96, 7   # XH_PHASE_NPAR, XH_PHASE_DAI_NTAB, XH_PHASE_NLIM
+# the outputs of xh_precip_phase_period in the order of their XH_PHASE_* bits
+PHASE_OUTPUTS = ("pr_sum", "solid_sum", "liquid_sum", "pr_n", "solid_n", "liquid_n", "tas_n", "snow_days", "snow_sum_over", "snow_n_over",
+                 "first_snow", "last_snow", "hplt_days", "rofg_days")
 _RESTYPES = {"xh_last_error": C.c_char_p}
+# (the tables of the first five headers keep their tuple; every table, the sixth included, is in _ALL_SIGNATURE_TABLES)
 _SIGNATURE_TABLES = (SIGNATURES, UNIT_SIGNATURES, HYDRO_SIGNATURES, RAIN_SIGNATURES, FLAGS_SIGNATURES)
+_ALL_SIGNATURE_TABLES = _SIGNATURE_TABLES + (PHASE_SIGNATURES,)
 
 
 def argtypes_of(name: str):
     """The argtypes of an entry point, whichever header's table declares it; None for a name that no table holds."""
-    return next((table[name] for table in _SIGNATURE_TABLES if name in table), None)
+    return next((table[name] for table in _ALL_SIGNATURE_TABLES if name in table), None)
 
 
 _lib = None
@@ -299,7 +312,7 @@ def library_path() -> str:
 
 def load_library() -> C.CDLL:
     """Load libxclimhip.so and declare every prototype of include/xclim_hip.h, include/xclim_hip_agro.h,
-    include/xclim_hip_hydro.h, include/xclim_hip_rain.h and include/xclim_hip_flags.h.  Raises
+    include/xclim_hip_hydro.h, include/xclim_hip_rain.h, include/xclim_hip_flags.h and include/xclim_hip_phase.h.  Raises
     BackendUnavailable."""
     global _lib
     with _lib_lock:
@@ -314,7 +327,7 @@ def load_library() -> C.CDLL:
             lib = C.CDLL(_LIB_PATH)
         except OSError as err:  # pragma: no cover
             raise BackendUnavailable(f"cannot load {_LIB_PATH}: {err}") from err
-        for name in (name for table in _SIGNATURE_TABLES for name in table):
+        for name in (name for table in _ALL_SIGNATURE_TABLES for name in table):
             fn = getattr(lib, name)  # AttributeError if the header and the library diverge
             fn.argtypes = argtypes_of(name)
             fn.restype = _RESTYPES.get(name, _int)

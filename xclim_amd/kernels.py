@@ -1713,3 +1713,77 @@ def doy_bounds(dev: Device, x: DeviceArray, tbase, window: int, n: float):
     dev.call("xh_doy_bounds", T, C_, C_, f64, _vp(x.ptr), np_ptr(tb if tb.size else np.full(1, -1, np.int32)), nyears, ndoy, int(window),
              float(n), _vp(lo.ptr), _vp(hi.ptr), C_)
     return lo, hi
+
+
+# ---- the snow / rain partition unit (include/xclim_hip_phase.h, xclim_amd/csrc/phase.hip) ----------------------------
+PHASE_MAP_OUTPUTS = ("snow", "rain")
+PHASE_LIMITS = ("snow_low", "snow_high", "snow_thresh", "hplt_pr", "hplt_tas", "rofg_pr", "rofg_frz")
+
+
+def _phase_partition(who, part: dict, T, C_):
+    """The arguments (method, par, tab, ntab, season, land) of a partition ``{"method", "par", "tab", "season", "land"}`` (built by
+    :func:`xclim_amd.phase.partition`), with the host arrays that must outlive the call."""
+    method = part["method"]
+    if method not in capi.PHASE_METHODS:
+        raise ValueError(f"{who}: unknown method {method!r}")
+    par = _host_table(who, part["par"], np.float64, capi.PHASE_NPAR, "par")
+    tab, ntab = part.get("tab"), 0
+    if tab is not None:
+        tab = np.ascontiguousarray(tab, dtype=np.float64).reshape(-1)
+        ntab = len(tab) // 2 if method == "auer" else len(tab)
+    season = part.get("season")
+    if season is not None:
+        season = _host_table(who, season, np.uint8, T, "season")
+    land = part.get("land")
+    if land is not None and (not isinstance(land, DeviceArray) or np.dtype(land.dtype) != np.uint8 or int(np.prod(land.shape)) != C_):
+        raise TypeError(f"{who}: land must be a uint8 device array with one entry per cell")
+    keep = (par, tab, season)
+    args = (capi.PHASE_METHODS[method], np_ptr(par), np_ptr(tab) if tab is not None else _vp(0), ntab,
+            np_ptr(season) if season is not None else _vp(0), _vp(land.ptr) if land is not None else _vp(0))
+    return args, keep
+
+
+def precip_phase_map(dev: Device, pr: DeviceArray, tas: DeviceArray, part: dict, outputs=PHASE_MAP_OUTPUTS) -> dict:
+    """xh_precip_phase_map: the snow and / or rain part of every sample of ``pr`` by ``tas`` (T, C), both float32 or both float64,
+    one launch.  Outputs have the dtype of the fields for the "binary" method and are float64 otherwise."""
+    who = "precip_phase_map"
+    outputs = _subset(who, outputs, PHASE_MAP_OUTPUTS)
+    T, C_, f64 = _same_fields(who, {"pr": pr, "tas": tas})
+    args, keep = _phase_partition(who, part, T, C_)
+    dtype = pr.dtype if part["method"] == "binary" else np.float64
+    outs = {o: dev.empty((T, C_), dtype) for o in outputs}
+    dev.call("xh_precip_phase_map", T, C_, C_, f64, _vp(pr.ptr), _vp(tas.ptr), *args, *(_ptr(outs, o) for o in PHASE_MAP_OUTPUTS), C_)
+    del keep
+    return outs
+
+
+def precip_phase_period(dev: Device, pr: DeviceArray, tas: DeviceArray, seg, part: dict, outputs, *, per_day: float = 86400.0,
+                        doy=None, window: int = 7, **limits) -> dict:
+    """xh_precip_phase_period: any subset of ``capi.PHASE_OUTPUTS`` per period from ONE launch and one read of ``pr`` and of the
+    second field (``tas``, or the solid precipitation itself with the "given" method).  ``seg`` (P + 1) host row offsets, ``doy``
+    host int (T), needed by first_snow / last_snow.  ``limits``: ``PHASE_LIMITS`` (snow limits in mm of ``snow * per_day``, the
+    others in the fields' own units).  Returns ``{name: (P, C) float64 DeviceArray}``."""
+    who = "precip_phase_period"
+    outputs = _subset(who, outputs, capi.PHASE_OUTPUTS)
+    T, C_, f64 = _same_fields(who, {"pr": pr, "tas": tas})
+    s, P = _periods(who, seg, T)
+    if set(limits) - set(PHASE_LIMITS):
+        raise TypeError(f"{who}: unknown limits {sorted(set(limits) - set(PHASE_LIMITS))}")
+    if part["method"] == "given" and {"hplt_days", "rofg_days"} & set(outputs):
+        raise ValueError(f"{who}: hplt_days and rofg_days need a temperature")
+    window = _rain_window(who, "window", window)
+    defaults = {"snow_low": 0.0, "snow_high": np.inf, "snow_thresh": 1.0, "hplt_pr": 0.0, "hplt_tas": 0.0, "rofg_pr": 0.0, "rofg_frz": 0.0}
+    lim = np.array([float(limits.get(k, defaults[k])) for k in PHASE_LIMITS], np.float64)
+    dy = None
+    if {"first_snow", "last_snow"} & set(outputs):
+        if doy is None:
+            raise ValueError(f"{who}: first_snow / last_snow need doy")
+        dy = _host_table(who, doy, np.int32, T, "doy")
+    args, keep = _phase_partition(who, part, T, C_)
+    outs = {o: dev.empty((P, C_), np.float64) for o in outputs}
+    ptrs = np.array([outs[o].ptr if o in outs else 0 for o in capi.PHASE_OUTPUTS], np.uint64)
+    mask = sum(1 << k for k, o in enumerate(capi.PHASE_OUTPUTS) if o in outs)
+    dev.call("xh_precip_phase_period", T, C_, C_, f64, _vp(pr.ptr), _vp(tas.ptr), float(per_day), P, np_ptr(s),
+             np_ptr(dy) if dy is not None else _vp(0), *args, np_ptr(lim), window, mask, np_ptr(ptrs), C_)
+    del keep
+    return outs

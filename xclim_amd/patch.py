@@ -152,7 +152,7 @@ def install(env=None, modules=None) -> list[str]:
     by default the real packages are used.  Functions the HIP path does not serve are forwarded to the saved originals."""
     import importlib
 
-    from . import agro, anuclim, dataflags, hydrology, rainseason
+    from . import agro, anuclim, dataflags, hydrology, phase, rainseason
     from .xr_adapter import make_wrappers
 
     env = env or real_env()
@@ -290,6 +290,11 @@ def install(env=None, modules=None) -> list[str]:
     # data_flags of core/dataflags.py: the whole list of checks of a variable in one launch; ecad_compliant calls it through the
     # module global and is thereby served
     install_mirror(("xclim.core.dataflags",), dataflags, "xarray", "VARIABLES", "_REGISTRY", "DataQualityException")
+    # the snow / rain partition and its period indices, defined in three modules: the two approximations of converters.py
+    # (_multivariate.py imports them by name), six functions of _multivariate.py and the four snowfall indices of _threshold.py
+    install_mirror(("xclim.indices.converters", "xclim.indices", "xclim.indices._multivariate"), phase.converters)
+    install_mirror(("xclim.indices._multivariate", "xclim.indices"), phase.multivariate)
+    install_mirror(("xclim.indices._threshold", "xclim.indices"), phase.threshold)
     cmod = resolve(_PET_MODULE)
     if cmod is not None and all(hasattr(cmod, n) for n in _PET_NAMES):
         from .converters import make_adapters as pet_adapters

@@ -294,7 +294,7 @@ class _SimLib:
                 return getattr(self._mock, name)
             raise NotImplementedError(f"{name}: not simulated on the host (kernels written at ISA level, or a runtime service the "
                                       "simulation does not provide)") from None
-        fn.argtypes = _capi.argtypes_of(name)
+        fn.argtypes = _capi.SIGNATURES.get(name)
         fn.restype = _capi._RESTYPES.get(name, C.c_int)
         setattr(self, name, fn)
         return fn

@@ -1,38 +1,70 @@
-"""A padded replay of ``Device.call``: every strided operand of an entry point of include/xclim_hip.h is moved into a view
-whose rows are longer than the field is wide, with poison in the extra columns, before the real entry point runs.
+"""A padded replay of ``Device.call``: every strided operand of an entry point is moved into a view whose rows are longer than the
+field is wide, with poison in the extra columns, before the real entry point runs.
 
-``TABLE`` maps each entry point to its strided operands (by the parameter names of the header); ``padded`` is the context
-manager that replaces ``dev.call`` on one Device.  The shapes of the tests are small, so every operand takes a host round
-trip (``wrap`` / ``get`` / ``to_device``): the helper runs on the real device and on the host simulation alike."""
+This module owns the parsing of the six headers under include/ (``header_declarations``; ``prototypes`` is its view of the names) and the
+registry of strided operands, by the parameter names of the headers.  The registry is two pairs of dicts, kept apart because the
+guards of tests/test_strided_abi_cpu.py and tests/test_unwritten_outputs_cpu.py range over the first pair alone:
+  * ``PROTOS`` / ``TABLE``: include/xclim_hip.h and the operands whose stride parameter matches ``STRIDE_NAME``, each reached by a
+    case of tests/test_gpu_strided_abi.py;
+  * ``UNIT_PROTOS`` / ``PITCHED``: the five unit headers, and the operands of every entry point whose row pitches are called ``ld``
+    and ``ld_out`` — those of the unit headers (``AGRO_TABLE`` ... ``PHASE_TABLE``, with ``AGRO_TABLES`` ... ``PHASE_TABLES`` for their
+    other pointers, the host tables) and the chill and BIO1-BIO19 entry points of the main header.  The padded cases of these
+    live in the GPU module of their unit.
+``parameters`` and ``operands`` look a name up in both.  ``padded`` is the context manager that replaces ``dev.call`` on one Device.
+The shapes of the tests are small, so every operand takes a host round trip (``wrap`` / ``get`` / ``to_device``): the helper runs
+on the real device and on the host simulation alike."""
 import contextlib
 import ctypes
+import glob
 import os
 import re
 from collections import namedtuple
 
 import numpy as np
 
-HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "xclim_hip.h")
+INCLUDE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
+HEADER = os.path.join(INCLUDE, "xclim_hip.h")
+HEADERS = sorted(glob.glob(os.path.join(INCLUDE, "*.h")))   # the main header first: "xclim_hip.h" sorts before "xclim_hip_*.h"
 _vp = ctypes.c_void_p
 
 STRIDE_NAME = re.compile(r"^(st\d*|sc|sn|fst|st_\w+|\w+_st|\w+_stride)$")
 
 
+def header_declarations(path=HEADER):
+    """{entry point: [(declaration text, parameter name), ...]} of a header, the context first."""
+    text = re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
+    found = {}
+    for name, params in re.findall(r"\b(?:int|const char\*)\s+(xh_\w+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
+        params = [" ".join(p.split()) for p in params.split(",")]
+        found[name] = [(p, re.findall(r"\w+", p)[-1]) for p in params if p and p != "void"]
+    return found
+
+
 def prototypes(path=HEADER):
     """{entry point: [parameter names]} of the header, the context first."""
-    text = re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
-    protos = {}
-    for name, params in re.findall(r"\b(?:int|const char\*)\s+(xh_\w+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
-        names = []
-        for p in params.split(","):
-            p = p.strip()
-            if p and p != "void":
-                names.append(re.findall(r"\w+", p)[-1])
-        protos[name] = names
-    return protos
+    return {name: [n for _, n in decl] for name, decl in header_declarations(path).items()}
+
+
+_KINDS = {"int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "uint32_t": ctypes.c_uint32, "int32_t": ctypes.c_int32,
+          "size_t": ctypes.c_size_t, "double": ctypes.c_double, "float": ctypes.c_float, "int": ctypes.c_int}
+
+
+def is_ctypes_kind(decl, argtype):
+    """Is `argtype` the ctypes kind of a parameter declared as `decl`?  A pointer is c_void_p, c_char_p or a POINTER(...) type;
+    a scalar is the one type of its C type name."""
+    if "*" in decl:
+        return argtype in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(argtype, ctypes._Pointer)
+    return argtype is _KINDS[decl.replace("const ", "").split()[0]]
 
 
 PROTOS = prototypes()
+UNIT_PROTOS = {name: names for path in HEADERS[1:] for name, names in prototypes(path).items()}
+
+
+def parameters(name):
+    """The parameter names of an entry point of any of the six headers, the context first."""
+    return PROTOS[name] if name in PROTOS else UNIT_PROTOS[name]
+
 
 # ptr / stride: parameter names.  rows / width / dtype: an expression over the call's arguments (by parameter name), or a
 # function (arguments, device).  mode: r (read), w (written everywhere), rw (written in part: what the caller held is kept).
@@ -160,6 +192,75 @@ TABLE = {
 # entry points with a stride-like parameter that move bytes and compute nothing
 EXEMPT = {}
 
+# ---- the pitched entry points (ld / ld_out): one slice per unit, imported by name by the unit's test modules ----------------
+_F = "'f8' if f64 else 'f4'"
+
+
+def _unit(reads, writes, rows="P", in_rows="T", ints=("valid_out", "n_out")):
+    return [R(n, "ld", in_rows, dtype=_F) for n in reads] + [W(n, "ld_out", rows, dtype="i4" if n in ints else "f8") for n in writes]
+
+
+AGRO_TABLE = {
+    "xh_agro_degree_sum": _unit(("tas", "tasmin", "tasmax"), ("hi_out", "bedd_out", "valid_out")),
+    "xh_agro_monthly": _unit(("tasmin", "tas", "pr", "evspsblpot"), ("cni_out", "mtwm_out", "di_out", "valid_out")),
+    "xh_egdd": _unit(("tasmin", "tasmax"), ("egdd_out", "start_out", "end_out", "valid_out")),
+    "xh_corn_heat_units": _unit(("tasmin", "tasmax"), ("out",), "T"),
+    "xh_qian_wma": _unit(("tas",), ("out",), "T"),
+}
+HYDRO_TABLE = {
+    "xh_flow_period_stats": _unit(("q",), ("bfi_out", "rbi_out", "mean_out", "sum_out", "valid_out")),
+    "xh_melt_period_max": _unit(("snw", "pr"), ("out",)),
+    "xh_antecedent_precip": _unit(("pr",), ("out",), "T"),
+    "xh_sen_slope": _unit(("x",), ("slope_out", "p_out", "n_out"), "K", in_rows="P"),
+}
+RAIN_TABLE = {
+    "xh_rain_season": _unit(("pr",), ("start_out", "end_out", "length_out")),
+    "xh_rolling_zones": _unit(("x",), ("out",), in_rows="P"),
+}
+# (the reduced form of `out` of xh_data_flags is K * P bytes without a pitch and is not replayed on padded views)
+FLAGS_TABLE = {
+    "xh_data_flags": [R("x", "ld", "T", dtype=_F), R("y0", "ld_y0", "T", dtype=_F), R("y1", "ld_y1", "T", dtype=_F),
+                      R("lo", "ld_tab", "D", dtype=_F), R("hi", "ld_tab", "D", dtype=_F), W("out", "ld_out", "K * P", dtype="u1")],
+    "xh_doy_bounds": [R("x", "ld", "T", dtype=_F), W("lo", "ld_out", "ndoy", dtype=_F), W("hi", "ld_out", "ndoy", dtype=_F)],
+}
+_FO = "'f8' if (f64 or method != 0) else 'f4'"
+PHASE_TABLE = {
+    "xh_precip_phase_map": [R("pr", "ld", "T", dtype=_F), R("tas", "ld", "T", dtype=_F), W("snow_out", "ld_out", "T", dtype=_FO),
+                            W("rain_out", "ld_out", "T", dtype=_FO)],
+    "xh_precip_phase_period": [R("pr", "ld", "T", dtype=_F), R("tas", "ld", "T", dtype=_F), W("outs", "ld_out", "P", dtype="f8", ptrs=14)],
+}
+CHILL_TABLE = {
+    "xh_chill_hourly": [R("tas", "ld", "H", dtype=_F), W("cp_out", "ld_out", "P", dtype="f8"), W("cu_out", "ld_out", "P", dtype="f8"),
+                        W("valid_out", "ld_out", "P", dtype="i4"), W("delta_out", "ld_out", "H", dtype="f8")],
+    "xh_chill_daily": [R("tasmin", "ld", "D", dtype=_F), R("tasmax", "ld", "D", dtype=_F), W("cp_out", "ld_out", "P", dtype="f8"),
+                       W("cu_out", "ld_out", "P", dtype="f8"), W("valid_out", "ld_out", "P", dtype="i4"),
+                       W("hourly_out", "ld_out", "24 * D", dtype="f8")],
+}
+BIOCLIM_TABLE = {"xh_bioclim": [R(n, "ld", "T", dtype=_F) for n in ("tas", "tasmin", "tasmax", "pr")]
+                 + [W("outputs", "ld_out", "P", dtype="f8", ptrs="19"), W("which_out", "ld_out", "P", dtype="i4", ptrs="4"),
+                    W("count_out", "ld_out", "P", dtype="i4", ptrs="4")]}
+PITCHED = {**AGRO_TABLE, **HYDRO_TABLE, **RAIN_TABLE, **FLAGS_TABLE, **PHASE_TABLE, **CHILL_TABLE, **BIOCLIM_TABLE}
+
+# every other pointer of the unit headers' entry points: the host tables and the dense per-cell / per-latitude inputs (no pitch)
+AGRO_TABLES = {
+    "xh_agro_degree_sum": ("seg", "day_sel", "k_cell", "k_day", "k_period", "lat_idx"),
+    "xh_agro_monthly": ("month_off", "month_cal", "month_days", "seg_months", "lat"),
+    "xh_egdd": ("seg", "doy", "start_from", "end_from", "day0", "label_doy", "label_days"),
+    "xh_corn_heat_units": (),
+    "xh_qian_wma": (),
+}
+HYDRO_TABLES = {"xh_flow_period_stats": ("seg",), "xh_melt_period_max": ("seg",), "xh_antecedent_precip": ("weights",),
+                "xh_sen_slope": ("period_of",)}
+RAIN_TABLES = {"xh_rain_season": ("seg", "flags", "doy"), "xh_rolling_zones": ("edges",)}
+FLAGS_TABLES = {"xh_data_flags": ("checks", "seg", "tidx"), "xh_doy_bounds": ("tbase",)}
+PHASE_TABLES = {"xh_precip_phase_map": ("par", "tab", "season", "land"), "xh_precip_phase_period": ("seg", "doy", "par", "tab", "season", "land", "lim")}
+HOST_TABLES = {**AGRO_TABLES, **HYDRO_TABLES, **RAIN_TABLES, **FLAGS_TABLES, **PHASE_TABLES}
+
+
+def operands(name):
+    """The strided operands of an entry point of either table; () for one that has none."""
+    return TABLE[name] if name in TABLE else PITCHED.get(name, ())
+
 _DTYPES = {"f4": np.float32, "f8": np.float64, "u1": np.uint8, "i4": np.int32}
 
 
@@ -178,13 +279,13 @@ def _ev(expr, env, dev):
     if callable(expr):
         return expr(env, dev)
     if isinstance(expr, str):
-        return eval(expr, {}, env)  # noqa: S307 - the expressions of TABLE above
+        return eval(expr, {}, env)  # noqa: S307 - the expressions of the tables above
     return expr
 
 
 def arguments(name, args):
     """{parameter name: value} of one dev.call (the context is not among the arguments)."""
-    names = PROTOS[name][1:]
+    names = parameters(name)[1:]
     assert len(names) == len(args), (name, len(names), len(args))
     return {n: _value(a) for n, a in zip(names, args)}
 
@@ -240,23 +341,24 @@ class _Buffer:
 
 @contextlib.contextmanager
 def padded(dev, monkeypatch, pads=(1, 3, 5), shift=0):
-    """Inside the block every call of an entry point of TABLE runs on padded, poisoned row views (see the module text).
+    """Inside the block every call of an entry point of TABLE or PITCHED runs on padded, poisoned row views (see the module text).
     Yields the log: one (entry point, {stride parameter: (stride used, width of the operand)}) per replayed call."""
     log = []
     real = dev.call
 
     def replay(name, *args):
-        if name not in TABLE:
+        ops = operands(name)
+        if not ops:
             return real(name, *args)
-        names = PROTOS[name][1:]
+        names = parameters(name)[1:]
         env = arguments(name, args)
         new = list(args)
         buffers, pad_of, used, finish = {}, {}, {}, []
         nread = 0
         # memory that one operand reads and another writes (an in-place call) is one buffer that keeps what the caller held
-        single = [op for op in TABLE[name] if op.ptrs is None and env[op.ptr]]
+        single = [op for op in ops if op.ptrs is None and env[op.ptr]]
         inplace = {env[op.ptr] for op in single if op.mode == "r"} & {env[op.ptr] for op in single if op.mode != "r"}
-        for op in TABLE[name]:
+        for op in ops:
             if not env[op.ptr]:
                 continue
             param, rows, width, dtype = layout(op, env, dev)

@@ -1,7 +1,7 @@
 """The agroclimatic heat-sum unit without a GPU: the numpy restatement tests/agrocpu.py against the known answers of the
 reference's own tests and against tests/golden/agro_vectors.npz; the host tables and coefficients of xclim_amd.agro against the
-restatement's; the C ABI of include/xclim_hip_agro.h (header, ctypes, exports, the operand table that the padded and
-unwritten-output checks of tests/test_gpu_agro.py run on); the refusals, on the host simulation.  ``golden_case``, ``check``,
+restatement's; what of the C ABI of include/xclim_hip_agro.h is the unit's own (tests/test_abi_cpu.py checks header, ctypes table,
+library and the operand table of tests/stridedabi.py); the refusals, on the host simulation.  ``golden_case``, ``check``,
 ``launch`` and ``refusals`` are what tests/test_gpu_agro.py runs on the device.
 
 Tolerance (check): |got - want| <= 1e-12 * scale, for float32 and float64 fields alike, because both widen the same values;
@@ -11,7 +11,6 @@ Counts, the EGDD start / end days and the NaN patterns must match exactly."""
 import ctypes
 import json
 import os
-import re
 import types
 
 import numpy as np
@@ -19,6 +18,7 @@ import pytest
 
 import agrocpu as A
 import stridedabi as S
+from stridedabi import AGRO_TABLE
 from xclim_amd import _capi, agro
 from xclim_amd.calendar import select_time_mask
 from xclim_amd.timeaxis import TimeAxis
@@ -324,79 +324,20 @@ def test_axes_and_arguments_that_are_not_served():
         agro.dryness_index(x[:365], x[:365], "north", time=TimeAxis.daily("2001-01-01", 365), flux_units="in/d")
 
 
-# ---- the C ABI -------------------------------------------------------------------------------------------------------
-_F = "'f8' if f64 else 'f4'"
-
-
-def _ops(reads, writes, rows="P"):
-    return [S.R(n, "ld", "T", dtype=_F) for n in reads] + [S.W(n, "ld_out", rows, dtype="i4" if n == "valid_out" else "f8") for n in writes]
-
-
-# every strided operand of the new header, by parameter name (stridedabi.padded and the unwritten-output watch run on it) ...
-AGRO_TABLE = {
-    "xh_agro_degree_sum": _ops(("tas", "tasmin", "tasmax"), ("hi_out", "bedd_out", "valid_out")),
-    "xh_agro_monthly": _ops(("tasmin", "tas", "pr", "evspsblpot"), ("cni_out", "mtwm_out", "di_out", "valid_out")),
-    "xh_egdd": _ops(("tasmin", "tasmax"), ("egdd_out", "start_out", "end_out", "valid_out")),
-    "xh_corn_heat_units": _ops(("tasmin", "tasmax"), ("out",), "T"),
-    "xh_qian_wma": _ops(("tas",), ("out",), "T"),
-}
-# ... and every other pointer: the host tables and the dense per-cell / per-latitude inputs (no pitch of their own)
-AGRO_TABLES = {
-    "xh_agro_degree_sum": ("seg", "day_sel", "k_cell", "k_day", "k_period", "lat_idx"),
-    "xh_agro_monthly": ("month_off", "month_cal", "month_days", "seg_months", "lat"),
-    "xh_egdd": ("seg", "doy", "start_from", "end_from", "day0", "label_doy", "label_days"),
-    "xh_corn_heat_units": (),
-    "xh_qian_wma": (),
-}
-
-
-def declarations(path=HEADER):
-    """{entry point: [declaration of every parameter]} of the header."""
-    txt = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return {name: [a.strip() for a in params.split(",")] for name, params in re.findall(r"\bint\s+(xh_\w+)\s*\(([^;]*)\);", txt)}
-
-
-def test_header_ctypes_and_exports_agree():
-    lib = _capi.load_library()
-    decls = declarations()
-    assert set(decls) == set(_capi.UNIT_SIGNATURES) == set(S.prototypes(HEADER)) == set(AGRO_TABLE)
-    assert not set(decls) & set(_capi.SIGNATURES)
-    for name, decl in decls.items():
-        sig = _capi.UNIT_SIGNATURES[name]
-        assert len(decl) == len(sig), name
-        for d, s in zip(decl, sig):
-            kind = (ctypes.c_void_p if "*" in d else ctypes.c_int64 if d.startswith("int64_t") else ctypes.c_double if d.startswith("double")
-                    else ctypes.c_int)
-            assert s is kind, (name, d, s)
-        fn = getattr(lib, name)                    # exported, and declared by load_library()
-        assert list(fn.argtypes) == sig and fn.restype is ctypes.c_int
+# ---- the C ABI (tests/test_abi_cpu.py checks the header against the ctypes table, the library and the registry) ---------
+def test_the_unit_is_built_and_its_operand_table_is_the_header_s():
+    assert set(S.prototypes(HEADER)) == set(AGRO_TABLE)
     assert "agro.hip" in open(os.path.join(ROOT, "xclim_amd", "csrc", "Makefile")).read()
     assert '#include "xclim_hip.h"' in open(HEADER).read()
 
 
-def test_every_pointer_and_pitch_of_the_new_header_is_in_the_tables():
-    protos = S.prototypes(HEADER)
-    for name, decl in declarations().items():
-        names = protos[name]
-        assert len(names) == len(decl)
-        ops = AGRO_TABLE[name]
-        listed = {op.ptr for op in ops} | set(AGRO_TABLES[name])
-        pointers = {n for n, d in zip(names, decl) if "*" in d and n != "ctx"}
-        assert pointers == listed, (name, pointers ^ listed)
-        pitches = {n for n in names if n.startswith("ld")}
-        assert pitches == {op.stride for op in ops} == {"ld", "ld_out"}, name
-        for op in ops:                             # inputs are const, outputs are not; the dtype of the table is the declared one
-            d = decl[names.index(op.ptr)]
-            assert ("const" in d) == (op.mode == "r"), (name, d)
-            assert op.mode == "r" or ("int32_t" in d) == (op.dtype == "i4"), (name, d)
-        out_rows = {op.rows for op in ops if op.mode == "w"}
+def test_the_outputs_have_the_rows_and_the_integer_type_of_the_header():
+    for name, decl in S.header_declarations(HEADER).items():
+        text = {n: t for t, n in decl}
+        for op in AGRO_TABLE[name]:                # the dtype of the table is the declared one
+            assert op.mode == "r" or ("int32_t" in text[op.ptr]) == (op.dtype == "i4"), (name, op.ptr)
+        out_rows = {op.rows for op in AGRO_TABLE[name] if op.mode == "w"}
         assert out_rows == ({"T"} if name in ("xh_corn_heat_units", "xh_qian_wma") else {"P"})
-
-
-def test_the_main_header_and_its_table_are_unchanged_in_count():
-    assert len(_capi.SIGNATURES) == 125
-    assert len(S.prototypes()) == 125
-    assert len(_capi.UNIT_SIGNATURES) == 5
 
 
 def test_entry_points_reject_a_null_context():
@@ -410,12 +351,6 @@ def test_entry_points_reject_a_null_context():
                        4) == _capi.XH_ERR_ARG
     assert lib.xh_corn_heat_units(null, 10, 4, 4, 0, some, some, 0.0, 4.44, 10.0, some, 4) == _capi.XH_ERR_ARG
     assert lib.xh_qian_wma(null, 10, 4, 4, 0, some, some, 4) == _capi.XH_ERR_ARG
-
-
-def entry(dev, name):
-    fn = getattr(dev.lib, name)
-    fn.argtypes, fn.restype = _capi.UNIT_SIGNATURES[name], ctypes.c_int
-    return fn
 
 
 def refusals(dev):
@@ -436,7 +371,7 @@ def refusals(dev):
     seg = np.array([0, 20, T], np.int64)
     many = np.zeros(65538, np.int64)
 
-    deg = entry(dev, "xh_agro_degree_sum")
+    deg = dev.lib.xh_agro_degree_sum
 
     def degree(ld=C, ld_out=C, seg=seg, P=P, tas=x, tasmin=x, tasmax=x, k_cell=None, k_day=None, lat_idx=None, L=0, hi=out, bedd=out,
                T=T, C=C, ctx=dev.ctx):
@@ -454,7 +389,7 @@ def refusals(dev):
     shared_refusals(degree, T, C, [("seg", seg, T, dict(seg=many, P=65536))])
 
     mo, mc, md, sm = np.array([0, 31, T], np.int64), np.array([1, 2], np.int32), np.array([31, 28], np.int32), np.array([0, 1, 2], np.int64)
-    mon = entry(dev, "xh_agro_monthly")
+    mon = dev.lib.xh_agro_monthly
 
     def monthly(mo=mo, mc=mc, md=md, sm=sm, lat=kc, hemisphere=0, cni=out, di=out, pr=x, ld=C, ld_out=C, P=P, T=T, C=C, ctx=dev.ctx):
         return mon(ctx, T, C, ld, 1, d(x), d(x), d(pr), d(x), 2, p(mo), p(mc), p(md), P, p(sm), d(lat), hemisphere, K2C, 86400.0, 200.0,
@@ -473,7 +408,7 @@ def refusals(dev):
     doy = np.arange(1, T + 1, dtype=np.int32)
     sf, ef, d0 = np.array([0, 20], np.int64), np.array([5, -1], np.int64), np.zeros(P, np.int64)
     ldoy, ldays = np.ones(P, np.int32), np.full(P, 365, np.int32)
-    eg = entry(dev, "xh_egdd")
+    eg = dev.lib.xh_egdd
 
     def egdd(seg=seg, doy=doy, sf=sf, ef=ef, d0=d0, ldoy=ldoy, ldays=ldays, method=0, o=out, tasmin=x, ld_out=C, ld=C, P=P, T=T, C=C,
              ctx=dev.ctx):
@@ -488,7 +423,7 @@ def refusals(dev):
     assert egdd(doy=np.zeros(T, np.int32)) == ARG and egdd(ldays=np.full(P, 300, np.int32)) == ARG
     shared_refusals(egdd, T, C, [("seg", seg, T, dict(seg=many, P=65536))])
 
-    chu, qian = entry(dev, "xh_corn_heat_units"), entry(dev, "xh_qian_wma")
+    chu, qian = dev.lib.xh_corn_heat_units, dev.lib.xh_qian_wma
     assert chu(dev.ctx, T, C, C - 1, 1, d(x), d(x), K2C, 4.44, 10.0, d(out), C) == LAYOUT
     assert chu(dev.ctx, T, C, C, 1, d(x), _vp(0), K2C, 4.44, 10.0, d(out), C) == ARG
     assert chu(dev.ctx, T, C, C, 1, d(x), d(x), K2C, 4.44, 10.0, _vp(0), C) == ARG

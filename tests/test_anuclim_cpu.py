@@ -5,13 +5,13 @@ NULL context).  ``golden_case`` is what tests/test_gpu_bioclim.py loads its case
 import ctypes
 import json
 import os
-import re
 import types
 
 import numpy as np
 import pytest
 
 import anuclimcpu as A
+import stridedabi as S
 from xclim_amd import _capi, anuclim
 from xclim_amd.timeaxis import TimeAxis
 
@@ -164,14 +164,11 @@ def test_axes_that_are_not_served():
 def test_entry_point_header_ctypes_and_exports():
     lib = _capi.load_library()
     assert hasattr(lib, "xh_bioclim")
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "xclim_hip.h")).read(), flags=re.S)
-    decl = [a.strip() for a in re.search(r"\bint\s+xh_bioclim\s*\(([^;]*)\);", txt).group(1).split(",")]
+    decl = S.header_declarations()["xh_bioclim"]
     sig = _capi.SIGNATURES["xh_bioclim"]
     assert len(decl) == 24 == len(sig)
-    for d, s in zip(decl, sig):
-        kind = (ctypes.c_void_p if "*" in d else ctypes.c_int64 if d.startswith("int64_t") else ctypes.c_double if d.startswith("double")
-                else ctypes.c_int)
-        assert s is kind, (d, s)
+    for (d, _), s in zip(decl, sig):
+        assert S.is_ctypes_kind(d, s) and (s is ctypes.c_void_p or "*" not in d), (d, s)
     assert "bioclim.hip" in open(os.path.join(ROOT, "xclim_amd", "csrc", "Makefile")).read()
 
 

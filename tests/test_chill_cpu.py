@@ -6,7 +6,6 @@ offsets and expected counts, argument errors)."""
 import ctypes
 import json
 import os
-import re
 import sys
 
 import numpy as np
@@ -18,6 +17,7 @@ sys.path.insert(0, HERE)
 sys.path.insert(0, ROOT)
 
 import chillcpu  # noqa: E402
+import stridedabi as S  # noqa: E402
 
 from xclim_amd import _capi  # noqa: E402
 from xclim_amd import chill  # noqa: E402
@@ -197,24 +197,15 @@ def test_nan_rule_of_the_dynamic_model():
 
 
 # ---- the C ABI -----------------------------------------------------------------------------------------------------
-def _header_decl(name):
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "xclim_hip.h")).read(), flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*)\);", txt)
-    assert m, name
-    return [a.strip() for a in m.group(1).split(",")]
-
-
 @pytest.mark.parametrize("name,nargs", [("xh_chill_hourly", 18), ("xh_chill_daily", 21)])
 def test_entry_point_header_ctypes_and_exports(name, nargs):
     lib = _capi.load_library()
     assert hasattr(lib, name)
-    decl = _header_decl(name)
+    decl = S.header_declarations()[name]
     sig = _capi.SIGNATURES[name]
     assert len(decl) == nargs == len(sig)
-    for d, s in zip(decl, sig):   # pointers, 64-bit sizes, ints and doubles line up one to one
-        kind = (ctypes.c_void_p if "*" in d else ctypes.c_int64 if d.startswith("int64_t") else ctypes.c_double if d.startswith("double")
-                else ctypes.c_int)
-        assert s is kind, (name, d, s)
+    for (d, _), s in zip(decl, sig):   # pointers, 64-bit sizes, ints and doubles line up one to one
+        assert S.is_ctypes_kind(d, s) and (s is ctypes.c_void_p or "*" not in d), (name, d, s)
 
 
 def test_entry_points_reject_bad_arguments():

@@ -4,7 +4,6 @@ point, and the argument errors of xclim_amd.ffdi (raised before any device is to
 
 import ctypes
 import os
-import re
 import sys
 
 import numpy as np
@@ -16,6 +15,7 @@ sys.path.insert(0, HERE)
 sys.path.insert(0, ROOT)
 
 import ffdicpu  # noqa: E402
+import stridedabi as S  # noqa: E402
 
 from xclim_amd import _capi  # noqa: E402
 from xclim_amd import ffdi  # noqa: E402
@@ -130,17 +130,10 @@ def test_ffdi_identity():
     np.testing.assert_allclose(ffdicpu.ffdi(D, T, H, V), exp, rtol=1e-6)
 
 
-def _header_decl(name):
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "xclim_hip.h")).read(), flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*)\);", txt)
-    assert m, name
-    return [a.strip() for a in m.group(1).split(",")]
-
-
 def test_entry_point_header_ctypes_and_exports():
     lib = _capi.load_library()
     assert hasattr(lib, "xh_mcarthur")
-    assert len(_header_decl("xh_mcarthur")) == 21 == len(_capi.SIGNATURES["xh_mcarthur"])
+    assert len(S.header_declarations()["xh_mcarthur"]) == 21 == len(_capi.SIGNATURES["xh_mcarthur"])
 
 
 def test_entry_point_rejects_bad_arguments():

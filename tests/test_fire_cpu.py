@@ -5,7 +5,6 @@ new entry points and the argument errors of xclim_amd.fire (raised before any de
 import ctypes
 import json
 import os
-import re
 import sys
 
 import numpy as np
@@ -17,6 +16,7 @@ sys.path.insert(0, HERE)
 sys.path.insert(0, ROOT)
 
 import firecpu  # noqa: E402
+import stridedabi as S  # noqa: E402
 
 from xclim_amd import _capi  # noqa: E402
 from xclim_amd import fire  # noqa: E402
@@ -98,18 +98,11 @@ def test_helper_known_answers():
         firecpu.day_length(91, 1)
 
 
-def _header_decl(name):
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "xclim_hip.h")).read(), flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*)\);", txt)
-    assert m, name
-    return [a.strip() for a in m.group(1).split(",")]
-
-
 @pytest.mark.parametrize("name,nargs", [("xh_fire_weather", 28), ("xh_overwintering_dc", 8)])
 def test_entry_points_header_ctypes_and_exports(name, nargs):
     lib = _capi.load_library()
     assert hasattr(lib, name)
-    assert len(_header_decl(name)) == nargs == len(_capi.SIGNATURES[name])
+    assert len(S.header_declarations()[name]) == nargs == len(_capi.SIGNATURES[name])
     assert lib.xh_abi_version() == 1
 
 

@@ -1,6 +1,6 @@
 """The data-quality flags without a GPU: the numpy restatement tests/flagscpu.py reproduces the known answers of the reference's
 own tests (tests/golden/flags_known_answers.json, with the defaults of tests/golden/flags_defaults.json); the names of the flags;
-what the mirror does not serve; header, ctypes table and library agree.  ``check_known_answers`` and ``refusals`` are shared with
+what the mirror does not serve; the mirrors of the header's #defines (tests/test_abi_cpu.py checks header, ctypes table and library).  ``check_known_answers`` and ``refusals`` are shared with
 tests/test_gpu_flags.py (the device) and, through it, tests/test_hostsim_flags_cpu.py (the host simulation).
 
 Every flag is a boolean: every comparison is exact."""
@@ -14,6 +14,7 @@ import pytest
 
 import flagscpu as R
 import stridedabi as S
+from stridedabi import FLAGS_TABLE
 from xclim_amd import _capi, dataflags
 from xclim_amd.timeaxis import TimeAxis
 
@@ -221,42 +222,18 @@ def test_no_launch_for_nothing_to_do():
     assert got["percentage_values_outside_of_bounds"].shape == (5, 0)
 
 
-# ---- the C ABI ---------------------------------------------------------------------------------------------------------------
-_F = "'f8' if f64 else 'f4'"
-# every strided operand of the new header, by parameter name (stridedabi.padded runs on it; the reduced form of `out` is K * P
-# bytes without a pitch and is not replayed on padded views) ...
-FLAGS_TABLE = {
-    "xh_data_flags": [S.R("x", "ld", "T", dtype=_F), S.R("y0", "ld_y0", "T", dtype=_F), S.R("y1", "ld_y1", "T", dtype=_F),
-                      S.R("lo", "ld_tab", "D", dtype=_F), S.R("hi", "ld_tab", "D", dtype=_F), S.W("out", "ld_out", "K * P", dtype="u1")],
-    "xh_doy_bounds": [S.R("x", "ld", "T", dtype=_F), S.W("lo", "ld_out", "ndoy", dtype=_F), S.W("hi", "ld_out", "ndoy", dtype=_F)],
-}
-# ... and every other pointer: the host tables
-FLAGS_TABLES = {"xh_data_flags": ("checks", "seg", "tidx"), "xh_doy_bounds": ("tbase",)}
-
-
-def declarations(path=HEADER):
-    """{entry point: [declaration of every parameter]} of the header."""
-    txt = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return {name: [a.strip() for a in params.split(",")] for name, params in re.findall(r"\bint\s+(xh_\w+)\s*\(([^;]*)\);", txt)}
-
-
-def test_header_ctypes_and_exports_agree():
-    lib = _capi.load_library()
-    decls = declarations()
-    assert set(decls) == set(_capi.FLAGS_SIGNATURES) == set(S.prototypes(HEADER)) == set(FLAGS_TABLE) and len(decls) == 2
-    for name, decl in decls.items():
-        sig = _capi.FLAGS_SIGNATURES[name]
-        assert len(decl) == len(sig), name
-        for d, s in zip(decl, sig):
-            kind = (ctypes.c_void_p if "*" in d else ctypes.c_int64 if d.startswith("int64_t") else ctypes.c_double if d.startswith("double")
-                    else ctypes.c_int)
-            assert s is kind, (name, d, s)
-        fn = getattr(lib, name)                    # exported, and declared by load_library()
-        assert list(fn.argtypes) == sig and fn.restype is ctypes.c_int
+# ---- the C ABI (tests/test_abi_cpu.py checks the header against the ctypes table, the library and the registry) ---------
+def test_the_unit_is_built_and_its_operand_table_is_the_header_s():
+    assert set(S.prototypes(HEADER)) == set(FLAGS_TABLE)
     make = open(os.path.join(ROOT, "xclim_amd", "csrc", "Makefile")).read()
     assert "dataflags.hip" in make and "xclim_hip_flags.h" in make
     txt = open(HEADER).read()
     assert '#include "xclim_hip.h"' in txt and "ASSUMPTION" in txt
+    assert len(re.findall(r"/\* host \*/", txt)) == 4                     # the host tables are marked
+
+
+def test_the_check_kinds_and_the_check_record_mirror_the_header():
+    txt = open(HEADER).read()
     kinds = (_capi.FLAG_CMP, _capi.FLAG_OUTSIDE, _capi.FLAG_PAIR, _capi.FLAG_REPEAT, _capi.FLAG_CLIM)
     assert kinds == (0, 1, 2, 3, 4)
     for code, name in zip(kinds, ("CMP", "OUTSIDE", "PAIR", "REPEAT", "CLIM")):
@@ -269,42 +246,11 @@ def test_header_ctypes_and_exports_agree():
                                                                  ("double", "a, b")]
 
 
-def test_the_new_table_shares_no_name_with_the_other_four():
-    others = set(_capi.SIGNATURES) | set(_capi.UNIT_SIGNATURES) | set(_capi.HYDRO_SIGNATURES) | set(_capi.RAIN_SIGNATURES)
-    assert not set(_capi.FLAGS_SIGNATURES) & others
-    assert _capi._SIGNATURE_TABLES[-1] is _capi.FLAGS_SIGNATURES and len(_capi._SIGNATURE_TABLES) == 5
-    assert (len(_capi.SIGNATURES), len(_capi.UNIT_SIGNATURES), len(_capi.HYDRO_SIGNATURES), len(_capi.RAIN_SIGNATURES)) == (125, 5, 4, 2)
-    assert _capi.argtypes_of("xh_data_flags") is _capi.FLAGS_SIGNATURES["xh_data_flags"]
-
-
-def test_every_pointer_and_pitch_of_the_new_header_is_in_the_tables():
-    protos = S.prototypes(HEADER)
-    for name, decl in declarations().items():
-        names = protos[name]
-        assert len(names) == len(decl)
-        ops = FLAGS_TABLE[name]
-        listed = {op.ptr for op in ops} | set(FLAGS_TABLES[name])
-        pointers = {n for n, d in zip(names, decl) if "*" in d and n != "ctx"}
-        assert pointers == listed, (name, pointers ^ listed)
-        assert {n for n in names if n.startswith("ld")} == {op.stride for op in ops}, name
-        for op in ops:                             # inputs are const, outputs are not
-            assert ("const" in decl[names.index(op.ptr)]) == (op.mode == "r"), (name, op.ptr)
-        for t in FLAGS_TABLES[name]:               # the host tables are const and marked
-            assert "const" in decl[names.index(t)]
-    assert len(re.findall(r"/\* host \*/", open(HEADER).read())) == 4
-
-
 def test_entry_points_reject_a_null_context():
     lib = _capi.load_library()
     null, some = _vp(0), _vp(64)   # never dereferenced: the check fails first
     assert lib.xh_data_flags(null, 10, 4, 4, 0, some, null, 4, null, 4, 1, some, 1, some, null, 0, null, null, 4, 0, some, 4) == _capi.XH_ERR_ARG
     assert lib.xh_doy_bounds(null, 10, 4, 4, 0, some, some, 1, 10, 5, 5.0, some, some, 4) == _capi.XH_ERR_ARG
-
-
-def entry(dev, name):
-    fn = getattr(dev.lib, name)
-    fn.argtypes, fn.restype = _capi.FLAGS_SIGNATURES[name], ctypes.c_int
-    return fn
 
 
 def checks_of(*rows):
@@ -328,7 +274,7 @@ def refusals(dev):
     tidx = (np.arange(T) % D).astype(np.int32)
     CMP, OUT, PAIR, REP, CLIM = range(5)
     good = checks_of((CMP, 0, 0, 0, 5.0, 0.0))
-    df, db = (entry(dev, n) for n in FLAGS_TABLE)
+    df, db = (getattr(dev.lib, n) for n in FLAGS_TABLE)
 
     def flags(ld=C, ld_out=C, seg=seg, P=P, xx=x, y0=None, y1=None, ld_y0=C, ld_y1=C, chk=good, K=None, tidx=tidx, D=D, lo=tab, hi=tab, ld_tab=C,
               red=0, o=out, T=T, C=C, ctx=dev.ctx):

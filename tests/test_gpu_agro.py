@@ -2,7 +2,7 @@
 and, at the cell counts and lengths no golden value exists for, against the numpy restatement tests/agrocpu.py; the host mirrors
 bit for bit against the kernel calls; empty periods; on padded, poisoned row views (tests/stridedabi.py); cross-checks against
 the project's own kernels; the refusals.  Every test runs on poisoned output buffers, and after every call of an entry point no
-output element may still hold the poison (tests/unwritten.py: watch, on the operand table of tests/test_agro_cpu.py).
+output element may still hold the poison (tests/unwritten.py: watch, on the operand table of tests/stridedabi.py).
 
 Tolerance (tests/test_agro_cpu.py: check): |got - want| <= 1e-12 * scale; counts, the EGDD bound days and the NaN patterns
 exactly.  The mirrors take the Gladstones and Jones coefficients from xh_solar_table, which carries its own 1e-12 against
@@ -15,32 +15,18 @@ import pytest
 
 import agrocpu as A
 import stridedabi as S
-import unwritten as U
-from test_agro_cpu import (AGRO_TABLE, BEDD_ANSWERS, HEADER, K2C, RTOL, RUNS, bedd_inputs, check, check_bedd, check_known_answers,
+from stridedabi import AGRO_TABLE
+from test_agro_cpu import (BEDD_ANSWERS, K2C, RTOL, RUNS, bedd_inputs, check, check_bedd, check_known_answers,
                            check_run, golden_case, refusals, spec_of)
 from xclim_amd import agro
 from xclim_amd import kernels as K
 from xclim_amd.calendar import select_time_mask
 from xclim_amd.timeaxis import TimeAxis
+from unwritten import watched  # noqa: F401  (autouse: after every call of an entry point no output element may still hold the poison)
 from poisoned import poisoned_outputs  # noqa: F401  (autouse: the tests of this module that use the device run on poisoned output buffers)
 
 pytestmark = pytest.mark.gpu
 DAY = 86400.0
-
-
-@pytest.fixture(autouse=True)
-def watched(request, monkeypatch):
-    """The operand table of the new header joins stridedabi's for the duration of a test, and every call of an entry point through
-    ``dev.call`` is followed by the check that it wrote every element of its outputs."""
-    protos = S.prototypes(HEADER)
-    for name, ops in AGRO_TABLE.items():
-        monkeypatch.setitem(S.TABLE, name, ops)
-        monkeypatch.setitem(S.PROTOS, name, protos[name])
-    if "dev" not in request.fixturenames:
-        yield None
-        return
-    with U.watch(request.getfixturevalue("dev"), monkeypatch) as log:
-        yield log
 
 
 def _host(outs):
@@ -236,7 +222,7 @@ def test_padded_views_give_the_same_bits(dev, monkeypatch, C, pitch, dtype):
     in front of their first row, 0xA5 bytes in those of the outputs (tests/stridedabi.py: padded, which asserts that they stay)."""
     for name, ops in AGRO_TABLE.items():
         for op in ops:
-            assert {op.ptr, op.stride} <= set(S.PROTOS[name]), (name, op)
+            assert {op.ptr, op.stride} <= set(S.parameters(name)), (name, op)
     t, lat, f, _ = _synth(C, 366, dtype)
     seg = t.segments("MS")[0]
     sel = select_time_mask(t, date_bounds=("04-01", "11-01"), include_bounds=(True, False))

@@ -16,6 +16,7 @@ import pytest
 
 import anuclimcpu as A
 import stridedabi as S
+from stridedabi import BIOCLIM_TABLE
 from test_anuclim_cpu import CV_BOUND, KNOWN, SEEDED, check, golden_case
 from xclim_amd import anuclim, indices
 from xclim_amd import kernels as K
@@ -198,19 +199,12 @@ def test_missing_mask(dev):
 
 
 # ---- padded, poisoned row views --------------------------------------------------------------------------------------
-_F = "'f8' if f64 else 'f4'"
-BIOCLIM_TABLE = {"xh_bioclim": [S.R(n, "ld", "T", dtype=_F) for n in ("tas", "tasmin", "tasmax", "pr")]
-                 + [S.W("outputs", "ld_out", "P", dtype="f8", ptrs="19"), S.W("which_out", "ld_out", "P", dtype="i4", ptrs="4"),
-                    S.W("count_out", "ld_out", "P", dtype="i4", ptrs="4")]}
-
-
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 @pytest.mark.parametrize("C,pitch", [(67, 80), (260, 272)])
 def test_padded_views_give_the_same_bits(dev, monkeypatch, C, pitch, dtype):
     """Every input and output in rows of `pitch` elements, NaN / 1e30 in the extra columns of the inputs and in front of their
     first row, 0xA5 bytes in those of the outputs (tests/stridedabi.py: padded, which asserts that they stay): the same bits."""
     for name, ops in BIOCLIM_TABLE.items():
-        monkeypatch.setitem(S.TABLE, name, ops)
         for op in ops:
             assert {op.ptr, op.stride} <= set(S.PROTOS[name]), (name, op)
     t, f, _ = _midyear(C, dtype)

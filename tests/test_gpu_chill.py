@@ -19,6 +19,7 @@ import pytest
 import chillcpu
 import fakexr
 import stridedabi as S
+from stridedabi import CHILL_TABLE
 from test_chill_cpu import DAILY, HOURLY, K2C, RTOL, check_delta, check_sums, golden_case, nan_empty
 from xclim_amd import chill, converters, patch
 from xclim_amd import kernels as K
@@ -230,17 +231,7 @@ def test_daily_shapes_against_restatement(dev, C, D, dtype):
 
 
 # ---- padded, poisoned row views --------------------------------------------------------------------------------------
-# The operands of the two entry points in the form of stridedabi.TABLE.  That table lists what tests/test_gpu_strided_abi.py
-# reaches with its own cases; these two entries live here, next to the cases that reach them, and join the table for the
-# duration of a test.
-_F = "'f8' if f64 else 'f4'"
-CHILL_TABLE = {
-    "xh_chill_hourly": [S.R("tas", "ld", "H", dtype=_F), S.W("cp_out", "ld_out", "P", dtype="f8"), S.W("cu_out", "ld_out", "P", dtype="f8"),
-                        S.W("valid_out", "ld_out", "P", dtype="i4"), S.W("delta_out", "ld_out", "H", dtype="f8")],
-    "xh_chill_daily": [S.R("tasmin", "ld", "D", dtype=_F), S.R("tasmax", "ld", "D", dtype=_F), S.W("cp_out", "ld_out", "P", dtype="f8"),
-                       S.W("cu_out", "ld_out", "P", dtype="f8"), S.W("valid_out", "ld_out", "P", dtype="i4"),
-                       S.W("hourly_out", "ld_out", "24 * D", dtype="f8")],
-}
+# (the operands of the two entry points: stridedabi.CHILL_TABLE)
 
 
 def _same_bits(a, b):
@@ -255,7 +246,6 @@ def test_padded_views_give_the_same_bits(dev, monkeypatch, C, pads, dtype):
     """Both entry points with every strided operand in rows longer than the field is wide, NaN / 1e30 in the extra columns of
     the inputs and 0xA5 bytes in those of the outputs (tests/stridedabi.py: padded): the same bits, untouched padding."""
     for name, ops in CHILL_TABLE.items():
-        monkeypatch.setitem(S.TABLE, name, ops)
         for op in ops:   # the table names parameters of the prototypes
             assert {op.ptr, op.stride} <= set(S.PROTOS[name]), (name, op)
     rng = np.random.default_rng(C)

@@ -12,7 +12,8 @@ import pytest
 
 import flagscpu as R
 import stridedabi as S
-from test_flags_cpu import DEFAULTS, FLAGS_TABLE, HEADER, check_known_answers, mirror_api, refusals
+from stridedabi import FLAGS_TABLE
+from test_flags_cpu import DEFAULTS, check_known_answers, mirror_api, refusals
 from xclim_amd import _capi, dataflags
 from xclim_amd import kernels as K
 from xclim_amd.timeaxis import TimeAxis
@@ -27,15 +28,6 @@ YEARS = np.asarray(TIME.segments("YS")[0], np.int64)          # [0, 365, 731, 10
 ROWS = np.arange(T + 1, dtype=np.int64)                        # P = T: the element-wise masks
 OPS = (">", "<", ">=", "<=", "==", "!=")
 A = 285.5                                                      # an operand that is a float32 value: a sample can sit exactly on it
-
-
-@pytest.fixture(autouse=True)
-def tables(monkeypatch):
-    """The operand table of the new header joins stridedabi's for the duration of a test."""
-    protos = S.prototypes(HEADER)
-    for name, ops in FLAGS_TABLE.items():
-        monkeypatch.setitem(S.TABLE, name, ops)
-        monkeypatch.setitem(S.PROTOS, name, protos[name])
 
 
 def launch(dev, x, specs, seg, reduce_cells=False, tables=None, tidx=None):

@@ -13,7 +13,8 @@ import pytest
 
 import fakexr
 import flagscpu as R
-from test_flags_cpu import DEFAULTS, FLAGS_TABLE
+from stridedabi import FLAGS_TABLE
+from test_flags_cpu import DEFAULTS
 from xclim_amd import dataflags, patch
 from xclim_amd.timeaxis import TimeAxis
 from poisoned import poisoned_outputs  # noqa: F401  (autouse: the tests of this module that use the device run on poisoned output buffers)

@@ -4,7 +4,7 @@ the kernel calls; every output subset of xh_flow_period_stats against the launch
 lengths that change its sort (one pair, odd and even numbers of slopes, the largest length) and on series with ties, absent and
 NaN years; on padded, poisoned row views (tests/stridedabi.py); the refusals.  Every test runs on poisoned output buffers, and
 after every call of an entry point no output element may still hold the poison (tests/unwritten.py: watch, on the operand table
-of tests/test_hydro_cpu.py).
+of tests/stridedabi.py).
 
 Tolerance (tests/test_hydro_cpu.py: check, check_run): |got - want| <= 1e-12 * scale, the scale being the sum of the absolute terms
 of the value; counts, n and the NaN patterns exactly; the Sen slope bit for bit; p within 1e-12 absolute."""
@@ -14,31 +14,17 @@ import pytest
 
 import hydrocpu as H
 import stridedabi as S
-import unwritten as U
-from test_hydro_cpu import (HEADER, HYDRO_TABLE, RUNS, bits, check, check_known_answers, check_run, golden_case, mirror_api, refusals,
+from stridedabi import HYDRO_TABLE
+from test_hydro_cpu import (RUNS, bits, check, check_known_answers, check_run, golden_case, mirror_api, refusals,
                             spec_of)
 from xclim_amd import hydrology
 from xclim_amd import kernels as K
 from xclim_amd.timeaxis import TimeAxis
+from unwritten import watched  # noqa: F401  (autouse: after every call of an entry point no output element may still hold the poison)
 from poisoned import poisoned_outputs  # noqa: F401  (autouse: the tests of this module that use the device run on poisoned output buffers)
 
 pytestmark = pytest.mark.gpu
 FLUX = "kg m-2 s-1"
-
-
-@pytest.fixture(autouse=True)
-def watched(request, monkeypatch):
-    """The operand table of the new header joins stridedabi's for the duration of a test, and every call of an entry point through
-    ``dev.call`` is followed by the check that it wrote every element of its outputs."""
-    protos = S.prototypes(HEADER)
-    for name, ops in HYDRO_TABLE.items():
-        monkeypatch.setitem(S.TABLE, name, ops)
-        monkeypatch.setitem(S.PROTOS, name, protos[name])
-    if "dev" not in request.fixturenames:
-        yield None
-        return
-    with U.watch(request.getfixturevalue("dev"), monkeypatch) as log:
-        yield log
 
 
 def _host(outs):
@@ -286,7 +272,7 @@ def test_padded_views_give_the_same_bits(dev, monkeypatch, C, pitch, dtype):
     in front of their first row, 0xA5 bytes in those of the outputs (tests/stridedabi.py: padded, which asserts that they stay)."""
     for name, ops in HYDRO_TABLE.items():
         for op in ops:
-            assert {op.ptr, op.stride} <= set(S.PROTOS[name]), (name, op)
+            assert {op.ptr, op.stride} <= set(S.parameters(name)), (name, op)
     t, f, _ = _synth(C, 800, dtype, "standard" if dtype == np.float64 else "noleap")
     seg = t.segments("QS-DEC")[0]
     po = H.season_year_table(t, "QS-DEC")[0]

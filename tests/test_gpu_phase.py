@@ -17,11 +17,12 @@ import pytest
 
 import phasecpu as R
 import stridedabi as S
-import unwritten as U
-from test_phase_cpu import CASES, HEADER, META, OUTPUTS, PHASE_TABLE, check_known_answers, golden_case, margin, mirror_api, refusals
+from stridedabi import PHASE_TABLE
+from test_phase_cpu import CASES, META, OUTPUTS, check_known_answers, golden_case, margin, mirror_api, refusals
 from xclim_amd import kernels as K
 from xclim_amd import phase
 from xclim_amd.timeaxis import TimeAxis
+from unwritten import watched  # noqa: F401  (autouse: after every call of an entry point no output element may still hold the poison)
 from poisoned import poisoned_outputs  # noqa: F401  (autouse: the tests of this module that use the device run on poisoned output buffers)
 
 pytestmark = pytest.mark.gpu
@@ -29,21 +30,6 @@ CELLS = (1, 63, 64, 65, 257)       # one lane, a wave less one, a wave, a wave a
 FREQS = ("YS", "YS-JUL", "MS")
 SUMS = ("pr_sum", "solid_sum", "liquid_sum", "snow_sum_over")
 RTOL = 1e-12
-
-
-@pytest.fixture(autouse=True)
-def watched(request, monkeypatch):
-    """The operand table of the new header joins stridedabi's for the duration of a test, and every call of an entry point through
-    ``dev.call`` is followed by the check that it wrote every element of its outputs."""
-    protos = S.prototypes(HEADER)
-    for name, ops in PHASE_TABLE.items():
-        monkeypatch.setitem(S.TABLE, name, ops)
-        monkeypatch.setitem(S.PROTOS, name, protos[name])
-    if "dev" not in request.fixturenames:
-        yield None
-        return
-    with U.watch(request.getfixturevalue("dev"), monkeypatch) as log:
-        yield log
 
 
 def setup(dev, name, cells=None, freq=None):
@@ -278,7 +264,7 @@ def test_padded_views_give_the_same_bits(dev, monkeypatch, name, C, pitch):
     in front of their first row, 0xA5 bytes in those of the outputs (tests/stridedabi.py: padded, which asserts that they stay)."""
     for entry, ops in PHASE_TABLE.items():
         for op in ops:
-            assert {op.ptr, op.stride} <= set(S.PROTOS[entry]), (entry, op)
+            assert {op.ptr, op.stride} <= set(S.parameters(entry)), (entry, op)
     m, pr, tas, time, freq, part, kw, _ = setup(dev, name, C)
 
     def run():

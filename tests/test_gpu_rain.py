@@ -3,7 +3,7 @@ tests/golden/rain_vectors.npz, the values of the numpy restatement tests/raincpu
 at 1, 2 and 32, all four method combinations, float32 and float64 fields, one period and three (a leap year, a short last one, a
 July year), 1 to 257 cells, every subset of the outputs, padded and poisoned row views; the host mirrors bit for bit against the
 kernel calls; the refusals.  Every test runs on poisoned output buffers, and after every call of an entry point no output element
-may still hold the poison (tests/unwritten.py: watch, on the operand table of tests/test_rain_cpu.py).
+may still hold the poison (tests/unwritten.py: watch, on the operand table of tests/stridedabi.py).
 
 Every result is an integer or NaN and every comparison is ``assert_array_equal``: the built amounts lie on a 0.25 mm grid (every
 window sum is exact in any order and precision), and the random float32 fields keep 1e-6 relative between every sum and its
@@ -14,31 +14,17 @@ import pytest
 
 import raincpu as R
 import stridedabi as S
-import unwritten as U
-from test_rain_cpu import (CASES, HEADER, META, OUTPUTS, RAIN_TABLE, ZONE_CASES, _Z, check_known_answers, golden_case, golden_time, mirror_api,
+from stridedabi import RAIN_TABLE
+from test_rain_cpu import (CASES, META, OUTPUTS, ZONE_CASES, _Z, check_known_answers, golden_case, golden_time, mirror_api,
                            refusals, same)
 from xclim_amd import kernels as K
 from xclim_amd import rainseason
 from xclim_amd.timeaxis import TimeAxis
+from unwritten import watched  # noqa: F401  (autouse: after every call of an entry point no output element may still hold the poison)
 from poisoned import poisoned_outputs  # noqa: F401  (autouse: the tests of this module that use the device run on poisoned output buffers)
 
 pytestmark = pytest.mark.gpu
 CELLS = (1, 63, 64, 65, 257)       # one lane, a wave less one, a wave, a wave and one, more than two workgroups of 128
-
-
-@pytest.fixture(autouse=True)
-def watched(request, monkeypatch):
-    """The operand table of the new header joins stridedabi's for the duration of a test, and every call of an entry point through
-    ``dev.call`` is followed by the check that it wrote every element of its outputs."""
-    protos = S.prototypes(HEADER)
-    for name, ops in RAIN_TABLE.items():
-        monkeypatch.setitem(S.TABLE, name, ops)
-        monkeypatch.setitem(S.PROTOS, name, protos[name])
-    if "dev" not in request.fixturenames:
-        yield None
-        return
-    with U.watch(request.getfixturevalue("dev"), monkeypatch) as log:
-        yield log
 
 
 def launch(dev, name, cells=None, outputs=OUTPUTS):
@@ -170,7 +156,7 @@ def test_padded_views_give_the_same_bits(dev, monkeypatch, name, C, pitch):
     in front of their first row, 0xA5 bytes in those of the outputs (tests/stridedabi.py: padded, which asserts that they stay)."""
     for entry, ops in RAIN_TABLE.items():
         for op in ops:
-            assert {op.ptr, op.stride} <= set(S.PROTOS[entry]), (entry, op)
+            assert {op.ptr, op.stride} <= set(S.parameters(entry)), (entry, op)
     e = R.zone_edges("usda", "degC")
     x = np.ascontiguousarray(_Z["zones.usda.degC/x"][:, np.arange(C) % 40]).astype(np.float32 if C == 130 else np.float64)
 

@@ -1,6 +1,6 @@
 """The hydrology unit without a GPU: the numpy restatement tests/hydrocpu.py against the reference's known answers
-(tests/golden/hydro_known_answers.json, recorded from its tests/test_hydrology.py) and against tests/golden/hydro_vectors.npz; the
-new header against its ctypes table and the library's exports; the host tables of the mirror; the refusals and the known answers
+(tests/golden/hydro_known_answers.json, recorded from its tests/test_hydrology.py) and against tests/golden/hydro_vectors.npz; what
+of the C ABI is the unit's own (tests/test_abi_cpu.py checks header, ctypes table and library); the host tables of the mirror; the refusals and the known answers
 on the host simulation of hydro.hip.
 
 Tolerance of the unit family: |got - want| <= 1e-12 * scale, the scale being the sum of the absolute terms of the value (hydrocpu
@@ -9,7 +9,6 @@ carries it); counts, n and NaN patterns exactly; the Sen slope bit for bit; p wi
 import ctypes
 import json
 import os
-import re
 import types
 
 import numpy as np
@@ -17,6 +16,7 @@ import pytest
 
 import hydrocpu as H
 import stridedabi as S
+from stridedabi import HYDRO_TABLE
 from xclim_amd import _capi, hydrology
 from xclim_amd.timeaxis import TimeAxis
 
@@ -320,65 +320,19 @@ def test_axes_and_arguments_that_are_not_served():
     assert "#define XH_HYDRO_MAX_WINDOW 32" in txt and "#define XH_SEN_MAX_YEARS 181" in txt
 
 
-# ---- the C ABI -------------------------------------------------------------------------------------------------------
-_F = "'f8' if f64 else 'f4'"
-# every strided operand of the new header, by parameter name (stridedabi.padded and the unwritten-output watch run on it) ...
-HYDRO_TABLE = {
-    "xh_flow_period_stats": [S.R("q", "ld", "T", dtype=_F)] + [S.W(n, "ld_out", "P", dtype="i4" if n == "valid_out" else "f8")
-                                                              for n in ("bfi_out", "rbi_out", "mean_out", "sum_out", "valid_out")],
-    "xh_melt_period_max": [S.R("snw", "ld", "T", dtype=_F), S.R("pr", "ld", "T", dtype=_F), S.W("out", "ld_out", "P", dtype="f8")],
-    "xh_antecedent_precip": [S.R("pr", "ld", "T", dtype=_F), S.W("out", "ld_out", "T", dtype="f8")],
-    "xh_sen_slope": [S.R("x", "ld", "P", dtype=_F)] + [S.W(n, "ld_out", "K", dtype="i4" if n == "n_out" else "f8")
-                                                      for n in ("slope_out", "p_out", "n_out")],
-}
-# ... and every other pointer: the host tables
-HYDRO_TABLES = {"xh_flow_period_stats": ("seg",), "xh_melt_period_max": ("seg",), "xh_antecedent_precip": ("weights",),
-                "xh_sen_slope": ("period_of",)}
-
-
-def declarations(path=HEADER):
-    """{entry point: [declaration of every parameter]} of the header."""
-    txt = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return {name: [a.strip() for a in params.split(",")] for name, params in re.findall(r"\bint\s+(xh_\w+)\s*\(([^;]*)\);", txt)}
-
-
-def test_header_ctypes_and_exports_agree():
-    lib = _capi.load_library()
-    decls = declarations()
-    assert set(decls) == set(_capi.HYDRO_SIGNATURES) == set(S.prototypes(HEADER)) == set(HYDRO_TABLE) and len(decls) == 4
-    for name, decl in decls.items():
-        sig = _capi.HYDRO_SIGNATURES[name]
-        assert len(decl) == len(sig), name
-        for d, s in zip(decl, sig):
-            kind = (ctypes.c_void_p if "*" in d else ctypes.c_int64 if d.startswith("int64_t") else ctypes.c_double if d.startswith("double")
-                    else ctypes.c_int)
-            assert s is kind, (name, d, s)
-        fn = getattr(lib, name)                    # exported, and declared by load_library()
-        assert list(fn.argtypes) == sig and fn.restype is ctypes.c_int
+# ---- the C ABI (tests/test_abi_cpu.py checks the header against the ctypes table, the library and the registry) ---------
+def test_the_unit_is_built_and_its_operand_table_is_the_header_s():
+    assert set(S.prototypes(HEADER)) == set(HYDRO_TABLE)
     make = open(os.path.join(ROOT, "xclim_amd", "csrc", "Makefile")).read()
     assert "hydro.hip" in make and "xclim_hip_hydro.h" in make
     assert '#include "xclim_hip.h"' in open(HEADER).read()
 
 
-def test_the_new_table_shares_no_name_with_the_other_two():
-    assert not set(_capi.HYDRO_SIGNATURES) & (set(_capi.SIGNATURES) | set(_capi.UNIT_SIGNATURES))
-    assert len(_capi.SIGNATURES) == 125 and len(_capi.UNIT_SIGNATURES) == 5
-
-
-def test_every_pointer_and_pitch_of_the_new_header_is_in_the_tables():
-    protos = S.prototypes(HEADER)
-    for name, decl in declarations().items():
-        names = protos[name]
-        assert len(names) == len(decl)
-        ops = HYDRO_TABLE[name]
-        listed = {op.ptr for op in ops} | set(HYDRO_TABLES[name])
-        pointers = {n for n, d in zip(names, decl) if "*" in d and n != "ctx"}
-        assert pointers == listed, (name, pointers ^ listed)
-        assert {n for n in names if n.startswith("ld")} == {op.stride for op in ops} == {"ld", "ld_out"}, name
-        for op in ops:                             # inputs are const, outputs are not; the dtype of the table is the declared one
-            d = decl[names.index(op.ptr)]
-            assert ("const" in d) == (op.mode == "r"), (name, d)
-            assert op.mode == "r" or ("int32_t" in d) == (op.dtype == "i4"), (name, d)
+def test_the_integer_outputs_are_the_header_s():
+    for name, decl in S.header_declarations(HEADER).items():
+        text = {n: t for t, n in decl}
+        for op in HYDRO_TABLE[name]:               # the dtype of the table is the declared one
+            assert op.mode == "r" or ("int32_t" in text[op.ptr]) == (op.dtype == "i4"), (name, op.ptr)
 
 
 def test_entry_points_reject_a_null_context():
@@ -388,12 +342,6 @@ def test_entry_points_reject_a_null_context():
     assert lib.xh_melt_period_max(null, 10, 4, 4, 0, some, some, 86400.0, 3, 1, some, some, 4) == _capi.XH_ERR_ARG
     assert lib.xh_antecedent_precip(null, 10, 4, 4, 0, some, 86400.0, 7, some, some, 4) == _capi.XH_ERR_ARG
     assert lib.xh_sen_slope(null, 10, 4, 4, 0, some, 5, 1, some, some, some, null, 4) == _capi.XH_ERR_ARG
-
-
-def entry(dev, name):
-    fn = getattr(dev.lib, name)
-    fn.argtypes, fn.restype = _capi.HYDRO_SIGNATURES[name], ctypes.c_int
-    return fn
 
 
 def refusals(dev):
@@ -410,7 +358,7 @@ def refusals(dev):
     d = lambda a: _vp(0) if a is None else _vp(a.ptr)             # noqa: E731
     seg = np.array([0, 20, T], np.int64)
     many = np.zeros(65538, np.int64)
-    fl, me, ap, se = (entry(dev, n) for n in HYDRO_TABLE)
+    fl, me, ap, se = (getattr(dev.lib, n) for n in HYDRO_TABLE)
 
     def flow(ld=C, ld_out=C, seg=seg, P=P, q=x, bfi=out, rbi=out, valid=cnt, T=T, C=C, ctx=dev.ctx):
         return fl(ctx, T, C, ld, 1, d(q), P, p(seg), d(bfi), d(rbi), _vp(0), _vp(0), d(valid), ld_out)

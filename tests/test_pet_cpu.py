@@ -5,7 +5,6 @@ any device is touched)."""
 
 import ctypes
 import os
-import re
 import sys
 
 import numpy as np
@@ -17,6 +16,7 @@ sys.path.insert(0, HERE)
 sys.path.insert(0, ROOT)
 
 import petcpu  # noqa: E402
+import stridedabi as S  # noqa: E402
 
 from xclim_amd import _capi  # noqa: E402
 from xclim_amd import converters as xc  # noqa: E402
@@ -75,18 +75,11 @@ def test_day_angle_known_answers():
     np.testing.assert_allclose(xc.day_angle(TimeAxis([1900], [3], [1], "julian")), [2 * np.pi * 60 / 366], rtol=1e-12)
 
 
-def _header_decl(name):
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "xclim_hip.h")).read(), flags=re.S)
-    m = re.search(r"\bint\s+" + name + r"\s*\(([^;]*)\);", txt)
-    assert m, name
-    return [a.strip() for a in m.group(1).split(",")]
-
-
 @pytest.mark.parametrize("name", sorted(ENTRY))
 def test_entry_point_header_ctypes_and_exports(name):
     lib = _capi.load_library()
     assert hasattr(lib, name)
-    assert len(_header_decl(name)) == ENTRY[name] == len(_capi.SIGNATURES[name])
+    assert len(S.header_declarations()[name]) == ENTRY[name] == len(_capi.SIGNATURES[name])
 
 
 def test_entry_points_reject_bad_arguments():

@@ -2,7 +2,7 @@
 reference's own tests (tests/golden/phase_known_answers.json: 13 of the two approximations, 20 of the period indices) to the
 tolerances those tests use, and the golden file tests/golden/phase_vectors.npz; the host logic of the mirror (season bytes, the
 fmin / fmax swap of the dai methods, the auer table, the float32 rounding of ``thresh``, the winter periods); what the mirror
-does not serve; header, ctypes table and library agree.  ``check_known_answers`` and ``refusals`` are shared with
+does not serve; the mirrors of the header's #defines (tests/test_abi_cpu.py checks header, ctypes table and library).  ``check_known_answers`` and ``refusals`` are shared with
 tests/test_gpu_phase.py (the device) and tests/test_hostsim_phase_cpu.py (the host simulation).
 
 None of the listed tests of the reference needs a data file, so none is left out; the three unit variants of the snowfall tests
@@ -17,6 +17,7 @@ import pytest
 
 import phasecpu as R
 import stridedabi as S
+from stridedabi import PHASE_TABLE
 from xclim_amd import _capi, phase
 from xclim_amd.timeaxis import TimeAxis
 
@@ -284,36 +285,13 @@ def test_fractional_fields_keep_their_distance_from_the_thresholds(name):
     assert margin(name) > 1e-9
 
 
-# ---- the C ABI -------------------------------------------------------------------------------------------------------------
-_F = "'f8' if f64 else 'f4'"
-_FO = "'f8' if (f64 or method != 0) else 'f4'"
-PHASE_TABLE = {
-    "xh_precip_phase_map": [S.R("pr", "ld", "T", dtype=_F), S.R("tas", "ld", "T", dtype=_F), S.W("snow_out", "ld_out", "T", dtype=_FO),
-                            S.W("rain_out", "ld_out", "T", dtype=_FO)],
-    "xh_precip_phase_period": [S.R("pr", "ld", "T", dtype=_F), S.R("tas", "ld", "T", dtype=_F),
-                               S.W("outs", "ld_out", "P", dtype="f8", ptrs=len(OUTPUTS))],
-}
-# every other pointer: the host tables, and the per-cell land bytes (dense, read)
-PHASE_TABLES = {"xh_precip_phase_map": ("par", "tab", "season", "land"), "xh_precip_phase_period": ("seg", "doy", "par", "tab", "season", "land", "lim")}
+# ---- the C ABI (tests/test_abi_cpu.py checks the header against the ctypes table, the library and the registry) ---------
+def test_the_operand_table_is_the_header_s():
+    assert set(S.prototypes(HEADER)) == set(PHASE_TABLE)
+    assert PHASE_TABLE["xh_precip_phase_period"][-1].ptrs == len(OUTPUTS)
 
 
-def declarations(path=HEADER):
-    txt = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return {name: [a.strip() for a in params.split(",")] for name, params in re.findall(r"\bint\s+(xh_\w+)\s*\(([^;]*)\);", txt)}
-
-
-def test_header_ctypes_and_exports_agree():
-    lib = _capi.load_library()
-    decls = declarations()
-    assert set(decls) == set(_capi.PHASE_SIGNATURES) == set(S.prototypes(HEADER)) == set(PHASE_TABLE) and len(decls) == 2
-    for name, decl in decls.items():
-        sig = _capi.PHASE_SIGNATURES[name]
-        assert len(decl) == len(sig), name
-        for d, s in zip(decl, sig):
-            kind = (ctypes.c_void_p if "*" in d else ctypes.c_int64 if d.startswith("int64_t") else ctypes.c_double if d.startswith("double")
-                    else ctypes.c_uint32 if d.startswith("uint32_t") else ctypes.c_int)
-            assert s is kind, (name, d)
-        assert getattr(lib, name).argtypes == sig
+def test_the_methods_outputs_and_sizes_mirror_the_header():
     txt = open(HEADER).read()
     for k, o in enumerate(OUTPUTS):
         assert re.search(rf"#define XH_PHASE_{o.upper()} {k}\b", txt), o
@@ -321,23 +299,6 @@ def test_header_ctypes_and_exports_agree():
         assert re.search(rf"#define XH_PHASE_{m.upper()} {k}\b", txt), m
     assert f"#define XH_PHASE_NOUT {len(OUTPUTS)}" in txt and f"#define XH_PHASE_NPAR {_capi.PHASE_NPAR}" in txt
     assert f"#define XH_PHASE_DAI_NTAB {_capi.PHASE_DAI_NTAB}" in txt and f"#define XH_PHASE_NLIM {_capi.PHASE_NLIM}" in txt
-    assert _capi._ALL_SIGNATURE_TABLES[-1] is _capi.PHASE_SIGNATURES and _capi.argtypes_of("xh_precip_phase_map") is _capi.PHASE_SIGNATURES["xh_precip_phase_map"]
-    others = [t for t in _capi._ALL_SIGNATURE_TABLES if t is not _capi.PHASE_SIGNATURES]
-    assert len(others) == 5 and not any(set(_capi.PHASE_SIGNATURES) & set(t) for t in others)
-
-
-def test_every_pointer_and_pitch_of_the_new_header_is_in_the_tables():
-    protos = S.prototypes(HEADER)
-    for name, decl in declarations().items():
-        names = protos[name]
-        ops = PHASE_TABLE[name]
-        listed = {op.ptr for op in ops} | set(PHASE_TABLES[name])
-        assert {n for n, d in zip(names, decl) if "*" in d and n != "ctx"} == listed, name
-        assert {n for n in names if n.startswith("ld")} == {op.stride for op in ops} == {"ld", "ld_out"}, name
-        for op in ops:
-            assert ("const" in decl[names.index(op.ptr)].split("*")[0]) == (op.mode == "r"), (name, op.ptr)
-        for t in PHASE_TABLES[name]:
-            assert "const" in decl[names.index(t)]
 
 
 def test_entry_points_reject_a_null_context():

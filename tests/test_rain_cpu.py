@@ -1,7 +1,7 @@
 """rain_season and hardiness_zones without a GPU: the numpy restatement tests/raincpu.py reproduces the known answers of the
 reference's own tests (tests/golden/rain_known_answers.json: eight for rain_season, six for hardiness_zones) and the golden file
 tests/golden/rain_vectors.npz; the flag byte of ``xclim_amd.rainseason.rain_flags`` against ``select_time_mask`` applied period by
-period; what the mirror does not serve; header, ctypes table and library agree.  ``refusals`` and ``check_known_answers`` are
+period; what the mirror does not serve; the mirrors of the header's #defines (tests/test_abi_cpu.py checks header, ctypes table and library).  ``refusals`` and ``check_known_answers`` are
 shared with tests/test_gpu_rain.py (the device) and tests/test_hostsim_units_cpu.py (the host simulation).
 
 Every result is an integer (a day of year, a number of days, a zone) or NaN: every comparison is exact."""
@@ -15,6 +15,7 @@ import pytest
 
 import raincpu as R
 import stridedabi as S
+from stridedabi import RAIN_TABLE
 from xclim_amd import _capi, rainseason
 from xclim_amd.calendar import select_time_mask
 from xclim_amd.timeaxis import TimeAxis
@@ -277,66 +278,19 @@ def test_axes_and_arguments_that_are_not_served():
     assert rainseason.ADAPTED == ("rain_season", "hardiness_zones")
 
 
-# ---- the C ABI -------------------------------------------------------------------------------------------------------
-_F = "'f8' if f64 else 'f4'"
-# every strided operand of the new header, by parameter name (stridedabi.padded and the unwritten-output watch run on it) ...
-RAIN_TABLE = {
-    "xh_rain_season": [S.R("pr", "ld", "T", dtype=_F)] + [S.W(n, "ld_out", "P", dtype="f8") for n in ("start_out", "end_out", "length_out")],
-    "xh_rolling_zones": [S.R("x", "ld", "P", dtype=_F), S.W("out", "ld_out", "P", dtype="f8")],
-}
-# ... and every other pointer: the host tables
-RAIN_TABLES = {"xh_rain_season": ("seg", "flags", "doy"), "xh_rolling_zones": ("edges",)}
-
-
-def declarations(path=HEADER):
-    """{entry point: [declaration of every parameter]} of the header."""
-    txt = re.sub(r"/\*.*?\*/", "", open(path).read(), flags=re.S)
-    return {name: [a.strip() for a in params.split(",")] for name, params in re.findall(r"\bint\s+(xh_\w+)\s*\(([^;]*)\);", txt)}
-
-
-def test_header_ctypes_and_exports_agree():
-    lib = _capi.load_library()
-    decls = declarations()
-    assert set(decls) == set(_capi.RAIN_SIGNATURES) == set(S.prototypes(HEADER)) == set(RAIN_TABLE) and len(decls) == 2
-    for name, decl in decls.items():
-        sig = _capi.RAIN_SIGNATURES[name]
-        assert len(decl) == len(sig), name
-        for d, s in zip(decl, sig):
-            kind = (ctypes.c_void_p if "*" in d else ctypes.c_int64 if d.startswith("int64_t") else ctypes.c_double if d.startswith("double")
-                    else ctypes.c_int)
-            assert s is kind, (name, d, s)
-        fn = getattr(lib, name)                    # exported, and declared by load_library()
-        assert list(fn.argtypes) == sig and fn.restype is ctypes.c_int
+# ---- the C ABI (tests/test_abi_cpu.py checks the header against the ctypes table, the library and the registry) ---------
+def test_the_unit_is_built_and_its_operand_table_is_the_header_s():
+    assert set(S.prototypes(HEADER)) == set(RAIN_TABLE)
     make = open(os.path.join(ROOT, "xclim_amd", "csrc", "Makefile")).read()
     assert "rainseason.hip" in make and "xclim_hip_rain.h" in make
     assert '#include "xclim_hip.h"' in open(HEADER).read()
+    assert len(re.findall(r"/\* host \*/", open(HEADER).read())) == 4      # the host tables are marked
+
+
+def test_the_flag_bits_mirror_the_header():
     assert (_capi.RAIN_START_WINDOW, _capi.RAIN_START_BOUNDS, _capi.RAIN_END_BOUNDS) == (1, 2, 4)
     for bit, name in ((1, "START_WINDOW"), (2, "START_BOUNDS"), (4, "END_BOUNDS")):
         assert re.search(rf"#define XH_RAIN_{name} {bit}\b", open(HEADER).read())
-
-
-def test_the_new_table_shares_no_name_with_the_other_three():
-    others = set(_capi.SIGNATURES) | set(_capi.UNIT_SIGNATURES) | set(_capi.HYDRO_SIGNATURES)
-    assert not set(_capi.RAIN_SIGNATURES) & others
-    assert len(_capi.SIGNATURES) == 125 and len(_capi.UNIT_SIGNATURES) == 5 and len(_capi.HYDRO_SIGNATURES) == 4
-
-
-def test_every_pointer_and_pitch_of_the_new_header_is_in_the_tables():
-    protos = S.prototypes(HEADER)
-    for name, decl in declarations().items():
-        names = protos[name]
-        assert len(names) == len(decl)
-        ops = RAIN_TABLE[name]
-        listed = {op.ptr for op in ops} | set(RAIN_TABLES[name])
-        pointers = {n for n, d in zip(names, decl) if "*" in d and n != "ctx"}
-        assert pointers == listed, (name, pointers ^ listed)
-        assert {n for n in names if n.startswith("ld")} == {op.stride for op in ops} == {"ld", "ld_out"}, name
-        for op in ops:                             # inputs are const, outputs are not
-            d = decl[names.index(op.ptr)]
-            assert ("const" in d) == (op.mode == "r"), (name, d)
-        for t in RAIN_TABLES[name]:                # the host tables are const and marked
-            assert "const" in decl[names.index(t)]
-    assert len(re.findall(r"/\* host \*/", open(HEADER).read())) == 4
 
 
 def test_entry_points_reject_a_null_context():
@@ -345,12 +299,6 @@ def test_entry_points_reject_a_null_context():
     assert lib.xh_rain_season(null, 10, 4, 4, 0, some, 1.0, 1, some, some, some, 25.0, 3, 30, 1.0, 7, 0, 0.0, 20, 0, some, some, some,
                               4) == _capi.XH_ERR_ARG
     assert lib.xh_rolling_zones(null, 10, 4, 4, 0, some, 3, 8, some, some, 4) == _capi.XH_ERR_ARG
-
-
-def entry(dev, name):
-    fn = getattr(dev.lib, name)
-    fn.argtypes, fn.restype = _capi.RAIN_SIGNATURES[name], ctypes.c_int
-    return fn
 
 
 def refusals(dev):
@@ -368,7 +316,7 @@ def refusals(dev):
     many = np.zeros(65538, np.int64)
     flags = np.full(T, 7, np.uint8)
     doy = np.arange(1, T + 1, dtype=np.int32)
-    rs, rz = (entry(dev, n) for n in RAIN_TABLE)
+    rs, rz = (getattr(dev.lib, n) for n in RAIN_TABLE)
 
     def rain(ld=C, ld_out=C, seg=seg, P=P, pr=x, flags=flags, doy=doy, ww=3, wnd=5, wd=4, ts=0, we=3, te=0, s=out, e=out, ln=out, T=T, C=C,
              ctx=dev.ctx):

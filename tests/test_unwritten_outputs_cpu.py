@@ -39,16 +39,8 @@ SIM_DENSE_SHAPES = [(1, 257), (7, 65), (366, 63), (800, 1), (1030, 3)]
 # ------------------------------------------------------------------------------------------------ the tables
 def output_parameters(path=S.HEADER):
     """{entry point: [names of its non-const pointer parameters]} of the header (the context aside): what a call can write."""
-    text = re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
-    found = {}
-    for name, params in re.findall(r"\b(?:int|const char\*)\s+(xh_\w+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
-        outs = []
-        for p in params.split(",")[1:]:
-            p = p.strip()
-            if "*" in p and "const" not in p.split("*")[0]:
-                outs.append(re.findall(r"\w+", p)[-1])
-        found[name] = outs
-    return found
+    return {name: [n for text, n in decl[1:] if "*" in text and "const" not in text.split("*")[0]]
+            for name, decl in S.header_declarations(path).items()}
 
 
 def test_plumbing_and_compute_entry_points_partition_the_header():

@@ -6,11 +6,11 @@ tests/poisoned.py in any element.  Before the call the same operands are looked 
 element is "armed" — it came from ``Device.empty`` under the fixture and nothing has written it yet — and the log says so, so
 that a sweep can tell a checked operand from one that merely happened to hold old values.
 
-The output operands of an entry point come from two tables, by the parameter names of include/xclim_hip.h:
-  * the strided ones from ``stridedabi.TABLE`` (mode "w"; "rw" operands keep what the caller held and are listed in EXEMPT);
-  * ``DENSE``, below: every output without a stride parameter of stridedabi's kind — the period reductions (P, C), the
-    quantile and percentile tables, factors, node tables, run statistics — and the outputs of the units whose row pitch is
-    called ``ld_out``.
+The output operands of an entry point come from two tables, by the parameter names of the headers under include/:
+  * the strided ones from ``stridedabi.operands`` (mode "w"; "rw" operands keep what the caller held and are listed in EXEMPT);
+  * ``DENSE``, below: every output of the main header without a stride parameter of stridedabi's kind — the period reductions
+    (P, C), the quantile and percentile tables, factors, node tables, run statistics — and the outputs of its units whose row pitch
+    is called ``ld_out`` (an operand listed here is taken from here, not from stridedabi.PITCHED).
 ``PLUMBING`` names the entry points that compute nothing.  tests/test_unwritten_outputs_cpu.py asserts that every other entry
 point of the header has its outputs in one of the tables or is listed in EXEMPT, and that EXEMPT names nothing but
 operands whose header comment says the caller's values are kept."""
@@ -19,6 +19,7 @@ import ctypes
 from collections import namedtuple
 
 import numpy as np
+import pytest
 
 import stridedabi as S
 from poisoned import unwritten
@@ -105,9 +106,12 @@ def compute_entry_points():
 
 
 def outputs_of(name):
-    """The output operands of an entry point as Out records: stridedabi's "w" operands, then DENSE's."""
-    outs = [Out(op.ptr, op.rows, op.width, op.dtype, (op.stride, op.minor), op.ptrs) for op in S.TABLE.get(name, ()) if op.mode == "w"]
-    return outs + list(DENSE.get(name, ()))
+    """The output operands of an entry point as Out records: stridedabi's "w" operands that DENSE does not list, then DENSE's."""
+    dense = list(DENSE.get(name, ()))
+    listed = {o.ptr for o in dense}
+    outs = [Out(op.ptr, op.rows, op.width, op.dtype, (op.stride, op.minor), op.ptrs) for op in S.operands(name)
+            if op.mode == "w" and op.ptr not in listed]
+    return outs + dense
 
 
 def _extents(name, env, dev):
@@ -148,7 +152,7 @@ def watch(dev, monkeypatch):
     real = dev.call
 
     def checked(name, *args):
-        if name in PLUMBING or name not in S.PROTOS:
+        if name in PLUMBING or not (name in S.PROTOS or name in S.UNIT_PROTOS):
             return real(name, *args)
         env = S.arguments(name, args)
         extents = _extents(name, env, dev)
@@ -167,4 +171,15 @@ def watch(dev, monkeypatch):
 
     with monkeypatch.context() as m:
         m.setattr(dev, "call", checked, raising=False)
+        yield log
+
+
+@pytest.fixture(autouse=True)
+def watched(request, monkeypatch):
+    """Imported by name into a GPU module: every call of an entry point through ``dev.call`` in a test that uses ``dev`` is followed by
+    the check that it wrote every element of its outputs.  Yields the log of ``watch`` (None for a test without the device)."""
+    if "dev" not in request.fixturenames:
+        yield None
+        return
+    with watch(request.getfixturevalue("dev"), monkeypatch) as log:
         yield log

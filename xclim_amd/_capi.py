@@ -107,8 +107,10 @@ class XclimHipError(RuntimeError):
 _i32, _i64, _u32, _u64 = C.c_int32, C.c_int64, C.c_uint32, C.c_uint64
 _vp, _dbl, _flt, _int, _sz = C.c_void_p, C.c_double, C.c_float, C.c_int, C.c_size_t
 
-# name -> argtypes (restype is always int unless listed in _RESTYPES); mirrors include/xclim_hip.h one to one
+# name -> argtypes (restype is always int unless listed in _RESTYPES); mirrors the six headers under include/ one to one, a group of
+# rows per header.  A new unit adds its header, its rows here, its operands in tests/stridedabi.py and the mirrors of its #defines.
 SIGNATURES: dict[str, list] = {
+    # include/xclim_hip.h (every .hip file of xclim_amd/csrc that no later group names)
     "xh_abi_version": [],
     "xh_last_error": [],
     "xh_device_count": [C.POINTER(_int)],
@@ -240,9 +242,7 @@ SIGNATURES: dict[str, list] = {
                        _i64],
     "xh_bioclim": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _int, _i64, _vp, _vp, _int, _dbl, _dbl, _dbl,
                    _vp, _vp, _vp, _i64],
-}
-# The entry points of include/xclim_hip_agro.h (xclim_amd/csrc/agro.hip): a table of its own next to the one of the main header.
-UNIT_SIGNATURES: dict[str, list] = {
+    # include/xclim_hip_agro.h (xclim_amd/csrc/agro.hip)
     "xh_agro_degree_sum": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _dbl, _dbl, _dbl,
                            _int, _dbl, _dbl, _dbl, _vp, _vp, _vp, _i64],
     "xh_agro_monthly": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _int, _dbl, _dbl, _dbl,
@@ -251,55 +251,39 @@ UNIT_SIGNATURES: dict[str, list] = {
                 _i64],
     "xh_corn_heat_units": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _dbl, _dbl, _dbl, _vp, _i64],
     "xh_qian_wma": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _i64],
-}
-# The entry points of include/xclim_hip_hydro.h (xclim_amd/csrc/hydro.hip): again a table of its own.
-HYDRO_SIGNATURES: dict[str, list] = {
+    # include/xclim_hip_hydro.h (xclim_amd/csrc/hydro.hip)
     "xh_flow_period_stats": [_vp, _i64, _i64, _i64, _int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64],
     "xh_melt_period_max": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _dbl, _int, _i64, _vp, _vp, _i64],
     "xh_antecedent_precip": [_vp, _i64, _i64, _i64, _int, _vp, _dbl, _int, _vp, _vp, _i64],
     "xh_sen_slope": [_vp, _i64, _i64, _i64, _int, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64],
-}
-HYDRO_MAX_WINDOW = 32   # XH_HYDRO_MAX_WINDOW
-SEN_MAX_YEARS = 181     # XH_SEN_MAX_YEARS
-# The entry points of include/xclim_hip_rain.h (xclim_amd/csrc/rainseason.hip): a table of its own as well.
-RAIN_SIGNATURES: dict[str, list] = {
+    # include/xclim_hip_rain.h (xclim_amd/csrc/rainseason.hip)
     "xh_rain_season": [_vp, _i64, _i64, _i64, _int, _vp, _dbl, _i64, _vp, _vp, _vp, _dbl, _int, _int, _dbl, _int, _int, _dbl, _int, _int,
                        _vp, _vp, _vp, _i64],
     "xh_rolling_zones": [_vp, _i64, _i64, _i64, _int, _vp, _int, _i64, _vp, _vp, _i64],
-}
-RAIN_MAX_WINDOW = 32    # XH_RAIN_MAX_WINDOW
-ZONES_MAX_EDGES = 32    # XH_ZONES_MAX_EDGES
-RAIN_START_WINDOW, RAIN_START_BOUNDS, RAIN_END_BOUNDS = 1, 2, 4   # the XH_RAIN_* flag bits
-# The entry points of include/xclim_hip_flags.h (xclim_amd/csrc/dataflags.hip): the fifth table.
-FLAGS_SIGNATURES: dict[str, list] = {
+    # include/xclim_hip_flags.h (xclim_amd/csrc/dataflags.hip)
     "xh_data_flags": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _i64, _vp, _i64, _int, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _int, _vp,
                       _i64],
     "xh_doy_bounds": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _int, _int, _int, _dbl, _vp, _vp, _i64],
+    # include/xclim_hip_phase.h (xclim_amd/csrc/phase.hip)
+    "xh_precip_phase_map": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64],
+    "xh_precip_phase_period": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _dbl, _i64, _vp, _vp, _int, _vp, _vp, _i64, _vp, _vp, _vp, _int,
+                               _u32, _vp, _i64],
 }
+_RESTYPES = {"xh_last_error": C.c_char_p}
+HYDRO_MAX_WINDOW = 32   # XH_HYDRO_MAX_WINDOW
+SEN_MAX_YEARS = 181     # XH_SEN_MAX_YEARS
+RAIN_MAX_WINDOW = 32    # XH_RAIN_MAX_WINDOW
+ZONES_MAX_EDGES = 32    # XH_ZONES_MAX_EDGES
+RAIN_START_WINDOW, RAIN_START_BOUNDS, RAIN_END_BOUNDS = 1, 2, 4   # the XH_RAIN_* flag bits
 FLAGS_MAX_CHECKS = 16   # XH_FLAGS_MAX_CHECKS
 FLAG_CMP, FLAG_OUTSIDE, FLAG_PAIR, FLAG_REPEAT, FLAG_CLIM = 0, 1, 2, 3, 4   # the XH_FLAG_* check kinds
 # struct xh_flag_check { int32_t kind, op, n, other; double a, b; }
 FLAG_CHECK_DTYPE = np.dtype([("kind", np.int32), ("op", np.int32), ("n", np.int32), ("other", np.int32), ("a", np.float64), ("b", np.float64)])
-# The entry points of include/xclim_hip_phase.h (xclim_amd/csrc/phase.hip): the sixth table.
-PHASE_SIGNATURES: dict[str, list] = {
-    "xh_precip_phase_map": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64],
-    "xh_precip_phase_period": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _dbl, _i64, _vp, _vp, _int, _vp, _vp, _i64, _vp, _vp, _vp, _int,
-                               C.c_uint32, _vp, _i64],
-}
 PHASE_METHODS = {"binary": 0, "brown": 1, "auer": 2, "dai_annual": 3, "dai_seasonal": 4, "given": 5}   # the XH_PHASE_* methods
 PHASE_NPAR, PHASE_DAI_NTAB, PHASE_NLIM = 6, 96, 7   # XH_PHASE_NPAR, XH_PHASE_DAI_NTAB, XH_PHASE_NLIM
 # the outputs of xh_precip_phase_period in the order of their XH_PHASE_* bits
 PHASE_OUTPUTS = ("pr_sum", "solid_sum", "liquid_sum", "pr_n", "solid_n", "liquid_n", "tas_n", "snow_days", "snow_sum_over", "snow_n_over",
                  "first_snow", "last_snow", "hplt_days", "rofg_days")
-_RESTYPES = {"xh_last_error": C.c_char_p}
-# (the tables of the first five headers keep their tuple; every table, the sixth included, is in _ALL_SIGNATURE_TABLES)
-_SIGNATURE_TABLES = (SIGNATURES, UNIT_SIGNATURES, HYDRO_SIGNATURES, RAIN_SIGNATURES, FLAGS_SIGNATURES)
-_ALL_SIGNATURE_TABLES = _SIGNATURE_TABLES + (PHASE_SIGNATURES,)
-
-
-def argtypes_of(name: str):
-    """The argtypes of an entry point, whichever header's table declares it; None for a name that no table holds."""
-    return next((table[name] for table in _ALL_SIGNATURE_TABLES if name in table), None)
 
 
 _lib = None
@@ -311,8 +295,7 @@ def library_path() -> str:
 
 
 def load_library() -> C.CDLL:
-    """Load libxclimhip.so and declare every prototype of include/xclim_hip.h, include/xclim_hip_agro.h,
-    include/xclim_hip_hydro.h, include/xclim_hip_rain.h, include/xclim_hip_flags.h and include/xclim_hip_phase.h.  Raises
+    """Load libxclimhip.so and declare every prototype of SIGNATURES (the six headers under include/).  Raises
     BackendUnavailable."""
     global _lib
     with _lib_lock:
@@ -327,9 +310,9 @@ def load_library() -> C.CDLL:
             lib = C.CDLL(_LIB_PATH)
         except OSError as err:  # pragma: no cover
             raise BackendUnavailable(f"cannot load {_LIB_PATH}: {err}") from err
-        for name in (name for table in _ALL_SIGNATURE_TABLES for name in table):
+        for name, argtypes in SIGNATURES.items():
             fn = getattr(lib, name)  # AttributeError if the header and the library diverge
-            fn.argtypes = argtypes_of(name)
+            fn.argtypes = argtypes
             fn.restype = _RESTYPES.get(name, _int)
         _lib = lib
         return lib

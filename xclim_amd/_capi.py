@@ -269,7 +269,23 @@ SIGNATURES: dict[str, list] = {
     "xh_precip_phase_period": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _dbl, _i64, _vp, _vp, _int, _vp, _vp, _i64, _vp, _vp, _vp, _int,
                                _u32, _vp, _i64],
 }
+# The prototypes of the headers under include/ext/ (units added while the ABI tests over include/*.h are frozen); checked by
+# tests/test_abi_ext_cpu.py.  load_library() declares them after SIGNATURES; the wrappers of these units convert every argument
+# to its ctypes type themselves (kernels._ext_call), so a call is right on a handle whose argtypes were never set.
+EXT_SIGNATURES: dict[str, list] = {
+    # include/ext/xclim_hip_analog.h (xclim_amd/csrc/analog.hip)
+    "xh_analog": [_vp, _int, _i64, _i64, _int, _vp, _i64, _i64, _int, _vp, _vp, _i64, _vp, _i64, _vp, _i64],
+}
 _RESTYPES = {"xh_last_error": C.c_char_p}
+# the XH_ANALOG_* methods, in the order of the reference's registry
+ANALOG_METHODS = {"seuclidean": 0, "nearest_neighbor": 1, "zech_aslan": 2, "szekely_rizzo": 3, "friedman_rafsky": 4,
+                  "kolmogorov_smirnov": 5, "kldiv": 6, "mahalanobis": 7}
+ANALOG_NMETHODS = 8      # XH_ANALOG_NMETHODS
+ANALOG_MAX_D = 10        # XH_ANALOG_MAX_D
+ANALOG_KS_MAX_D = 6      # XH_ANALOG_KS_MAX_D
+ANALOG_MAX_SAMPLE = 512  # XH_ANALOG_MAX_SAMPLE
+ANALOG_MAX_K = 32        # XH_ANALOG_MAX_K
+ANALOG_MAX_NK = 16       # XH_ANALOG_MAX_NK
 HYDRO_MAX_WINDOW = 32   # XH_HYDRO_MAX_WINDOW
 SEN_MAX_YEARS = 181     # XH_SEN_MAX_YEARS
 RAIN_MAX_WINDOW = 32    # XH_RAIN_MAX_WINDOW
@@ -295,7 +311,8 @@ def library_path() -> str:
 
 
 def load_library() -> C.CDLL:
-    """Load libxclimhip.so and declare every prototype of SIGNATURES (the six headers under include/).  Raises
+    """Load libxclimhip.so and declare every prototype of SIGNATURES (the six headers under include/) and of EXT_SIGNATURES
+    (include/ext/).  Raises
     BackendUnavailable."""
     global _lib
     with _lib_lock:
@@ -310,7 +327,7 @@ def load_library() -> C.CDLL:
             lib = C.CDLL(_LIB_PATH)
         except OSError as err:  # pragma: no cover
             raise BackendUnavailable(f"cannot load {_LIB_PATH}: {err}") from err
-        for name, argtypes in SIGNATURES.items():
+        for name, argtypes in (*SIGNATURES.items(), *EXT_SIGNATURES.items()):
             fn = getattr(lib, name)  # AttributeError if the header and the library diverge
             fn.argtypes = argtypes
             fn.restype = _RESTYPES.get(name, _int)

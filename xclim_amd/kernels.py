@@ -1787,3 +1787,44 @@ def precip_phase_period(dev: Device, pr: DeviceArray, tas: DeviceArray, seg, par
              np_ptr(dy) if dy is not None else _vp(0), *args, np_ptr(lim), window, mask, np_ptr(ptrs), C_)
     del keep
     return outs
+
+
+# ---- the spatial-analogue unit (include/ext/xclim_hip_analog.h, xclim_amd/csrc/analog.hip) ---------------------------
+def _ext_call(dev: Device, name: str, *args):
+    """``dev.call`` of an entry point of ``capi.EXT_SIGNATURES`` with every argument converted to the ctypes type of the table
+    here: the call is right on a library handle whose ``argtypes`` were never set."""
+    kinds = capi.EXT_SIGNATURES[name][1:]
+    if len(kinds) != len(args):
+        raise TypeError(f"{name}: {len(kinds)} arguments, got {len(args)}")
+    dev.call(name, *(a if isinstance(a, kind) else kind(a) for kind, a in zip(kinds, args)))
+
+
+def analog(dev: Device, method: str, x, fields, *, par=None, k=None, C_: int | None = None, ld: int | None = None,
+           out: DeviceArray | None = None, ld_out: int | None = None) -> DeviceArray:
+    """xh_analog: the dissimilarity ``method`` (a key of ``capi.ANALOG_METHODS``) between the target sample ``x``, host float64
+    (n, d), and the candidate sample of every cell: ``fields``, a sequence of d DeviceArrays (m, C), all float32 or all float64.
+    ``par``: the method's host parameters (zech_aslan: [dmin]; szekely_rizzo: [standardize]; mahalanobis: VI (d, d)).  ``k``:
+    kldiv's list.  Returns float64 (1, C), or (nk, C) for kldiv; one launch.  ``C_`` / ``ld`` / ``out`` / ``ld_out``: the cells
+    and the row pitches of padded views, and an output buffer of the caller's (default: dense fields, a new (rows, C) array)."""
+    who = "analog"
+    if method not in capi.ANALOG_METHODS:
+        raise ValueError(f"{who}: unknown method {method!r}")
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    fields = list(fields)
+    if x.ndim != 2 or len(fields) != x.shape[1] or not fields:
+        raise ValueError(f"{who}: x must be (n, d) and fields hold d arrays")
+    n, d = x.shape
+    m, width, f64 = _same_fields(who, {f"field {i}": f for i, f in enumerate(fields)})
+    ld = width if ld is None else int(ld)
+    C_ = ld if C_ is None else int(C_)
+    par = np.zeros(0) if par is None else np.ascontiguousarray(par, dtype=np.float64).reshape(-1)
+    ks = np.zeros(0, np.int32) if k is None else np.ascontiguousarray(k, dtype=np.int32).reshape(-1)
+    rows = len(ks) if method == "kldiv" else 1
+    if out is None:
+        ld_out = C_
+        out = dev.empty((rows, C_), np.float64)
+    ptrs = np.array([f.ptr for f in fields], np.uint64)
+    _ext_call(dev, "xh_analog", capi.ANALOG_METHODS[method], n, m, d, np_ptr(x), C_, ld, f64, np_ptr(ptrs),
+              np_ptr(par) if par.size else _vp(0), par.size, np_ptr(ks) if ks.size else _vp(0), ks.size, _vp(out.ptr),
+              C_ if ld_out is None else int(ld_out))
+    return out

@@ -152,7 +152,7 @@ def install(env=None, modules=None) -> list[str]:
     by default the real packages are used.  Functions the HIP path does not serve are forwarded to the saved originals."""
     import importlib
 
-    from . import agro, anuclim, dataflags, hydrology, phase, rainseason
+    from . import agro, analog, anuclim, dataflags, hydrology, phase, rainseason
     from .xr_adapter import make_wrappers
 
     env = env or real_env()
@@ -295,6 +295,8 @@ def install(env=None, modules=None) -> list[str]:
     install_mirror(("xclim.indices.converters", "xclim.indices", "xclim.indices._multivariate"), phase.converters)
     install_mirror(("xclim.indices._multivariate", "xclim.indices"), phase.multivariate)
     install_mirror(("xclim.indices._threshold", "xclim.indices"), phase.threshold)
+    # spatial_analogs of analog.py: one launch with a lane per candidate cell instead of a Python call per cell
+    install_mirror(("xclim.analog",), analog)
     cmod = resolve(_PET_MODULE)
     if cmod is not None and all(hasattr(cmod, n) for n in _PET_NAMES):
         from .converters import make_adapters as pet_adapters

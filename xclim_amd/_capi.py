@@ -276,7 +276,31 @@ EXT_SIGNATURES: dict[str, list] = {
     # include/ext/xclim_hip_analog.h (xclim_amd/csrc/analog.hip)
     "xh_analog": [_vp, _int, _i64, _i64, _int, _vp, _i64, _i64, _int, _vp, _vp, _i64, _vp, _i64, _vp, _i64],
 }
+# The prototypes of the headers under include/units/ (one header per unit added while both tests above are frozen); checked by
+# tests/test_abi_units_cpu.py, which takes the headers from the directory and from the group comments below.  A new unit adds
+# its header there, a comment line naming it and its .hip file, its rows, and the mirrors of its #defines; its wrappers call
+# through kernels._ext_call like those of EXT_SIGNATURES.
+UNIT_SIGNATURES: dict[str, list] = {
+    # include/units/xclim_hip_distfit.h (xclim_amd/csrc/distfit.hip)
+    "xh_dist_fit": [_vp, _vp, _i64, _i64, _i64, _int, _int, _int, _int, _dbl, _vp, _int, _int, _vp, _i64, _vp, _vp, _vp, _i64],
+    "xh_dist_eval": [_vp, _int, _int, _vp, _i64, _i64, _vp, _int, _vp, _i64],
+}
 _RESTYPES = {"xh_last_error": C.c_char_p}
+# include/units/xclim_hip_distfit.h: the XH_DIST_* distributions, methods and functions, the XH_DISTFIT_* limit and status bytes
+DIST_CODES = {"norm": 0, "gumbel_r": 1, "genextreme": 2, "gamma": 3, "fisk": 4, "lognorm": 5}
+DIST_NDISTS = 6          # XH_DIST_NDISTS
+DIST_METHODS = {"APP": 0, "ML": 1}
+DIST_FUNCS = {"ppf": 0, "isf": 1, "cdf": 2, "pdf": 3}
+DISTFIT_MAX_Q = 16       # XH_DISTFIT_MAX_Q
+DISTFIT_STATUS = {"fitted": 0, "nan": 1, "budget": 2, "support": 3}
+# header under include/units/ -> every integer #define of it, spelled from the mirrors above (tests/test_abi_units_cpu.py compares
+# each header with its entry, so a #define without a mirror, or a mirror with another value, fails there)
+UNIT_DEFINES = {
+    "xclim_hip_distfit.h": {
+        **{f"XH_DIST_{k.upper()}": v for k, v in DIST_CODES.items()}, "XH_DIST_NDISTS": DIST_NDISTS,
+        **{f"XH_DIST_{k}": v for k, v in DIST_METHODS.items()}, **{f"XH_DIST_{k.upper()}": v for k, v in DIST_FUNCS.items()},
+        "XH_DISTFIT_MAX_Q": DISTFIT_MAX_Q, **{f"XH_DISTFIT_{k.upper()}": v for k, v in DISTFIT_STATUS.items()}},
+}
 # the XH_ANALOG_* methods, in the order of the reference's registry
 ANALOG_METHODS = {"seuclidean": 0, "nearest_neighbor": 1, "zech_aslan": 2, "szekely_rizzo": 3, "friedman_rafsky": 4,
                   "kolmogorov_smirnov": 5, "kldiv": 6, "mahalanobis": 7}
@@ -311,8 +335,8 @@ def library_path() -> str:
 
 
 def load_library() -> C.CDLL:
-    """Load libxclimhip.so and declare every prototype of SIGNATURES (the six headers under include/) and of EXT_SIGNATURES
-    (include/ext/).  Raises
+    """Load libxclimhip.so and declare every prototype of SIGNATURES (the six headers under include/), of EXT_SIGNATURES
+    (include/ext/) and of UNIT_SIGNATURES (include/units/).  Raises
     BackendUnavailable."""
     global _lib
     with _lib_lock:
@@ -327,7 +351,7 @@ def load_library() -> C.CDLL:
             lib = C.CDLL(_LIB_PATH)
         except OSError as err:  # pragma: no cover
             raise BackendUnavailable(f"cannot load {_LIB_PATH}: {err}") from err
-        for name, argtypes in (*SIGNATURES.items(), *EXT_SIGNATURES.items()):
+        for name, argtypes in (*SIGNATURES.items(), *EXT_SIGNATURES.items(), *UNIT_SIGNATURES.items()):
             fn = getattr(lib, name)  # AttributeError if the header and the library diverge
             fn.argtypes = argtypes
             fn.restype = _RESTYPES.get(name, _int)

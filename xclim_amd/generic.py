@@ -553,3 +553,27 @@ def season(data, thresh: float, window: int, op: str, time: TimeAxis, freq: str,
     cond = K.spell_mask(dev, x, 1, "min", sym, float(thresh))
     return hrl.season(cond.reshape((x.shape[0],) + tuple(cell_shape)), window, mid_date, time=time, freq=freq,
                       coord="dayofyear", device=dev)
+
+
+_MONTH_ABBREVIATIONS = {1: "JAN", 2: "FEB", 3: "MAR", 4: "APR", 5: "MAY", 6: "JUN", 7: "JUL", 8: "AUG", 9: "SEP", 10: "OCT",
+                        11: "NOV", 12: "DEC"}
+
+
+def default_freq(**indexer) -> str:
+    """gen:224-252: "YS-JAN", or the year anchored at the first month of the time selection (``season=``: "YS-DEC";
+    ``doy_bounds=``: the month of the first day in a leap year)."""
+    freq = "YS-JAN"
+    if indexer:
+        group, value = indexer.popitem()
+        if group == "season":
+            month = 12
+        elif group == "month":
+            month = int(np.take(value, 0))
+        elif group == "doy_bounds":
+            month = int(np.searchsorted(np.cumsum([31, 29, 31, 30, 31, 30, 31, 31, 30, 31, 30, 31]), int(value[0]), side="left")) + 1
+        elif group == "date_bounds":
+            month = int(value[0][:2])
+        else:
+            raise ValueError(f"Unknown group `{group}`.")
+        freq = "YS-" + _MONTH_ABBREVIATIONS[month]
+    return freq

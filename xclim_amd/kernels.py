@@ -1791,9 +1791,10 @@ def precip_phase_period(dev: Device, pr: DeviceArray, tas: DeviceArray, seg, par
 
 # ---- the spatial-analogue unit (include/ext/xclim_hip_analog.h, xclim_amd/csrc/analog.hip) ---------------------------
 def _ext_call(dev: Device, name: str, *args):
-    """``dev.call`` of an entry point of ``capi.EXT_SIGNATURES`` with every argument converted to the ctypes type of the table
-    here: the call is right on a library handle whose ``argtypes`` were never set."""
-    kinds = capi.EXT_SIGNATURES[name][1:]
+    """``dev.call`` of an entry point of ``capi.EXT_SIGNATURES`` or ``capi.UNIT_SIGNATURES`` with every argument converted to
+    the ctypes type of its table here: the call is right on a library handle whose ``argtypes`` were never set."""
+    table = capi.EXT_SIGNATURES if name in capi.EXT_SIGNATURES else capi.UNIT_SIGNATURES
+    kinds = table[name][1:]
     if len(kinds) != len(args):
         raise TypeError(f"{name}: {len(kinds)} arguments, got {len(args)}")
     dev.call(name, *(a if isinstance(a, kind) else kind(a) for kind, a in zip(kinds, args)))
@@ -1827,4 +1828,58 @@ def analog(dev: Device, method: str, x, fields, *, par=None, k=None, C_: int | N
     _ext_call(dev, "xh_analog", capi.ANALOG_METHODS[method], n, m, d, np_ptr(x), C_, ld, f64, np_ptr(ptrs),
               np_ptr(par) if par.size else _vp(0), par.size, np_ptr(ks) if ks.size else _vp(0), ks.size, _vp(out.ptr),
               C_ if ld_out is None else int(ld_out))
+    return out
+
+
+# ---- the distribution-fit unit (include/units/xclim_hip_distfit.h, xclim_amd/csrc/distfit.hip) --------------------------
+def dist_nparams(dist: str) -> int:
+    return 2 if dist in ("norm", "gumbel_r") else 3
+
+
+def dist_fit(dev: Device, x: DeviceArray, dist: str, method: str = "ML", floc=None, q=None, qfunc: str = "ppf", *,
+             C_: int | None = None, ld: int | None = None, outs: dict | None = None, pitches: dict | None = None):
+    """xh_dist_fit: the parameters of ``dist`` (a key of ``capi.DIST_CODES``) for every cell of a (T, C) float32 or float64
+    field, one launch.  ``q`` (at most ``capi.DISTFIT_MAX_Q`` probabilities) adds the fused levels ``qfunc`` ("ppf" / "isf").
+    Returns ``(params (nparams, C) float64, nfev (C) int32, status (C) uint8, levels (nq, C) float64 or None)`` as
+    DeviceArrays.  ``C_`` / ``ld`` / ``outs`` / ``pitches``: the cells and the row pitch of a padded view, output buffers of the
+    caller's (keys params, nfev, status, levels) and their row pitches (keys params, levels)."""
+    who = "dist_fit"
+    if dist not in capi.DIST_CODES:
+        raise ValueError(f"{who}: unknown distribution {dist!r}")
+    if method not in capi.DIST_METHODS:
+        raise ValueError(f"{who}: unknown method {method!r}")
+    T, width, f64 = _field(x)
+    ld = width if ld is None else int(ld)
+    C_ = ld if C_ is None else int(C_)
+    qs = np.zeros(0) if q is None else np.ascontiguousarray(q, dtype=np.float64).reshape(-1)
+    outs = dict(outs or {})
+    pitches = dict(pitches or {})
+    params = outs.get("params") or dev.empty((dist_nparams(dist), C_), np.float64)
+    nfev = outs.get("nfev") or dev.empty((C_,), np.int32)
+    status = outs.get("status") or dev.empty((C_,), np.uint8)
+    levels = (outs.get("levels") or dev.empty((len(qs), C_), np.float64)) if len(qs) else None
+    _ext_call(dev, "xh_dist_fit", _vp(x.ptr), T, C_, ld, int(f64), capi.DIST_CODES[dist], capi.DIST_METHODS[method],
+              int(floc is not None), float(floc if floc is not None else 0.0), np_ptr(qs) if len(qs) else _vp(0), len(qs),
+              capi.DIST_FUNCS[qfunc], _vp(params.ptr), int(pitches.get("params", C_)), _vp(nfev.ptr), _vp(status.ptr),
+              _vp(levels.ptr if levels is not None else 0), int(pitches.get("levels", C_)))
+    return params, nfev, status, levels
+
+
+def dist_eval(dev: Device, params: DeviceArray, dist: str, func: str, v, *, C_: int | None = None, ld: int | None = None,
+              out: DeviceArray | None = None, ld_out: int | None = None) -> DeviceArray:
+    """xh_dist_eval: ``func`` ("ppf" / "isf" / "cdf" / "pdf") of ``dist`` at the host values ``v`` for every cell of the
+    (nparams, C) float64 parameters; returns (nv, C) float64.  ``C_`` / ``ld`` / ``out`` / ``ld_out``: padded views."""
+    who = "dist_eval"
+    if dist not in capi.DIST_CODES or func not in capi.DIST_FUNCS:
+        raise ValueError(f"{who}: unknown distribution or function ({dist!r}, {func!r})")
+    if np.dtype(params.dtype) != np.float64 or len(params.shape) != 2 or params.shape[0] != dist_nparams(dist):
+        raise TypeError(f"{who}: params must be float64 ({dist_nparams(dist)}, C), got {np.dtype(params.dtype).name} {params.shape}")
+    ld = int(params.shape[1]) if ld is None else int(ld)
+    C_ = ld if C_ is None else int(C_)
+    vs = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+    if out is None:
+        ld_out = C_
+        out = dev.empty((len(vs), C_), np.float64)
+    _ext_call(dev, "xh_dist_eval", capi.DIST_CODES[dist], capi.DIST_FUNCS[func], _vp(params.ptr), C_, ld,
+              np_ptr(vs) if len(vs) else _vp(0), len(vs), _vp(out.ptr), C_ if ld_out is None else int(ld_out))
     return out

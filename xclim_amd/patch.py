@@ -105,6 +105,12 @@ _SI_NAMES = ("standardized_index", "standardized_index_fit_params")
 _SI_BY_NAME = {"xclim.indices.stats": _SI_NAMES, "xclim.indices._agro": ("standardized_index",),
                "xclim.indices._hydrology": ("standardized_index",)}
 
+# the distribution fits: stats.py defines the six; indicators/generic/_stats.py:7-8 imports ``fit as _fit`` and
+# ``frequency_analysis`` by name.  module -> {attribute there: function of stats.FIT_ADAPTED}
+_FIT_BY_NAME = {"xclim.indices.stats": {n: n for n in ("fit", "parametric_quantile", "parametric_cdf", "parametric_pdf", "fa",
+                                                       "frequency_analysis")},
+                "xclim.indicators.generic._stats": {"_fit": "fit", "frequency_analysis": "frequency_analysis"}}
+
 _FIRE_MODULE = "xclim.indices.fire._cffwis"
 _FIRE_NAMES = ("_fire_weather_calc", "_fire_season")
 _FFDI_MODULE = "xclim.indices.fire._ffdi"
@@ -325,6 +331,14 @@ def install(env=None, modules=None) -> list[str]:
         for modname, names in _SI_BY_NAME.items():
             for name in names:
                 patch(modname, name, si[name])
+    # fit, the parametric functions, fa and frequency_analysis, and the two names the generic indicators import
+    if smod is not None and all(hasattr(smod, n) for n in _FIT_BY_NAME[_SI_MODULE]):
+        from .stats import make_fit_adapters
+
+        fits = make_fit_adapters(env, {n: _saved.get((_SI_MODULE, n), getattr(smod, n)) for n in _FIT_BY_NAME[_SI_MODULE]})
+        for modname, names in _FIT_BY_NAME.items():
+            for attr, name in names.items():
+                patch(modname, attr, fits[name])
     _saved_modules.update({} if modules is None else modules)
     return done
 

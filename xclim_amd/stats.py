@@ -40,12 +40,13 @@ import warnings
 import numpy as np
 
 from . import kernels as K
-from ._capi import DeviceArray, float64_native, float64_policy, get_device, handle_float64
+from ._capi import DISTFIT_MAX_Q, DISTFIT_STATUS, DeviceArray, float64_native, float64_policy, get_device, handle_float64
 from .calendar import _flatten
 from .fields import NotServed
 from .timeaxis import TimeAxis
 
-__all__ = ["NotServed", "SIParams", "standardized_index_fit_params", "standardized_index", "preprocessed_time"]
+__all__ = ["NotServed", "SIParams", "standardized_index_fit_params", "standardized_index", "preprocessed_time", "Fitted", "fit",
+           "parametric_quantile", "parametric_cdf", "parametric_pdf", "fa", "frequency_analysis"]
 
 DIST_PARAMS = {"gamma": ("a", "loc", "scale"), "fisk": ("c", "loc", "scale")}
 _MAX_DOY = {"360_day": 360, "noleap": 365, "365_day": 365}  # every other calendar: 366
@@ -440,3 +441,344 @@ def make_adapters(env, orig_index, orig_fit, device=None) -> dict:
     standardized_index_.__wrapped__ = orig_index
     fit_params.__wrapped__ = orig_fit
     return {"standardized_index": standardized_index_, "standardized_index_fit_params": fit_params}
+
+
+# ==== distribution fits and return levels (stats.py:45-548; xclim_amd/csrc/distfit.hip) ==================================================
+# fit, parametric_quantile / _cdf / _pdf, fa and frequency_analysis on arrays with TIME ON AXIS 0.  One launch per call (xh_dist_fit,
+# xh_dist_eval); fa and frequency_analysis take their levels from the fit launch itself.
+#
+# Served: ``dist`` one of FIT_DISTS, by name or as the scipy singleton of that name; ``method`` ML / MLE (lognorm only with
+# ``floc``) and APP (genextreme, gamma, fisk, lognorm; for norm and gumbel_r the reference itself raises KeyError); ``floc`` for
+# gamma, fisk and lognorm.  Refused with NotServed: other distributions and rv_continuous objects, the methods MM / PWM / MSE /
+# MPS, lognorm ML without floc, floc for norm / gumbel_r / genextreme, every other fit keyword, integer fields.
+#
+# ASSUMPTION: all arithmetic is float64 on the widened values.  The reference hands scipy a float32 slice of a float32 field, so
+# its start values are float32 means; this unit does not reproduce that.
+#
+# Differences from the reference, all where scipy itself fails for the cell (and the reference with it, for the whole call): NaN
+# parameters where brentq finds no sign change or meets a NaN function value (gumbel_r on identical values, where scipy returns
+# (inf, tiny)), where gamma with floc has a value at or below floc, where lognorm with floc ends with a shape of zero, and where a
+# Nelder–Mead fit ends off the parameter domain.  gamma's isf(q) is ppf(1 - q).  No ``history`` attribute is written.
+FIT_DISTS = {"norm": ("loc", "scale"), "gumbel_r": ("loc", "scale"), "genextreme": ("c", "loc", "scale"),
+             "gamma": ("a", "loc", "scale"), "fisk": ("c", "loc", "scale"), "lognorm": ("s", "loc", "scale")}
+_METHOD_NAME = {"ML": "maximum likelihood", "MM": "method of moments", "MLE": "maximum likelihood",
+                "MSE": "maximum product of spacings", "MPS": "maximum product of spacings", "PWM": "probability weighted moments",
+                "APP": "approximative method"}
+_FLOC_DISTS = ("gamma", "fisk", "lognorm")
+
+
+class Fitted:
+    """The result of :func:`fit`: ``values`` (nparams, *cells) float64 (``keep=True``: the (nparams, C) DeviceArray), ``attrs``
+    (the reference's), ``dist``, ``cell_shape``, and per cell ``nfev`` (objective evaluations) and ``status``
+    (``_capi.DISTFIT_STATUS``) as host arrays.  Unpacks as ``values, attrs = fit(...)``."""
+
+    def __init__(self, values, attrs, dist, cell_shape, nfev, status):
+        self.values, self.attrs, self.dist, self.cell_shape = values, attrs, dist, tuple(cell_shape)
+        self.nfev, self.status = nfev, status
+
+    def __iter__(self):
+        return iter((self.values, self.attrs))
+
+
+def dist_name(dist) -> str:
+    """The name of a served distribution given by name or as the scipy singleton of that name; NotServed otherwise."""
+    if isinstance(dist, str):
+        if dist in FIT_DISTS:
+            return dist
+        raise NotServed(f"distribution fits: the distribution {dist!r} is not served ({', '.join(FIT_DISTS)})")
+    name = getattr(dist, "name", None)
+    if name in FIT_DISTS:
+        import sys
+
+        sst = sys.modules.get("scipy.stats")   # (an rv_continuous object exists only where scipy.stats was imported)
+        if sst is not None and getattr(sst, name, None) is dist:
+            return name
+    raise NotServed(f"distribution fits: {dist!r} is not one of scipy's {', '.join(FIT_DISTS)}")
+
+
+def _check_fit(dist, method, fitkwargs):
+    """(name, the method in capitals, "ML" | "APP" for the kernel, floc or None) of a served fit; ValueError for an unknown method, NotServed for the rest."""
+    method = method.upper()
+    if method not in _METHOD_NAME:
+        raise ValueError(f"Fitting method not recognized: {method}")
+    name = dist_name(dist)
+    if method not in ("ML", "MLE", "APP"):
+        raise NotServed(f"distribution fits: the method {method} is not served (ML, MLE, APP)")
+    extra = set(fitkwargs) - {"floc"}
+    if extra:
+        raise NotServed(f"distribution fits: fit keywords {sorted(extra)} are not served (floc only)")
+    floc = fitkwargs.get("floc")
+    if floc is not None:
+        if name not in _FLOC_DISTS:
+            raise NotServed(f"distribution fits: floc is not served for {name}")
+        floc = float(floc)
+    if method == "APP" and name in ("norm", "gumbel_r"):
+        raise NotServed(f"distribution fits: the reference has no APP method for {name}")
+    if name == "lognorm" and method != "APP" and floc is None:
+        raise NotServed("distribution fits: lognorm by maximum likelihood is served with floc only")
+    return name, method, ("APP" if method == "APP" else "ML"), floc
+
+
+def _fit_field(da, dev):
+    """(DeviceArray (T, C) float32 or float64, cell shape): float fields only, float64 read natively."""
+    if not isinstance(da, DeviceArray):
+        da = np.asarray(da)
+        if da.dtype.kind != "f":
+            raise NotServed(f"distribution fits: {da.dtype.name} fields are not served (float32, float64)")
+        if da.dtype not in (np.float32, np.float64):
+            da = da.astype(np.float32)
+    if len(da.shape) < 1:
+        raise ValueError("distribution fits: the field needs a time axis")
+    return _flatten(da, dev, f64=True)
+
+
+def fit_attrs(name: str, method: str, attrs: dict | None = None) -> dict:
+    """The attributes of the reference's fit (stats.py:203-217, without ``history``)."""
+    out = {}
+    for k, v in (attrs or {}).items():
+        out[f"original_{k}" if k in ("standard_name", "long_name", "units", "description") else k] = v
+    out.update(long_name=f"{name} parameters", description=f"Parameters of the {name} distribution", method=method,
+               estimator=_METHOD_NAME[method].capitalize(), scipy_dist=name, units="")
+    return out
+
+
+def _raise_support(name, status):
+    # lognorm_gen.fit raises FitDataError (a ValueError) for the whole call; scipy's text
+    if name == "lognorm" and (status == DISTFIT_STATUS["support"]).any():
+        raise ValueError("Invalid values in `data`.  Maximum likelihood estimation with 'lognorm' requires that 0.0 < "
+                         "(x - loc)/scale  < inf for each x in `data`.")
+
+
+def fit(da, dist="norm", method: str = "ML", *, attrs: dict | None = None, device=None, keep: bool = False, **fitkwargs) -> Fitted:
+    """stats.py:115-218 on a (T, *cells) field: the parameters (nparams, *cells) float64 of ``dist`` for every cell.  NaN values
+    of a cell are dropped; fewer than two values, or a NaN parameter, make all of the cell's parameters NaN."""
+    name, method, kmethod, floc = _check_fit(dist, method, fitkwargs)
+    dev = device or get_device()
+    x, cells = _fit_field(da, dev)
+    params, nfev, status, _ = K.dist_fit(dev, x, name, kmethod, floc)
+    st = status.get()
+    _raise_support(name, st)
+    values = params if keep else params.get().reshape(len(FIT_DISTS[name]), *cells)
+    return Fitted(values, fit_attrs(name, method, attrs), name, cells, nfev.get(), st)
+
+
+def _params_of(p, dist, dev):
+    """(DeviceArray (nparams, C), name, cell shape) of a Fitted, a DeviceArray (nparams, C) or a host array (nparams, *cells)."""
+    if isinstance(p, Fitted):
+        name = dist_name(dist or p.attrs["scipy_dist"])
+        v, cells = p.values, p.cell_shape
+    else:
+        if dist is None:
+            raise ValueError("parametric functions of a plain array need `dist`")
+        name, v = dist_name(dist), p
+        cells = None
+    n = len(FIT_DISTS[name])
+    if isinstance(v, DeviceArray):
+        if np.dtype(v.dtype) != np.float64 or v.shape[0] != n:
+            raise TypeError(f"{name} parameters must be float64 ({n}, C), got {np.dtype(v.dtype).name} {v.shape}")
+        cells = tuple(v.shape[1:]) if cells is None else cells
+        return v.reshape(n, -1), name, cells
+    v = np.asarray(v)
+    if v.dtype.kind != "f":
+        raise NotServed(f"distribution fits: {v.dtype.name} parameters are not served")
+    if v.ndim < 1 or v.shape[0] != n:
+        raise ValueError(f"{name} has {n} parameters, got an array of shape {v.shape}")
+    return dev.to_device(v.reshape(n, -1), dtype=np.float64), name, tuple(v.shape[1:])
+
+
+def _parametric(p, v, dist, func, device, keep):
+    dev = device or get_device()
+    d, name, cells = _params_of(p, dist, dev)
+    v = np.atleast_1d(np.asarray(v, dtype=np.float64))
+    if v.ndim != 1:
+        raise ValueError("`v` must be one-dimensional.")
+    out = K.dist_eval(dev, d, name, func, v)
+    return out if keep else out.get().reshape(len(v), *cells)
+
+
+def quantile_route(q) -> tuple[str, np.ndarray]:
+    """The switch of parametric_quantile (stats.py:254-262): ("isf", 1 - q) when every q > 0.5, else ("ppf", q)."""
+    q = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    return ("isf", 1 - q) if np.all(q > 0.5) else ("ppf", q)
+
+
+def parametric_quantile(p, q, dist=None, *, device=None, keep: bool = False):
+    """stats.py:221-292: (nq, *cells) float64, the quantiles ``q`` of the fitted distribution of every cell."""
+    func, arg = quantile_route(q)
+    return _parametric(p, arg, dist, func, device, keep)
+
+
+def parametric_cdf(p, v, dist=None, *, device=None, keep: bool = False):
+    """stats.py:297-360: (nv, *cells) float64."""
+    return _parametric(p, v, dist, "cdf", device, keep)
+
+
+def parametric_pdf(p, v, dist=None, *, device=None, keep: bool = False):
+    """stats.py:363-426: (nv, *cells) float64."""
+    return _parametric(p, v, dist, "pdf", device, keep)
+
+
+def _return_quantiles(t, mode):
+    t = np.atleast_1d(t)
+    if mode in ["max", "high"]:
+        return t, 1 - 1.0 / t
+    if mode in ["min", "low"]:
+        return t, 1.0 / t
+    raise ValueError(f"Mode `{mode}` should be either 'max' or 'min'.")
+
+
+def fa(da, t, dist="norm", mode: str = "max", method: str = "ML", *, device=None, keep: bool = False):
+    """stats.py:429-482: (nt, *cells) float64, the value with return period ``t`` from the maximized / minimized ``da``
+    (T, *cells).  Fit and levels are ONE launch for up to ``_capi.DISTFIT_MAX_Q`` periods."""
+    name, method, kmethod, floc = _check_fit(dist, method, {})
+    t, q = _return_quantiles(t, mode)
+    func, arg = quantile_route(q)
+    dev = device or get_device()
+    x, cells = _fit_field(da, dev)
+    if len(arg) <= DISTFIT_MAX_Q:
+        _, _, _, out = K.dist_fit(dev, x, name, kmethod, floc, q=arg, qfunc=func)
+    else:
+        params, _, _, _ = K.dist_fit(dev, x, name, kmethod, floc)
+        out = K.dist_eval(dev, params, name, func, arg)
+    return out if keep else out.get().reshape(len(arg), *cells)
+
+
+def frequency_analysis(da, mode: str, t, dist, time: TimeAxis = None, window: int = 1, freq: str | None = None,
+                       method: str = "ML", *, device=None, keep: bool = False, **indexer):
+    """stats.py:485-548 on a daily (T, *cells) field with its TimeAxis: the trailing rolling mean (``skipna=False``), the
+    period extremes (``generic.select_resample_op``; ``freq=None``: ``generic.default_freq(**indexer)``), kept on the device,
+    and :func:`fa` on them."""
+    from . import generic
+    from .calendar import _flatten as flatten
+
+    if time is None:
+        raise TypeError("frequency_analysis needs the field's TimeAxis (time=)")
+    _check_fit(dist, method, {})
+    _return_quantiles(t, mode)
+    if mode not in ("max", "min"):
+        raise NotServed(f"frequency_analysis: the resampling operator {mode!r} is not served (max, min)")
+    dev = device or get_device()
+    if int(window) > 1:
+        x, cells = flatten(da, dev, f64=float64_native() and not indexer)
+        da = K.rolling_reduce(dev, x, int(window), "mean", center=False)
+    else:
+        cells = tuple(da.shape[1:])
+    freq = freq or generic.default_freq(**indexer)
+    sel = generic.select_resample_op(da, mode, time, freq, device=dev, keep=True, **indexer)
+    out = fa(sel, t, dist, mode, method, device=dev, keep=True)
+    return out if keep else out.get().reshape(out.shape[0], *cells)
+
+
+FIT_ADAPTED = ("fit", "parametric_quantile", "parametric_cdf", "parametric_pdf", "fa", "frequency_analysis")
+
+
+def make_fit_adapters(env, origs: dict, device=None) -> dict:
+    """Same-signature replacements of the six functions of FIT_ADAPTED on DataArrays (``dim`` may be anywhere; ``dparams``,
+    ``quantile`` / ``return_period``, ``cdf`` and ``v`` land where the reference transposes them).  NotServed forms, chunked
+    fields and float64 refusals go to ``origs``."""
+    from ._capi import Float64FieldError
+    from .xr_adapter import is_chunked, time_axis_of
+
+    DA = env.DataArray
+
+    def _moved(a, dim):
+        """(values with `dim` first, the position of `dim`, the other dims, the coordinates without `dim`)"""
+        ax = a.dims.index(dim)
+        rest = tuple(d for d in a.dims if d != dim)
+        vals = np.ascontiguousarray(a.transpose(dim, *rest).values)
+        coords = {k: v for k, v in a.coords.items() if dim not in getattr(v, "dims", ())}
+        return vals, ax, rest, coords
+
+    def _put(values, ax, rest, coords, newdim, labels, attrs):
+        coords = dict(coords)
+        coords[newdim] = labels
+        dims = rest[:ax] + (newdim,) + rest[ax:]
+        return DA(np.moveaxis(np.asarray(values), 0, ax), coords=coords, dims=dims, attrs=attrs)
+
+    def _ok(da, dim):
+        return isinstance(da, DA) and dim in da.dims and not is_chunked(da)
+
+    def fit_(da, dist="norm", method="ML", dim="time", **fitkwargs):
+        if not _ok(da, dim):
+            return origs["fit"](da, dist, method, dim, **fitkwargs)
+        try:
+            vals, ax, rest, coords = _moved(da, dim)
+            p = fit(vals, dist, method, attrs=da.attrs, device=device, **fitkwargs)
+        except (NotServed, Float64FieldError):
+            return origs["fit"](da, dist, method, dim, **fitkwargs)
+        return _put(p.values, ax, rest, coords, "dparams", list(FIT_DISTS[p.dist]), p.attrs)
+
+    def _unprefixed(attrs):
+        out = {}
+        for k, v in attrs.items():
+            if k in ("original_units", "original_standard_name"):
+                out[k[len("original_"):]] = v
+            elif k not in out:
+                out[k] = v
+        return out
+
+    def _param_call(fn, p, arg, dist, newdim, label, cell_methods, what):
+        if not _ok(p, "dparams") or not (dist or "scipy_dist" in p.attrs):
+            return None
+        arg_da = arg if isinstance(arg, DA) else None
+        if arg_da is not None and len(arg_da.dims) > 1:
+            raise ValueError("`v` must be one-dimensional.")
+        a = np.atleast_1d(np.asarray(arg_da.values if arg_da is not None else arg, dtype=np.float64))
+        try:
+            dname = dist_name(dist or p.attrs["scipy_dist"])
+            vals, ax, rest, coords = _moved(p, "dparams")
+            out = fn(vals, a, dname, device=device)
+        except (NotServed, Float64FieldError):
+            return None
+        attrs = _unprefixed(p.attrs)
+        attrs.update(long_name=f"{dname} {label}", description=f"{what} estimated by the {dname} distribution",
+                     cell_methods=cell_methods)
+        labels = a if arg_da is None else DA(a, dims=(newdim,), attrs=arg_da.attrs)
+        return _put(out, ax, rest, coords, newdim, labels, attrs)
+
+    def parametric_quantile_(p, q, dist=None):
+        out = _param_call(parametric_quantile, p, q, dist, "quantile", "quantiles", "dparams: ppf", "Quantiles")
+        return origs["parametric_quantile"](p, q, dist) if out is None else out
+
+    def parametric_cdf_(p, v, dist=None):
+        out = _param_call(parametric_cdf, p, v, dist, "cdf", "cdf", "dparams: cdf", "CDF")
+        return origs["parametric_cdf"](p, v, dist) if out is None else out
+
+    def parametric_pdf_(p, v, dist=None):
+        out = _param_call(parametric_pdf, p, v, dist, "v", "PDF", "dparams: v", "PDF")
+        return origs["parametric_pdf"](p, v, dist) if out is None else out
+
+    def fa_(da, t, dist="norm", mode="max", method="ML"):
+        if not _ok(da, "time"):
+            return origs["fa"](da, t, dist, mode, method)
+        try:
+            vals, ax, rest, coords = _moved(da, "time")
+            out = fa(vals, t, dist, mode, method, device=device)
+            attrs = _unprefixed(fit_attrs(dist_name(dist), method.upper(), da.attrs))
+        except (NotServed, Float64FieldError):
+            return origs["fa"](da, t, dist, mode, method)
+        dname = attrs["scipy_dist"]
+        attrs.update(long_name=f"{dname} quantiles", description=f"Quantiles estimated by the {dname} distribution",
+                     cell_methods="dparams: ppf", mode=mode)
+        return _put(out, ax, rest, coords, "return_period", np.atleast_1d(t), attrs)
+
+    def frequency_analysis_(da, mode, t, dist, window=1, freq=None, method="ML", **indexer):
+        if not _ok(da, "time"):
+            return origs["frequency_analysis"](da, mode, t, dist, window, freq, method, **indexer)
+        try:
+            vals, ax, rest, coords = _moved(da, "time")
+            out = frequency_analysis(vals, mode, t, dist, time_axis_of(da), window, freq, method, device=device, **indexer)
+            attrs = _unprefixed(fit_attrs(dist_name(dist), method.upper(), da.attrs))
+        except (NotServed, Float64FieldError):
+            return origs["frequency_analysis"](da, mode, t, dist, window, freq, method, **indexer)
+        dname = attrs["scipy_dist"]
+        attrs.update(long_name=f"{dname} quantiles", description=f"Quantiles estimated by the {dname} distribution",
+                     cell_methods="dparams: ppf", mode=mode)
+        return _put(out, ax, rest, coords, "return_period", np.atleast_1d(t), attrs)
+
+    adapters = {"fit": fit_, "parametric_quantile": parametric_quantile_, "parametric_cdf": parametric_cdf_,
+                "parametric_pdf": parametric_pdf_, "fa": fa_, "frequency_analysis": frequency_analysis_}
+    for n, fn in adapters.items():
+        fn.__wrapped__ = origs[n]
+        fn.__name__ = n
+    return adapters

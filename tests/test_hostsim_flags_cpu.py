@@ -47,7 +47,8 @@ def test_the_refusals_on_the_simulation(sim):
 
 
 def test_the_gpu_modules_on_the_simulation(sim):
-    _child_run(sim, GPU_MODULES, at_least=60)
+    # (of tests/test_gpu_footprint.py: the cases on this unit's entry points, by their id "flags-...", and the test named "flags")
+    _child_run(sim, GPU_MODULES + ["tests/test_gpu_footprint.py"], skip="footprint and not (flags- or test_flags)", at_least=60 + 6)
 
 
 def test_standalone_sanitizer_run(tmp_path):

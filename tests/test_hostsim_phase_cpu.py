@@ -48,7 +48,8 @@ def test_the_refusals_on_the_simulation(sim):
 
 
 def test_the_gpu_modules_on_the_simulation(sim):
-    _child_run(sim, GPU_MODULES, at_least=100)
+    # (of tests/test_gpu_footprint.py: the cases on this unit's entry points, by their id "phase-...")
+    _child_run(sim, GPU_MODULES + ["tests/test_gpu_footprint.py"], skip="footprint and not phase-", at_least=100 + 6)
 
 
 def test_standalone_sanitizer_run(tmp_path):

@@ -13,18 +13,19 @@ import pytest
 from test_hostsim_cpu import _child_run
 
 # unit -> (the entry points that must resolve: the unit's own and those of the units linked with it,
-#          the GPU modules of the child run, the least number of tests that must pass there)
+#          the GPU modules of the child run, the least number of tests that must pass there: the unit's own and, where
+#          tests/test_gpu_footprint.py has cases on the unit's entry points, those)
 UNITS = {
-    "chill": (("xh_chill_hourly", "xh_chill_daily", "xh_solar_table"), ["tests/test_gpu_chill.py"], 76),
+    "chill": (("xh_chill_hourly", "xh_chill_daily", "xh_solar_table"), ["tests/test_gpu_chill.py", "tests/test_gpu_footprint.py"], 76 + 4),
     "bioclim": (("xh_bioclim", "xh_resample_reduce_f64", "xh_range_reduce_f64"),
-                ["tests/test_gpu_bioclim.py", "tests/test_gpu_anuclim_adapter.py"], 55),
+                ["tests/test_gpu_bioclim.py", "tests/test_gpu_anuclim_adapter.py", "tests/test_gpu_footprint.py"], 55 + 4),
     "agro": (("xh_agro_degree_sum", "xh_agro_monthly", "xh_egdd", "xh_corn_heat_units", "xh_qian_wma", "xh_solar_table", "xh_resample_reduce_f64"),
-             ["tests/test_gpu_agro.py", "tests/test_gpu_agro_adapter.py"], 170),
+             ["tests/test_gpu_agro.py", "tests/test_gpu_agro_adapter.py", "tests/test_gpu_footprint.py"], 170 + 12),
     "hydro": (("xh_flow_period_stats", "xh_melt_period_max", "xh_antecedent_precip", "xh_sen_slope",
                "xh_resample_reduce", "xh_resample_reduce_f64", "xh_threshold_count_doy", "xh_nan_quantile_f64"),
-              ["tests/test_gpu_hydro.py", "tests/test_gpu_hydro_adapter.py"], 100),
+              ["tests/test_gpu_hydro.py", "tests/test_gpu_hydro_adapter.py", "tests/test_gpu_footprint.py"], 100 + 20),
     "rain": (("xh_rain_season", "xh_rolling_zones", "xh_resample_reduce", "xh_resample_reduce_f64"),
-             ["tests/test_gpu_rain.py", "tests/test_gpu_rain_adapter.py"], 90),
+             ["tests/test_gpu_rain.py", "tests/test_gpu_rain_adapter.py", "tests/test_gpu_footprint.py"], 90 + 6),
 }
 
 # What the child runs leave out, and why.
@@ -88,7 +89,9 @@ def test_the_known_answers_of_rain_on_the_simulation(tmp_path_factory):
 
 def test_the_gpu_modules_on_the_simulation(unit, sim):
     _, files, at_least = UNITS[unit]
-    _child_run(sim, files, deselect=sorted(d for d in DESELECTED if d.split("::")[0] in files), at_least=at_least)
+    # (of tests/test_gpu_footprint.py: the cases whose entry points this library holds, by their id "<unit>-...")
+    _child_run(sim, files, skip=f"footprint and not {unit}-", deselect=sorted(d for d in DESELECTED if d.split("::")[0] in files),
+               at_least=at_least)
 
 
 # Every program runs its entry points under AddressSanitizer and UBSan in a process of its own, on malloc blocks of exactly

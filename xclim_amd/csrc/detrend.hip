@@ -202,9 +202,18 @@ k_trend_apply_groups(const float* x, int64_t C, int64_t st, const int32_t* __res
 // Centred window mean over the valid samples (xsdba.detrending._polydetrend_get_trend with a windowed Grouper:
 // rolling(time=window, center=True).construct("window") pads the ends with NaN, then da.mean over the window dimension skips
 // NaN): out[t, c] = mean { x[s, c] : |s - t| <= window / 2, 0 <= s < T, x[s, c] valid }, NaN when the window holds no valid
-// sample.  A thread = one column x one stretch of WM_ROWS output rows: a running float64 sum and count (float32 samples: every
-// add / subtract is exact to 2^-53 of the sum), the window's first rows summed up front.
+// sample.  A thread = one column x one stretch of WM_ROWS output rows: a running float64 sum and count, the window's first rows
+// summed up front.  An add or subtract is exact to 2^-53 of the LARGER of sum and sample, so a sample that dwarfs the rest of
+// its window (an unmasked fill value: -9999, 1e20) swallows the low bits of the others while it is in the sum and leaves their
+// loss behind when it is subtracted.  Hence: when the leaving sample is more than WM_RESUM times what remains, the window is
+// summed again from its rows, and the damage ends with the last window that holds the sample; otherwise every leaving sample
+// adds at most WM_RESUM * 2^-52 of the sum to the error, and the losses add up over the leaving samples of a stretch (at most
+// WM_ROWS of them: 128 * 1024 * 2^-52 = 2.9e-11 of the sum, against the 6e-8 of the float32 result).  The test is against the
+// SUM that remains, not the sum of magnitudes: on a field centred on zero (anomalies, degC) plain cancellation makes the sum small
+// and triggers the re-read with no outlier in sight.  That is correct and costs a divergent pass over the window; it was not
+// timed on such a field.
 constexpr int WM_ROWS = 128;
+constexpr double WM_RESUM = 1024.0;
 __global__ void __launch_bounds__(XH_BLOCK)
 k_window_nanmean(const float* __restrict__ x, int64_t T, int64_t C, int64_t st, int half, float* __restrict__ out, int64_t ost) {
   const int64_t c = (int64_t)blockIdx.x * XH_BLOCK + threadIdx.x;
@@ -226,7 +235,17 @@ k_window_nanmean(const float* __restrict__ x, int64_t T, int64_t C, int64_t st, 
     }
     if (sout >= 0 && sout >= t0 - half) {
       const float v = x[sout * st + c];
-      if (v == v) { sum -= (double)v; --cnt; }
+      if (v == v) {
+        sum -= (double)v;
+        --cnt;
+        if (!(fabs((double)v) <= WM_RESUM * fabs(sum))) {  // (also when the sum is no longer a number: an infinity has left)
+          sum = 0.0;
+          for (int64_t s = sout + 1; s <= sin && s < T; ++s) {
+            const float u = x[s * st + c];
+            if (u == u) sum += (double)u;
+          }
+        }
+      }
     }
     // (a window that lost all its samples: the running sum is rounding residue, not data)
     if (cnt == 0) sum = 0.0;

@@ -2,9 +2,13 @@
 //
 // The sample set of doy d is the union of the W day-sets {(year y, doy d + k)} (same decomposition as the multi-year
 // percentile kernels, pdoy.h).  One lane per cell marches over a chunk of doys: every day-set is gathered ONCE (rows
-// resolved with one vector load + readlane, unconditional loads), reduced to (sum, sum of squares, count) of the values
-// shifted by a per-cell pivot K, kept in a ring of W partials; mean = K + S1 / N, var = (S2 - S1^2 / N) / N in fp64 (the
-// shift keeps the one-pass variance well conditioned: |v - K| is of the order of the spread, not of the magnitude).
+// resolved with one vector load + readlane, unconditional loads) and reduced, in two passes over its registers, to
+// (count, mean, M2 = sum of squares about ITS OWN mean), kept in a ring of W partials.  Every doy combines the W partials
+// of its window afresh with the pairwise-variance formula, in fp64:
+//     N = sum n_i,   mean = sum n_i mean_i / N,   M2 = sum (M2_i + n_i (mean_i - mean)^2),   var = M2 / N.
+// There is no shift by a pivot sample and no running window sum: a partial reaches exactly the W doys whose window holds
+// its day-set, so one huge sample (an unmasked fill value) changes those doys and no other, and the variance is a sum of
+// non-negative terms whatever the magnitude of the field (relative error of a few 2^-53 of M2).
 // The generic kernel (reduce2.hip) re-reads every row W times and twice for its two-pass std; it remains the exact path
 // for irregular doys (calendar gaps).
 #include <stdlib.h>
@@ -26,54 +30,51 @@ k_doy_stats_sets(const float* __restrict__ x, int64_t T, int64_t C, int64_t st, 
   constexpr int half = W / 2;
   int d0 = blockIdx.y * chunk, d1 = d0 + chunk;
   if (d1 > ndoy) d1 = ndoy;
-  double s1[W], s2[W];
+  double mu[W], m2[W];
   int n[W];
 #pragma unroll
-  for (int w = 0; w < W; ++w) { s1[w] = 0.0; s2[w] = 0.0; n[w] = 0; }
+  for (int w = 0; w < W; ++w) { mu[w] = 0.0; m2[w] = 0.0; n[w] = 0; }
   float raw[NYP];
-  float K = 0.0f;
-  bool haveK = false;
+  const double inv_ny = 1.0 / (double)nyears;
   auto rows_of = [&](int dn) { return pdoy_row(lane, nyears, ndoy, dn, 0, tbase, nullptr, T, T); };
-  auto reduce_into = [&](double& a1, double& a2, int& an) {
-    if (!haveK) {  // pivot: the first valid value this lane meets
-#pragma unroll
-      for (int y = 0; y < NYP; ++y)
-        if (!haveK && raw[y] == raw[y]) { K = raw[y]; haveK = true; }
-    }
-    double b1 = 0.0, b2 = 0.0;
+  // the day-set in raw[] -> (count, mean, M2 about that mean); an empty day-set is (0, 0, 0).  1 / n is a wave-uniform
+  // constant when every lane's day-set is complete (the usual case; the same quotient either way)
+  auto reduce_into = [&](double& amu, double& am2, int& an) {
+    double b1 = 0.0;
     int bn = 0;
 #pragma unroll
     for (int y = 0; y < NYP; ++y) {
       const float v = raw[y];
       const bool ok = v == v;
-      const double dv = ok ? (double)v - (double)K : 0.0;
-      b1 += dv;
-      b2 += dv * dv;
+      b1 += ok ? (double)v : 0.0;
       bn += ok ? 1 : 0;
     }
-    a1 = b1; a2 = b2; an = bn;
+    const bool allfull = __all(bn == nyears ? 1 : 0) != 0;
+    const double m = b1 * (allfull ? inv_ny : 1.0 / (double)(bn > 0 ? bn : 1));
+    double b2 = 0.0;
+#pragma unroll
+    for (int y = 0; y < NYP; ++y) {
+      const float v = raw[y];
+      const double dv = (v == v) ? (double)v - m : 0.0;
+      b2 += dv * dv;
+    }
+    amu = m; am2 = b2; an = bn;
   };
   // ring[w] = day-set of doy (d - half + w); prologue fills slots 1 .. W-1 for d = d0 - 1
 #pragma unroll
   for (int w = 1; w < W; ++w) {
     pdoy_gather<NYP>(raw, rows_of(d0 - 1 - half + w), x, st, cc);
-    reduce_into(s1[w], s2[w], n[w]);
+    reduce_into(mu[w], m2[w], n[w]);
   }
   pdoy_gather<NYP>(raw, rows_of(d0 + half), x, st, cc);
   int rows_next = rows_of(d0 + half + 1);
   // The ring does not shift: the day loop is unrolled by W and the partial of the day-set that enters at step u of a group
   // lands in the static slot (u + W - 1) % W — the slot of the day-set that leaves (20 64-bit moves per doy before).
-  // Running window sums: RS += entering partial - leaving partial (fp64 drift over a chunk of doys ~1e-15 relative; the
-  // contract is 1e-6).  1 / N is a wave-uniform constant when every lane's window is complete (the usual case), the
-  // standard deviation comes from the hardware fp32 square root: the divide / divide / fp64 sqrt per doy was most of
-  // the VALU work of this (VALU-bound) kernel on short base periods.
+  // 1 / N is a wave-uniform constant when every lane's window is complete (the usual case), the standard deviation comes
+  // from the hardware fp32 square root.
 #pragma unroll
-  for (int w = 0; w < W - 1; ++w) { s1[w] = s1[w + 1]; s2[w] = s2[w + 1]; n[w] = n[w + 1]; }  // prologue slots 1..W-1 -> 0..W-2
-  s1[W - 1] = 0.0; s2[W - 1] = 0.0; n[W - 1] = 0;
-  double RS1 = 0.0, RS2 = 0.0;
-  int RN = 0;
-#pragma unroll
-  for (int w = 0; w < W - 1; ++w) { RS1 += s1[w]; RS2 += s2[w]; RN += n[w]; }
+  for (int w = 0; w < W - 1; ++w) { mu[w] = mu[w + 1]; m2[w] = m2[w + 1]; n[w] = n[w + 1]; }  // prologue slots 1..W-1 -> 0..W-2
+  mu[W - 1] = 0.0; m2[W - 1] = 0.0; n[W - 1] = 0;
   const int nfull = W * nyears;
   const double inv_full = 1.0 / (double)nfull;
   for (int db = d0; db < d1; db += W) {
@@ -82,25 +83,29 @@ k_doy_stats_sets(const float* __restrict__ x, int64_t T, int64_t C, int64_t st, 
       const int d = db + u;
       if (d < d1) {
         const int SLOT = (u + W - 1) % W;  // (compile-time after unrolling)
-        double b1, b2;
-        int bn;
-        reduce_into(b1, b2, bn);
-        RS1 += b1 - s1[SLOT]; RS2 += b2 - s2[SLOT]; RN += bn - n[SLOT];
-        s1[SLOT] = b1; s2[SLOT] = b2; n[SLOT] = bn;
+        reduce_into(mu[SLOT], m2[SLOT], n[SLOT]);
         if (d + 1 < d1) {
           pdoy_gather<NYP>(raw, rows_next, x, st, cc);
           rows_next = rows_of(d + 2 + half);
         }
         if (regular[d]) {
-          const bool allfull = __all(RN == nfull ? 1 : 0) != 0;
+          int N = 0;
+          double S = 0.0;
+#pragma unroll
+          for (int w = 0; w < W; ++w) { N += n[w]; S += (double)n[w] * mu[w]; }
+          const bool allfull = __all(N == nfull ? 1 : 0) != 0;
           float m = xh_nan32(), sd = xh_nan32();
-          if (allfull || RN > 0) {
-            const double invN = allfull ? inv_full : 1.0 / (double)(RN > 0 ? RN : 1);
-            const double mean_s = RS1 * invN;
-            double var = (RS2 - RS1 * mean_s) * invN;
-            var = var > 0.0 ? var : 0.0;
-            m = (float)((double)K + mean_s);
-            sd = __builtin_amdgcn_sqrtf((float)var);
+          if (allfull || N > 0) {
+            const double invN = allfull ? inv_full : 1.0 / (double)(N > 0 ? N : 1);
+            const double mean = S * invN;
+            double M2 = 0.0;
+#pragma unroll
+            for (int w = 0; w < W; ++w) {
+              const double dm = mu[w] - mean;
+              M2 += m2[w] + (double)n[w] * (dm * dm);
+            }
+            m = (float)mean;
+            sd = __builtin_amdgcn_sqrtf((float)(M2 * invN));
           }
           if (active) {
             mean_out[(int64_t)d * C + c] = m;
@@ -115,7 +120,7 @@ k_doy_stats_sets(const float* __restrict__ x, int64_t T, int64_t C, int64_t st, 
 // ONE contiguous year (row of doy index i = t0 + i): the day-sets are single rows, the climatology is a centred,
 // NaN-skipping rolling mean / std over consecutive rows.  Four cells per lane, rows in double-buffered batches of 8
 // (xh_march_rows), the window in a register ring with static slots; mean and population std (two passes over the W
-// values in fp64 — exact, no pivot) per doy.  The per-day-set kernel above moves 256 bytes per wave and row.
+// values in fp64) per doy.  The per-day-set kernel above moves 256 bytes per wave and row.
 template <int W, int VEC>
 __global__ void __launch_bounds__(XH_BLOCK)
 k_doy_stats_year(const float* __restrict__ x, int64_t T, int64_t C, int64_t st, int64_t t0, int ndoy, int chunk,

@@ -284,6 +284,10 @@ UNIT_SIGNATURES: dict[str, list] = {
     # include/units/xclim_hip_distfit.h (xclim_amd/csrc/distfit.hip)
     "xh_dist_fit": [_vp, _vp, _i64, _i64, _i64, _int, _int, _int, _int, _dbl, _vp, _int, _int, _vp, _i64, _vp, _vp, _vp, _i64],
     "xh_dist_eval": [_vp, _int, _int, _vp, _i64, _i64, _vp, _int, _vp, _i64],
+    # include/units/xclim_hip_thermal.h (xclim_amd/csrc/thermal.hip)
+    "xh_esat": [_vp, _vp, _i64, _i64, _i64, _int, _int, _int, _dbl, _dbl, _dbl, _vp, _i64],
+    "xh_thermal_comfort": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _vp, _vp,
+                           _vp, _i64],
 }
 _RESTYPES = {"xh_last_error": C.c_char_p}
 # include/units/xclim_hip_distfit.h: the XH_DIST_* distributions, methods and functions, the XH_DISTFIT_* limit and status bytes
@@ -293,6 +297,15 @@ DIST_METHODS = {"APP": 0, "ML": 1}
 DIST_FUNCS = {"ppf": 0, "isf": 1, "cdf": 2, "pdf": 3}
 DISTFIT_MAX_Q = 16       # XH_DISTFIT_MAX_Q
 DISTFIT_STATUS = {"fitted": 0, "nan": 1, "budget": 2, "support": 3}
+# include/units/xclim_hip_thermal.h: the XH_ESAT_* methods and cases, the XH_THERMAL_* table rows, modes, stats and flag bits
+ESAT_METHODS = {"sonntag90": 0, "goffgratch46": 1, "its90": 2, "tetens30": 3, "wmo08": 4, "buck81": 5, "aerk96": 6, "ecmwf": 7}
+ESAT_NMETHODS = 8        # XH_ESAT_NMETHODS
+ESAT_CASES = {"water": 0, "binary": 1, "interp": 2}
+THERMAL_ROWS = {"sin_dec": 0, "cos_dec": 1, "tan_dec": 2, "h_utc": 3, "interval": 4, "tcorr": 5, "inv_d2": 6}
+THERMAL_NROW = 7         # XH_THERMAL_NROW
+THERMAL_MODES = {"daily": 0, "subdaily": 1}
+THERMAL_STATS = {"sunlit": 0, "instant": 1}
+THERMAL_FLAGS = {"mask_invalid": 1, "wind_cap_min": 2}
 # header under include/units/ -> every integer #define of it, spelled from the mirrors above (tests/test_abi_units_cpu.py compares
 # each header with its entry, so a #define without a mirror, or a mirror with another value, fails there)
 UNIT_DEFINES = {
@@ -300,6 +313,13 @@ UNIT_DEFINES = {
         **{f"XH_DIST_{k.upper()}": v for k, v in DIST_CODES.items()}, "XH_DIST_NDISTS": DIST_NDISTS,
         **{f"XH_DIST_{k}": v for k, v in DIST_METHODS.items()}, **{f"XH_DIST_{k.upper()}": v for k, v in DIST_FUNCS.items()},
         "XH_DISTFIT_MAX_Q": DISTFIT_MAX_Q, **{f"XH_DISTFIT_{k.upper()}": v for k, v in DISTFIT_STATUS.items()}},
+    "xclim_hip_thermal.h": {
+        **{f"XH_ESAT_{k.upper()}": v for k, v in ESAT_METHODS.items()}, "XH_ESAT_NMETHODS": ESAT_NMETHODS,
+        **{f"XH_ESAT_{k.upper()}": v for k, v in ESAT_CASES.items()},
+        **{f"XH_THERMAL_{k.upper()}": v for k, v in THERMAL_ROWS.items()}, "XH_THERMAL_NROW": THERMAL_NROW,
+        **{f"XH_THERMAL_{k.upper()}": v for k, v in THERMAL_MODES.items()},
+        **{f"XH_THERMAL_{k.upper()}": v for k, v in THERMAL_STATS.items()},
+        **{f"XH_THERMAL_{k.upper()}": v for k, v in THERMAL_FLAGS.items()}},
 }
 # the XH_ANALOG_* methods, in the order of the reference's registry
 ANALOG_METHODS = {"seuclidean": 0, "nearest_neighbor": 1, "zech_aslan": 2, "szekely_rizzo": 3, "friedman_rafsky": 4,

@@ -1883,3 +1883,77 @@ def dist_eval(dev: Device, params: DeviceArray, dist: str, func: str, v, *, C_: 
     _ext_call(dev, "xh_dist_eval", capi.DIST_CODES[dist], capi.DIST_FUNCS[func], _vp(params.ptr), C_, ld,
               np_ptr(vs) if len(vs) else _vp(0), len(vs), _vp(out.ptr), C_ if ld_out is None else int(ld_out))
     return out
+
+
+# ---- the thermal-comfort unit (include/units/xclim_hip_thermal.h, xclim_amd/csrc/thermal.hip) -----------------------------
+def esat(dev: Device, tas: DeviceArray, method: str = "sonntag90", case: str = "water", ice_thresh: float = 0.0,
+         water_thresh: float = 273.15, interp_power: float = 1.0, *, C_: int | None = None, ld: int | None = None,
+         out: DeviceArray | None = None, ld_out: int | None = None) -> DeviceArray:
+    """xh_esat: the saturation vapour pressure [Pa] of a (R, C) float32 or float64 field [K], in the field's dtype.  ``method``: a
+    key of ``capi.ESAT_METHODS``; ``case``: a key of ``capi.ESAT_CASES``.  ``C_`` / ``ld`` / ``out`` / ``ld_out``: padded views."""
+    who = "esat"
+    if method not in capi.ESAT_METHODS or case not in capi.ESAT_CASES:
+        raise ValueError(f"{who}: unknown method or case ({method!r}, {case!r})")
+    R, width, f64 = _field(tas)
+    ld = width if ld is None else int(ld)
+    C_ = ld if C_ is None else int(C_)
+    if out is None:
+        ld_out = C_
+        out = dev.empty((R, C_), tas.dtype)
+    _ext_call(dev, "xh_esat", _vp(tas.ptr), R, C_, ld, int(f64), capi.ESAT_METHODS[method], capi.ESAT_CASES[case], float(ice_thresh),
+              float(water_thresh), float(interp_power), _vp(out.ptr), C_ if ld_out is None else int(ld_out))
+    return out
+
+
+THERMAL_FIELDS = ("tas", "hurs", "sfcWind", "mrt", "rsds", "rsus", "rlds", "rlus")
+THERMAL_OUTPUTS = ("utci", "mrt", "csza")
+
+
+def thermal_comfort(dev: Device, fields: dict, rows=None, lat=None, lon=None, *, mode: str = "daily", stat: str = "sunlit",
+                    mask_invalid: bool = True, wind_cap_min: bool = False, outputs=("utci",), shape=None, C_: int | None = None,
+                    ld: int | None = None, outs: dict | None = None, ld_out: int | None = None) -> dict:
+    """xh_thermal_comfort: one launch over the (R, C) device fields of ``fields`` (keys of ``THERMAL_FIELDS``, all float32 or all
+    float64; ``mrt`` given: the radiation fields are not read).  ``rows``: the float64 (``capi.THERMAL_NROW``, R) per-row solar
+    table; ``lat`` / ``lon``: float64 (C), the wrapped latitude and the longitude in rad (host arrays, uploaded per call, or device arrays).  ``outputs``: of ``THERMAL_OUTPUTS``;
+    returns ``{name: DeviceArray (R, C)}``, utci in the fields' dtype, mrt and csza float64.  ``shape``: (R, C, float64?) when no
+    field is passed (csza alone).  ``C_`` / ``ld`` / ``outs`` / ``ld_out``: padded views and output buffers of the caller's."""
+    who = "thermal_comfort"
+    fields = {k: v for k, v in fields.items() if v is not None}
+    if set(fields) - set(THERMAL_FIELDS) or set(outputs) - set(THERMAL_OUTPUTS) or not outputs:
+        raise ValueError(f"{who}: fields of {THERMAL_FIELDS}, outputs of {THERMAL_OUTPUTS}")
+    if mode not in capi.THERMAL_MODES or stat not in capi.THERMAL_STATS:
+        raise ValueError(f"{who}: unknown mode or stat ({mode!r}, {stat!r})")
+    R, width, f64 = _same_fields(who, fields) if fields else shape
+    ld = width if ld is None else int(ld)
+    C_ = ld if C_ is None else int(C_)
+    keep = []
+
+    def table(a, shape_, what):
+        if a is None:
+            return _vp(0)
+        if isinstance(a, DeviceArray):   # a table the caller keeps on the device
+            if np.dtype(a.dtype) != np.float64 or tuple(a.shape) != shape_:
+                raise TypeError(f"{who}: {what} must be a float64 {shape_} device array")
+            return _vp(a.ptr)
+        t = np.ascontiguousarray(a, dtype=np.float64)
+        if t.shape != shape_:
+            raise ValueError(f"{who}: {what} must have the shape {shape_}, got {t.shape}")
+        keep.append(dev.to_device(t))
+        return _vp(keep[-1].ptr)
+
+    d_rows = table(rows, (capi.THERMAL_NROW, R), "rows")
+    d_lat, d_lon = table(lat, (C_,), "lat"), table(lon, (C_,), "lon")
+    outs = dict(outs or {})
+    res = {}
+    for o in outputs:
+        res[o] = outs[o] if o in outs else dev.empty((R, C_), (np.float64 if f64 else np.float32) if o == "utci" else np.float64)
+    flags = (capi.THERMAL_FLAGS["mask_invalid"] if mask_invalid else 0) | (capi.THERMAL_FLAGS["wind_cap_min"] if wind_cap_min else 0)
+
+    def p(d, k):
+        return _vp(d[k].ptr if k in d else 0)
+
+    _ext_call(dev, "xh_thermal_comfort", R, C_, ld, int(f64), p(fields, "tas"), p(fields, "hurs"), p(fields, "sfcWind"), p(fields, "mrt"),
+              p(fields, "rsds"), p(fields, "rsus"), p(fields, "rlds"), p(fields, "rlus"), d_rows, d_lat, d_lon, capi.THERMAL_MODES[mode],
+              capi.THERMAL_STATS[stat], flags, p(res, "utci"), p(res, "mrt"), p(res, "csza"), C_ if ld_out is None else int(ld_out))
+    del keep   # (released to the pool: the stream's order protects the tables of the launch)
+    return res

@@ -127,6 +127,9 @@ _AGRO_MODULES = ("xclim.indices._agro", "xclim.indices")   # indices/__init__.py
 _HYDRO_MODULES = ("xclim.indices._hydrology", "xclim.indices")   # indices/__init__.py: ``from ._hydrology import *``
 _PET_MODULE = "xclim.indices.converters"
 _PET_NAMES = ("potential_evapotranspiration", "water_budget")
+_THERMAL_NAMES = ("saturation_vapor_pressure", "mean_radiant_temperature", "universal_thermal_climate_index")
+_THERMAL_MODULES = ("xclim.indices.converters", "xclim.indices", "xclim.indices._conversion")
+_THERMAL_INDICATORS = {"xclim.indicators.convert._conversion": ("universal_thermal_climate_index", "mean_radiant_temperature")}
 _PET_INDICATORS = {"xclim.indicators.convert._conversion": ("potential_evapotranspiration", "water_budget_from_tas",
                                                            "water_budget")}
 
@@ -314,6 +317,28 @@ def install(env=None, modules=None) -> list[str]:
             patch(_PET_MODULE, name, pet[name])
         by_orig = {id(origs[n]): pet[n] for n in _PET_NAMES}
         for modname, names in _PET_INDICATORS.items():
+            imod = resolve(modname)
+            for name in names:
+                cls = type(getattr(imod, name, None))
+                own = cls.__dict__.get("compute") if imod is not None else None
+                if isinstance(own, staticmethod) and id(own.__func__) in by_orig and cls not in _saved_compute:
+                    _saved_compute[cls] = own
+                    cls.compute = staticmethod(by_orig[id(own.__func__)])
+                    done.append(f"{modname}.{name}.compute")
+    # thermal comfort: the three functions of converters.py, by identity where xclim.indices and xclim.indices._conversion re-export
+    # them, and the ``compute`` of the two Converter indicators that hold them (as the PET indicators above)
+    if cmod is not None and all(hasattr(cmod, n) for n in _THERMAL_NAMES):
+        from .thermal import make_adapters as thermal_adapters
+
+        origs = {n: _saved.get((_PET_MODULE, n), getattr(cmod, n)) for n in _THERMAL_NAMES}
+        th = thermal_adapters(env, origs, getattr(cmod, "_gather_lat", None), getattr(cmod, "_gather_lon", None))
+        for modname in _THERMAL_MODULES:
+            m = resolve(modname)
+            for name in _THERMAL_NAMES:
+                if m is not None and _saved.get((modname, name), getattr(m, name, None)) is origs[name]:
+                    patch(modname, name, th[name])
+        by_orig = {id(origs[n]): th[n] for n in _THERMAL_NAMES}
+        for modname, names in _THERMAL_INDICATORS.items():
             imod = resolve(modname)
             for name in names:
                 cls = type(getattr(imod, name, None))

@@ -288,6 +288,12 @@ UNIT_SIGNATURES: dict[str, list] = {
     "xh_esat": [_vp, _vp, _i64, _i64, _i64, _int, _int, _int, _dbl, _dbl, _dbl, _vp, _i64],
     "xh_thermal_comfort": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _vp, _vp,
                            _vp, _i64],
+    # include/units/xclim_hip_robust.h (xclim_amd/csrc/robust.hip)
+    "xh_change_test": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _int, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                       _vp, _vp, _i64],
+    "xh_robust_fractions": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _int, _int, _dbl, _vp, _i64],
+    "xh_robust_coefficient": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp, _vp, _vp],
+    "xh_ar6_gamma": [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _vp, _int, _vp, _i64, _dbl, _vp, _i64],
 }
 _RESTYPES = {"xh_last_error": C.c_char_p}
 # include/units/xclim_hip_distfit.h: the XH_DIST_* distributions, methods and functions, the XH_DISTFIT_* limit and status bytes
@@ -306,6 +312,16 @@ THERMAL_NROW = 7         # XH_THERMAL_NROW
 THERMAL_MODES = {"daily": 0, "subdaily": 1}
 THERMAL_STATS = {"sunlit": 0, "instant": 1}
 THERMAL_FLAGS = {"mask_invalid": 1, "wind_cap_min": 2}
+# include/units/xclim_hip_robust.h: the XH_CT_* tests, status bytes and limits, the XH_RF_* output rows and threshold kinds
+CT_TESTS = {"moments": 0, "ttest": 1, "welch": 2, "mwu": 3, "bf": 4}
+CT_NTESTS = 5            # XH_CT_NTESTS
+CT_STATUS = {"done": 0, "nan": 1, "exact_pending": 2}
+CT_MAX_T = 512           # XH_CT_MAX_T
+CT_LDS_SLOTS = 64        # XH_CT_LDS_SLOTS
+RF_ROWS = {"changed": 0, "positive": 1, "changed_positive": 2, "negative": 3, "changed_negative": 4, "valid": 5, "agree": 6}
+RF_NFRAC = 7             # XH_RF_NFRAC
+RF_THRESH = {"none": 0, "abs": 1, "rel": 2}
+RC_MAX_POOL = 8192       # XH_RC_MAX_POOL
 # header under include/units/ -> every integer #define of it, spelled from the mirrors above (tests/test_abi_units_cpu.py compares
 # each header with its entry, so a #define without a mirror, or a mirror with another value, fails there)
 UNIT_DEFINES = {
@@ -320,6 +336,11 @@ UNIT_DEFINES = {
         **{f"XH_THERMAL_{k.upper()}": v for k, v in THERMAL_MODES.items()},
         **{f"XH_THERMAL_{k.upper()}": v for k, v in THERMAL_STATS.items()},
         **{f"XH_THERMAL_{k.upper()}": v for k, v in THERMAL_FLAGS.items()}},
+    "xclim_hip_robust.h": {
+        **{f"XH_CT_{k.upper()}": v for k, v in CT_TESTS.items()}, "XH_CT_NTESTS": CT_NTESTS,
+        **{f"XH_CT_{k.upper()}": v for k, v in CT_STATUS.items()}, "XH_CT_MAX_T": CT_MAX_T, "XH_CT_LDS_SLOTS": CT_LDS_SLOTS,
+        **{f"XH_RF_{k.upper()}": v for k, v in RF_ROWS.items()}, "XH_RF_NFRAC": RF_NFRAC,
+        **{f"XH_RF_THRESH_{k.upper()}": v for k, v in RF_THRESH.items()}, "XH_RC_MAX_POOL": RC_MAX_POOL},
 }
 # the XH_ANALOG_* methods, in the order of the reference's registry
 ANALOG_METHODS = {"seuclidean": 0, "nearest_neighbor": 1, "zech_aslan": 2, "szekely_rizzo": 3, "friedman_rafsky": 4,

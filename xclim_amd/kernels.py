@@ -1957,3 +1957,126 @@ def thermal_comfort(dev: Device, fields: dict, rows=None, lat=None, lon=None, *,
               capi.THERMAL_STATS[stat], flags, p(res, "utci"), p(res, "mrt"), p(res, "csza"), C_ if ld_out is None else int(ld_out))
     del keep   # (released to the pool: the stream's order protects the tables of the launch)
     return res
+
+
+# ---- the change-robustness unit (include/units/xclim_hip_robust.h, xclim_amd/csrc/robust.hip) -----------------------------
+CT_OUTPUTS = ("delta", "mean_ref", "n_fut", "n_ref", "stat", "df", "pvals", "status")
+_CT_DTYPES = {"delta": np.float64, "mean_ref": np.float64, "n_fut": np.int32, "n_ref": np.int32, "stat": np.float64, "df": np.float64,
+              "pvals": np.float64, "status": np.uint8}
+
+
+def change_test(dev: Device, fut: DeviceArray, ref: DeviceArray, test: str = "moments", sf=None, *, C_: int | None = None,
+                ld_fut: int | None = None, ld_ref: int | None = None, outs: dict | None = None, ld_out: int | None = None) -> dict:
+    """xh_change_test: ``fut`` (R, T1, C) and ``ref`` (R, T2, C) or (T2, C), both float32 or both float64 device arrays; ``test``
+    a key of ``capi.CT_TESTS``; ``sf``: the host table of the exact Mann-Whitney route (``ensembles.mwu_exact_sf``), needed where
+    a length is at most 8.  Returns ``{name: DeviceArray (R, C)}`` for ``CT_OUTPUTS`` (the first four for "moments").  ``C_`` /
+    ``ld_*`` / ``outs`` / ``ld_out``: the cells and row pitches of padded views and output buffers of the caller's."""
+    who = "change_test"
+    if test not in capi.CT_TESTS:
+        raise ValueError(f"{who}: unknown test {test!r}")
+    if len(fut.shape) != 3 or len(ref.shape) not in (2, 3) or np.dtype(fut.dtype) != np.dtype(ref.dtype):
+        raise TypeError(f"{who}: fut (R, T1, C) and ref (R, T2, C) or (T2, C) of one dtype, got {fut.shape} {fut.dtype}, {ref.shape} {ref.dtype}")
+    if np.dtype(fut.dtype) not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise TypeError(f"{who}: float32 or float64 fields, got {np.dtype(fut.dtype).name}")
+    R, T1, width = (int(v) for v in fut.shape)
+    T2 = int(ref.shape[-2])
+    if (ld_ref is None and int(ref.shape[-1]) != width) or (len(ref.shape) == 3 and int(ref.shape[0]) != R):
+        raise ValueError(f"{who}: ref {ref.shape} does not match fut {fut.shape}")
+    ld_fut = width if ld_fut is None else int(ld_fut)
+    ld_ref = int(ref.shape[-1]) if ld_ref is None else int(ld_ref)
+    C_ = width if C_ is None else int(C_)
+    names = CT_OUTPUTS[:4] if test == "moments" else CT_OUTPUTS
+    outs = dict(outs or {})
+    res = {k: outs[k] if k in outs else dev.empty((R, C_), _CT_DTYPES[k]) for k in names}
+    table = None if sf is None else np.ascontiguousarray(sf, dtype=np.float64).reshape(-1)
+
+    def p(k):
+        return _vp(res[k].ptr if k in res else 0)
+
+    _ext_call(dev, "xh_change_test", _vp(fut.ptr), _vp(ref.ptr), R, T1, T2, C_, ld_fut, T1 * ld_fut, ld_ref,
+              T2 * ld_ref if len(ref.shape) == 3 else 0, int(np.dtype(fut.dtype) == np.float64), capi.CT_TESTS[test],
+              np_ptr(table) if table is not None else _vp(0), 0 if table is None else table.size, *(p(k) for k in CT_OUTPUTS),
+              C_ if ld_out is None else int(ld_out))
+    return res
+
+
+def robust_fractions(dev: Device, delta: DeviceArray, weights, *, changed: DeviceArray | None = None, valid: DeviceArray | None = None,
+                     mean_ref: DeviceArray | None = None, strict_sign: bool = True, abs_thresh=None, rel_thresh=None,
+                     C_: int | None = None, ld: int | None = None, out: DeviceArray | None = None, ld_out: int | None = None) -> DeviceArray:
+    """xh_robust_fractions: the seven fractions (``capi.RF_ROWS``) of the float64 (R, C) ``delta``; ``changed`` / ``valid`` uint8
+    (R, C) or None, ``weights`` host (R).  ``abs_thresh`` / ``rel_thresh`` (with ``mean_ref``) decide ``changed`` in the kernel.
+    Returns float64 (7, C).  ``C_`` / ``ld`` / ``out`` / ``ld_out``: padded views."""
+    who = "robust_fractions"
+    if np.dtype(delta.dtype) != np.float64 or len(delta.shape) != 2:
+        raise TypeError(f"{who}: delta must be float64 (R, C), got {np.dtype(delta.dtype).name} {delta.shape}")
+    for name, m in (("changed", changed), ("valid", valid)):
+        if m is not None and (np.dtype(m.dtype) != np.uint8 or tuple(m.shape) != tuple(delta.shape)):
+            raise TypeError(f"{who}: {name} must be uint8 {tuple(delta.shape)}")
+    if mean_ref is not None and (np.dtype(mean_ref.dtype) != np.float64 or tuple(mean_ref.shape) != tuple(delta.shape)):
+        raise TypeError(f"{who}: mean_ref must be float64 {tuple(delta.shape)}")
+    R, width = (int(v) for v in delta.shape)
+    w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+    if w.size != R:
+        raise ValueError(f"{who}: {R} weights needed, got {w.size}")
+    if abs_thresh is not None and rel_thresh is not None:
+        raise ValueError(f"{who}: abs_thresh and rel_thresh are both given")
+    kind = "abs" if abs_thresh is not None else "rel" if rel_thresh is not None else "none"
+    thresh = float(abs_thresh if kind == "abs" else rel_thresh if kind == "rel" else 0.0)
+    ld = width if ld is None else int(ld)
+    C_ = ld if C_ is None else int(C_)
+    if out is None:
+        ld_out = C_
+        out = dev.empty((capi.RF_NFRAC, C_), np.float64)
+    _ext_call(dev, "xh_robust_fractions", _vp(delta.ptr), _vp(changed.ptr if changed is not None else 0),
+              _vp(valid.ptr if valid is not None else 0), _vp(mean_ref.ptr if mean_ref is not None else 0), R, C_, ld, np_ptr(w),
+              int(bool(strict_sign)), capi.RF_THRESH[kind], thresh, _vp(out.ptr), C_ if ld_out is None else int(ld_out))
+    return out
+
+
+def robust_coefficient(dev: Device, fut: DeviceArray, ref: DeviceArray, *, C_: int | None = None, ld_fut: int | None = None,
+                       ld_ref: int | None = None, outs: dict | None = None, parts: bool = False):
+    """xh_robust_coefficient: ``fut`` (R, T1, C) and ``ref`` (T2, C), both float32 or both float64; returns the float64 (C)
+    coefficient, with ``parts`` the tuple (R, A1, A2).  ``C_`` / ``ld_*`` / ``outs`` (keys out, a1, a2): padded views."""
+    who = "robust_coefficient"
+    if len(fut.shape) != 3 or len(ref.shape) != 2 or np.dtype(fut.dtype) != np.dtype(ref.dtype):
+        raise TypeError(f"{who}: fut (R, T1, C) and ref (T2, C) of one dtype, got {fut.shape} {fut.dtype}, {ref.shape} {ref.dtype}")
+    if np.dtype(fut.dtype) not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise TypeError(f"{who}: float32 or float64 fields, got {np.dtype(fut.dtype).name}")
+    R, T1, width = (int(v) for v in fut.shape)
+    T2 = int(ref.shape[0])
+    if ld_ref is None and int(ref.shape[1]) != width:
+        raise ValueError(f"{who}: ref {ref.shape} does not match fut {fut.shape}")
+    ld_fut = width if ld_fut is None else int(ld_fut)
+    ld_ref = width if ld_ref is None else int(ld_ref)
+    C_ = width if C_ is None else int(C_)
+    outs = dict(outs or {})
+    names = ("out", "a1", "a2") if parts else ("out",)
+    res = {k: outs[k] if k in outs else dev.empty((C_,), np.float64) for k in names}
+    _ext_call(dev, "xh_robust_coefficient", _vp(fut.ptr), _vp(ref.ptr), R, T1, T2, C_, ld_fut, T1 * ld_fut, ld_ref,
+              int(np.dtype(fut.dtype) == np.float64), _vp(res["out"].ptr), _vp(res["a1"].ptr if parts else 0),
+              _vp(res["a2"].ptr if parts else 0))
+    return (res["out"], res["a1"], res["a2"]) if parts else res["out"]
+
+
+def ar6_gamma(dev: Device, y: DeviceArray, x, deg: int, factor: float, seg=None, *, C_: int | None = None, ld: int | None = None,
+              out: DeviceArray | None = None, ld_out: int | None = None) -> DeviceArray:
+    """xh_ar6_gamma: ``y`` (R, T, C) annual values, float32 or float64; ``x`` host (T) days; ``deg`` 1 or 2; ``seg`` the host offsets
+    of the blocks or None.  Returns float64 (R, C): ``factor`` * std of the detrended values (or of their block means).  ``C_`` /
+    ``ld`` / ``out`` / ``ld_out``: padded views."""
+    who = "ar6_gamma"
+    if len(y.shape) != 3 or np.dtype(y.dtype) not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise TypeError(f"{who}: y must be float32 or float64 (R, T, C), got {np.dtype(y.dtype).name} {y.shape}")
+    R, T, width = (int(v) for v in y.shape)
+    xs = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+    if xs.size != T:
+        raise ValueError(f"{who}: {T} abscissa values needed, got {xs.size}")
+    sg = None if seg is None else np.ascontiguousarray(seg, dtype=np.int64).reshape(-1)
+    ld = width if ld is None else int(ld)
+    C_ = ld if C_ is None else int(C_)
+    if out is None:
+        ld_out = C_
+        out = dev.empty((R, C_), np.float64)
+    _ext_call(dev, "xh_ar6_gamma", _vp(y.ptr), R, T, C_, ld, T * ld, int(np.dtype(y.dtype) == np.float64), np_ptr(xs), int(deg),
+              np_ptr(sg) if sg is not None else _vp(0), 0 if sg is None else sg.size - 1, float(factor), _vp(out.ptr),
+              C_ if ld_out is None else int(ld_out))
+    return out

@@ -161,7 +161,7 @@ def install(env=None, modules=None) -> list[str]:
     by default the real packages are used.  Functions the HIP path does not serve are forwarded to the saved originals."""
     import importlib
 
-    from . import agro, analog, anuclim, dataflags, hydrology, phase, rainseason
+    from . import agro, analog, anuclim, dataflags, ensembles, hydrology, phase, rainseason
     from .xr_adapter import make_wrappers
 
     env = env or real_env()
@@ -306,6 +306,9 @@ def install(env=None, modules=None) -> list[str]:
     install_mirror(("xclim.indices._threshold", "xclim.indices"), phase.threshold)
     # spatial_analogs of analog.py: one launch with a lane per candidate cell instead of a Python call per cell
     install_mirror(("xclim.analog",), analog)
+    # robustness_fractions and robustness_coefficient of ensembles/_robustness.py: one launch per test instead of a scipy call per
+    # (cell, realization); robustness_categories is a handful of xarray comparisons and stays xclim's
+    install_mirror(("xclim.ensembles._robustness", "xclim.ensembles"), ensembles, "xr", "gen_call_string", "SIGNIFICANCE_TESTS")
     cmod = resolve(_PET_MODULE)
     if cmod is not None and all(hasattr(cmod, n) for n in _PET_NAMES):
         from .converters import make_adapters as pet_adapters

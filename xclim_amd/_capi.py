@@ -294,6 +294,10 @@ UNIT_SIGNATURES: dict[str, list] = {
     "xh_robust_fractions": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _int, _int, _dbl, _vp, _i64],
     "xh_robust_coefficient": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp, _vp, _vp],
     "xh_ar6_gamma": [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _vp, _int, _vp, _i64, _dbl, _vp, _i64],
+    # include/units/xclim_hip_humidity.h (xclim_amd/csrc/humidity.hip)
+    "xh_air_moisture": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _dbl, _dbl, _dbl, _int, _int, _int, _int,
+                        _int, _vp, _i64],
+    "xh_wind_map": [_vp, _int, _i64, _i64, _i64, _int, _vp, _vp, _vp, _int, _vp, _vp, _i64],
 }
 _RESTYPES = {"xh_last_error": C.c_char_p}
 # include/units/xclim_hip_distfit.h: the XH_DIST_* distributions, methods and functions, the XH_DISTFIT_* limit and status bytes
@@ -322,6 +326,16 @@ RF_ROWS = {"changed": 0, "positive": 1, "changed_positive": 2, "negative": 3, "c
 RF_NFRAC = 7             # XH_RF_NFRAC
 RF_THRESH = {"none": 0, "abs": 1, "rel": 2}
 RC_MAX_POOL = 8192       # XH_RC_MAX_POOL
+# include/units/xclim_hip_humidity.h: the XH_AM_* outputs, the XH_RH_* / XH_INVALID_* / XH_DEW_* choices, the XH_WIND_* operations and flags
+AM_OUTPUTS = {"esat": 0, "vp": 1, "vpd": 2, "hurs": 3, "huss": 4, "huss_dew": 5, "tdps": 6, "humidex": 7, "heat_index": 8}
+AM_NOUT = 9              # XH_AM_NOUT
+RH_METHODS = {"esat": 0, "bohren98": 1}
+INVALID_RULES = {"none": 0, "clip": 1, "mask": 2}
+DEW_METHODS = {"tetens30": 0, "wmo08": 1, "buck81": 2, "aerk96": 3}
+WIND_OPS = {"from_uv": 0, "to_uv": 1, "chill": 2, "power": 3}
+WIND_NOPS = 4            # XH_WIND_NOPS
+WIND_FLAGS = {"celsius": 1, "kmh": 2, "us": 4, "mask_invalid": 8}
+WIND_NPAR = 3            # XH_WIND_NPAR
 # header under include/units/ -> every integer #define of it, spelled from the mirrors above (tests/test_abi_units_cpu.py compares
 # each header with its entry, so a #define without a mirror, or a mirror with another value, fails there)
 UNIT_DEFINES = {
@@ -341,6 +355,12 @@ UNIT_DEFINES = {
         **{f"XH_CT_{k.upper()}": v for k, v in CT_STATUS.items()}, "XH_CT_MAX_T": CT_MAX_T, "XH_CT_LDS_SLOTS": CT_LDS_SLOTS,
         **{f"XH_RF_{k.upper()}": v for k, v in RF_ROWS.items()}, "XH_RF_NFRAC": RF_NFRAC,
         **{f"XH_RF_THRESH_{k.upper()}": v for k, v in RF_THRESH.items()}, "XH_RC_MAX_POOL": RC_MAX_POOL},
+    "xclim_hip_humidity.h": {
+        **{f"XH_AM_{k.upper()}": v for k, v in AM_OUTPUTS.items()}, "XH_AM_NOUT": AM_NOUT,
+        **{f"XH_RH_{k.upper()}": v for k, v in RH_METHODS.items()}, **{f"XH_INVALID_{k.upper()}": v for k, v in INVALID_RULES.items()},
+        **{f"XH_DEW_{k.upper()}": v for k, v in DEW_METHODS.items()},
+        **{f"XH_WIND_{k.upper()}": v for k, v in WIND_OPS.items()}, "XH_WIND_NOPS": WIND_NOPS,
+        **{f"XH_WIND_{k.upper()}": v for k, v in WIND_FLAGS.items()}, "XH_WIND_NPAR": WIND_NPAR},
 }
 # the XH_ANALOG_* methods, in the order of the reference's registry
 ANALOG_METHODS = {"seuclidean": 0, "nearest_neighbor": 1, "zech_aslan": 2, "szekely_rizzo": 3, "friedman_rafsky": 4,

@@ -1959,8 +1959,69 @@ def thermal_comfort(dev: Device, fields: dict, rows=None, lat=None, lon=None, *,
     return res
 
 
+# ---- the humidity, heat-stress and wind unit (include/units/xclim_hip_humidity.h, xclim_amd/csrc/humidity.hip) -------------
+AM_FIELDS = ("tas", "tdps", "hurs", "huss", "ps")
+
+
+def air_moisture(dev: Device, fields: dict, outputs, *, celsius: bool = False, method: str = "sonntag90", case: str = "water",
+                 ice_thresh: float = 0.0, water_thresh: float = 273.15, interp_power: float = 1.0, rh_method: str = "esat",
+                 invalid_rh: str = "clip", invalid_q: str = "none", dew_method: str = "buck81", dew_variant: str = "water",
+                 C_: int | None = None, ld: int | None = None, outs: dict | None = None, ld_out: int | None = None) -> dict:
+    """xh_air_moisture: one launch over the (R, C) device fields of ``fields`` (keys of ``AM_FIELDS``, all float32 or all float64)
+    for the ``outputs`` (keys of ``capi.AM_OUTPUTS``); returns ``{name: DeviceArray (R, C)}`` in the fields' dtype.  ``celsius``:
+    tas and tdps are in degC.  ``C_`` / ``ld`` / ``outs`` / ``ld_out``: padded views and output buffers of the caller's."""
+    who = "air_moisture"
+    fields = {k: v for k, v in fields.items() if v is not None}
+    outputs = tuple(outputs)
+    if set(fields) - set(AM_FIELDS) or set(outputs) - set(capi.AM_OUTPUTS) or not fields:
+        raise ValueError(f"{who}: fields of {AM_FIELDS}, outputs of {tuple(capi.AM_OUTPUTS)}")
+    if method not in capi.ESAT_METHODS or case not in capi.ESAT_CASES:
+        raise ValueError(f"{who}: unknown method or case ({method!r}, {case!r})")
+    if dew_variant not in ("water", "ice"):
+        raise ValueError(f"{who}: dew_variant must be 'water' or 'ice', got {dew_variant!r}")
+    R, width, f64 = _same_fields(who, fields)
+    ld = width if ld is None else int(ld)
+    C_ = ld if C_ is None else int(C_)
+    outs = dict(outs or {})
+    res = {o: outs[o] if o in outs else dev.empty((R, C_), np.float64 if f64 else np.float32) for o in outputs}
+    ptrs = np.zeros(capi.AM_NOUT, np.uint64)
+    for o, v in res.items():
+        ptrs[capi.AM_OUTPUTS[o]] = v.ptr
+
+    def p(k):
+        return _vp(fields[k].ptr if k in fields else 0)
+
+    _ext_call(dev, "xh_air_moisture", R, C_, ld, int(f64), p("tas"), p("tdps"), p("hurs"), p("huss"), p("ps"), int(bool(celsius)),
+              capi.ESAT_METHODS[method], capi.ESAT_CASES[case], float(ice_thresh), float(water_thresh), float(interp_power),
+              capi.RH_METHODS[rh_method], capi.INVALID_RULES[invalid_rh], capi.INVALID_RULES[invalid_q], capi.DEW_METHODS[dew_method],
+              int(dew_variant == "ice"), np_ptr(ptrs), C_ if ld_out is None else int(ld_out))
+    return res
+
+
+def wind_map(dev: Device, op: str, a: DeviceArray, b: DeviceArray | None = None, par=None, *, flags=(), outputs=(0,),
+             C_: int | None = None, ld: int | None = None, outs: dict | None = None, ld_out: int | None = None) -> dict:
+    """xh_wind_map: the operation ``op`` (a key of ``capi.WIND_OPS``) on the (R, C) device fields ``a`` and ``b`` of one dtype;
+    ``par``: its host parameters, ``flags``: names of ``capi.WIND_FLAGS``, ``outputs``: of 0 and 1.  Returns ``{0 / 1: DeviceArray
+    (R, C)}`` in the fields' dtype.  ``C_`` / ``ld`` / ``outs`` / ``ld_out``: padded views and output buffers of the caller's."""
+    who = "wind_map"
+    if op not in capi.WIND_OPS or set(outputs) - {0, 1} or not outputs:
+        raise ValueError(f"{who}: op of {tuple(capi.WIND_OPS)}, outputs of 0 and 1")
+    R, width, f64 = _same_fields(who, {"a": a} if b is None else {"a": a, "b": b})
+    ld = width if ld is None else int(ld)
+    C_ = ld if C_ is None else int(C_)
+    outs = dict(outs or {})
+    res = {o: outs[o] if o in outs else dev.empty((R, C_), np.float64 if f64 else np.float32) for o in outputs}
+    pv = np.zeros(capi.WIND_NPAR)
+    if par is not None:
+        pv[:len(par)] = par
+    _ext_call(dev, "xh_wind_map", capi.WIND_OPS[op], R, C_, ld, int(f64), _vp(a.ptr), _vp(b.ptr if b is not None else 0), np_ptr(pv),
+              sum(capi.WIND_FLAGS[f] for f in flags), _vp(res[0].ptr if 0 in res else 0), _vp(res[1].ptr if 1 in res else 0),
+              C_ if ld_out is None else int(ld_out))
+    return res
+
+
 # ---- the change-robustness unit (include/units/xclim_hip_robust.h, xclim_amd/csrc/robust.hip) -----------------------------
-CT_OUTPUTS = ("delta", "mean_ref", "n_fut", "n_ref", "stat", "df", "pvals", "status")
+CT_OUTPUTS =("delta", "mean_ref", "n_fut", "n_ref", "stat", "df", "pvals", "status")
 _CT_DTYPES = {"delta": np.float64, "mean_ref": np.float64, "n_fut": np.int32, "n_ref": np.int32, "stat": np.float64, "df": np.float64,
               "pvals": np.float64, "status": np.uint8}
 

@@ -130,6 +130,11 @@ _PET_NAMES = ("potential_evapotranspiration", "water_budget")
 _THERMAL_NAMES = ("saturation_vapor_pressure", "mean_radiant_temperature", "universal_thermal_climate_index")
 _THERMAL_MODULES = ("xclim.indices.converters", "xclim.indices", "xclim.indices._conversion")
 _THERMAL_INDICATORS = {"xclim.indicators.convert._conversion": ("universal_thermal_climate_index", "mean_radiant_temperature")}
+# indicators/convert/_conversion.py:66-413: the Converter indicators whose ``compute`` is one of humidity.ADAPTED
+_HUMIDITY_INDICATORS = {"xclim.indicators.convert._conversion": (
+    "humidex", "heat_index", "wind_speed_from_vector", "wind_vector_from_speed", "wind_power_potential", "relative_humidity_from_dewpoint",
+    "relative_humidity", "specific_humidity", "specific_humidity_from_dewpoint", "dewpoint_from_specific_humidity", "vapor_pressure",
+    "vapor_pressure_deficit", "wind_chill_index")}
 _PET_INDICATORS = {"xclim.indicators.convert._conversion": ("potential_evapotranspiration", "water_budget_from_tas",
                                                            "water_budget")}
 
@@ -342,6 +347,29 @@ def install(env=None, modules=None) -> list[str]:
                     patch(modname, name, th[name])
         by_orig = {id(origs[n]): th[n] for n in _THERMAL_NAMES}
         for modname, names in _THERMAL_INDICATORS.items():
+            imod = resolve(modname)
+            for name in names:
+                cls = type(getattr(imod, name, None))
+                own = cls.__dict__.get("compute") if imod is not None else None
+                if isinstance(own, staticmethod) and id(own.__func__) in by_orig and cls not in _saved_compute:
+                    _saved_compute[cls] = own
+                    cls.compute = staticmethod(by_orig[id(own.__func__)])
+                    done.append(f"{modname}.{name}.compute")
+    # the humidity, heat-stress and wind conversions: the twelve functions of converters.py (only where it holds all of them), by
+    # identity where xclim.indices and xclim.indices._conversion re-export them, and the ``compute`` of the Converter indicators that
+    # hold them (both relative_humidity indicators hold the one function)
+    from . import humidity
+
+    if cmod is not None and all(hasattr(cmod, n) for n in humidity.ADAPTED):
+        origs = {n: _saved.get((_PET_MODULE, n), getattr(cmod, n)) for n in humidity.ADAPTED}
+        hum = humidity.make_adapters(env, origs)
+        for modname in _THERMAL_MODULES:
+            m = resolve(modname)
+            for name in humidity.ADAPTED:
+                if m is not None and _saved.get((modname, name), getattr(m, name, None)) is origs[name]:
+                    patch(modname, name, hum[name])
+        by_orig = {id(origs[n]): hum[n] for n in humidity.ADAPTED}
+        for modname, names in _HUMIDITY_INDICATORS.items():
             imod = resolve(modname)
             for name in names:
                 cls = type(getattr(imod, name, None))

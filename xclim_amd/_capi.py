@@ -298,6 +298,11 @@ UNIT_SIGNATURES: dict[str, list] = {
     "xh_air_moisture": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _dbl, _dbl, _dbl, _int, _int, _int, _int,
                         _int, _vp, _i64],
     "xh_wind_map": [_vp, _int, _i64, _i64, _i64, _int, _vp, _vp, _vp, _int, _vp, _vp, _i64],
+    # include/units/xclim_hip_partition.h (xclim_amd/csrc/partition.hip)
+    "xh_partition_smooth": [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _int, _vp, _int, _int, _int, _int, _i64, _i64, _vp, _vp, _i64,
+                            _i64, _vp, _vp, _i64, _vp],
+    "xh_partition_components": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _int, _vp, _int, _int, _i64, _vp, _vp, _i64, _vp],
+    "xh_ensemble_stats": [_vp, _vp, _i64, _i64, _i64, _int, _vp, _int, _vp, _i64],
 }
 _RESTYPES = {"xh_last_error": C.c_char_p}
 # include/units/xclim_hip_distfit.h: the XH_DIST_* distributions, methods and functions, the XH_DISTFIT_* limit and status bytes
@@ -336,6 +341,22 @@ WIND_OPS = {"from_uv": 0, "to_uv": 1, "chill": 2, "power": 3}
 WIND_NOPS = 4            # XH_WIND_NOPS
 WIND_FLAGS = {"celsius": 1, "kmh": 2, "us": 4, "mask_invalid": 8}
 WIND_NPAR = 3            # XH_WIND_NPAR
+# include/units/xclim_hip_partition.h: the XH_PT_* limits, rolling statistics, status bytes, baselines, rules, weights and
+# variability rules, the XH_ES_* output rows
+PT_MAX_T = 512           # XH_PT_MAX_T
+PT_MAX_DEG = 4           # XH_PT_MAX_DEG
+PT_ROLL = {"mean": 0, "var": 1}
+PT_STATUS = {"fitted": 0, "allnan": 1, "illposed": 2}
+PT_BASE = {"none": 0, "sub": 1, "div": 2}
+PT_MAX_AXES = 4          # XH_PT_MAX_AXES
+PT_MAX_AXIS = 64         # XH_PT_MAX_AXIS
+PT_MAX_MEMBERS = 4096    # XH_PT_MAX_MEMBERS
+PT_MAX_COMP = 8          # XH_PT_MAX_COMP
+PT_RULES = {"var_then_mean": 0, "mean_then_var": 1}
+PT_WEIGHTS = {"none": 0, "count": 1, "user": 2}
+PT_VARIAB = {"mean_all": 0, "hs": 1}
+ES_ROWS = {"mean": 0, "std": 1, "max": 2, "min": 3}
+ES_NSTAT = 4             # XH_ES_NSTAT
 # header under include/units/ -> every integer #define of it, spelled from the mirrors above (tests/test_abi_units_cpu.py compares
 # each header with its entry, so a #define without a mirror, or a mirror with another value, fails there)
 UNIT_DEFINES = {
@@ -361,6 +382,13 @@ UNIT_DEFINES = {
         **{f"XH_DEW_{k.upper()}": v for k, v in DEW_METHODS.items()},
         **{f"XH_WIND_{k.upper()}": v for k, v in WIND_OPS.items()}, "XH_WIND_NOPS": WIND_NOPS,
         **{f"XH_WIND_{k.upper()}": v for k, v in WIND_FLAGS.items()}, "XH_WIND_NPAR": WIND_NPAR},
+    "xclim_hip_partition.h": {
+        "XH_PT_MAX_T": PT_MAX_T, "XH_PT_MAX_DEG": PT_MAX_DEG, **{f"XH_PT_ROLL_{k.upper()}": v for k, v in PT_ROLL.items()},
+        **{f"XH_PT_{k.upper()}": v for k, v in PT_STATUS.items()}, **{f"XH_PT_BASE_{k.upper()}": v for k, v in PT_BASE.items()},
+        "XH_PT_MAX_AXES": PT_MAX_AXES, "XH_PT_MAX_AXIS": PT_MAX_AXIS, "XH_PT_MAX_MEMBERS": PT_MAX_MEMBERS, "XH_PT_MAX_COMP": PT_MAX_COMP,
+        **{f"XH_PT_{k.upper()}": v for k, v in PT_RULES.items()}, **{f"XH_PT_W_{k.upper()}": v for k, v in PT_WEIGHTS.items()},
+        **{f"XH_PT_VARIAB_{k.upper()}": v for k, v in PT_VARIAB.items()},
+        **{f"XH_ES_{k.upper()}": v for k, v in ES_ROWS.items()}, "XH_ES_NSTAT": ES_NSTAT},
 }
 # the XH_ANALOG_* methods, in the order of the reference's registry
 ANALOG_METHODS = {"seuclidean": 0, "nearest_neighbor": 1, "zech_aslan": 2, "szekely_rizzo": 3, "friedman_rafsky": 4,

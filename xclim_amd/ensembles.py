@@ -23,6 +23,9 @@ from . import _capi as capi
 from . import kernels as K
 from ._capi import DeviceArray, get_device, handle_float64
 from .fields import NotServed
+from .partitioning import (HS_COMPONENTS, LS_COMPONENTS, ensemble_mean_std_max_min, fractional_uncertainty,  # noqa: F401
+                           general_components, general_partition, hawkins_sutton, hawkins_sutton_09_weighting, lafferty_sriver,
+                           poly_smooth)
 
 # _base.py:21-28
 _quantile_params = {

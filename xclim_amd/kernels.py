@@ -2141,3 +2141,121 @@ def ar6_gamma(dev: Device, y: DeviceArray, x, deg: int, factor: float, seg=None,
               np_ptr(sg) if sg is not None else _vp(0), 0 if sg is None else sg.size - 1, float(factor), _vp(out.ptr),
               C_ if ld_out is None else int(ld_out))
     return out
+
+
+# ---- the uncertainty-partitioning unit (include/units/xclim_hip_partition.h, xclim_amd/csrc/partition.hip) ----------------
+PT_SMOOTH_OUTPUTS = ("sm", "roll", "n_valid", "status", "flag")
+
+
+def _float_field(who: str, a: DeviceArray, ndim: int, what: str):
+    if len(a.shape) != ndim or np.dtype(a.dtype) not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise TypeError(f"{who}: {what} must be a float32 or float64 array of {ndim} dimensions, got {np.dtype(a.dtype).name} {a.shape}")
+
+
+def partition_smooth(dev: Device, y: DeviceArray | None, q=None, *, sm_in: DeviceArray | None = None, window: int = 11, stat: str = "var",
+                     baseline=None, kind: str = "+", outputs=PT_SMOOTH_OUTPUTS, C_: int | None = None, ld: int | None = None,
+                     stride_n: int | None = None, outs: dict | None = None, ld_out: int | None = None, stride_n_out: int | None = None,
+                     ld_nc: int | None = None) -> dict:
+    """xh_partition_smooth: ``y`` (T, N, C) float32 or float64; ``q`` the host basis (T, deg + 1), or ``sm_in`` (T, N, C) of y's
+    dtype instead of a fit; ``window`` / ``stat`` (10, "mean") or (11, "var"); ``baseline`` a row range (b0, b1) with ``kind`` "+"
+    or "*".  Returns ``{name: DeviceArray}`` for the requested ``outputs``: sm and roll float64 (T, N, C), n_valid int32 and
+    status uint8 (N, C), flag uint8 (1).  ``C_`` / ``ld`` / ``stride_n`` / ``outs`` / ``ld_out`` / ``stride_n_out`` / ``ld_nc``:
+    the cells, pitches and output buffers of padded views."""
+    who = "partition_smooth"
+    lead = y if y is not None else sm_in
+    if lead is None:
+        raise ValueError(f"{who}: neither y nor sm_in")
+    for name, a in (("y", y), ("sm_in", sm_in)):
+        if a is not None:
+            _float_field(who, a, 3, name)
+            if tuple(a.shape) != tuple(lead.shape) or np.dtype(a.dtype) != np.dtype(lead.dtype):
+                raise TypeError(f"{who}: y and sm_in must have one shape and dtype")
+    if stat not in capi.PT_ROLL:
+        raise ValueError(f"{who}: unknown statistic {stat!r}")
+    if kind not in ("+", "*"):
+        raise ValueError(kind)
+    T, N, width = (int(v) for v in lead.shape)
+    C_ = width if C_ is None else int(C_)
+    stride_n = width if stride_n is None else int(stride_n)
+    ld = N * stride_n if ld is None else int(ld)
+    stride_n_out = C_ if stride_n_out is None else int(stride_n_out)
+    ld_out = N * stride_n_out if ld_out is None else int(ld_out)
+    ld_nc = C_ if ld_nc is None else int(ld_nc)
+    deg = 0
+    basis = None
+    if sm_in is None:
+        basis = np.ascontiguousarray(q, dtype=np.float64)
+        if basis.ndim != 2 or basis.shape[0] != T:
+            raise ValueError(f"{who}: the basis must be (T, deg + 1), got {basis.shape}")
+        deg = basis.shape[1] - 1
+    outputs = _subset(who, outputs, PT_SMOOTH_OUTPUTS)
+    shapes = {"sm": ((T, N, C_), np.float64), "roll": ((T, N, C_), np.float64), "n_valid": ((N, C_), np.int32),
+              "status": ((N, C_), np.uint8), "flag": ((1,), np.uint8)}
+    outs = dict(outs or {})
+    res = {k: outs[k] if k in outs else dev.empty(*shapes[k]) for k in outputs}
+    b0, b1 = (0, 0) if baseline is None else (int(baseline[0]), int(baseline[1]))
+    base = "none" if baseline is None else ("sub" if kind == "+" else "div")
+    _ext_call(dev, "xh_partition_smooth", _vp(y.ptr if y is not None else 0), _vp(sm_in.ptr if sm_in is not None else 0), T, N, C_, ld,
+              stride_n, int(np.dtype(lead.dtype) == np.float64), np_ptr(basis) if basis is not None else _vp(0), deg, int(window),
+              capi.PT_ROLL[stat], capi.PT_BASE[base], b0, b1, _ptr(res, "sm"), _ptr(res, "roll"), ld_out, stride_n_out,
+              _ptr(res, "n_valid"), _ptr(res, "status"), ld_nc, _ptr(res, "flag"))
+    return res
+
+
+def partition_components(dev: Device, sm: DeviceArray, roll: DeviceArray, dims, comps, *, weights=None, w_axis: int = 0,
+                         variab: str = "mean_all", t0: int = 0, g_order=(0, 1, 2, 3), with_g: bool = True, C_: int | None = None,
+                         ld: int | None = None, stride_n: int | None = None, out: DeviceArray | None = None, g: DeviceArray | None = None,
+                         ld_out: int | None = None):
+    """xh_partition_components: ``sm`` and ``roll`` float64 (T, N, C) with N the product of ``dims`` (up to 4 member axes);
+    ``comps`` a sequence of (axis, rule, weight) with the names of ``capi.PT_RULES`` / ``capi.PT_WEIGHTS``; ``weights`` the host
+    vector over ``w_axis``; ``variab`` a key of ``capi.PT_VARIAB`` with ``t0``.  Returns (out (K + 2, T, C), g (T, C) or None):
+    plane 0 the variability, then the components, then the total."""
+    who = "partition_components"
+    for name, a in (("sm", sm), ("roll", roll)):
+        if len(a.shape) != 3 or np.dtype(a.dtype) != np.float64 or tuple(a.shape) != tuple(sm.shape):
+            raise TypeError(f"{who}: {name} must be float64 (T, N, C) like sm")
+    T, N, width = (int(v) for v in sm.shape)
+    d = [int(v) for v in dims]
+    if len(d) > capi.PT_MAX_AXES:
+        raise ValueError(f"{who}: at most {capi.PT_MAX_AXES} member axes, got {len(d)}")
+    d4 = np.array(d + [1] * (capi.PT_MAX_AXES - len(d)), np.int64)
+    if int(np.prod(d4)) != N:
+        raise ValueError(f"{who}: the member axes {d} do not multiply to {N}")
+    table = np.array([[int(ax), capi.PT_RULES[rule], capi.PT_WEIGHTS[wt]] for ax, rule, wt in comps], np.int32).reshape(-1, 3)
+    K_ = table.shape[0]
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+    if w is not None and (not 0 <= int(w_axis) < capi.PT_MAX_AXES or w.size != d4[int(w_axis)]):
+        raise ValueError(f"{who}: the weights do not fit axis {w_axis}")
+    order = np.array(list(g_order) + [k for k in range(capi.PT_MAX_AXES) if k not in g_order], np.int32)
+    C_ = width if C_ is None else int(C_)
+    stride_n = width if stride_n is None else int(stride_n)
+    ld = N * stride_n if ld is None else int(ld)
+    ld_out = C_ if ld_out is None else int(ld_out)
+    if out is None:
+        out = dev.empty((K_ + 2, T, C_), np.float64)
+    if g is None and with_g:
+        g = dev.empty((T, C_), np.float64)
+    _ext_call(dev, "xh_partition_components", _vp(sm.ptr), _vp(roll.ptr), T, np_ptr(d4), C_, ld, stride_n, np_ptr(table) if K_ else _vp(0),
+              K_, np_ptr(w) if w is not None else _vp(0), int(w_axis), capi.PT_VARIAB[variab], int(t0), np_ptr(order), _vp(out.ptr), ld_out,
+              _vp(g.ptr if g is not None else 0))
+    return out, g
+
+
+def ensemble_stats(dev: Device, x: DeviceArray, weights=None, min_members: int = 1, *, E_: int | None = None, ld: int | None = None,
+                   out: DeviceArray | None = None, ld_out: int | None = None) -> DeviceArray:
+    """xh_ensemble_stats: ``x`` (R, E) float32 or float64; ``weights`` host (R) or None.  Returns float64 (4, E): the rows of
+    ``capi.ES_ROWS``.  ``E_`` / ``ld`` / ``out`` / ``ld_out``: padded views."""
+    who = "ensemble_stats"
+    _float_field(who, x, 2, "x")
+    R, width = (int(v) for v in x.shape)
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+    if w is not None and w.size != R:
+        raise ValueError(f"{who}: {R} weights needed, got {w.size}")
+    ld = width if ld is None else int(ld)
+    E_ = ld if E_ is None else int(E_)
+    if out is None:
+        ld_out = E_
+        out = dev.empty((capi.ES_NSTAT, E_), np.float64)
+    _ext_call(dev, "xh_ensemble_stats", _vp(x.ptr), R, E_, ld, int(np.dtype(x.dtype) == np.float64), np_ptr(w) if w is not None else _vp(0),
+              int(min_members), _vp(out.ptr), E_ if ld_out is None else int(ld_out))
+    return out

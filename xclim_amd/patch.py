@@ -166,7 +166,7 @@ def install(env=None, modules=None) -> list[str]:
     by default the real packages are used.  Functions the HIP path does not serve are forwarded to the saved originals."""
     import importlib
 
-    from . import agro, analog, anuclim, dataflags, ensembles, hydrology, phase, rainseason
+    from . import agro, analog, anuclim, dataflags, ensembles, hydrology, partitioning, phase, rainseason
     from .xr_adapter import make_wrappers
 
     env = env or real_env()
@@ -314,6 +314,10 @@ def install(env=None, modules=None) -> list[str]:
     # robustness_fractions and robustness_coefficient of ensembles/_robustness.py: one launch per test instead of a scipy call per
     # (cell, realization); robustness_categories is a handful of xarray comparisons and stays xclim's
     install_mirror(("xclim.ensembles._robustness", "xclim.ensembles"), ensembles, "xr", "gen_call_string", "SIGNIFICANCE_TESTS")
+    # hawkins_sutton, lafferty_sriver and general_partition of ensembles/_partitioning.py: one launch fits every series where polyfit
+    # makes one Python call per series with a NaN; ensemble_mean_std_max_min of ensembles/_base.py rides on the same unit
+    install_mirror(("xclim.ensembles._partitioning", "xclim.ensembles"), partitioning, "xr")
+    install_mirror(("xclim.ensembles._base", "xclim.ensembles"), partitioning.base_mirror, "xr", "update_history")
     cmod = resolve(_PET_MODULE)
     if cmod is not None and all(hasattr(cmod, n) for n in _PET_NAMES):
         from .converters import make_adapters as pet_adapters

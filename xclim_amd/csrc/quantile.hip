@@ -170,6 +170,15 @@ __device__ __forceinline__ void sort_small(uint32_t (&k)[W]) {
 // every percentile clips to the window maximum (1) / minimum (2) when the window is full, e.g. per = 90 with 5
 // samples, utl:443-452) selects a path without the sorting network when no lane of the wave holds a NaN.
 //
+// The halo is NOT what the kernel waits for.  Every doy chunk re-reads its W - 1 halo rows and fetches one row past its end
+// (FETCH_SIZE: 1.742 GB for the 1.514 GB field of the benchmark).  Round 27 removed those bytes two ways and kept neither:
+// a workgroup of one wave-width of cells by four consecutive chunks, the even waves marching backwards so that two waves
+// start on the same W - 1 rows and share them through LDS (1.547 GB fetched, same registers and occupancy, results
+// identical) ran 2 % SLOWER on the headline, with chunks of 23 or 31 days and with non-temporal loads of the field too;
+// re-reading the chunk's last row instead of the one past it (1.697 GB) is lost in the run-to-run spread.  The 3 GB of
+// table stores set the pace, and what the sweeps of that geometry did show is that SHORTER chunks win in either geometry:
+// the host now launches chunks of 10 days where no window is sorted, with MORE halo bytes.
+//
 // The quantile table (at most 8 percentiles x 8 valid counts, 1 KiB) travels BY VALUE in the kernel arguments: it is rebuilt
 // from the call's arguments on every call, and an upload of 96 bytes was a copy kernel of its own in stream order.
 struct QTabArg {
@@ -829,7 +838,12 @@ static int pdoy_impl(xh_ctx* ctx, const float* x, int64_t T, int64_t C, int64_t 
     memset(&targ, 0, sizeof(targ));
     QTab* tab = targ.e;
     build_qtab(window, qh, nper, alpha, beta, tab);
-    int chunk = 32;
+    // doys per workgroup (W - 1 halo rows each).  The halo is cheap beside the stores and short workgroups fill the
+    // device evenly: 8 / 10 / 12 / 16 / 20 / 24 / 32 -> 1.476 / 1.473 / 1.475 / 1.478 / 1.478 / 1.484 / 1.491 ms for the
+    // benchmark's whole step (profiles/r27/bench_ab.txt).  That is the path without the sorting network (every percentile
+    // clips to the window's maximum / minimum); where the windows are sorted the kernel waits for its arithmetic, and the
+    // same chunks of 10 cost it 6 % (per = 50: 1.01 -> 1.07 ms): those calls keep 32
+    int chunk = slide_fast_mode(tab, nper, window) != 0 ? 10 : 32;
     if (const char* e = xh_diag_env("XH_PDOY_SLIDE_CHUNK")) chunk = atoi(e) > 0 ? atoi(e) : chunk;  // diagnostics
     const int vec = slide_vec(x, C, st, out);
     dim3 grid((unsigned)cdiv64(cdiv64(C, vec), XH_BLOCK), (unsigned)((ndoy + chunk - 1) / chunk));

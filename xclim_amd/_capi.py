@@ -303,6 +303,12 @@ UNIT_SIGNATURES: dict[str, list] = {
                             _i64, _vp, _vp, _i64, _vp],
     "xh_partition_components": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _vp, _int, _vp, _int, _int, _i64, _vp, _vp, _i64, _vp],
     "xh_ensemble_stats": [_vp, _vp, _i64, _i64, _i64, _int, _vp, _int, _vp, _i64],
+    # include/units/xclim_hip_compound.h (xclim_amd/csrc/compound.hip)
+    "xh_compound_doy_days": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
+                             _i64],
+    "xh_degree_exceedance_date": [_vp, _i64, _i64, _i64, _int, _vp, _dbl, _int, _dbl, _i64, _vp, _vp, _vp, _vp, _vp, _i64],
+    "xh_blowing_snow_days": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _dbl, _dbl, _int, _i64, _vp, _vp, _vp, _i64],
+    "xh_pair_period_sum": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _dbl, _i64, _vp, _vp, _i64],
 }
 _RESTYPES = {"xh_last_error": C.c_char_p}
 # include/units/xclim_hip_distfit.h: the XH_DIST_* distributions, methods and functions, the XH_DISTFIT_* limit and status bytes
@@ -357,6 +363,10 @@ PT_WEIGHTS = {"none": 0, "count": 1, "user": 2}
 PT_VARIAB = {"mean_all": 0, "hs": 1}
 ES_ROWS = {"mean": 0, "std": 1, "max": 2, "min": 3}
 ES_NSTAT = 4             # XH_ES_NSTAT
+# include/units/xclim_hip_compound.h: the XH_CD_* output bits, in the order of the entry point's output pointers, and the window limit
+CD_OUTPUTS = {"cold_dry": 1, "warm_dry": 2, "warm_wet": 4, "cold_wet": 8}
+CD_NOUT = 4              # XH_CD_NOUT
+BS_MAX_WINDOW = 32       # XH_BS_MAX_WINDOW
 # header under include/units/ -> every integer #define of it, spelled from the mirrors above (tests/test_abi_units_cpu.py compares
 # each header with its entry, so a #define without a mirror, or a mirror with another value, fails there)
 UNIT_DEFINES = {
@@ -389,6 +399,8 @@ UNIT_DEFINES = {
         **{f"XH_PT_{k.upper()}": v for k, v in PT_RULES.items()}, **{f"XH_PT_W_{k.upper()}": v for k, v in PT_WEIGHTS.items()},
         **{f"XH_PT_VARIAB_{k.upper()}": v for k, v in PT_VARIAB.items()},
         **{f"XH_ES_{k.upper()}": v for k, v in ES_ROWS.items()}, "XH_ES_NSTAT": ES_NSTAT},
+    "xclim_hip_compound.h": {
+        **{f"XH_CD_{k.upper()}": v for k, v in CD_OUTPUTS.items()}, "XH_CD_NOUT": CD_NOUT, "XH_BS_MAX_WINDOW": BS_MAX_WINDOW},
 }
 # the XH_ANALOG_* methods, in the order of the reference's registry
 ANALOG_METHODS = {"seuclidean": 0, "nearest_neighbor": 1, "zech_aslan": 2, "szekely_rizzo": 3, "friedman_rafsky": 4,

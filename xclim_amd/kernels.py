@@ -2259,3 +2259,100 @@ def ensemble_stats(dev: Device, x: DeviceArray, weights=None, min_members: int =
     _ext_call(dev, "xh_ensemble_stats", _vp(x.ptr), R, E_, ld, int(np.dtype(x.dtype) == np.float64), np_ptr(w) if w is not None else _vp(0),
               int(min_members), _vp(out.ptr), E_ if ld_out is None else int(ld_out))
     return out
+
+
+# ---- the compound-extreme unit (include/units/xclim_hip_compound.h, xclim_amd/csrc/compound.hip) -------------------------
+CD_TABLES = ("tas_lo", "tas_hi", "pr_lo", "pr_hi")
+CD_NEEDS = {"cold_dry": ("tas_lo", "pr_lo"), "warm_dry": ("tas_hi", "pr_lo"), "warm_wet": ("tas_hi", "pr_hi"), "cold_wet": ("tas_lo", "pr_hi")}
+
+
+def _padded(width, C_, ld):
+    """(cells, row pitch) of a field of ``width`` columns: dense by default, a padded view with ``C_`` / ``ld``."""
+    ld = width if ld is None else int(ld)
+    return (ld if C_ is None else int(C_)), ld
+
+
+def _period_out(dev, P, C_, out, ld_out):
+    if out is None:
+        return dev.empty((P, C_), np.float64), C_
+    return out, C_ if ld_out is None else int(ld_out)
+
+
+def compound_doy_days(dev: Device, tas: DeviceArray, pr: DeviceArray, tables: dict, tidx, seg, outputs, *, C_: int | None = None,
+                      ld: int | None = None, ld_tab: int | None = None, outs: dict | None = None, ld_out: int | None = None) -> dict:
+    """xh_compound_doy_days: ``tas`` and ``pr`` (T, C) DeviceArrays, both float32 or both float64; ``tables``: the float64
+    (ndoy, C) DeviceArrays of ``CD_TABLES`` that the ``outputs`` (keys of ``capi.CD_OUTPUTS``) need (``CD_NEEDS``), all of one
+    shape; ``tidx`` host int (T), the table row of every field row; ``seg`` host (P + 1).  Returns ``{name: DeviceArray (P, C)
+    float64}``; one launch.  ``C_`` / ``ld`` / ``ld_tab`` / ``outs`` / ``ld_out``: padded views and output buffers of the caller's."""
+    who = "compound_doy_days"
+    outputs = _subset(who, outputs, tuple(capi.CD_OUTPUTS))
+    T, width, f64 = _same_fields(who, {"tas": tas, "pr": pr})
+    C_, ld = _padded(width, C_, ld)
+    tables = {k: v for k, v in tables.items() if v is not None}
+    needed = {t for o in outputs for t in CD_NEEDS[o]}
+    if set(tables) - set(CD_TABLES) or needed - set(tables):
+        raise ValueError(f"{who}: the outputs {outputs} need the tables {sorted(needed)}, got {sorted(tables)}")
+    shapes = {tuple(int(s) for s in tables[t].shape) for t in needed}
+    if len(shapes) != 1 or len(next(iter(shapes))) != 2 or any(np.dtype(tables[t].dtype) != np.float64 for t in needed):
+        raise TypeError(f"{who}: the tables must be float64 (ndoy, C) device arrays of one shape")
+    ndoy, twidth = shapes.pop()
+    ld_tab = twidth if ld_tab is None else int(ld_tab)
+    s, P = _periods(who, seg, T)
+    ti = _host_table(who, tidx, np.int32, T, "tidx")
+    outs = dict(outs or {})
+    res = {o: outs[o] if o in outs else dev.empty((P, C_), np.float64) for o in outputs}
+    _ext_call(dev, "xh_compound_doy_days", T, C_, ld, f64, _vp(tas.ptr), _vp(pr.ptr), ndoy, ld_tab,
+              *(_vp(tables[t].ptr if t in needed else 0) for t in CD_TABLES), np_ptr(ti), P, np_ptr(s),
+              *(_ptr(res, o) for o in capi.CD_OUTPUTS), C_ if ld_out is None else int(ld_out))
+    return res
+
+
+def degree_exceedance_date(dev: Device, tas: DeviceArray, seg, start, never, doy, *, thresh: float, sum_thresh: float, below: bool = False,
+                           C_: int | None = None, ld: int | None = None, out: DeviceArray | None = None,
+                           ld_out: int | None = None) -> DeviceArray:
+    """xh_degree_exceedance_date: ``tas`` (T, C) float32 or float64; ``seg`` host (P + 1); ``start`` host int (P), the row the sum
+    starts on or -1 for a NaN period; ``never`` host float64 (P), NaN for None; ``doy`` host int (T).  ``thresh`` in the units of
+    the field.  Returns float64 (P, C)."""
+    who = "degree_exceedance_date"
+    T, width, f64 = _same_fields(who, {"tas": tas})
+    C_, ld = _padded(width, C_, ld)
+    s, P = _periods(who, seg, T)
+    st = _host_table(who, start, np.int64, P, "start")
+    nv = _host_table(who, never, np.float64, P, "never")
+    dy = _host_table(who, doy, np.int32, T, "doy")
+    out, ld_out = _period_out(dev, P, C_, out, ld_out)
+    _ext_call(dev, "xh_degree_exceedance_date", T, C_, ld, f64, _vp(tas.ptr), float(thresh), int(bool(below)), float(sum_thresh), P,
+              np_ptr(s), np_ptr(st), np_ptr(nv), np_ptr(dy), _vp(out.ptr), ld_out)
+    return out
+
+
+def blowing_snow_days(dev: Device, snd: DeviceArray, sfcWind: DeviceArray, seg, flags=None, *, snd_thresh: float, wind_thresh: float,
+                      window: int = 3, C_: int | None = None, ld: int | None = None, out: DeviceArray | None = None,
+                      ld_out: int | None = None) -> DeviceArray:
+    """xh_blowing_snow_days: ``snd`` and ``sfcWind`` (T, C), both float32 or both float64; ``seg`` host (P + 1); ``flags``: host
+    bool / uint8 (T), the rows the indexer selects, or None for all.  Thresholds in the units of the fields.  Returns float64
+    (P, C)."""
+    who = "blowing_snow_days"
+    T, width, f64 = _same_fields(who, {"snd": snd, "sfcWind": sfcWind})
+    C_, ld = _padded(width, C_, ld)
+    s, P = _periods(who, seg, T)
+    window = _rain_window(who, "window", window)
+    if window > capi.BS_MAX_WINDOW:
+        raise ValueError(f"{who}: windows of up to {capi.BS_MAX_WINDOW} rows are served, got {window}")
+    fl = _row_selection(who, flags, T)
+    out, ld_out = _period_out(dev, P, C_, out, ld_out)
+    _ext_call(dev, "xh_blowing_snow_days", T, C_, ld, f64, _vp(snd.ptr), _vp(sfcWind.ptr), float(snd_thresh), float(wind_thresh), window, P,
+              np_ptr(s), np_ptr(fl) if fl is not None else _vp(0), _vp(out.ptr), ld_out)
+    return out
+
+
+def pair_period_sum(dev: Device, a: DeviceArray, b: DeviceArray, seg, scale: float = 1.0, *, C_: int | None = None, ld: int | None = None,
+                    out: DeviceArray | None = None, ld_out: int | None = None) -> DeviceArray:
+    """xh_pair_period_sum: the NaN-skipping period sums of ``(a + b) * scale``, ``a`` and ``b`` (T, C) of one dtype; float64 (P, C)."""
+    who = "pair_period_sum"
+    T, width, f64 = _same_fields(who, {"a": a, "b": b})
+    C_, ld = _padded(width, C_, ld)
+    s, P = _periods(who, seg, T)
+    out, ld_out = _period_out(dev, P, C_, out, ld_out)
+    _ext_call(dev, "xh_pair_period_sum", T, C_, ld, f64, _vp(a.ptr), _vp(b.ptr), float(scale), P, np_ptr(s), _vp(out.ptr), ld_out)
+    return out

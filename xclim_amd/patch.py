@@ -166,7 +166,7 @@ def install(env=None, modules=None) -> list[str]:
     by default the real packages are used.  Functions the HIP path does not serve are forwarded to the saved originals."""
     import importlib
 
-    from . import agro, analog, anuclim, dataflags, ensembles, hydrology, partitioning, phase, rainseason
+    from . import agro, analog, anuclim, compound, dataflags, ensembles, hydrology, partitioning, phase, rainseason
     from .xr_adapter import make_wrappers
 
     env = env or real_env()
@@ -309,6 +309,11 @@ def install(env=None, modules=None) -> list[str]:
     install_mirror(("xclim.indices.converters", "xclim.indices", "xclim.indices._multivariate"), phase.converters)
     install_mirror(("xclim.indices._multivariate", "xclim.indices"), phase.multivariate)
     install_mirror(("xclim.indices._threshold", "xclim.indices"), phase.threshold)
+    # the compound percentile-day counts, blowing_snow and water_cycle_intensity of _multivariate.py and
+    # degree_days_exceedance_date of _threshold.py: xarray expressions that reach no replaced generic / run_length function, one
+    # launch each here
+    install_mirror(("xclim.indices._multivariate", "xclim.indices"), compound.multivariate)
+    install_mirror(("xclim.indices._threshold", "xclim.indices"), compound.threshold)
     # spatial_analogs of analog.py: one launch with a lane per candidate cell instead of a Python call per cell
     install_mirror(("xclim.analog",), analog)
     # robustness_fractions and robustness_coefficient of ensembles/_robustness.py: one launch per test instead of a scipy call per

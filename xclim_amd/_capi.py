@@ -309,6 +309,10 @@ UNIT_SIGNATURES: dict[str, list] = {
     "xh_degree_exceedance_date": [_vp, _i64, _i64, _i64, _int, _vp, _dbl, _int, _dbl, _i64, _vp, _vp, _vp, _vp, _vp, _i64],
     "xh_blowing_snow_days": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _dbl, _dbl, _int, _i64, _vp, _vp, _vp, _i64],
     "xh_pair_period_sum": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _dbl, _i64, _vp, _vp, _i64],
+    # include/units/xclim_hip_grid.h (xclim_amd/csrc/grid.hip)
+    "xh_grid_masked_dot": [_vp, _i64, _i64, _i64, _int, _vp, _vp, _dbl, _vp, _vp],
+    "xh_grid_box_mean": [_vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _int, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64],
+    "xh_grid_filter_argmax": [_vp, _i64, _i64, _vp, _i64, _int, _vp, _vp, _i64, _vp, _vp],
 }
 _RESTYPES = {"xh_last_error": C.c_char_p}
 # include/units/xclim_hip_distfit.h: the XH_DIST_* distributions, methods and functions, the XH_DISTFIT_* limit and status bytes
@@ -367,6 +371,12 @@ ES_NSTAT = 4             # XH_ES_NSTAT
 CD_OUTPUTS = {"cold_dry": 1, "warm_dry": 2, "warm_wet": 4, "cold_wet": 8}
 CD_NOUT = 4              # XH_CD_NOUT
 BS_MAX_WINDOW = 32       # XH_BS_MAX_WINDOW
+# include/units/xclim_hip_grid.h: the tile of xh_grid_masked_dot, the XH_GRID_* output bits in the order of the entry point's output
+# pointers, and the filter limit
+GRID_CHUNK = 2048        # XH_GRID_CHUNK
+GRID_ROWS = 8            # XH_GRID_ROWS
+GRID_OUTPUTS = {"dot": 1, "msum": 2}
+GRID_MAX_WINDOW = 128    # XH_GRID_MAX_WINDOW
 # header under include/units/ -> every integer #define of it, spelled from the mirrors above (tests/test_abi_units_cpu.py compares
 # each header with its entry, so a #define without a mirror, or a mirror with another value, fails there)
 UNIT_DEFINES = {
@@ -401,6 +411,9 @@ UNIT_DEFINES = {
         **{f"XH_ES_{k.upper()}": v for k, v in ES_ROWS.items()}, "XH_ES_NSTAT": ES_NSTAT},
     "xclim_hip_compound.h": {
         **{f"XH_CD_{k.upper()}": v for k, v in CD_OUTPUTS.items()}, "XH_CD_NOUT": CD_NOUT, "XH_BS_MAX_WINDOW": BS_MAX_WINDOW},
+    "xclim_hip_grid.h": {
+        "XH_GRID_CHUNK": GRID_CHUNK, "XH_GRID_ROWS": GRID_ROWS, **{f"XH_GRID_{k.upper()}": v for k, v in GRID_OUTPUTS.items()},
+        "XH_GRID_MAX_WINDOW": GRID_MAX_WINDOW},
 }
 # the XH_ANALOG_* methods, in the order of the reference's registry
 ANALOG_METHODS = {"seuclidean": 0, "nearest_neighbor": 1, "zech_aslan": 2, "szekely_rizzo": 3, "friedman_rafsky": 4,

@@ -2356,3 +2356,78 @@ def pair_period_sum(dev: Device, a: DeviceArray, b: DeviceArray, seg, scale: flo
     out, ld_out = _period_out(dev, P, C_, out, ld_out)
     _ext_call(dev, "xh_pair_period_sum", T, C_, ld, f64, _vp(a.ptr), _vp(b.ptr), float(scale), P, np_ptr(s), _vp(out.ptr), ld_out)
     return out
+
+
+# ---- the grid-reduction unit (include/units/xclim_hip_grid.h, xclim_amd/csrc/grid.hip) -----------------------------------
+def grid_masked_dot(dev: Device, x: DeviceArray, w: DeviceArray, thr: float, outputs=("dot", "msum"), *, C_: int | None = None,
+                    ld: int | None = None, outs: dict | None = None) -> dict:
+    """xh_grid_masked_dot: ``x`` (T, C) float32 or float64, ``w`` (C) float64 device weights, ``thr`` in the units of the field.
+    ``outputs``: keys of ``capi.GRID_OUTPUTS`` — "dot", the sums of ``(x >= thr ? x : 0) * w``, and "msum", those of
+    ``(x >= thr ? 1 : 0) * w``.  Returns ``{name: DeviceArray (T) float64}``; one launch reads the field once for both.
+    ``C_`` / ``ld`` / ``outs``: a padded view and output buffers of the caller's."""
+    who = "grid_masked_dot"
+    outputs = _subset(who, outputs, tuple(capi.GRID_OUTPUTS))
+    T, width, f64 = _same_fields(who, {"x": x})
+    C_, ld = _padded(width, C_, ld)
+    if not isinstance(w, DeviceArray) or np.dtype(w.dtype) != np.float64 or int(np.prod(w.shape, dtype=np.int64)) < C_:
+        raise TypeError(f"{who}: the weights must be a float64 device array of {C_} cells")
+    outs = dict(outs or {})
+    res = {o: outs[o] if o in outs else dev.empty((T,), np.float64) for o in outputs}
+    _ext_call(dev, "xh_grid_masked_dot", T, C_, ld, f64, _vp(x.ptr), _vp(w.ptr), float(thr), *(_ptr(res, o) for o in capi.GRID_OUTPUTS))
+    return res
+
+
+def grid_box_mean(dev: Device, u: DeviceArray, T: int, ld: int, extents, strides, iz, iy, ix, *, out: DeviceArray | None = None,
+                  ld_out: int | None = None) -> DeviceArray:
+    """xh_grid_box_mean: ``u`` a float32 or float64 device array of at least ``T * ld`` elements whose sample (t, z, y, x) is
+    element ``t * ld + z * sz + y * sy + x * sx``; ``extents`` (Z, Y, X), ``strides`` (sz, sy, sx); ``iz`` / ``iy`` / ``ix``: the
+    selected indices along each axis (host integers, or int32 device arrays).  Returns the float64 (T, ny) means over the selected
+    levels and longitudes of the samples that are not NaN."""
+    who = "grid_box_mean"
+    if np.dtype(u.dtype) not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise TypeError(f"{who}: u must be float32 or float64")
+    (Z, Y, X), (sz, sy, sx) = (int(v) for v in extents), (int(v) for v in strides)
+    T, ld = int(T), int(ld)
+    if int(np.prod(u.shape, dtype=np.int64)) < T * ld:
+        raise ValueError(f"{who}: u holds fewer than T * ld = {T * ld} elements")
+    lists = []
+    for name, idx, n in (("iz", iz, Z), ("iy", iy, Y), ("ix", ix, X)):
+        if not isinstance(idx, DeviceArray):
+            h = np.ascontiguousarray(idx, dtype=np.int64).reshape(-1)
+            if h.size and (h.min() < 0 or h.max() >= n):
+                raise ValueError(f"{who}: {name} outside [0, {n})")
+            idx = dev.to_device(h.astype(np.int32)) if h.size else dev.empty((1,), np.int32)
+            idx = (idx, int(h.size))
+        else:
+            if np.dtype(idx.dtype) != np.int32:
+                raise TypeError(f"{who}: {name} must be int32")
+            idx = (idx, int(np.prod(idx.shape, dtype=np.int64)))
+        lists.append(idx)
+    (dz, nz), (dy, ny), (dx, nx) = lists
+    if out is None:
+        out, ld_out = dev.empty((T, ny), np.float64), ny
+    _ext_call(dev, "xh_grid_box_mean", T, ld, Z, Y, X, sz, sy, sx, int(np.dtype(u.dtype) == np.float64), _vp(u.ptr), nz, _vp(dz.ptr),
+              ny, _vp(dy.ptr), nx, _vp(dx.ptr), _vp(out.ptr), ny if ld_out is None else int(ld_out))
+    return out
+
+
+def grid_filter_argmax(dev: Device, zm: DeviceArray, wts, outputs=("smax", "jmax"), *, ny: int | None = None, ld: int | None = None,
+                       outs: dict | None = None, ld_f: int | None = None) -> dict:
+    """xh_grid_filter_argmax: ``zm`` (T, ny) float64; ``wts`` host float64 (W), 1 <= W <= ``capi.GRID_MAX_WINDOW``.  ``outputs``: a
+    subset of "f" (the centred filter, float64 (T, ny), NaN where the window leaves the rows or holds a NaN), "smax" (float64 (T),
+    the row maximum of the values that are not NaN) and "jmax" (int32 (T), its first index, -1 for a row of NaN)."""
+    who = "grid_filter_argmax"
+    outputs = _subset(who, outputs, ("f", "smax", "jmax"))
+    T, width = _tc(zm, np.float64)
+    ny, ld = _padded(width, ny, ld)
+    w = np.ascontiguousarray(wts, dtype=np.float64)
+    if w.ndim != 1 or w.size < 1:
+        raise ValueError(f"{who}: the filter must have at least 1 weight")
+    if w.size > capi.GRID_MAX_WINDOW:
+        raise ValueError(f"{who}: filters of up to {capi.GRID_MAX_WINDOW} weights are served, got {w.size}")
+    outs = dict(outs or {})
+    shapes = {"f": ((T, ny), np.float64), "smax": ((T,), np.float64), "jmax": ((T,), np.int32)}
+    res = {o: outs[o] if o in outs else dev.empty(*shapes[o]) for o in outputs}
+    _ext_call(dev, "xh_grid_filter_argmax", T, ny, _vp(zm.ptr), ld, int(w.size), np_ptr(w), _ptr(res, "f"), ny if ld_f is None else int(ld_f),
+              _ptr(res, "smax"), _ptr(res, "jmax"))
+    return res

@@ -166,7 +166,7 @@ def install(env=None, modules=None) -> list[str]:
     by default the real packages are used.  Functions the HIP path does not serve are forwarded to the saved originals."""
     import importlib
 
-    from . import agro, analog, anuclim, compound, dataflags, ensembles, hydrology, partitioning, phase, rainseason
+    from . import agro, analog, anuclim, compound, dataflags, ensembles, grid, hydrology, partitioning, phase, rainseason
     from .xr_adapter import make_wrappers
 
     env = env or real_env()
@@ -314,6 +314,10 @@ def install(env=None, modules=None) -> list[str]:
     # launch each here
     install_mirror(("xclim.indices._multivariate", "xclim.indices"), compound.multivariate)
     install_mirror(("xclim.indices._threshold", "xclim.indices"), compound.threshold)
+    # sea_ice_area / sea_ice_extent of _threshold.py and jetstream_metric_woollings of _synoptic.py: what reduces across the grid
+    # (xarray.dot, cf.mean and rolling().construct().dot() in the reference), one or two launches each here
+    install_mirror(("xclim.indices._threshold", "xclim.indices"), grid.threshold)
+    install_mirror(("xclim.indices._synoptic", "xclim.indices"), grid.synoptic)
     # spatial_analogs of analog.py: one launch with a lane per candidate cell instead of a Python call per cell
     install_mirror(("xclim.analog",), analog)
     # robustness_fractions and robustness_coefficient of ensembles/_robustness.py: one launch per test instead of a scipy call per

@@ -5,7 +5,8 @@ number of years; every instance has its own keys per lane, threads per column an
 below run both sides of every switch point (s and s + 1) and one size inside every range, against the oracle with the
 exactness the rest of the suite asks of that operation.  The split tables are read by the CPU guard at the end of the
 module, which checks them against the dispatch constants in the .hip sources: an instance added or moved without
-extending these tables fails that guard on any machine.
+extending these tables fails that guard on any machine.  The grouped sdba kernels (rows per group, window rows, nodes)
+have their tables and their tests in tests/test_gpu_sdba_edges.py; the guard here reads those tables too.
 """
 
 import os
@@ -22,11 +23,13 @@ from oracle.timeutil import OTime
 from xclim_amd.timeaxis import TimeAxis
 from poisoned import poisoned_outputs  # noqa: F401  (autouse: the tests of this module that use the device run on poisoned output buffers)
 
+import test_gpu_sdba_edges as edges   # (the split tables of the grouped sdba kernels)
+
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "xclim_amd", "csrc")
 
 # switch points: the instance for sizes <= s differs from the one for s + 1
-COL_SPLITS = (512, 1024, 2048, 3072, 4096, 6144, 8192, 10240, 11264, 12288, 14336, 16384, 32768)   # xh_select_columns (+ lean)
-TM_SPLITS = (512, 1024, 32768, 65535)            # time-major: short-series kernels | select4.hip | its counter limits
+COL_SPLITS = (384, 512, 1024, 2048, 3072, 4096, 6144, 8192, 10240, 11264, 12288, 14336, 16384, 32768)   # xh_select_columns (+ lean)
+TM_SPLITS = (384, 512, 1024, 32768, 65535)       # time-major: short-series kernels (6 | 8 keys per lane) | select4.hip | its counter limits
 QDM_SPLITS = (512, 2048, 4096, 8192, 12288, 16384, 32768)                                           # xh_qdm_columns | sorted
 EQM_SPLITS = (10, 20, 32)                        # xh_eqm_adjust (nearest / linear / cubic), xh_eqm_adjust_g2d
 PLANE_SPLITS = (20, 32)                          # plane_run: row kernel instances, linear pair path, nearest limit
@@ -325,8 +328,9 @@ def test_spell_mask_weights_per_cell_threshold(dev, rng, window):
 
 
 # ---------------------------------------------------------------- the guard (CPU)
-# (source, function, size variable, split table): every comparison of the variable with an integer literal in the
-# function body, outside its XH_REQUIRE argument checks, must be a listed switch point
+# (source, function, size variable, split table): every comparison of the variable with an integer literal or a named
+# `constexpr int` of the file in the function body, outside its XH_REQUIRE argument checks, must be a listed switch point.
+# A function that dispatches on several sizes lists a tuple of variables and a tuple of tables, in the same order.
 DISPATCH = [
     ("select.hip", "xh_select_columns", "T", COL_SPLITS),
     ("select2.hip", "xh_select_columns_lean", "T", COL_SPLITS),
@@ -342,6 +346,13 @@ DISPATCH = [
     ("pdoy_quad.hip", "xh_launch_pdoy_quad", "nyears", PDOY_SPLITS),
     ("pdoy_walk.hip", "xh_launch_pdoy_walk", "nyears", PDOY_SPLITS),
     ("doystats.hip", "xh_launch_doy_stats_sets", "nyears", DOYSTATS_SPLITS),
+    # the grouped sdba kernels: their tables and their tests are tests/test_gpu_sdba_edges.py.  ws_train's `most` (a window
+    # that GROWS past 1024 rows after a first window that fits) is a shape the schedules of xclim_amd/sdba.py never have: it runs
+    # in test_sliding_window_that_grows_past_its_capacity_is_declined alone, on a hand-made schedule (1024 | 1026 rows)
+    ("winsel.hip", "ws_train", ("n0", "most", "per", "nq"), (edges.WINDOW_ROW_SPLITS, edges.WINDOW_ROW_SPLITS, edges.GROUP_SPLITS, edges.NODE_SPLITS)),
+    ("winsel.hip", "gq_train", ("most", "nq"), (edges.GROUP_SPLITS, edges.GQ_NODE_SPLITS)),
+    ("qdm.hip", "xh_qdm_adjust_groups", ("most", "nq"), (edges.GROUP_SPLITS, edges.NODE_SPLITS)),
+    ("select.hip", "launch_select_grp_g", "T", COL_SPLITS),
 ]
 
 
@@ -368,22 +379,45 @@ def _function_body(src, name):
 
 
 def dispatch_points(csrc, fname, func, var):
-    """The switch points of `var` in `func`: `var <= N` / `var > N` / `var == N` split at N, `var < N` / `var >= N` at N - 1."""
-    body = _function_body(open(os.path.join(csrc, fname)).read(), func)
+    """The switch points of `var` in `func`: `var <= N` / `var > N` / `var == N` split at N, `var < N` / `var >= N` at N - 1.
+    N is an integer literal or a named constant of the file (`constexpr int WS_CAP = 1024;`)."""
+    src = open(os.path.join(csrc, fname)).read()
+    consts = {n: int(v) for n, v in re.findall(r"\bconstexpr\s+int\s+([A-Za-z_]\w*)\s*=\s*(\d+)\s*;", src)}
+    body = _function_body(src, func)
     while True:   # argument checks are limits, not switch points
         m = re.search(r"\bXH_REQUIRE\s*\(", body)
         if not m:
             break
         body = body[: m.start()] + body[_close(body, m.end() - 1, "(", ")"):]
     pts = set()
-    for op, n in re.findall(r"(?<![\w.>])" + var + r"\s*(<=|>=|==|<|>)\s*(\d+)\b", body):
+    for op, n in re.findall(r"(?<![\w.>])" + var + r"\s*(<=|>=|==|<|>)\s*(\d+|[A-Z][A-Z0-9_]*)\b", body):
+        if not n.isdigit():
+            assert n in consts, f"{fname}:{func}: `{var} {op} {n}` compares with a name that is no `constexpr int` of the file"
+            n = consts[n]
         pts.add(int(n) - 1 if op in ("<", ">=") else int(n))
     return pts
 
 
 @pytest.mark.parametrize("fname,func,var,splits", DISPATCH, ids=[f"{f}:{fn}" for f, fn, _, _ in DISPATCH])
 def test_dispatch_points_are_tested(fname, func, var, splits):
-    pts = dispatch_points(CSRC, fname, func, var)
-    assert pts, f"{fname}:{func}: no `{var}` comparison found (was the dispatch renamed?)"
-    missing = sorted(pts - set(splits))
-    assert not missing, f"{fname}:{func} switches at {var} = {missing}, which the ladder tests of this module do not run"
+    """`var` / `splits`: one size variable and its table, or a tuple of variables with a tuple of tables (a function that
+    dispatches on several sizes: rows per group, window rows, nodes) — every variable is held to its own table."""
+    pairs = [(var, splits)] if isinstance(var, str) else list(zip(var, splits, strict=True))
+    for v, table in pairs:
+        pts = dispatch_points(CSRC, fname, func, v)
+        assert pts, f"{fname}:{func}: no `{v}` comparison found (was the dispatch renamed?)"
+        missing = sorted(pts - set(table))
+        assert not missing, f"{fname}:{func} switches at {v} = {missing}, which the ladder tests do not run"
+
+
+def test_the_group_size_tables_are_what_the_edge_module_runs():
+    """The tables of the grouped sdba kernels live next to their tests (tests/test_gpu_sdba_edges.py): both sides of every
+    split must be among that module's parametrizations."""
+    assert {s + d for s in edges.GROUP_SPLITS for d in (0, 1)} <= set(edges.LADDER_YEARS)
+    assert {y for y, w, c in edges.WINDOW_CASES} >= {s + 1 for s in edges.GROUP_SPLITS}          # per | per group: 33, 65 years
+    assert {s + d for s in edges.NODE_SPLITS for d in (0, 1)} <= set(edges.LADDER_NQ)       # k_qdm_groups
+    assert {s + d for s in edges.NODE_SPLITS for d in (0, 1)} <= set(edges.WINDOW_NQ)       # the window kernel's own ladder
+    assert {s + d for s in edges.GQ_NODE_SPLITS for d in (0, 1)} <= set(edges.GQ_LADDER_NQ)
+    for s in edges.WINDOW_ROW_SPLITS:   # rows of the first window and of the largest: a case just inside, one just beyond
+        assert any(s - 64 <= r <= s for r in edges.WINDOW_ROWS) and any(s < r <= s + 64 for r in edges.WINDOW_ROWS)
+    assert {s + d for s in edges.SELECT_GRP_SPLITS for d in (0, 1)} <= set(_both_sides(COL_SPLITS)) & set(_both_sides(TM_SPLITS))

@@ -464,6 +464,54 @@ def test_qdm_small_groups_on_the_simulation(sim, rng, interp):
     assert K.qdm_adjust_groups(sim, d_x, np.r_[np.arange(T), np.arange(10)], np.array([0, T + 10]), d_af, q) is None
 
 
+@pytest.fixture(scope="module")
+def tedge():
+    """tests/test_gpu_sdba_edges.py: the grouped sdba kernels against the ORACLE at their size edges — its checks are functions
+    of (device, sizes); here at fiber sizes."""
+    import tests.test_gpu_sdba_edges as mod
+
+    return mod
+
+
+@pytest.mark.parametrize("interp", ["nearest", "linear"])
+def test_qdm_empty_groups_on_the_simulation(sim, tedge, interp):
+    """k_qdm_groups with empty groups — a trailing day 366, a run of empty groups that ends the table, one in the middle — as the
+    GPU module runs them.  (An empty group at the end of the table used to index the row list one element past its end.)"""
+    tedge.check_empty_trailing_groups(sim, interp, short=False)
+    tedge.check_empty_trailing_groups(sim, interp, short=True)
+    tedge.check_empty_middle_group(sim, interp)
+
+
+@pytest.mark.parametrize("T", [300, 800])
+def test_tiny_spans_on_the_simulation(sim, tedge, T):
+    """Columns on both sides of zero inside +-1e-37 and below: k_select_grp (300) / k_select_quantile (800), the staged
+    time-major kernel, k_qdm_columns, EQM train + adjust.  (x86 converts +inf to 0 where the GPU saturates: what the overflow
+    of the bin scale did on the device shows in tests/test_common_host_build.py, not here.)"""
+    tedge.check_tiny_quantiles(sim, T, 1)
+    if T <= 512:
+        tedge.check_tiny_quantiles(sim, T, 0)
+    tedge.check_tiny_qdm(sim, T)
+    if T == 800:
+        tedge.check_tiny_eqm(sim, T)
+
+
+@pytest.mark.parametrize("years,kind", [(33, "+"), (64, "*")])
+def test_group_size_ladder_on_the_simulation(sim, tedge, years, kind):
+    """The 64-key instances of k_group_quantiles / k_qdm_groups (33 and 64 rows per group) on six edge cells against the oracle."""
+    tedge.check_group_training(sim, years, "noleap", kind, 8, cells=tedge.FEW_CELLS)
+    tedge.check_group_qdm(sim, years, "noleap", kind, "linear" if years == 33 else "nearest", 8, cells=tedge.FEW_CELLS)
+
+
+def test_window_kernel_beyond_32_rows_per_step_on_the_simulation(sim, tedge):
+    """k_window_quantiles with per = 40 (the 64-slot sorts and lanes 32 .. 63 of the leave / enter bookkeeping): the first 40
+    groups of a 40-year series with a window of 5 days, against the oracle.  And a hand-made schedule that grows to exactly 1024
+    rows (served) and past them (declined)."""
+    tedge.check_window_kernel(sim, 40, 5, "+", 40)
+    tedge.check_window_kernel(sim, 40, 5, "*", 8, nq=32)     # 64 targets: one on every lane
+    tedge.check_window_kernel(sim, 40, 5, "*", 8, nq=33)     # declined
+    tedge.check_window_growing_past_capacity(sim)
+
+
 @pytest.mark.parametrize("kind", ["+", "*"])
 def test_small_group_training_on_the_simulation(sim, rng, kind):
     """k_group_quantiles (winsel.hip, round 6: the training of all groups of a day-of-year grouping without a window in one launch)

@@ -6,7 +6,11 @@ Four cases in ten train a DETRENDED mapping instead (xh_dqm_train_window: the wi
 its per-group chain (xh_poly_trend, xh_trend_apply, xh_eqm_train): the means agree to their summation order, so the tables are
 compared for the same NaN / infinity pattern and to a few float32 ulps (cells with a negative or zero mean, kind "*": the order
 reverses, samples drop out).
-usage: python tools/fuzz_winsel.py [seconds]"""
+Years run up to 64 (beyond 32 rows leave and enter per step: the 64-slot sorts of the window kernel) with years * window <= 1024,
+the window's capacity.
+--oracle: compare with oracle/sdba.py (eqm_train_grouped / dqm_train_grouped, at the tolerances of the oracle tests) instead of
+the per-group HIP route — a change that moves that route moves both sides of the default comparison together.
+usage: python tools/fuzz_winsel.py [seconds] [--oracle]"""
 import json
 import os
 import sys
@@ -22,16 +26,39 @@ from fuzzdev import get_fuzz_device  # noqa: E402
 
 dev = get_fuzz_device()
 SMALL = os.environ.get("FUZZ_DEVICE") == "hostsim"
-budget = float(sys.argv[1]) if len(sys.argv) > 1 else 60.0
+ORACLE = "--oracle" in sys.argv[1:]
+_args = [a for a in sys.argv[1:] if a != "--oracle"]
+budget = float(_args[0]) if _args else 60.0
+if ORACLE:
+    from oracle import sdba as osdba  # noqa: E402
+    from oracle.timeutil import OTime  # noqa: E402
+
+
+def oracle_ok(model, dqm, ref, hist, start, T, cal, window, nq, kind):
+    """The tables of `model` against the oracle's, NaN / infinity patterns equal: EQM hist_q rtol 1e-6, af rtol 1e-6 / atol 1e-5;
+    DQM scaling rtol 1e-6, hist_q rtol 1e-5 / atol 2e-6, af rtol 1e-5 / atol 1e-5 (tests/test_gpu_sdba_edges.py)."""
+    ot = OTime.standard(start, T) if cal == "standard" else OTime.noleap(int(start[:4]), T, cal)
+
+    def same(x, y, rtol, atol=0.0):
+        return (np.array_equal(np.isnan(x), np.isnan(y)) and np.array_equal(np.isinf(x), np.isinf(y))
+                and bool(np.allclose(x, y, rtol=rtol, atol=atol, equal_nan=True)))
+
+    if dqm:
+        _, eaf, ehq, esc = osdba.dqm_train_grouped(ref, hist, ot, "dayofyear", nq, kind, window=window)
+        return same(model.scaling, esc, 1e-6) and same(model.hist_q, ehq, 1e-5, 2e-6) and same(model.af, eaf, 1e-5, 1e-5)
+    eaf, ehq, _ = osdba.eqm_train_grouped(ref, hist, ot, "dayofyear", window, nq, kind)
+    return same(model.hist_q, ehq, 1e-6) and same(model.af, eaf, 1e-6, 1e-5)
+
+
 rng = np.random.default_rng(int(os.environ.get("FUZZ_SEED", "2026")))
 os.environ["XH_DIAGNOSTICS"] = "1"
-t_end, it, served, n_dqm = time.time() + budget, 0, 0, 0
+t_end, it, served, n_dqm, n_oracle = time.time() + budget, 0, 0, 0, 0
 while time.time() < t_end:
     cal = str(rng.choice(["noleap", "360_day", "standard"]))
-    years = int(rng.integers(2, 5 if SMALL else 33))
+    years = int(rng.integers(2, 5 if SMALL else 65))
     window = int(rng.choice([3, 5, 7, 15, 31]))
-    if years * window > 1000:
-        window = max(3, (1000 // years) | 1)
+    if years * window > 1024:       # the largest odd window with years * window <= 1024 (64 years: 15 -> 960 rows)
+        window = max(3, (1024 // years - 1) | 1)
     ylen = 360 if cal == "360_day" else 365
     T = years * ylen + int(rng.integers(-100, 100))
     start = f"{int(rng.integers(1990, 2010))}-{int(rng.integers(1, 13)):02d}-01" if rng.random() < 0.3 else "2000-01-01"
@@ -76,6 +103,15 @@ while time.time() < t_end:
     hit = any(n == entry for n, _ in tr)
     served += hit
     n_dqm += dqm and hit
+    if ORACLE:
+        if cal == "standard" or start.endswith("-01-01"):   # (the oracle's noleap / 360_day axes start on 1 January; others: not compared)
+            n_oracle += 1
+            if not oracle_ok(a, dqm, ref, hist, start, T, cal, window, nq, kind):
+                print(json.dumps({"ok": False, "against": "oracle", "it": it, "dqm": bool(dqm), "kind": kind, "cal": cal, "years": years,
+                                  "window": window, "T": T, "start": start, "cells": cells, "nq": nq, "mode": mode}))
+                sys.exit(1)
+        it += 1
+        continue
     os.environ["XH_WINSEL"] = "0"
     b = Model.train(ref, hist, nquantiles=nq, kind=kind, group="time.dayofyear", window=window, time=ta, device=dev)
     if dqm:
@@ -102,4 +138,5 @@ while time.time() < t_end:
                           "cells": cells, "nq": nq, "mode": mode, "first_bad": bad[:5].tolist()}))
         sys.exit(1)
     it += 1
-print(json.dumps({"ok": True, "iterations": it, "through_the_sliding_kernel": served, "of_them_dqm": int(n_dqm)}))
+print(json.dumps({"ok": True, "iterations": it, "through_the_sliding_kernel": served, "of_them_dqm": int(n_dqm),
+                  **({"compared_with_the_oracle": n_oracle} if ORACLE else {})}))

@@ -334,24 +334,37 @@ struct XhValueBins {
   int on;
   float lo, scale;
 };
+// Switched on only for a finite scale: a span below (nb - 1) / FLT_MAX (samples inside +-1e-37, denormals) would make it +inf,
+// every product above kmin2 +inf, and the conversion of +inf to uint32 saturates to 0xFFFFFFFF on the GPU, which the `1u + bin`
+// of select.hip wraps to bin 0.  Such columns keep the key-space bins.  And span * scale may round one ulp above nb - 1: the
+// scale is then one ulp lower (scale <= (nb - 1) / span * (1 + 2^-24), one ulp off is at least a factor 1 - 2^-24: the exact
+// product is below nb - 1), so that (f - lo) * scale <= span * scale <= nb - 1 for every key of [kmin2, kmax] — subtraction and
+// multiplication by a positive number are monotone — at no cost per key.
 __device__ __forceinline__ XhValueBins xh_value_bins(uint32_t kmin2, uint32_t kmax, bool any, int nb) {
   XhValueBins v{0, 0.f, 0.f};
   if (any && kmin2 < 0x80000000u && kmax >= 0x80000000u && kmax != 0xFFFFFFFFu) {
     const float lo = xh_key2f(kmin2), hi = xh_key2f(kmax);
     const float span = hi - lo;
     if (span > 0.f && span - span == 0.f) {   // (finite)
-      v.on = 1;
-      v.lo = lo;
-      v.scale = (float)(nb - 1) / span;
+      const float top = (float)(nb - 1);
+      float scale = top / span;
+      if (scale - scale == 0.f) {             // (finite)
+        if (span * scale > top) scale = __uint_as_float(__float_as_uint(scale) - 1u);
+        v.on = 1;
+        v.lo = lo;
+        v.scale = scale;
+      }
     }
   }
   return v;
 }
-// bin index in [0, nb - 1] (callers clamp); garbage for a NaN key or a key below kmin2, which callers never use
-__device__ __forceinline__ uint32_t xh_value_bin(const XhValueBins& v, uint32_t kk) {
+// the float that xh_value_bin converts: finite and in [0, nb - 1] for every key in [kmin2, kmax]
+__device__ __forceinline__ float xh_value_bin_pos(const XhValueBins& v, uint32_t kk) {
   const float d = (xh_key2f(kk) - v.lo) * v.scale;
-  return d > 0.f ? (uint32_t)d : 0u;
+  return d > 0.f ? d : 0.f;
 }
+// bin index in [0, nb - 1], monotone in the key; garbage for a NaN key or a key below kmin2, which callers never use
+__device__ __forceinline__ uint32_t xh_value_bin(const XhValueBins& v, uint32_t kk) { return (uint32_t)xh_value_bin_pos(v, kk); }
 
 // s / n for a small positive integer n, given inv = 1.0 / n: q = RN(s * inv), r = s - n * q (exact with FMA),
 // q' = RN(q + r * inv) is the correctly rounded quotient (Markstein's theorem; inv is the correctly rounded

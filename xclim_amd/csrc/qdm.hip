@@ -289,6 +289,7 @@ k_qdm_groups(const float* __restrict__ x, int64_t C, int64_t st, const int32_t* 
   const int64_t g = blockIdx.y;
   const int64_t k0 = offs[g];
   const int m = (int)(offs[g + 1] - k0);                        // rows of the group (<= PER)
+  if (m == 0) return;   // an empty group writes nothing; rows[k0] may lie past the list (a trailing day 366 without a leap year)
   int nvn = 0;
   for (int j = 0; j < nq; ++j) {
     const float a = af[((int64_t)g * nq + j) * C + c];
@@ -298,7 +299,7 @@ k_qdm_groups(const float* __restrict__ x, int64_t C, int64_t st, const int32_t* 
   uint32_t n = 0, kmin = 0xFFFFFFFFu, kmax = 0u;
 #pragma unroll
   for (int j = 0; j < PER; ++j) {
-    const int32_t row = rows[k0 + (j < m ? j : 0)];
+    const int32_t row = rows[k0 + (j < m ? j : 0)];   // (m >= 1 here: rows[k0] is the group's own first row)
     const float f = x[(int64_t)row * st + c];
     const uint32_t kk = j < m ? xh_f2key(f + 0.0f) : 0xFFFFFFFFu;   // (-0.0 + 0.0 = +0.0: the two zeros tie)
     key[j] = kk;

@@ -151,7 +151,7 @@ __device__ __forceinline__ uint32_t ws_sort1(uint32_t v, int lane) {
 // element" and a byte "this element leaves"] | leaving positions [64] | entering keys [64] | picked keys [64]; per workgroup: the
 // staged samples of a step [2 * WS_PER][WS_WAVES]
 constexpr int ws_words_per_wave() { return WS_CAP + 64 + 516 + 3 * 64; }
-// (per = 30 years: 77 824 + 3 840 bytes — two workgroups share a CU's 160 KiB)
+// (1 796 words per wave; per = 30 years: 114 944 + 3 840 = 118 784 bytes, per = 64: 123 136 — one workgroup per CU's 160 KiB)
 inline size_t ws_lds(int per) { return (size_t)WS_WAVES * ws_words_per_wave() * 4 + (size_t)2 * (size_t)per * WS_WAVES * 4; }
 
 // the targets' positions in a sorted sample of n (type 7; utl:395, 417-491): lane t < 2 nq holds the position of target t

@@ -190,7 +190,13 @@ class Grouper:
                 for k in range(g, e):
                     en[k - g, :len(ent[k])] = ent[k]
                     lv[k - g, :len(lev[k])] = lev[k]
-                stretches.append((g, rows_of[g], en, lv))
+                # The cap above counts the VALID rows, the kernel's limit is on the list it is handed: where the -1 padding of a
+                # series end takes the list beyond it (17 years x window 61: 1037 entries, 1024 valid rows) the valid rows alone
+                # are passed — else the kernel declines and every group is silently redone from its gathered sample.  A list
+                # within the limit goes on as it is, padding included (the kernel skips -1): the recorded launch plans of
+                # tests/golden/sdba_plans.json hold those lists byte for byte
+                rows0 = rows_of[g] if len(rows_of[g]) <= cap else rows_of[g][rows_of[g] >= 0]
+                stretches.append((g, rows0, en, lv))
                 covered[g:e + 1] = True
             g = e + 1
         return stretches, [int(k) for k in np.nonzero(~covered)[0]], rows_of
